@@ -3,6 +3,13 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: either launched by torch.distributed.run, one rank per GPU,
                                                           or from a plain shell -- bench.py then starts its N ranks itself)
+  python bench.py ... --full                             (everything below "The JSON line also carries" as well)
+  python bench.py ... --dump-outputs DIR                 (what the last timed step returned, as DIR/*.npy)
+
+A plain run sets up, runs W warm-up steps and the K timed steps, and prints the headline line (metric, value, unit, ms_per_step,
+dtype, config; the N > 1 diagnostics below).  Whatever takes runs of its own -- the per-kernel profiled passes, the roofline,
+the 1-GPU bitwise check of the sharded image, the extras, the RCCL probe child, the CPU baseline, the scaling model -- runs
+only with --full.
 
 Workload (default, every N): BASELINE.json's metric config "RDN-CiaoSR x4 on 2K LR input, tiled inference" (C3; C4 for
 N > 1): RDN-CiaoSR (c64b16) x4, ONE synthetic DIV2K-shaped LR image of 1356x2040 -> 5424x8160, `clip_test` tiling
@@ -399,7 +406,7 @@ def live_pmc_traffic(kernel_substr, unit_workload, precision, timeout_s=300):
         d = tempfile.mkdtemp(prefix='ciaosr_pmc_', dir='/tmp')
         cmd = ['rocprofv3', '--pmc', counter, '--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'p', '--',
                sys.executable, os.path.join(REPO, 'bench.py'), '--workload', unit_workload, '--precision', precision, '--steps', '1',
-               '--warmup', '1', '--no-cpu-baseline', '--no-extras', '--no-live-pmc', '--no-rccl-probe']
+               '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extras', '--no-live-pmc', '--no-rccl-probe']
         try:
             subprocess.run(cmd, cwd='/tmp', env=dict(os.environ, TMPDIR='/tmp'), timeout=timeout_s, check=True,
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -660,11 +667,40 @@ def time_steps(fn, n, dev):
     return (time.perf_counter() - t0) / n * 1e3
 
 
+DUMP_MAX_VALUES = 1 << 22        # 16 MB of float32 values (+ 32 MB of float64 indices when sampled): under 64 MB per dump
+
+
+def dump_outputs(out, path, seed=0):
+    """`--dump-outputs DIR`: the image the timed path returned in its last step, as float32 .npy files under DIR.  An image of
+    at most DUMP_MAX_VALUES values is written whole (`output.npy`); a larger one (C3: 3 x 5424 x 8160) as a fixed sample --
+    DUMP_MAX_VALUES flat indices drawn from a CPU generator seeded with `seed`, sorted (the same indices for every run of the
+    same shape): `output_sample.npy`, `output_sample_index.npy` (the flat indices, float64: exact) and `output_shape.npy`."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = out.detach().reshape(-1)
+    if flat.numel() <= DUMP_MAX_VALUES:
+        files = {'output': flat.float().cpu().numpy().reshape(tuple(out.shape))}
+    else:
+        idx = torch.randint(flat.numel(), (DUMP_MAX_VALUES,), generator=torch.Generator().manual_seed(seed)).sort().values
+        files = {'output_sample': flat[idx.to(flat.device)].float().cpu().numpy(), 'output_sample_index': idx.double().numpy(),
+                 'output_shape': np.array(out.shape, dtype=np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what takes runs of its own: a profiled warm-up step (per-kernel HIP events) and the '
+                         'dominant kernel\'s roofline, the 1-GPU bitwise check of the sharded image (N > 1), the extras, the RCCL '
+                         'probe child, the CPU baseline and the scaling model (--no-live-pmc, --no-extras, --no-rccl-probe and '
+                         '--no-cpu-baseline leave parts of it out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the image the last timed step returned as DIR/*.npy (float32; a fixed, '
+                         'seeded sample of it when it holds more than %d values)' % DUMP_MAX_VALUES)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-live-pmc', action='store_true', help='do not spawn the two rocprofv3 --pmc child passes that measure roofline.traffic')
     ap.add_argument('--no-extras', action='store_true', help='skip the extra measurements (C2, one bf16 tile, staged K4) after the timed region')
@@ -694,8 +730,10 @@ def main():
                     help='c3 (default; the config BASELINE.json\'s metric is quoted on): LR 1356x2040, 117 tiles; c3s: LR 339x510 (6 tiles); '
                          'c3tile: one 192x192 LR tile; c2: LR 48x48 (BASELINE configs[1]); c2q: C2 with its query range sharded over the ranks '
                          'after a broadcast of the encoder features.  --gpus N > 1 (C4): the tiles of the ONE image are sharded over the ranks '
-                         '(tile t -> rank t % N), strong scaling')
+                         '(tile t -> rank t %% N), strong scaling')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -838,18 +876,19 @@ def main():
                 share.update(value=float(v[0]), source=f'auto: tile {v[1]:.2f} ms, rank-0 blends + finalize + de-normalise {v[2]:.2f} ms per image')
             else:
                 share.update(value=float(args.rank0_share))
-        # correctness of the sharded path before timing it: rank 0's blended image must be bitwise equal to the
-        # single-process clip_test of the same image on this GPU (this step also sets up every peer connection of the
-        # communicator: nothing is connected lazily inside the timed region)
-        out = step()
-        if rank == 0:
-            watchdog.beat()
-            ref = model.restore(lq, options=opt)[0]
-            assert torch.equal(out, ref), f'tile-sharded output differs from 1-GPU output by {(out - ref).abs().max().item()}'
-            del ref
-        del out
+        if args.full:
+            # correctness of the sharded path before timing it: rank 0's blended image must be bitwise equal to the
+            # single-process clip_test of the same image on this GPU (this step also sets up every peer connection of the
+            # communicator; a plain run's warm-up steps do that)
+            out = step()
+            if rank == 0:
+                watchdog.beat()
+                ref = model.restore(lq, options=opt)[0]
+                assert torch.equal(out, ref), f'tile-sharded output differs from 1-GPU output by {(out - ref).abs().max().item()}'
+                del ref
+            del out
 
-    # warm-up; the last warm-up step is fully profiled (per-kernel HIP events) to find the dominant kernel.  The weights are packed
+    # warm-up; with --full the last warm-up step is fully profiled (per-kernel HIP events) to find the dominant kernel.  The weights are packed
     # first (Restorer.prepare: once per model, what the first call would do), so that the profiled step lists a steady-state step's
     # kernels and not the 6900 one-time pack_fragments launches of the Winograd weight sets
     # Per-kernel event timings need the kernels one after the other on one stream: the product default `test_cfg.encoder_ahead` (the next tile
@@ -862,16 +901,21 @@ def main():
     prepare_s = time.perf_counter() - t_prep
     ahead = not args.no_encoder_ahead
     model.test_cfg['encoder_ahead'] = ahead
-    for _ in range(max(args.warmup - 1, 0)):
-        step()
-    model.test_cfg['encoder_ahead'] = False
-    with hip_ops.profile():
-        step()
-        torch.cuda.synchronize(dev)
-    model.test_cfg['encoder_ahead'] = ahead
-    if args.warmup > 0:
-        step()                                      # the side stream's scratch and events exist before the timed region
-    prof_all = hip_ops.profile.results()
+    if args.full:
+        for _ in range(max(args.warmup - 1, 0)):
+            step()
+        model.test_cfg['encoder_ahead'] = False
+        with hip_ops.profile():
+            step()
+            torch.cuda.synchronize(dev)
+        model.test_cfg['encoder_ahead'] = ahead
+        if args.warmup > 0:
+            step()                                  # the side stream's scratch and events exist before the timed region
+        prof_all = hip_ops.profile.results()
+    else:
+        for _ in range(args.warmup):
+            step()
+        prof_all = {}                               # no profiled pass: no dominant kernel, no roofline
     dominant = max(prof_all, key=lambda k: prof_all[k]['total_ms']) if prof_all else None
     step_ms_est = sum(v['total_ms'] for v in prof_all.values()) or 1.0
 
@@ -881,21 +925,29 @@ def main():
     lib = _lib.load()
     two_streams = world == 1 and ahead and n_tiles_img > model.tile_batch(opt)     # the timed region overlaps two streams: no live event timing
     live = bool(dominant) and prof_all[dominant]['launches'] * 0.004 < 0.003 * step_ms_est and not two_streams
-    lib.ciaosr_prof_filter(dominant.encode() if dominant else None)
-    lib.ciaosr_prof_reset()
-    lib.ciaosr_prof_enable(1 if live else 0)
+    if args.full:
+        lib.ciaosr_prof_filter(dominant.encode() if dominant else None)
+        lib.ciaosr_prof_reset()
+        lib.ciaosr_prof_enable(1 if live else 0)
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        if i + 1 < args.steps:
+            step()
+        else:
+            last = step()                           # only the last step's image is kept (--dump-outputs)
     sync()
     elapsed = time.perf_counter() - t0
-    lib.ciaosr_prof_enable(0)
+    if args.full:
+        lib.ciaosr_prof_enable(0)
+    if args.dump_outputs and last is not None:      # rank 0's image (the other ranks' steps return None)
+        dump_outputs(last, args.dump_outputs)
+    del last
     prof_steps = args.steps
     # the separate pass contains collectives when world > 1: every rank must take it if ANY rank needs it (ranks can
     # disagree on the dominant kernel, e.g. the query-sharded mode runs the encoder on rank 0 only)
     need_pass = int(bool(dominant) and not live)
-    if world > 1:
+    if world > 1 and args.full:
         flag = torch.tensor([need_pass], device=dev if backend == 'nccl' else 'cpu', dtype=torch.int32)
         dist.all_reduce(flag, op=dist.ReduceOp.MAX)
         need_pass = int(flag.item())
@@ -910,8 +962,10 @@ def main():
         sync()
         lib.ciaosr_prof_enable(0)
         model.test_cfg['encoder_ahead'] = ahead
-    prof_dom = hip_ops.profile.results()
-    lib.ciaosr_prof_filter(None)
+    prof_dom = {}
+    if args.full:
+        prof_dom = hip_ops.profile.results()
+        lib.ciaosr_prof_filter(None)
 
     rank_ms = None
     if world > 1:
@@ -1016,12 +1070,12 @@ def main():
                                                  'rank 0 under compute, rank-0 blend in the reference order')),
                        'lr': [lr_h, lr_w], 'scale': scale, 'tiles': n_tiles_img, 'queries_per_step': out_pixels,
                        'parallelism': (f'query-shard x{world}' if args.workload == 'c2q' else f'tile-shard x{world}')},
-            'roofline': roof,
             'prepare_s': round(prepare_s, 3),        # model.prepare(): one-time weight packing (not in the timed region)
             'encoder_ahead': bool(two_streams),
-            'kernels_ms_per_step': {k: round(v['total_ms'], 4) for k, v in sorted(
-                prof_all.items(), key=lambda kv: -kv[1]['total_ms'])},
         }
+        if args.full:
+            line['roofline'] = roof
+            line['kernels_ms_per_step'] = {k: round(v['total_ms'], 4) for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1]['total_ms'])}
         if world > 1:
             from ciaosr_amd.tile_shard import partition
             line['rank_ms_per_step'] = rank_ms
@@ -1035,7 +1089,7 @@ def main():
                     # round's receives, the remaining blends, tile_finalize and denorm_clamp -- the part of the exchange that does
                     # NOT hide under compute (last timed step)
                     line['exposed_tail_ms'] = round(tail['last_own_tile'].elapsed_time(tail['ready']), 3)
-        if world == 1 and not args.no_extras and roof is not None:
+        if args.full and world == 1 and not args.no_extras and roof is not None:
             extras = {}
             # (1) the HBM-bound kernels of the staged routes (north star: >= 40 % of the HBM roofline on the local-attention kernel K4;
             # K1 gather-rows and K4 are the HBM-bound stages) on ONE tile of this workload right after the timed region
@@ -1116,18 +1170,18 @@ def main():
                     extras[f'c3s_6tiles_fp32_ms_tile_streams_{ns}'] = round(time_steps(lambda: model.restore(c3s), 2, dev), 2)
                 model.test_cfg['tile_streams'] = 1
             line['extras'] = extras
-        if world == 1 and not args.no_rccl_probe:
+        if args.full and world == 1 and not args.no_rccl_probe:
             # N = 1: `rccl_ranks` as a communicator counts them -- a fresh child creates a 1-rank RCCL group on this GPU and hands a tile to
             # itself through the exchange code (tile_shard.rccl_self_probe); None when RCCL could not be brought up
             probe = rccl_probe()
             line['rccl_probe'] = probe
             line['rccl_ranks'] = probe.get('ranks') if probe.get('ok') else None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload in ('c2', 'c2q'):
                 line['cpu_baseline'] = cpu_baseline_c2(scale)
             else:
                 line['cpu_baseline'] = cpu_baseline_c3(n_tiles_img, out_pixels, scale)
-        if world == 1 and args.workload == 'c3' and args.head_route == 'fused':
+        if args.full and world == 1 and args.workload == 'c3' and args.head_route == 'fused':
             line['scale_model'] = scale_model(model, ms, n_tiles_img, lr_h * scale, lr_w * scale, dev)
         if 'extras' in line and 'c3_f16_mode_mpix_s' in line['extras']:
             # the opt-in modes of the same workload at a glance (whole C3 image, one timed step each; PSNR-gated, see README): flat, up front

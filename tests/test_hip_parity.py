@@ -1994,7 +1994,7 @@ def test_swinir_trunk_hip_vs_torch(dev, hw):
 
 
 def test_bench_line_contract(dev):
-    """`python bench.py` prints ONE JSON line with the driver's contract fields, the roofline object of the dominant kernel
+    """`python bench.py --full` prints ONE JSON line with the headline contract fields, the roofline object of the dominant kernel
     and the CPU baseline (bounded sample of one tile, extrapolated).  Run on the 6-tile C3 variant (c3s: same code path
     as the default 117-tile C3, 20x cheaper); the default workload must be C3."""
     import subprocess
@@ -2002,7 +2002,7 @@ def test_bench_line_contract(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, 'bench.py')).read()
     assert "ap.add_argument('--workload', default='c3'" in src
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'c3s', '--steps', '2', '--warmup', '1'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'c3s', '--steps', '2', '--warmup', '1', '--full'],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{')]
@@ -2030,3 +2030,31 @@ def test_bench_line_contract(dev):
         assert k in c, k
     assert c['kind'] == 'port' and c['value'] > 0 and d['value'] / c['value'] >= 50     # north star: >= 50x the CPU path
     assert 'EXTRAPOLATED' in c['sample'] and c['cs_attn_hoisted']['value'] > c['value']
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(dev, tmp_path):
+    """`python bench.py` without --full: the headline line only (no profiled pass, roofline, extras, RCCL probe, CPU baseline);
+    `--dump-outputs DIR` writes the image of the last timed step -- the image restore() computes here from the same seeded
+    weights and input."""
+    import subprocess
+    import sys
+    import bench
+    from ciaosr_amd.init_utils import seeded_init_, synthetic_pair
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'c2', '--steps', '3', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'Mpix/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['metric'].startswith('HR Mpix/s') and abs(d['value'] - 192 * 192 / 1e6 / (d['ms_per_step'] * 1e-3)) < 1e-2 * d['value']
+    for k in ('roofline', 'kernels_ms_per_step', 'extras', 'rccl_probe', 'cpu_baseline', 'scale_model'):
+        assert k not in d, k
+    assert os.listdir(tmp_path) == ['output.npy']
+    got = np.load(tmp_path / 'output.npy')
+    model = bench.rdn_ciaosr(dict(scale=4, tile=192, tile_overlap=32))
+    seeded_init_(model, seed=0, gain=1.0)
+    want = model.to(dev).restore(synthetic_pair(48, 48, 4)[0].to(dev)).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape == (1, 3, 192, 192)
+    assert np.abs(got - want).max() <= 1e-5

@@ -248,14 +248,24 @@ def test_configs_build_through_the_shim_import_paths(kind):
 
 
 def test_reference_rdn_config_loads_unmodified():
-    """The reference's own RDN config file executes unmodified against the shim packages (its EDSR and SwinIR
-    config files have an unbalanced parenthesis upstream and cannot be parsed by any loader)."""
-    ref = '/root/reference/configs/001_localimplicitsr_rdn_div2k_g1_c64b16_1000k_unfold_lec_mulwkv_res_nonlocal.py'
-    if not os.path.exists(ref):
-        pytest.skip('reference tree not present (GPU box)')
+    """The reference's own RDN config, as the loader parses the unmodified file (tests/golden/ref_rdn_config.json, made by
+    tools/make_golden.py: its settings, each class by the `mmedited.models...` path the file imports it from), resolves and builds
+    against the shim packages (its EDSR and SwinIR config files have an unbalanced parenthesis upstream and cannot be parsed by any
+    loader)."""
+    import importlib
     import ciaosr_amd
-    from ciaosr_amd.config import Config
-    cfg = Config.fromfile(ref)
+    from ciaosr_amd.config import Config, _wrap
+
+    def dec(v):
+        if isinstance(v, dict) and set(v) == {'__class__'}:
+            mod, name = v['__class__'].rsplit('.', 1)
+            return getattr(importlib.import_module(mod), name)
+        if isinstance(v, dict):
+            return {k: dec(x) for k, x in v.items()}
+        return [dec(x) for x in v] if isinstance(v, list) else v
+    with open(os.path.join(GOLDEN, 'ref_rdn_config.json')) as f:
+        cfg = Config({k: _wrap(dec(v)) for k, v in json.load(f).items()})
+    assert cfg.model.type.__module__.startswith('ciaosr_amd') and cfg.model.generator.type.__module__.startswith('ciaosr_amd')
     model = ciaosr_amd.build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     assert type(model).__name__ == 'CiaoSR' and type(model.generator).__name__ == 'LocalImplicitSRRDN'
     assert cfg.data.test.filename_tmpl == '{}' and cfg.dist_params.backend == 'nccl'
@@ -425,3 +435,29 @@ def test_round6_host_logic_options_tile_batch_and_error_feedback_rounding():
     assert prefix_ef <= 0.5 * ulp + 1e-12, (prefix_ef, ulp)
     assert prefix_rne > 4 * prefix_ef, (prefix_rne, prefix_ef)
     assert (q - w).abs().max().item() <= ulp                                 # an element moves by at most one spacing (rne: half)
+
+
+def test_bench_dump_outputs_whole_or_fixed_seeded_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: an image of at most DUMP_MAX_VALUES values is written whole; a larger one as a sample at
+    indices that depend only on the seed and the shape (two runs of the same arguments compare value for value), float32 values
+    with their exact flat indices; a sampled dump stays under 64 MB."""
+    import numpy as np
+    import bench
+    assert bench.DUMP_MAX_VALUES * (4 + 8) <= 64 << 20
+    img = torch.rand(1, 3, 20, 30, generator=torch.Generator().manual_seed(7))
+    bench.dump_outputs(img, str(tmp_path / 'whole'))
+    assert sorted(os.listdir(tmp_path / 'whole')) == ['output.npy']
+    whole = np.load(tmp_path / 'whole' / 'output.npy')
+    assert whole.dtype == np.float32 and np.array_equal(whole, img.numpy())
+    monkeypatch.setattr(bench, 'DUMP_MAX_VALUES', 500)
+    for d in ('a', 'b'):
+        bench.dump_outputs(img, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['output_sample.npy', 'output_sample_index.npy', 'output_shape.npy']
+    got = {f[:-len('.npy')]: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(np.array_equal(got[f[:-len('.npy')]], np.load(tmp_path / 'b' / f)) for f in files)
+    assert got['output_sample'].dtype == np.float32 and got['output_sample'].shape == (500,)
+    assert got['output_sample_index'].dtype == np.float64 and got['output_shape'].tolist() == [1, 3, 20, 30]
+    idx = got['output_sample_index'].astype(np.int64)
+    assert np.all(np.diff(idx) >= 0) and idx.min() >= 0 and idx.max() < img.numel()
+    assert np.array_equal(got['output_sample'], img.numpy().reshape(-1)[idx])

@@ -82,9 +82,9 @@ def test_bench_eight_ranks_c3_from_a_plain_shell(gpu):
 
 
 def test_bench_starts_its_own_ranks_from_a_plain_shell(gpu):
-    """`python bench.py --gpus 2` with no WORLD_SIZE in the environment (how the driver starts N = 1): bench.py spawns its ranks,
+    """`python bench.py --gpus 2 --full` with no WORLD_SIZE in the environment (a plain shell, as for N = 1): bench.py spawns its ranks,
     asserts the sharded image bitwise against restore() before timing, and rank 0 prints the one JSON line."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'c3s', '--steps', '2', '--warmup', '1']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'c3s', '--steps', '2', '--warmup', '1', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=_env())
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{')]

@@ -116,13 +116,17 @@ def test_csattn_c64(tag):
 
 @pytest.mark.slow
 def test_head_c64_x4():
-    fx = load_golden('head_c64_x4')
-    P = seeded_head(64, int(fx['weight_seed']))
-    feat = randn((1, 64, 48, 48), fx['feat_seed'])
+    """Full-size head (Q = 36 864) against the reference, both in float64: an fp32 run of this head moves by ~2e-4 with the sgemm
+    kernel the host CPU gets (tools/make_golden.py, gen_head_c64_f64), so only a float64 pin holds on every CPU.  The fp32
+    `head_c64_x4` fixture stays the HIP path's."""
+    fx = load_golden('head_c64_x4_f64')
+    P = {k: v.double() for k, v in seeded_head(64, int(fx['weight_seed'])).items()}
+    feat = randn((1, 64, 48, 48), fx['feat_seed']).double()
     ht, wt = [int(v) for v in fx['target']]
-    coord, cell = make_coord((ht, wt)).unsqueeze(0), make_cell((ht, wt)).unsqueeze(0)
+    coord, cell = make_coord((ht, wt)).unsqueeze(0).double(), make_cell((ht, wt)).unsqueeze(0).double()
     out = orc.batched_predict(feat, coord, cell, P, eval_bsize=30000, hoist_nonlocal=True)
-    assert (out[0] - _t(fx['out'])).abs().max() < 5e-5
+    assert out.dtype == torch.float64 and fx['out'].dtype == np.float64
+    assert (out[0] - _t(fx['out'])).abs().max() < 1e-9
 
 
 def test_head_c64_x3p3_sampled_queries():

@@ -42,10 +42,10 @@ def test_one_rank_rccl_group_handoff_and_loopback_tiles_are_bitwise():
 
 
 def test_bench_n1_line_counts_its_ranks_over_rccl():
-    """`python bench.py` at N = 1 reports `rccl_ranks` as counted by a communicator (probe child), not as a constant."""
+    """`python bench.py --full` at N = 1 reports `rccl_ranks` as counted by a communicator (probe child), not as a constant."""
     if not torch.cuda.is_available():
         pytest.skip('needs the MI355X')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'c2', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'c2', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
            '--no-extras', '--no-live-pmc']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=_child_env())
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])

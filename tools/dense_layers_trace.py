@@ -1,5 +1,5 @@
 """Developer tool: per-layer launch durations of the 16-bit dense kernel from a rocprofv3 kernel trace of a C3 step (layer = launch index mod 8).
-   rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --workload c3 --precision f16 --steps 1 --warmup 1 --no-...
+   rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --workload c3 --precision f16 --steps 1 --warmup 1 --no-...
    python tools/dense_layers_trace.py DIR/t_kernel_trace.csv"""
 import collections
 import csv

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from ciaosr_amd import _lib  # noqa: E402
 
-sys.argv = ['bench.py'] + (sys.argv[1:] or ['--workload', 'c3']) + ['--precision', 'f16', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-live-pmc', '--no-extras', '--no-rccl-probe']
+sys.argv = ['bench.py'] + (sys.argv[1:] or ['--workload', 'c3']) + ['--precision', 'f16', '--steps', '1', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-live-pmc', '--no-extras', '--no-rccl-probe']
 with contextlib.redirect_stdout(io.StringIO()):
     bench.main()
 lib = _lib.load()

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--workload c3tile --steps 2 --warmup 1 --no-live-pmc --no-cpu-baseline --no-extras --no-rccl-probe"
+COMMON="--full --workload c3tile --steps 2 --warmup 1 --no-live-pmc --no-cpu-baseline --no-extras --no-rccl-probe"
 for ROUTE in as-written staged as-written-bf16 as-written-f16; do
   D=$O/staged_$ROUTE
   rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -o s -- python3 $R/bench.py $COMMON --head-route $ROUTE > $D.bench.json 2> $D.stats.err

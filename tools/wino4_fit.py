@@ -1,7 +1,7 @@
 """Developer tool: per-launch durations of the F(4x4) dense-layer kernel from a rocprofv3 kernel trace, fitted as a + b * groups
 (one 192x192 tile = 72 workgroups = one per CU: the fit reads workgroup time directly).
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/w4 -o w4 -- python3 $R/bench.py --workload c3tile --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-live-pmc
-    python tools/wino4_fit.py /tmp/w4"""
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o w4 -- python3 bench.py --full --workload c3tile --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-live-pmc
+    python tools/wino4_fit.py DIR"""
 import csv, glob, sys
 import numpy as np
 rows = []
