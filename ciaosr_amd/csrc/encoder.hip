@@ -81,12 +81,13 @@ extern "C" size_t ciaosr_rdn_workspace_bytes(int H, int W, const ciaosr_rdn_weig
 // once per batch instead of once per image) and the row-wise 1x1 kernels of the f16 route; the few 3x3 convolutions outside the
 // blocks run per image.  Each image is computed by exactly the workgroups, in exactly the order, of a single-image call: bitwise equal.
 static int rdn_forward(const float* x_nchw, int B, int H, int W, const ciaosr_rdn_weights_t* w, float* feat_hwc,
-                       const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream_, Prec prec) {
-    // f16_pairs = 2 ("f16x3", the fp32-tolerance fast mode): the trunk runs its fp32 route -- half ACTIVATIONS in 128 dense layers
-    // alone cost rms 4.6e-5 / max 4e-4 on the full C3 tile, and activation pairs (three MFMAs per product + a second patch) would
-    // cost the dense layers about what the fp32 Winograd form does
-    if ((prec == kF16 || prec == kBF16) && opt && opt->f16_pairs == 2) prec = kF32;      // "f16x3" and (round 6) "bf16x3"
-    const bool bf16 = prec != kF32;      // a 16-bit MFMA mode (bf16 or f16 entry)
+                       const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream_, Prec entry) {
+    // "f16x3" / "bf16x3" run the fp32 trunk (Mode::trunk): half ACTIVATIONS in 128 dense layers alone cost rms 4.6e-5 / max 4e-4 on the
+    // full C3 tile, and activation pairs (three MFMAs per product + a second patch) would cost the dense layers about what the fp32
+    // Winograd form does
+    const Mode m = resolve_mode(entry, opt);
+    const Prec prec = m.trunk;
+    const bool bf16 = prec != kF32;      // a 16-bit MFMA trunk (bf16 or f16)
     // route thresholds (per-call options; defaults: halo-resident dense layers from 128 tiles of 12x12 pixels on, small-map
     // kernels up to 18432 pixels = 128 such tiles)
     const int min_tiles = opt && opt->dense_min_tiles ? opt->dense_min_tiles : 128;
@@ -113,7 +114,7 @@ static int rdn_forward(const float* x_nchw, int B, int H, int W, const ciaosr_rd
         for (int i = 0; i < B; i += (int)bmax) {
             const int nb = B - i < (int)bmax ? B - i : (int)bmax;
             const int rc = rdn_forward(x_nchw + (size_t)i * 3 * HW, nb, H, W, w, feat_hwc + (size_t)i * HW * C, opt, workspace, workspace_bytes,
-                                       stream_, prec);
+                                       stream_, entry);
             if (rc != CIAOSR_OK) return rc;
         }
         return CIAOSR_OK;
@@ -148,14 +149,13 @@ static int rdn_forward(const float* x_nchw, int B, int H, int W, const ciaosr_rd
     for (int i = 0; i < NB * NL && wino4; ++i) wino4 = w->dense[i].frag_wino4 != nullptr;
     // f16 mode: the local feature fusion (1x1 over the block's 576 channels) too reads the 16-bit copy of the block buffer, on the
     // 16-bit GEMM with bias + residual in its epilogue; the dense layers then need no fp32 copy of their outputs, and the epilogue
-    // writes the next block's 16-bit input group.  (bf16 mode keeps the fp32 lff: its weights would need the hi + lo pair.)
-    const bool pairs16 = prec == kF16 && opt && opt->f16_pairs;       // half weight pairs: the lff keeps its fp32 weights, like the bf16 mode
-    const bool lff16 = dense16 && prec == kF16 && !pairs16 && cb % 8 == 0 && G % 4 == 0 && G <= 128;
+    // writes the next block's 16-bit input group.  (The bf16 and weight-pair modes keep the fp32 lff: its weights would need the hi + lo pair.)
+    const bool lff16 = dense16 && m.lff16 && cb % 8 == 0 && G % 4 == 0 && G <= 128;
     int rc;
 #define RUN(x) do { rc = (x); if (rc != CIAOSR_OK) return rc; } while (0)
     if (B > 1 && !(dense16 || dense32)) {       // small maps: one image after the other through the single-image routes
         for (int i = 0; i < B; ++i)
-            RUN(rdn_forward(x_nchw + (size_t)i * 3 * HW, 1, H, W, w, feat_hwc + (size_t)i * HW * C, opt, workspace, workspace_bytes, stream_, prec));
+            RUN(rdn_forward(x_nchw + (size_t)i * 3 * HW, 1, H, W, w, feat_hwc + (size_t)i * HW * C, opt, workspace, workspace_bytes, stream_, entry));
         return CIAOSR_OK;
     }
     if (lff16) {
@@ -183,7 +183,7 @@ static int rdn_forward(const float* x_nchw, int B, int H, int W, const ciaosr_rd
                 const ciaosr_conv_t& c = w->dense[b * NL + l];
                 CIAOSR_CHECK_ARG(conv_ok(c, C + G * l, G, 3));
                 RUN(h16_ops(prec).dense_layer(lff16 ? nullptr : x, cb, Xb, cb, H, W, l, c.frag16,
-                                              (prec == kF16 ? !pairs16 : (opt && opt->bf16_single)) ? nullptr : c.frag16_lo, c.bias, B, s,
+                                              m.trunk_pairs ? c.frag16_lo : nullptr, c.bias, B, s,
                                               dd == 1 ? 1 : 0));
             }
             if (lff16) {

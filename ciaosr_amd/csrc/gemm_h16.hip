@@ -549,7 +549,11 @@ int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int l
     ProfScope prof(tag ? tag : "gemm" CIAOSR_H16_SUFFIX, s);
     // big plain GEMMs (the operand stream from L2 bounds the narrow tile): 192 x 256 tiles, eight waves, where they fill the chip
     const long wide_tiles = (long)ceil_div(M, 192) * ceil_div(N, WN);
-    static const bool narrow_only = getenv("CIAOSR_GEMM16_NARROW") != nullptr;          // developer A/B switch
+#ifdef CIAOSR_PROBE       // developer A/B only: the product library reads no environment
+    static const bool narrow_only = getenv("CIAOSR_GEMM16_NARROW") != nullptr;
+#else
+    constexpr bool narrow_only = false;
+#endif
     // (deep K only: at K = 576 -- the logit table's slices -- one workgroup per CU hides its 18 k-tiles' prologue worse than two: 45 vs 39 us)
     if (N % WN == 0 && K >= 2048 && wide_tiles >= 256 && !narrow_only) {
         p.tiles_n = N / WN;
@@ -802,7 +806,11 @@ int conv1x1_h16(const unsigned short* A, int lda, const unsigned short* W16, int
         q.M = M; q.K = K; q.nks = K >> 4; q.wpitch = K * 2 + 16;
         const size_t lds = (size_t)SK_N * q.wpitch;
         ProfScope prof(tag, s);
-        static const bool quarter_lines = getenv("CIAOSR_CONV1X1_QUARTER_LINES") != nullptr;       // developer A/B switch: the round-3 kernel
+#ifdef CIAOSR_PROBE       // developer A/B only: the round-3 kernel
+        static const bool quarter_lines = getenv("CIAOSR_CONV1X1_QUARTER_LINES") != nullptr;
+#else
+        constexpr bool quarter_lines = false;
+#endif
         if ((K & 63) == 0 && !quarter_lines) {
             const size_t lds8 = lds + 8 * 8192;
             CIAOSR_BIG_LDS(conv1x1_lines_h16_kernel, lds8);

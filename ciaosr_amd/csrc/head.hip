@@ -128,13 +128,10 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
                         const ciaosr_csattn_weights_t* csattn, const float* x_lr_nchw, const float* coord,
                         const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt, void* workspace,
                         size_t workspace_bytes, void* stream_, Prec prec) {
+    const Mode m = resolve_mode(prec, opt);
     const bool bf16 = prec != kF32;                  // a 16-bit MFMA mode (bf16 or f16 entry)
     const int route = opt ? opt->head_route : 0;
-    // hi + lo weight pairs: the bf16 entry unless single is asked for, the f16 entry when pairs are asked for
-    const bool lo = (prec == kBF16 && (!(opt && opt->bf16_single) || (opt && opt->f16_pairs == 2))) || (prec == kF16 && opt && opt->f16_pairs);
-    // f16_pairs = 2 / 3 ("f16x3" / "f16x3-fast"): the activations of the three MLP chains as half pairs too (head_fused_wide.hip), every table in fp32
-    // (round 6: the _bf16 entry takes f16_pairs = 2 too -- "bf16x3": bf16 hi + lo weights AND activations; bf16_single is ignored then)
-    const bool x3 = (prec == kF16 && opt && opt->f16_pairs >= 2) || (prec == kBF16 && opt && opt->f16_pairs == 2);
+    const bool lo = m.lo, x3 = m.x3;                 // x3: the activations of the three MLP chains as pairs too, every table in fp32
     // f16x3 runs the wide-workgroup kernels (head_fused_wide.hip: its two activation arrays leave room for one workgroup per CU);
     // f16 / f16-pairs keep the 128-row kernels with two workgroups per CU (head_fused_h16.hip) and take the wide form -- 256 rows, half
     // the weight stream per MFMA, measured equal in time: one workgroup per CU exposes its gather phases -- only with head_route bit 3
@@ -206,7 +203,7 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
     // exact layer-1 hoist: T = U . W1[:, :fan]^T + b1, one row per LR pixel
     // f16 mode: on the 16-bit GEMM from a half copy of U (the staged route's activation buffers are free on the fused route)
     const size_t u16_bytes = (size_t)p.HW * p.Dv * 2 + 256, w16_bytes = (size_t)(p.wk0 + p.wv0) * p.Dv * 2 + 512;
-    if (prec == kF16 && !lo && (p.D & 7) == 0 && (p.Dv & 7) == 0 && u16_bytes + w16_bytes <= R * p.wmax * sizeof(float) &&
+    if (m.hoist16 && (p.D & 7) == 0 && (p.Dv & 7) == 0 && u16_bytes + w16_bytes <= R * p.wmax * sizeof(float) &&
         (size_t)p.HW * p.Dv * 2 < 0xFFFFFF00ull) {
         const H16Ops& h = h16_ops(prec);
         unsigned short* U16 = reinterpret_cast<unsigned short*>(bufA);
@@ -237,11 +234,11 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
         const long total = (long)p.HW * 9;
         // 16-bit modes: the table GEMM on the 16-bit MFMA (fp32 table out).  (Half-pairs mode: the exact-fp32 GEMM here was measured
         // and changes nothing -- max |delta| 1.04e-3 -> 1.14e-3 on the full-tile vector, +0.9 ms: W5's rounding is not what limits it.)
-        const bool table16 = bf16 && !x3 && (p.D & 7) == 0;
+        const bool table16 = m.table16 && (p.D & 7) == 0;
         if (table16) RUN(transpose_cast_h16(w->k.weight[last], w->k.ld[last], p.D, 256, W5T, prec == kF16, s));
         // fp32, C = 64: nine Winograd convolutions of the product maps Pi_o = F . shift_o(F) (same sums as the GEMM rows below,
         // re-associated through the transform; 2.25x fewer multiplies).  The maps live where the GEMM would keep its row chunk.
-        const bool table_wino = (prec == kF32 || x3) && w->k_out_wino && !(route & CIAOSR_HEAD_TABLE_GEMM) && p.C == 64 && !w->no_unfold &&
+        const bool table_wino = !m.table16 && w->k_out_wino && !(route & CIAOSR_HEAD_TABLE_GEMM) && p.C == 64 && !w->no_unfold &&
                                 p.HW >= 512 && p.HW <= kQkChunk;
         if (table_wino) {
             RUN(qk_maps(feat_hwc, p.C, p.C, H, W, QK, s));

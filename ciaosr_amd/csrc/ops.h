@@ -217,6 +217,31 @@ namespace f16 { CIAOSR_H16_DECLS }
 
 // precision of an entry point: the suffix of its name
 enum Prec { kF32 = 0, kBF16 = 1, kF16 = 2 };
+
+// What a call runs: (entry point, opt->f16_pairs, opt->bf16_single) decoded once, as the table of precision modes in
+// include/ciaosr_hip.h reads them (ignored combinations included).  Nothing else reads those two fields but options_ok().
+struct Mode {
+    Prec trunk;        // element type of the RDN trunk: kF32 for "f16x3" / "bf16x3"
+    bool trunk_pairs;  // 16-bit trunk: dense-layer weights as hi + lo pairs (ciaosr_conv_t.frag16_lo)
+    bool lff16;        // 16-bit trunk: the local feature fusion may run on the 16-bit GEMM (single half weights only)
+    bool lo;           // 16-bit head: weights as hi + lo pairs (frag16_lo, chain16_pairs)
+    bool x3;           // 16-bit head: activations as pairs too, three MFMAs per product (the wide kernels)
+    bool hoist16;      // head: the layer-0 tables on the 16-bit GEMM (single half weights only)
+    bool table16;      // head: the logit table on the 16-bit GEMM; else it runs fp32
+};
+inline Mode resolve_mode(Prec entry, const ciaosr_options_t* opt) {
+    const int pairs = entry == kF32 || !opt ? 0 : opt->f16_pairs;
+    const bool single = entry == kBF16 && opt && opt->bf16_single;
+    Mode m;
+    m.x3 = pairs == 2 || (entry == kF16 && pairs == 3);
+    m.lo = (entry == kBF16 && (!single || m.x3)) || (entry == kF16 && pairs != 0);
+    m.trunk = pairs == 2 ? kF32 : entry;
+    m.trunk_pairs = m.trunk != kF32 && m.lo;
+    m.lff16 = m.trunk == kF16 && !m.trunk_pairs;
+    m.hoist16 = entry == kF16 && !m.lo;
+    m.table16 = entry != kF32 && !m.x3;
+    return m;
+}
 struct H16Ops {
     decltype(&b16::gemm_h16_nt) gemm_nt;
     decltype(&b16::cast_rows_h16) cast_rows;

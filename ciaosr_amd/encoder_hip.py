@@ -98,8 +98,9 @@ class PackedEncoder:
         return [p for m in mods for p in m.parameters()]
 
     def struct(self, half=None):
-        """The trunk's weight struct.  half='bf16' | 'f16' (RDN): the copy whose dense layers carry the 16-bit hi + lo fragment pairs of that
-        element type, packed when the mode is first used (one launch pair per layer); None: the fp32 forms only."""
+        """The trunk's weight struct for trunk element type `half` (hip_ops.Mode.trunk).  'bf16' | 'f16' (RDN): the copy whose dense layers
+        carry the 16-bit hi + lo fragment pairs of that element type, packed when the mode is first used (one launch pair per layer);
+        None: the fp32 forms only (the fp32 trunk of every mode that runs one)."""
         key = tuple((p.data_ptr(), p._version) for p in self._params())
         if self._st is None or key != self._key:
             self._build(key)
@@ -119,7 +120,7 @@ class PackedEncoder:
                 c = dense[i]
                 n_, k_ = c.cout, c.ksize * c.ksize * c.cin
                 f = torch.empty(getattr(lib, f'ciaosr_fragment_{half}_bytes')(n_, k_), dtype=torch.uint8, device=self._keep[0].device)
-                lo = torch.empty_like(f)                     # h16(w - h16(w)): the lo half of the weight pair (bf16 default, Options(f16_pairs=1))
+                lo = torch.empty_like(f)                     # h16(w - h16(w)): the lo half of the weight pair (read by the weight-pair modes)
                 _lib.call(f'ciaosr_pack_fragments_{half}_pair', c.weight, k_, n_, k_, hip_ops.ptr(f), hip_ops.ptr(lo), hip_ops.stream_ptr())
                 keep += [f, lo]
                 c.frag16 = f.data_ptr()
@@ -234,7 +235,7 @@ class PackedEncoder:
         x_bchw = x_bchw.contiguous().float()
         hip_ops.require_gpu(x_bchw)
         _, _, H, W = x_bchw.shape
-        st = self.struct(opt.half)
+        st = self.struct(opt.mode.trunk)
         nbytes = _lib.load().ciaosr_rdn_workspace_bytes_batch(B, H, W, C.byref(st))
         ws = hip_ops.workspace(nbytes, x_bchw.device, slot='encoder')
         out = torch.empty(B, H, W, st.mid_channels, dtype=torch.float32, device=x_bchw.device)
@@ -249,7 +250,7 @@ class PackedEncoder:
         x_chw = x_chw.contiguous().float()
         hip_ops.require_gpu(x_chw)
         _, H, W = x_chw.shape
-        st = self.struct(opt.half)
+        st = self.struct(opt.mode.trunk)
         lib = _lib.load()
         if self.kind == 'rdn':
             nbytes = lib.ciaosr_rdn_workspace_bytes(H, W, C.byref(st))

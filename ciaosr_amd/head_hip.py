@@ -28,12 +28,23 @@ class PackedHead:
         self._key = None
         self._st = None
         self._keep = None
-        self._st_half = {}        # per 16-bit element type: (copy of the struct with that type's fragment pairs + chain stream, kept tensors)
+        self._st_half = {}        # per 16-bit weight form: (_form_key, copy of the struct with that form's fragments + chain stream, kept tensors)
         self._grid_opts = {}      # (Options, grid width) -> Options carrying the traversal hint
 
     def _version_key(self):
         mods = [self.net.imnet_q, self.net.imnet_k, self.net.imnet_v]
         return tuple((p.data_ptr(), p._version) for m in mods for p in m.parameters())
+
+    def _form_key(self, form):
+        """What a 16-bit weight form reads beyond the MLPs (whose change rebuilds every form): for 'bf16-single', whose pack-time
+        calibration runs the trunk and cs_attn, the version keys of their own packs.  Those are refreshed whenever the trunk and cs_attn
+        run, so a call sees a change of their weights by the time it reaches the head; reading them is free, where the ~300 parameters
+        of an RDN trunk would cost about a millisecond of host time per tile."""
+        if form != 'bf16-single':
+            return ()
+        net = self.net
+        cs = net.cs_attn._packed if net.non_local_attn else None
+        return (getattr(getattr(net, '_encoder_hip', None), '_key', None), cs[0] if cs is not None else None)
 
     def _pack_mlp(self, mlp, col_perm=None, row_perm=None, frag_layers=()):
         st = _lib.MlpT()
@@ -78,39 +89,42 @@ class PackedHead:
         st.in_dim = lin[0].weight.shape[1]
         return st, keep, srcs
 
-    def struct(self, half=None, single=False):
-        """The ciaosr_head_weights_t of the net.  half=None: fp32 fragments only (the _f32 entry).  half='bf16' | 'f16': the copy that also
-        carries the 16-bit hi + lo fragment pairs of that element type and the weight stream of the chained kv kernel -- packed when the
-        mode is first used.  single=True (half='bf16' only; `Options('bf16', bf16_single=1)` = 'bf16-single'): the copy for ONE bf16 weight
-        per product, packed so that it meets the PSNR gate -- see `_build_single`."""
+    def struct(self, form=None):
+        """The ciaosr_head_weights_t of the net in weight form `form` (hip_ops.Mode.head).  None: fp32 fragments only (the _f32 entry).
+        'bf16' | 'f16': the copy that also carries the 16-bit hi + lo fragment pairs of that element type and the weight stream of the
+        chained kv kernel.  'bf16-single': the copy for ONE bf16 weight per product, packed so that it meets the PSNR gate -- see
+        `_build_single`.  The 16-bit forms are packed when first used, and again when a parameter their pack reads has changed."""
         key = self._version_key()
         if self._st is None or self._key != key:
             self._build()
             self._st_half = {}
-        if half not in ('bf16', 'f16'):
+        if form is None:
             return self._st
-        if single and half == 'bf16':
-            if 'bf16-single' not in self._st_half:
-                self._st_half['bf16-single'] = self._build_single()
-            return self._st_half['bf16-single'][0]
-        if half not in self._st_half:
-            st = _lib.HeadWeightsT()
-            C.memmove(C.byref(st), C.byref(self._st), C.sizeof(st))
-            keep = []
-            lib = _lib.load()
-            for name in ('k', 'v', 'q'):
-                m = getattr(st, name)
-                for i, w in self._srcs[name]:
-                    n, k = w.shape
-                    f = torch.empty(getattr(lib, f'ciaosr_fragment_{half}_bytes')(n, k), dtype=torch.uint8, device=w.device)
-                    lo = torch.empty_like(f)                 # h16(w - h16(w)): the lo half of the weight pair
-                    _lib.call(f'ciaosr_pack_fragments_{half}_pair', hip_ops.ptr(w), w.stride(0), n, k, hip_ops.ptr(f), hip_ops.ptr(lo), hip_ops.stream_ptr())
-                    keep += [f, lo]
-                    m.frag16[i] = f.data_ptr()
-                    m.frag16_lo[i] = lo.data_ptr()
-            keep += self._pack_chain(st, half)
-            self._st_half[half] = (st, keep)
-        return self._st_half[half][0]
+        hit = self._st_half.get(form)
+        if hit is None or hit[0] != self._form_key(form):
+            built = self._build_single() if form == 'bf16-single' else self._build_pairs(form)
+            hit = self._st_half[form] = (self._form_key(form),) + built       # keyed after the build: the calibration packs the trunk
+        return hit[1]
+
+    def _build_pairs(self, half):
+        """(struct, kept tensors) of the 'bf16' / 'f16' weight form: hi + lo fragment pairs of every layer the fused kernels take from
+        16-bit fragments, and the chained kernel's weight stream."""
+        st = _lib.HeadWeightsT()
+        C.memmove(C.byref(st), C.byref(self._st), C.sizeof(st))
+        keep = []
+        lib = _lib.load()
+        for name in ('k', 'v', 'q'):
+            m = getattr(st, name)
+            for i, w in self._srcs[name]:
+                n, k = w.shape
+                f = torch.empty(getattr(lib, f'ciaosr_fragment_{half}_bytes')(n, k), dtype=torch.uint8, device=w.device)
+                lo = torch.empty_like(f)                 # h16(w - h16(w)): the lo half of the weight pair
+                _lib.call(f'ciaosr_pack_fragments_{half}_pair', hip_ops.ptr(w), w.stride(0), n, k, hip_ops.ptr(f), hip_ops.ptr(lo), hip_ops.stream_ptr())
+                keep += [f, lo]
+                m.frag16[i] = f.data_ptr()
+                m.frag16_lo[i] = lo.data_ptr()
+        keep += self._pack_chain(st, half)
+        return st, keep
 
     # ---- one bf16 weight per product that meets the gate (round 6) ---------------------------------------------------------------------
     # Round-to-nearest single-bf16 weights fail the 0.01 dB gate on the full C3 tile (0.042 dB) although the rms error is small: the weight
@@ -122,7 +136,7 @@ class PackedHead:
     #     dW -- the row sum in particular -- stays within half an ulp (the response to the all-ones component of the activations vanishes);
     #   * calibrated bias correction b' = b + dW E[x]: the mean input vector E[x] of every rounded layer is measured ONCE per model, at
     #     pack time, on a fixed synthetic 48x48 image through the fp32 trunk and the fp32 staged head (input-independent, deterministic).
-    # The kernels are the bf16_single ones; nothing changes at run time.
+    # The kernels are those of the single form; nothing changes at run time.
     @staticmethod
     def _ef_round_bf16(w):
         """Error-feedback round-to-bf16 of every row of w [N, K] (fp32, any device) along K; returns fp32 values that ARE bf16 numbers."""
@@ -301,7 +315,8 @@ class PackedHead:
         hip_ops.require_gpu(feature_hwc if feature_hwc is not None else feature_chw, x_lr_chw, coord, cell)
         Cc, H, W = feature_chw.shape
         Q = coord.shape[0]
-        st = self.struct(opt.half, single=bool(opt.bf16_single))
+        cs = net.cs_attn.packed()[0] if net.non_local_attn else None       # first: the 'bf16-single' form is keyed on its pack
+        st = self.struct(opt.mode.head)
         gw = hip_ops.grid_width_of(coord) if (opt.half and not opt.query_grid_w) else 0
         if gw:                        # traversal hint of the 16-bit chained head kernel: the queries are a make_coord grid
             key = (opt, gw)
@@ -311,9 +326,6 @@ class PackedHead:
                     self._grid_opts.clear()
                 hinted = self._grid_opts[key] = opt.replace(query_grid_w=gw)
             opt = hinted
-        cs = None
-        if net.non_local_attn:
-            cs, _ = net.cs_attn.packed()
         feat_hwc = feature_hwc if feature_hwc is not None else hip_ops.nchw_to_hwc(feature_chw)
         nbytes = _lib.load().ciaosr_head_workspace_bytes(H, W, C.byref(st), Q)
         ws = hip_ops.workspace(nbytes, coord.device)

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: device pointers from `tensor.data_ptr()`, the stream
 from `torch.cuda.current_stream()`.  PyTorch is used for device memory and streams only."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -211,44 +212,68 @@ def tile_finalize(E, Wt):
     return out
 
 
-PRECISIONS = ('fp32', 'bf16', 'bf16-single', 'bf16x3', 'f16', 'f16-pairs', 'f16x3', 'f16x3-fast')       # what Options(precision) / test_cfg.precision accept
+class Mode(namedtuple('Mode', 'name precision f16_pairs bf16_single trunk head')):
+    """One named arithmetic mode.  (precision, f16_pairs, bf16_single): the entry suffix and the canonical ciaosr_options_t fields
+    (include/ciaosr_hip.h, "Precision modes").  trunk: element type of the RDN trunk's dense layers, None = the fp32 trunk.  head: the
+    head weight form PackedHead packs, None = fp32 only, 'bf16' / 'f16' = hi + lo fragment pairs, 'bf16-single' = one
+    error-feedback-rounded bf16 weight per product with calibrated biases."""
+    __slots__ = ()
+
+
+MODES = {m.name: m for m in (
+    Mode('fp32', 'fp32', 0, 0, None, None),          # exact-fp32 MFMA, the contract precision
+    Mode('bf16', 'bf16', 0, 0, 'bf16', 'bf16'),      # bf16 MFMA inputs, fp32 accumulation, weights as bf16 hi + lo pairs
+    Mode('bf16-single', 'bf16', 0, 1, 'bf16', 'bf16-single'),   # ONE bf16 weight per product (head_hip.py: _build_single)
+    Mode('bf16x3', 'bf16', 2, 0, None, 'bf16'),      # the head's weights AND activations as bf16 pairs (three MFMAs per product), fp32 trunk
+    Mode('f16', 'f16', 0, 0, 'f16', 'f16'),          # IEEE half MFMA inputs, one MFMA per product, saturating at 65504
+    Mode('f16-pairs', 'f16', 1, 0, 'f16', 'f16'),    # half activations, every weight as a half hi + lo pair
+    Mode('f16x3', 'f16', 2, 0, None, 'f16'),         # the fp32-tolerance fast mode: 'bf16x3' in half
+    Mode('f16x3-fast', 'f16', 3, 0, 'f16', 'f16'),   # the head of 'f16x3' on the trunk of 'f16-pairs'; PSNR-gated only
+)}
+PRECISIONS = tuple(MODES)       # what Options(precision) / test_cfg.precision accept
+_ALIASES = {'f32': 'fp32', 'bf16_single': 'bf16-single', 'bf16-x3': 'bf16x3', 'fp16': 'f16', 'half': 'f16', 'f16_pairs': 'f16-pairs',
+            'f16p': 'f16-pairs', 'f16-x3': 'f16x3'}
+
+
+def resolve_mode(precision='fp32', f16_pairs=None, bf16_single=None):
+    """The MODES row a call runs: the name (or alias) gives the defaults, explicit raw fields override them, and the result reads the
+    way the C entry points read it -- the _f32 entries ignore both fields, the _bf16 entries ignore f16_pairs 1 and 3 and
+    bf16_single under f16_pairs 2, the _f16 entries ignore bf16_single."""
+    name = _ALIASES.get(precision, precision)
+    if name not in MODES:
+        raise ValueError(f'unknown precision {precision!r}: one of {PRECISIONS} (or an alias: {sorted(_ALIASES)})')
+    m = MODES[name]
+    pairs = m.f16_pairs if f16_pairs is None else int(f16_pairs)
+    single = m.bf16_single if bf16_single is None else int(bf16_single)
+    if pairs not in (0, 1, 2, 3) or single not in (0, 1):
+        raise ValueError(f'f16_pairs must be 0..3 and bf16_single 0 or 1, got {pairs} / {single}')
+    if m.precision == 'fp32':
+        return m
+    if m.precision == 'bf16':
+        return MODES['bf16x3' if pairs == 2 else 'bf16-single' if single else 'bf16']
+    return MODES[('f16', 'f16-pairs', 'f16x3', 'f16x3-fast')[pairs]]
 
 
 class Options:
     """Per-call evaluation options, passed explicitly down the call chain (no process-global switches).
 
-    precision  'fp32' (exact-fp32 MFMA, the contract precision), 'bf16' (bf16 MFMA inputs, fp32 accumulation; weights as
-               hi + lo pairs unless bf16_single), 'f16' (IEEE half MFMA inputs, one MFMA per product, saturating at 65504)
-               'f16-pairs' (= 'f16' with f16_pairs=1: half activations, every weight as a half hi + lo pair) or 'f16x3'
-               (= 'f16' with f16_pairs=2, the fp32-tolerance fast mode: the head's weights AND activations as half pairs, three
-               MFMAs per product, fp32 trunk and tables, half cs_attn contractions), 'bf16-single' (= 'bf16' with bf16_single=1: one
-               bf16 weight per product, packed with error feedback + calibrated biases), 'bf16x3' (= 'bf16' with f16_pairs=2: the bf16
-               counterpart of 'f16x3'): selects the _f32 / _bf16 / _f16 entry point.
+    precision  a name of PRECISIONS (or an alias), optionally refined by raw f16_pairs / bf16_single: resolved to ONE row of MODES,
+               `opt.mode`; `precision`, `f16_pairs` and `bf16_single` then hold that row's canonical values ('fp32' | 'bf16' | 'f16':
+               the _f32 / _bf16 / _f16 entry point).
     the rest   fields of ciaosr_options_t (include/ciaosr_hip.h): result-equivalent route choices; 0 = default.
     Immutable; `replace()` returns a modified copy."""
     _C_FIELDS = ('head_route', 'csa_composed_min', 'dense_min_tiles', 'scatter_small_max', 'kv_rows', 'decode_rows', 'bf16_single', 'dense_direct', 'csa_scores_gemm', 'csa_attn_tile128', 'query_grid_w', 'f16_pairs')
-    __slots__ = ('precision',) + _C_FIELDS + ('_c',)
+    _MODE_FIELDS = ('precision', 'f16_pairs', 'bf16_single')
+    __slots__ = ('mode', 'precision') + _C_FIELDS + ('_c',)
 
-    def __init__(self, precision='fp32', **kw):
-        if precision in ('bf16-single', 'bf16_single'):          # ONE bf16 weight per product, error-feedback rounding + calibrated biases (head_hip.py)
-            precision = 'bf16'
-            kw.setdefault('bf16_single', 1)
-        if precision in ('bf16x3', 'bf16-x3'):                   # bf16 hi + lo weights AND activations in the head (three MFMAs per product, fp32 Z), fp32 trunk
-            precision = 'bf16'                                   # and tables, bf16 cs_attn contractions: the bf16 counterpart of 'f16x3' (round 6)
-            kw.setdefault('f16_pairs', 2)
-        if precision in ('f16-pairs', 'f16_pairs', 'f16p'):      # the fp32-tolerance fast mode: half activations, half weight PAIRS
-            precision = 'f16'
-            kw.setdefault('f16_pairs', 1)
-        if precision in ('f16x3', 'f16-x3'):                     # ... with the activations of the MLP chains as pairs too
-            precision = 'f16'
-            kw.setdefault('f16_pairs', 2)
-        if precision == 'f16x3-fast':                            # ... and the trunk back on half weight pairs (fp32 trunk = 'f16x3'); PSNR-gated
-                                                                 # only: 2.7e-2 max on trained-like trunk statistics (f16x3: 1.1e-4)
-            precision = 'f16'
-            kw.setdefault('f16_pairs', 3)
-        object.__setattr__(self, 'precision', {'fp32': 'fp32', 'f32': 'fp32', 'bf16': 'bf16', 'f16': 'f16', 'fp16': 'f16', 'half': 'f16'}[precision])
+    def __init__(self, precision='fp32', f16_pairs=None, bf16_single=None, **kw):
+        mode = resolve_mode(precision, f16_pairs, bf16_single)
+        object.__setattr__(self, 'mode', mode)
+        for f in self._MODE_FIELDS:
+            object.__setattr__(self, f, getattr(mode, f))
         for f in self._C_FIELDS:
-            object.__setattr__(self, f, int(kw.pop(f, 0)))
+            if f not in self._MODE_FIELDS:
+                object.__setattr__(self, f, int(kw.pop(f, 0)))
         if kw:
             raise TypeError(f'unknown option(s): {sorted(kw)}')
         st = None
@@ -262,7 +287,9 @@ class Options:
         raise AttributeError('Options is immutable; use replace()')
 
     def replace(self, **kw):
-        cur = {f: getattr(self, f) for f in ('precision',) + self._C_FIELDS}
+        """A copy with some fields changed; `precision` may name any mode (its f16_pairs / bf16_single unless given too)."""
+        cur = {f: getattr(self, f) for f in self._C_FIELDS if f not in self._MODE_FIELDS}
+        cur['precision'] = self.mode.name
         cur.update(kw)
         return Options(**cur)
 
@@ -285,8 +312,8 @@ class Options:
         return C.byref(self._c) if self._c is not None else None
 
     def __repr__(self):
-        extra = ''.join(f', {f}={getattr(self, f)}' for f in self._C_FIELDS if getattr(self, f))
-        return f'Options({self.precision!r}{extra})'
+        extra = ''.join(f', {f}={getattr(self, f)}' for f in self._C_FIELDS if getattr(self, f) and f not in self._MODE_FIELDS)
+        return f'Options({self.mode.name!r}{extra})'
 
 
 DEFAULT_OPTIONS = Options()

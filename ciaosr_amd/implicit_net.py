@@ -220,15 +220,15 @@ class LocalImplicitSRSWINIR(LocalImplicitSRNet):
         `test_cfg.allow_f16_substitute = True` (or the generator attribute), ran the IEEE-half kernels with a warning: that opt-in is
         still honoured.  The launch-bound SwinIR trunk is fp32 in every mode."""
         opt = hip_ops.as_options(options)
-        if opt.precision != 'bf16' or opt.f16_pairs == 2:      # 'bf16x3' asked for by name
+        if opt.mode.name not in ('bf16', 'bf16-single'):      # 'bf16x3' asked for by name, or not a bf16 mode
             return opt
         cfg = getattr(self, '_test_cfg', None)
         if not (self.allow_f16_substitute or (cfg is not None and cfg.get('allow_f16_substitute', False))):
-            return opt.replace(f16_pairs=2, bf16_single=0)     # bf16 as named: the pair form that meets the gate
+            return opt.replace(precision='bf16x3')             # bf16 as named: the pair form that meets the gate
         if not LocalImplicitSRSWINIR._warned_bf16:
             import warnings
             warnings.warn("precision='bf16' on the SwinIR-CiaoSR head does not meet the 0.01 dB PSNR gate (8-bit activations in front of "
                           "the local attention: 0.060 dB at 30 dB on BASELINE config 5); running the IEEE-half ('f16') kernels instead "
                           "(allow_f16_substitute)", RuntimeWarning, stacklevel=3)
             LocalImplicitSRSWINIR._warned_bf16 = True
-        return opt.replace(precision='f16', bf16_single=0)
+        return opt.replace(precision='f16')

@@ -151,11 +151,11 @@ class CiaoSR(BasicRestorer):
         head = getattr(gen, '_head', None)
         enc = getattr(gen, '_encoder_hip', None)
         if enc is not None and enc.supported():
-            enc.struct(opt.half)
+            enc.struct(opt.mode.trunk)
         if getattr(gen, 'non_local_attn', False):
             gen.cs_attn.packed()
         if head is not None:      # last: the 'bf16-single' form runs a pack-time calibration through the (packed) fp32 trunk and cs_attn
-            head.struct(opt.half, single=bool(opt.bf16_single))
+            head.struct(opt.mode.head)
 
     @torch.no_grad()
     def clip_test(self, img_lq, model=None, tile_fn=None, options=None):
@@ -289,8 +289,7 @@ class CiaoSR(BasicRestorer):
         v = self.test_cfg.get('tile_batch', None)
         if v is None:
             opt = self.options(options)
-            fp32_trunk = opt.precision == 'fp32' or (opt.precision == 'f16' and opt.f16_pairs == 2)       # 'f16x3' keeps the fp32 trunk
-            v = 7 if (opt.dense_direct == 0 if fp32_trunk else opt.dense_direct != 1) else 8
+            v = 7 if (opt.dense_direct == 0 if opt.mode.trunk is None else opt.dense_direct != 1) else 8
         return min(int(v or 1), 16)
 
     def options(self, options=None):

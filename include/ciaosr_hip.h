@@ -78,6 +78,34 @@ int ciaosr_prof_names(char* buf /*host*/, int buflen); /* ';'-separated kernel n
 #define CIAOSR_HEAD_NO_DECODE_CHAIN 64 /* head_route bit 6: keep imnet_q on the 128-row kernel while phi_k / phi_v run chained (imnet_q follows the
                                        * chained form where the blob carries its stream: Dv a multiple of 128, four 256-wide layers + the 3-row
                                        * output layer, which then enters the MFMA as a hi + lo pair instead of an fp32 VALU tail) */
+/* Precision modes.  The entry suffix, f16_pairs and bf16_single together name one of eight modes; "hi + lo pair" = w as h16(w) +
+ * h16(w - h16(w)), two MFMAs per product; "x3" = weights AND activations of the head's three MLP chains as pairs, three MFMAs per
+ * product (w_hi a_hi + w_lo a_hi + w_hi a_lo, head_fused_wide_h16.hip), Z in fp32.  Max |delta| against the reference on the full C3
+ * tile unless stated.
+ *
+ *   mode         entry  f16_pairs  bf16_single  trunk dense layers     head                   logit table  hoist  accuracy
+ *   fp32         _f32   0          0            fp32                   fp32                   fp32         fp32   the contract precision
+ *   bf16         _bf16  0          0            bf16, weight pairs     bf16, weight pairs     bf16         fp32   PSNR-gated
+ *   bf16-single  _bf16  0          1            bf16, single weights   bf16, single weights   bf16         fp32   PSNR-gated (0.0004 dB, below)
+ *   bf16x3       _bf16  2          0            fp32                   bf16 x3                fp32         fp32   1.8e-4; SwinIR-CiaoSR at BASELINE
+ *                                                                                                                 config 5: 9.3e-6
+ *   f16          _f16   0          0            half, single weights   half, single weights   half         half   PSNR-gated
+ *   f16-pairs    _f16   1          0            half, weight pairs     half, weight pairs     half         fp32   1.04e-3, PSNR-gated
+ *   f16x3        _f16   2          0            fp32                   half x3                fp32         fp32   2.7e-5 (rms 2.1e-6)
+ *   f16x3-fast   _f16   3          0            half, weight pairs     half x3                fp32         fp32   4.0e-4; 2.7e-2 on trained-like
+ *                                                                                                                 trunk statistics: PSNR-gated
+ *
+ * Trunk dense layers: the RDN's big-map route; its 1x1 fusion layers run in half in f16 only, fp32 elsewhere.  Activations are single
+ * 16-bit values outside the x3 heads; cs_attn's contractions run in the entry's element type; "hoist" = the layer-0 tables of the fused
+ * head.  Ignored combinations -- accepted, and resolved as listed:
+ *   _f32 entries: both fields ignored                                                   -> fp32
+ *   _bf16 entries: f16_pairs 1 or 3 ignored                                             -> bf16 / bf16-single by bf16_single
+ *                  bf16_single ignored under f16_pairs 2                                -> bf16x3
+ *   _f16 entries: bf16_single ignored                                                   -> the mode of f16_pairs
+ * Single bf16 weights rounded to nearest fail the 0.01 dB PSNR gate on smooth features (0.042 dB on the full C3 tile: a fixed,
+ * spatially coherent perturbation).  A binding that wants bf16-single INSIDE the gate packs the head's weights the way
+ * ciaosr_amd/head_hip.py::_build_single does: error-feedback rounding along K (a weight that already is a bf16 number passes through
+ * the pack entries unchanged) and bias[i] += (w - w_q) E[x] with the layer's mean input measured once on a calibration image. */
 typedef struct ciaosr_options {
     int head_route;         /* CIAOSR_HEAD_* bits; 0 = automatic */
     int csa_composed_min;   /* cs_attn: LR pixels (after padding) from which the composed fold+down tail applies;
@@ -88,14 +116,7 @@ typedef struct ciaosr_options {
                              * < 0 = never */
     int kv_rows;            /* fp32 fused head: (query, sample) rows per workgroup, 32 or 64; 0 = automatic (64 from 32768 queries) */
     int decode_rows;        /* fp32 fused decode: queries per workgroup, 32 (default) or 64 */
-    int bf16_single;        /* _bf16 entries: 0 (default) = every weight enters the MFMA as a bf16 PAIR hi + lo (hi = bf16(w),
-                             * lo = bf16(w - hi): 16 mantissa bits, two MFMAs per product); 1 = hi only (one MFMA, 8 bits).
-                             * Rounding WEIGHTS to nearest is a fixed perturbation whose response is spatially coherent and fails
-                             * the 0.01 dB PSNR gate on smooth features (0.042 dB on the full C3 tile).  A binding that
-                             * wants the single form INSIDE the gate packs the head's weights the way ciaosr_amd/head_hip.py::
-                             * _build_single does (round 6: error-feedback rounding along K -- a weight that already is a bf16
-                             * number passes through the pack entries unchanged -- and bias[i] += (w - w_q) E[x] with the layer's
-                             * mean input measured once on a calibration image): 0.0004 dB.  Activations stay single bf16 */
+    int bf16_single;        /* 0 or 1: selects a precision mode (table above) */
     int dense_direct;       /* _f32 RDN trunk, big maps: 0 (default) = dense layers in Winograd form -- F(4x4, 3x3) when ciaosr_conv_t.frag_wino4
                              * is given, else F(2x2, 3x3) when frag_wino is (fp32 arithmetic on transformed operands: not bitwise a direct
                              * convolution; the trunk stays within 2e-4 x its scale of the direct form, tests/test_hip_parity.py);
@@ -112,24 +133,7 @@ typedef struct ciaosr_options {
                              * the call are the rows of a row-major grid with W columns (q = i W + j, Q a multiple of W: what
                              * ciaosr_make_coord_cell_f32 produces); the chained kernel then walks them in 16 x 4 blocks so that a wave's rows
                              * gather from a handful of LR pixels.  Results do not depend on it; 0 = walk them in index order */
-    int f16_pairs;          /* _f16 entries: 0 (default) = one IEEE-half weight per product; 1 = every dense-layer / head weight enters
-                             * the MFMA as a half PAIR hi + lo (hi = half(w), lo = half(w - hi): ~20 mantissa bits, two MFMAs per product)
-                             * and the layers the plain f16 mode runs with single 16-bit weights elsewhere (RDB local feature fusion,
-                             * layer-0 tables) take the fp32 route of the bf16 mode (activations stay half: max |delta| 1.04e-3 on the
-                             * full C3 tile, 4 % outside the fp32 tolerance);
-                             * 2 = "f16x3", the fp32-tolerance fast mode: the ACTIVATIONS of the three MLP chains are half pairs too
-                             * (w_hi a_hi + w_lo a_hi + w_hi a_lo: three MFMAs per product, head_fused_wide.hip), Z travels in fp32, the
-                             * layer-0 and logit tables and the whole RDN trunk take their _f32 routes, cs_attn's contractions stay half
-                             * (full C3 tile: max |delta| 2.7e-5, rms 2.1e-6 against the reference);
-                             * 3 = "f16x3-fast": the head of 2 on the trunk of 1 (half weight pairs, half activations in the dense
-                             * layers): max |delta| 4.0e-4, rms 4.6e-5 on the Gaussian-weight C3 tile at 2/3 of the time -- but NOT an
-                             * fp32-tolerance mode in general: on trained-like trunk statistics (features of magnitude > 100, tests/golden/
-                             * stress_rdn_x4_*) the half activations of the dense layers leave max |delta| 2.7e-2 (rms 2.6e-4; both PSNR
-                             * gates hold, 0.0006 dB at 30 dB).  It is a PSNR-gated mode like 1; the fp32-tolerance mode is 2.
-                             * _bf16 entries (round 6): 2 = "bf16x3", the same form with bf16 hi + lo pairs (16 mantissa bits per operand;
-                             * frag16 + frag16_lo of every head layer are read, bf16_single is ignored, fp32 trunk and tables, bf16
-                             * cs_attn contractions): full C3 tile max |delta| 1.8e-4, SwinIR-CiaoSR (C = 180) at BASELINE config 5's
-                             * size 9.3e-6 -- the bf16 mode that meets the gate there (8-bit bf16 activations: 0.060 dB); 1 and 3 are ignored by the _bf16 entries */
+    int f16_pairs;          /* 0 to 3: selects a precision mode (table above) */
 } ciaosr_options_t;
 
 /* ---- layout plumbing -------------------------------------------------------------------- */
@@ -279,8 +283,7 @@ typedef struct ciaosr_head_weights {
     const float* k_out_wino4;
     /* optional (16-bit entries; hidden_list = [256] * 4 for imnet_k and imnet_v): the weight stream of the weights-stationary head kernel,
      * packed by ciaosr_pack_head_chain_bf16 / _f16 with pairs = 0 (chain16: one 16-bit weight per product) and pairs = 1 (chain16_pairs:
-     * every tile followed by its rounding residuals; read by the _bf16 entry unless opt->bf16_single, by the _f16 entry with
-     * opt->f16_pairs = 1).  ciaosr_head_chain_bytes() each (the stream of phi_k / phi_v, followed by imnet_q's where its shape allows one).
+     * every tile followed by its rounding residuals; read in the modes bf16 and f16-pairs).  ciaosr_head_chain_bytes() each (the stream of phi_k / phi_v, followed by imnet_q's where its shape allows one).
      * NULL = the kernels that read ciaosr_mlp_t.frag16 */
     const void* chain16;
     const void* chain16_pairs;

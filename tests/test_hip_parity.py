@@ -1172,6 +1172,33 @@ def test_dense_16bit_wide_tiles_vs_12x12_kernels_and_batch_invariance(dev, preci
             assert torch.equal(batch[i], want[i]), (len(seq), i, (batch[i] - want[i]).abs().max().item())
 
 
+def test_bf16_single_recalibrates_after_an_in_place_trunk_weight_change(dev):
+    """The 'bf16-single' head form carries biases calibrated through the trunk and cs_attn (head_hip.py::_build_single): a trunk weight
+    changed in place after a restore must re-run that calibration, so that the next restore is bitwise a freshly built model's with the
+    new weight."""
+    from ciaosr_amd import hip_ops
+    from ciaosr_amd.init_utils import seeded_init_, synthetic_pair
+
+    def build():
+        m = _restorer('rdn', 4, dev, dict(scale=4, tile=192, tile_overlap=32), blocks=2)
+        seeded_init_(m, seed=4, gain=1.5, head_gain=SQRT6)
+        return m.to(dev)
+
+    opt = hip_ops.Options('bf16-single')
+    lq = synthetic_pair(24, 24, 4)[0].to(dev)
+    model = build()
+    before = model.restore(lq, options=opt)
+    with torch.no_grad():
+        model.generator.sfe1.weight.mul_(1.25)
+    after = model.restore(lq, options=opt)
+    fresh = build()
+    with torch.no_grad():
+        fresh.generator.sfe1.weight.mul_(1.25)
+    want = fresh.restore(lq, options=opt)
+    assert not torch.equal(after, before)
+    assert torch.equal(after, want), (after - want).abs().max().item()
+
+
 def _f16_storage_points_report(model, lq, dev):
     """Where the IEEE-half head STORES 16-bit values (unfold rows U incl. the non-local map, the hidden activations of the three MLPs, the
     attention output z), evaluated with the fp32 staged entry points on the same input: (max magnitude, count above the half range 65 504 =

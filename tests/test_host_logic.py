@@ -405,7 +405,8 @@ def r_swin_bf16_is_x3():
 
 
 def test_round6_host_logic_options_tile_batch_and_error_feedback_rounding():
-    """Host-side pieces of round 6 that need no GPU: `Options('bf16-single')` is the bf16 entry with `bf16_single = 1`; the default
+    """Host-side pieces of round 6 that need no GPU: `Options('bf16-single')` is the bf16 entry with `bf16_single = 1`, and every mode name,
+    alias and raw-field combination resolves to one row of the mode table, as the C entry points read it; the default
     tile batch is 7 wherever the dense layers run a 16x32-pixel-tile kernel (fp32 Winograd F(4x4) and, now, the 16-bit modes) and 8 with
     `dense_direct = 1`; error-feedback rounding to bf16 (`PackedHead._ef_round_bf16`) returns bf16 numbers whose rounding error has every
     prefix sum -- the row sum in particular -- within half an ulp of the largest element, where round-to-nearest accumulates a random walk."""
@@ -417,10 +418,38 @@ def test_round6_host_logic_options_tile_batch_and_error_feedback_rounding():
     x3 = hip_ops.Options('bf16x3')
     assert x3.precision == 'bf16' and x3.f16_pairs == 2 and x3.suffix == 'bf16' and 'bf16x3' in hip_ops.PRECISIONS
     assert r_swin_bf16_is_x3()
+    # one mode table: every name and alias resolves to its row's canonical (precision, f16_pairs, bf16_single)
+    triples = {'fp32': ('fp32', 0, 0), 'bf16': ('bf16', 0, 0), 'bf16-single': ('bf16', 0, 1), 'bf16x3': ('bf16', 2, 0),
+               'f16': ('f16', 0, 0), 'f16-pairs': ('f16', 1, 0), 'f16x3': ('f16', 2, 0), 'f16x3-fast': ('f16', 3, 0)}
+    aliases = {'f32': 'fp32', 'bf16_single': 'bf16-single', 'bf16-x3': 'bf16x3', 'fp16': 'f16', 'half': 'f16', 'f16_pairs': 'f16-pairs',
+               'f16p': 'f16-pairs', 'f16-x3': 'f16x3'}
+    assert hip_ops.PRECISIONS == tuple(triples)
+    for name in list(triples) + list(aliases):
+        o = hip_ops.Options(name)
+        want = triples[aliases.get(name, name)]
+        assert o.mode.name == aliases.get(name, name) and (o.precision, o.f16_pairs, o.bf16_single) == want, name
+        assert (o.mode.precision, o.mode.f16_pairs, o.mode.bf16_single) == want and o.suffix == ('f32' if want[0] == 'fp32' else want[0])
+        assert o.replace(dense_direct=2).mode == o.mode
+    # combinations the header calls ignored resolve the way the C entry points read them
+    plain = hip_ops.Options('bf16x3')
+    x3s = hip_ops.Options('bf16x3', bf16_single=1)
+    assert x3s.mode == plain.mode and x3s.mode.head == 'bf16' and x3s.mode.trunk is None
+    assert (x3s.precision, x3s.f16_pairs, x3s.bf16_single, x3s.half, x3s.suffix) == (plain.precision, plain.f16_pairs, plain.bf16_single, plain.half, plain.suffix)
+    assert bytes(x3s._c) == bytes(plain._c)
+    assert hip_ops.Options('bf16-single', f16_pairs=2).mode.name == 'bf16x3'
+    assert hip_ops.Options('bf16', f16_pairs=1).mode.name == 'bf16' and hip_ops.Options('bf16', f16_pairs=3).mode.name == 'bf16'
+    assert hip_ops.Options('bf16', f16_pairs=1).c_arg() is None                # canonical fields: all defaults again
+    assert hip_ops.Options('f16', bf16_single=1).mode.name == 'f16' and hip_ops.Options('fp32', f16_pairs=2).mode.name == 'fp32'
+    assert hip_ops.Options('f16', f16_pairs=1).mode.name == 'f16-pairs' and hip_ops.Options('f16x3', f16_pairs=1).mode.name == 'f16-pairs'
+    assert hip_ops.Options('bf16-single').mode.head == 'bf16-single' and hip_ops.Options('f16x3-fast').mode.trunk == 'f16'
+    for bad in (dict(f16_pairs=4), dict(bf16_single=2)):
+        with pytest.raises(ValueError):
+            hip_ops.Options('bf16', **bad)
     r = _small_restorer(dict(scale=2))
     assert r.tile_batch() == 7 and r.tile_batch(hip_ops.Options('f16')) == 7 and r.tile_batch(hip_ops.Options('bf16-single')) == 7
     assert r.tile_batch(hip_ops.Options('f16', dense_direct=1)) == 8 and r.tile_batch(hip_ops.Options('fp32', dense_direct=1)) == 8
     assert r.tile_batch(hip_ops.Options('f16x3')) == 7                       # fp32 trunk
+    assert r.tile_batch(hip_ops.Options('bf16x3')) == 7 and r.tile_batch(hip_ops.Options('bf16x3', dense_direct=2)) == 8     # fp32 trunk too
     r.test_cfg['tile_batch'] = 3
     assert r.tile_batch(hip_ops.Options('f16')) == 3
     g = torch.Generator().manual_seed(7)
