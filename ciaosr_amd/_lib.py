@@ -157,6 +157,8 @@ SIGNATURES = {
     'ciaosr_denorm_clamp_f32': (_I, [_P, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
     'ciaosr_tile_blend_f32': (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, _P]),
     'ciaosr_tile_finalize_f32': (_I, [_P, _P, _P, _I, _I, _P]),
+    'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),
+    'ciaosr_resample_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _S, _P]),
 }
 
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)

@@ -13,6 +13,12 @@ def imread_rgb01(path):
     return torch.from_numpy(img).permute(2, 0, 1).contiguous()
 
 
+def imread_u8(path):
+    """-> HxWx3 uint8 RGB array: LoadImageFromFile(flag='color', channel_order='rgb') before any conversion."""
+    from PIL import Image
+    return np.array(Image.open(path).convert('RGB'), dtype=np.uint8)
+
+
 def imwrite(img_bgr_u8, path):
     """mmcv.imwrite of a tensor2img result (HxWx3 BGR uint8)."""
     from PIL import Image

@@ -36,12 +36,27 @@ if val_scale <= 4:   # tiled inference; larger tile is better
 else:                # x6, x8, x12: whole image
     test_cfg = dict(metrics=['PSNR', 'SSIM'], crop_border=val_scale, scale=val_scale, convert_to='y')
 
+# x6 and up: GT folder only, the LR input is down-sampled from the GT as it is loaded (Pillow-exact bicubic, on the GPU)
+valid_pipeline = [
+    dict(type='LoadImageFromFile', io_backend='disk', key='gt', flag='color', channel_order='rgb'),
+    dict(type='RandomDownSampling', scale_min=val_scale, scale_max=val_scale),
+    dict(type='RescaleToZeroOne', keys=['lq', 'gt']),
+    dict(type='ImageToTensor', keys=['lq', 'gt']),
+    dict(type='GenerateCoordinateAndCell', scale=val_scale),
+    dict(type='Collect', keys=['lq', 'gt', 'coord', 'cell'], meta_keys=['gt_path'])]
+
 data_dir = 'data'
-data = dict(
-    test=dict(type='SRFolderDataset',
-              lq_folder=f'{data_dir}/Classical/{data_type}/LRbicx{val_scale}',
-              gt_folder=f'{data_dir}/Classical/{data_type}/GTmod12',
-              scale=val_scale, filename_tmpl='{}'))
+if val_scale <= 4:
+    data = dict(
+        test=dict(type='SRFolderDataset',
+                  lq_folder=f'{data_dir}/Classical/{data_type}/LRbicx{val_scale}',
+                  gt_folder=f'{data_dir}/Classical/{data_type}/GTmod12',
+                  scale=val_scale, filename_tmpl='{}'))
+else:
+    data = dict(
+        test=dict(type='SRFolderGTDataset',
+                  gt_folder=f'{data_dir}/Classical/{data_type}/GTmod12',
+                  pipeline=valid_pipeline, scale=val_scale))
 
 dist_params = dict(backend='nccl')
 test_checkpoint_path = f'./work_dirs/{exp_name}/latest.pth'

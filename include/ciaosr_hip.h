@@ -518,6 +518,21 @@ int ciaosr_tile_blend_f32(float* E, float* Wt, int Himg, int Wimg, const float* 
 /* out_q3[(y*W+x)*3+c] = E[c][y][x] / Wt[c][y][x]                          (rest:255-256) */
 int ciaosr_tile_finalize_f32(const float* E, const float* Wt, float* out_q3, int Himg, int Wimg, void* stream);
 
+/* ---- test data: GT -> LR degradation (configs/001_*.py, val_scale > 4) ---------------------- */
+/* Pillow-exact bicubic resample of an 8-bit RGB image, PIL Image.resize((Wo, Ho), BICUBIC) -- the resize of mmedit's
+ * RandomDownSampling (mmcv.imresize, backend 'pillow').  src[y * pitch + 3 x + c] (bytes), the top-left H x W of a possibly wider
+ * image; pitch >= 3 W.  Tables per axis, built by the host in float64 in Pillow's order (ciaosr_amd/degrade.py):
+ * bounds [n_out][2] = (first input, tap count), coef [n_out][ksize] int32 with 22 fractional bits.  Horizontal pass only if
+ * Wo != W, vertical only if Ho != H (the other axis's tables may be NULL); out = clip((1 << 21 + sum src * coef) >> 22, 0, 255).
+ * Writes dst_u8 [Ho][Wo][3] and / or dst_chw [3][Ho][Wo] = dst_u8 / 255 (fp32, correctly rounded); either may be NULL.
+ * The source rows are read in aligned 16-byte blocks: bytes next to the image within such a block are read, never used.
+ * workspace: 16-byte aligned, ciaosr_resample_u8_workspace_bytes().  H, Ho <= 65535; CIAOSR_ERR_UNSUPPORTED beyond a
+ * ~4000x horizontal down-scale. */
+size_t ciaosr_resample_u8_workspace_bytes(int H, int W, int Ho, int Wo);
+int ciaosr_resample_u8(const unsigned char* src, size_t pitch, int H, int W, int Ho, int Wo, const int* bounds_x, const int* coef_x,
+                       int ksize_x, const int* bounds_y, const int* coef_y, int ksize_y, unsigned char* dst_u8, float* dst_chw,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

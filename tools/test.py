@@ -4,7 +4,8 @@
     python tools/test.py CONFIG CHECKPOINT [--save-path DIR] [--out FILE] [--launcher none|pytorch] ...
 
 Config = a python config file (this repo's configs/ or the reference's parsable ones); checkpoint = an
-mmcv-style .pth ({'state_dict': ...} or a bare state_dict, keys `generator.*`).  Single process: every image
+mmcv-style .pth ({'state_dict': ...} or a bare state_dict, keys `generator.*`).  data.test is an SRFolderDataset (LQ + GT
+folders) or, for val_scale > 4, an SRFolderGTDataset (GT folder only; the LR input is down-sampled on the GPU).  Single process: every image
 runs on cuda:0.  `--launcher pytorch` (started by torch.distributed.run): the TILES of each image are sharded
 over the ranks (ciaosr_amd/tile_shard.py) instead of the reference's image-level sharding.
 """
@@ -65,7 +66,7 @@ def parse_args(argv=None):
     p.add_argument('--launcher', choices=['none', 'pytorch', 'slurm', 'mpi'], default='none')
     p.add_argument('--local_rank', type=int, default=0)
     p.add_argument('--gpus', type=int, default=0, help='with --launcher pytorch from a plain shell: ranks to start (default: every visible GPU)')
-    p.add_argument('--lq-folder', default=None, help='override cfg.data.test.lq_folder')
+    p.add_argument('--lq-folder', default=None, help='override cfg.data.test.lq_folder (SRFolderDataset configs only)')
     p.add_argument('--gt-folder', default=None, help='override cfg.data.test.gt_folder')
     return p.parse_args(argv)
 
@@ -88,7 +89,7 @@ def main(argv=None):
     import ciaosr_amd
     from ciaosr_amd.checkpoint import load_checkpoint
     from ciaosr_amd.config import Config
-    from ciaosr_amd.dataset import SRFolderDataset
+    from ciaosr_amd.dataset import SRFolderDataset, build_test_dataset
     from ciaosr_amd.tile_shard import StepDeadline, clip_test_distributed, rccl_env_defaults
 
     cfg = Config.fromfile(args.config)
@@ -113,8 +114,10 @@ def main(argv=None):
     dev = torch.device('cuda', torch.cuda.current_device())
 
     tcfg = cfg.data['test']
-    dataset = SRFolderDataset(args.lq_folder or tcfg['lq_folder'], args.gt_folder or tcfg['gt_folder'],
-                              scale=tcfg.get('scale', 4), filename_tmpl=tcfg.get('filename_tmpl', '{}'))
+    try:
+        dataset = build_test_dataset(tcfg, dev, lq_folder=args.lq_folder, gt_folder=args.gt_folder)
+    except ValueError as e:
+        sys.exit(f'tools/test.py: {e}')
     model = ciaosr_amd.build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     if args.checkpoint:
         load_checkpoint(model, args.checkpoint, map_location='cpu')
