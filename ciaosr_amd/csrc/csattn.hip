@@ -192,6 +192,21 @@ static int cs_attn(const float* feat_hwc, int ld_feat, int H, int W, const ciaos
         RUN(patch_rows(E, C, p.Hp, p.Wp, C, 3, 2, 3, Hh + 3, Wh + 3, PE, 9 * C, 0, 0.f, s, "csa_patch_down"));
         RUN(gemm_f32(PE, 9 * C, w->w_down_masked, 9 * C, false, Pc, 9 * C, nullptr, (Hh + 3) * (Wh + 3), 9 * C, 9 * C, 1.f,
                      CIAOSR_ACT_NONE, 0.f, s, "csa_down_partial"));
+        if (prec == kF32 && !(opt && opt->csa_attn_v16) && csa_attn_v4_ok(p.Hp, p.Wp, C, p.Lld) && (size_t)4 * HWp * C <= p.n_O &&
+            (size_t)p.L * 9 * C <= p.n_Vp) {
+            // attn.V on the four diagonal tap blocks (csa_attn_v4_f32.hip): four key-row quarters of partial sums in O; the edge rule of
+            // row 0 / column 0 as three skinny contractions with the tap-0 variants, subtracted in the combine
+            float* part = O;
+            float* Ve = Vp;
+            RUN(csa_gather_vedge(Pc, Hh, Wh, C, Ve, s));
+            RUN(csa_attn_v4_f32(S, p.Lld, st, Pc, part, p.Hp, p.Wp, C, opt && opt->csa_attn_tile128, s));
+            RUN(gemm_f32_softmax_a(S, p.Lld, st, 1, Ve, 9 * C, true, Otop, 4 * C, p.Wp, 4 * C, p.L, Y, p.n_Y, s, "csa_attn_v_edge"));
+            RUN(gemm_f32_softmax_a(S, p.Wp * p.Lld, st, p.Wp, Ve + 4 * C, 9 * C, true, Oleft, 4 * C, p.Hp, 4 * C, p.L, Y, p.n_Y, s,
+                                   "csa_attn_v_edge"));
+            RUN(gemm_f32_softmax_a(S, p.Lld, st, 1, Ve + 8 * C, 9 * C, true, Otl, C, 1, C, p.L, Y, p.n_Y, s, "csa_attn_v_edge"));
+            RUN(csa_attn_v4_combine(part, Otop, Oleft, Otl, w->b_down, H, W, p.Hp, p.Wp, C, out, ld_out, s));
+            return CIAOSR_OK;
+        }
         RUN(csa_gather_vprime(Pc, Hh, Wh, C, Vp, s));
         // attn.V: at a C3 tile's size (768 tiles of 192 x 256) one workgroup per CU, else -- or on request -- the 128 x 128 kernel; bitwise equal
         if (!(opt && opt->csa_attn_tile128) && gemm_big_softmax_f32_ok(p.Lld, 25 * C, HWp, 16 * C, p.L, true) &&

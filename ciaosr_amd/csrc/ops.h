@@ -104,6 +104,14 @@ int csa_gather_vprime(const float* Pc, int Hh, int Wh, int C, float* Vp, hipStre
 int csa_gather_out(const float* Op, const float* Otop, const float* Oleft, const float* Otl, const float* bd, int H, int W,
                    int Hp, int Wp, int C, float* out, int ld_out, long ld_main, long ld_top, long ld_left, hipStream_t s);
 int csa_gather_vprime_t_h16(const float* Pc, int Hh, int Wh, int C, unsigned short* VpT, int ldt, bool f16, hipStream_t s);
+// csa_attn_v4_f32.hip: fp32 attn.V of the composed tail on the four diagonal tap blocks (C = 64): part[4][HpWp][64] partial sums,
+// the edge-rule V columns Ve[L][9C] (top 4C, left 4C, corner C: tap 0 instead of {1,2}) and the combine into out
+bool csa_attn_v4_ok(int Hp, int Wp, int C, int Lld);
+int csa_attn_v4_f32(const float* S, int Lld, const float* stats2, const float* Pc, float* part, int Hp, int Wp, int C, bool tile128,
+                    hipStream_t s);
+int csa_gather_vedge(const float* Pc, int Hh, int Wh, int C, float* Ve, hipStream_t s);
+int csa_attn_v4_combine(const float* part, const float* Otop, const float* Oleft, const float* Otl, const float* bd, int H, int W, int Hp,
+                        int Wp, int C, float* out, int ld_out, hipStream_t s);
 // head_ops.hip
 int head_indices(const float* coord, const float* cell, long q0, int nq, int chunk, int H, int W, int local_size,
                  int* q_idx, int* k_idx, float* rel, hipStream_t s);

@@ -126,14 +126,18 @@ typedef struct ciaosr_options {
                              * rounds 1-3 (same 16-bit products, K split over the waves: another summation order) */
     int csa_scores_gemm;    /* _f32 cs_attn with 32 match channels: 0 (default) = correlation scores as a 3x3 diagonal box sum of the
                              * per-pixel correlation (K = 32, no patch rows); 1 = the 288-wide patch-row GEMM.  Same fp32 products, other order */
-    int csa_attn_tile128;   /* _f32 cs_attn, attn.V (softmax formed in the operand staging): 0 (default) = the 192 x 256 one-workgroup-per-CU kernel
-                             * (gemm_big_f32.hip) where the problem fills the chip (>= 256 workgroup tiles, K a multiple of 16), else and with 1 the
-                             * 128 x 128 kernel.  Bitwise the same result */
+    int csa_attn_tile128;   /* _f32 cs_attn, attn.V (softmax formed in the operand staging), 0 or 1.  Four-block route (csa_attn_v16 below):
+                             * 0 (default) = work items of 192 queries (one query row) per workgroup, 1 = items of 96 queries.  16C route:
+                             * 0 = the 192 x 256 one-workgroup-per-CU kernel (gemm_big_f32.hip) where the problem fills the chip (>= 256
+                             * workgroup tiles, K a multiple of 16), else and with 1 the 128 x 128 kernel.  Either way bitwise the same result */
     int query_grid_w;       /* traversal hint of the 16-bit fused head, >= 0 (a negative value is CIAOSR_ERR_BAD_ARG): W > 0 = the Q queries of
                              * the call are the rows of a row-major grid with W columns (q = i W + j, Q a multiple of W: what
                              * ciaosr_make_coord_cell_f32 produces); the chained kernel then walks them in 16 x 4 blocks so that a wave's rows
                              * gather from a handful of LR pixels.  Results do not depend on it; 0 = walk them in index order */
     int f16_pairs;          /* 0 to 3: selects a precision mode (table above) */
+    int csa_attn_v16;       /* _f32 cs_attn, composed tail, 64 channels: 0 (default) = attn.V on the four diagonal tap blocks
+                             * (csa_attn_v4_f32.hip: K = 4 (Hp/2+3)(Wp/2+3) instead of 16 L; where the logit matrix is under 2 GiB);
+                             * 1 = the 16C route of 16 offset columns.  Same products summed in another order */
 } ciaosr_options_t;
 
 /* ---- layout plumbing -------------------------------------------------------------------- */
