@@ -160,6 +160,9 @@ SIGNATURES = {
     'ciaosr_tile_finalize_f32': (_I, [_P, _P, _P, _I, _I, _P]),
     'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_resample_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _S, _P]),
+    'ciaosr_tensor2img_u8': (_I, [_P, _I, _I, _P, _S, _P]),
+    'ciaosr_psnr_ssim_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),
+    'ciaosr_psnr_ssim_u8': (_I, [_P, _S, _P, _S, _I, _I, _I, _I, _I, _P, _P, _S, _P]),
 }
 
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)

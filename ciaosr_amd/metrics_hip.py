@@ -1,0 +1,105 @@
+"""PSNR / SSIM of `BasicRestorer.evaluate` on the MI355X (csrc/metrics_u8.hip), opt-in through `test_cfg.gpu_metrics`.
+
+Same definitions as ciaosr_amd/metrics.py (basic_restorer.py:101-124 -> mmedited/core/evaluation/metrics.py:181-226, :229-318):
+both images are quantised to 8 bits first (`tensor2img`), then compared.  `tensor2img_u8` is bitwise `metrics.tensor2img`;
+`psnr_ssim_u8` evaluates both metrics in one pass over the two byte images and leaves twelve doubles on the device, which the
+host finishes with a mean and a log10 -- that copy is the only synchronisation.  There is no CPU fallback.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib, hip_ops
+from ._lib import CiaoSRHipError
+
+WANT_BITS = {'PSNR': 1, 'SSIM': 2}        # CIAOSR_METRIC_PSNR / CIAOSR_METRIC_SSIM
+SSIM_WINDOW = 11
+
+
+def tensor2img_u8(t):
+    """`metrics.tensor2img` on the device: [1, 3, H, W] or [3, H, W] RGB in [0, 1] -> uint8 [H, W, 3] BGR (x255, round half even)."""
+    t = t.detach()
+    while t.dim() > 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f'tensor2img_u8 expects [1, 3, H, W] or [3, H, W], got {tuple(t.shape)}')
+    t = t.float().contiguous()
+    hip_ops.require_gpu(t)
+    h, w = t.shape[1], t.shape[2]
+    img = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
+    _lib.call('ciaosr_tensor2img_u8', hip_ops.ptr(t), h, w, hip_ops.ptr(img), C.c_size_t(img.stride(0)), hip_ops.stream_ptr(t.device))
+    return img
+
+
+def _check_image(img):
+    if not isinstance(img, torch.Tensor):
+        raise CiaoSRHipError(f'expected a uint8 HxWx3 cuda tensor, got {type(img).__name__}')
+    if not img.is_cuda:
+        hip_ops.require_gpu(img)              # raises: no CPU fallback
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise CiaoSRHipError(f'expected a uint8 HxWx3 image, got {img.dtype} {tuple(img.shape)}')
+    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * img.shape[1]:
+        raise CiaoSRHipError('expected HWC rows of 3*W contiguous bytes (a crop of a larger image is fine)')
+    if img.device.index != torch.cuda.current_device():
+        raise CiaoSRHipError(f'image on cuda:{img.device.index} but the current device is cuda:{torch.cuda.current_device()}')
+
+
+def finish(sums, want):
+    """{name: float} from the kernel's [3][sse, pixels, ssim sum, map pixels] (a host list of 12 floats), as metrics.psnr / .ssim."""
+    res = {}
+    for name in want:
+        if name == 'PSNR':
+            n = sum(sums[4 * c + 1] for c in range(3))
+            mse = sum(sums[4 * c] for c in range(3)) / n
+            res[name] = float('inf') if mse == 0 else 20.0 * math.log10(255.0 / math.sqrt(mse))
+        else:
+            vals = [sums[4 * c + 2] / sums[4 * c + 3] for c in range(3) if sums[4 * c + 3] > 0]
+            res[name] = float(sum(vals) / len(vals))
+    return res
+
+
+def launch_psnr_ssim_u8(a, b, crop_border=0, convert_to=None, want=('PSNR', 'SSIM')):
+    """Checks + the two launches of `psnr_ssim_u8` without the result copy: returns the 12 doubles on the device
+    ([3][sse, pixels, ssim sum, map pixels]) and does not synchronise."""
+    _check_image(a)
+    _check_image(b)
+    assert a.shape == b.shape, f'Image shapes are different: {a.shape}, {b.shape}.'
+    if isinstance(convert_to, str) and convert_to.lower() == 'y':
+        to_y = 1
+    elif convert_to is not None:
+        raise ValueError('Wrong color model. Supported values are "Y" and None.')
+    else:
+        to_y = 0
+    h, w = a.shape[0], a.shape[1]
+    crop = int(crop_border)
+    if crop < 0 or 2 * crop >= h or 2 * crop >= w:
+        raise ValueError(f'crop_border={crop_border} leaves nothing of a {h}x{w} image')
+    if 'SSIM' in want and (h - 2 * crop < SSIM_WINDOW or w - 2 * crop < SSIM_WINDOW):
+        raise ValueError(f'SSIM needs at least {SSIM_WINDOW}x{SSIM_WINDOW} pixels after the crop, got {h - 2 * crop}x{w - 2 * crop}')
+    bits = 0
+    for name in want:
+        bits |= WANT_BITS[name]
+    dev = a.device
+    lib = _lib.load()
+    nbytes = lib.ciaosr_psnr_ssim_u8_workspace_bytes(h, w, crop, to_y)
+    if nbytes == 0:
+        raise CiaoSRHipError(f'psnr_ssim_u8: a {h}x{w} image with crop_border={crop} is beyond the kernel\'s index range')
+    ws = hip_ops.workspace(nbytes, dev, slot='metrics')
+    out = torch.empty(12, dtype=torch.float64, device=dev)
+    _lib.call('ciaosr_psnr_ssim_u8', hip_ops.ptr(a), C.c_size_t(a.stride(0)), hip_ops.ptr(b), C.c_size_t(b.stride(0)), h, w, crop,
+              to_y, bits, hip_ops.ptr(out), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    return out
+
+
+def psnr_ssim_u8(a, b, crop_border=0, convert_to=None, want=('PSNR', 'SSIM')):
+    """`metrics.psnr` / `metrics.ssim` of two uint8 [H, W, 3] BGR images on the device -> {name: python float} in the order of
+    `want`.  PSNR is inf for identical images.  Rows may be pitched (a crop view of a larger image).  The copy of the twelve
+    doubles to the host is the only synchronisation."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    for name in want:
+        if name not in WANT_BITS:
+            raise KeyError(name)
+    if not want:
+        return {}
+    return finish(launch_psnr_ssim_u8(a, b, crop_border, convert_to, want).cpu().tolist(), want)

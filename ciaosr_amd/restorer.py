@@ -68,8 +68,16 @@ class BasicRestorer(nn.Module):
             return self.forward_test(lq, gt, **kwargs)
         raise NotImplementedError('forward_train / train_step are out of scope of the MI355X inference path')
 
-    def evaluate(self, output, gt):
-        """PSNR/SSIM on uint8 BGR images as basic_restorer.py:101-124."""
+    def gpu_metrics(self):
+        """`test_cfg.gpu_metrics` (an extension; default off): quantise and evaluate on the device (ciaosr_amd/metrics_hip.py)."""
+        return bool(self.test_cfg is not None and self.test_cfg.get('gpu_metrics', False))
+
+    def evaluate(self, output, gt, out_img=None):
+        """PSNR/SSIM on uint8 BGR images as basic_restorer.py:101-124.  With `test_cfg.gpu_metrics` both tensors are quantised
+        and compared on the device (`out_img`: the already quantised output, if the caller has it); the output must be there
+        -- no fallback -- and a GT on the host is moved."""
+        if self.gpu_metrics():
+            return self._evaluate_gpu(output, gt, out_img)
         crop_border = self.test_cfg.crop_border
         out_img, gt_img = metrics.tensor2img(output), metrics.tensor2img(gt)
         res = {}
@@ -80,6 +88,22 @@ class BasicRestorer(nn.Module):
             else:
                 res[metric] = fn(out_img, gt_img, crop_border)
         return res
+
+    def _evaluate_gpu(self, output, gt, out_img=None):
+        from . import metrics_hip
+        names = list(self.test_cfg.metrics)
+        for metric in names:
+            self.allowed_metrics[metric]                       # an unknown name fails as on the host path
+        if not output.is_cuda:
+            hip_ops.require_gpu(output)                        # raises CiaoSRHipError
+        if not gt.is_cuda:
+            gt = gt.to(output.device)
+        if out_img is None:
+            out_img = metrics_hip.tensor2img_u8(output)
+        gt_img = metrics_hip.tensor2img_u8(gt)
+        convert_to = self.test_cfg.convert_to if 'convert_to' in self.test_cfg else None
+        res = metrics_hip.psnr_ssim_u8(out_img, gt_img, self.test_cfg.crop_border, convert_to, want=names)
+        return {metric: res[metric] for metric in names}
 
 
 def tile_starts(n, tile, overlap):
@@ -406,9 +430,13 @@ class CiaoSR(BasicRestorer):
         if gt is not None:
             shape = [lq.shape[0], pred.shape[2], pred.shape[3], 3]
             gt = gt.view(*shape).permute(0, 3, 1, 2).contiguous()
+        out_img = None
+        if self.gpu_metrics() and save_image:
+            from . import metrics_hip
+            out_img = metrics_hip.tensor2img_u8(pred)              # quantised once, for the metrics and for the file
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
             assert gt is not None, 'evaluation with metrics must have gt images.'
-            results = dict(eval_result=self.evaluate(pred, gt))
+            results = dict(eval_result=self.evaluate(pred, gt, out_img))
         else:
             results = dict(lq=lq.cpu(), output=pred.cpu())
             if gt is not None:
@@ -425,7 +453,7 @@ class CiaoSR(BasicRestorer):
             else:
                 raise ValueError(f'iteration should be number or None, but got {type(iteration)}')
             from .imageio import imwrite
-            imwrite(metrics.tensor2img(pred), save_path)
+            imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(pred), save_path)
         return results
 
     def init_weights(self, pretrained=None, strict=True):

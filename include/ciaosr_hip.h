@@ -537,6 +537,27 @@ int ciaosr_resample_u8(const unsigned char* src, size_t pitch, int H, int W, int
                        int ksize_x, const int* bounds_y, const int* coef_y, int ksize_y, unsigned char* dst_u8, float* dst_chw,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- evaluation on 8-bit images (mmedited/models/restorers/basic_restorer.py:101-124) -------- */
+#define CIAOSR_METRIC_PSNR 1
+#define CIAOSR_METRIC_SSIM 2
+/* mmedit.core.tensor2img (called at basic_restorer.py:108-109; restated in ciaosr_amd/metrics.py:10-25) for min_max = (0, 1) and
+ * out_type uint8: src_chw [3][H][W] fp32 RGB -> dst_hwc[y * dst_pitch + 3 x + c] bytes in BGR order, each
+ * rint(clamp(v, 0, 1) * 255) with one fp32 multiply and round-half-to-even; NaN -> 0.  dst_pitch >= 3 W.  H <= 65535. */
+int ciaosr_tensor2img_u8(const float* src_chw, int H, int W, unsigned char* dst_hwc, size_t dst_pitch, void* stream);
+/* psnr and ssim of mmedited/core/evaluation/metrics.py:181-226 and :229-318 on two 8-bit BGR images a, b [H][W][3] with row pitches
+ * in bytes (>= 3 W), in one pass.  crop_border pixels are removed on every side first.  convert_to_y = 1: both metrics on
+ * Y = mmcv.bgr2ycbcr(img / 255, y_only=True) * 255 evaluated in fp32 with individually rounded operations; 0: the three channels
+ * separately.  SSIM: 11-tap Gaussian (sigma 1.5), separable 'valid' filter, C1 = 6.5025, C2 = 58.5225, filtered maps and all sums in
+ * fp64.  want = CIAOSR_METRIC_PSNR | CIAOSR_METRIC_SSIM (either or both; the value of one does not depend on the other being asked for).
+ * result: 12 doubles on the DEVICE, [channel 0..2][sum of squared differences, pixels, sum of the SSIM map, map pixels] (channel 0
+ * only with convert_to_y; unused entries 0): the host finishes with mse = sum sse / sum pixels, PSNR = 10 log10(255^2 / mse),
+ * SSIM = mean over channels of (sum / map pixels).  No atomics: bitwise reproducible, independent of the pitches.
+ * workspace: 8-byte aligned, ciaosr_psnr_ssim_u8_workspace_bytes() (0 = unsupported geometry); fully rewritten by every call.
+ * CIAOSR_ERR_UNSUPPORTED: 2 crop_border >= H or W, a cropped side < 11 with SSIM wanted, H or W > 2^20. */
+size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int convert_to_y);
+int ciaosr_psnr_ssim_u8(const unsigned char* a, size_t pitch_a, const unsigned char* b, size_t pitch_b, int H, int W, int crop_border,
+                        int convert_to_y, int want, double* result, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,16 @@ def parse_args(argv=None):
     p.add_argument('--gpus', type=int, default=0, help='with --launcher pytorch from a plain shell: ranks to start (default: every visible GPU)')
     p.add_argument('--lq-folder', default=None, help='override cfg.data.test.lq_folder (SRFolderDataset configs only)')
     p.add_argument('--gt-folder', default=None, help='override cfg.data.test.gt_folder')
+    p.add_argument('--gpu-metrics', action='store_true',
+                   help='test_cfg.gpu_metrics = True: quantise and evaluate PSNR / SSIM on the GPU (default: on the host)')
     return p.parse_args(argv)
+
+
+def apply_overrides(cfg, args):
+    """Command-line switches that end up in the loaded config (before the model is built from it)."""
+    if args.gpu_metrics:
+        cfg.test_cfg['gpu_metrics'] = True
+    return cfg
 
 
 def collect_results(mine, n_items, rank, world, group=None):
@@ -92,7 +101,7 @@ def main(argv=None):
     from ciaosr_amd.dataset import SRFolderDataset, build_test_dataset
     from ciaosr_amd.tile_shard import StepDeadline, clip_test_distributed, rccl_env_defaults
 
-    cfg = Config.fromfile(args.config)
+    cfg = apply_overrides(Config.fromfile(args.config), args)
     if args.checkpoint in (None, 'None'):
         args.checkpoint = cfg.get('test_checkpoint_path')
     distributed = args.launcher != 'none'
@@ -141,11 +150,16 @@ def main(argv=None):
             h, w = round(lq.shape[-2] * model.test_cfg.scale), round(lq.shape[-1] * model.test_cfg.scale)
             out = hip_ops.denorm_clamp(pred[0].contiguous(), h, w, model.rgb_mean, model.rgb_std).unsqueeze(0)
             gt_img = gt.view(1, h, w, 3).permute(0, 3, 1, 2).contiguous()
-            res = dict(eval_result=model.evaluate(out, gt_img))
+            out_img = None
+            if save and model.gpu_metrics():
+                from ciaosr_amd import metrics_hip
+                out_img = metrics_hip.tensor2img_u8(out)          # quantised once, for the metrics and for the file
+            res = dict(eval_result=model.evaluate(out, gt_img, out_img))
             if save:
                 from ciaosr_amd.imageio import imwrite
                 name = os.path.splitext(os.path.basename(d['meta']['gt_path']))[0]
-                imwrite(metrics.tensor2img(out), os.path.join(args.save_path, f'{name}.png'))
+                imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(out),
+                        os.path.join(args.save_path, f'{name}.png'))
         else:
             if world > 1 and i % world != rank:
                 continue
