@@ -18,15 +18,26 @@
 //
 // Work item: one query row oy, QW (= 192, or 96 for csa_attn_tile128) queries of it, one quarter of the padded key rows; the four
 // quarters write fixed-order partial outputs part[q][o][0..64) that csa_attn_v4_combine sums.  A step = one padded key row gy and
-// KW = 20 padded key columns gx0 .. gx0+19, all four blocks (K = 80):
-//   T phase: exp2 of the four logit blocks (query row oy+dy) x (key row gy-1+dy), (QW+3) x 23 each with the halos, into LDS;
-//            U's 80 x 64 tile into LDS; one thread per diagonal o - k of the QW x 20 tile reads its 23 probabilities per dy, forms the
-//            four A values of 20 (o, k) and writes them to the [k][o] A tile.
-//   M phase: 4 waves of 96 x 32 (3 MFMA tiles, v_mfma_f32_32x32x2f32), 40 k-pairs; the global loads of the next step behind the MFMAs.
+// SW = 20 padded key columns gx0 .. gx0+19 in two halves of KW = 10, all four blocks (K = 40 per half).  The workgroup is
+// wave-specialised (as csa_scores_box_f32_kernel), three roles with one wave of each on every SIMD, one A and one U tile per half in
+// LDS, three barriers per step:
+//   stagers (waves 0-3)    X: exp2 of the four logit blocks (query row oy+dy) x (key row gy-1+dy), (QW+3) x 23 each with the halos,
+//                          into LDS.  Y0, Y1: the next step's logit loads, two blocks each.  These waves spend Y0 and Y1 waiting on
+//                          the memory pipeline (72 dword loads of 92-byte row pieces per thread: the probe shows ~4 500 cycles per
+//                          half), which is why the loads have waves of their own: nothing else waits with them.
+//   diagonals (waves 4-7)  X: U loads of the step.  Y0: U's 40 x 64 tile of half 0; one thread per diagonal o - k of the QW x 10
+//                          tile reads its 13 probabilities per dy, forms the four A values of 10 (o, k) and writes them to the
+//                          [k][o] A tile 0.  Y1: the same for half 1.
+//   consumers (waves 8-11; two for QW = 96)  half 0 of step n during Y1(n) and X(n+1), half 1 during X(n+1) and Y0(n+1): each
+//                          tile is rewritten one phase after its last read.  A wave owns 96 x 32 outputs (3 MFMA tiles,
+//                          v_mfma_f32_32x32x2f32, 20 k-pairs per half), carries no staging registers and reads its fragments
+//                          AV_PF k-pairs ahead.
+// The fp32 MFMA and the VALU are the same lanes of a SIMD, so a step costs the sum of the three roles' issue cycles, not
+// their maximum; what the split removes is every wait: on the loads, on the LDS round trips of fragments and diagonals, on barriers.
 // Key rows are walked as gy = base + (t + oy) mod n, so the four items oy = qy - dy that need the logit block (qy, ly) read it in the
 // same step; the XCD-aware remap keeps consecutive query rows on one XCD (its L2 serves the three re-reads).
-// The K order of an output (gy walk, gx0 ascending, block, k ascending) depends on (oy, quarter) only: both tile widths give bitwise
-// the same result.
+// The K order of an output (gy walk, gx0 ascending, half, block, k ascending) depends on (oy, quarter) only: both tile widths give
+// bitwise the same result.
 #include "ops.h"
 
 namespace ciaosr {
@@ -34,26 +45,42 @@ namespace ciaosr {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int AV_KW = 20;                  // padded key columns per step and block
-constexpr int AV_RS = AV_KW + 3;           // staged logit columns per row (x-halo -3 .. +2 around the step)
+constexpr int AV_KW = 10;                  // padded key columns per half step and block
+constexpr int AV_SW = 2 * AV_KW;           // padded key columns per step
+constexpr int AV_RS = AV_SW + 3;           // staged logit columns per row (x-halo -3 .. +2 around the step)
 constexpr int AV_C = 64;                   // channels (N)
-constexpr int AV_NCOL = 4 * AV_KW;         // K per step
-constexpr int AV_BT = AV_NCOL * AV_C;      // U tile: [80][64]
+constexpr int AV_NCOL = 4 * AV_KW;         // K per half
+constexpr int AV_BT = AV_NCOL * AV_C;      // U tile: [40][64]
+constexpr int AV_KP = AV_NCOL / 2;         // k-pairs (MFMA k = 2) per half
+constexpr int AV_SA = 14;                  // k-pairs of half 0 the consumers run in Y1 (the others in X)
+constexpr int AV_SB = 8;                   // k-pairs of half 1 the consumers run in X (the others in Y0)
+constexpr int AV_PF = 4;                   // k-pairs of fragments a consumer reads ahead
+static_assert(AV_SA % 2 == 0 && AV_SB % 2 == 0 && AV_PF % 2 == 0 && AV_KP % 2 == 0 && AV_SA > 0 && AV_SA + AV_PF <= AV_KP && AV_SB > 0 &&
+              AV_SB < AV_KP, "k-pair groups; half 1 is not read before the barrier that completes it");
 
 template <int QW>
 struct AvCfg {
-    static constexpr int NT = QW == 192 ? 256 : 128;          // threads: 4 or 2 waves of 96 x 32
-    static constexpr int TR = NT / AV_RS;                      // staging: threads per column of the logit block (11 or 5)
-    static constexpr int NI = (QW + 3 + TR - 1) / TR;         // staged rows per thread and block (18 or 20)
+    static constexpr int NP = 256;                             // threads of the staging role and of the diagonal role (4 waves each)
+    static constexpr int NT = 2 * NP + 64 * (QW / 48);         // and 4 or 2 consumer waves of 96 x 32
+    static constexpr int TR = NP / AV_RS;                      // staging: threads per column of the logit block (11)
+    static constexpr int NI = (QW + 3 + TR - 1) / TR;         // staged rows per thread and block (18 or 9)
     static constexpr int NRB = TR * NI;                        // rows per staged block (>= QW + 3)
     static constexpr int PST = 4 * NRB * AV_RS;                // staged probabilities
-    static constexpr int AT = AV_NCOL * QW;                    // A tile [80][QW]
-    static constexpr size_t LDS = (size_t)(AV_BT + PST + AT) * sizeof(float);
+    static constexpr int AT = AV_NCOL * QW;                    // A tile [40][QW]
+    static constexpr size_t LDS = (size_t)(2 * AV_BT + PST + 2 * AT) * sizeof(float);
 };
-static_assert(AvCfg<192>::LDS <= 163840, "LDS");
-static_assert(AvCfg<192>::NT >= 192 + AV_KW - 1 && AvCfg<96>::NT >= 96 + AV_KW - 1, "one thread per diagonal");
-// the diagonal reads of rows -19 .. NRB + 18 of a block stay inside the allocation: U tile before, A tile after the staged blocks
-static_assert(AV_BT >= (AV_KW - 1) * AV_RS && AvCfg<96>::AT >= 24 * AV_RS, "diagonal read guard");
+static_assert(AvCfg<192>::LDS <= 163840 && AvCfg<96>::LDS <= 163840, "LDS");
+static_assert(AvCfg<192>::NP >= 192 + AV_KW - 1 && AvCfg<96>::NP >= 96 + AV_KW - 1, "one thread per diagonal");
+static_assert(AvCfg<192>::NRB >= 192 + 3 && AvCfg<96>::NRB >= 96 + 3, "staged rows");
+// the diagonal reads of rows -(KW-1) .. QW + KW + 1 of a block stay inside the allocation: U tiles before, A tiles after the staged blocks
+static_assert(2 * AV_BT >= (AV_KW - 1) * AV_RS && 2 * AvCfg<96>::AT >= (AV_KW + 2) * AV_RS + AV_RS, "diagonal read guard");
+
+#ifdef CIAOSR_PROBE      // developer probe build (make probe; tools/csattn_v4_probe.py): cycle sums of the last <192> launch's workgroups
+__device__ unsigned long long g_avprobe[1024 * 48];
+#define AVPROBE_T() __builtin_readcyclecounter()
+#else
+#define AVPROBE_T() 0ull
+#endif
 
 struct CsaAv4P {
     const float* S; const float2* st; const float* Pc; float* part;
@@ -61,15 +88,23 @@ struct CsaAv4P {
     unsigned s_bytes, pc_bytes;
 };
 
+// s_barrier that no memory access is moved across by the compiler, without the waits of a fence: for the consumer waves, whose reads
+// in flight at such a barrier are of tiles that stay unwritten through the next phase
+__device__ __forceinline__ void av_phase_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 template <int QW>
 __global__ __launch_bounds__(AvCfg<QW>::NT) void csa_attn_v4_kernel(CsaAv4P p) {
     using Cfg = AvCfg<QW>;
-    constexpr int NT = Cfg::NT, TR = Cfg::TR, NI = Cfg::NI, NRB = Cfg::NRB;
-    constexpr int NB = AV_BT / 4 / NT;                         // float4 of the U tile per thread (5 or 10)
+    constexpr int NP = Cfg::NP, TR = Cfg::TR, NI = Cfg::NI, NRB = Cfg::NRB;
+    constexpr int NB = (AV_BT / 4 + NP - 1) / NP;              // float4 of a U tile per producer thread (3, the last one partial)
     extern __shared__ __attribute__((aligned(16))) float avs[];
-    float* Bt = avs;
-    float* Pst = avs + AV_BT;
-    float* At = Pst + Cfg::PST;
+    float* Bt = avs;                                            // [2][40][64]
+    float* Pst = avs + 2 * AV_BT;
+    float* At = Pst + Cfg::PST;                                 // [2][40][QW]
 
     // XCD-aware bijective remap (as gemm_big_softmax_f32_kernel): an XCD walks a contiguous run of items, consecutive query rows
     const int bid = blockIdx.x;
@@ -81,152 +116,258 @@ __global__ __launch_bounds__(AvCfg<QW>::NT) void csa_attn_v4_kernel(CsaAv4P p) {
     const int x0 = seg * QW, nq = min(QW, p.Wp - x0);
     const int ngy = p.Hh + 3, gyb = quarter * ngy / 4, nr = (quarter + 1) * ngy / 4 - gyb;
     const int HWp = p.Hp * p.Wp;
+    const int nsteps = nr * p.nch;
 
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = w >> 1, wn = w & 1, li = lane & 31, lh = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.S), 0, p.s_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_pc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Pc), 0, p.pc_bytes, 0x00020000);
+#ifdef CIAOSR_PROBE
+    const bool stamp = QW == 192 && lane == 0 && (w & 3) == 0 && bid < 1024;
+    unsigned long long pacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const unsigned long long pstart = AVPROBE_T();
+#define AVPROBE_ADD(slot, t0) do { const unsigned long long now_ = AVPROBE_T(); pacc[slot] += now_ - (t0); (t0) = now_; } while (0)
+#define AVPROBE_OUT(role) do { if (stamp) { for (int i_ = 0; i_ < 10; ++i_) g_avprobe[bid * 48 + 16 * (role) + i_] = pacc[i_];                \
+        g_avprobe[bid * 48 + 16 * (role) + 14] = AVPROBE_T() - pstart; g_avprobe[bid * 48 + 16 * (role) + 15] = (unsigned long long)nsteps; } } while (0)
+#else
+#define AVPROBE_ADD(slot, t0) do { } while (0)
+#define AVPROBE_OUT(role) do { } while (0)
+#endif
 
-    // staging coordinates: column j of the block, rows r0 + TR i.  Query pixel (oy + dy, x0 + r - 2), key (gy - 1 + dy, gx0 - 3 + j).
-    const bool stager = t < TR * AV_RS;
-    const int sj = t % AV_RS, sr0 = t / AV_RS;
-    float negm[4][NI];                                          // -m' per staged element; -inf outside the query grid (P = 0)
-#pragma unroll
-    for (int dyi = 0; dyi < 4; ++dyi) {
-        const int qy = oy + dyi - 2;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int qx = x0 + sr0 + TR * i - 2;
-            float v = -__builtin_inff();
-            if (stager && qy >= 0 && qy < p.Hp && qx >= 0 && qx < p.Wp) {
-                const float2 s2 = p.st[(size_t)qy * p.Wp + qx];
-                v = -(s2.x - __builtin_amdgcn_logf(s2.y));    // exp2(x l2e - mx) / sum = exp2(x l2e - (mx - log2(1 / sum)))
-            }
-            negm[dyi][i] = v;
-        }
-    }
-    const int s_thread = sr0 * p.Lld + sj;                      // element offset of (r0, j) relative to the block's (r = 0, j = 0)
-    const int s_istep = TR * p.Lld;
-    // U tile: float4 s of the thread = (kk = idx / 16, c4 = idx % 16); kk = block * KW + k
-    int b_rel[NB], b_k[NB];
-#pragma unroll
-    for (int s = 0; s < NB; ++s) {
-        const int idx = t + NT * s, kk = idx >> 4, c4 = idx & 15;
-        const int blk = kk / AV_KW, k = kk - blk * AV_KW;
-        const int pcb = blk == 0 ? 8 : blk == 1 ? 6 : blk == 2 ? 2 : 0;     // (A,A) (A,B) (B,A) (B,B): 3 r + s with {0} = 0, {1,2} = 2
-        b_rel[s] = k * 9 * AV_C + pcb * AV_C + 4 * c4;
-        b_k[s] = k;
-    }
-
-    float ra[4][NI];
-    float4 rb[NB];
-    auto issue_loads = [&](int gy, int gx0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int dyi = 0; dyi < 4; ++dyi) {
-            const int dy = dyi - 2;
-            // may be negative (rows above the grid, x-halo left of column 0): as unsigned it is past s_bytes (< 2 GiB) and reads 0
-            const int base = ((oy + dy) * p.Wp + x0 - 2) * p.Lld + (gy - 1 + dy) * p.Wh + gx0 - 3 + s_thread;
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-                ra[dyi][i] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_s, (base + i * s_istep) * 4, 0, 0));
-        }
-        const int brow = (gy * (p.Wh + 3) + gx0) * 9 * AV_C;
-#pragma unroll
-        for (int s = 0; s < NB; ++s) {
-            const unsigned off = gx0 + b_k[s] < p.Wh + 3 ? (unsigned)(brow + b_rel[s]) * 4u : 0x80000000u;
-            const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_pc, off, 0, 0);
-            rb[s] = make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
-        }
+    int trow = 0, ch = 0;
+    int gy = gyb + oy % nr, gx0 = 0;
+    auto next_step = [&]() __attribute__((always_inline)) {
+        if (++ch == p.nch) { ch = 0; ++trow; }
+        gy = gyb + (trow + oy) % nr; gx0 = ch * AV_SW;
     };
-    // T phase, part 1: probabilities into the staged blocks.  EDGE: some key of the step lies outside the key grid (its logit may be
-    // anything, the pad columns of S included): those elements are replaced by 0.
-    auto stage = [&](int gy, int gx0, auto edge_c) __attribute__((always_inline)) {
-        constexpr bool EDGE = decltype(edge_c)::value;
-        constexpr float kL2e = 1.4426950408889634f;
-        const bool kx = (unsigned)(gx0 - 3 + sj) < (unsigned)p.Wh;
+
+    if (w < NP / 64) {
+        // ================= stagers: logits -> probabilities in LDS =================
+        const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.S), 0, p.s_bytes, 0x00020000);
+        // staging coordinates: column j of the block, rows r0 + TR i.  Query pixel (oy + dy, x0 + r - 2), key (gy - 1 + dy, gx0 - 3 + j).
+        const bool stager = t < TR * AV_RS;
+        const int sj = t % AV_RS, sr0 = t / AV_RS;
+        float negm[4][NI];                                      // -m' per staged element; -inf outside the query grid (P = 0)
 #pragma unroll
         for (int dyi = 0; dyi < 4; ++dyi) {
-            const bool ok = kx && (unsigned)(gy - 3 + dyi) < (unsigned)p.Hh;
-            float* dst = Pst + dyi * NRB * AV_RS + sr0 * AV_RS + sj;
+            const int qy = oy + dyi - 2;
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
-                float v = __builtin_amdgcn_exp2f(__builtin_fmaf(ra[dyi][i], kL2e, negm[dyi][i]));
-                if (EDGE) v = ok ? v : 0.f;
-                if (stager) dst[i * TR * AV_RS] = v;
+                const int qx = x0 + sr0 + TR * i - 2;
+                float v = -__builtin_inff();
+                if (stager && qy >= 0 && qy < p.Hp && qx >= 0 && qx < p.Wp) {
+                    const float2 s2 = p.st[(size_t)qy * p.Wp + qx];
+                    v = -(s2.x - __builtin_amdgcn_logf(s2.y));    // exp2(x l2e - mx) / sum = exp2(x l2e - (mx - log2(1 / sum)))
+                }
+                negm[dyi][i] = v;
             }
         }
-    };
+        const int s_thread = sr0 * p.Lld + sj;                  // element offset of (r0, j) relative to the block's (r = 0, j = 0)
+        const int s_istep = TR * p.Lld;
+        float ra[4][NI];
+        auto issue_logits = [&](auto dy0_c) __attribute__((always_inline)) {
+            constexpr int DY0 = decltype(dy0_c)::value;
+#pragma unroll
+            for (int dyi = DY0; dyi < DY0 + 2; ++dyi) {
+                const int dy = dyi - 2;
+                // may be negative (rows above the grid, x-halo left of column 0): as unsigned it is past s_bytes (< 2 GiB) and reads 0
+                const int base = ((oy + dy) * p.Wp + x0 - 2) * p.Lld + (gy - 1 + dy) * p.Wh + gx0 - 3 + s_thread;
+#pragma unroll
+                for (int i = 0; i < NI; ++i)
+                    ra[dyi][i] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_s, (base + i * s_istep) * 4, 0, 0));
+            }
+        };
+        // probabilities into the staged blocks.  EDGE: some key of the step lies outside the key grid (its logit may be anything, the
+        // pad columns of S included): those elements are replaced by 0.
+        auto stage = [&](auto edge_c) __attribute__((always_inline)) {
+            constexpr bool EDGE = decltype(edge_c)::value;
+            constexpr float kL2e = 1.4426950408889634f;
+            const bool kx = (unsigned)(gx0 - 3 + sj) < (unsigned)p.Wh;
+#pragma unroll
+            for (int dyi = 0; dyi < 4; ++dyi) {
+                const bool ok = kx && (unsigned)(gy - 3 + dyi) < (unsigned)p.Hh;
+                float* dst = Pst + dyi * NRB * AV_RS + sr0 * AV_RS + sj;
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    float v = __builtin_amdgcn_exp2f(__builtin_fmaf(ra[dyi][i], kL2e, negm[dyi][i]));
+                    if (EDGE) v = ok ? v : 0.f;
+                    if (stager) dst[i * TR * AV_RS] = v;
+                }
+                __builtin_amdgcn_sched_barrier(0);              // block by block: each waits only for its own loads, the later ones still land
+            }
+        };
+        issue_logits(std::integral_constant<int, 0>{});
+        issue_logits(std::integral_constant<int, 2>{});
+        [[maybe_unused]] unsigned long long pt0 = AVPROBE_T();
+#pragma unroll 1
+        for (int step = 0; step < nsteps; ++step) {
+            // ---- X ----
+            const bool edge = gy < 3 || gy >= p.Hh || gx0 < 3 || gx0 + AV_SW - 1 >= p.Wh;
+            if (edge) stage(std::true_type{});
+            else stage(std::false_type{});
+            AVPROBE_ADD(0, pt0);
+            __syncthreads();
+            AVPROBE_ADD(1, pt0);
+            // ---- Y0, Y1 ----  the next step's logits: the wave waits here on the memory pipeline, beside the diagonal waves' work
+            next_step();
+            const bool more = step + 1 < nsteps;
+            if (more) issue_logits(std::integral_constant<int, 0>{});
+            AVPROBE_ADD(2, pt0);
+            __syncthreads();
+            AVPROBE_ADD(3, pt0);
+            if (more) issue_logits(std::integral_constant<int, 2>{});
+            AVPROBE_ADD(4, pt0);
+            __syncthreads();
+            AVPROBE_ADD(5, pt0);
+        }
+        AVPROBE_OUT(0);
+        return;
+    }
 
+    if (w < 2 * NP / 64) {
+        // ================= diagonal waves: probabilities -> A tiles, U tiles =================
+        const int td = t - NP;
+        const __amdgpu_buffer_rsrc_t rs_pc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Pc), 0, p.pc_bytes, 0x00020000);
+        // U tiles: float4 s of the thread = (kk = idx / 16, c4 = idx % 16); kk = block * KW + k, half h at key column gx0 + KW h + k
+        int b_rel[NB], b_k[NB];
+#pragma unroll
+        for (int s = 0; s < NB; ++s) {
+            const int idx = td + NP * s, kk = idx >> 4, c4 = idx & 15;
+            const int blk = kk / AV_KW, k = kk - blk * AV_KW;
+            const int pcb = blk == 0 ? 8 : blk == 1 ? 6 : blk == 2 ? 2 : 0;     // (A,A) (A,B) (B,A) (B,B): 3 r + s with {0} = 0, {1,2} = 2
+            b_rel[s] = k * 9 * AV_C + pcb * AV_C + 4 * c4;
+            b_k[s] = idx < AV_BT / 4 ? k : 0x40000000;          // past the tile: never in range, never written
+        }
+        float4 rb[2][NB];
+        auto issue_u = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int brow = (gy * (p.Wh + 3) + gx0 + AV_KW * h) * 9 * AV_C;
+#pragma unroll
+                for (int s = 0; s < NB; ++s) {
+                    const unsigned off = gx0 + AV_KW * h + b_k[s] < p.Wh + 3 ? (unsigned)(brow + b_rel[s]) * 4u : 0x80000000u;
+                    const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_pc, off, 0, 0);
+                    rb[h][s] = make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
+                }
+            }
+        };
+        // diagonal of this thread in either half: outputs (o = c + k, k), k = 0 .. KW-1, 0 <= o < nq
+        const int c = td - (AV_KW - 1);
+        const bool diag = td < QW + AV_KW - 1;
+        const float* dsrc = Pst + c * AV_RS;                    // half h: row c + j, column KW h + j: + KW h + j (RS + 1)
+        float* adst0 = At + c;                                  // A[h][kk][o]: + h AT + kk QW + k
+        auto half = [&](auto h_c) __attribute__((always_inline)) {
+            constexpr int H = decltype(h_c)::value;
+#pragma unroll
+            for (int s = 0; s < NB; ++s)
+                if (NP * (s + 1) <= AV_BT / 4 || td + NP * s < AV_BT / 4)
+                    *reinterpret_cast<float4*>(Bt + H * AV_BT + 4 * (td + NP * s)) = rb[H][s];
+            if (diag) {
+                float* adst = adst0 + H * Cfg::AT;
+                float xa2[AV_KW], xb2[AV_KW], ya[AV_KW], yb[AV_KW];
+#pragma unroll
+                for (int dyi = 0; dyi < 4; ++dyi) {
+                    float d[AV_KW + 3];
+#pragma unroll
+                    for (int j = 0; j < AV_KW + 3; ++j) d[j] = dsrc[dyi * NRB * AV_RS + AV_KW * H + j * (AV_RS + 1)];
+#pragma unroll
+                    for (int k = 0; k < AV_KW; ++k) {
+                        const float pr = d[k + 1] + d[k + 2];
+                        const float xa = pr + d[k + 3], xb = pr + d[k];
+                        if (dyi == 0) { xa2[k] = xa; xb2[k] = xb; }
+                        else if (dyi == 1) { ya[k] = xa; yb[k] = xb; }
+                        else if (dyi == 2) {
+                            ya[k] = ya[k] + xa; yb[k] = yb[k] + xb;
+                            if ((unsigned)(c + k) < (unsigned)nq) {
+                                adst[(2 * AV_KW + k) * QW + k] = ya[k] + xa2[k];     // (B, A)
+                                adst[(3 * AV_KW + k) * QW + k] = yb[k] + xb2[k];     // (B, B)
+                            }
+                        } else if ((unsigned)(c + k) < (unsigned)nq) {
+                            adst[(0 * AV_KW + k) * QW + k] = ya[k] + xa;              // (A, A)
+                            adst[(1 * AV_KW + k) * QW + k] = yb[k] + xb;              // (A, B)
+                        }
+                    }
+                }
+            }
+        };
+        [[maybe_unused]] unsigned long long pt0 = AVPROBE_T();
+#pragma unroll 1
+        for (int step = 0; step < nsteps; ++step) {
+            issue_u();                                          // X: these waves' only work; the tiles are written in Y0 and Y1
+            __syncthreads();                                    // X | Y0: the staged blocks of this step are complete
+            AVPROBE_ADD(0, pt0);
+            half(std::integral_constant<int, 0>{});
+            AVPROBE_ADD(1, pt0);
+            __syncthreads();
+            AVPROBE_ADD(2, pt0);
+            half(std::integral_constant<int, 1>{});
+            next_step();
+            AVPROBE_ADD(3, pt0);
+            __syncthreads();
+            AVPROBE_ADD(4, pt0);
+        }
+        AVPROBE_OUT(1);
+        return;
+    }
+
+    // ================= consumers =================
+    const int cw = w - 2 * NP / 64, wm = cw >> 1, wn = cw & 1, li = lane & 31, lh = lane >> 5;
     f32x16 acc[3];
 #pragma unroll
     for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
-
-    // diagonal of this thread: outputs (o = c + k, k), k = 0 .. KW-1, 0 <= o < nq
-    const int c = t - (AV_KW - 1);
-    const bool diag = t < QW + AV_KW - 1;
-    const float* dsrc = Pst + c * AV_RS;                        // row c + j, column j: + j (RS + 1)
-    float* adst = At + c;                                       // A[kk][o]: + kk QW + k
-    // fragments: lane (li, lh) reads A[kk = 2 s + lh][o = wm 96 + mi 32 + li], U[kk][wn 32 + li]
+    // fragments: lane (li, lh) reads A[h][kk = 2 s + lh][o = wm 96 + mi 32 + li], U[h][kk][wn 32 + li]
     const float* fa = At + lh * QW + wm * 96 + li;
     const float* fb = Bt + lh * AV_C + wn * 32 + li;
-
-    const int nsteps = nr * p.nch;
-    int trow = 0, ch = 0;
-    int gy = gyb + oy % nr, gx0 = 0;
-    issue_loads(gy, gx0);
-#pragma unroll 1
-    for (int step = 0; step < nsteps; ++step) {
-        // ---- T phase ----
-        const bool edge = gy < 3 || gy >= p.Hh || gx0 < 3 || gx0 + AV_KW - 1 >= p.Wh;
-        if (edge) stage(gy, gx0, std::integral_constant<bool, true>{});
-        else stage(gy, gx0, std::integral_constant<bool, false>{});
-        __syncthreads();
-        // the U tile: its last reads (M phase of the previous step) are behind the barrier above
+    [[maybe_unused]] unsigned long long ct0 = AVPROBE_T();
+    // One step: the 2 x 20 k-pairs (entry e = half * 20 + k-pair) with the fragments read AV_PF entries ahead of their MFMAs, in fenced
+    // groups of two (the scheduler otherwise sinks every read to just in front of its MFMA and waits for it there).  NBAR barriers on
+    // the way: behind entry SA - 1 (Y1 | X: completes half 1, which is first read behind it) and behind entry 20 + SB - 1 (X | Y0).
+    auto mma_step = [&](auto nbar_c) __attribute__((always_inline)) {
+        constexpr int NBAR = decltype(nbar_c)::value, NE = 2 * AV_KP;
+        float a[NE][3], b[NE];
+        auto ld = [&](int e) __attribute__((always_inline)) {
+            const int h = e / AV_KP, kp = e - h * AV_KP;
+            b[e] = fb[h * AV_BT + 2 * kp * AV_C];
 #pragma unroll
-        for (int s = 0; s < NB; ++s) *reinterpret_cast<float4*>(Bt + 4 * (t + NT * s)) = rb[s];
-        if (diag) {
-            float xa2[AV_KW], xb2[AV_KW], ya[AV_KW], yb[AV_KW];
+            for (int mi = 0; mi < 3; ++mi) a[e][mi] = fa[h * Cfg::AT + 2 * kp * QW + mi * 32];
+        };
 #pragma unroll
-            for (int dyi = 0; dyi < 4; ++dyi) {
-                float d[AV_RS];
+        for (int e = 0; e < AV_PF; ++e) ld(e);
 #pragma unroll
-                for (int j = 0; j < AV_RS; ++j) d[j] = dsrc[dyi * NRB * AV_RS + j * (AV_RS + 1)];
+        for (int e = 0; e < NE; e += 2) {
+            if (e + AV_PF < NE) { ld(e + AV_PF); ld(e + AV_PF + 1); }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = 0; k < AV_KW; ++k) {
-                    const float pr = d[k + 1] + d[k + 2];
-                    const float xa = pr + d[k + 3], xb = pr + d[k];
-                    if (dyi == 0) { xa2[k] = xa; xb2[k] = xb; }
-                    else if (dyi == 1) { ya[k] = xa; yb[k] = xb; }
-                    else if (dyi == 2) {
-                        ya[k] = ya[k] + xa; yb[k] = yb[k] + xb;
-                        if ((unsigned)(c + k) < (unsigned)nq) {
-                            adst[(2 * AV_KW + k) * QW + k] = ya[k] + xa2[k];     // (B, A)
-                            adst[(3 * AV_KW + k) * QW + k] = yb[k] + xb2[k];     // (B, B)
-                        }
-                    } else if ((unsigned)(c + k) < (unsigned)nq) {
-                        adst[(0 * AV_KW + k) * QW + k] = ya[k] + xa;              // (A, A)
-                        adst[(1 * AV_KW + k) * QW + k] = yb[k] + xb;              // (A, B)
-                    }
-                }
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int mi = 0; mi < 3; ++mi)
+                    acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e + u][mi], b[e + u], acc[mi], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (NBAR >= 1 && e + 2 == AV_SA) {
+                AVPROBE_ADD(0, ct0);
+                av_phase_barrier();
+                AVPROBE_ADD(1, ct0);
+            }
+            if (NBAR >= 2 && e + 2 == AV_KP + AV_SB) {
+                AVPROBE_ADD(2, ct0);
+                av_phase_barrier();
+                AVPROBE_ADD(3, ct0);
             }
         }
-        // next step's coordinates and loads
-        if (++ch == p.nch) { ch = 0; ++trow; }
-        const int ngy_ = gyb + (trow + oy) % nr, ngx0 = ch * AV_KW;
+    };
+    if (nsteps > 0) {                                           // X and Y0 of step 0: nothing to consume yet
+        av_phase_barrier();
         __syncthreads();
-        // ---- M phase ----
-        if (step + 1 < nsteps) issue_loads(ngy_, ngx0);
-#pragma unroll
-        for (int kp = 0; kp < AV_NCOL / 2; ++kp) {
-            const float b = fb[2 * kp * AV_C];
-#pragma unroll
-            for (int mi = 0; mi < 3; ++mi)
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[2 * kp * QW + mi * 32], b, acc[mi], 0, 0, 0);
-        }
-        gy = ngy_; gx0 = ngx0;
     }
+    ct0 = AVPROBE_T();
+#pragma unroll 1
+    for (int step = 0; step + 1 < nsteps; ++step) {
+        mma_step(std::integral_constant<int, 2>{});
+        AVPROBE_ADD(4, ct0);
+        __syncthreads();                                        // Y0 | Y1: tiles 0 of the next step are complete, tiles 1 are free
+        AVPROBE_ADD(5, ct0);
+    }
+    if (nsteps > 0) mma_step(std::integral_constant<int, 1>{}); // the last step: the producers leave behind their Y1
+    AVPROBE_OUT(2);
 
     // part[quarter][o][col]: D[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     float* dst = p.part + ((size_t)quarter * HWp + (size_t)oy * p.Wp + x0) * AV_C + wn * 32 + li;
@@ -238,6 +379,8 @@ __global__ __launch_bounds__(AvCfg<QW>::NT) void csa_attn_v4_kernel(CsaAv4P p) {
             if (row < nq) dst[(size_t)row * AV_C] = acc[mi][r];
         }
 }
+#undef AVPROBE_ADD
+#undef AVPROBE_OUT
 
 
 // V columns of the edge-rule contractions, Ve[l][blk * C + co]: blk 0..3 top (dy = 0, dx = blk - 2, tap rows {0}, columns R(dx)),
@@ -326,7 +469,7 @@ int csa_attn_v4_f32(const float* S, int Lld, const float* stats2, const float* P
     p.Hp = Hp; p.Wp = Wp; p.Hh = Hp / 2; p.Wh = Wp / 2; p.Lld = Lld;
     const int qw = tile128 ? 96 : 192;
     p.nseg = ceil_div(Wp, qw);
-    p.nch = ceil_div(p.Wh + 3, AV_KW);
+    p.nch = ceil_div(p.Wh + 3, AV_SW);
     p.n_wg = Hp * p.nseg * 4;
     p.s_bytes = (unsigned)((size_t)Hp * Wp * Lld * sizeof(float));
     p.pc_bytes = (unsigned)((size_t)(p.Hh + 3) * (p.Wh + 3) * 9 * C * sizeof(float));
@@ -356,3 +499,9 @@ int csa_attn_v4_combine(const float* part, const float* Otop, const float* Oleft
 }
 
 }  // namespace ciaosr
+
+#ifdef CIAOSR_PROBE
+extern "C" int ciaosr_debug_probe_av4_read(unsigned long long* host, int n_words) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(ciaosr::g_avprobe), (size_t)n_words * 8) == hipSuccess ? 0 : -1;
+}
+#endif
