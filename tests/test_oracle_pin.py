@@ -114,6 +114,23 @@ def test_csattn_c64(tag):
     assert (y[0] - _t(fx['out'])).abs().max() < TOL
 
 
+@pytest.mark.parametrize('tag', ['48', '45x51', '64x64', '67x70'])
+def test_csattn_c64_float64(tag):
+    """The float64 run of the oracle that the GPU tests use as their reference at sizes without a fixture (tests/independent_refs.py::
+    csattn_oracle64, test_csattn_oracle_gpu.py) against the reference's fp32 outputs: measured 2.6e-6 .. 4.0e-6 at an output scale of
+    about 1.8 (the fixtures' own fp32 round-off), bound 1e-5."""
+    from tests import independent_refs as refs
+    fx = load_golden('csattn_c64_' + tag)
+    h, w = [int(v) for v in fx['shape']]
+    att = refs.csattn_module(64, seed=int(fx['weight_seed']), gain=float(fx['gain']))
+    assert state_dict_sha256(att) == str(fx['sha'])
+    y = refs.csattn_oracle64(att, randn((1, 64, h, w), fx['in_seed']))
+    assert y.dtype == torch.float64
+    err = (y[0] - _t(fx['out']).double()).abs().max().item()
+    print(f'float64 oracle vs csattn_c64_{tag}: max|d| {err:.2e} (scale {np.abs(fx["out"]).max():.3f})')
+    assert err < 1e-5
+
+
 @pytest.mark.slow
 def test_head_c64_x4():
     """Full-size head (Q = 36 864) against the reference, both in float64: an fp32 run of this head moves by ~2e-4 with the sgemm
