@@ -47,7 +47,7 @@ class OptionsT(C.Structure):
     _fields_ = [('head_route', C.c_int), ('csa_composed_min', C.c_int), ('dense_min_tiles', C.c_int),
                 ('scatter_small_max', C.c_int), ('kv_rows', C.c_int), ('decode_rows', C.c_int), ('bf16_single', C.c_int),
                 ('dense_direct', C.c_int), ('csa_scores_gemm', C.c_int), ('csa_attn_tile128', C.c_int), ('query_grid_w', C.c_int), ('f16_pairs', C.c_int),
-                ('csa_attn_v16', C.c_int)]
+                ('csa_attn_v16', C.c_int), ('csa_block_mb', C.c_int)]
 
 
 HEAD_STAGED, HEAD_NO_LOGIT_TABLE, HEAD_TABLE_GEMM, HEAD_WIDE_WG, HEAD_TABLE_WINO2, HEAD_NO_CHAIN, HEAD_NO_DECODE_CHAIN = 1, 2, 4, 8, 16, 32, 64
@@ -106,6 +106,8 @@ SIGNATURES = {
     'ciaosr_patch_rows_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _F, _P]),
     'ciaosr_cs_attn_workspace_bytes': (_S, [_I, _I, _I]),
     'ciaosr_cs_attn_workspace_bytes_scale': (_S, [_I, _I, _I, _I]),
+    'ciaosr_cs_attn_workspace_bytes_opt': (_S, [_I, _I, _I, _I, _O]),
+    'ciaosr_cs_attn_block_rows': (_I, [_I, _I, _I, _I, _I, _O]),
     'ciaosr_cs_attn_f32': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
     'ciaosr_cs_attn_bf16': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
     'ciaosr_make_coord_cell_f32': (_I, [_P, _P, _I, _I, _P]),
@@ -136,6 +138,7 @@ SIGNATURES = {
     'ciaosr_mlp_forward_f16': (_I, [_P, _I, C.POINTER(MlpT), _I, _P, _I, _P, _S, _P]),
     'ciaosr_decode_residual_f32': (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
     'ciaosr_head_workspace_bytes': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I]),
+    'ciaosr_head_workspace_bytes_opt': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I, _O]),
     'ciaosr_head_forward_f32': (_I, [_P, _I, _I, C.POINTER(HeadWeightsT), C.POINTER(CsAttnWeightsT), _P, _P, _P,
                                      _I, _I, _P, _O, _P, _S, _P]),
     'ciaosr_head_forward_bf16': (_I, [_P, _I, _I, C.POINTER(HeadWeightsT), C.POINTER(CsAttnWeightsT), _P, _P, _P,

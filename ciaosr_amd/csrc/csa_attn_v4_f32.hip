@@ -85,6 +85,7 @@ __device__ unsigned long long g_avprobe[1024 * 48];
 struct CsaAv4P {
     const float* S; const float2* st; const float* Pc; float* part;
     int Hp, Wp, Hh, Wh, Lld, nseg, nch, n_wg;
+    int ys, oy0, noy;          // S holds the logit rows ys .. (s_bytes worth) of the map; the launch's items are the query rows oy0 .. oy0 + noy - 1
     unsigned s_bytes, pc_bytes;
 };
 
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(AvCfg<QW>::NT) void csa_attn_v4_kernel(CsaAv4P p) {
     const int q8 = p.n_wg >> 3, r8 = p.n_wg & 7;
     const int xcd = bid & 7, slot0 = bid >> 3;
     const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot0;
-    const int oy = lid % p.Hp, rest = lid / p.Hp;
+    const int oy = p.oy0 + lid % p.noy, rest = lid / p.noy;     // the global query row: the key-row walk below does not depend on the band
     const int seg = rest % p.nseg, quarter = rest / p.nseg;
     const int x0 = seg * QW, nq = min(QW, p.Wp - x0);
     const int ngy = p.Hh + 3, gyb = quarter * ngy / 4, nr = (quarter + 1) * ngy / 4 - gyb;
@@ -167,8 +168,9 @@ __global__ __launch_bounds__(AvCfg<QW>::NT) void csa_attn_v4_kernel(CsaAv4P p) {
 #pragma unroll
             for (int dyi = DY0; dyi < DY0 + 2; ++dyi) {
                 const int dy = dyi - 2;
-                // may be negative (rows above the grid, x-halo left of column 0): as unsigned it is past s_bytes (< 2 GiB) and reads 0
-                const int base = ((oy + dy) * p.Wp + x0 - 2) * p.Lld + (gy - 1 + dy) * p.Wh + gx0 - 3 + s_thread;
+                // may be negative (rows above the grid or the band, x-halo left of column 0): as unsigned it is past s_bytes (< 2 GiB) and
+                // reads 0.  A band holds every row of the map among oy - 2 .. oy + 1; the others have P = 0 (negm = -inf) whatever is read
+                const int base = ((oy + dy - p.ys) * p.Wp + x0 - 2) * p.Lld + (gy - 1 + dy) * p.Wh + gx0 - 3 + s_thread;
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
                     ra[dyi][i] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_s, (base + i * s_istep) * 4, 0, 0));
@@ -456,22 +458,28 @@ static inline int av_grid(long n) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
-bool csa_attn_v4_ok(int Hp, int Wp, int C, int Lld) {
-    return C == AV_C && Hp >= 4 && Wp >= 4 && (Hp & 1) == 0 && (Wp & 1) == 0 && (Lld & 3) == 0 &&
-           (size_t)Hp * Wp * Lld * sizeof(float) < 0x80000000ull;     // every offset the kernel forms (negative ones included) is < 2^32
+// s_rows: the logit rows S holds at a time (Hp, or a band of query rows with its halo)
+bool csa_attn_v4_ok(int Hp, int Wp, int C, int Lld, int s_rows) {
+    return C == AV_C && Hp >= 4 && Wp >= 4 && (Hp & 1) == 0 && (Wp & 1) == 0 && (Lld & 3) == 0 && s_rows >= 1 &&
+           (size_t)s_rows * Wp * Lld * sizeof(float) < 0x80000000ull;     // every offset the kernel forms (negative ones included) is < 2^32
 }
 
+// The items of query rows oy0 <= oy < oy1 from S = the logit rows ys .. ys + s_rows - 1 (every row of the map among oy0 - 2 .. oy1);
+// stats2 and part are whole-map arrays.  The whole map in one launch: ys = 0, s_rows = Hp, oy0 = 0, oy1 = Hp.
 int csa_attn_v4_f32(const float* S, int Lld, const float* stats2, const float* Pc, float* part, int Hp, int Wp, int C, bool tile128,
-                    hipStream_t s) {
-    CIAOSR_CHECK_ARG(S && stats2 && Pc && part && csa_attn_v4_ok(Hp, Wp, C, Lld) && aligned16(Pc) && aligned16(part));
+                    int ys, int s_rows, int oy0, int oy1, hipStream_t s) {
+    CIAOSR_CHECK_ARG(S && stats2 && Pc && part && csa_attn_v4_ok(Hp, Wp, C, Lld, s_rows) && aligned16(Pc) && aligned16(part));
+    CIAOSR_CHECK_ARG(0 <= oy0 && oy0 < oy1 && oy1 <= Hp && ys >= 0 && ys + s_rows <= Hp && ys <= (oy0 > 2 ? oy0 - 2 : 0) &&
+                     ys + s_rows >= (oy1 < Hp ? oy1 + 1 : Hp));
     CsaAv4P p;
     p.S = S; p.st = reinterpret_cast<const float2*>(stats2); p.Pc = Pc; p.part = part;
     p.Hp = Hp; p.Wp = Wp; p.Hh = Hp / 2; p.Wh = Wp / 2; p.Lld = Lld;
     const int qw = tile128 ? 96 : 192;
     p.nseg = ceil_div(Wp, qw);
     p.nch = ceil_div(p.Wh + 3, AV_SW);
-    p.n_wg = Hp * p.nseg * 4;
-    p.s_bytes = (unsigned)((size_t)Hp * Wp * Lld * sizeof(float));
+    p.ys = ys; p.oy0 = oy0; p.noy = oy1 - oy0;
+    p.n_wg = p.noy * p.nseg * 4;
+    p.s_bytes = (unsigned)((size_t)s_rows * Wp * Lld * sizeof(float));
     p.pc_bytes = (unsigned)((size_t)(p.Hh + 3) * (p.Wh + 3) * 9 * C * sizeof(float));
     ProfScope prof("csa_attn_v", s);
     if (tile128) {

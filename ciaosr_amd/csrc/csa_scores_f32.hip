@@ -28,9 +28,10 @@ constexpr unsigned kOobB = 0xFFFFFFF0u;
 
 struct BoxP {
     const float* M; int ldm; unsigned m_bytes; int Hp, Wp;      // query map [Hp*Wp][ldm], 32 channels
+    int y0, y1;                                                  // the band of query rows this launch scores: S holds rows y0 .. y1-1
     const float* R; int ldr; unsigned r_bytes; int Hl, Wl;      // key map [Hl*Wl][ldr]
     const float* nrm;                                            // [Hl*Wl] alpha / max(patch norm, floor)
-    float* S; int lds_; size_t s_floats;                         // [Hp*Wp][lds_]; s_floats: extent
+    float* S; int lds_; size_t s_floats;                         // [(y1-y0)*Wp][lds_]; s_floats: extent
     int pbx, lbx, n_lb, n_items;                                 // blocks per row of each map, key blocks in total, (query, key) block pairs
 };
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(512) void csa_scores_box_f32_kernel(BoxP p) {
         i32x4 fa[6][4];                                              // query-halo tiles: resident per query block
         i32x4 fbc[4], fbn[4];                                        // this wave's key-halo tile of the current / next item
         auto load_a = [&](int pb) {
-            const int py0 = (pb / p.pbx) * BSH, px0 = (pb % p.pbx) * BSW;
+            const int py0 = p.y0 + (pb / p.pbx) * BSH, px0 = (pb % p.pbx) * BSW;      // the halo reads M's rows outside the band too
 #pragma unroll
             for (int pt = 0; pt < 6; ++pt) {
                 const unsigned mo = row_off(32 * pt + li, BPN, py0, px0, p.Hp, p.Wp, p.ldm);
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(512) void csa_scores_box_f32_kernel(BoxP p) {
             if (it > i0) {
                 const int ci = it - 1, k = (ci - i0) & 1;
                 const int pb = item_pb(ci), lb = item_lb(ci);
-                const int py0 = (pb / p.pbx) * BSH, px0 = (pb % p.pbx) * BSW;
+                const int py0 = p.y0 + (pb / p.pbx) * BSH, px0 = (pb % p.pbx) * BSW;
                 const int ly = (lb / p.lbx) * BLH + lyy, lx = (lb % p.lbx) * BLW + lxx;
                 const bool l_ok = ly < p.Hl && lx < p.Wl;
                 const float sc = l_ok ? p.nrm[(size_t)ly * p.Wl + lx] : 0.f;
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(512) void csa_scores_box_f32_kernel(BoxP p) {
                 const unsigned lane_off = l_ok ? (unsigned)((size_t)ly * p.Wl + lx) * 4u : kOobB;
                 const int qy0 = py0 + (q0 >> 4);
                 // (the descriptor is based at this wave's first output row: S as a whole may exceed the 4 GiB a descriptor spans)
-                const size_t s_base = ((size_t)qy0 * p.Wp + px0) * p.lds_;                      // floats, wave-uniform
+                const size_t s_base = ((size_t)(qy0 - p.y0) * p.Wp + px0) * p.lds_;               // floats, wave-uniform
                 const size_t s_left = p.s_floats > s_base ? (p.s_floats - s_base) * 4 : 0;      // bytes up to the end of S
                 const size_t s_span = ((size_t)p.Wp + BSW) * p.lds_ * 4;                        // two output rows of this block
                 const __amdgpu_buffer_rsrc_t rs_s =
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(512) void csa_scores_box_f32_kernel(BoxP p) {
                     float s = dk[0][(pyy * BHW + pxx) * BDP];
 #pragma unroll
                     for (int e = 1; e < 9; ++e) s += dk[e][((pyy + e / 3) * BHW + pxx + e % 3) * BDP];     // same order as before: (a, b) row-major
-                    const bool row_ok = qy0 + pyy < p.Hp && px0 + pxx < p.Wp;           // wave-uniform
+                    const bool row_ok = qy0 + pyy < p.y1 && px0 + pxx < p.Wp;           // wave-uniform
                     const unsigned soff = (unsigned)(((size_t)pyy * p.Wp + pxx) * p.lds_ * 4);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(s * sc), rs_s, (int)(row_ok ? lane_off : kOobB), (int)(row_ok ? soff : 0u), 0);
                 }
@@ -195,26 +196,29 @@ __global__ __launch_bounds__(512) void csa_scores_box_f32_kernel(BoxP p) {
 
 bool csa_scores_box_ok(int Ch, int ldm, int ldr) { return Ch == 32 && (ldm & 3) == 0 && (ldr & 3) == 0; }
 
-// S[p][l] (row stride ld_s) = alpha <3x3 patch of M at p, 3x3 patch of R at l> / max(|patch of R at l|, floor); nrm: Hl*Wl floats scratch
-int csa_scores_box_f32(const float* M, int ldm, int Hp, int Wp, const float* R, int ldr, int Hl, int Wl, int Ch, float alpha, float floor_,
-                       float* nrm, float* S, int ld_s, hipStream_t s) {
-    CIAOSR_CHECK_ARG(M && R && nrm && S && csa_scores_box_ok(Ch, ldm, ldr) && aligned16(M) && aligned16(R));
+// nrm[l] = alpha / max(|3x3 patch of R at l|, floor): the per-key factor of the scores below
+int csa_key_norms(const float* R, int ldr, int Hl, int Wl, int Ch, float alpha, float floor_, float* nrm, hipStream_t s) {
+    CIAOSR_CHECK_ARG(R && nrm && csa_scores_box_ok(Ch, Ch, ldr));
+    ProfScope prof("csa_key_norms", s);
+    hipLaunchKernelGGL(csa_key_norms_kernel, dim3(ceil_div((long)Hl * Wl, 4)), dim3(256), 0, s, R, ldr, Hl, Wl, Ch, floor_, alpha, nrm);
+    return launch_status("csa_key_norms");
+}
+
+// S[p - y0 Wp][l] (row stride ld_s) = <3x3 patch of M at p, 3x3 patch of R at l> nrm[l] for the query rows y0 <= y < y1 of the Hp x Wp map
+// (the whole map: y0 = 0, y1 = Hp).  A score does not depend on the band it is computed in: its nine products are summed in (a, b) order.
+int csa_scores_box_f32(const float* M, int ldm, int Hp, int Wp, const float* R, int ldr, int Hl, int Wl, int Ch, const float* nrm, float* S,
+                       int ld_s, int y0, int y1, hipStream_t s) {
+    CIAOSR_CHECK_ARG(M && R && nrm && S && csa_scores_box_ok(Ch, ldm, ldr) && aligned16(M) && aligned16(R) && 0 <= y0 && y0 < y1 && y1 <= Hp);
     const size_t mb = (size_t)Hp * Wp * ldm * 4, rb = (size_t)Hl * Wl * ldr * 4;
-    const size_t s_floats = ((size_t)Hp * Wp - 1) * ld_s + (size_t)Hl * Wl;
+    const size_t s_floats = ((size_t)(y1 - y0) * Wp - 1) * ld_s + (size_t)Hl * Wl;
     CIAOSR_CHECK_ARG(mb < 0xFFFFFF00ull && rb < 0xFFFFFF00ull && ((size_t)Wp + BSW) * ld_s * 4 < 0xFFFFFF00ull);
-    {
-        ProfScope prof("csa_key_norms", s);
-        hipLaunchKernelGGL(csa_key_norms_kernel, dim3(ceil_div((long)Hl * Wl, 4)), dim3(256), 0, s, R, ldr, Hl, Wl, Ch, floor_, alpha, nrm);
-    }
-    int rc = launch_status("csa_key_norms");
-    if (rc != CIAOSR_OK) return rc;
     BoxP p;
-    p.M = M; p.ldm = ldm; p.m_bytes = (unsigned)mb; p.Hp = Hp; p.Wp = Wp;
+    p.M = M; p.ldm = ldm; p.m_bytes = (unsigned)mb; p.Hp = Hp; p.Wp = Wp; p.y0 = y0; p.y1 = y1;
     p.R = R; p.ldr = ldr; p.r_bytes = (unsigned)rb; p.Hl = Hl; p.Wl = Wl;
     p.nrm = nrm; p.S = S; p.lds_ = ld_s; p.s_floats = s_floats;
     p.pbx = ceil_div(Wp, BSW); p.lbx = ceil_div(Wl, BLW);
     p.n_lb = ceil_div(Hl, BLH) * p.lbx;
-    const long n_items = (long)ceil_div(Hp, BSH) * p.pbx * p.n_lb;
+    const long n_items = (long)ceil_div(y1 - y0, BSH) * p.pbx * p.n_lb;
     CIAOSR_CHECK_ARG(n_items < 0x7FFFFFFF);
     p.n_items = (int)n_items;
     CIAOSR_BIG_LDS(csa_scores_box_f32_kernel, kBoxLds);

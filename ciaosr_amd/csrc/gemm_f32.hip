@@ -365,7 +365,7 @@ int gemm_f32_splitk(const float* A, int lda, const float* B, int ldb, bool b_kn,
 
 int gemm_f32(const float* A, int lda, const float* B, int ldb, bool b_kn, float* C, int ldc,
              const float* bias, int M, int N, int K, float alpha, int act, float slope,
-             hipStream_t stream, const char* tag) {
+             hipStream_t stream, const char* tag, int plan_rows) {
     if (M <= 0 || N <= 0) return CIAOSR_OK;
     CIAOSR_CHECK_ARG(K > 0 && A && B && C);
     CIAOSR_CHECK_ARG((lda & 3) == 0 && (ldb & 3) == 0);
@@ -374,9 +374,10 @@ int gemm_f32(const float* A, int lda, const float* B, int ldb, bool b_kn, float*
         // A spans more than one buffer descriptor (4 GiB): rows are independent, so run row blocks (multiples of the row tile while
         // there are that many rows; a strided row set -- one row per image line -- may have to go down to single rows)
         const int half = M > BM ? (M / 2 + BM - 1) / BM * BM : (M + 1) / 2;
-        const int rc = gemm_f32(A, lda, B, ldb, b_kn, C, ldc, bias, half, N, K, alpha, act, slope, stream, tag);
+        const int rc = gemm_f32(A, lda, B, ldb, b_kn, C, ldc, bias, half, N, K, alpha, act, slope, stream, tag, plan_rows);
         if (rc != CIAOSR_OK) return rc;
-        return gemm_f32(A + (size_t)half * lda, lda, B, ldb, b_kn, C + (size_t)half * ldc, ldc, bias, M - half, N, K, alpha, act, slope, stream, tag);
+        return gemm_f32(A + (size_t)half * lda, lda, B, ldb, b_kn, C + (size_t)half * ldc, ldc, bias, M - half, N, K, alpha, act, slope, stream, tag,
+                        plan_rows);
     }
     GemmP p;
     p.A = A; p.B = B; p.C = C; p.bias = bias;
@@ -400,7 +401,7 @@ int gemm_f32(const float* A, int lda, const float* B, int ldb, bool b_kn, float*
 #ifndef CIAOSR_GEMM32_TN1
     if (p.kt_per_split <= 24 && act == CIAOSR_ACT_NONE) {
         tn = ceil_div(CIAOSR_GEMM32_TNK, p.kt_per_split);
-        while (tn > 1 && (long)ceil_div(M, BM) * ceil_div(p.tiles_n, tn) < 2048) --tn;
+        while (tn > 1 && (long)ceil_div(plan_rows > M ? plan_rows : M, BM) * ceil_div(p.tiles_n, tn) < 2048) --tn;
     }
 #endif
     p.tn_per_wg = tn; p.groups_n = ceil_div(p.tiles_n, tn);
@@ -512,5 +513,5 @@ extern "C" int ciaosr_gemm_f32(const float* A, int lda, const float* B, int ldb,
                                int ldc, const float* bias, int M, int N, int K, float alpha, int act,
                                float slope, void* stream) {
     return ciaosr::gemm_f32(A, lda, B, ldb, b_is_kn != 0, C, ldc, bias, M, N, K, alpha, act, slope,
-                            (hipStream_t)stream, nullptr);
+                            (hipStream_t)stream, nullptr, 0);
 }

@@ -526,16 +526,17 @@ static int launch_gemm16(Gemm16P& p, int mt, hipStream_t s) {
 }
 
 int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int ldb, void* C, int ldc, bool c_bf16, int M, int N,
-                 int K, float alpha, hipStream_t s, const char* tag) {
+                 int K, float alpha, hipStream_t s, const char* tag, int plan_rows) {
     if (M <= 0 || N <= 0) return CIAOSR_OK;
     CIAOSR_CHECK_ARG(A && B && C && K > 0 && (K & 7) == 0);
     CIAOSR_CHECK_ARG((lda & 7) == 0 && (ldb & 7) == 0 && (ldc & 3) == 0 && aligned16(A) && aligned16(B) && aligned16(C));
     if (((size_t)(M - 1) * lda + K) * 2 >= 0xFFFFFF00ull && M > GM) {       // A past one buffer descriptor (4 GiB): independent row blocks
         const int half = (M / 2 + GM - 1) / GM * GM;
         const size_t c_row = (size_t)ldc * (c_bf16 ? 2 : 4);
-        const int rc = gemm_h16_nt(A, lda, B, ldb, C, ldc, c_bf16, half, N, K, alpha, s, tag);
+        const int rc = gemm_h16_nt(A, lda, B, ldb, C, ldc, c_bf16, half, N, K, alpha, s, tag, plan_rows);
         if (rc != CIAOSR_OK) return rc;
-        return gemm_h16_nt(A + (size_t)half * lda, lda, B, ldb, static_cast<char*>(C) + (size_t)half * c_row, ldc, c_bf16, M - half, N, K, alpha, s, tag);
+        return gemm_h16_nt(A + (size_t)half * lda, lda, B, ldb, static_cast<char*>(C) + (size_t)half * c_row, ldc, c_bf16, M - half, N, K, alpha, s, tag,
+                           plan_rows);
     }
     Gemm16P p;
     p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.c_bf16 = c_bf16 ? 1 : 0;
@@ -548,6 +549,7 @@ int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int l
     p.tiles_n = ceil_div(N, GN);
     ProfScope prof(tag ? tag : "gemm" CIAOSR_H16_SUFFIX, s);
     // big plain GEMMs (the operand stream from L2 bounds the narrow tile): 192 x 256 tiles, eight waves, where they fill the chip
+    const int Mp = plan_rows > M ? plan_rows : M;        // the kernel and its row tile are chosen for the whole problem (ops.h: plan_rows)
     const long wide_tiles = (long)ceil_div(M, 192) * ceil_div(N, WN);
 #ifdef CIAOSR_PROBE       // developer A/B only: the product library reads no environment
     static const bool narrow_only = getenv("CIAOSR_GEMM16_NARROW") != nullptr;
@@ -555,7 +557,7 @@ int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int l
     constexpr bool narrow_only = false;
 #endif
     // (deep K only: at K = 576 -- the logit table's slices -- one workgroup per CU hides its 18 k-tiles' prologue worse than two: 45 vs 39 us)
-    if (N % WN == 0 && K >= 2048 && wide_tiles >= 256 && !narrow_only) {
+    if (N % WN == 0 && K >= 2048 && (long)ceil_div(Mp, 192) * ceil_div(N, WN) >= 256 && !narrow_only) {
         p.tiles_n = N / WN;
         p.n_wg = (int)wide_tiles;
         const size_t lds = (size_t)WNS * 32 * 1024;
@@ -563,7 +565,7 @@ int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int l
         hipLaunchKernelGGL((gemm_h16_wide_kernel<3>), dim3(p.n_wg), dim3(512), lds, s, p);
         return launch_status("gemm_wide" CIAOSR_H16_SUFFIX);
     }
-    const int rc = launch_gemm16<0>(p, pick_mt(M, p.tiles_n), s);
+    const int rc = launch_gemm16<0>(p, pick_mt(Mp, p.tiles_n), s);
     if (rc != CIAOSR_OK) return rc;
     return launch_status("gemm" CIAOSR_H16_SUFFIX);
 }
@@ -863,7 +865,7 @@ __global__ void softmax_stats_merge_kernel(const float2* __restrict__ part, int 
 size_t softmax_gemm_scratch_floats(long M, int N) { return (size_t)M * (2 * (size_t)ceil_div(N, GN) + 1) * 2 + 64; }
 
 int softmax_gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int ldb, unsigned short* P, int ldp, int M, int N, int K,
-                        float alpha, float* scratch, size_t scratch_floats, hipStream_t s, const char* tag) {
+                        float alpha, float* scratch, size_t scratch_floats, hipStream_t s, const char* tag, int plan_rows) {
     if (M <= 0 || N <= 0) return CIAOSR_OK;
     CIAOSR_CHECK_ARG(A && B && P && scratch && K > 0 && (K & 7) == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && (ldp & 7) == 0 && ldp >= N);
     CIAOSR_CHECK_ARG(aligned16(A) && aligned16(B) && aligned16(P) && aligned16(scratch) && scratch_floats >= softmax_gemm_scratch_floats(M, N));
@@ -884,7 +886,7 @@ int softmax_gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* 
     p.stats = stats;
     p.npad = (int)round_up((size_t)N, 8) <= ldp ? (int)round_up((size_t)N, 8) : ldp;
     ProfScope prof(tag, s);
-    const int mt = pick_mt(M, p.tiles_n);
+    const int mt = pick_mt(plan_rows > M ? plan_rows : M, p.tiles_n);
     int rc = launch_gemm16<1>(p, mt, s);
     if (rc != CIAOSR_OK) return rc;
     hipLaunchKernelGGL(softmax_stats_merge_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, s, p.part, p.n_part, (long)M, stats);

@@ -22,7 +22,7 @@ constexpr int kQkChunk = 65536;  // rows of (q*key) products materialised at a t
 
 static int n_samples(int local_size) { return local_size == 1 ? 1 : (local_size == 2 ? 4 : 9); }
 
-static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q) {
+static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt) {
     HeadPlan p;
     p.H = H; p.W = W; p.C = w->channels; p.Cn = w->nonlocal_channels;
     p.D = (w->no_unfold ? 1 : 9) * p.C; p.Dv = p.D + p.Cn; p.J = n_samples(w->local_size); p.HW = H * W;
@@ -37,7 +37,15 @@ static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q) {
     p.qcf = Q < (1 << 20) ? Q : (1 << 20);
     const long zcap = (long)(0xE0000000ull / ((size_t)p.Dv * sizeof(float)));      // Z is addressed through a 32-bit buffer descriptor
     if (p.qcf > zcap) p.qcf = (int)zcap;
-    p.csa_bytes = p.Cn > 0 ? ciaosr_cs_attn_workspace_bytes_scale(H, W, p.C, w->nonlocal_max_scale ? w->nonlocal_max_scale : 2) : 0;
+    const int max_sc = w->nonlocal_max_scale ? w->nonlocal_max_scale : 2;
+    p.csa_bytes = p.Cn > 0 ? ciaosr_cs_attn_workspace_bytes_scale(H, W, p.C, max_sc) : 0;
+    if (p.Cn > 0 && opt && opt->csa_block_mb > 0) {         // cs_attn in bands: the largest of the scales' sizes (a band's S does not grow with the scale)
+        p.csa_bytes = 0;
+        for (int sc = 2; sc <= (max_sc < 2 || max_sc > 4 ? 4 : max_sc); ++sc) {
+            const size_t n = ciaosr_cs_attn_workspace_bytes_opt(H, W, p.C, sc, opt);
+            p.csa_bytes = n > p.csa_bytes ? n : p.csa_bytes;
+        }
+    }
     return p;
 }
 
@@ -121,7 +129,11 @@ using namespace ciaosr;
 
 extern "C" size_t ciaosr_head_workspace_bytes(int H, int W, const ciaosr_head_weights_t* w, int Q) {
     if (!w || H <= 0 || W <= 0 || Q <= 0) return 0;
-    return head_ws_bytes(head_plan(H, W, w, Q));
+    return head_ws_bytes(head_plan(H, W, w, Q, nullptr));
+}
+extern "C" size_t ciaosr_head_workspace_bytes_opt(int H, int W, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt) {
+    if (!w || H <= 0 || W <= 0 || Q <= 0 || !options_ok(opt)) return 0;
+    return head_ws_bytes(head_plan(H, W, w, Q, opt));
 }
 
 static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w,
@@ -144,7 +156,7 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
     CIAOSR_CHECK_ARG(mlp_ok(w->q) && mlp_ok(w->k) && mlp_ok(w->v));
     CIAOSR_CHECK_ARG((w->nonlocal_channels > 0) == (csattn != nullptr));
     hipStream_t s = (hipStream_t)stream_;
-    const HeadPlan p = head_plan(H, W, w, Q);
+    const HeadPlan p = head_plan(H, W, w, Q, opt);
     // dims wiring of LocalImplicitSRNet.__init__ (ciaosr_net.py:61-76)
     CIAOSR_CHECK_ARG(w->k.in_dim == p.D + 4 && w->k.width[w->k.n_layers - 1] == p.D);
     CIAOSR_CHECK_ARG(w->v.in_dim == p.Dv + 4 && w->v.width[w->v.n_layers - 1] == p.Dv);
@@ -251,7 +263,7 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
             RUN(qk_rows(U, p.Dv, p.D, H, W, r0, nr, w->k.bias[last], QK, G, kLdG, table16 ? (int)prec : 0, s));
             if (table16) {
                 RUN(h16_ops(prec).gemm_nt(reinterpret_cast<const unsigned short*>(QK), p.D, W5T, p.D, G + (size_t)r0 * kLdG, kLdG, false, nr,
-                                          256, p.D, 1.f, s, prec == kF16 ? "head_logit_table_f16" : "head_logit_table_bf16"));
+                                          256, p.D, 1.f, s, prec == kF16 ? "head_logit_table_f16" : "head_logit_table_bf16", 0));
                 continue;
             }
             // G[r][n] = sum_d QK[r][d] * W5k[d][n]: the Linear weight [D][256] is the [K][N] operand as stored

@@ -47,8 +47,11 @@ struct DecodeP {
 };
 
 // gemm_f32.hip
+// plan_rows > 0: A is a block of rows of a plan_rows-row problem (cs_attn's bands of query rows); everything a launch derives from the
+// number of rows that could change an output's value or summation order is then derived from plan_rows, so a row's result does not
+// depend on the block it is computed in
 int gemm_f32(const float* A, int lda, const float* B, int ldb, bool b_kn, float* C, int ldc, const float* bias,
-             int M, int N, int K, float alpha, int act, float slope, hipStream_t stream, const char* tag);
+             int M, int N, int K, float alpha, int act, float slope, hipStream_t stream, const char* tag, int plan_rows = 0);
 int gemm_f32_splitk(const float* A, int lda, const float* B, int ldb, bool b_kn, float* C, int ldc, const float* bias,
                     int M, int N, int K, float alpha, int act, float slope, float* partial, size_t partial_floats,
                     hipStream_t stream, const char* tag);
@@ -77,8 +80,9 @@ int wino_table_f32(const float* Pi, int H, int W, const float* frag_wino, int n_
 int wino4_table_f32(const float* Pi, int H, int W, const float* frag_wino4, int n_blk, float* out, int ldg, hipStream_t s);   // dense_wino4_f32.hip
 // csa_scores_f32.hip: fp32 cs_attn correlation scores as a 3x3 diagonal box sum of the per-pixel correlation (Ch = 32)
 bool csa_scores_box_ok(int Ch, int ldm, int ldr);
-int csa_scores_box_f32(const float* M, int ldm, int Hp, int Wp, const float* R, int ldr, int Hl, int Wl, int Ch, float alpha, float floor_,
-                       float* nrm, float* S, int ld_s, hipStream_t s);
+int csa_key_norms(const float* R, int ldr, int Hl, int Wl, int Ch, float alpha, float floor_, float* nrm, hipStream_t s);
+int csa_scores_box_f32(const float* M, int ldm, int Hp, int Wp, const float* R, int ldr, int Hl, int Wl, int Ch, const float* nrm, float* S,
+                       int ld_s, int y0, int y1, hipStream_t s);     // query rows y0 <= y < y1 into S[(y - y0) Wp + x]
 // conv1x1_f32.hip: weights-resident fp32 1x1 convolution to 64 channels (the RDB local feature fusion on big maps)
 bool conv1x1_resident_ok(long M, int N, int K, int ldx, int ldw);
 int conv1x1_resident_f32(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* res, int ldres, float* dst,
@@ -95,6 +99,7 @@ int pad_reflect(const float* src, int ld_src, int H, int W, int C, float* dst, i
 int avgpool2(const float* src, int Hp, int Wp, int C, float* dst, hipStream_t s);
 int patch_rows(const float* src, int ld_src, int Hs, int Ws, int Cs, int k, int stride, int pad, int OH, int OW,
                float* out, int ld_out, int normalize, float floor_, hipStream_t s, const char* tag);
+int copy_rows(const float* src, long row_stride, int nrows, int cols, float* dst, int ld_dst, hipStream_t s, const char* tag);
 int softmax_rows(float* S, long rows, int L, int ld, hipStream_t s);
 int softmax_stats_rows(const float* S, long rows, int L, int ld, float* stats2 /* [rows] (max * log2 e, 1 / sum) */, hipStream_t s);
 int fold(const float* O, int ldo, int Hp, int Wp, int C, float* Y, hipStream_t s);
@@ -106,9 +111,9 @@ int csa_gather_out(const float* Op, const float* Otop, const float* Oleft, const
 int csa_gather_vprime_t_h16(const float* Pc, int Hh, int Wh, int C, unsigned short* VpT, int ldt, bool f16, hipStream_t s);
 // csa_attn_v4_f32.hip: fp32 attn.V of the composed tail on the four diagonal tap blocks (C = 64): part[4][HpWp][64] partial sums,
 // the edge-rule V columns Ve[L][9C] (top 4C, left 4C, corner C: tap 0 instead of {1,2}) and the combine into out
-bool csa_attn_v4_ok(int Hp, int Wp, int C, int Lld);
+bool csa_attn_v4_ok(int Hp, int Wp, int C, int Lld, int s_rows);
 int csa_attn_v4_f32(const float* S, int Lld, const float* stats2, const float* Pc, float* part, int Hp, int Wp, int C, bool tile128,
-                    hipStream_t s);
+                    int ys, int s_rows, int oy0, int oy1, hipStream_t s);
 int csa_gather_vedge(const float* Pc, int Hh, int Wh, int C, float* Ve, hipStream_t s);
 int csa_attn_v4_combine(const float* part, const float* Otop, const float* Oleft, const float* Otl, const float* bd, int H, int W, int Hp,
                         int Wp, int C, float* out, int ld_out, hipStream_t s);
@@ -182,7 +187,7 @@ int head_decode_fused(const FusedQP& p, hipStream_t s);
 // (h16_util.h): the same functions exist in ciaosr::b16 (bf16) and ciaosr::f16 (IEEE half).
 #define CIAOSR_H16_DECLS                                                                                                              \
     int gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int ldb, void* C, int ldc, bool c_bf16, int M, int N,  \
-                    int K, float alpha, hipStream_t s, const char* tag);                                                              \
+                    int K, float alpha, hipStream_t s, const char* tag, int plan_rows /* as gemm_f32's; 0 = M */);                    \
     int cast_rows_h16(const float* src, int ld_src, unsigned short* dst, int ld_dst, long rows, int cols, hipStream_t s);             \
     int linear_h16(const unsigned short* A, int lda, const unsigned short* W16, int ldw, const float* bias, bool relu, void* C, int ldc,      \
                    bool c_16bit, int M, int N, int K, hipStream_t s, const char* tag);                                                      \
@@ -212,7 +217,8 @@ int head_decode_fused(const FusedQP& p, hipStream_t s);
     int cast_many_h16(const float* const* src, int n, int rows, int cols, unsigned short* dst, hipStream_t s);                       \
     size_t softmax_gemm_scratch_floats(long M, int N);                                                                                \
     int softmax_gemm_h16_nt(const unsigned short* A, int lda, const unsigned short* B, int ldb, unsigned short* P, int ldp, int M,    \
-                            int N, int K, float alpha, float* scratch, size_t scratch_floats, hipStream_t s, const char* tag);        \
+                            int N, int K, float alpha, float* scratch, size_t scratch_floats, hipStream_t s, const char* tag,         \
+                            int plan_rows);                                                                                           \
     int rows_to_f32_h16(const unsigned short* src, long ld_src, long row0, long row_stride, int nrows, int cols, float* dst,          \
                         int ld_dst, hipStream_t s);
 namespace b16 { CIAOSR_H16_DECLS }

@@ -599,6 +599,24 @@ int csa_gather_vprime_t_h16(const float* Pc, int Hh, int Wh, int C, unsigned sho
     return launch_status("csa_gather_vprime_t");
 }
 
+// dst[r][0 .. cols) = src[r * row_stride][0 .. cols): nrows rows of a matrix, every row_stride-th one, as a dense block (cols % 4 == 0)
+__global__ void copy_rows_kernel(const float* __restrict__ src, long row_stride, int nrows, int cols, float* __restrict__ dst, int ld_dst) {
+    const int c4n = cols >> 2;
+    const long n = (long)nrows * c4n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / c4n;
+        const int c = (int)(i - r * c4n) * 4;
+        *reinterpret_cast<float4*>(dst + (size_t)r * ld_dst + c) = *reinterpret_cast<const float4*>(src + (size_t)r * row_stride + c);
+    }
+}
+int copy_rows(const float* src, long row_stride, int nrows, int cols, float* dst, int ld_dst, hipStream_t s, const char* tag) {
+    CIAOSR_CHECK_ARG(src && dst && nrows > 0 && cols > 0 && (cols & 3) == 0 && (row_stride & 3) == 0 && (ld_dst & 3) == 0 && cols <= ld_dst &&
+                     aligned16(src) && aligned16(dst));
+    ProfScope prof(tag, s);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3(ew_grid((long)nrows * (cols >> 2))), dim3(256), 0, s, src, row_stride, nrows, cols, dst, ld_dst);
+    return launch_status("copy_rows");
+}
+
 int downsample(const float* src, int Hp, int Wp, int C, int scale, float* dst, hipStream_t s) {
     CIAOSR_CHECK_ARG(scale >= 2 && scale <= 4 && Hp % scale == 0 && Wp % scale == 0);
     ProfScope prof("avgpool2", s);

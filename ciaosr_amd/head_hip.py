@@ -327,7 +327,7 @@ class PackedHead:
                 hinted = self._grid_opts[key] = opt.replace(query_grid_w=gw)
             opt = hinted
         feat_hwc = feature_hwc if feature_hwc is not None else hip_ops.nchw_to_hwc(feature_chw)
-        nbytes = _lib.load().ciaosr_head_workspace_bytes(H, W, C.byref(st), Q)
+        nbytes = _lib.load().ciaosr_head_workspace_bytes_opt(H, W, C.byref(st), Q, opt.c_arg())
         ws = hip_ops.workspace(nbytes, coord.device)
         rgb = torch.empty(Q, 3, dtype=torch.float32, device=coord.device)
         _lib.call('ciaosr_head_forward_' + opt.suffix, hip_ops.ptr(feat_hwc), H, W,

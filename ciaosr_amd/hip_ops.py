@@ -73,15 +73,16 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def workspace(nbytes, device, slot='head'):
-    """Grow-only scratch buffer per (slot, device, stream): two streams or two devices never share scratch."""
+def workspace(nbytes, device, slot='head', exact=False):
+    """Grow-only scratch buffer per (slot, device, stream): two streams or two devices never share scratch.  `exact`: grow to nbytes
+    and no further (a caller that bounds its scratch on purpose: cs_attn under Options.csa_block_mb), else with 5 % of headroom."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     key = (slot, device.type, idx, torch.cuda.current_stream(idx).cuda_stream)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = None
         _workspaces[key] = None
-        buf = torch.empty(int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=device)
+        buf = torch.empty(int(nbytes) if exact else int(nbytes * 1.05) + 4096, dtype=torch.uint8, device=device)
         _workspaces[key] = buf
     return buf
 
@@ -263,7 +264,7 @@ class Options:
     the rest   fields of ciaosr_options_t (include/ciaosr_hip.h): result-equivalent route choices; 0 = default.
     Immutable; `replace()` returns a modified copy."""
     _C_FIELDS = ('head_route', 'csa_composed_min', 'dense_min_tiles', 'scatter_small_max', 'kv_rows', 'decode_rows', 'bf16_single', 'dense_direct', 'csa_scores_gemm', 'csa_attn_tile128', 'query_grid_w', 'f16_pairs',
-                 'csa_attn_v16')
+                 'csa_attn_v16', 'csa_block_mb')
     _MODE_FIELDS = ('precision', 'f16_pairs', 'bf16_single')
     __slots__ = ('mode', 'precision') + _C_FIELDS + ('_c',)
 

@@ -96,15 +96,15 @@ class CrossScaleAttention(nn.Module):
     @torch.no_grad()
     def forward(self, input, options=None):
         """[B,C,H,W] -> [B,C,H,W] like the reference module (batch items are independent,
-        arch_csnln.py:491).  `options`: hip_ops.Options (precision, csa_composed_min); None = fp32 defaults."""
+        arch_csnln.py:491).  `options`: hip_ops.Options (precision, csa_composed_min, csa_block_mb); None = fp32 defaults."""
         opt = hip_ops.as_options(options)
         x = input.contiguous().float()
         hip_ops.require_gpu(x)
         B, Cc, H, W = x.shape
         sts, _keep = self.packed()
         ns = len(self.scale)
-        nbytes = _lib.load().ciaosr_cs_attn_workspace_bytes_scale(H, W, Cc, max(self.scale))
-        ws = hip_ops.workspace(nbytes, x.device)
+        nbytes = max(_lib.load().ciaosr_cs_attn_workspace_bytes_opt(H, W, Cc, s_, opt.c_arg()) for s_ in self.scale)
+        ws = hip_ops.workspace(nbytes, x.device, exact=opt.csa_block_mb > 0)      # bounded scratch is the point of the option
         out = torch.empty(B, ns * Cc, H, W, dtype=torch.float32, device=x.device)       # torch.cat(res_y, dim=1), csa:528
         for b in range(B):
             f = hip_ops.nchw_to_hwc(x[b])

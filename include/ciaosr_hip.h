@@ -136,8 +136,15 @@ typedef struct ciaosr_options {
                              * gather from a handful of LR pixels.  Results do not depend on it; 0 = walk them in index order */
     int f16_pairs;          /* 0 to 3: selects a precision mode (table above) */
     int csa_attn_v16;       /* _f32 cs_attn, composed tail, 64 channels: 0 (default) = attn.V on the four diagonal tap blocks
-                             * (csa_attn_v4_f32.hip: K = 4 (Hp/2+3)(Wp/2+3) instead of 16 L; where the logit matrix is under 2 GiB);
+                             * (csa_attn_v4_f32.hip: K = 4 (Hp/2+3)(Wp/2+3) instead of 16 L; where the logit matrix -- under csa_block_mb: a band's -- is under 2 GiB);
                              * 1 = the 16C route of 16 offset columns.  Same products summed in another order */
+    int csa_block_mb;       /* cs_attn in bands of query rows: 0 (default) = off, the logit matrix S [Hp Wp][L] (and the 16-bit entries' probability
+                             * matrix P16) whole in the workspace; n > 0 = at most n MiB of score storage at a time -- one band's S rows plus, in
+                             * the _bf16 / _f16 entries, its P16 rows (ciaosr_cs_attn_block_rows names the band height).  Scores, softmax and
+                             * attn.V run per band, every other stage once; the route is chosen for a band, so maps whose whole S is past the
+                             * 2 GiB of the four-block route or the 4 GiB of a buffer descriptor keep the fast kernels.  Size the workspace
+                             * with the _opt functions.  The result does not depend on the band height where the same route runs; a negative
+                             * value is CIAOSR_ERR_BAD_ARG */
 } ciaosr_options_t;
 
 /* ---- layout plumbing -------------------------------------------------------------------- */
@@ -191,6 +198,14 @@ typedef struct ciaosr_csattn_weights {
 
 size_t ciaosr_cs_attn_workspace_bytes(int H, int W, int C);          /* scale 2 */
 size_t ciaosr_cs_attn_workspace_bytes_scale(int H, int W, int C, int scale);
+/* The same under opt->csa_block_mb (what a call with that option checks its workspace against; any entry's precision): equal to the
+ * function above when the option is 0 or opt is NULL, else the whole-map S and P16 replaced by one band's and by the edge rows
+ * [(Hp + Wp)][L] that outlive a band.  A budget below the smallest band (8 logit rows; 4 in the 16-bit entries) is not met: the size is that band's. */
+size_t ciaosr_cs_attn_workspace_bytes_opt(int H, int W, int C, int scale, const ciaosr_options_t* opt /*host, may be NULL*/);
+/* Padded query rows a band of ciaosr_cs_attn_<precision> produces (halo rows of the four-block route not counted): Hp = the padded map's
+ * rows when the option is off or one band covers the map.  precision: 0 = _f32, 1 = _bf16, 2 = _f16; scale 2..4.  Host arithmetic only,
+ * the same that drives the call (ceil(Hp / rows) bands); 0 on a bad argument. */
+int ciaosr_cs_attn_block_rows(int H, int W, int C, int scale, int precision, const ciaosr_options_t* opt /*host, may be NULL*/);
 /* feat_hwc [H][W][ld_feat] -> out [H][W] rows of C floats with leading dimension ld_out
  * (lets the caller write straight into the tail columns of the unfold rows, net:137). */
 int ciaosr_cs_attn_f32(const float* feat_hwc, int ld_feat, int H, int W, const ciaosr_csattn_weights_t* w,
@@ -365,6 +380,8 @@ int ciaosr_decode_residual_f32(const float* h, int ld_h, int width, const float*
                                void* stream);
 
 size_t ciaosr_head_workspace_bytes(int H, int W, const ciaosr_head_weights_t* w, int Q);
+/* the same with cs_attn's share sized by ciaosr_cs_attn_workspace_bytes_opt: what ciaosr_head_forward_* checks under opt->csa_block_mb */
+size_t ciaosr_head_workspace_bytes_opt(int H, int W, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt /*host, may be NULL*/);
 
 /* query_rgb + batched_predict + bilinear residual (net:88-248) given the encoder feature map.
  *   feat_hwc   [H][W][C]                      encoder output, channels-last
