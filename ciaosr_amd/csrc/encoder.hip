@@ -57,210 +57,266 @@ static int conv3(const float* src, int ld_src, int H, int W, const ciaosr_conv_t
                       alpha, part, pf, s, "enc_conv3x3");
 }
 
+// ---- RDN.  rdn_forward() checks its arguments, plans the sizes (rdn_plan), decides the route (rdn_route: the only place that reads options, the
+// precision mode, the weights' presence and the map's size; it launches nothing), validates every layer the route reads (rdn_layers_ok),
+// carves the workspace (rdn_carve: the only list of buffers) and calls one function per stage:
+//   stage, route            launches in order (profiler tags)                                     scratch: reads -> writes
+//   lff16_weights           cast_weights_<h> per 16 blocks (lff16 only)                           lff weights -> Wl16
+//   stem                    per image: image_to_hwc4, enc_patch_first, enc_conv_first,            x -> img4 -> rows -> sfe1 -> X[0][:, :C]
+//                           enc_conv3x3 (sfe2)
+//   block_dense  h16        [enc_cast_<h>], enc_dense_<h> x NL                                    X[b & 1] -> Xb -> X, Xb (lff16: Xb alone)
+//                direct | wino2 | wino4   enc_dense_gather | enc_dense_wino | enc_dense_wino4, x NL   X[b & 1] in place: layer l adds columns C + l G ..
+//                scatter    enc_dense_scatter x NL: per step the small-map kernel where the step  X in place, sums in accb (partials in part)
+//                           has fragments, else the scatter step
+//                generic    enc_conv3x3 x NL                                                      X in place (partials in part)
+//   block_fuse   lff16      enc_conv1x1_f16                                                       Xb, Wl16 -> Gc[:, b G ..), X[(b + 1) & 1][:, :G], Xb
+//                resident   enc_conv1x1, the whole batch in one launch                            X[b & 1] -> Gc[:, b G ..), X[(b + 1) & 1][:, :G]
+//                small | generic   enc_conv1x1 per image                                          the same
+//   global_fuse  small | generic   per image: enc_conv1x1 (enc_gff1x1 behind lff16), enc_conv3x3  Gc -> g0;  g0, sfe1 -> feat
+// A batch runs whole on the halo-resident dense routes (h16, direct, wino2, wino4), in sub-batches where its block buffers outgrow 32-bit
+// offsets, and image by image on the small-map routes (RdnRoute::batch).
+struct RdnPlan {
+    int B, H, W, C, G, NB, NL, cb;     // cb: channels of a block buffer (the block's input and its NL dense layers' outputs)
+    size_t HW, BHW, pf;                // pf: floats of split-K partials (conv_f32.hip)
+};
+static RdnPlan rdn_plan(int B, int H, int W, const ciaosr_rdn_weights_t* w) {
+    RdnPlan p = {B, H, W, w->mid_channels, w->growth, w->num_blocks, w->num_layers, w->mid_channels + w->growth * w->num_layers};
+    p.HW = (size_t)H * W; p.BHW = (size_t)B * p.HW; p.pf = 16 * p.HW * (size_t)(p.C > p.G ? p.C : p.G);
+    return p;
+}
+
+struct RdnBuffers : RdnPlan {
+    float *img4, *rows, *sfe1, *X[2], *Gc, *g0, *accb, *part;
+    unsigned short *Xb, *Wl16;
+};
+// The one list of carve-outs, in carve order: take(floats) is Arena::take (256-byte aligned) for a call, a running sum for the byte count.
+template <class Take>
+static RdnBuffers rdn_carve(const RdnPlan& p, Take take) {
+    RdnBuffers b = {p};
+    b.img4 = take(p.HW * 4); b.rows = take(p.HW * 36);          // first-conv temporaries, one image at a time
+    b.sfe1 = take(p.BHW * p.C);
+    b.X[0] = take(p.BHW * p.cb); b.X[1] = take(p.BHW * p.cb);   // block buffers
+    b.Gc = take(p.BHW * (size_t)p.G * p.NB);                    // global concat
+    b.g0 = take(p.BHW * p.C);
+    b.accb = take(p.HW * (size_t)p.G * p.NL);                   // scatter sums
+    b.part = take(p.pf);
+    b.Xb = reinterpret_cast<unsigned short*>(take(p.BHW * p.cb / 2 + 64));               // 16-bit copy of one block buffer
+    b.Wl16 = reinterpret_cast<unsigned short*>(take((size_t)p.NB * p.G * p.cb / 2 + 64));   // 16-bit copies of the lff weights (f16 mode)
+    return b;
+}
+
+enum RdnDense { kDenseH16, kDenseDirect, kDenseWino2, kDenseWino4, kDenseScatter, kDenseGeneric };
+enum RdnFuse { kFuseResident, kFuseSmall, kFuseGeneric };
+struct RdnRoute {
+    int batch;             // images per pass: B, or fewer: the call runs as passes of that many
+    RdnDense dense;
+    bool h16_direct;       // kDenseH16: the kernel's direct form (opt->dense_direct = 1)
+    bool pairs;            // kDenseH16: weights as hi + lo pairs
+    bool scatter_small;    // kDenseScatter: the one-launch small-map step wherever a step has its fragments
+    bool lff16;            // the local fusion on the 16-bit GEMM; else `lff` in fp32
+    RdnFuse lff;
+    bool gff_small;        // the global fusion's 1x1 on the no-staging GEMM
+    const char* gff_tag;
+    bool resident() const { return dense <= kDenseWino4; }     // halo-resident dense layers: the batch shares every launch
+};
+template <class T>
+static bool dense_all(const RdnPlan& p, const ciaosr_rdn_weights_t* w, T ciaosr_conv_t::*field) {
+    for (int i = 0; i < p.NB * p.NL; ++i)
+        if (!(w->dense[i].*field)) return false;
+    return true;
+}
+// What a call runs; launches nothing.  m.trunk: "f16x3" / "bf16x3" run the fp32 trunk: half ACTIVATIONS in 128 dense layers alone cost
+// rms 4.6e-5 / max 4e-4 on the full C3 tile, and activation pairs (three MFMAs per product + a second patch) would cost the dense layers
+// about what the fp32 Winograd form does
+static RdnRoute rdn_route(const RdnPlan& p, const Mode& m, const ciaosr_options_t* opt, const ciaosr_rdn_weights_t* w) {
+    // thresholds (per-call options; defaults: halo-resident dense layers from 128 tiles of 12x12 pixels on, small-map kernels up to
+    // 18432 pixels = 128 such tiles)
+    const int min_tiles = opt && opt->dense_min_tiles ? opt->dense_min_tiles : 128;
+    const int small_max = opt && opt->scatter_small_max ? opt->scatter_small_max : 18432;
+    const int dd = opt ? opt->dense_direct : 0;       // 0 = best Winograd form available, 1 = direct, 2 = F(2x2)
+    const int C = p.C, G = p.G, cb = p.cb;
+    // The batched block buffers [B*HW][cb] are addressed with 32-bit buffer offsets by the halo-resident dense kernels: a batch that
+    // does not fit runs as sub-batches that do (same workgroups per image: still bitwise the one-image result); a SINGLE image that
+    // does not fit leaves the halo-resident routes to the generic ones, whose launchers check their own operands.
+    const size_t widest = (size_t)(cb > G * p.NB ? cb : G * p.NB);      // block buffer or global concat rows, whichever is wider
+    const bool fits32 = p.BHW * widest * sizeof(float) < 0xFFFFFF00ull, big = fits32 && C == 64 && G == 64 && min_tiles > 0;
+    RdnRoute r = {p.B, kDenseGeneric, dd == 1, m.trunk_pairs, false, false, kFuseGeneric, false, "enc_conv1x1"};
+    // 16-bit modes: the dense layers (97 % of the trunk's MACs) run on the bf16 / f16 MFMA when the map is big enough to give
+    // every CU a tile (dense_h16.hip); first/last convolutions, LFF/GFF 1x1 and all residual sums stay fp32
+    if (big && m.trunk != kF32 && b16::dense_h16_tiles(p.H, p.W) >= min_tiles && dense_all(p, w, &ciaosr_conv_t::frag16)) r.dense = kDenseH16;
+    // big maps, fp32: halo-resident gather-form dense layers (dense_f32.hip) instead of the scatter form, in Winograd F(4x4, 3x3) form
+    // (4x fewer MFMAs, dense_wino4_f32.hip) or F(2x2, 3x3) (2.25x, dense_wino_f32.hip) when the transformed weights are there
+    else if (big && dense_f32_tiles(p.H, p.W) >= min_tiles && dense_all(p, w, &ciaosr_conv_t::frag))
+        r.dense = dd == 0 && dense_all(p, w, &ciaosr_conv_t::frag_wino4) ? kDenseWino4
+                  : dd != 1 && dense_all(p, w, &ciaosr_conv_t::frag_wino) ? kDenseWino2 : kDenseDirect;
+    // scatter form: input group s (64 channels) feeds every later dense layer in ONE convolution with N = 64*(NL-s) output channels
+    // and K = 576: no split-K slabs, 8 launches instead of 16
+    else if (w->scatter_weight && w->scatter_bias && C == 64 && G == 64) {
+        r.dense = kDenseScatter;
+        r.scatter_small = w->scatter_frag && (long)p.HW <= small_max;
+    }
+    if (p.B > 1 && !fits32) {
+        const size_t bmax = (size_t)(0xFFFFFF00ull - 1) / (p.HW * widest * sizeof(float));
+        r.batch = bmax < 1 ? 1 : (int)bmax;
+    } else if (p.B > 1 && !r.resident()) {
+        r.batch = 1;       // small maps: one image after the other through the single-image routes
+    }
+    // f16 mode: the local feature fusion (1x1 over the block's 576 channels) too reads the 16-bit copy of the block buffer, on the
+    // 16-bit GEMM with bias + residual in its epilogue; the dense layers then need no fp32 copy of their outputs, and the epilogue
+    // writes the next block's 16-bit input group.  (The bf16 and weight-pair modes keep the fp32 lff: its weights would need the hi + lo pair.)
+    r.lff16 = r.dense == kDenseH16 && m.lff16 && cb % 8 == 0 && G % 4 == 0 && G <= 128;
+    // big maps: the whole batch in ONE launch of the weights-resident kernel (the B images' rows are contiguous in every buffer)
+    r.lff = conv1x1_resident_ok((long)p.HW, G, cb, cb, cb) && fits32 ? kFuseResident : gemm_small_ok((int)p.HW, G, cb, cb, cb) ? kFuseSmall : kFuseGeneric;
+    r.gff_small = gemm_small_ok((int)p.HW, C, G * p.NB, G * p.NB, G * p.NB);
+    // its own profiler tag when the blocks' 1x1 convolutions ran on the 16-bit path (the "enc_conv1x1" work figure of bench.py counts both)
+    if (r.lff16) r.gff_tag = "enc_gff1x1";
+    return r;
+}
+// every layer the route reads (the scatter form reads its own packed weights, not w->dense)
+static bool rdn_layers_ok(const RdnPlan& p, const RdnRoute& r, const ciaosr_rdn_weights_t* w) {
+    for (int i = 0; i < p.NB * p.NL && r.dense != kDenseScatter; ++i)
+        if (!conv_ok(w->dense[i], p.C + p.G * (i % p.NL), p.G, 3)) return false;
+    for (int b = 0; b < p.NB; ++b)
+        if (!conv_ok(w->lff[b], p.cb, p.G, 1)) return false;
+    return true;
+}
+
+#define RDN_RUN(x) do { const int rc_ = (x); if (rc_ != CIAOSR_OK) return rc_; } while (0)
+// One pass: the plan, the buffers, the route and one function per stage.  On the halo-resident routes the B images share every dense-layer
+// launch (grid.y = image: the 128 strictly dependent launches per image pay their ~8.5 us ramp / first-load / K-slice-reduction / drain
+// once per batch instead of once per image) and the row-wise 1x1 kernels of the f16 route; the few 3x3 convolutions outside the
+// blocks run per image.  Each image is computed by exactly the workgroups, in exactly the order, of a single-image call: bitwise equal.
+struct RdnCall : RdnBuffers {
+    RdnRoute r; Prec prec; const ciaosr_rdn_weights_t* w; hipStream_t s;
+
+    int lff16_weights() const {
+        const float* src[16];
+        for (int b0 = 0; b0 < NB && r.lff16; b0 += 16) {
+            const int n = NB - b0 < 16 ? NB - b0 : 16;
+            for (int i = 0; i < n; ++i) src[i] = w->lff[b0 + i].weight;
+            RDN_RUN(h16_ops(prec).cast_many(src, n, G, cb, Wl16 + (size_t)b0 * G * cb, s));
+        }
+        return CIAOSR_OK;
+    }
+    // first conv, and sfe2 -> block 0 input (columns [0, C) of X[0])
+    int stem(const float* x_nchw) const {
+        for (int i = 0; i < B; ++i) {
+            RDN_RUN(first_conv(x_nchw + (size_t)i * 3 * HW, H, W, w->sfe1, img4, rows, sfe1 + (size_t)i * HW * C, C, s));
+            RDN_RUN(conv3(sfe1 + (size_t)i * HW * C, C, H, W, w->sfe2, X[0] + (size_t)i * HW * cb, cb, nullptr, 0, CIAOSR_ACT_NONE, 1.f, part, pf, s));
+        }
+        return CIAOSR_OK;
+    }
+    int block_dense(int b) const {
+        float* x = X[b & 1];
+        if (r.dense == kDenseH16 && !(r.lff16 && b > 0)) RDN_RUN(h16_ops(prec).cast_group(x, cb, Xb, cb, 0, (long)BHW, s));   // else: written by the previous lff
+        for (int l = 0; l < NL; ++l) {
+            const ciaosr_conv_t& c = w->dense[b * NL + l];
+            const int cin = C + G * l;
+            switch (r.dense) {
+            case kDenseH16:
+                RDN_RUN(h16_ops(prec).dense_layer(r.lff16 ? nullptr : x, cb, Xb, cb, H, W, l, c.frag16, r.pairs ? c.frag16_lo : nullptr, c.bias, B, s,
+                                                  r.h16_direct ? 1 : 0));
+                break;
+            case kDenseWino4: RDN_RUN(dense_layer_wino4_f32(x, cb, H, W, l, c.frag_wino4, c.bias, B, s)); break;
+            case kDenseWino2: RDN_RUN(dense_layer_wino_f32(x, cb, H, W, l, c.frag_wino, c.bias, B, s)); break;
+            case kDenseDirect: RDN_RUN(dense_layer_f32(x, cb, H, W, l, c.frag, c.bias, B, s)); break;
+            case kDenseScatter: {     // step l
+                const float* sbias = w->scatter_bias + (size_t)b * NL * 64;
+                if (r.scatter_small && w->scatter_frag[b * NL + l]) RDN_RUN(dense_scatter_small(x, cb, H, W, l, NL, w->scatter_frag[b * NL + l], sbias, accb, s));
+                else RDN_RUN(dense_scatter_step(x, cb, H, W, l, NL, w->scatter_weight[b * NL + l], sbias, accb, part, pf, s));
+                break;
+            }
+            case kDenseGeneric:       // DenseLayer: cat([x, relu(conv(x))]) == write the G new channels next to the inputs
+                RDN_RUN(conv2d_hwc(x, cb, H, W, cin, c.weight, 9 * cin, c.bias, G, 3, x + cin, cb, nullptr, 0, nullptr, 0, CIAOSR_ACT_RELU, 1.f, part, pf, s,
+                                   "enc_conv3x3"));
+                break;
+            }
+        }
+        return CIAOSR_OK;
+    }
+    // RDB output = x + lff(dense): goes to the global concat and is the next block's input
+    int block_fuse(int b) const {
+        float *x = X[b & 1], *xn = b + 1 < NB ? X[(b + 1) & 1] : nullptr;
+        const ciaosr_conv_t& f = w->lff[b];
+        // from the 16-bit rows: fp32 to the global concat and the next block's input, 16-bit to the next block's input group (rows of Xb
+        // this workgroup alone reads and writes: N = G is one column tile)
+        if (r.lff16)
+            return h16_ops(prec).conv1x1(Xb, cb, Wl16 + (size_t)b * G * cb, cb, f.bias, x, cb, Gc + (size_t)b * G, G * NB, xn, cb, xn ? Xb : nullptr, cb,
+                                         (int)BHW, G, cb, s, "enc_conv1x1_f16");
+        if (r.lff == kFuseResident)
+            return conv1x1_resident_f32(x, cb, f.weight, cb, f.bias, x, cb, Gc + (size_t)b * G, G * NB, xn, cb, (long)BHW, cb, s, "enc_conv1x1");
+        for (int i = 0; i < B; ++i) {
+            float* xi = x + (size_t)i * HW * cb;
+            float* xni = xn ? xn + (size_t)i * HW * cb : nullptr;
+            float* gi = Gc + (size_t)i * HW * G * NB + (size_t)b * G;
+            if (r.lff == kFuseSmall)
+                RDN_RUN(gemm_small_f32(xi, cb, f.weight, cb, f.bias, gi, G * NB, xni, cb, xi, cb, (int)HW, G, cb, CIAOSR_ACT_NONE, 0.f, 1.f, s, "enc_conv1x1"));
+            else
+                RDN_RUN(conv2d_hwc(xi, cb, H, W, cb, f.weight, cb, f.bias, G, 1, gi, G * NB, xni, cb, xi, cb, CIAOSR_ACT_NONE, 1.f, part, pf, s, "enc_conv1x1"));
+        }
+        return CIAOSR_OK;
+    }
+    int global_fuse(float* feat_hwc) const {
+        const int K = G * NB;
+        for (int i = 0; i < B; ++i) {
+            const float* gci = Gc + (size_t)i * HW * K;
+            float* g0i = g0 + (size_t)i * HW * C;
+            if (r.gff_small)
+                RDN_RUN(gemm_small_f32(gci, K, w->gff0.weight, K, w->gff0.bias, g0i, C, nullptr, 0, nullptr, 0, (int)HW, C, K, CIAOSR_ACT_NONE, 0.f, 1.f, s,
+                                       r.gff_tag));
+            else
+                RDN_RUN(conv2d_hwc(gci, K, H, W, K, w->gff0.weight, K, w->gff0.bias, C, 1, g0i, C, nullptr, 0, nullptr, 0, CIAOSR_ACT_NONE, 1.f, part, pf, s,
+                                   r.gff_tag));
+            RDN_RUN(conv3(g0i, C, H, W, w->gff1, feat_hwc + (size_t)i * HW * C, C, sfe1 + (size_t)i * HW * C, C, CIAOSR_ACT_NONE, 1.f, part, pf, s));
+        }
+        return CIAOSR_OK;
+    }
+};
+
 }  // namespace ciaosr
 
 using namespace ciaosr;
 
 extern "C" size_t ciaosr_rdn_workspace_bytes_batch(int B, int H, int W, const ciaosr_rdn_weights_t* w) {
     if (!w || B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t HW = (size_t)H * W, BHW = (size_t)B * HW;
-    const int C = w->mid_channels, G = w->growth, cb = C + G * w->num_layers;
-    size_t n = HW * 4 + HW * 36 /*first-conv temporaries, one image at a time*/ + BHW * C /*sfe1*/ + 2 * BHW * cb /*block buffers*/ +
-               BHW * (size_t)G * w->num_blocks /*global concat*/ + BHW * C /*gff0*/ + HW * (size_t)G * w->num_layers /*scatter sums*/ +
-               16 * HW * (size_t)(C > G ? C : G) + BHW * cb / 2 + 64 /*16-bit copy of one block buffer*/ +
-               (size_t)w->num_blocks * G * cb / 2 + 64 /*16-bit copies of the lff weights (f16 mode)*/;
-    return n * sizeof(float) + 17 * 256;
+    size_t n = 0;
+    rdn_carve(rdn_plan(B, H, W, w), [&](size_t floats) { n += floats; return (float*)nullptr; });
+    return n * sizeof(float) + 17 * 256;              // room for the 256-byte alignment of each carve-out
 }
 
 extern "C" size_t ciaosr_rdn_workspace_bytes(int H, int W, const ciaosr_rdn_weights_t* w) {
     return ciaosr_rdn_workspace_bytes_batch(1, H, W, w);
 }
 
-// B images of the same size through the trunk.  On the big-map routes (halo-resident dense layers) the B images share every dense-layer
-// launch (grid.y = image: the 128 strictly dependent launches per image pay their ~8.5 us ramp / first-load / K-slice-reduction / drain
-// once per batch instead of once per image) and the row-wise 1x1 kernels of the f16 route; the few 3x3 convolutions outside the
-// blocks run per image.  Each image is computed by exactly the workgroups, in exactly the order, of a single-image call: bitwise equal.
+// B images of the same size through the trunk
 static int rdn_forward(const float* x_nchw, int B, int H, int W, const ciaosr_rdn_weights_t* w, float* feat_hwc,
                        const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream_, Prec entry) {
-    // "f16x3" / "bf16x3" run the fp32 trunk (Mode::trunk): half ACTIVATIONS in 128 dense layers alone cost rms 4.6e-5 / max 4e-4 on the
-    // full C3 tile, and activation pairs (three MFMAs per product + a second patch) would cost the dense layers about what the fp32
-    // Winograd form does
-    const Mode m = resolve_mode(entry, opt);
-    const Prec prec = m.trunk;
-    const bool bf16 = prec != kF32;      // a 16-bit MFMA trunk (bf16 or f16)
-    // route thresholds (per-call options; defaults: halo-resident dense layers from 128 tiles of 12x12 pixels on, small-map
-    // kernels up to 18432 pixels = 128 such tiles)
-    const int min_tiles = opt && opt->dense_min_tiles ? opt->dense_min_tiles : 128;
-    const int small_max = opt && opt->scatter_small_max ? opt->scatter_small_max : 18432;
     CIAOSR_CHECK_ARG(x_nchw && w && feat_hwc && workspace && B >= 1 && H > 0 && W > 0);
     CIAOSR_CHECK_ARG(options_ok(opt));
-    const int C = w->mid_channels, G = w->growth, NB = w->num_blocks, NL = w->num_layers;
-    CIAOSR_CHECK_ARG(C % 32 == 0 && G % 32 == 0 && NB >= 1 && NL >= 1 && w->dense && w->lff);
-    CIAOSR_CHECK_ARG(C == G);   // mmedit's RDN feeds rdbs[b>0] with channel_growth channels and adds sfe1 (mid) at the end
-    CIAOSR_CHECK_ARG(conv_ok(w->sfe1, 3, C, 3) && conv_ok(w->sfe2, C, C, 3));
-    CIAOSR_CHECK_ARG(conv_ok(w->gff0, G * NB, C, 1) && conv_ok(w->gff1, C, C, 3));
+    const RdnPlan p = rdn_plan(B, H, W, w);
+    CIAOSR_CHECK_ARG(p.C % 32 == 0 && p.G % 32 == 0 && p.NB >= 1 && p.NL >= 1 && w->dense && w->lff);
+    CIAOSR_CHECK_ARG(p.C == p.G);   // mmedit's RDN feeds rdbs[b>0] with channel_growth channels and adds sfe1 (mid) at the end
+    CIAOSR_CHECK_ARG(conv_ok(w->sfe1, 3, p.C, 3) && conv_ok(w->sfe2, p.C, p.C, 3));
+    CIAOSR_CHECK_ARG(conv_ok(w->gff0, p.G * p.NB, p.C, 1) && conv_ok(w->gff1, p.C, p.C, 3));
     if (workspace_bytes < ciaosr_rdn_workspace_bytes_batch(B, H, W, w)) return CIAOSR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream_;
-    const size_t HW = (size_t)H * W, BHW = (size_t)B * HW;
-    const int cb = C + G * NL;
-    // The batched block buffers [B*HW][cb] are addressed with 32-bit buffer offsets by the halo-resident dense kernels: a batch that
-    // does not fit runs as sub-batches that do (same workgroups per image: still bitwise the one-image result); a SINGLE image that
-    // does not fit leaves the halo-resident routes to the generic ones, whose launchers check their own operands.
-    const size_t widest = (size_t)(cb > G * NB ? cb : G * NB);      // block buffer or global concat rows, whichever is wider
-    const bool fits32 = BHW * widest * sizeof(float) < 0xFFFFFF00ull;
-    if (B > 1 && !fits32) {
-        size_t bmax = (size_t)(0xFFFFFF00ull - 1) / (HW * widest * sizeof(float));
-        if (bmax < 1) bmax = 1;
-        for (int i = 0; i < B; i += (int)bmax) {
-            const int nb = B - i < (int)bmax ? B - i : (int)bmax;
-            const int rc = rdn_forward(x_nchw + (size_t)i * 3 * HW, nb, H, W, w, feat_hwc + (size_t)i * HW * C, opt, workspace, workspace_bytes,
-                                       stream_, entry);
-            if (rc != CIAOSR_OK) return rc;
-        }
-        return CIAOSR_OK;
+    const Mode m = resolve_mode(entry, opt);
+    const RdnRoute r = rdn_route(p, m, opt, w);
+    for (int i = 0; i < B && r.batch < B; i += r.batch) {          // passes of r.batch images, each routed for its own size
+        const int nb = B - i < r.batch ? B - i : r.batch;
+        RDN_RUN(rdn_forward(x_nchw + (size_t)i * 3 * p.HW, nb, H, W, w, feat_hwc + (size_t)i * p.HW * p.C, opt, workspace, workspace_bytes, stream_, entry));
     }
+    if (r.batch < B) return CIAOSR_OK;
+    CIAOSR_CHECK_ARG(rdn_layers_ok(p, r, w));                      // before the first launch
     Arena ar(workspace, workspace_bytes);
-    float* img4 = ar.take<float>(HW * 4);
-    float* rows = ar.take<float>(HW * 36);
-    float* sfe1 = ar.take<float>(BHW * C);
-    float* X[2] = {ar.take<float>(BHW * cb), ar.take<float>(BHW * cb)};
-    float* Gc = ar.take<float>(BHW * (size_t)G * NB);
-    float* g0 = ar.take<float>(BHW * C);
-    float* accb = ar.take<float>(HW * (size_t)G * NL);
-    const size_t pf = 16 * HW * (size_t)(C > G ? C : G);
-    float* part = ar.take<float>(pf);
-    unsigned short* Xb = reinterpret_cast<unsigned short*>(ar.take<float>(BHW * cb / 2 + 64));
-    unsigned short* Wl16 = reinterpret_cast<unsigned short*>(ar.take<float>((size_t)NB * G * cb / 2 + 64));
+    const RdnCall c = {rdn_carve(p, [&](size_t floats) { return ar.take<float>(floats); }), r, m.trunk, w, (hipStream_t)stream_};
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
-    // 16-bit modes: the dense layers (97 % of the trunk's MACs) run on the bf16 / f16 MFMA when the map is big enough to give
-    // every CU a tile (dense_h16.hip); first/last convolutions, LFF/GFF 1x1 and all residual sums stay fp32
-    bool dense16 = fits32 && bf16 && C == 64 && G == 64 && min_tiles > 0 && b16::dense_h16_tiles(H, W) >= min_tiles;
-    if (bf16)
-        for (int i = 0; i < NB * NL && dense16; ++i) dense16 = w->dense[i].frag16 != nullptr;
-    // big maps, fp32: halo-resident gather-form dense layers (dense_f32.hip) instead of the scatter form
-    bool dense32 = fits32 && !dense16 && C == 64 && G == 64 && min_tiles > 0 && dense_f32_tiles(H, W) >= min_tiles;
-    for (int i = 0; i < NB * NL && dense32; ++i) dense32 = w->dense[i].frag != nullptr;
-    // ... in Winograd F(2x2, 3x3) form when the transformed weights are there (2.25x fewer MFMAs; dense_wino_f32.hip)
-    const int dd = opt ? opt->dense_direct : 0;       // 0 = best Winograd form available, 1 = direct, 2 = F(2x2)
-    bool wino32 = dense32 && dd != 1;
-    for (int i = 0; i < NB * NL && wino32; ++i) wino32 = w->dense[i].frag_wino != nullptr;
-    // ... or F(4x4, 3x3): 4x fewer MFMAs than the direct form (dense_wino4_f32.hip)
-    bool wino4 = dense32 && dd == 0;
-    for (int i = 0; i < NB * NL && wino4; ++i) wino4 = w->dense[i].frag_wino4 != nullptr;
-    // f16 mode: the local feature fusion (1x1 over the block's 576 channels) too reads the 16-bit copy of the block buffer, on the
-    // 16-bit GEMM with bias + residual in its epilogue; the dense layers then need no fp32 copy of their outputs, and the epilogue
-    // writes the next block's 16-bit input group.  (The bf16 and weight-pair modes keep the fp32 lff: its weights would need the hi + lo pair.)
-    const bool lff16 = dense16 && m.lff16 && cb % 8 == 0 && G % 4 == 0 && G <= 128;
-    int rc;
-#define RUN(x) do { rc = (x); if (rc != CIAOSR_OK) return rc; } while (0)
-    if (B > 1 && !(dense16 || dense32)) {       // small maps: one image after the other through the single-image routes
-        for (int i = 0; i < B; ++i)
-            RUN(rdn_forward(x_nchw + (size_t)i * 3 * HW, 1, H, W, w, feat_hwc + (size_t)i * HW * C, opt, workspace, workspace_bytes, stream_, entry));
-        return CIAOSR_OK;
+    RDN_RUN(c.lff16_weights());
+    RDN_RUN(c.stem(x_nchw));
+    for (int b = 0; b < p.NB; ++b) {
+        RDN_RUN(c.block_dense(b));
+        RDN_RUN(c.block_fuse(b));
     }
-    if (lff16) {
-        const float* src[16];
-        for (int b0 = 0; b0 < NB; b0 += 16) {
-            const int n = NB - b0 < 16 ? NB - b0 : 16;
-            for (int i = 0; i < n; ++i) {
-                CIAOSR_CHECK_ARG(conv_ok(w->lff[b0 + i], cb, G, 1));
-                src[i] = w->lff[b0 + i].weight;
-            }
-            RUN(h16_ops(prec).cast_many(src, n, G, cb, Wl16 + (size_t)b0 * G * cb, s));
-        }
-    }
-    for (int i = 0; i < B; ++i) {
-        RUN(first_conv(x_nchw + (size_t)i * 3 * HW, H, W, w->sfe1, img4, rows, sfe1 + (size_t)i * HW * C, C, s));
-        // sfe2 -> block 0 input (columns [0, C) of X[0])
-        RUN(conv3(sfe1 + (size_t)i * HW * C, C, H, W, w->sfe2, X[0] + (size_t)i * HW * cb, cb, nullptr, 0, CIAOSR_ACT_NONE, 1.f, part, pf, s));
-    }
-    for (int b = 0; b < NB; ++b) {
-        float* x = X[b & 1];
-        float* xn = X[(b + 1) & 1];
-        if (dense16) {
-            if (!(lff16 && b > 0)) RUN(h16_ops(prec).cast_group(x, cb, Xb, cb, 0, (long)BHW, s));     // else: written by the previous lff
-            for (int l = 0; l < NL; ++l) {
-                const ciaosr_conv_t& c = w->dense[b * NL + l];
-                CIAOSR_CHECK_ARG(conv_ok(c, C + G * l, G, 3));
-                RUN(h16_ops(prec).dense_layer(lff16 ? nullptr : x, cb, Xb, cb, H, W, l, c.frag16,
-                                              m.trunk_pairs ? c.frag16_lo : nullptr, c.bias, B, s,
-                                              dd == 1 ? 1 : 0));
-            }
-            if (lff16) {
-                // RDB output = x + lff(dense) from the 16-bit rows: fp32 to the global concat and the next block's input, 16-bit to the
-                // next block's input group (rows of Xb this workgroup alone reads and writes: N = G is one column tile)
-                const bool more = b + 1 < NB;
-                RUN(h16_ops(prec).conv1x1(Xb, cb, Wl16 + (size_t)b * G * cb, cb, w->lff[b].bias, x, cb, Gc + (size_t)b * G, G * NB,
-                                          more ? xn : nullptr, cb, more ? Xb : nullptr, cb, (int)BHW, G, cb, s, "enc_conv1x1_f16"));
-                continue;
-            }
-        } else if (dense32) {
-            for (int l = 0; l < NL; ++l) {
-                const ciaosr_conv_t& c = w->dense[b * NL + l];
-                CIAOSR_CHECK_ARG(conv_ok(c, C + G * l, G, 3));
-                if (wino4) RUN(dense_layer_wino4_f32(x, cb, H, W, l, c.frag_wino4, c.bias, B, s));
-                else if (wino32) RUN(dense_layer_wino_f32(x, cb, H, W, l, c.frag_wino, c.bias, B, s));
-                else RUN(dense_layer_f32(x, cb, H, W, l, c.frag, c.bias, B, s));
-            }
-        } else if (w->scatter_weight && w->scatter_bias && C == 64 && G == 64) {
-            // scatter form: input group s (64 channels) feeds every later dense layer in ONE convolution with
-            // N = 64*(NL-s) output channels and K = 576: no split-K slabs, 8 launches instead of 16
-            const bool small = w->scatter_frag && (long)HW <= small_max;
-            for (int st = 0; st < NL; ++st) {
-                if (small && w->scatter_frag[b * NL + st])
-                    RUN(dense_scatter_small(x, cb, H, W, st, NL, w->scatter_frag[b * NL + st], w->scatter_bias + (size_t)b * NL * 64,
-                                            accb, s));
-                else
-                    RUN(dense_scatter_step(x, cb, H, W, st, NL, w->scatter_weight[b * NL + st],
-                                           w->scatter_bias + (size_t)b * NL * 64, accb, part, pf, s));
-            }
-        } else {
-            for (int l = 0; l < NL; ++l) {
-                const ciaosr_conv_t& c = w->dense[b * NL + l];
-                const int cin = C + G * l;
-                CIAOSR_CHECK_ARG(conv_ok(c, cin, G, 3));
-                // DenseLayer: cat([x, relu(conv(x))]) == write the G new channels next to the inputs
-                RUN(conv2d_hwc(x, cb, H, W, cin, c.weight, 9 * cin, c.bias, G, 3, x + cin, cb, nullptr, 0, nullptr, 0,
-                               CIAOSR_ACT_RELU, 1.f, part, pf, s, "enc_conv3x3"));
-            }
-        }
-        const ciaosr_conv_t& f = w->lff[b];
-        CIAOSR_CHECK_ARG(conv_ok(f, cb, G, 1));
-        // RDB output = x + lff(dense): goes to the global concat and is the next block's input
-        if (conv1x1_resident_ok((long)HW, G, cb, cb, cb) && fits32) {
-            // big maps: the whole batch in ONE launch of the weights-resident kernel (the B images' rows are contiguous in every buffer)
-            RUN(conv1x1_resident_f32(x, cb, f.weight, cb, f.bias, x, cb, Gc + (size_t)b * G, G * NB, b + 1 < NB ? xn : nullptr, cb, (long)BHW, cb,
-                                     s, "enc_conv1x1"));
-            continue;
-        }
-        for (int i = 0; i < B; ++i) {
-            float* xi = x + (size_t)i * HW * cb;
-            float* xni = b + 1 < NB ? xn + (size_t)i * HW * cb : nullptr;
-            float* gi = Gc + (size_t)i * HW * G * NB + (size_t)b * G;
-            if (gemm_small_ok((int)HW, G, cb, cb, cb))
-                RUN(gemm_small_f32(xi, cb, f.weight, cb, f.bias, gi, G * NB, xni, cb, xi, cb, (int)HW, G, cb, CIAOSR_ACT_NONE, 0.f, 1.f, s,
-                                   "enc_conv1x1"));
-            else
-                RUN(conv2d_hwc(xi, cb, H, W, cb, f.weight, cb, f.bias, G, 1, gi, G * NB, xni, cb, xi, cb, CIAOSR_ACT_NONE, 1.f, part, pf, s,
-                               "enc_conv1x1"));
-        }
-    }
-    // global feature fusion; its own profiler tag when the blocks' 1x1 convolutions ran on the 16-bit path (the "enc_conv1x1" work
-    // figure of bench.py counts both)
-    const char* gff_tag = lff16 ? "enc_gff1x1" : "enc_conv1x1";
-    for (int i = 0; i < B; ++i) {
-        const float* gci = Gc + (size_t)i * HW * G * NB;
-        float* g0i = g0 + (size_t)i * HW * C;
-        if (gemm_small_ok((int)HW, C, G * NB, G * NB, G * NB))
-            RUN(gemm_small_f32(gci, G * NB, w->gff0.weight, G * NB, w->gff0.bias, g0i, C, nullptr, 0, nullptr, 0, (int)HW, C, G * NB,
-                               CIAOSR_ACT_NONE, 0.f, 1.f, s, gff_tag));
-        else
-            RUN(conv2d_hwc(gci, G * NB, H, W, G * NB, w->gff0.weight, G * NB, w->gff0.bias, C, 1, g0i, C, nullptr, 0, nullptr, 0,
-                           CIAOSR_ACT_NONE, 1.f, part, pf, s, gff_tag));
-        RUN(conv3(g0i, C, H, W, w->gff1, feat_hwc + (size_t)i * HW * C, C, sfe1 + (size_t)i * HW * C, C, CIAOSR_ACT_NONE, 1.f, part, pf, s));
-    }
-#undef RUN
-    return CIAOSR_OK;
+    return c.global_fuse(feat_hwc);
 }
 
 extern "C" int ciaosr_rdn_forward_f32(const float* x_nchw, int H, int W, const ciaosr_rdn_weights_t* w,

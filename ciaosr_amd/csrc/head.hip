@@ -1,12 +1,37 @@
-// LocalImplicitSRNet.forward minus the encoder (ciaosr_net.py:88-248): one C entry point that
-// runs unfold -> cs_attn -> layer-1 tables -> [per work-chunk: rows, MLP chains, local attention,
-// decode] on one stream.  Staged form: every stage is its own kernel with a clean roofline.
+// LocalImplicitSRNet.forward minus the encoder (ciaosr_net.py:88-248) as a sequence of launches on one stream.  head_forward() checks its
+// arguments, plans the sizes (head_plan), carves the workspace (head_carve: the only list of buffers; HeadBuffers names every second use
+// of one), decides the route (head_route: the only place that reads options, the precision mode, the weights' presence and the
+// capacities; it launches nothing, so a call it refuses has enqueued nothing) and calls one function per stage:
+//   stage, route          launches in order (profiler tags)                                  scratch: reads -> writes
+//   unfold                head_unfold                                                        feat -> U[:, :D]
+//   cs_attn               one cs_attn call per scale (csattn.hip)                            feat -> U[:, D + i C ..);  its own workspace csa_ws
+//   layer0_tables  h16    cast_rows x 3, head_table_f16 x 2                                  U, W0k, W0v -> u16, wk16, wv16 (bufA) -> Tk, Tv
+//                  small  head_table x 2 (the no-staging GEMM)                               U -> Tk, Tv
+//                  gemm   head_table x 2                                                     U -> Tk, Tv
+//   logit_table    none   --
+//                  wino4  head_qk_maps, head_logit_table_w4, head_qk_rows (bias term)        feat -> qk_maps (QK) -> G;  U -> G[:, 256]
+//                  wino2  head_qk_maps, head_logit_table_w2, head_qk_rows                    the same
+//                  gemm32 per 65 536 rows: head_qk_rows, head_logit_table                    U -> QK -> G
+//                  gemm16 transpose_cast_h16, per 65 536 rows: head_qk_rows,                 W5k -> W5T;  U -> qk16 (QK);  qk16, W5T -> G
+//                         head_logit_table_<h>
+//   -- per chunk of queries (fused: plan.qcf, one chunk up to 2^20 queries;  staged: plan.qc = 65 536) ------------------------------------
+//   kv      fused32       head_kv_fused                                                      U, Tk, Tv, [G] -> Z
+//           fused16       head_kv_fused_<h>                                                  the same
+//           wide          head_kv_fused_wide (its mode: f16, f16 pairs, x3)                  the same
+//           chain         memset, head_kv_chain[_pairs]_<h>, then fused16 gated on the flag  U, Tk, Tv, G -> Z, chain_flag
+//   decode  fused32 | fused16 | wide | chain                                                 Z -> rgb
+//                         head_decode_fused[_<h>] | .._wide | head_decode_chain[_pairs]_<h>
+//   staged_chunk          head_rows, mlp_hidden x n, mlp_out_k, mlp_hidden x n, mlp_out_v,   Tk, Tv -> bufA (Hk), Hv, q_idx, k_idx -> bufB <-> bufA -> WK;
+//                         local_attention, mlp_in_q, mlp_hidden_q x n, decode_residual       Hv -> bufA <-> bufB -> WV;  U, WK, WV -> Z -> bufA <-> bufB -> rgb
+// The fused routes need local_size 2, ReLU chains of 256-wide layers and packed fragments; everything else, and head_route bit 0, runs staged
+// (fp32 only: a 16-bit entry without a fused route is refused).  Staged form: every stage is its own kernel with a clean roofline.
 #include "ops.h"
 
 namespace ciaosr {
 
 struct HeadPlan {
     int H, W, C, Cn, D, Dv, J, HW;
+    long Q;
     int wk0, wv0;            // layer-0 widths
     int wmax;                // widest hidden activation among k / v / q chains
     int qc;                  // queries per work-chunk of the STAGED route (its [4 qc][..] intermediates are the big buffers)
@@ -15,6 +40,7 @@ struct HeadPlan {
                              // in which the 4-workgroups-per-CU overlap that the kernels live on decays (probe: a workgroup lives
                              // 685k cycles, a 65 536-query launch 3.0M, so ~1/4 of every launch ran under-occupied)
     size_t csa_bytes;
+    size_t R() const { return (size_t)qc * J; }      // key / value rows of a staged chunk
 };
 
 constexpr int kLdG = 260;        // logit-table row: 256 coefficients + the bias term + pad
@@ -24,7 +50,7 @@ static int n_samples(int local_size) { return local_size == 1 ? 1 : (local_size 
 
 static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt) {
     HeadPlan p;
-    p.H = H; p.W = W; p.C = w->channels; p.Cn = w->nonlocal_channels;
+    p.H = H; p.W = W; p.C = w->channels; p.Cn = w->nonlocal_channels; p.Q = Q;
     p.D = (w->no_unfold ? 1 : 9) * p.C; p.Dv = p.D + p.Cn; p.J = n_samples(w->local_size); p.HW = H * W;
     p.wk0 = w->k.width[0];
     p.wv0 = w->v.width[0];
@@ -49,20 +75,50 @@ static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q, c
     return p;
 }
 
+// The workspace.  Each buffer is named for its first occupant (head_carve); every later use of one is a view here, with the reason it
+// fits: a capacity that always holds as a comment, one that can fail as a *_fits predicate that head_route() consults.
+struct HeadBuffers : HeadPlan {
+    float *U, *Tk, *Tv, *bufA, *bufB, *Hv, *WK, *WV, *Z, *G, *QK, *csa_ws;
+    int *q_idx, *k_idx, *chain_flag;
+    unsigned short* W5T;
+    // h16 layer-0 tables: 16-bit copies of U [HW][Dv] and of both layer-0 weights [wk0][D], [wv0][Dv], where the staged route keeps its
+    // activations (free on the fused routes, the only ones with a 16-bit mode): u16_fits
+    unsigned short* u16() const { return reinterpret_cast<unsigned short*>(bufA); }
+    unsigned short* wk16() const { return u16() + round_up((size_t)HW * Dv, 128); }
+    unsigned short* wv16() const { return wk16() + round_up((size_t)wk0 * D, 128); }
+    // the nine product maps [9][HW][C] of the Winograd logit table, where the GEMM forms keep a chunk of rows [kQkChunk][9C]: qk_maps_fits
+    float* qk_maps() const { return QK; }
+    // the same chunk of rows in 16 bits for the 16-bit table GEMM.  2 kQkChunk D <= 4 kQkChunk D
+    unsigned short* qk16() const { return reinterpret_cast<unsigned short*>(QK); }
+};
+static bool u16_fits(const HeadPlan& p) {                                                              // not at small Q
+    return (size_t)p.HW * p.Dv * 2 + 256 + (size_t)(p.wk0 + p.wv0) * p.Dv * 2 + 512 <= p.R() * p.wmax * sizeof(float);
+}
+static bool qk_maps_fits(const HeadPlan& p) { return p.HW <= kQkChunk; }                               // not above 256 x 256 pixels
+
+// The one list of carve-outs, in carve order: take(floats) is Arena::take (256-byte aligned) for a call, a running sum for the byte count.
+template <class Take>
+static HeadBuffers head_carve(const HeadPlan& p, Take take) {
+    const size_t HW = p.HW, R = p.R();
+    HeadBuffers b = {p};
+    b.U = take(HW * p.Dv);                            // unfold rows [HW][D] and, behind them, the non-local maps [HW][Cn]
+    b.Tk = take(HW * p.wk0); b.Tv = take(HW * p.wv0);       // layer-0 tables
+    b.bufA = take(R * p.wmax); b.bufB = take(R * p.wmax);   // staged: ping-pong activations
+    b.Hv = take(R * p.wv0);                           // staged: layer-0 rows of the value chain, kept while the key chain runs
+    b.WK = take(R * p.D); b.WV = take(R * p.Dv);      // staged: the chains' outputs
+    b.Z = take((size_t)p.qcf * p.Dv);                 // attention output of a chunk (sized for the fused routes' chunk)
+    b.q_idx = reinterpret_cast<int*>(take(p.qc)); b.k_idx = reinterpret_cast<int*>(take(R));
+    b.G = take(HW * 9 * kLdG);                        // logit table
+    b.QK = take((size_t)kQkChunk * p.D);              // one chunk of its GEMM rows
+    b.W5T = reinterpret_cast<unsigned short*>(take((size_t)128 * p.D + 64));   // 16-bit modes: transposed 16-bit copy [256][D] of imnet_k's output layer
+    b.chain_flag = reinterpret_cast<int*>(take(64));  // 16-bit chained kernel: its "redo with the 128-row kernel" flag
+    b.csa_ws = take(p.csa_bytes / sizeof(float));     // cs_attn's workspace (a whole number of floats: csa_carve_bytes)
+    return b;
+}
 static size_t head_ws_bytes(const HeadPlan& p) {
-    const size_t R = (size_t)p.qc * p.J;
     size_t n = 0;
-    n += (size_t)p.HW * p.Dv;                 // U
-    n += (size_t)p.HW * (p.wk0 + p.wv0);      // tables
-    n += 2 * R * p.wmax;                      // ping-pong activations
-    n += R * p.wv0;                           // Hv (layer-1 rows of the value chain, kept while the key chain runs)
-    n += R * p.D + R * p.Dv;                  // WK, WV
-    n += (size_t)p.qcf * p.Dv;                // Z (sized for the fused route's chunk)
-    n += (size_t)p.qc + R;                    // q_idx, k_idx (ints, same size as float)
-    n += (size_t)p.HW * 9 * kLdG + (size_t)kQkChunk * p.D;   // logit table + one chunk of its GEMM rows
-    n += (size_t)128 * p.D + 64;                             // bf16 mode: transposed bf16 copy of imnet_k's output layer
-    n += 64;                                                 // 16-bit chained kernel: its "redo with the 128-row kernel" flag
-    return n * sizeof(float) + p.csa_bytes + 32 * 256;
+    head_carve(p, [&](size_t floats) { n += floats; return (float*)nullptr; });
+    return n * sizeof(float) + 32 * 256;              // room for the 256-byte alignment of each carve-out
 }
 
 static int mlp_act(const ciaosr_mlp_t& m) { return m.act == CIAOSR_ACT_SIN || m.act == CIAOSR_ACT_COS ? m.act : CIAOSR_ACT_RELU; }
@@ -74,54 +130,254 @@ static bool mlp_ok(const ciaosr_mlp_t& m) {
     return true;
 }
 
-// layers 1 .. n-1 of an MLP on rows already holding the layer-0 activations.
-// Returns the buffer holding the result; the last layer writes to `last_out` (ld_last) with no ReLU.
-static int run_tail(const ciaosr_mlp_t& m, const float* h0, int ld0, float* bufA, float* bufB, float* last_out,
-                    int ld_last, long rows, hipStream_t s, const char* tag_hidden, const char* tag_out) {
-    const float* cur = h0;
-    int ld_cur = ld0;
-    float* pp[2] = {bufA, bufB};
-    int flip = 0;
-    for (int i = 1; i < m.n_layers; ++i) {
-        const bool last = (i == m.n_layers - 1);
-        float* dst = last ? last_out : pp[flip];
-        const int ldd = last ? ld_last : m.width[i];
-        int rc = gemm_f32(cur, ld_cur, m.weight[i], m.ld[i], false, dst, ldd, m.bias[i], (int)rows, m.width[i],
-                          m.width[i - 1], 1.f, last ? CIAOSR_ACT_NONE : mlp_act(m), 0.f, s,
-                          last ? tag_out : tag_hidden);
-        if (rc != CIAOSR_OK) return rc;
-        cur = dst;
-        ld_cur = ldd;
-        flip ^= 1;
-    }
-    return CIAOSR_OK;
-}
-
 // fused kernels: hidden width 256 everywhere, fragments packed, 4 key samples
-static bool chain_fused_ok(const ciaosr_mlp_t& m, bool is_q, bool bf16) {
+static bool chain_fused_ok(const ciaosr_mlp_t& m, bool is_q, bool h16) {
     if (m.n_layers < 2 || mlp_act(m) != CIAOSR_ACT_RELU) return false;
     for (int i = 0; i + 1 < m.n_layers; ++i)
         if (m.width[i] != 256) return false;
     for (int i = is_q ? 0 : 1; i < m.n_layers - (is_q ? 1 : 0); ++i)
-        if (!(bf16 ? m.frag16[i] : (const void*)m.frag[i])) return false;
+        if (!(h16 ? m.frag16[i] : (const void*)m.frag[i])) return false;
     return true;
 }
 
-static void fill_chain(FusedChain& c, const ciaosr_mlp_t& m, const float* table, int fan, bool bf16, bool lo) {
+enum HeadTables { kTablesH16, kTablesSmall, kTablesGemm };
+enum HeadLogit { kLogitNone, kLogitGemm32, kLogitGemm16, kLogitWino2, kLogitWino4 };
+enum HeadKernel { kHeadFused32, kHeadFused16, kHeadWide, kHeadChain };
+struct HeadRoute {
+    int refusal;            // CIAOSR_OK, or what the call returns before its first launch
+    bool fused;             // else staged: one kernel per stage (fp32 only)
+    bool h16, lo;           // fused: 16-bit fragments; their hi + lo weight pairs
+    HeadTables tables;
+    HeadLogit logit;
+    HeadKernel kernel;      // kv and decode of the fused routes; behind the chained kv kernel it runs gated
+    int wide_mode;          // kHeadWide: 0 = f16, 1 = f16 pairs, 2 = x3
+    bool chain, decode_chain;   // the chained kernels, as far as it does not depend on the chunk
+    // The chained kv kernel addresses a chunk's 16-bit Z rows with 32-bit offsets: the one condition asked per chunk of queries.
+    HeadKernel kv(const HeadPlan& p, int nq) const { return chain && (size_t)nq * p.Dv * 2 < 0xFFFFFF00ull ? kHeadChain : kernel; }
+    HeadKernel decode(const HeadPlan& p, int nq) const { return decode_chain && kv(p, nq) == kHeadChain ? kHeadChain : kernel; }
+};
+
+// What a call runs; launches nothing.
+static HeadRoute head_route(const HeadPlan& p, Prec prec, const Mode& m, const ciaosr_options_t* opt, const ciaosr_head_weights_t* w) {
+    const int bits = opt ? opt->head_route : 0;
+    HeadRoute r = {CIAOSR_OK, false, prec != kF32, m.lo, kTablesGemm, kLogitNone, kHeadFused32, m.x3 ? 2 : (m.lo ? 1 : 0), false, false};
+    r.fused = !(bits & CIAOSR_HEAD_STAGED) && w->local_size == 2 && chain_fused_ok(w->k, false, r.h16) && chain_fused_ok(w->v, false, r.h16) &&
+              chain_fused_ok(w->q, true, r.h16) && (p.Dv & 7) == 0;
+    if (r.h16 && !r.fused) r.refusal = CIAOSR_ERR_UNSUPPORTED;        // the 16-bit modes exist for the fused kernels only
+    if (m.x3 && r.refusal == CIAOSR_OK) {                              // the pair kernels read every lo fragment unconditionally
+        bool all = true;
+        for (int i = 1; i < w->k.n_layers; ++i) all = all && w->k.frag16_lo[i];
+        for (int i = 1; i < w->v.n_layers; ++i) all = all && w->v.frag16_lo[i];
+        for (int i = 0; i + 1 < w->q.n_layers; ++i) all = all && w->q.frag16_lo[i];
+        if (!all) r.refusal = CIAOSR_ERR_BAD_ARG;
+    }
+    // exact layer-1 hoist: T = U . W1[:, :fan]^T + b1, one row per LR pixel.  f16 mode: on the 16-bit GEMM from a half copy of U
+    if (m.hoist16 && (p.D & 7) == 0 && (p.Dv & 7) == 0 && u16_fits(p)) r.tables = kTablesH16;
+    else if (gemm_small_ok(p.HW, p.wk0, p.D, p.Dv, w->k.ld[0]) && gemm_small_ok(p.HW, p.wv0, p.Dv, p.Dv, w->v.ld[0]) && p.HW <= 4096)
+        r.tables = kTablesSmall;
+    // logit table of imnet_k's output layer (exact fold, head_ops.hip): pays off when queries outnumber LR pixels
+    const int last = w->k.n_layers - 1;
+    if (r.fused && !(bits & CIAOSR_HEAD_NO_LOGIT_TABLE) && w->k.width[last] == p.D && w->k.width[last - 1] == 256 && p.Q * p.J > (long)p.HW * 9 &&
+        (size_t)p.HW * 9 * kLdG * sizeof(float) < 0xFFFFFF00ull) {
+        // 16-bit modes: the table GEMM on the 16-bit MFMA (fp32 table out).  (Half-pairs mode: the exact-fp32 GEMM here was measured
+        // and changes nothing -- max |delta| 1.04e-3 -> 1.14e-3 on the full-tile vector, +0.9 ms: W5's rounding is not what limits it.)
+        r.logit = m.table16 && (p.D & 7) == 0 ? kLogitGemm16 : kLogitGemm32;
+        // fp32, C = 64: nine Winograd convolutions of the product maps Pi_o = F . shift_o(F) (same sums as the GEMM rows, re-associated
+        // through the transform; 2.25x fewer multiplies, F(4x4): 4x), the maps where the GEMM would keep its row chunk
+        if (!m.table16 && w->k_out_wino && !(bits & CIAOSR_HEAD_TABLE_GEMM) && p.C == 64 && !w->no_unfold && p.HW >= 512 && qk_maps_fits(p))
+            r.logit = w->k_out_wino4 && !(bits & CIAOSR_HEAD_TABLE_WINO2) ? kLogitWino4 : kLogitWino2;
+    }
+    if (!r.fused) return r;
+    // f16x3 runs the wide-workgroup kernels (head_fused_wide.hip: its two activation arrays leave room for one workgroup per CU);
+    // f16 / f16-pairs keep the 128-row kernels with two workgroups per CU (head_fused_h16.hip) and take the wide form -- 256 rows, half
+    // the weight stream per MFMA, measured equal in time: one workgroup per CU exposes its gather phases -- only with head_route bit 3
+    const bool wide = m.x3 || (prec == kF16 && (bits & CIAOSR_HEAD_WIDE_WG));
+    r.kernel = wide ? kHeadWide : r.h16 ? kHeadFused16 : kHeadFused32;
+    // 16-bit default: the weights-stationary, register-chained kernel (head_chain_h16.hip) where its weight stream is given and the
+    // logit table exists; imnet_q through the same form where the blob carries its stream (Dv a multiple of 128, 256-wide layers)
+    r.chain = r.kernel == kHeadFused16 && r.logit != kLogitNone && (m.lo ? w->chain16_pairs : w->chain16) && !(bits & CIAOSR_HEAD_NO_CHAIN) &&
+              h16_ops(prec).head_chain_ok(w);
+    r.decode_chain = r.chain && !(bits & CIAOSR_HEAD_NO_DECODE_CHAIN) && h16_ops(prec).head_decode_chain_ok(w);
+    return r;
+}
+
+// The fp32 ping-pong loop of the staged route: layers i0 <= i < i1 of m on `rows` rows, from cur [rows][ld_cur] (K = k_cur), hidden
+// activations packed (ld = width) alternately into pp0, pp1; the MLP's last layer, when in range, writes last_out (ld_last) without
+// activation under tag_out.  *end = the rows the last launch wrote.
+static int mlp_layers_f32(const ciaosr_mlp_t& m, int i0, int i1, const float* cur, int ld_cur, int k_cur, float* pp0, float* pp1, float* last_out,
+                          int ld_last, long rows, hipStream_t s, const char* tag_first, const char* tag_hidden, const char* tag_out,
+                          const float** end = nullptr) {
+    float* pp[2] = {pp0, pp1};
+    for (int i = i0; i < i1; ++i) {
+        const bool last = i == m.n_layers - 1;
+        float* dst = last ? last_out : pp[(i - i0) & 1];
+        const int ldd = last ? ld_last : m.width[i];
+        const int rc = gemm_f32(cur, ld_cur, m.weight[i], m.ld[i], false, dst, ldd, m.bias[i], (int)rows, m.width[i], k_cur, 1.f,
+                                last ? CIAOSR_ACT_NONE : mlp_act(m), 0.f, s, last ? tag_out : i == i0 ? tag_first : tag_hidden);
+        if (rc != CIAOSR_OK) return rc;
+        cur = dst; ld_cur = ldd; k_cur = m.width[i];
+    }
+    if (end) *end = cur;
+    return CIAOSR_OK;
+}
+
+// the fields FusedChain (imnet_k, imnet_v) and FusedQP (imnet_q) share: the hidden layers 1 .. n - 2
+template <class P>
+static void fill_hidden(P& c, const ciaosr_mlp_t& m, const HeadRoute& r) {
+    c.n_hidden = m.n_layers - 2;
+    for (int i = 0; i < c.n_hidden; ++i) {
+        c.frag_hidden[i] = r.h16 ? m.frag16[i + 1] : (const void*)m.frag[i + 1];
+        c.frag_hidden_lo[i] = (r.h16 && r.lo) ? m.frag16_lo[i + 1] : nullptr;
+        c.bias_hidden[i] = m.bias[i + 1];
+    }
+}
+static void fill_chain(FusedChain& c, const ciaosr_mlp_t& m, const float* table, int fan, const HeadRoute& r) {
+    const int last = m.n_layers - 1;
     c.table = table;
     c.tail = m.weight[0] + fan;
     c.ld_tail = m.ld[0];
-    c.n_hidden = m.n_layers - 2;
-    for (int i = 0; i < c.n_hidden; ++i) {
-        c.frag_hidden[i] = bf16 ? m.frag16[i + 1] : (const void*)m.frag[i + 1];
-        c.frag_hidden_lo[i] = (bf16 && lo) ? m.frag16_lo[i + 1] : nullptr;
-        c.bias_hidden[i] = m.bias[i + 1];
-    }
-    c.frag_out = bf16 ? m.frag16[m.n_layers - 1] : (const void*)m.frag[m.n_layers - 1];
-    c.frag_out_lo = (bf16 && lo) ? m.frag16_lo[m.n_layers - 1] : nullptr;
-    c.bias_out = m.bias[m.n_layers - 1];
-    c.n_out = m.width[m.n_layers - 1];
+    fill_hidden(c, m, r);
+    c.frag_out = r.h16 ? m.frag16[last] : (const void*)m.frag[last];
+    c.frag_out_lo = (r.h16 && r.lo) ? m.frag16_lo[last] : nullptr;
+    c.bias_out = m.bias[last];
+    c.n_out = m.width[last];
 }
+
+static const decltype(&ciaosr_cs_attn_f32) kCsAttnEntry[3] = {ciaosr_cs_attn_f32, ciaosr_cs_attn_bf16, ciaosr_cs_attn_f16};   // by Prec
+static const char* const kLogitTableTag16[3] = {nullptr, "head_logit_table_bf16", "head_logit_table_f16"};
+
+#define HEAD_RUN(x) do { const int rc_ = (x); if (rc_ != CIAOSR_OK) return rc_; } while (0)
+// One call: the plan, the buffers, the route and one function per stage.
+struct HeadCall : HeadBuffers {
+    HeadRoute r; Prec prec;
+    const float* feat; const ciaosr_head_weights_t* w; const ciaosr_csattn_weights_t* csattn;
+    const float *x_lr, *coord, *cell; int chunk; float* rgb; const ciaosr_options_t* opt; hipStream_t s;
+
+    // unfold rows U[:, :9C] (net:132-136); feat_unfold=False (net:139-141): the "unfold" row is the pixel's C features (a 1x1 patch)
+    int unfold() const {
+        const int k = w->no_unfold ? 1 : 3;
+        return patch_rows(feat, C, H, W, C, k, 1, k / 2, H, W, U, Dv, 0, 0.f, s, "head_unfold");
+    }
+    // the non-local maps into U[:, 9C:] (net:134-137): one C-column slice per scale, in the order of multi_scale (csa:528 torch.cat(res_y, dim=1))
+    int cs_attn(int n_scales) const {
+        for (int i = 0; i < n_scales; ++i)
+            HEAD_RUN(kCsAttnEntry[prec](feat, C, H, W, csattn + i, U + D + (size_t)i * C, Dv, opt, csa_ws, csa_bytes, s));
+        return CIAOSR_OK;
+    }
+    int layer0_tables() const {
+        const struct { const ciaosr_mlp_t& m; float* T; int n, fan; } kv[2] = {{w->k, Tk, wk0, D}, {w->v, Tv, wv0, Dv}};
+        if (r.tables == kTablesH16) {
+            const H16Ops& h = h16_ops(prec);
+            unsigned short* const w16[2] = {wk16(), wv16()};
+            HEAD_RUN(h.cast_rows(U, Dv, u16(), Dv, HW, Dv, s));
+            for (int i = 0; i < 2; ++i) HEAD_RUN(h.cast_rows(kv[i].m.weight[0], kv[i].m.ld[0], w16[i], kv[i].fan, kv[i].n, kv[i].fan, s));
+            for (int i = 0; i < 2; ++i)
+                HEAD_RUN(h.conv1x1(u16(), Dv, w16[i], kv[i].fan, kv[i].m.bias[0], nullptr, 0, kv[i].T, kv[i].n, nullptr, 0, nullptr, 0, HW, kv[i].n, kv[i].fan, s,
+                                   "head_table_f16"));
+            return CIAOSR_OK;
+        }
+        for (const auto& t : kv)
+            HEAD_RUN(r.tables == kTablesSmall ? gemm_small_f32(U, Dv, t.m.weight[0], t.m.ld[0], t.m.bias[0], t.T, t.n, nullptr, 0, nullptr, 0, HW, t.n, t.fan,
+                                                               CIAOSR_ACT_NONE, 0.f, 1.f, s, "head_table")
+                                              : gemm_f32(U, Dv, t.m.weight[0], t.m.ld[0], false, t.T, t.n, t.m.bias[0], HW, t.n, t.fan, 1.f, CIAOSR_ACT_NONE, 0.f, s,
+                                                         "head_table"));
+        return CIAOSR_OK;
+    }
+    int logit_table() const {
+        if (r.logit == kLogitNone) return CIAOSR_OK;
+        const int last = w->k.n_layers - 1;
+        const long total = (long)HW * 9;
+        const float *w5 = w->k.weight[last], *b5 = w->k.bias[last];
+        if (r.logit == kLogitWino4 || r.logit == kLogitWino2) {
+            HEAD_RUN(ciaosr::qk_maps(feat, C, C, H, W, qk_maps(), s));
+            HEAD_RUN(r.logit == kLogitWino4 ? wino4_table_f32(qk_maps(), H, W, w->k_out_wino4, 4, G, kLdG, s)
+                                            : wino_table_f32(qk_maps(), H, W, w->k_out_wino, 4, G, kLdG, s));
+            return qk_rows(U, Dv, D, H, W, 0, (int)total, b5, nullptr, G, kLdG, 3, s);
+        }
+        const bool t16 = r.logit == kLogitGemm16;
+        if (t16) HEAD_RUN(transpose_cast_h16(w5, w->k.ld[last], D, 256, W5T, prec == kF16, s));
+        for (long r0 = 0; r0 < total; r0 += kQkChunk) {
+            const int nr = (int)((total - r0) < kQkChunk ? (total - r0) : kQkChunk);
+            HEAD_RUN(qk_rows(U, Dv, D, H, W, r0, nr, b5, QK, G, kLdG, t16 ? (int)prec : 0, s));
+            // G[r][n] = sum_d QK[r][d] * W5k[d][n]: the Linear weight [D][256] is the [K][N] operand as stored
+            HEAD_RUN(t16 ? h16_ops(prec).gemm_nt(qk16(), D, W5T, D, G + (size_t)r0 * kLdG, kLdG, false, nr, 256, D, 1.f, s, kLogitTableTag16[prec], 0)
+                         : gemm_f32(QK, D, w5, w->k.ld[last], true, G + (size_t)r0 * kLdG, kLdG, nullptr, nr, 256, D, 1.f, CIAOSR_ACT_NONE, 0.f, s,
+                                    "head_logit_table"));
+        }
+        return CIAOSR_OK;
+    }
+
+    const void* chain_blob() const { return r.lo ? w->chain16_pairs : w->chain16; }
+    // imnet_k, imnet_v and the local attention of nq queries into Z.  Chained: the 128-row kernel is launched behind the chained one, gated
+    // on the flag that one raises when a key leaves its query's 3x3 neighbourhood (cannot happen for 0 < cell < 1): it then redoes the
+    // launch, else it returns at once
+    int kv(long q0, int nq) const {
+        FusedKVP kp;
+        kp.coord = coord; kp.cell = cell; kp.q0 = q0; kp.nq = nq; kp.chunk = chunk; kp.H = H; kp.W = W;
+        kp.U = U; kp.ldu = Dv; kp.D = D; kp.Dv = Dv;
+        kp.u_bytes = (unsigned)((size_t)HW * Dv * sizeof(float));
+        fill_chain(kp.k, w->k, Tk, D, r);
+        fill_chain(kp.v, w->v, Tv, Dv, r);
+        kp.softmax_scale = w->softmax_scale;
+        kp.Z = Z; kp.ldz = Dv;
+        kp.rows_per_wg = opt ? opt->kv_rows : 0;
+        kp.G = r.logit != kLogitNone ? G : nullptr; kp.ldg = kLdG; kp.g_bytes = (unsigned)((size_t)HW * 9 * kLdG * sizeof(float));
+        kp.gate = nullptr;
+        if (r.kv(*this, nq) == kHeadChain) {
+            if (hipMemsetAsync(chain_flag, 0, sizeof(int), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+            HEAD_RUN(h16_ops(prec).head_kv_chain(kp, w, chain_blob(), r.lo ? 1 : 0, opt ? opt->query_grid_w : 0, chain_flag, s));
+            kp.gate = chain_flag;
+        }
+        if (r.kernel == kHeadWide) return h16_ops(prec).head_kv_fused_wide(kp, r.wide_mode, s);
+        return r.kernel == kHeadFused16 ? h16_ops(prec).head_kv_fused(kp, s) : head_kv_fused(kp, s);
+    }
+    // imnet_q on Z with the bilinear residual of the last layer, into rgb
+    int decode(long q0, int nq) const {
+        const ciaosr_mlp_t& mq = w->q;
+        const int last = mq.n_layers - 1;
+        FusedQP qp;
+        qp.Z = Z; qp.ldz = Dv; qp.Dv = Dv;
+        qp.frag_in = r.h16 ? mq.frag16[0] : (const void*)mq.frag[0]; qp.bias_in = mq.bias[0];
+        qp.frag_in_lo = (r.h16 && r.lo) ? mq.frag16_lo[0] : nullptr;
+        qp.nj_in = r.h16 ? (Dv + 15) / 16 : (Dv + 7) / 8;
+        fill_hidden(qp, mq, r);
+        qp.w_last = mq.weight[last]; qp.ld_last = mq.ld[last]; qp.b_last = mq.bias[last];
+        qp.rows_per_wg = opt ? opt->decode_rows : 0;
+        qp.x_lr = x_lr; qp.coord = coord; qp.q0 = q0; qp.nq = nq; qp.H = H; qp.W = W; qp.rgb = rgb;
+        if (r.decode(*this, nq) == kHeadChain) {
+            const H16Ops& h = h16_ops(prec);
+            return h.head_decode_chain(qp, w, reinterpret_cast<const unsigned char*>(chain_blob()) + h.head_kv_chain_bytes(w, r.lo ? 1 : 0), r.lo ? 1 : 0, s);
+        }
+        if (r.kernel == kHeadWide) return h16_ops(prec).head_decode_fused_wide(qp, r.wide_mode, s);
+        return r.kernel == kHeadFused16 ? h16_ops(prec).head_decode_fused(qp, s) : head_decode_fused(qp, s);
+    }
+    int staged_chunk(long q0, int nq) const {
+        const long rows = (long)nq * J;
+        HeadRowsP hp;
+        hp.coord = coord; hp.cell = cell; hp.q0 = q0; hp.nq = nq; hp.chunk = chunk; hp.H = H; hp.W = W;
+        hp.local_size = w->local_size; hp.J = J;
+        hp.Tk = Tk; hp.Tv = Tv;
+        hp.tailK = w->k.weight[0] + D;      // columns [9C, 9C+4) of layer 0, stride ld -> packed copy below
+        hp.tailV = w->v.weight[0] + Dv;
+        hp.wk0 = wk0; hp.wv0 = wv0; hp.relu_k = mlp_act(w->k); hp.relu_v = mlp_act(w->v);
+        hp.Hk = bufA; hp.Hv = Hv; hp.q_idx = q_idx; hp.k_idx = k_idx;
+        hp.ld_tail_k = w->k.ld[0]; hp.ld_tail_v = w->v.ld[0];
+        HEAD_RUN(head_rows(hp, s));
+        // imnet_k layers 1..n-1 -> WK   (bufA holds layer-0 rows; ping-pong through bufB/bufA)
+        HEAD_RUN(mlp_layers_f32(w->k, 1, w->k.n_layers, bufA, wk0, wk0, bufB, bufA, WK, D, rows, s, "mlp_hidden", "mlp_hidden", "mlp_out_k"));
+        // imnet_v: layer-0 rows are in Hv
+        HEAD_RUN(mlp_layers_f32(w->v, 1, w->v.n_layers, Hv, wv0, wv0, bufA, bufB, WV, Dv, rows, s, "mlp_hidden", "mlp_hidden", "mlp_out_v"));
+        LocalAttnP lp{U, Dv, D, Dv, q_idx, k_idx, WK, D, WV, Dv, Z, Dv, nq, J, w->softmax_scale};
+        HEAD_RUN(local_attention(lp, s));
+        // imnet_q: layer 0 on Z, hidden layers, last layer fused with the bilinear residual
+        const ciaosr_mlp_t& mq = w->q;
+        const int last = mq.n_layers - 1;
+        const float* h;
+        HEAD_RUN(mlp_layers_f32(mq, 0, last, Z, Dv, Dv, bufA, bufB, nullptr, 0, nq, s, "mlp_in_q", "mlp_hidden_q", nullptr, &h));
+        DecodeP dp{h, mq.width[last - 1], mq.width[last - 1], mq.weight[last], mq.ld[last], mq.bias[last], x_lr, coord, q0, nq, H, W, rgb};
+        return decode_residual(dp, s);
+    }
+};
 
 }  // namespace ciaosr
 
@@ -136,26 +392,15 @@ extern "C" size_t ciaosr_head_workspace_bytes_opt(int H, int W, const ciaosr_hea
     return head_ws_bytes(head_plan(H, W, w, Q, opt));
 }
 
-static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w,
-                        const ciaosr_csattn_weights_t* csattn, const float* x_lr_nchw, const float* coord,
-                        const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt, void* workspace,
-                        size_t workspace_bytes, void* stream_, Prec prec) {
-    const Mode m = resolve_mode(prec, opt);
-    const bool bf16 = prec != kF32;                  // a 16-bit MFMA mode (bf16 or f16 entry)
-    const int route = opt ? opt->head_route : 0;
-    const bool lo = m.lo, x3 = m.x3;                 // x3: the activations of the three MLP chains as pairs too, every table in fp32
-    // f16x3 runs the wide-workgroup kernels (head_fused_wide.hip: its two activation arrays leave room for one workgroup per CU);
-    // f16 / f16-pairs keep the 128-row kernels with two workgroups per CU (head_fused_h16.hip) and take the wide form -- 256 rows, half
-    // the weight stream per MFMA, measured equal in time: one workgroup per CU exposes its gather phases -- only with head_route bit 3
-    const bool wide16 = x3 || (prec == kF16 && (route & CIAOSR_HEAD_WIDE_WG));
-    const int wide_mode = x3 ? 2 : (lo ? 1 : 0);
+static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
+                        const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
+                        void* workspace, size_t workspace_bytes, void* stream_, Prec prec) {
     CIAOSR_CHECK_ARG(feat_hwc && w && coord && cell && rgb && workspace && H >= 1 && W >= 1 && Q >= 1);
     CIAOSR_CHECK_ARG(options_ok(opt));
     CIAOSR_CHECK_ARG(w->channels >= 4 && (w->channels & 3) == 0 && (w->nonlocal_channels & 3) == 0);
     CIAOSR_CHECK_ARG(w->local_size >= 1 && w->local_size <= 3 && w->softmax_scale != 0.f);
     CIAOSR_CHECK_ARG(mlp_ok(w->q) && mlp_ok(w->k) && mlp_ok(w->v));
     CIAOSR_CHECK_ARG((w->nonlocal_channels > 0) == (csattn != nullptr));
-    hipStream_t s = (hipStream_t)stream_;
     const HeadPlan p = head_plan(H, W, w, Q, opt);
     // dims wiring of LocalImplicitSRNet.__init__ (ciaosr_net.py:61-76)
     CIAOSR_CHECK_ARG(w->k.in_dim == p.D + 4 && w->k.width[w->k.n_layers - 1] == p.D);
@@ -172,218 +417,46 @@ static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_w
         }
     }
     if (workspace_bytes < head_ws_bytes(p)) return CIAOSR_ERR_WORKSPACE;
-    CIAOSR_CHECK_ARG((size_t)p.HW * p.Dv * sizeof(float) < 0xFFFFFF00ull);   // 32-bit buffer offsets into U
-
+    CIAOSR_CHECK_ARG((size_t)p.HW * p.Dv * sizeof(float) < 0xFFFFFF00ull);   // 32-bit buffer offsets into U (and into its 16-bit copy)
     Arena ar(workspace, workspace_bytes);
-    const size_t R = (size_t)p.qc * p.J;
-    float* U = ar.take<float>((size_t)p.HW * p.Dv);
-    float* Tk = ar.take<float>((size_t)p.HW * p.wk0);
-    float* Tv = ar.take<float>((size_t)p.HW * p.wv0);
-    float* bufA = ar.take<float>(R * p.wmax);
-    float* bufB = ar.take<float>(R * p.wmax);
-    float* Hv = ar.take<float>(R * p.wv0);
-    float* WK = ar.take<float>(R * p.D);
-    float* WV = ar.take<float>(R * p.Dv);
-    float* Z = ar.take<float>((size_t)p.qcf * p.Dv);
-    int* q_idx = ar.take<int>(p.qc);
-    int* k_idx = ar.take<int>(R);
-    float* G = ar.take<float>((size_t)p.HW * 9 * kLdG);
-    float* QK = ar.take<float>((size_t)kQkChunk * p.D);
-    unsigned short* W5T = reinterpret_cast<unsigned short*>(ar.take<float>((size_t)128 * p.D + 64));
-    int* chain_flag = ar.take<int>(64);
-    char* csa_ws = ar.take<char>(p.csa_bytes);
+    const HeadCall c = {head_carve(p, [&](size_t floats) { return ar.take<float>(floats); }), head_route(p, prec, resolve_mode(prec, opt), opt, w),
+                        prec, feat_hwc, w, csattn, x_lr_nchw, coord, cell, chunk, rgb, opt, (hipStream_t)stream_};
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
-
-    int rc;
-#define RUN(x) do { rc = (x); if (rc != CIAOSR_OK) return rc; } while (0)
-    // unfold rows U[:, :9C] (net:132-136) and the non-local map into U[:, 9C:] (net:134-137)
-    if (w->no_unfold)     // feat_unfold=False (net:139-141): the "unfold" row is the pixel's C features (a 1x1 patch)
-        RUN(patch_rows(feat_hwc, p.C, H, W, p.C, 1, 1, 0, H, W, U, p.Dv, 0, 0.f, s, "head_unfold"));
-    else
-        RUN(patch_rows(feat_hwc, p.C, H, W, p.C, 3, 1, 1, H, W, U, p.Dv, 0, 0.f, s, "head_unfold"));
-    for (int i = 0; i < n_scales; ++i)     // one C-column slice per scale, in the order of multi_scale (csa:528 torch.cat(res_y, dim=1))
-        RUN((prec == kF16 ? ciaosr_cs_attn_f16 : prec == kBF16 ? ciaosr_cs_attn_bf16 : ciaosr_cs_attn_f32)(feat_hwc, p.C, H, W, csattn + i, U + p.D + (size_t)i * p.C, p.Dv, opt, csa_ws,
-                                                              p.csa_bytes, stream_));
-    const bool fused = !(route & CIAOSR_HEAD_STAGED) && w->local_size == 2 && chain_fused_ok(w->k, false, bf16) &&
-                       chain_fused_ok(w->v, false, bf16) && chain_fused_ok(w->q, true, bf16) && (p.Dv & 7) == 0;
-    if (bf16 && !fused) return CIAOSR_ERR_UNSUPPORTED;   // the 16-bit modes exist for the fused kernels only
-    if (x3) {                                            // the pair kernels read every lo fragment unconditionally
-        for (int i = 1; i < w->k.n_layers; ++i) CIAOSR_CHECK_ARG(w->k.frag16_lo[i]);
-        for (int i = 1; i < w->v.n_layers; ++i) CIAOSR_CHECK_ARG(w->v.frag16_lo[i]);
-        for (int i = 0; i + 1 < w->q.n_layers; ++i) CIAOSR_CHECK_ARG(w->q.frag16_lo[i]);
-    }
-    // exact layer-1 hoist: T = U . W1[:, :fan]^T + b1, one row per LR pixel
-    // f16 mode: on the 16-bit GEMM from a half copy of U (the staged route's activation buffers are free on the fused route)
-    const size_t u16_bytes = (size_t)p.HW * p.Dv * 2 + 256, w16_bytes = (size_t)(p.wk0 + p.wv0) * p.Dv * 2 + 512;
-    if (m.hoist16 && (p.D & 7) == 0 && (p.Dv & 7) == 0 && u16_bytes + w16_bytes <= R * p.wmax * sizeof(float) &&
-        (size_t)p.HW * p.Dv * 2 < 0xFFFFFF00ull) {
-        const H16Ops& h = h16_ops(prec);
-        unsigned short* U16 = reinterpret_cast<unsigned short*>(bufA);
-        unsigned short* Wk16 = U16 + round_up((size_t)p.HW * p.Dv, 128);
-        unsigned short* Wv16 = Wk16 + round_up((size_t)p.wk0 * p.D, 128);
-        RUN(h.cast_rows(U, p.Dv, U16, p.Dv, p.HW, p.Dv, s));
-        RUN(h.cast_rows(w->k.weight[0], w->k.ld[0], Wk16, p.D, p.wk0, p.D, s));
-        RUN(h.cast_rows(w->v.weight[0], w->v.ld[0], Wv16, p.Dv, p.wv0, p.Dv, s));
-        RUN(h.conv1x1(U16, p.Dv, Wk16, p.D, w->k.bias[0], nullptr, 0, Tk, p.wk0, nullptr, 0, nullptr, 0, p.HW, p.wk0, p.D, s, "head_table_f16"));
-        RUN(h.conv1x1(U16, p.Dv, Wv16, p.Dv, w->v.bias[0], nullptr, 0, Tv, p.wv0, nullptr, 0, nullptr, 0, p.HW, p.wv0, p.Dv, s, "head_table_f16"));
-    } else if (gemm_small_ok(p.HW, p.wk0, p.D, p.Dv, w->k.ld[0]) && gemm_small_ok(p.HW, p.wv0, p.Dv, p.Dv, w->v.ld[0]) && p.HW <= 4096) {
-        RUN(gemm_small_f32(U, p.Dv, w->k.weight[0], w->k.ld[0], w->k.bias[0], Tk, p.wk0, nullptr, 0, nullptr, 0, p.HW, p.wk0, p.D,
-                           CIAOSR_ACT_NONE, 0.f, 1.f, s, "head_table"));
-        RUN(gemm_small_f32(U, p.Dv, w->v.weight[0], w->v.ld[0], w->v.bias[0], Tv, p.wv0, nullptr, 0, nullptr, 0, p.HW, p.wv0, p.Dv,
-                           CIAOSR_ACT_NONE, 0.f, 1.f, s, "head_table"));
-    } else {
-        RUN(gemm_f32(U, p.Dv, w->k.weight[0], w->k.ld[0], false, Tk, p.wk0, w->k.bias[0], p.HW, p.wk0, p.D, 1.f,
-                     CIAOSR_ACT_NONE, 0.f, s, "head_table"));
-        RUN(gemm_f32(U, p.Dv, w->v.weight[0], w->v.ld[0], false, Tv, p.wv0, w->v.bias[0], p.HW, p.wv0, p.Dv, 1.f,
-                     CIAOSR_ACT_NONE, 0.f, s, "head_table"));
-    }
-
-    // logit table of imnet_k's output layer (exact fold, head_ops.hip): pays off when queries outnumber LR pixels
-    const bool use_table = fused && !(route & CIAOSR_HEAD_NO_LOGIT_TABLE) && w->k.width[w->k.n_layers - 1] == p.D && w->k.width[w->k.n_layers - 2] == 256 &&
-                           (long)Q * p.J > (long)p.HW * 9 && (size_t)p.HW * 9 * kLdG * sizeof(float) < 0xFFFFFF00ull;
-    if (use_table) {
-        const int last = w->k.n_layers - 1;
-        const long total = (long)p.HW * 9;
-        // 16-bit modes: the table GEMM on the 16-bit MFMA (fp32 table out).  (Half-pairs mode: the exact-fp32 GEMM here was measured
-        // and changes nothing -- max |delta| 1.04e-3 -> 1.14e-3 on the full-tile vector, +0.9 ms: W5's rounding is not what limits it.)
-        const bool table16 = m.table16 && (p.D & 7) == 0;
-        if (table16) RUN(transpose_cast_h16(w->k.weight[last], w->k.ld[last], p.D, 256, W5T, prec == kF16, s));
-        // fp32, C = 64: nine Winograd convolutions of the product maps Pi_o = F . shift_o(F) (same sums as the GEMM rows below,
-        // re-associated through the transform; 2.25x fewer multiplies).  The maps live where the GEMM would keep its row chunk.
-        const bool table_wino = !m.table16 && w->k_out_wino && !(route & CIAOSR_HEAD_TABLE_GEMM) && p.C == 64 && !w->no_unfold &&
-                                p.HW >= 512 && p.HW <= kQkChunk;
-        if (table_wino) {
-            RUN(qk_maps(feat_hwc, p.C, p.C, H, W, QK, s));
-            if (w->k_out_wino4 && !(route & CIAOSR_HEAD_TABLE_WINO2)) RUN(wino4_table_f32(QK, H, W, w->k_out_wino4, 4, G, kLdG, s));
-            else RUN(wino_table_f32(QK, H, W, w->k_out_wino, 4, G, kLdG, s));
-            RUN(qk_rows(U, p.Dv, p.D, H, W, 0, (int)total, w->k.bias[last], nullptr, G, kLdG, 3, s));
-        }
-        for (long r0 = 0; r0 < total && !table_wino; r0 += kQkChunk) {
-            const int nr = (int)((total - r0) < kQkChunk ? (total - r0) : kQkChunk);
-            RUN(qk_rows(U, p.Dv, p.D, H, W, r0, nr, w->k.bias[last], QK, G, kLdG, table16 ? (int)prec : 0, s));
-            if (table16) {
-                RUN(h16_ops(prec).gemm_nt(reinterpret_cast<const unsigned short*>(QK), p.D, W5T, p.D, G + (size_t)r0 * kLdG, kLdG, false, nr,
-                                          256, p.D, 1.f, s, prec == kF16 ? "head_logit_table_f16" : "head_logit_table_bf16", 0));
-                continue;
-            }
-            // G[r][n] = sum_d QK[r][d] * W5k[d][n]: the Linear weight [D][256] is the [K][N] operand as stored
-            RUN(gemm_f32(QK, p.D, w->k.weight[last], w->k.ld[last], true, G + (size_t)r0 * kLdG, kLdG, nullptr, nr, 256, p.D,
-                         1.f, CIAOSR_ACT_NONE, 0.f, s, "head_logit_table"));
-        }
-    }
-    const int step = fused ? p.qcf : p.qc;
+    if (c.r.refusal == CIAOSR_ERR_UNSUPPORTED) return CIAOSR_ERR_UNSUPPORTED;     // the route's refusals: before the first launch
+    CIAOSR_CHECK_ARG(c.r.refusal == CIAOSR_OK);                                   // x3 without every lo fragment
+    HEAD_RUN(c.unfold());
+    HEAD_RUN(c.cs_attn(n_scales));
+    HEAD_RUN(c.layer0_tables());
+    HEAD_RUN(c.logit_table());
+    const int step = c.r.fused ? p.qcf : p.qc;
     for (long q0 = 0; q0 < Q; q0 += step) {
         const int nq = (int)((Q - q0) < step ? (Q - q0) : step);
-        const long rows = (long)nq * p.J;
-        if (fused) {
-            FusedKVP kp;
-            kp.coord = coord; kp.cell = cell; kp.q0 = q0; kp.nq = nq; kp.chunk = chunk; kp.H = H; kp.W = W;
-            kp.U = U; kp.ldu = p.Dv; kp.D = p.D; kp.Dv = p.Dv;
-            kp.u_bytes = (unsigned)((size_t)p.HW * p.Dv * sizeof(float));
-            fill_chain(kp.k, w->k, Tk, p.D, bf16, lo);
-            fill_chain(kp.v, w->v, Tv, p.Dv, bf16, lo);
-            kp.softmax_scale = w->softmax_scale;
-            kp.Z = Z; kp.ldz = p.Dv;
-            kp.rows_per_wg = opt ? opt->kv_rows : 0;
-            kp.G = use_table ? G : nullptr; kp.ldg = kLdG; kp.g_bytes = (unsigned)((size_t)p.HW * 9 * kLdG * sizeof(float));
-            kp.gate = nullptr;
-            // 16-bit default: the weights-stationary, register-chained kernel (head_chain_h16.hip) where its weight stream is given and the
-            // logit table exists; the 128-row kernel is launched behind it, gated on the flag the chained kernel raises when a key leaves its
-            // query's 3x3 neighbourhood (cannot happen for 0 < cell < 1): it then redoes the launch, else it returns at once
-            const void* blob = lo ? w->chain16_pairs : w->chain16;
-            const bool chained = bf16 && !wide16 && !x3 && use_table && blob && !(route & CIAOSR_HEAD_NO_CHAIN) && h16_ops(prec).head_chain_ok(w) &&
-                                 (size_t)nq * p.Dv * 2 < 0xFFFFFF00ull;
-            if (chained) {
-                if (hipMemsetAsync(chain_flag, 0, sizeof(int), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-                RUN(h16_ops(prec).head_kv_chain(kp, w, blob, lo ? 1 : 0, opt ? opt->query_grid_w : 0, chain_flag, s));
-                kp.gate = chain_flag;
-            }
-            RUN(wide16 ? (prec == kF16 ? f16::wide::head_kv_fused_wide(kp, wide_mode, s) : b16::wide::head_kv_fused_wide(kp, wide_mode, s))
-                       : bf16 ? h16_ops(prec).head_kv_fused(kp, s) : head_kv_fused(kp, s));
-            const ciaosr_mlp_t& mq = w->q;
-            FusedQP qp;
-            qp.Z = Z; qp.ldz = p.Dv; qp.Dv = p.Dv;
-            qp.frag_in = bf16 ? mq.frag16[0] : (const void*)mq.frag[0]; qp.bias_in = mq.bias[0];
-            qp.frag_in_lo = (bf16 && lo) ? mq.frag16_lo[0] : nullptr;
-            qp.nj_in = bf16 ? (p.Dv + 15) / 16 : (p.Dv + 7) / 8;
-            qp.n_hidden = mq.n_layers - 2;
-            for (int i = 0; i < qp.n_hidden; ++i) {
-                qp.frag_hidden[i] = bf16 ? mq.frag16[i + 1] : (const void*)mq.frag[i + 1];
-                qp.frag_hidden_lo[i] = (bf16 && lo) ? mq.frag16_lo[i + 1] : nullptr;
-                qp.bias_hidden[i] = mq.bias[i + 1];
-            }
-            qp.w_last = mq.weight[mq.n_layers - 1]; qp.ld_last = mq.ld[mq.n_layers - 1];
-            qp.b_last = mq.bias[mq.n_layers - 1];
-            qp.rows_per_wg = opt ? opt->decode_rows : 0;
-            qp.x_lr = x_lr_nchw; qp.coord = coord; qp.q0 = q0; qp.nq = nq; qp.H = H; qp.W = W; qp.rgb = rgb;
-            // imnet_q through the same weights-stationary form where the blob carries its stream (Dv a multiple of 128, 256-wide layers)
-            if (chained && !(route & CIAOSR_HEAD_NO_DECODE_CHAIN) && h16_ops(prec).head_decode_chain_ok(w)) {
-                const unsigned char* qblob = reinterpret_cast<const unsigned char*>(blob) + h16_ops(prec).head_kv_chain_bytes(w, lo ? 1 : 0);
-                RUN(h16_ops(prec).head_decode_chain(qp, w, qblob, lo ? 1 : 0, s));
-                continue;
-            }
-            RUN(wide16 ? (prec == kF16 ? f16::wide::head_decode_fused_wide(qp, wide_mode, s) : b16::wide::head_decode_fused_wide(qp, wide_mode, s))
-                       : bf16 ? h16_ops(prec).head_decode_fused(qp, s) : head_decode_fused(qp, s));
-            continue;
+        if (c.r.fused) {
+            HEAD_RUN(c.kv(q0, nq));
+            HEAD_RUN(c.decode(q0, nq));
+        } else {
+            HEAD_RUN(c.staged_chunk(q0, nq));
         }
-        HeadRowsP hp;
-        hp.coord = coord; hp.cell = cell; hp.q0 = q0; hp.nq = nq; hp.chunk = chunk; hp.H = H; hp.W = W;
-        hp.local_size = w->local_size; hp.J = p.J;
-        hp.Tk = Tk; hp.Tv = Tv;
-        hp.tailK = w->k.weight[0] + p.D;      // columns [9C, 9C+4) of layer 0, stride ld -> packed copy below
-        hp.tailV = w->v.weight[0] + p.Dv;
-        hp.wk0 = p.wk0; hp.wv0 = p.wv0; hp.relu_k = mlp_act(w->k); hp.relu_v = mlp_act(w->v);
-        hp.Hk = bufA; hp.Hv = Hv; hp.q_idx = q_idx; hp.k_idx = k_idx;
-        hp.ld_tail_k = w->k.ld[0]; hp.ld_tail_v = w->v.ld[0];
-        RUN(head_rows(hp, s));
-        // imnet_k layers 1..n-1 -> WK   (bufA holds layer-0 rows; ping-pong through bufB/bufA)
-        RUN(run_tail(w->k, bufA, p.wk0, bufB, bufA, WK, p.D, rows, s, "mlp_hidden", "mlp_out_k"));
-        // imnet_v: layer-0 rows are in Hv
-        RUN(run_tail(w->v, Hv, p.wv0, bufA, bufB, WV, p.Dv, rows, s, "mlp_hidden", "mlp_out_v"));
-        LocalAttnP lp{U, p.Dv, p.D, p.Dv, q_idx, k_idx, WK, p.D, WV, p.Dv, Z, p.Dv, nq, p.J, w->softmax_scale};
-        RUN(local_attention(lp, s));
-        // imnet_q: layer 0 on Z, hidden layers, last layer fused with the bilinear residual
-        const ciaosr_mlp_t& mq = w->q;
-        const float* cur = Z;
-        int ld_cur = p.Dv, k_cur = p.Dv;
-        float* pp[2] = {bufA, bufB};
-        int flip = 0;
-        for (int i = 0; i + 1 < mq.n_layers; ++i) {
-            RUN(gemm_f32(cur, ld_cur, mq.weight[i], mq.ld[i], false, pp[flip], mq.width[i], mq.bias[i], nq,
-                         mq.width[i], k_cur, 1.f, mlp_act(mq), 0.f, s, i == 0 ? "mlp_in_q" : "mlp_hidden_q"));
-            cur = pp[flip]; ld_cur = mq.width[i]; k_cur = mq.width[i];
-            flip ^= 1;
-        }
-        DecodeP dp{cur, ld_cur, k_cur, mq.weight[mq.n_layers - 1], mq.ld[mq.n_layers - 1],
-                   mq.bias[mq.n_layers - 1], x_lr_nchw, coord, q0, nq, H, W, rgb};
-        RUN(decode_residual(dp, s));
     }
-#undef RUN
     return CIAOSR_OK;
 }
 
-extern "C" int ciaosr_head_forward_f32(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w,
-                                       const ciaosr_csattn_weights_t* csattn, const float* x_lr_nchw,
-                                       const float* coord, const float* cell, int Q, int chunk, float* rgb,
-                                       const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream) {
-    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes,
-                        stream, kF32);
+extern "C" int ciaosr_head_forward_f32(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
+                                       const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes, stream, kF32);
 }
 
-extern "C" int ciaosr_head_forward_bf16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w,
-                                        const ciaosr_csattn_weights_t* csattn, const float* x_lr_nchw,
-                                        const float* coord, const float* cell, int Q, int chunk, float* rgb,
-                                        const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream) {
-    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes,
-                        stream, kBF16);
+extern "C" int ciaosr_head_forward_bf16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
+                                        const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes, stream, kBF16);
 }
 
-extern "C" int ciaosr_head_forward_f16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w,
-                                       const ciaosr_csattn_weights_t* csattn, const float* x_lr_nchw,
-                                       const float* coord, const float* cell, int Q, int chunk, float* rgb,
-                                       const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream) {
-    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes,
-                        stream, kF16);
+extern "C" int ciaosr_head_forward_f16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
+                                       const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes, stream, kF16);
 }
 
 // ---- staged MLPRefiner (mlp_refiner.py:87-102), layer by layer, no hoist -------------------------------------
@@ -410,6 +483,7 @@ extern "C" int ciaosr_mlp_forward_f32(const float* x, int ld_x, const ciaosr_mlp
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
     const float* cur = x;
     int ld_cur = ld_x, k_cur = m->in_dim;
+    // Not mlp_layers_f32: these hidden rows have one stride (wmax) and the last layer RUN writes `out`, activated unless it is the MLP's last
     for (int i = 0; i < n; ++i) {
         const bool last = i + 1 == n;
         float* dst = last ? out : pp[i & 1];
@@ -425,15 +499,22 @@ extern "C" int ciaosr_mlp_forward_f32(const float* x, int ld_x, const ciaosr_mlp
 // ---- staged MLP with 16-bit operands (SURVEY 8(b-2) "ciaosr_mlp5_bf16"): every Linear on the 16-bit MFMA GEMM, activations 16-bit between layers,
 // fp32 accumulation, biases and the last layer's output fp32.  ReLU MLPs only (what the 16-bit modes are defined for).
 static size_t round8(size_t v) { return (v + 7) & ~(size_t)7; }
+// Row lengths in 16-bit elements, each padded to a multiple of 8: x (k0), the widest layer output (wmax: an activation row, and the rows
+// of the widest weight matrix) and the widest contraction (kmax: a weight row)
+struct Mlp16Sizes { size_t k0, wmax, kmax; };
+static Mlp16Sizes mlp16_sizes(const ciaosr_mlp_t* m) {
+    Mlp16Sizes z = {round8((size_t)m->in_dim), 0, round8((size_t)m->in_dim)};
+    for (int i = 0; i < m->n_layers; ++i) {
+        z.wmax = std::max(z.wmax, round8((size_t)m->width[i]));
+        if (i + 1 < m->n_layers) z.kmax = std::max(z.kmax, round8((size_t)m->width[i]));
+    }
+    return z;
+}
 extern "C" size_t ciaosr_mlp_workspace_bytes_16(const ciaosr_mlp_t* m, int rows) {
     if (!m || rows <= 0 || !mlp_ok(*m)) return 0;
-    size_t wmax = 0, kmax = round8((size_t)m->in_dim);
-    for (int i = 0; i < m->n_layers; ++i) {
-        wmax = std::max(wmax, round8((size_t)m->width[i]));
-        if (i + 1 < m->n_layers) kmax = std::max(kmax, round8((size_t)m->width[i]));
-    }
+    const Mlp16Sizes z = mlp16_sizes(m);
     // x as 16 bits, two ping-pong activation buffers, one layer's weights as 16 bits; 256 B of slack per buffer for alignment
-    return ((size_t)rows * round8((size_t)m->in_dim) + 2 * (size_t)rows * wmax + wmax * kmax) * 2 + 4 * 256;
+    return ((size_t)rows * z.k0 + 2 * (size_t)rows * z.wmax + z.wmax * z.kmax) * 2 + 4 * 256;
 }
 
 template <typename CastFn, typename LinFn>
@@ -447,15 +528,11 @@ static int mlp_forward_16(CastFn cast_rows, LinFn linear, const float* x, int ld
     for (int i = 0; i < m->n_layers; ++i) CIAOSR_CHECK_ARG((m->width[i] & 3) == 0 || i + 1 == m->n_layers);
     if (workspace_bytes < ciaosr_mlp_workspace_bytes_16(m, rows)) return CIAOSR_ERR_WORKSPACE;
     Arena ar(workspace, workspace_bytes);
-    size_t wmax = 0, kmax = round8((size_t)m->in_dim);
-    for (int i = 0; i < m->n_layers; ++i) {
-        wmax = std::max(wmax, round8((size_t)m->width[i]));
-        if (i + 1 < m->n_layers) kmax = std::max(kmax, round8((size_t)m->width[i]));
-    }
-    const int k0 = (int)round8((size_t)m->in_dim);
-    unsigned short* x16 = ar.take<unsigned short>((size_t)rows * k0);
-    unsigned short* pp[2] = {ar.take<unsigned short>((size_t)rows * wmax), ar.take<unsigned short>((size_t)rows * wmax)};
-    unsigned short* w16 = ar.take<unsigned short>(wmax * kmax);
+    const Mlp16Sizes z = mlp16_sizes(m);
+    const int k0 = (int)z.k0;
+    unsigned short* x16 = ar.take<unsigned short>((size_t)rows * z.k0);
+    unsigned short* pp[2] = {ar.take<unsigned short>((size_t)rows * z.wmax), ar.take<unsigned short>((size_t)rows * z.wmax)};
+    unsigned short* w16 = ar.take<unsigned short>(z.wmax * z.kmax);
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
     // cast_rows zeroes the pad columns [cols, ld_dst): K is padded to a multiple of 8 on both operands
     int rc = cast_rows(x, ld_x, x16, k0, (long)rows, (m->in_dim + 3) & ~3, s);

@@ -274,18 +274,22 @@ struct H16Ops {
     decltype(&b16::head_decode_chain_ok) head_decode_chain_ok;
     decltype(&b16::head_kv_chain_bytes) head_kv_chain_bytes;
     decltype(&b16::head_decode_chain_h16) head_decode_chain;
+    decltype(&b16::wide::head_kv_fused_wide) head_kv_fused_wide;
+    decltype(&b16::wide::head_decode_fused_wide) head_decode_fused_wide;
 };
 inline const H16Ops& h16_ops(Prec prec) {
     static const H16Ops kB = {b16::gemm_h16_nt, b16::cast_rows_h16, b16::softmax_rows_h16, b16::head_kv_fused_h16,
                               b16::head_decode_fused_h16, b16::cast_group_h16, b16::dense_layer_h16, b16::conv1x1_h16,
                               b16::cast_many_h16, b16::rows_to_f32_h16, b16::softmax_gemm_h16_nt,
                               b16::softmax_gemm_scratch_floats, b16::head_chain_ok, b16::head_kv_chain_h16,
-                              b16::head_decode_chain_ok, b16::head_kv_chain_bytes, b16::head_decode_chain_h16};
+                              b16::head_decode_chain_ok, b16::head_kv_chain_bytes, b16::head_decode_chain_h16,
+                              b16::wide::head_kv_fused_wide, b16::wide::head_decode_fused_wide};
     static const H16Ops kH = {f16::gemm_h16_nt, f16::cast_rows_h16, f16::softmax_rows_h16, f16::head_kv_fused_h16,
                               f16::head_decode_fused_h16, f16::cast_group_h16, f16::dense_layer_h16, f16::conv1x1_h16,
                               f16::cast_many_h16, f16::rows_to_f32_h16, f16::softmax_gemm_h16_nt,
                               f16::softmax_gemm_scratch_floats, f16::head_chain_ok, f16::head_kv_chain_h16,
-                              f16::head_decode_chain_ok, f16::head_kv_chain_bytes, f16::head_decode_chain_h16};
+                              f16::head_decode_chain_ok, f16::head_kv_chain_bytes, f16::head_decode_chain_h16,
+                              f16::wide::head_kv_fused_wide, f16::wide::head_decode_fused_wide};
     return prec == kF16 ? kH : kB;
 }
 
