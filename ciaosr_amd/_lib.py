@@ -33,6 +33,12 @@ class HeadWeightsT(C.Structure):
                 ('chain16', C.c_void_p), ('chain16_pairs', C.c_void_p)]
 
 
+class HeadSceneT(C.Structure):
+    """ciaosr_head_scene_t: what ciaosr_head_prepare_* built (include/ciaosr_hip.h); offsets and total in 256-byte units."""
+    _fields_ = [(n, C.c_int) for n in ('magic', 'H', 'W', 'C', 'Cn', 'D', 'Dv', 'J', 'q_plan', 'precision', 'route',
+                                       'off_u', 'off_tk', 'off_tv', 'off_g', 'total')]
+
+
 class CsAttnWeightsT(C.Structure):
     _fields_ = [('channels', C.c_int), ('scale', C.c_int),
                 ('w_match1', C.c_void_p), ('b_match1', C.c_void_p), ('slope_match1', C.c_float),
@@ -111,6 +117,7 @@ SIGNATURES = {
     'ciaosr_cs_attn_f32': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
     'ciaosr_cs_attn_bf16': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
     'ciaosr_make_coord_cell_f32': (_I, [_P, _P, _I, _I, _P]),
+    'ciaosr_make_coord_cell_window_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     'ciaosr_fragment_floats': (_S, [_I, _I]),
     'ciaosr_pack_fragments_f32': (_I, [_P, _I, _I, _I, _P, _P]),
     'ciaosr_cs_attn_f16': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
@@ -145,6 +152,14 @@ SIGNATURES = {
                                       _I, _I, _P, _O, _P, _S, _P]),
     'ciaosr_head_forward_f16': (_I, [_P, _I, _I, C.POINTER(HeadWeightsT), C.POINTER(CsAttnWeightsT), _P, _P, _P,
                                       _I, _I, _P, _O, _P, _S, _P]),
+    'ciaosr_head_route_code': (_I, [_I, _I, C.POINTER(HeadWeightsT), _I, _I, _O]),
+    'ciaosr_head_scene_bytes': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I, _O]),
+    'ciaosr_head_prepare_workspace_bytes': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I, _O]),
+    'ciaosr_head_query_workspace_bytes': (_S, [C.POINTER(HeadSceneT), C.POINTER(HeadWeightsT), _I, _O]),
+    **{'ciaosr_head_prepare_' + sfx: (_I, [_P, _I, _I, C.POINTER(HeadWeightsT), C.POINTER(CsAttnWeightsT), _I, _O, _P, _S,
+                                          C.POINTER(HeadSceneT), _P, _S, _P]) for sfx in ('f32', 'bf16', 'f16')},
+    **{'ciaosr_head_query_' + sfx: (_I, [_P, _S, C.POINTER(HeadSceneT), C.POINTER(HeadWeightsT), _P, _P, _P, _I, _I, _P, _O, _P, _S, _P])
+       for sfx in ('f32', 'bf16', 'f16')},
     'ciaosr_rdn_workspace_bytes': (_S, [_I, _I, C.POINTER(RdnWeightsT)]),
     'ciaosr_rdn_forward_f32': (_I, [_P, _I, _I, C.POINTER(RdnWeightsT), _P, _O, _P, _S, _P]),
     'ciaosr_rdn_forward_bf16': (_I, [_P, _I, _I, C.POINTER(RdnWeightsT), _P, _O, _P, _S, _P]),
@@ -170,7 +185,7 @@ SIGNATURES = {
 
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)
 STRUCTS = {'ciaosr_options_t': OptionsT, 'ciaosr_csattn_weights_t': CsAttnWeightsT, 'ciaosr_mlp_t': MlpT,
-           'ciaosr_head_weights_t': HeadWeightsT, 'ciaosr_conv_t': ConvT, 'ciaosr_rdn_weights_t': RdnWeightsT,
+           'ciaosr_head_weights_t': HeadWeightsT, 'ciaosr_head_scene_t': HeadSceneT, 'ciaosr_conv_t': ConvT, 'ciaosr_rdn_weights_t': RdnWeightsT,
            'ciaosr_edsr_weights_t': EdsrWeightsT, 'ciaosr_swin_block_t': SwinBlockT,
            'ciaosr_swinir_weights_t': SwinirWeightsT}
 

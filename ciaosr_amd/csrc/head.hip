@@ -25,6 +25,9 @@
 //                         local_attention, mlp_in_q, mlp_hidden_q x n, decode_residual       Hv -> bufA <-> bufB -> WV;  U, WK, WV -> Z -> bufA <-> bufB -> rgb
 // The fused routes need local_size 2, ReLU chains of 256-wide layers and packed fragments; everything else, and head_route bit 0, runs staged
 // (fp32 only: a 16-bit entry without a fused route is refused).  Staged form: every stage is its own kernel with a clean roofline.
+// The stages above the dashed line depend on the LR image only (HeadCall::per_image), those below on the queries (per_query).
+// ciaosr_head_prepare_* runs the first half into a caller-owned scene (U, Tk, Tv, [G]), ciaosr_head_query_* the second half from it, any
+// number of times: the same stage functions, the same route (planned for q_plan queries), the same carve list with an owner per buffer.
 #include "ops.h"
 
 namespace ciaosr {
@@ -80,10 +83,10 @@ static HeadPlan head_plan(int H, int W, const ciaosr_head_weights_t* w, int Q, c
 struct HeadBuffers : HeadPlan {
     float *U, *Tk, *Tv, *bufA, *bufB, *Hv, *WK, *WV, *Z, *G, *QK, *csa_ws;
     int *q_idx, *k_idx, *chain_flag;
-    unsigned short* W5T;
-    // h16 layer-0 tables: 16-bit copies of U [HW][Dv] and of both layer-0 weights [wk0][D], [wv0][Dv], where the staged route keeps its
-    // activations (free on the fused routes, the only ones with a 16-bit mode): u16_fits
-    unsigned short* u16() const { return reinterpret_cast<unsigned short*>(bufA); }
+    unsigned short *W5T, *H16;
+    // h16 layer-0 tables: 16-bit copies of U [HW][Dv] and of both layer-0 weights [wk0][D], [wv0][Dv].  One call: where the staged route
+    // keeps its activations (H16 = bufA, free on the fused routes, the only ones with a 16-bit mode): u16_fits.  A scene: their own buffer
+    unsigned short* u16() const { return H16; }
     unsigned short* wk16() const { return u16() + round_up((size_t)HW * Dv, 128); }
     unsigned short* wv16() const { return wk16() + round_up((size_t)wk0 * D, 128); }
     // the nine product maps [9][HW][C] of the Winograd logit table, where the GEMM forms keep a chunk of rows [kQkChunk][9C]: qk_maps_fits
@@ -95,30 +98,52 @@ static bool u16_fits(const HeadPlan& p) {                                       
     return (size_t)p.HW * p.Dv * 2 + 256 + (size_t)(p.wk0 + p.wv0) * p.Dv * 2 + 512 <= p.R() * p.wmax * sizeof(float);
 }
 static bool qk_maps_fits(const HeadPlan& p) { return p.HW <= kQkChunk; }                               // not above 256 x 256 pixels
+static size_t h16_floats(const HeadPlan& p) {                                                          // u16 | wk16 | wv16, as floats
+    return (round_up((size_t)p.HW * p.Dv, 128) + round_up((size_t)p.wk0 * p.D, 128) + (size_t)p.wv0 * p.Dv + 1) / 2;
+}
 
-// The one list of carve-outs, in carve order: take(floats) is Arena::take (256-byte aligned) for a call, a running sum for the byte count.
+// Who owns a buffer when the head runs as prepare + query (ciaosr_head_prepare_* / ciaosr_head_query_*): the scene holds what the per-image
+// stages write and the per-query kernels read, the two workspaces what only one side touches.  ciaosr_head_forward_* carves all of them
+// from its one workspace.
+enum Owner { kScene, kPrepare, kQuery };
+struct SceneLayout { bool logit, h16; };      // what of the scene's optional buffers its route needs
+
+// The one list of carve-outs, in carve order: take(owner, floats) is Arena::take (256-byte aligned) on the owner's arena for a call, a
+// running sum for a byte count.  scene = nullptr: the one-call layout (every buffer, the 16-bit copies inside bufA).
 template <class Take>
-static HeadBuffers head_carve(const HeadPlan& p, Take take) {
+static HeadBuffers head_carve(const HeadPlan& p, const SceneLayout* scene, Take take) {
     const size_t HW = p.HW, R = p.R();
     HeadBuffers b = {p};
-    b.U = take(HW * p.Dv);                            // unfold rows [HW][D] and, behind them, the non-local maps [HW][Cn]
-    b.Tk = take(HW * p.wk0); b.Tv = take(HW * p.wv0);       // layer-0 tables
-    b.bufA = take(R * p.wmax); b.bufB = take(R * p.wmax);   // staged: ping-pong activations
-    b.Hv = take(R * p.wv0);                           // staged: layer-0 rows of the value chain, kept while the key chain runs
-    b.WK = take(R * p.D); b.WV = take(R * p.Dv);      // staged: the chains' outputs
-    b.Z = take((size_t)p.qcf * p.Dv);                 // attention output of a chunk (sized for the fused routes' chunk)
-    b.q_idx = reinterpret_cast<int*>(take(p.qc)); b.k_idx = reinterpret_cast<int*>(take(R));
-    b.G = take(HW * 9 * kLdG);                        // logit table
-    b.QK = take((size_t)kQkChunk * p.D);              // one chunk of its GEMM rows
-    b.W5T = reinterpret_cast<unsigned short*>(take((size_t)128 * p.D + 64));   // 16-bit modes: transposed 16-bit copy [256][D] of imnet_k's output layer
-    b.chain_flag = reinterpret_cast<int*>(take(64));  // 16-bit chained kernel: its "redo with the 128-row kernel" flag
-    b.csa_ws = take(p.csa_bytes / sizeof(float));     // cs_attn's workspace (a whole number of floats: csa_carve_bytes)
+    b.U = take(kScene, HW * p.Dv);                    // unfold rows [HW][D] and, behind them, the non-local maps [HW][Cn]
+    b.Tk = take(kScene, HW * p.wk0); b.Tv = take(kScene, HW * p.wv0);       // layer-0 tables
+    b.bufA = take(kQuery, R * p.wmax); b.bufB = take(kQuery, R * p.wmax);   // staged: ping-pong activations
+    b.Hv = take(kQuery, R * p.wv0);                   // staged: layer-0 rows of the value chain, kept while the key chain runs
+    b.WK = take(kQuery, R * p.D); b.WV = take(kQuery, R * p.Dv);            // staged: the chains' outputs
+    b.Z = take(kQuery, (size_t)p.qcf * p.Dv);         // attention output of a chunk (sized for the fused routes' chunk)
+    b.q_idx = reinterpret_cast<int*>(take(kQuery, p.qc)); b.k_idx = reinterpret_cast<int*>(take(kQuery, R));
+    b.G = take(kScene, !scene || scene->logit ? HW * 9 * kLdG : 0);         // logit table
+    b.QK = take(kPrepare, (size_t)kQkChunk * p.D);    // one chunk of its GEMM rows
+    b.W5T = reinterpret_cast<unsigned short*>(take(kPrepare, (size_t)128 * p.D + 64));   // 16-bit modes: transposed 16-bit copy [256][D] of imnet_k's output layer
+    b.chain_flag = reinterpret_cast<int*>(take(kQuery, 64));  // 16-bit chained kernel: its "redo with the 128-row kernel" flag
+    b.csa_ws = take(kPrepare, p.csa_bytes / sizeof(float));   // cs_attn's workspace (a whole number of floats: csa_carve_bytes)
+    b.H16 = reinterpret_cast<unsigned short*>(scene ? take(kPrepare, scene->h16 ? h16_floats(p) : 0) : b.bufA);
     return b;
 }
 static size_t head_ws_bytes(const HeadPlan& p) {
     size_t n = 0;
-    head_carve(p, [&](size_t floats) { n += floats; return (float*)nullptr; });
+    head_carve(p, nullptr, [&](Owner, size_t floats) { n += floats; return (float*)nullptr; });
     return n * sizeof(float) + 32 * 256;              // room for the 256-byte alignment of each carve-out
+}
+// prepare + query: each owner's buffers from its own arena (nullptr: not this side's), at the offsets the same takes give every time
+static HeadBuffers head_carve_split(const HeadPlan& p, const SceneLayout& lay, Arena* const (&ar)[3]) {
+    return head_carve(p, &lay, [&](Owner o, size_t floats) { return ar[o] ? ar[o]->take<float>(floats) : (float*)nullptr; });
+}
+struct SplitBytes { size_t n[3]; };                   // by Owner
+static SplitBytes head_split_bytes(const HeadPlan& p, const SceneLayout& lay) {
+    Arena a[3] = {Arena(nullptr, ~(size_t)0), Arena(nullptr, ~(size_t)0), Arena(nullptr, ~(size_t)0)};
+    Arena* const ar[3] = {&a[0], &a[1], &a[2]};
+    head_carve_split(p, lay, ar);
+    return {{round_up(a[0].off, 256), round_up(a[1].off, 256), round_up(a[2].off, 256)}};
 }
 
 static int mlp_act(const ciaosr_mlp_t& m) { return m.act == CIAOSR_ACT_SIN || m.act == CIAOSR_ACT_COS ? m.act : CIAOSR_ACT_RELU; }
@@ -377,6 +402,27 @@ struct HeadCall : HeadBuffers {
         DecodeP dp{h, mq.width[last - 1], mq.width[last - 1], mq.weight[last], mq.ld[last], mq.bias[last], x_lr, coord, q0, nq, H, W, rgb};
         return decode_residual(dp, s);
     }
+    // The two halves of a call.  per_image: what depends on the LR image only (writes the scene's buffers); per_query: the Q queries of
+    // coord / cell in chunks of the route's step (reads them)
+    int per_image(int n_scales) const {
+        HEAD_RUN(unfold());
+        HEAD_RUN(cs_attn(n_scales));
+        HEAD_RUN(layer0_tables());
+        return logit_table();
+    }
+    int per_query(long Q) const {
+        const int step = r.fused ? qcf : qc;
+        for (long q0 = 0; q0 < Q; q0 += step) {
+            const int nq = (int)((Q - q0) < step ? (Q - q0) : step);
+            if (r.fused) {
+                HEAD_RUN(kv(q0, nq));
+                HEAD_RUN(decode(q0, nq));
+            } else {
+                HEAD_RUN(staged_chunk(q0, nq));
+            }
+        }
+        return CIAOSR_OK;
+    }
 };
 
 }  // namespace ciaosr
@@ -392,53 +438,60 @@ extern "C" size_t ciaosr_head_workspace_bytes_opt(int H, int W, const ciaosr_hea
     return head_ws_bytes(head_plan(H, W, w, Q, opt));
 }
 
-static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
-                        const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
-                        void* workspace, size_t workspace_bytes, void* stream_, Prec prec) {
-    CIAOSR_CHECK_ARG(feat_hwc && w && coord && cell && rgb && workspace && H >= 1 && W >= 1 && Q >= 1);
+// The argument checks the head's entry points share, in the order head_forward has always made them
+static int head_check_weights(int H, int W, const ciaosr_head_weights_t* w, const ciaosr_options_t* opt) {
+    CIAOSR_CHECK_ARG(w && H >= 1 && W >= 1);
     CIAOSR_CHECK_ARG(options_ok(opt));
     CIAOSR_CHECK_ARG(w->channels >= 4 && (w->channels & 3) == 0 && (w->nonlocal_channels & 3) == 0);
     CIAOSR_CHECK_ARG(w->local_size >= 1 && w->local_size <= 3 && w->softmax_scale != 0.f);
     CIAOSR_CHECK_ARG(mlp_ok(w->q) && mlp_ok(w->k) && mlp_ok(w->v));
-    CIAOSR_CHECK_ARG((w->nonlocal_channels > 0) == (csattn != nullptr));
-    const HeadPlan p = head_plan(H, W, w, Q, opt);
+    return CIAOSR_OK;
+}
+static int head_check_dims(const HeadPlan& p, const ciaosr_head_weights_t* w) {
     // dims wiring of LocalImplicitSRNet.__init__ (ciaosr_net.py:61-76)
     CIAOSR_CHECK_ARG(w->k.in_dim == p.D + 4 && w->k.width[w->k.n_layers - 1] == p.D);
     CIAOSR_CHECK_ARG(w->v.in_dim == p.Dv + 4 && w->v.width[w->v.n_layers - 1] == p.Dv);
     CIAOSR_CHECK_ARG(w->q.in_dim == p.Dv && w->q.width[w->q.n_layers - 1] == 3);
     CIAOSR_CHECK_ARG(w->k.n_layers >= 2 && w->v.n_layers >= 2 && w->q.n_layers >= 2);
     CIAOSR_CHECK_ARG((p.wk0 & 3) == 0 && (p.wv0 & 3) == 0);
-    const int n_scales = csattn ? p.Cn / p.C : 0;            // csattn = host array, one struct per entry of multi_scale
+    return CIAOSR_OK;
+}
+static int head_check_csattn(const HeadPlan& p, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int* n_scales) {
+    CIAOSR_CHECK_ARG((w->nonlocal_channels > 0) == (csattn != nullptr));
+    *n_scales = csattn ? p.Cn / p.C : 0;                     // csattn = host array, one struct per entry of multi_scale
     if (csattn) {
-        CIAOSR_CHECK_ARG(p.Cn == n_scales * p.C && n_scales >= 1 && n_scales <= 3);
-        for (int i = 0; i < n_scales; ++i) {
+        CIAOSR_CHECK_ARG(p.Cn == *n_scales * p.C && *n_scales >= 1 && *n_scales <= 3);
+        for (int i = 0; i < *n_scales; ++i) {
             const int sc = csattn[i].scale ? csattn[i].scale : 2;
             CIAOSR_CHECK_ARG(csattn[i].channels == p.C && sc <= (w->nonlocal_max_scale ? w->nonlocal_max_scale : 2));
         }
     }
+    return CIAOSR_OK;
+}
+static int head_route_refusal(const HeadRoute& r) {          // the route's refusals: before the first launch
+    if (r.refusal == CIAOSR_ERR_UNSUPPORTED) return CIAOSR_ERR_UNSUPPORTED;
+    CIAOSR_CHECK_ARG(r.refusal == CIAOSR_OK);                // x3 without every lo fragment
+    return CIAOSR_OK;
+}
+
+static int head_forward(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
+                        const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt,
+                        void* workspace, size_t workspace_bytes, void* stream_, Prec prec) {
+    CIAOSR_CHECK_ARG(feat_hwc && w && coord && cell && rgb && workspace && H >= 1 && W >= 1 && Q >= 1);
+    HEAD_RUN(head_check_weights(H, W, w, opt));
+    const HeadPlan p = head_plan(H, W, w, Q, opt);
+    HEAD_RUN(head_check_dims(p, w));
+    int n_scales;
+    HEAD_RUN(head_check_csattn(p, w, csattn, &n_scales));
     if (workspace_bytes < head_ws_bytes(p)) return CIAOSR_ERR_WORKSPACE;
     CIAOSR_CHECK_ARG((size_t)p.HW * p.Dv * sizeof(float) < 0xFFFFFF00ull);   // 32-bit buffer offsets into U (and into its 16-bit copy)
     Arena ar(workspace, workspace_bytes);
-    const HeadCall c = {head_carve(p, [&](size_t floats) { return ar.take<float>(floats); }), head_route(p, prec, resolve_mode(prec, opt), opt, w),
+    const HeadCall c = {head_carve(p, nullptr, [&](Owner, size_t floats) { return ar.take<float>(floats); }), head_route(p, prec, resolve_mode(prec, opt), opt, w),
                         prec, feat_hwc, w, csattn, x_lr_nchw, coord, cell, chunk, rgb, opt, (hipStream_t)stream_};
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
-    if (c.r.refusal == CIAOSR_ERR_UNSUPPORTED) return CIAOSR_ERR_UNSUPPORTED;     // the route's refusals: before the first launch
-    CIAOSR_CHECK_ARG(c.r.refusal == CIAOSR_OK);                                   // x3 without every lo fragment
-    HEAD_RUN(c.unfold());
-    HEAD_RUN(c.cs_attn(n_scales));
-    HEAD_RUN(c.layer0_tables());
-    HEAD_RUN(c.logit_table());
-    const int step = c.r.fused ? p.qcf : p.qc;
-    for (long q0 = 0; q0 < Q; q0 += step) {
-        const int nq = (int)((Q - q0) < step ? (Q - q0) : step);
-        if (c.r.fused) {
-            HEAD_RUN(c.kv(q0, nq));
-            HEAD_RUN(c.decode(q0, nq));
-        } else {
-            HEAD_RUN(c.staged_chunk(q0, nq));
-        }
-    }
-    return CIAOSR_OK;
+    HEAD_RUN(head_route_refusal(c.r));
+    HEAD_RUN(c.per_image(n_scales));
+    return c.per_query(Q);
 }
 
 extern "C" int ciaosr_head_forward_f32(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn,
@@ -458,6 +511,132 @@ extern "C" int ciaosr_head_forward_f16(const float* feat_hwc, int H, int W, cons
                                        void* workspace, size_t workspace_bytes, void* stream) {
     return head_forward(feat_hwc, H, W, w, csattn, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes, stream, kF16);
 }
+
+// ---- a persistent scene: the per-image half once (prepare), the per-query half any number of times (query) -----------------------------
+// The route is planned for q_plan queries (head_route reads Q in the logit-table threshold and in u16_fits); a query of any Q runs under
+// it, in chunks computed from its own Q.  The descriptor records what the scene was built as; query checks it before its first launch.
+constexpr int kSceneMagic = 0x43530001;               // 'CS', layout version 1
+
+static int route_code(const HeadRoute& r) {
+    if (r.refusal != CIAOSR_OK) return r.refusal;
+    return (r.fused ? 1 : 0) | (int)r.tables << 1 | (int)r.logit << 3 | (int)r.kernel << 6 | (r.chain ? 1 : 0) << 8 | (r.decode_chain ? 1 : 0) << 9 |
+           (r.h16 ? 1 : 0) << 10 | (r.lo ? 1 : 0) << 11 | r.wide_mode << 12;
+}
+static SceneLayout scene_layout(const HeadRoute& r) { return {r.logit != kLogitNone, r.tables == kTablesH16}; }
+
+// plan + route of a scene for q_plan queries, after every check that needs no pointer but w
+static int scene_route(int H, int W, const ciaosr_head_weights_t* w, int q_plan, Prec prec, const ciaosr_options_t* opt, HeadPlan* p, HeadRoute* r) {
+    CIAOSR_CHECK_ARG(q_plan >= 1);
+    HEAD_RUN(head_check_weights(H, W, w, opt));
+    *p = head_plan(H, W, w, q_plan, opt);
+    HEAD_RUN(head_check_dims(*p, w));
+    CIAOSR_CHECK_ARG((size_t)p->HW * p->Dv * sizeof(float) < 0xFFFFFF00ull);
+    *r = head_route(*p, prec, resolve_mode(prec, opt), opt, w);
+    return head_route_refusal(*r);
+}
+
+extern "C" int ciaosr_head_route_code(int H, int W, const ciaosr_head_weights_t* w, int Q, int precision, const ciaosr_options_t* opt) {
+    CIAOSR_CHECK_ARG(precision >= kF32 && precision <= kF16);
+    HeadPlan p; HeadRoute r;
+    HEAD_RUN(scene_route(H, W, w, Q, (Prec)precision, opt, &p, &r));
+    return route_code(r);
+}
+
+// the entry points that size a scene take no precision: the largest over the precisions that have a route
+static size_t scene_bytes_max(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt, Owner o) {
+    size_t n = 0;
+    for (int prec = kF32; prec <= kF16; ++prec) {
+        HeadPlan p; HeadRoute r;
+        if (scene_route(H, W, w, q_plan, (Prec)prec, opt, &p, &r) != CIAOSR_OK) continue;
+        const size_t m = head_split_bytes(p, scene_layout(r)).n[o];
+        n = m > n ? m : n;
+    }
+    return n;
+}
+extern "C" size_t ciaosr_head_scene_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt) {
+    return scene_bytes_max(H, W, w, q_plan, opt, kScene);
+}
+extern "C" size_t ciaosr_head_prepare_workspace_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt) {
+    return scene_bytes_max(H, W, w, q_plan, opt, kPrepare);
+}
+
+static int off256(const void* p, const void* base) { return p ? (int)(((const char*)p - (const char*)base) >> 8) : -1; }
+
+static int head_prepare(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int q_plan,
+                        const ciaosr_options_t* opt, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc, void* workspace,
+                        size_t workspace_bytes, void* stream_, Prec prec) {
+    CIAOSR_CHECK_ARG(feat_hwc && scene && desc && workspace);
+    HeadPlan p; HeadRoute r;
+    HEAD_RUN(scene_route(H, W, w, q_plan, prec, opt, &p, &r));
+    int n_scales;
+    HEAD_RUN(head_check_csattn(p, w, csattn, &n_scales));
+    const SceneLayout lay = scene_layout(r);
+    const SplitBytes need = head_split_bytes(p, lay);
+    CIAOSR_CHECK_ARG(need.n[kScene] >> 8 < 0x7FFFFFFFull);                        // the descriptor counts 256-byte units in an int
+    if (scene_bytes < need.n[kScene] || workspace_bytes < need.n[kPrepare]) return CIAOSR_ERR_WORKSPACE;
+    Arena sc(scene, scene_bytes), ws(workspace, workspace_bytes);
+    Arena* const ar[3] = {&sc, &ws, nullptr};
+    const HeadCall c = {head_carve_split(p, lay, ar), r, prec, feat_hwc, w, csattn, nullptr, nullptr, nullptr, 0, nullptr, opt, (hipStream_t)stream_};
+    if (!sc.ok || !ws.ok) return CIAOSR_ERR_WORKSPACE;
+    *desc = {kSceneMagic, p.H, p.W, p.C, p.Cn, p.D, p.Dv, p.J, q_plan, (int)prec, route_code(r),
+             off256(c.U, scene), off256(c.Tk, scene), off256(c.Tv, scene), lay.logit ? off256(c.G, scene) : -1, (int)(need.n[kScene] >> 8)};
+    return c.per_image(n_scales);
+}
+
+// What query (and its size function) make of a descriptor: the plan for Q queries and the route the scene was planned under, or the
+// refusal.  prec < 0: the descriptor's own.
+static int scene_open(const ciaosr_head_scene_t* d, const ciaosr_head_weights_t* w, int Q, int prec, const ciaosr_options_t* opt, HeadPlan* p,
+                      HeadRoute* r) {
+    CIAOSR_CHECK_ARG(d && d->magic == kSceneMagic && Q >= 1 && d->precision >= kF32 && d->precision <= kF16);
+    CIAOSR_CHECK_ARG(prec < 0 || prec == d->precision);
+    HeadPlan pp;
+    HEAD_RUN(scene_route(d->H, d->W, w, d->q_plan, (Prec)d->precision, opt, &pp, r));
+    CIAOSR_CHECK_ARG(pp.C == d->C && pp.Cn == d->Cn && pp.D == d->D && pp.Dv == d->Dv && pp.J == d->J);
+    CIAOSR_CHECK_ARG(route_code(*r) == d->route);                                  // a route-changing option, other weights
+    *p = head_plan(d->H, d->W, w, Q, opt);
+    return CIAOSR_OK;
+}
+
+extern "C" size_t ciaosr_head_query_workspace_bytes(const ciaosr_head_scene_t* desc, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt) {
+    HeadPlan p; HeadRoute r;
+    if (scene_open(desc, w, Q, -1, opt, &p, &r) != CIAOSR_OK) return 0;
+    return head_split_bytes(p, scene_layout(r)).n[kQuery];
+}
+
+static int head_query(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc, const ciaosr_head_weights_t* w, const float* x_lr_nchw,
+                      const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt, void* workspace,
+                      size_t workspace_bytes, void* stream_, Prec prec) {
+    CIAOSR_CHECK_ARG(scene && coord && cell && rgb && workspace);
+    HeadPlan p; HeadRoute r;
+    HEAD_RUN(scene_open(desc, w, Q, (int)prec, opt, &p, &r));
+    const SceneLayout lay = scene_layout(r);
+    const SplitBytes need = head_split_bytes(p, lay);
+    CIAOSR_CHECK_ARG((int)(need.n[kScene] >> 8) == desc->total);
+    if (scene_bytes < need.n[kScene] || workspace_bytes < need.n[kQuery]) return CIAOSR_ERR_WORKSPACE;
+    Arena sc(const_cast<void*>(scene), scene_bytes), ws(workspace, workspace_bytes);
+    Arena* const ar[3] = {&sc, nullptr, &ws};
+    const HeadCall c = {head_carve_split(p, lay, ar), r, prec, nullptr, w, nullptr, x_lr_nchw, coord, cell, chunk, rgb, opt, (hipStream_t)stream_};
+    if (!sc.ok || !ws.ok) return CIAOSR_ERR_WORKSPACE;
+    CIAOSR_CHECK_ARG(off256(c.U, scene) == desc->off_u && off256(c.Tk, scene) == desc->off_tk && off256(c.Tv, scene) == desc->off_tv &&
+                     (lay.logit ? off256(c.G, scene) : -1) == desc->off_g);
+    return c.per_query(Q);
+}
+
+#define CIAOSR_HEAD_SCENE_ENTRIES(sfx, prec)                                                                                                          \
+    extern "C" int ciaosr_head_prepare_##sfx(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, \
+                                             int q_plan, const ciaosr_options_t* opt, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc,   \
+                                             void* workspace, size_t workspace_bytes, void* stream) {                                                \
+        return head_prepare(feat_hwc, H, W, w, csattn, q_plan, opt, scene, scene_bytes, desc, workspace, workspace_bytes, stream, prec);            \
+    }                                                                                                                                                 \
+    extern "C" int ciaosr_head_query_##sfx(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc, const ciaosr_head_weights_t* w,   \
+                                           const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb,             \
+                                           const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream) {                    \
+        return head_query(scene, scene_bytes, desc, w, x_lr_nchw, coord, cell, Q, chunk, rgb, opt, workspace, workspace_bytes, stream, prec);       \
+    }
+CIAOSR_HEAD_SCENE_ENTRIES(f32, kF32)
+CIAOSR_HEAD_SCENE_ENTRIES(bf16, kBF16)
+CIAOSR_HEAD_SCENE_ENTRIES(f16, kF16)
+#undef CIAOSR_HEAD_SCENE_ENTRIES
 
 // ---- staged MLPRefiner (mlp_refiner.py:87-102), layer by layer, no hoist -------------------------------------
 static int mlp_wmax(const ciaosr_mlp_t* m) {

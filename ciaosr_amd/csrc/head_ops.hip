@@ -527,6 +527,25 @@ __global__ void make_coord_cell_kernel(float* __restrict__ coord, float* __restr
     }
 }
 
+// One axis of a window grid: the global make_coord value of HR index k, or its image in an LR tile's frame (host-made fp64 factors;
+// every operation rounded on its own: an FMA would change the double before it is rounded to fp32)
+struct WindowAxis { int n_hr, k0, framed; double half_n, y0, inv_half_t; float cell; };
+__device__ __forceinline__ float window_coord(const WindowAxis& a, int k) {
+#pragma clang fp contract(off)
+    const float g = pixel_centre(k, a.n_hr);
+    if (!a.framed) return g;
+    const double u = ((double)g + 1.0) * a.half_n;
+    const double v = (u - a.y0) * a.inv_half_t;
+    return (float)(v - 1.0);
+}
+__global__ void make_coord_cell_window_kernel(float* __restrict__ coord, float* __restrict__ cell, WindowAxis ay, WindowAxis ax, int wn, long n) {
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
+        const int i = (int)(q / wn), j = (int)(q - (long)i * wn);
+        reinterpret_cast<float2*>(coord)[q] = make_float2(window_coord(ay, ay.k0 + i), window_coord(ax, ax.k0 + j));
+        reinterpret_cast<float2*>(cell)[q] = make_float2(ay.cell, ax.cell);
+    }
+}
+
 // ---- host wrappers --------------------------------------------------------------------------
 int head_indices(const float* coord, const float* cell, long q0, int nq, int chunk, int H, int W, int local_size,
                  int* q_idx, int* k_idx, float* rel, hipStream_t s) {
@@ -630,6 +649,29 @@ extern "C" int ciaosr_make_coord_cell_f32(float* coord, float* cell, int Ht, int
     hipLaunchKernelGGL(make_coord_cell_kernel, dim3(grid > 2048 ? 2048 : grid), dim3(256), 0, (hipStream_t)stream, coord,
                        cell, Ht, Wt);
     return launch_status("make_coord_cell");
+}
+
+static WindowAxis window_axis(int n_hr, int k0, const int* f) {
+    WindowAxis a = {n_hr, k0, 0, 0.0, 0.0, 0.0, (float)(2.0 / (double)n_hr)};
+    if (f && !(f[1] == 0 && f[2] == f[0])) {          // a tile that covers the whole axis keeps the global values
+        a.framed = 1;
+        a.half_n = (double)f[0] / 2.0; a.y0 = (double)f[1]; a.inv_half_t = 2.0 / (double)f[2];
+        a.cell = (float)((2.0 / (double)n_hr) * ((double)f[0] / (double)f[2]));
+    }
+    return a;
+}
+
+extern "C" int ciaosr_make_coord_cell_window_f32(float* coord, float* cell, int Ht, int Wt, int i0, int i1, int j0, int j1, const int* frame,
+                                                 void* stream) {
+    CIAOSR_CHECK_ARG(coord && cell && Ht > 0 && Wt > 0 && 0 <= i0 && i0 < i1 && i1 <= Ht && 0 <= j0 && j0 < j1 && j1 <= Wt);
+    CIAOSR_CHECK_ARG(!frame || (frame[0] > 0 && frame[2] > 0 && frame[1] >= 0 && frame[1] + frame[2] <= frame[0] && frame[3] > 0 && frame[5] > 0 &&
+                                frame[4] >= 0 && frame[4] + frame[5] <= frame[3]));
+    ProfScope prof("make_coord_cell_window", (hipStream_t)stream);
+    const long n = (long)(i1 - i0) * (j1 - j0);
+    const long grid = (n + 255) / 256;
+    hipLaunchKernelGGL(make_coord_cell_window_kernel, dim3((int)(grid > 2048 ? 2048 : grid)), dim3(256), 0, (hipStream_t)stream, coord, cell,
+                       window_axis(Ht, i0, frame), window_axis(Wt, j0, frame ? frame + 3 : nullptr), j1 - j0, n);
+    return launch_status("make_coord_cell_window");
 }
 
 extern "C" int ciaosr_local_attention_f32(const float* unfold, int ld_u, int C, int Cn, const int* q_idx,

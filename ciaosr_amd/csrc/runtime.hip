@@ -71,7 +71,7 @@ int launch_status(const char* what) {
 
 using namespace ciaosr;
 
-extern "C" int ciaosr_version(void) { return 220; }
+extern "C" int ciaosr_version(void) { return 230; }
 
 // sizeof of every struct of the ABI, by name: lets a binding (ciaosr_amd/_lib.py's ctypes mirrors) verify its layout
 extern "C" size_t ciaosr_sizeof(const char* type_name) {
@@ -81,6 +81,7 @@ extern "C" size_t ciaosr_sizeof(const char* type_name) {
         {"ciaosr_csattn_weights_t", sizeof(ciaosr_csattn_weights_t)},
         {"ciaosr_mlp_t", sizeof(ciaosr_mlp_t)},
         {"ciaosr_head_weights_t", sizeof(ciaosr_head_weights_t)},
+        {"ciaosr_head_scene_t", sizeof(ciaosr_head_scene_t)},
         {"ciaosr_conv_t", sizeof(ciaosr_conv_t)},
         {"ciaosr_rdn_weights_t", sizeof(ciaosr_rdn_weights_t)},
         {"ciaosr_edsr_weights_t", sizeof(ciaosr_edsr_weights_t)},

@@ -20,6 +20,25 @@ def unfold_perm(channels, device):
     return torch.arange(9 * channels, device=device).view(channels, 9).t().reshape(-1)
 
 
+class Scene:
+    """What PackedHead.prepare built from one feature map: the device buffer the per-query kernels read (owned here: a torch.empty, not a
+    hip_ops.workspace slot, which is scratch that the next call overwrites), its descriptor, the Options it was built with, the version
+    keys of the weights it was built from and an event recorded behind the last prepare launch."""
+    __slots__ = ('buf', 'desc', 'options', 'q_plan', 'keys', 'event')
+
+    def __init__(self, buf, desc, options, q_plan, keys, event):
+        self.buf, self.desc, self.options, self.q_plan, self.keys, self.event = buf, desc, options, q_plan, keys, event
+
+    @property
+    def nbytes(self):
+        return self.buf.numel()
+
+    @property
+    def shape(self):
+        """(H, W) of the LR map."""
+        return self.desc.H, self.desc.W
+
+
 class PackedHead:
     """Packed (device-order, contiguous fp32) copies of a LocalImplicitSRNet head's weights."""
 
@@ -317,15 +336,7 @@ class PackedHead:
         Q = coord.shape[0]
         cs = net.cs_attn.packed()[0] if net.non_local_attn else None       # first: the 'bf16-single' form is keyed on its pack
         st = self.struct(opt.mode.head)
-        gw = hip_ops.grid_width_of(coord) if (opt.half and not opt.query_grid_w) else 0
-        if gw:                        # traversal hint of the 16-bit chained head kernel: the queries are a make_coord grid
-            key = (opt, gw)
-            hinted = self._grid_opts.get(key)
-            if hinted is None:
-                if len(self._grid_opts) > 64:
-                    self._grid_opts.clear()
-                hinted = self._grid_opts[key] = opt.replace(query_grid_w=gw)
-            opt = hinted
+        opt = self._hinted(opt, coord)
         feat_hwc = feature_hwc if feature_hwc is not None else hip_ops.nchw_to_hwc(feature_chw)
         nbytes = _lib.load().ciaosr_head_workspace_bytes_opt(H, W, C.byref(st), Q, opt.c_arg())
         ws = hip_ops.workspace(nbytes, coord.device)
@@ -334,6 +345,89 @@ class PackedHead:
                   C.byref(st), cs if cs is not None else None, hip_ops.ptr(x_lr_chw), hip_ops.ptr(coord),
                   hip_ops.ptr(cell), Q, int(chunk or 0), hip_ops.ptr(rgb), opt.c_arg(), hip_ops.ptr(ws), ws.numel(),
                   hip_ops.stream_ptr())
+        return rgb
+
+    def _weights_key(self):
+        net = self.net
+        return (self._version_key(), net.cs_attn._version_key() if net.non_local_attn else None)
+
+    def _hinted(self, opt, coord):
+        """`opt` with the traversal hint of the 16-bit chained head kernel when the queries are a make_coord grid."""
+        gw = hip_ops.grid_width_of(coord) if (opt.half and not opt.query_grid_w) else 0
+        if not gw:
+            return opt
+        key = (opt, gw)
+        hinted = self._grid_opts.get(key)
+        if hinted is None:
+            if len(self._grid_opts) > 64:
+                self._grid_opts.clear()
+            hinted = self._grid_opts[key] = opt.replace(query_grid_w=gw)
+        return hinted
+
+    def route_code(self, H, W, Q, options=None):
+        """ciaosr_head_route_code of a call of Q queries on an H x W map under `options`: two calls with equal codes run the same kernels
+        (a scene planned for one serves the other bit for bit).  Launches nothing."""
+        opt = hip_ops.as_options(options)
+        st = self.struct(opt.mode.head)
+        rc = _lib.load().ciaosr_head_route_code(H, W, C.byref(st), int(Q), ('fp32', 'bf16', 'f16').index(opt.precision), opt.c_arg())
+        if rc < 0:
+            _lib.check(rc, 'ciaosr_head_route_code')
+        return rc
+
+    @torch.no_grad()
+    def prepare(self, feature_chw, options=None, q_plan=None, feature_hwc=None):
+        """The per-image half of `forward`, once: feature [C,H,W] (or channels-last via feature_hwc) -> Scene.  `q_plan`: the query count
+        the route is planned for -- the largest full render intended (include/ciaosr_hip.h, "a persistent head scene")."""
+        net = self.net
+        opt = hip_ops.as_options(options)
+        if q_plan is None or int(q_plan) < 1:
+            raise ValueError('prepare needs q_plan >= 1: the number of queries of the largest full render intended')
+        if feature_hwc is None:
+            feature_chw = feature_chw.contiguous().float()
+            hip_ops.require_gpu(feature_chw)
+            feature_hwc = hip_ops.nchw_to_hwc(feature_chw)
+        feature_hwc = feature_hwc.contiguous().float()
+        hip_ops.require_gpu(feature_hwc)
+        H, W, _ = feature_hwc.shape
+        dev = feature_hwc.device
+        cs = net.cs_attn.packed()[0] if net.non_local_attn else None
+        st = self.struct(opt.mode.head)
+        keys = self._weights_key()
+        lib = _lib.load()
+        n_scene = lib.ciaosr_head_scene_bytes(H, W, C.byref(st), int(q_plan), opt.c_arg())
+        n_ws = lib.ciaosr_head_prepare_workspace_bytes(H, W, C.byref(st), int(q_plan), opt.c_arg())
+        if n_scene == 0:
+            raise _lib.CiaoSRHipError(f'no head route for a {H} x {W} scene under {opt!r}')
+        buf = torch.empty(n_scene, dtype=torch.uint8, device=dev)
+        ws = hip_ops.workspace(n_ws, dev)
+        desc = _lib.HeadSceneT()
+        _lib.call('ciaosr_head_prepare_' + opt.suffix, hip_ops.ptr(feature_hwc), H, W, C.byref(st), cs if cs is not None else None, int(q_plan),
+                  opt.c_arg(), hip_ops.ptr(buf), buf.numel(), C.byref(desc), hip_ops.ptr(ws), ws.numel(), hip_ops.stream_ptr())
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        return Scene(buf, desc, opt, int(q_plan), keys, ev)
+
+    @torch.no_grad()
+    def query(self, scene, x_lr_chw, coord, cell, chunk=None):
+        """The per-query half of `forward` on a Scene: x_lr [3,H,W] or None, coord/cell [Q,2] -> rgb [Q,3].  Any Q, any number of times;
+        raises CiaoSRHipError when a weight the scene was built from has changed since."""
+        if scene.keys != self._weights_key():
+            raise _lib.CiaoSRHipError('stale scene: a weight of the head or of cs_attn changed after prepare; encode again')
+        coord = coord.contiguous().float()
+        cell = cell.contiguous().float()
+        if x_lr_chw is not None:
+            x_lr_chw = x_lr_chw.contiguous().float()
+        hip_ops.require_gpu(scene.buf.view(torch.float32), x_lr_chw, coord, cell)
+        Q = coord.shape[0]
+        st = self.struct(scene.options.mode.head)
+        opt = self._hinted(scene.options, coord)
+        torch.cuda.current_stream(coord.device).wait_event(scene.event)
+        nbytes = _lib.load().ciaosr_head_query_workspace_bytes(C.byref(scene.desc), C.byref(st), Q, opt.c_arg())
+        ws = hip_ops.workspace(nbytes, coord.device)
+        rgb = torch.empty(Q, 3, dtype=torch.float32, device=coord.device)
+        _lib.call('ciaosr_head_query_' + opt.suffix, hip_ops.ptr(scene.buf), scene.buf.numel(), C.byref(scene.desc), C.byref(st),
+                  hip_ops.ptr(x_lr_chw), hip_ops.ptr(coord), hip_ops.ptr(cell), Q, int(chunk or 0), hip_ops.ptr(rgb), opt.c_arg(),
+                  hip_ops.ptr(ws), ws.numel(), hip_ops.stream_ptr())
         return rgb
 
     @torch.no_grad()

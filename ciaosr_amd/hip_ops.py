@@ -63,10 +63,32 @@ def make_coord_cell(ht, wt, device):
 _grid_width = {}
 
 
+_window_width = {}
+
+
+def make_coord_cell_window(ht, wt, i0, i1, j0, j1, device, frame=None):
+    """Rows [i0, i1) x columns [j0, j1) of the ht x wt target grid, made on the device: (coord, cell), each [(i1-i0)*(j1-j0), 2].
+    frame = None: the `make_coord_cell` values at those rows and columns.  frame = (n_lr_y, y0, th, n_lr_x, x0, tw): the grid in the
+    frame of that LR tile (tile_plan.axis_local's values).  Not cached -- windows do not repeat the way tile shapes do -- but the
+    window's width is registered for `grid_width_of`."""
+    n = (i1 - i0) * (j1 - j0)
+    if not (0 <= i0 < i1 <= ht and 0 <= j0 < j1 <= wt):
+        raise ValueError(f'window rows [{i0}, {i1}) x columns [{j0}, {j1}) outside the {ht} x {wt} grid (or empty)')
+    coord = torch.empty(n, 2, dtype=torch.float32, device=device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=device)
+    fr = (C.c_int * 6)(*[int(v) for v in frame]) if frame is not None else None
+    _lib.call('ciaosr_make_coord_cell_window_f32', ptr(coord), ptr(cell), ht, wt, i0, i1, j0, j1, fr, stream_ptr())
+    if len(_window_width) > 64:
+        _window_width.clear()
+    _window_width[(coord.data_ptr(), n)] = j1 - j0
+    return coord, cell
+
+
 def grid_width_of(coord):
-    """Columns of the row-major target grid when `coord` [Q, 2] is (a view of) a tensor `make_coord_cell` produced, else 0: the
-    traversal hint ciaosr_options_t.query_grid_w of the 16-bit fused head (results do not depend on it)."""
-    return _grid_width.get((coord.data_ptr(), coord.shape[0]), 0)
+    """Columns of the row-major target grid when `coord` [Q, 2] is (a view of) a tensor `make_coord_cell` or `make_coord_cell_window`
+    produced, else 0: the traversal hint ciaosr_options_t.query_grid_w of the 16-bit fused head (results do not depend on it)."""
+    key = (coord.data_ptr(), coord.shape[0])
+    return _grid_width.get(key, 0) or _window_width.get(key, 0)
 
 
 def ptr(t):

@@ -24,6 +24,19 @@ from .nonlocal_attn import CrossScaleAttention
 from .registry import build_backbone, build_component
 
 
+class EncodedFeatures:
+    """What `LocalImplicitSRNet.encode` keeps of a batch: one head Scene per item, the normalised LR batch (for the bilinear residual)
+    and the Options the scenes were built with."""
+    __slots__ = ('scenes', 'x', 'options')
+
+    def __init__(self, scenes, x, options):
+        self.scenes, self.x, self.options = scenes, x, options
+
+    @property
+    def nbytes(self):
+        return sum(s.nbytes for s in self.scenes)
+
+
 class LocalImplicitSRNet(nn.Module):
     def __init__(self, encoder, imnet_q, imnet_k, imnet_v, query_mlp=None, key_mlp=None, value_mlp=None,
                  local_size=2, feat_unfold=True, eval_bsize=None, non_local_attn=True, multi_scale=[2],
@@ -85,6 +98,35 @@ class LocalImplicitSRNet(nn.Module):
             return torch.stack(outs, 0)
         features = self.gen_feature(x, options)
         return self._predict(features, coord, cell, chunk, x, options)
+
+    @torch.no_grad()
+    def encode(self, x, options=None, q_plan=None):
+        """The part of `forward` that depends on the LR batch only, once: trunk, then per item the head's per-image stages into a Scene
+        (head_hip.PackedHead.prepare).  `q_plan`: the query count of the largest full render intended (default: the x4 grid).  An
+        extension, absent from the reference."""
+        options = self.effective_options(options)
+        enc = getattr(self, '_encoder_hip', None)
+        if enc is None:
+            raise CiaoSRHipError('encode needs a generator with a HIP trunk')
+        self._require_hip_trunk(x)
+        x = x.contiguous().float()
+        if q_plan is None:
+            q_plan = 16 * x.shape[-2] * x.shape[-1]
+        if hasattr(enc, 'forward_hwc_batch'):
+            feats = enc.forward_hwc_batch(x, options)
+        else:
+            feats = [enc.forward_hwc(x[b], options) for b in range(x.shape[0])]
+        return EncodedFeatures([self._head.prepare(None, options, q_plan, feature_hwc=feats[b]) for b in range(x.shape[0])], x, options)
+
+    @torch.no_grad()
+    def render(self, enc, coord, cell):
+        """`forward(x, coord, cell, test_mode=True)` from an `encode` result: coord/cell [B,Q,2] (or [Q,2], shared by the batch) -> [B,Q,3],
+        for any Q, any number of times."""
+        outs = []
+        for b, scene in enumerate(enc.scenes):
+            cq, cl = (coord, cell) if coord.dim() == 2 else (coord[b], cell[b])
+            outs.append(self._head.query(scene, enc.x[b], cq, cl, self.eval_bsize))
+        return torch.stack(outs, 0)
 
     def effective_options(self, options=None):
         """The hip_ops.Options a call on THIS generator really runs with (subclasses may narrow what they accept)."""

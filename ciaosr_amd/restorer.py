@@ -356,6 +356,72 @@ class CiaoSR(BasicRestorer):
                 hip_ops.tile_blend(E[bi], Wt[bi], out[bi].contiguous(), t['i0'], t['j0'], t['i1'] - t['i0'], t['j1'] - t['j0'])
         return torch.stack([hip_ops.tile_finalize(E[bi], Wt[bi]) for bi in range(b)])
 
+    # -- encode once, render any scale or window (an extension, absent from the reference) ---------------------------------------------
+    @torch.no_grad()
+    def encode(self, lq, options=None, max_scale=None):
+        """Everything `restore` computes from the LR image alone, kept: -> scene.EncodedImage for `render`.  Without `test_cfg.tile` the
+        whole image's trunk and head scene, built here when `max_scale` is known (the argument, else `test_cfg.scale`; else at the first
+        render, from its scale).  With `test_cfg.tile` one scene per LR tile, each built when a render first touches the tile and held
+        under `test_cfg.scene_cache_mb` (default 4096) MiB, least recently used first out.  `max_scale` sizes the plan of every scene:
+        the full (tile) grid at that scale is the largest render whose route is `restore`'s own (include/ciaosr_hip.h, q_plan)."""
+        from .scene import EncodedImage
+        opt = self.options(options)
+        x = self.normalize(lq)
+        gen = self.generator
+        if max_scale is None:
+            max_scale = self.test_cfg.get('scale', None)
+        tile = self.test_cfg.get('tile', None)
+        h, w = x.shape[-2:]
+        t = min(tile, h, w) if tile else None
+
+        def build(key):
+            b, origin = key
+            patch = x[b:b + 1] if origin is None else x[b:b + 1, :, origin[0]:origin[0] + t, origin[1]:origin[1] + t].contiguous()
+            ph, pw = patch.shape[-2:]
+            return gen.encode(patch, opt, q_plan=max(1, round(ph * enc.max_scale) * round(pw * enc.max_scale)))
+
+        enc = EncodedImage(x, opt, max_scale, int(self.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build)
+        if not tile and max_scale is not None:
+            for b in range(x.shape[0]):
+                enc.cache.get((b, None))
+        return enc
+
+    @torch.no_grad()
+    def render(self, enc, size=None, scale=None, window=None, as_u8=False):
+        """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
+        round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,
+        or with `as_u8` the metrics_hip.tensor2img_u8 image of it.  Only the LR tiles whose HR rectangle meets the window are touched."""
+        from . import scene as sc
+        x = enc.x
+        nb, _, h, w = x.shape
+        ht, wt = sc.target_size(h, w, size, scale)
+        wi0, wj0, wh, ww = sc.check_window(ht, wt, window)
+        if enc.max_scale is None:
+            enc.max_scale = max(ht / h, wt / w)
+        gen = self.generator
+        tile = self.test_cfg.get('tile', None)
+        if not tile:
+            coord, cell = hip_ops.make_coord_cell_window(ht, wt, wi0, wi0 + wh, wj0, wj0 + ww, x.device)
+            preds = [gen.render(enc.cache.get((b, None)), coord, cell)[0] for b in range(nb)]
+        else:
+            tiles = sc.plan_window(h, w, tile, self.test_cfg.get('tile_overlap', None), ht, wt, (wi0, wj0, wh, ww),
+                                   scale=self.test_cfg.get('scale', None), any_scale=bool(self.test_cfg.get('tile_any_scale', False)))
+            preds = []
+            for b in range(nb):
+                E = torch.zeros(3, wh, ww, dtype=torch.float32, device=x.device)
+                Wt = torch.zeros_like(E)
+                for t in tiles:              # the reference's blend order
+                    gh, gw, r0, r1, c0, c1, frame = t['grid']
+                    coord, cell = hip_ops.make_coord_cell_window(gh, gw, r0, r1, c0, c1, x.device, frame)
+                    out = gen.render(enc.cache.get((b, (t['y0'], t['x0']))), coord, cell)[0]
+                    hip_ops.tile_blend(E, Wt, out, t['a0'] - wi0, t['b0'] - wj0, t['a1'] - t['a0'], t['b1'] - t['b0'])
+                preds.append(hip_ops.tile_finalize(E, Wt))
+        out = torch.stack([hip_ops.denorm_clamp(p.contiguous(), wh, ww, self.rgb_mean, self.rgb_std) for p in preds])
+        if as_u8:
+            from . import metrics_hip
+            return metrics_hip.tensor2img_u8(out)
+        return out
+
     def _restore(self, lq, coord=None, cell=None, options=None):
         x = self.normalize(lq)
         if self.test_cfg.get('tile', None) and self.test_cfg.get('tile_any_scale', False) and coord is not None:

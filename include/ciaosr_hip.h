@@ -321,6 +321,12 @@ int ciaosr_pack_head_chain_f16(const ciaosr_head_weights_t* w, int pairs, void* 
  * seq[i] = fp32(-1 + 1/n) + fp32(2/n) * fp32(i), cell[q] = (2/Ht, 2/Wt), q = i*Wt + j
  * (mmedit make_coord, call site rest:240; cell rest:241-243). */
 int ciaosr_make_coord_cell_f32(float* coord, float* cell, int Ht, int Wt, void* stream);
+/* Rows [i0, i1) x columns [j0, j1) of the same grid, q = (i - i0) (j1 - j0) + (j - j0): a window render's queries, made on the device.
+ * frame = NULL: the values above at (i, j), bitwise.  frame = {n_lr_y, y0, th, n_lr_x, x0, tw} (host): the grid as LR tile [y0, y0 + th) x
+ * [x0, x0 + tw) of an n_lr_y x n_lr_x image sees it: coord = fp32(((g + 1) (n_lr / 2) - y0) (2 / th) - 1) with g the global value, every
+ * operation a rounded fp64 one, cell = fp32((2 / n_hr) (n_lr / th)); a tile that covers its whole axis keeps the global values. */
+int ciaosr_make_coord_cell_window_f32(float* coord, float* cell, int Ht, int Wt, int i0, int i1, int j0, int j1, const int* frame /*host, may be NULL*/,
+                                      void* stream);
 
 /* Index math only (test/debug): nearest LR index of every query and of its key samples.
  * q_idx [Q] (= iy*W+ix), k_idx [Q][J], rel [Q][J][2], following net:145-146,159-193. */
@@ -413,6 +419,57 @@ int ciaosr_head_forward_f16(const float* feat_hwc, int H, int W, const ciaosr_he
                             const float* coord, const float* cell, int Q, int chunk, float* rgb,
                             const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ---- a persistent head scene: encode once, query any scale or window ---------------------------------------------------------------
+ * ciaosr_head_forward_* = the stages that depend on the LR image only (unfold rows, cs_attn, the layer-0 tables, the logit table)
+ * followed by the per-query kernels.  The two entry-point families below run the halves apart: prepare writes what the per-query
+ * kernels read into a caller-owned device buffer, the scene; query renders any Q >= 1 queries from it, any number of times.
+ *   scene      U [HW][Dv] (unfold rows | non-local maps), Tk [HW][wk0], Tv [HW][wv0] and, when the route has a logit table, G
+ *              [9 HW][260], each 256-byte aligned.  C = 64, hidden 256: 13 968 B per LR pixel with G, 4 608 B without.
+ *   q_plan     the route is a function of the query count in two places (the logit table exists iff Q J > 9 HW; the f16 layer-0 tables
+ *              ask for the room a call of Q queries has), so a scene is planned for q_plan queries -- the largest full render intended --
+ *              and every query runs under the route ciaosr_head_forward_* takes at Q = q_plan, in chunks computed from its own Q.
+ *              prepare + query at Q = q_plan is bitwise ciaosr_head_forward_*; so is every subset of its rows queried alone.
+ *   desc       host struct written by prepare; query refuses (CIAOSR_ERR_BAD_ARG, CIAOSR_ERR_WORKSPACE for a short buffer; before its
+ *              first launch) a descriptor that does not fit w, opt, the entry's precision or scene_bytes.
+ * Workspaces are scratch of one call, as everywhere: prepare's holds cs_attn's workspace and the tables' operands, query's the
+ * attention rows of a chunk (and the staged route's activations).  No entry allocates, synchronises or keeps state. */
+typedef struct ciaosr_head_scene {
+    int magic;                          /* layout tag + version */
+    int H, W, C, Cn, D, Dv, J;          /* LR map, channels, non-local channels, 9C (C without unfold), D + Cn, key samples per query */
+    int q_plan;
+    int precision;                      /* 0 = f32, 1 = bf16, 2 = f16: the suffix of the prepare entry */
+    int route;                          /* ciaosr_head_route_code of (H, W, w, q_plan, precision, opt) */
+    int off_u, off_tk, off_tv, off_g;   /* carve offsets into the scene in 256-byte units; off_g = -1: no logit table */
+    int total;                          /* scene bytes in 256-byte units */
+} ciaosr_head_scene_t;
+
+/* What a call of Q queries runs, packed: bit 0 fused, 1-2 layer-0 tables (h16 / small / gemm), 3-5 logit table (none / gemm32 / gemm16 /
+ * wino2 / wino4), 6-7 kernel (fused32 / fused16 / wide / chain), 8 chained kv, 9 chained decode, 10 16-bit, 11 weight pairs, 12-13 wide
+ * mode.  Negative: the error code the call would return.  precision: 0 | 1 | 2 as above.  Launches nothing. */
+int ciaosr_head_route_code(int H, int W, const ciaosr_head_weights_t* w, int Q, int precision, const ciaosr_options_t* opt /*host, may be NULL*/);
+/* Sizes for any precision of (w, opt) (the largest); 0 = bad arguments */
+size_t ciaosr_head_scene_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt /*host, may be NULL*/);
+size_t ciaosr_head_prepare_workspace_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt /*host, may be NULL*/);
+size_t ciaosr_head_query_workspace_bytes(const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt /*host, may be NULL*/);
+int ciaosr_head_prepare_f32(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int q_plan,
+                            const ciaosr_options_t* opt /*host, NULL = defaults*/, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc /*host, out*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_head_prepare_bf16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int q_plan,
+                             const ciaosr_options_t* opt /*host, NULL = defaults*/, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc /*host, out*/,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_head_prepare_f16(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int q_plan,
+                            const ciaosr_options_t* opt /*host, NULL = defaults*/, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc /*host, out*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_head_query_f32(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w,
+                          const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb,
+                          const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_head_query_bf16(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w,
+                           const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb,
+                           const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_head_query_f16(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w,
+                          const float* x_lr_nchw, const float* coord, const float* cell, int Q, int chunk, float* rgb,
+                          const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- encoder trunks: gen_feature (net:321-342 RDN, net:393-408 EDSR) -------------------------- */
 typedef struct ciaosr_conv {

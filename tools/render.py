@@ -1,0 +1,74 @@
+#!/usr/bin/env python
+"""Render one image at several scales (or one window of each) from ONE encode:
+
+    python tools/render.py CONFIG CHECKPOINT IMAGE --scale S [S ...] [--window I0 J0 H W] [--precision P] --out DIR
+
+Config and checkpoint as for tools/test.py.  The trunk, cs_attn and the head's per-image tables run once (CiaoSR.encode); every
+scale is a CiaoSR.render from the kept scenes and is written to DIR/<image name>_x<S>.png, the image `restore` gives for that
+target under the same test_cfg.  The configs tile integer scales only (`clip_test`), so this tool turns on
+`test_cfg.tile_any_scale` where the config sets `tile`: an image no larger than the tile is then the whole-image path, a larger
+one is tiled by tile_plan.  `--window` is in HR pixels of each scale's own grid; `--max-scale` sizes the scenes' plan (default: the
+largest --scale).
+"""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description='ciaosr_amd multi-scale renderer')
+    p.add_argument('config', help='test config file path')
+    p.add_argument('checkpoint', help='checkpoint file ("None" = cfg.test_checkpoint_path)')
+    p.add_argument('image', help='LR image file')
+    p.add_argument('--scale', type=float, nargs='+', required=True, help='one output per scale: round(h * s) x round(w * s)')
+    p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
+    p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
+    p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale)')
+    p.add_argument('--out', required=True, help='output directory')
+    return p.parse_args(argv)
+
+
+def scale_tag(s):
+    return f'{s:g}'.replace('.', 'p')
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import ciaosr_amd
+    from ciaosr_amd import metrics
+    from ciaosr_amd.checkpoint import load_checkpoint
+    from ciaosr_amd.config import Config
+    from ciaosr_amd.imageio import imread_rgb01, imwrite
+
+    cfg = Config.fromfile(args.config)
+    if args.checkpoint in (None, 'None'):
+        args.checkpoint = cfg.get('test_checkpoint_path')
+    if args.precision:
+        cfg.test_cfg['precision'] = args.precision
+    if cfg.test_cfg.get('tile', None):
+        cfg.test_cfg['tile_any_scale'] = True
+    dev = torch.device('cuda', torch.cuda.current_device())
+    model = ciaosr_amd.build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
+    if args.checkpoint:
+        load_checkpoint(model, args.checkpoint, map_location='cpu')
+    model = model.to(dev).eval()
+
+    lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
+    enc = model.encode(lq, max_scale=args.max_scale or max(args.scale))
+    name = os.path.splitext(os.path.basename(args.image))[0]
+    paths = []
+    for s in args.scale:
+        out = model.render(enc, scale=s, window=args.window)
+        paths.append(os.path.join(args.out, f'{name}_x{scale_tag(s)}.png'))
+        imwrite(metrics.tensor2img(out), paths[-1])
+        print(f'{paths[-1]}: {out.shape[-2]} x {out.shape[-1]}')
+    return paths
+
+
+if __name__ == '__main__':
+    main()
