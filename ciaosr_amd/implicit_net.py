@@ -260,7 +260,13 @@ class LocalImplicitSRSWINIR(LocalImplicitSRNet):
         max |delta| 9.3e-6, 0.00005 dB (inside the fp32 tolerance) at 3.83 ms per image (f16: 3.71, fp32: 4.97).  `effective_options(opt)`
         returns what actually runs (labels and ratios are taken from it: bench.py does).  Rounds 4-5 refused the name or, on
         `test_cfg.allow_f16_substitute = True` (or the generator attribute), ran the IEEE-half kernels with a warning: that opt-in is
-        still honoured.  The launch-bound SwinIR trunk is fp32 in every mode."""
+        still honoured.
+
+        The SwinIR trunk is fp32 in every mode unless the options carry `swin_h16=1` (`test_cfg.hip_options`): then the modes whose trunk
+        element type is f16 -- `opt.mode.trunk == 'f16'`: 'f16', 'f16-pairs', 'f16x3-fast' -- run qkv / proj / fc1 / fc2 of every Swin block on
+        the f16 MFMA (csrc/swinir_h16.hip, PSNR-gated) and batches of tiles share those launches.  In 'fp32', 'f16x3' and every bf16 mode
+        the option is ignored: 'f16x3' and 'bf16x3' promise the fp32 tolerance with an fp32 trunk, and 'bf16' here runs as 'bf16x3'.  The
+        rule is applied to what this function RETURNS (PackedSwinIR.uses_h16)."""
         opt = hip_ops.as_options(options)
         if opt.mode.name not in ('bf16', 'bf16-single'):      # 'bf16x3' asked for by name, or not a bf16 mode
             return opt

@@ -118,6 +118,26 @@ def tile_grid(h, w, tile, overlap):
     return tile, [(hi, wi) for hi in tile_starts(h, tile, overlap) for wi in tile_starts(w, tile, overlap)]
 
 
+# Tiles per call of the f16-linear SwinIR trunk (`hip_options.swin_h16`) when `test_cfg.tile_batch` is not given.
+# UNMEASURED: tools/swinir_tile_probe.py times the candidates 1, 2, 4, 7, 8 at tile = 192 (profiles/swinir_h16.txt records the run
+# that chose a value); until such a run exists this is 4 -- 1.23 GiB of trunk workspace at that tile size.
+SWIN_TILE_BATCH = 4
+
+
+def trunk_batches(generator, options):
+    """Whether the tile loops feed this generator's trunk batches of tiles: it has a `forward_hwc_batch`, and -- where the trunk says
+    so itself (PackedSwinIR.batches: only the opt-in f16-linear trunk shares launches) -- the options make it batch.  The options are
+    the ones the generator really runs with (`effective_options`)."""
+    enc = getattr(generator, '_encoder_hip', None)
+    if not hasattr(enc, 'forward_hwc_batch'):
+        return False
+    if not hasattr(enc, 'batches'):
+        return True
+    if hasattr(generator, 'effective_options'):
+        options = generator.effective_options(options)
+    return enc.batches(options)
+
+
 class CiaoSR(BasicRestorer):
     def __init__(self, generator, pixel_loss, rgb_mean=(0.5, 0.5, 0.5), rgb_std=(0.5, 0.5, 0.5), train_cfg=None,
                  test_cfg=None, pretrained=None):
@@ -175,7 +195,8 @@ class CiaoSR(BasicRestorer):
         head = getattr(gen, '_head', None)
         enc = getattr(gen, '_encoder_hip', None)
         if enc is not None and enc.supported():
-            enc.struct(opt.mode.trunk)
+            # (the SwinIR trunk reads 16-bit weights only under hip_options.swin_h16: it names its own `half`)
+            enc.struct(enc.trunk_half(opt) if hasattr(enc, 'trunk_half') else opt.mode.trunk)
         if getattr(gen, 'non_local_attn', False):
             gen.cs_attn.packed()
         if head is not None:      # last: the 'bf16-single' form runs a pack-time calibration through the (packed) fp32 trunk and cs_attn
@@ -206,7 +227,7 @@ class CiaoSR(BasicRestorer):
         n_streams = int(self.test_cfg.get('tile_streams', 1) or 1)
         n_batch = self.tile_batch(options)
         if (tile_fn is None and n_streams <= 1 and n_batch > 1 and b == 1 and len(origins) > 1 and img_lq.is_cuda and
-                hasattr(getattr(self.generator, '_encoder_hip', None), 'forward_hwc_batch')):
+                trunk_batches(self.generator, self.options(options))):
             # `test_cfg.tile_batch` (an extension; default 7 or 8, see tile_batch()) consecutive tiles share the encoder's dense-layer launches; every tile
             # is bitwise the one-at-a-time result and the blend order is the reference's
             if self.test_cfg.get('encoder_ahead', True) and len(origins) > n_batch and getattr(self.generator, '_head', None) is not None:
@@ -264,6 +285,8 @@ class CiaoSR(BasicRestorer):
         per-tile order: the image is bitwise the default path's."""
         gen = self.generator
         opt = self.options(options)
+        if hasattr(gen, 'effective_options'):
+            opt = gen.effective_options(opt)                 # what gen.forward would run with: the trunk and the head see the same options
         gen._require_hip_trunk(img_lq)                       # an uncovered trunk raises CiaoSRHipError here, not a C-level argument error
         enc = gen._encoder_hip
         dev = img_lq.device
@@ -309,10 +332,12 @@ class CiaoSR(BasicRestorer):
         Default 7 where the trunk's dense layers run a kernel whose workgroup covers 16 x 32 pixels -- the F(4x4, 3x3) Winograd kernel
         of the fp32 trunk (dense_direct = 0) and, since round 6, the 16-bit dense kernel (dense_direct != 1): a 192 x 192 tile is 72
         workgroups / items, 8 tiles are 576 = 2.25 rounds of the 256 CUs (a third round at a quarter of the chip), 7 tiles are 504 =
-        1.97 -- else 8."""
+        1.97 -- else 8.  The SwinIR trunk (batched only under `hip_options.swin_h16`): SWIN_TILE_BATCH."""
         v = self.test_cfg.get('tile_batch', None)
         if v is None:
             opt = self.options(options)
+            if hasattr(getattr(self.generator, '_encoder_hip', None), 'uses_h16'):
+                return SWIN_TILE_BATCH
             v = 7 if (opt.dense_direct == 0 if opt.mode.trunk is None else opt.dense_direct != 1) else 8
         return min(int(v or 1), 16)
 

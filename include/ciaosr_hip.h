@@ -138,6 +138,10 @@ typedef struct ciaosr_options {
     int csa_attn_v16;       /* _f32 cs_attn, composed tail, 64 channels: 0 (default) = attn.V on the four diagonal tap blocks
                              * (csa_attn_v4_f32.hip: K = 4 (Hp/2+3)(Wp/2+3) instead of 16 L; where the logit matrix -- under csa_block_mb: a band's -- is under 2 GiB);
                              * 1 = the 16C route of 16 offset columns.  Same products summed in another order */
+    int swin_h16;           /* SwinIR trunk, 0 or 1 (added in front of csa_block_mb, which stays the last field; version 240); READ ABOVE THE ABI (as query_grid_w is produced there): no entry point changes what it runs
+                             * on it.  0 (default) = ciaosr_swinir_forward_f32 in every precision mode; 1 = the callers (PackedSwinIR, the
+                             * restorer's tile loop) take ciaosr_swinir_forward_batch_f16 in the modes whose trunk element type is half
+                             * (f16, f16-pairs, f16x3-fast) and keep the fp32 trunk elsewhere (fp32, f16x3 and every bf16 mode) */
     int csa_block_mb;       /* cs_attn in bands of query rows: 0 (default) = off, the logit matrix S [Hp Wp][L] (and the 16-bit entries' probability
                              * matrix P16) whole in the workspace; n > 0 = at most n MiB of score storage at a time -- one band's S rows plus, in
                              * the _bf16 / _f16 entries, its P16 rows (ciaosr_cs_attn_block_rows names the band height).  Scores, softmax and
@@ -567,6 +571,9 @@ typedef struct ciaosr_swin_block {     /* SwinTransformerBlock (swinir_net.py:14
     const float *mask;                 /* shifted blocks: attention mask [nW][N][N] (0 / -100) for THIS call's padded map size:
                                         * the block's attn_mask buffer when the size equals its input_resolution, else
                                         * calculate_mask(x_size) (swinir_net.py:192-213, :233-236); NULL for shift 0 */
+    /* IEEE-half copies of the four Linear weights in the layouts above ([3C][ld] with the q scale folded in, [C][ld], [hidden][ld],
+     * [C][ldh], pad columns zero, 16-byte aligned), read by ciaosr_swinir_forward_batch_f16 only: NULL for the fp32 entry */
+    const unsigned short *qkv_w16, *proj_w16, *fc1_w16, *fc2_w16;
 } ciaosr_swin_block_t;
 
 typedef struct ciaosr_swinir_weights {
@@ -582,6 +589,17 @@ size_t ciaosr_swinir_workspace_bytes(int H, int W, const ciaosr_swinir_weights_t
 /* x_nchw [3][H][W] normalised LR image -> feat_hwc [H][W][embed_dim] */
 int ciaosr_swinir_forward_f32(const float* x_nchw, int H, int W, const ciaosr_swinir_weights_t* w, float* feat_hwc,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The same trunk with qkv / proj / fc1 / fc2 of every Swin block on the f16 MFMA (LayerNorm fused into the qkv and fc1 operand staging:
+ * five launches per block instead of seven), B >= 1 equally sized images per call: x_bchw [B][3][H][W] -> feat_bhwc [B][H][W][embed_dim].
+ * Every block launch is shared by the B images; image b is bitwise the B = 1 call on that image.  The residual stream, the window
+ * attention (its output is rounded to half for the proj), the LayerNorm statistics, conv_first, the 3x3 convolutions and both outer norms
+ * stay fp32.  Shape checks as ciaosr_swinir_forward_f32; needs the four *_w16 pointers of every block (CIAOSR_ERR_BAD_ARG without them;
+ * the fp32 qkv_w / proj_w / fc1_w / fc2_w are not read).  Every refusal happens before anything is enqueued.  A batch of more than
+ * 2^30 tokens (B * Hp * Wp) is refused (CIAOSR_ERR_BAD_ARG), not split into sub-batches.  Accuracy: PSNR-gated. */
+size_t ciaosr_swinir_workspace_bytes_batch_f16(int B, int H, int W, const ciaosr_swinir_weights_t* w);
+int ciaosr_swinir_forward_batch_f16(const float* x_bchw, int B, int H, int W, const ciaosr_swinir_weights_t* w, float* feat_bhwc,
+                                    const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace, size_t workspace_bytes,
+                                    void* stream);
 
 /* ---- restorer plumbing (rest:142-169, :218-258) --------------------------------------------- */
 /* x = (lq - mean) / std on [3][H][W] */
