@@ -1,0 +1,280 @@
+// Affine views of an encoded scene (include/ciaosr_hip.h, "views"): the queries of an Hv x Wv output grid under a 2 x 3 matrix into LR
+// pixel units, sorted into the LR tiles of the reference's tiling and blended back.  Four roles -- count, select, blend, finalize -- and
+// the whole grid's coordinates in one frame.  No atomics: tile membership is counted with wave ballots, a block's members are placed at
+// (exclusive scan of the per-block counts) + (rank inside the block), so every result is bitwise repeatable.
+#include <climits>
+#include <cmath>
+
+#include "common.h"
+
+namespace ciaosr {
+
+// A block of kViewThreads threads owns kViewChunk consecutive queries, in kViewRounds rounds of one query per thread: query
+// q = block * kViewChunk + round * kViewThreads + thread, so (round, wave, lane) in lexicographic order is increasing q.
+constexpr int kViewThreads = 256, kViewRounds = 4, kViewChunk = kViewThreads * kViewRounds, kViewWaves = kViewThreads / kWave;
+constexpr int kViewTileBatch = 256;        // tiles whose per-wave counts one pass of the count kernel keeps in LDS
+
+struct ViewP { double myy, myx, ty, mxy, mxx, tx; int Hv, Wv; long Q; };
+struct ViewFrame { double y0, x0, y1, x1, th, tw; };       // [y0, y1) x [x0, x1) in LR pixel units, y1 = y0 + th (exact: integers)
+
+// LR position of the centre of output pixel q, fp64, every operation rounded on its own (an FMA would change the value that the
+// membership tests and the fp32 rounding of the coordinate see)
+__device__ __forceinline__ void view_point(const ViewP& p, long q, double& y, double& x) {
+#pragma clang fp contract(off)
+    const int i = (int)(q / p.Wv), j = (int)(q - (long)i * p.Wv);
+    const double v = (double)i + 0.5, u = (double)j + 0.5;
+    y = (p.myy * v + p.myx * u) + p.ty;
+    x = (p.mxy * v + p.mxx * u) + p.tx;
+}
+__device__ __forceinline__ bool view_member(double y, double x, const ViewFrame& f) {
+    return y >= f.y0 && y < f.y1 && x >= f.x0 && x < f.x1;           // NaN: no member
+}
+__device__ __forceinline__ float2 view_coord(double y, double x, const ViewFrame& f) {
+#pragma clang fp contract(off)
+    return make_float2((float)(((y - f.y0) / f.th) * 2.0 - 1.0), (float)(((x - f.x0) / f.tw) * 2.0 - 1.0));
+}
+__device__ __forceinline__ ViewFrame view_frame(int y0, int x0, int th, int tw) {
+    return ViewFrame{(double)y0, (double)x0, (double)y0 + (double)th, (double)x0 + (double)tw, (double)th, (double)tw};
+}
+
+// part[t * n_blocks + b] = members of tile t among block b's queries.  Per tile one ballot per round and wave; lane 0 of each wave owns
+// its LDS slot, so nothing is added concurrently.
+__global__ __launch_bounds__(kViewThreads) void view_count_kernel(ViewP p, const int* __restrict__ tiles, int n_tiles, int n_blocks,
+                                                                  int* __restrict__ part) {
+    __shared__ int s_cnt[kViewTileBatch][kViewWaves];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const long q0 = (long)blockIdx.x * kViewChunk + tid;
+    double y[kViewRounds], x[kViewRounds];
+    bool live[kViewRounds];
+#pragma unroll
+    for (int r = 0; r < kViewRounds; ++r) {
+        const long q = q0 + (long)r * kViewThreads;
+        live[r] = q < p.Q;
+        y[r] = x[r] = 0.0;
+        if (live[r]) view_point(p, q, y[r], x[r]);
+    }
+    for (int t0 = 0; t0 < n_tiles; t0 += kViewTileBatch) {
+        const int nt = min(kViewTileBatch, n_tiles - t0);
+        for (int t = 0; t < nt; ++t) {
+            const int4 tl = reinterpret_cast<const int4*>(tiles)[t0 + t];          // (y0, x0, th, tw): the same for every lane
+            const ViewFrame f = view_frame(tl.x, tl.y, tl.z, tl.w);
+            int c = 0;
+#pragma unroll
+            for (int r = 0; r < kViewRounds; ++r) c += __popcll(__ballot(live[r] && view_member(y[r], x[r], f)));
+            if (lane == 0) s_cnt[t][wave] = c;
+        }
+        __syncthreads();
+        for (int t = tid; t < nt; t += kViewThreads) {
+            int c = 0;
+#pragma unroll
+            for (int w = 0; w < kViewWaves; ++w) c += s_cnt[t][w];
+            part[(size_t)(t0 + t) * n_blocks + blockIdx.x] = c;
+        }
+        __syncthreads();
+    }
+}
+
+// One wave per tile: part[t][*] becomes its exclusive scan over the blocks, counts[t] the total
+__global__ __launch_bounds__(kWave) void view_scan_kernel(int* __restrict__ part, int n_blocks, int* __restrict__ counts) {
+    int* row = part + (size_t)blockIdx.x * n_blocks;
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int b0 = 0; b0 < n_blocks; b0 += kWave) {
+        const int b = b0 + lane;
+        const int v = b < n_blocks ? row[b] : 0;
+        int incl = v;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int up = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += up;
+        }
+        if (b < n_blocks) row[b] = carry + incl - v;
+        carry += __shfl(incl, kWave - 1, kWave);
+    }
+    if (lane == 0) counts[blockIdx.x] = carry;
+}
+
+// The members of one tile in increasing q: position = offs[block] + members of the block before this one
+__global__ __launch_bounds__(kViewThreads) void view_select_kernel(ViewP p, ViewFrame f, float2 cellv, const int* __restrict__ offs, long n,
+                                                                   int* __restrict__ q_index, float* __restrict__ coord,
+                                                                   float* __restrict__ cell) {
+    __shared__ int s_cnt[kViewRounds][kViewWaves];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const long q0 = (long)blockIdx.x * kViewChunk + tid;
+    double y[kViewRounds], x[kViewRounds];
+    int rank[kViewRounds];                     // among the members of the same round and wave, -1: no member
+#pragma unroll
+    for (int r = 0; r < kViewRounds; ++r) {
+        const long q = q0 + (long)r * kViewThreads;
+        bool m = false;
+        y[r] = x[r] = 0.0;
+        if (q < p.Q) {
+            view_point(p, q, y[r], x[r]);
+            m = view_member(y[r], x[r], f);
+        }
+        const unsigned long long mask = __ballot(m);
+        rank[r] = m ? __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+        if (lane == 0) s_cnt[r][wave] = __popcll(mask);
+    }
+    __syncthreads();
+    long pos = offs[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < kViewRounds; ++r) {
+#pragma unroll
+        for (int w = 0; w < kViewWaves; ++w) {
+            if (w == wave && rank[r] >= 0) {
+                const long o = pos + rank[r];
+                if (o >= 0 && o < n) {         // holds whenever offs / n come from the count of the same view and tile
+                    q_index[o] = (int)(q0 + (long)r * kViewThreads);
+                    reinterpret_cast<float2*>(coord)[o] = view_coord(y[r], x[r], f);
+                    reinterpret_cast<float2*>(cell)[o] = cellv;
+                }
+            }
+            pos += s_cnt[r][w];
+        }
+    }
+}
+
+__global__ void view_coord_cell_kernel(ViewP p, ViewFrame f, float2 cellv, float* __restrict__ coord, float* __restrict__ cell) {
+    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < p.Q; q += (long)gridDim.x * blockDim.x) {
+        double y, x;
+        view_point(p, q, y, x);
+        reinterpret_cast<float2*>(coord)[q] = view_coord(y, x, f);
+        reinterpret_cast<float2*>(cell)[q] = cellv;
+    }
+}
+
+__global__ void view_blend_kernel(float* __restrict__ E, float* __restrict__ Wt, long Q, const int* __restrict__ q_index,
+                                  const float* __restrict__ rgb, long n) {
+    for (long s = blockIdx.x * (long)blockDim.x + threadIdx.x; s < n; s += (long)gridDim.x * blockDim.x) {
+        const long q = q_index ? (long)q_index[s] : s;
+        if (q < 0 || q >= Q) continue;
+        E[q] += rgb[s * 3];
+        E[Q + q] += rgb[s * 3 + 1];
+        E[2 * Q + q] += rgb[s * 3 + 2];
+        Wt[q] += 1.f;
+    }
+}
+
+struct Fill3 { float v[3]; };
+__global__ void view_finalize_kernel(const float* __restrict__ E, const float* __restrict__ Wt, float* __restrict__ out, long Q, Fill3 fill) {
+    const long n = 3 * Q;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i / Q);
+        const long q = i - (long)c * Q;
+        const float w = Wt[q];
+        out[q * 3 + c] = w > 0.f ? E[i] / w : fill.v[c];
+    }
+}
+
+static inline int view_grid(long n) {
+    const long g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+static inline bool view_ok(const double* m, int Hv, int Wv) {
+    if (!m || Hv <= 0 || Wv <= 0 || (long)Hv * Wv > (long)INT_MAX) return false;
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(m[i])) return false;
+    return true;
+}
+static inline ViewP view_p(const double* m, int Hv, int Wv) { return ViewP{m[0], m[1], m[2], m[3], m[4], m[5], Hv, Wv, (long)Hv * Wv}; }
+static inline bool frame_ok(const int* f) { return f && f[0] >= 0 && f[1] >= 0 && f[2] > 0 && f[3] > 0 && f[0] <= INT_MAX - f[2] && f[1] <= INT_MAX - f[3]; }
+static inline ViewFrame frame_of(const int* f) {
+    return ViewFrame{(double)f[0], (double)f[1], (double)f[0] + (double)f[2], (double)f[1] + (double)f[3], (double)f[2], (double)f[3]};
+}
+// the view's cell in a th x tw frame: the norm of a matrix row is the output pixel's extent along that LR axis
+static inline float2 view_cell(const double* m, const int* f) {
+    return make_float2((float)(std::hypot(m[0], m[1]) * 2.0 / (double)f[2]), (float)(std::hypot(m[3], m[4]) * 2.0 / (double)f[3]));
+}
+static inline int view_blocks(long Q) { return (int)((Q + kViewChunk - 1) / kViewChunk); }
+
+// The value v with clamp(v * std + mean, 0, 1) == fill in ciaosr_denorm_clamp_f32's arithmetic (two rounded fp32 operations), searched
+// among the neighbours of (fill - mean) / std; where no fp32 value maps onto fill, the one that comes nearest
+static float fill_preimage(float fill, float mean, float std_) {
+#pragma clang fp contract(off)
+    float best = (float)(((double)fill - (double)mean) / (double)std_);
+    float lo = best, hi = best;
+    double best_err = HUGE_VAL;
+    float pick = best;
+    for (int k = 0; k <= 8; ++k) {
+        const float cand[2] = {lo, hi};
+        for (int s = 0; s < 2; ++s) {
+            volatile float prod = cand[s] * std_;
+            volatile float sum = prod + mean;
+            const float got = fminf(fmaxf(sum, 0.f), 1.f);
+            const double err = std::fabs((double)got - (double)fill);
+            if (err < best_err) { best_err = err; pick = cand[s]; }
+        }
+        if (best_err == 0.0) break;
+        lo = std::nextafterf(lo, -HUGE_VALF);
+        hi = std::nextafterf(hi, HUGE_VALF);
+    }
+    return pick;
+}
+
+}  // namespace ciaosr
+
+using namespace ciaosr;
+
+extern "C" int ciaosr_view_block_queries(void) { return kViewChunk; }
+
+extern "C" size_t ciaosr_view_workspace_bytes(int Hv, int Wv, int n_tiles) {
+    if (Hv <= 0 || Wv <= 0 || n_tiles <= 0 || (long)Hv * Wv > (long)INT_MAX) return 0;
+    return (size_t)n_tiles * (size_t)view_blocks((long)Hv * Wv) * sizeof(int);
+}
+
+extern "C" int ciaosr_view_coord_cell_f32(float* coord, float* cell, const double* m, int Hv, int Wv, const int* frame, void* stream) {
+    CIAOSR_CHECK_ARG(coord && cell && view_ok(m, Hv, Wv) && frame_ok(frame));
+    ProfScope prof("view_coord_cell", (hipStream_t)stream);
+    const ViewP p = view_p(m, Hv, Wv);
+    hipLaunchKernelGGL(view_coord_cell_kernel, dim3(view_grid(p.Q)), dim3(256), 0, (hipStream_t)stream, p, frame_of(frame), view_cell(m, frame),
+                       coord, cell);
+    return launch_status("view_coord_cell");
+}
+
+extern "C" int ciaosr_view_count_i32(const double* m, int Hv, int Wv, const int* tiles, int n_tiles, int* counts, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(view_ok(m, Hv, Wv) && tiles && n_tiles > 0 && counts && workspace && aligned16(tiles));
+    if (workspace_bytes < ciaosr_view_workspace_bytes(Hv, Wv, n_tiles)) return CIAOSR_ERR_WORKSPACE;
+    ProfScope prof("view_count", (hipStream_t)stream);
+    const ViewP p = view_p(m, Hv, Wv);
+    const int n_blocks = view_blocks(p.Q);
+    hipLaunchKernelGGL(view_count_kernel, dim3(n_blocks), dim3(kViewThreads), 0, (hipStream_t)stream, p, tiles, n_tiles, n_blocks,
+                       (int*)workspace);
+    hipLaunchKernelGGL(view_scan_kernel, dim3(n_tiles), dim3(kWave), 0, (hipStream_t)stream, (int*)workspace, n_blocks, counts);
+    return launch_status("view_count");
+}
+
+extern "C" int ciaosr_view_select_f32(const double* m, int Hv, int Wv, const int* tile, int tile_index, int n_tiles, const void* workspace,
+                                      size_t workspace_bytes, int n, int* q_index, float* coord, float* cell, void* stream) {
+    CIAOSR_CHECK_ARG(view_ok(m, Hv, Wv) && frame_ok(tile) && n_tiles > 0 && tile_index >= 0 && tile_index < n_tiles && workspace);
+    CIAOSR_CHECK_ARG(n > 0 && (long)n <= (long)Hv * Wv && q_index && coord && cell);
+    if (workspace_bytes < ciaosr_view_workspace_bytes(Hv, Wv, n_tiles)) return CIAOSR_ERR_WORKSPACE;
+    ProfScope prof("view_select", (hipStream_t)stream);
+    const ViewP p = view_p(m, Hv, Wv);
+    const int n_blocks = view_blocks(p.Q);
+    hipLaunchKernelGGL(view_select_kernel, dim3(n_blocks), dim3(kViewThreads), 0, (hipStream_t)stream, p, frame_of(tile), view_cell(m, tile),
+                       (const int*)workspace + (size_t)tile_index * n_blocks, (long)n, q_index, coord, cell);
+    return launch_status("view_select");
+}
+
+extern "C" int ciaosr_view_blend_f32(float* E, float* Wt, int Q, const int* q_index, const float* rgb, int n, void* stream) {
+    CIAOSR_CHECK_ARG(E && Wt && rgb && Q > 0 && n > 0 && n <= Q);
+    ProfScope prof("view_blend", (hipStream_t)stream);
+    hipLaunchKernelGGL(view_blend_kernel, dim3(view_grid(n)), dim3(256), 0, (hipStream_t)stream, E, Wt, (long)Q, q_index, rgb, (long)n);
+    return launch_status("view_blend");
+}
+
+extern "C" int ciaosr_view_finalize_f32(const float* E, const float* Wt, float* out_q3, int Q, const float* fill3, const float* mean3,
+                                        const float* std3, void* stream) {
+    CIAOSR_CHECK_ARG(E && Wt && out_q3 && Q > 0 && fill3 && mean3 && std3);
+    Fill3 fill;
+    for (int c = 0; c < 3; ++c) {
+        CIAOSR_CHECK_ARG(fill3[c] >= 0.f && fill3[c] <= 1.f && std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] != 0.f);
+        fill.v[c] = fill_preimage(fill3[c], mean3[c], std3[c]);
+    }
+    ProfScope prof("view_finalize", (hipStream_t)stream);
+    hipLaunchKernelGGL(view_finalize_kernel, dim3(view_grid(3L * Q)), dim3(256), 0, (hipStream_t)stream, E, Wt, out_q3, (long)Q, fill);
+    return launch_status("view_finalize");
+}

@@ -235,6 +235,77 @@ def tile_finalize(E, Wt):
     return out
 
 
+# ---- affine views of an encoded scene (include/ciaosr_hip.h, "views"; the definition and the host helpers: scene.py) -------------------
+def _m6(m):
+    m = [float(v) for v in m]
+    if len(m) != 6:
+        raise ValueError(f'a view matrix is (m_yy, m_yx, t_y, m_xy, m_xx, t_x), got {len(m)} numbers')
+    return (C.c_double * 6)(*m)
+
+
+def _i4(frame):
+    return (C.c_int * 4)(*[int(v) for v in frame])
+
+
+def view_block_queries():
+    """Consecutive queries one workgroup of the count / select kernels owns."""
+    return _lib.load().ciaosr_view_block_queries()
+
+
+def make_coord_cell_view(m, hv, wv, frame, device):
+    """(coord, cell), each [hv * wv, 2], of the whole hv x wv view under matrix `m` in the frame (y0, x0, th, tw), made on the device,
+    members of the frame or not.  The grid's width is registered for `grid_width_of`: a view is walked as a row-major grid."""
+    n = hv * wv
+    coord = torch.empty(n, 2, dtype=torch.float32, device=device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=device)
+    _lib.call('ciaosr_view_coord_cell_f32', ptr(coord), ptr(cell), _m6(m), hv, wv, _i4(frame), stream_ptr())
+    if len(_window_width) > 64:
+        _window_width.clear()
+    _window_width[(coord.data_ptr(), n)] = wv
+    return coord, cell
+
+
+def view_count(m, hv, wv, tiles):
+    """tiles [n_tiles, 4] int32 on the device, rows (y0, x0, th, tw) -> (counts [n_tiles] int32 on the device, ws): the members of every
+    tile among the hv x wv queries, in one pass over the queries; `ws` is what `view_select` places a tile's members with."""
+    require_gpu(tiles)
+    n_tiles = tiles.shape[0]
+    lib = _lib.load()
+    ws = workspace(lib.ciaosr_view_workspace_bytes(hv, wv, n_tiles), tiles.device, slot='view')
+    counts = torch.empty(n_tiles, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_view_count_i32', _m6(m), hv, wv, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws
+
+
+def view_select(m, hv, wv, frame, index, n_tiles, ws, n):
+    """The `n` members (view_count's number) of tile `index` = `frame`, in increasing query index: (q_index [n] int32, coord [n, 2],
+    cell [n, 2] in the tile's frame).  No grid hint is registered: the head sees a caller's own list of coordinates."""
+    q_index = torch.empty(n, dtype=torch.int32, device=ws.device)
+    coord = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    _window_width.pop((coord.data_ptr(), n), None)          # the allocator may hand out the address of a dead grid's coordinates
+    _lib.call('ciaosr_view_select_f32', _m6(m), hv, wv, _i4(frame), index, n_tiles, ptr(ws), ws.numel(), n, ptr(q_index), ptr(coord),
+              ptr(cell), stream_ptr())
+    return q_index, coord, cell
+
+
+def view_blend(E, Wt, q_index, rgb):
+    """E[:, q_index[s]] += rgb[s], Wt[q_index[s]] += 1 (E [3, Q], Wt [Q], rgb [n, 3]); q_index None: s itself."""
+    require_gpu(E, Wt, q_index, rgb)
+    if E.shape != (3, Wt.shape[0]) or rgb.dim() != 2 or rgb.shape[1] != 3 or (q_index is not None and q_index.shape != (rgb.shape[0],)):
+        raise ValueError(f'view_blend: E {tuple(E.shape)}, Wt {tuple(Wt.shape)}, rgb {tuple(rgb.shape)} do not fit together')
+    _lib.call('ciaosr_view_blend_f32', ptr(E), ptr(Wt), Wt.shape[0], ptr(q_index), ptr(rgb), rgb.shape[0], stream_ptr())
+
+
+def view_finalize(E, Wt, fill, mean, std):
+    """[Q, 3] for `denorm_clamp`: E / Wt where a tile claimed the query, elsewhere what `denorm_clamp` turns into `fill` (three floats in
+    the output's [0, 1])."""
+    require_gpu(E, Wt)
+    out = torch.empty(Wt.shape[0], 3, dtype=torch.float32, device=E.device)
+    _lib.call('ciaosr_view_finalize_f32', ptr(E), ptr(Wt), ptr(out), Wt.shape[0], _f3(fill), _f3(mean), _f3(std), stream_ptr())
+    return out
+
+
 class Mode(namedtuple('Mode', 'name precision f16_pairs bf16_single trunk head')):
     """One named arithmetic mode.  (precision, f16_pairs, bf16_single): the entry suffix and the canonical ciaosr_options_t fields
     (include/ciaosr_hip.h, "Precision modes").  trunk: element type of the RDN trunk's dense layers, None = the fp32 trunk.  head: the

@@ -447,6 +447,58 @@ class CiaoSR(BasicRestorer):
             return metrics_hip.tensor2img_u8(out)
         return out
 
+    @torch.no_grad()
+    def render_view(self, enc, matrix, size, fill=0.0, as_u8=False):
+        """The Hv x Wv (`size`) affine view `matrix` = (m_yy, m_yx, t_y, m_xy, m_xx, t_x) of an `encode` result (scene.py: the definition,
+        `view_matrix`, `view_of_window`): [B, 3, Hv, Wv], de-normalised and clamped, or with `as_u8` the metrics_hip.tensor2img_u8 image
+        of it.  A pixel whose centre falls outside the image holds `fill` (one number or three, in the output's [0, 1]).  The queries are
+        made, sorted into the LR tiles (the whole image without `test_cfg.tile`) and blended back on the device, in the reference's
+        row-major tile order; a tile without a member is neither built nor queried.  With `test_cfg.tile` this needs
+        `test_cfg.tile_any_scale`.  Per batch item ONE device-to-host copy -- the tiles' member counts, which size the per-tile query
+        lists -- is the only synchronisation of a view render.  An axis-aligned view is not bitwise the window `render` shows (its
+        coordinates differ by up to 2^-22, see `scene.view_of_window`)."""
+        from . import scene as sc
+        x = enc.x
+        nb, _, h, w = x.shape
+        hv, wv = int(size[0]), int(size[1])
+        if hv < 1 or wv < 1:
+            raise ValueError(f'empty view grid {hv} x {wv}')
+        m = tuple(float(v) for v in matrix)
+        tile = self.test_cfg.get('tile', None)
+        frames = sc.plan_view(h, w, tile, self.test_cfg.get('tile_overlap', None), bool(self.test_cfg.get('tile_any_scale', False)))
+        sc.view_cell(m, frames[0][2], frames[0][3])                      # ValueError: singular, or a cell >= 1
+        fill = tuple(float(v) for v in fill) if hasattr(fill, '__len__') else (float(fill),) * 3
+        if len(fill) != 3 or not all(0.0 <= v <= 1.0 for v in fill):
+            raise ValueError(f'fill is one number or three in [0, 1], got {fill}')
+        if enc.max_scale is None:
+            enc.max_scale = sc.view_max_scale(m)
+        if enc.view_tiles is None:                                      # uploaded once per encoded image, not per view
+            enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
+        gen = self.generator
+        n_q = hv * wv
+        preds = []
+        for b in range(nb):
+            counts, ws = hip_ops.view_count(m, hv, wv, enc.view_tiles)
+            counts = counts.tolist()                                    # the one synchronisation
+            E = torch.zeros(3, n_q, dtype=torch.float32, device=x.device)
+            Wt = torch.zeros(n_q, dtype=torch.float32, device=x.device)
+            for k, (frame, n) in enumerate(zip(frames, counts)):        # the reference's blend order
+                if n == 0:
+                    continue
+                tile_scene = enc.cache.get((b, (frame[0], frame[1]) if tile else None))
+                if n == n_q:                                            # the tile owns the whole view: a grid, known to the head as one
+                    q_index = None
+                    coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frame, x.device)
+                else:
+                    q_index, coord, cell = hip_ops.view_select(m, hv, wv, frame, k, len(frames), ws, n)
+                hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
+            preds.append(hip_ops.view_finalize(E, Wt, fill, self.rgb_mean, self.rgb_std))
+        out = torch.stack([hip_ops.denorm_clamp(p, hv, wv, self.rgb_mean, self.rgb_std) for p in preds])
+        if as_u8:
+            from . import metrics_hip
+            return metrics_hip.tensor2img_u8(out)
+        return out
+
     def _restore(self, lq, coord=None, cell=None, options=None):
         x = self.normalize(lq)
         if self.test_cfg.get('tile', None) and self.test_cfg.get('tile_any_scale', False) and coord is not None:

@@ -1,9 +1,12 @@
 """Encode once, render any scale or window: the host side of the persistent head scene (include/ciaosr_hip.h, "a persistent head scene").
 
 Pure Python, no GPU: the window planner (which LR tiles a window of the HR grid touches, and which part of each), the least-recently-used
-cache that bounds the bytes of tile scenes kept alive, and the record `CiaoSR.encode` returns.  The device work is in
-`PackedHead.prepare` / `query` (head_hip.py) and `hip_ops.make_coord_cell_window`.
+cache that bounds the bytes of tile scenes kept alive, the record `CiaoSR.encode` returns, and the affine views of
+`CiaoSR.render_view` (their matrices, cells and tile lists).  The device work is in `PackedHead.prepare` / `query` (head_hip.py),
+`hip_ops.make_coord_cell_window` and the `hip_ops.view_*` wrappers.
 """
+import ctypes
+import math
 from collections import OrderedDict
 
 from . import tile_plan
@@ -77,6 +80,83 @@ def plan_window(h, w, tile, overlap, ht, wt, window=None, scale=None, any_scale=
     return out
 
 
+# ---- affine views (include/ciaosr_hip.h, "views") ------------------------------------------------------------------------------------
+# A view is an output grid Hv x Wv and m = (m_yy, m_yx, t_y, m_xy, m_xx, t_x), y first: output pixel (i, j), centre v = i + 0.5,
+# u = j + 0.5, looks at y_lr = (m_yy v + m_yx u) + t_y, x_lr = (m_xy v + m_xx u) + t_x in LR pixel units (the image is [0, h) x [0, w),
+# LR pixel k has its centre at k + 0.5), fp64, every operation rounded on its own.
+_QUARTER_TURNS = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}
+
+
+def view_matrix(center, zoom, angle_deg, size):
+    """The matrix of the Hv x Wv view (`size`) whose centre (v, u) = (Hv / 2, Wv / 2) looks at `center` = (cy, cx), LR pixel units,
+    with `zoom` output pixels per LR pixel, turned by `angle_deg`:
+        y_lr - cy = (cos a (v - Hv / 2) - sin a (u - Wv / 2)) / zoom
+        x_lr - cx = (sin a (v - Hv / 2) + cos a (u - Wv / 2)) / zoom
+    -- the rotation matrix [[cos, -sin], [sin, cos]] on (v, u), y first.  Sign: a positive angle turns the picture clockwise on the
+    screen (the camera counter-clockwise).  At 90 degrees the view's top-left corner shows the image's bottom-left, and walking right
+    in the view walks up the image; -32 degrees straightens a picture that hangs 32 degrees clockwise.  Multiples of 90 degrees use exact
+    0 / +-1 for cos / sin, so the entries are exactly 0 or +-1 / zoom."""
+    cy, cx = (float(v) for v in center)
+    hv, wv = int(size[0]), int(size[1])
+    zoom = float(zoom)
+    if not (zoom > 0 and math.isfinite(zoom)) or hv < 1 or wv < 1:
+        raise ValueError(f'view_matrix needs zoom > 0 and a grid of at least 1 x 1 (zoom {zoom}, size {hv} x {wv})')
+    turn = math.fmod(float(angle_deg), 360.0) % 360.0
+    c, s = _QUARTER_TURNS.get(turn) or (math.cos(math.radians(turn)), math.sin(math.radians(turn)))
+    inv = 1.0 / zoom
+    myy, myx, mxy, mxx = c * inv + 0.0, -s * inv + 0.0, s * inv + 0.0, c * inv + 0.0
+    return (myy, myx, cy - (myy * (hv / 2.0) + myx * (wv / 2.0)), mxy, mxx, cx - (mxy * (hv / 2.0) + mxx * (wv / 2.0)))
+
+
+def view_of_window(h, w, ht, wt, window=None):
+    """(matrix, (Hv, Wv)) of the axis-aligned view that looks at the window (i0, j0, hh, ww) of the ht x wt target grid of an h x w image
+    (default: the whole grid): what `render(enc, size=(ht, wt), window=window)` shows.  Not bitwise that render: its coordinates round
+    three times in fp32 (make_coord), a view's once from fp64; the two differ by at most 2^-22."""
+    i0, j0, hh, ww = check_window(ht, wt, window)
+    sy, sx = h / ht, w / wt
+    return (sy, 0.0, i0 * sy, 0.0, sx, j0 * sx), (hh, ww)
+
+
+def _f32(v):
+    return ctypes.c_float(v).value
+
+
+def view_cell(matrix, th, tw):
+    """(cell_y, cell_x) of a view in a th x tw frame, the fp32 values the kernels write: hypot(row) * 2 / t -- the norm of a matrix row is
+    the extent of an output pixel along that LR axis, so this is make_cell's 2 / Ht for an axis-aligned view and does not change under
+    rotation.  ValueError for a singular (or non-finite) matrix and for a cell component >= 1: the reference divides by 1 - cell."""
+    m = [float(v) for v in matrix]
+    if len(m) != 6 or not all(math.isfinite(v) for v in m):
+        raise ValueError(f'a view matrix is six finite numbers (m_yy, m_yx, t_y, m_xy, m_xx, t_x), got {matrix!r}')
+    if m[0] * m[4] - m[1] * m[3] == 0.0:
+        raise ValueError(f'singular view matrix {tuple(m)}: the view collapses onto a line or a point of the image')
+    cell = (_f32(math.hypot(m[0], m[1]) * 2.0 / th), _f32(math.hypot(m[3], m[4]) * 2.0 / tw))
+    if max(cell) >= 1.0:
+        raise ValueError(f'view cell {cell} >= 1 in a {th} x {tw} frame: an output pixel may span less than half the frame '
+                         f'(the reference divides by 1 - cell)')
+    return cell
+
+
+def view_max_scale(matrix):
+    """Output pixels per LR pixel along the finer of the two LR axes: what `encode`'s max_scale is set to by a first view render."""
+    return max(1.0 / math.hypot(matrix[0], matrix[1]), 1.0 / math.hypot(matrix[3], matrix[4]))
+
+
+def plan_view(h, w, tile=None, overlap=None, any_scale=False):
+    """The frames (y0, x0, th, tw) a view of an h x w image is sorted into, row-major (the reference's blend order): the whole image
+    without `tile`, else the reference's LR tiling (`plan_window`'s).  A query belongs to every frame its LR position lies in -- 1, 2 or
+    4 with overlapping tiles.  Tiled views need `tile_any_scale`: `clip_test`'s integer-scale HR rectangles mean nothing under a
+    rotation or a fractional pan."""
+    if not tile:
+        return [(0, 0, h, w)]
+    if not any_scale:
+        raise ValueError(f'tiled rendering without test_cfg.tile_any_scale makes the ({h} * s) x ({w} * s) image of the integer '
+                         f'test_cfg.scale only (asked: an affine view)')
+    tile = min(int(tile), h, w)
+    overlap = min(int(overlap or 0), tile - 1)
+    return [(y0, x0, tile, tile) for y0 in tile_plan.tile_starts(h, tile, overlap) for x0 in tile_plan.tile_starts(w, tile, overlap)]
+
+
 class SceneCache:
     """Least-recently-used cache of built scenes under a byte budget.  `build(key)` returns an object with `.nbytes`.  The entry `get`
     returns is never evicted by that call, so the smallest budget still works, by rebuilding; `builds` counts every build, rebuilt
@@ -125,6 +205,7 @@ class EncodedImage:
         self.options = options
         self.max_scale = max_scale
         self.cache = SceneCache(budget_bytes, build)
+        self.view_tiles = None          # render_view's frame list on the device, uploaded by the first view render
 
     @property
     def shape(self):

@@ -614,6 +614,41 @@ int ciaosr_tile_blend_f32(float* E, float* Wt, int Himg, int Wimg, const float* 
 /* out_q3[(y*W+x)*3+c] = E[c][y][x] / Wt[c][y][x]                          (rest:255-256) */
 int ciaosr_tile_finalize_f32(const float* E, const float* Wt, float* out_q3, int Himg, int Wimg, void* stream);
 
+/* ---- views: an encoded scene seen through an affine map (an extension, absent from the reference) ------------------------------------
+ * A view is an output grid Hv x Wv and a host matrix m[6] = {m_yy, m_yx, t_y, m_xy, m_xx, t_x} (y first).  Output pixel (i, j), query
+ * q = i Wv + j, has its centre at v = i + 0.5, u = j + 0.5 and maps to LR pixel units (the image is [0, h) x [0, w), LR pixel k has its
+ * centre at k + 0.5):
+ *     y_lr = (m_yy v + m_yx u) + t_y,   x_lr = (m_xy v + m_xx u) + t_x
+ * in fp64, every operation rounded on its own (no FMA).  A frame or tile {y0, x0, th, tw} (ints, LR pixels; the whole image is
+ * {0, 0, h, w}) owns the queries with y0 <= y_lr < y0 + th and x0 <= x_lr < x0 + tw, decided in fp64: tile_plan's centre membership.
+ * In that frame coord = fp32(((y_lr - y0) / th) 2 - 1) (likewise x), one rounding of an fp64 value, and the cell -- constant over an
+ * affine view -- is fp32(hypot(m_yy, m_yx) 2 / th), fp32(hypot(m_xy, m_xx) 2 / tw), the norms made on the host in fp64.  An
+ * axis-aligned view is NOT bitwise ciaosr_make_coord_cell_window_f32's grid (three fp32 roundings there): the two differ by <= 2^-22.
+ * Hv Wv <= 2^31 - 1.  No entry allocates, synchronises or keeps state; no atomics: every result is bitwise repeatable. */
+/* queries per workgroup of count / select (their workspace holds one int per tile and workgroup) */
+int ciaosr_view_block_queries(void);
+size_t ciaosr_view_workspace_bytes(int Hv, int Wv, int n_tiles);
+/* coord, cell [Hv Wv][2] of the whole grid in one frame (host ints), members or not */
+int ciaosr_view_coord_cell_f32(float* coord, float* cell, const double* m /*host [6]*/, int Hv, int Wv, const int* frame /*host [4]*/,
+                               void* stream);
+/* count: one pass over all queries.  tiles: n_tiles x {y0, x0, th, tw} on the DEVICE, 16-byte aligned.  counts [n_tiles] (device): the
+ * members of every tile.  workspace (ciaosr_view_workspace_bytes, 4-byte aligned): per tile, the exclusive scan over the workgroups of
+ * their member counts -- what select places a tile's members with; valid until the next count on the same workspace. */
+int ciaosr_view_count_i32(const double* m /*host [6]*/, int Hv, int Wv, const int* tiles, int n_tiles, int* counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* select: the members of tile `tile_index` of the list count saw (`tile`: its four ints, host), in increasing q: q_index [n], coord and
+ * cell [n][2] in the tile's frame, n = counts[tile_index] (nothing is written past n). */
+int ciaosr_view_select_f32(const double* m /*host [6]*/, int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles,
+                           const void* workspace, size_t workspace_bytes, int n, int* q_index, float* coord, float* cell, void* stream);
+/* blend: E[c][q_index[s]] += rgb[s][c], Wt[q_index[s]] += 1 for s < n; E [3][Q], Wt [Q].  q_index = NULL: s itself (a tile that owns the
+ * whole view).  An index may appear once per call at most; one outside [0, Q) is skipped. */
+int ciaosr_view_blend_f32(float* E, float* Wt, int Q, const int* q_index /*may be NULL*/, const float* rgb, int n, void* stream);
+/* finalize: out_q3[q][c] = E[c][q] / Wt[q] where Wt[q] > 0 (ciaosr_denorm_clamp_f32's input layout); elsewhere the value that
+ * ciaosr_denorm_clamp_f32 with mean3 / std3 turns into fill3[c] (in [0, 1], the output's space) -- exactly, whenever some fp32 value
+ * near (fill - mean) / std does (always for 0 and 1, which the clamp reaches), else into the nearest value it can give. */
+int ciaosr_view_finalize_f32(const float* E, const float* Wt, float* out_q3, int Q, const float* fill3 /*host*/, const float* mean3 /*host*/,
+                             const float* std3 /*host*/, void* stream);
+
 /* ---- test data: GT -> LR degradation (configs/001_*.py, val_scale > 4) ---------------------- */
 /* Pillow-exact bicubic resample of an 8-bit RGB image, PIL Image.resize((Wo, Ho), BICUBIC) -- the resize of mmedit's
  * RandomDownSampling (mmcv.imresize, backend 'pillow').  src[y * pitch + 3 x + c] (bytes), the top-left H x W of a possibly wider

@@ -1,14 +1,18 @@
 #!/usr/bin/env python
-"""Render one image at several scales (or one window of each) from ONE encode:
+"""Render one image at several scales (or one window of each), and rotated / panned / zoomed views of it, from ONE encode:
 
     python tools/render.py CONFIG CHECKPOINT IMAGE --scale S [S ...] [--window I0 J0 H W] [--precision P] --out DIR
+    python tools/render.py CONFIG CHECKPOINT IMAGE [--scale ...] --view CY CX ZOOM ANGLE --size H W [--view ... --size ...] --out DIR
 
 Config and checkpoint as for tools/test.py.  The trunk, cs_attn and the head's per-image tables run once (CiaoSR.encode); every
 scale is a CiaoSR.render from the kept scenes and is written to DIR/<image name>_x<S>.png, the image `restore` gives for that
 target under the same test_cfg.  The configs tile integer scales only (`clip_test`), so this tool turns on
 `test_cfg.tile_any_scale` where the config sets `tile`: an image no larger than the tile is then the whole-image path, a larger
 one is tiled by tile_plan.  `--window` is in HR pixels of each scale's own grid; `--max-scale` sizes the scenes' plan (default: the
-largest --scale).
+largest --scale; without --scale the largest view ZOOM).  Every `--view` (repeatable; alone or alongside --scale) is a CiaoSR.render_view of
+ciaosr_amd.scene.view_matrix((CY, CX), ZOOM, ANGLE, (H, W)): an H x W picture whose centre looks at LR position (CY, CX) with ZOOM output
+pixels per LR pixel, turned by ANGLE degrees (positive: the picture turns clockwise), written to DIR/<image name>_view<k>.png, k = 0,
+1, ... in command-line order; one `--size` per `--view`, or a single one for all of them.  Pixels outside the image are black.
 """
 import argparse
 import os
@@ -25,12 +29,22 @@ def parse_args(argv=None):
     p.add_argument('config', help='test config file path')
     p.add_argument('checkpoint', help='checkpoint file ("None" = cfg.test_checkpoint_path)')
     p.add_argument('image', help='LR image file')
-    p.add_argument('--scale', type=float, nargs='+', required=True, help='one output per scale: round(h * s) x round(w * s)')
+    p.add_argument('--scale', type=float, nargs='+', default=[], help='one output per scale: round(h * s) x round(w * s)')
+    p.add_argument('--view', type=float, nargs=4, action='append', default=[], metavar=('CY', 'CX', 'ZOOM', 'ANGLE'),
+                   help='one output per view: centre in LR pixels, output pixels per LR pixel, degrees (repeatable)')
+    p.add_argument('--size', type=int, nargs=2, action='append', default=[], metavar=('H', 'W'), help='output size of each --view')
     p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
-    p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale)')
+    p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM)')
     p.add_argument('--out', required=True, help='output directory')
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not args.scale and not args.view:
+        p.error('give --scale, --view or both')
+    if args.view and len(args.size) not in (1, len(args.view)):
+        p.error('give one --size H W per --view, or a single one for all views')
+    if args.size and not args.view:
+        p.error('--size belongs to --view')
+    return args
 
 
 def scale_tag(s):
@@ -59,12 +73,19 @@ def main(argv=None):
     model = model.to(dev).eval()
 
     lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
-    enc = model.encode(lq, max_scale=args.max_scale or max(args.scale))
+    enc = model.encode(lq, max_scale=args.max_scale or max(args.scale or [v[2] for v in args.view]))
     name = os.path.splitext(os.path.basename(args.image))[0]
     paths = []
     for s in args.scale:
         out = model.render(enc, scale=s, window=args.window)
         paths.append(os.path.join(args.out, f'{name}_x{scale_tag(s)}.png'))
+        imwrite(metrics.tensor2img(out), paths[-1])
+        print(f'{paths[-1]}: {out.shape[-2]} x {out.shape[-1]}')
+    from ciaosr_amd.scene import view_matrix
+    for k, (cy, cx, zoom, angle) in enumerate(args.view):
+        size = args.size[k if len(args.size) > 1 else 0]
+        out = model.render_view(enc, view_matrix((cy, cx), zoom, angle, size), size)
+        paths.append(os.path.join(args.out, f'{name}_view{k}.png'))
         imwrite(metrics.tensor2img(out), paths[-1])
         print(f'{paths[-1]}: {out.shape[-2]} x {out.shape[-1]}')
     return paths

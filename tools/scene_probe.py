@@ -5,7 +5,14 @@ Per size and precision, after two warm-up passes of every call: `--reps` rounds 
 restore x2, render x2, ..., encode), each call between two device synchronisations.  Reported per call: mean, min and max in ms; per
 scale the ratio render / restore of the means and of the minima.  `restore` is the path of every earlier version; a full-grid render
 from a ready scene runs a strict subset of its launches (no trunk, cs_attn or tables), so it must not come out slower beyond the
-min-max spread shown.  Also: the scene's bytes and the peak allocated memory of a render-only loop against a restore-only loop."""
+min-max spread shown.  Also: the scene's bytes and the peak allocated memory of a render-only loop against a restore-only loop.
+
+`--legs view` (profiles/view_render.txt) instead times CiaoSR.render_view on the first of `--sizes` (the C3 tile: one 192 x 192 LR image,
+whole-image test_cfg, scene planned for x4), per precision, three legs alternating in one process, each call between two device
+synchronisations: an angle-0 view and a 30-degree view of `--view-size` (768) squared about the image centre at zoom x4, and the window
+render of that size from the same scene.  Per leg: wall time (mean, min, max over `--reps` rounds after two warm-up rounds, profiler
+off), and from one more round under hip_ops.profile the device time of the view kernels (count + select + blend + finalize), of the
+coordinate kernels and of the head query (every other launch of the call but denorm_clamp)."""
 import argparse
 import os
 import sys
@@ -24,6 +31,8 @@ ap.add_argument('--sizes', default='192,48')
 ap.add_argument('--precisions', default='fp32,f16')
 ap.add_argument('--scales', default='4,2,3.3')
 ap.add_argument('--reps', type=int, default=5)
+ap.add_argument('--legs', default='scene', choices=('scene', 'view'))
+ap.add_argument('--view-size', type=int, default=768)
 args = ap.parse_args()
 
 dev = torch.device('cuda:0')
@@ -55,8 +64,47 @@ def peak_of(fn, n=2):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
+def view_legs():
+    from ciaosr_amd.scene import view_matrix
+    size, n = int(args.sizes.split(',')[0]), args.view_size
+    lq = synthetic_pair(size, size, 4)[0].to(dev)
+    groups = (('view kernels', lambda k: k.startswith('view_') and k != 'view_coord_cell'),
+              ('coordinates', lambda k: k in ('view_coord_cell', 'make_coord_cell_window', 'make_coord_cell')),
+              ('head query', lambda k: not k.startswith(('view_', 'make_coord_cell')) and k != 'denorm_clamp'))
+    for precision in args.precisions.split(','):
+        model.test_cfg = dict(scale=4, precision=precision)
+        enc = model.encode(lq)
+        off = (size * 4 - n) // 2
+        calls = {'view   0 deg': lambda: model.render_view(enc, view_matrix((size / 2, size / 2), 4.0, 0, (n, n)), (n, n)),
+                 'view  30 deg': lambda: model.render_view(enc, view_matrix((size / 2, size / 2), 4.0, 30, (n, n)), (n, n)),
+                 'window render': lambda: model.render(enc, size=(size * 4, size * 4), window=(off, off, n, n))}
+        a, b = calls['view   0 deg'](), calls['window render']()
+        print(f'\n{size}x{size} LR, {precision}, {n} x {n} output at x4: angle-0 view against the window render: max |diff| = '
+              f'{(a - b).abs().max().item():.3e}; 30-degree view: {(calls["view  30 deg"]().sum(1) == 0).float().mean().item():.1%} of the pixels outside')
+        for _ in range(2):
+            for fn in calls.values():
+                fn()
+        times = {k: [] for k in calls}
+        for _ in range(args.reps):
+            for k, fn in calls.items():
+                times[k].append(timed(fn)[0])
+        for k, fn in calls.items():
+            with hip_ops.profile():
+                fn()
+            prof = hip_ops.profile.results()
+            v = times[k]
+            parts = ', '.join(f'{name} {sum(r["total_ms"] for kk, r in prof.items() if pick(kk)):8.3f} ms '
+                              f'({sum(r["launches"] for kk, r in prof.items() if pick(kk))} launches)' for name, pick in groups)
+            print(f'    {k:14s} wall mean {sum(v) / len(v):8.3f} ms  min {min(v):8.3f}  max {max(v):8.3f} | device: {parts}')
+        del enc, calls
+        hip_ops.release_workspaces()
+        torch.cuda.empty_cache()
+
+
 scales = [float(s) for s in args.scales.split(',')]
-for size in (int(v) for v in args.sizes.split(',')):
+if args.legs == 'view':
+    view_legs()
+for size in (int(v) for v in args.sizes.split(',') if args.legs == 'scene'):
     lq = synthetic_pair(size, size, 4)[0].to(dev)
     for precision in args.precisions.split(','):
         model.test_cfg = dict(scale=4, precision=precision)
