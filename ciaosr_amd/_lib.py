@@ -183,6 +183,10 @@ SIGNATURES = {
     'ciaosr_view_workspace_bytes': (_S, [_I, _I, _I]),
     'ciaosr_view_coord_cell_f32': (_I, [_P, _P, C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _P]),
     'ciaosr_view_count_i32': (_I, [C.POINTER(C.c_double), _I, _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_view_count_many_max_views': (_I, []),
+    'ciaosr_view_many_workspace_bytes': (_S, [C.POINTER(_I), _I, _I]),
+    'ciaosr_view_many_workspace_offset': (_S, [C.POINTER(_I), _I, _I, _I]),
+    'ciaosr_view_count_many_i32': (_I, [C.POINTER(C.c_double), C.POINTER(_I), _I, _P, _I, _P, _P, _S, _P]),
     'ciaosr_view_select_f32': (_I, [C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P, _P]),
     'ciaosr_view_blend_f32': (_I, [_P, _P, _I, _P, _P, _I, _P]),
     'ciaosr_view_finalize_f32': (_I, [_P, _P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P]),

@@ -38,12 +38,11 @@ __device__ __forceinline__ ViewFrame view_frame(int y0, int x0, int th, int tw) 
 }
 
 // part[t * n_blocks + b] = members of tile t among block b's queries.  Per tile one ballot per round and wave; lane 0 of each wave owns
-// its LDS slot, so nothing is added concurrently.
-__global__ __launch_bounds__(kViewThreads) void view_count_kernel(ViewP p, const int* __restrict__ tiles, int n_tiles, int n_blocks,
-                                                                  int* __restrict__ part) {
-    __shared__ int s_cnt[kViewTileBatch][kViewWaves];
+// its LDS slot, so nothing is added concurrently.  `block` is the block's number within ITS view (blockIdx.x for a single view).
+__device__ __forceinline__ void view_count_block(const ViewP& p, const int* __restrict__ tiles, int n_tiles, int n_blocks, int block,
+                                                 int* __restrict__ part, int (*s_cnt)[kViewWaves]) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const long q0 = (long)blockIdx.x * kViewChunk + tid;
+    const long q0 = (long)block * kViewChunk + tid;
     double y[kViewRounds], x[kViewRounds];
     bool live[kViewRounds];
 #pragma unroll
@@ -68,15 +67,20 @@ __global__ __launch_bounds__(kViewThreads) void view_count_kernel(ViewP p, const
             int c = 0;
 #pragma unroll
             for (int w = 0; w < kViewWaves; ++w) c += s_cnt[t][w];
-            part[(size_t)(t0 + t) * n_blocks + blockIdx.x] = c;
+            part[(size_t)(t0 + t) * n_blocks + block] = c;
         }
         __syncthreads();
     }
 }
 
-// One wave per tile: part[t][*] becomes its exclusive scan over the blocks, counts[t] the total
-__global__ __launch_bounds__(kWave) void view_scan_kernel(int* __restrict__ part, int n_blocks, int* __restrict__ counts) {
-    int* row = part + (size_t)blockIdx.x * n_blocks;
+__global__ __launch_bounds__(kViewThreads) void view_count_kernel(ViewP p, const int* __restrict__ tiles, int n_tiles, int n_blocks,
+                                                                  int* __restrict__ part) {
+    __shared__ int s_cnt[kViewTileBatch][kViewWaves];
+    view_count_block(p, tiles, n_tiles, n_blocks, (int)blockIdx.x, part, s_cnt);
+}
+
+// One wave: row[*] (a tile's per-block counts) becomes its exclusive scan over the blocks, *total their sum
+__device__ __forceinline__ void view_scan_row(int* __restrict__ row, int n_blocks, int* __restrict__ total) {
     const int lane = threadIdx.x;
     int carry = 0;
     for (int b0 = 0; b0 < n_blocks; b0 += kWave) {
@@ -91,7 +95,40 @@ __global__ __launch_bounds__(kWave) void view_scan_kernel(int* __restrict__ part
         if (b < n_blocks) row[b] = carry + incl - v;
         carry += __shfl(incl, kWave - 1, kWave);
     }
-    if (lane == 0) counts[blockIdx.x] = carry;
+    if (lane == 0) *total = carry;
+}
+
+// One wave per tile: part[t][*] becomes its exclusive scan over the blocks, counts[t] the total
+__global__ __launch_bounds__(kWave) void view_scan_kernel(int* __restrict__ part, int n_blocks, int* __restrict__ counts) {
+    view_scan_row(part + (size_t)blockIdx.x * n_blocks, n_blocks, counts + blockIdx.x);
+}
+
+// ---- the members of several views in one launch pair --------------------------------------------------------------------------------
+// Up to kViewMany views travel BY VALUE as kernel arguments (no staging copy): their parameters, the prefix table first[] over their
+// workgroup counts (workgroup b of the launch is workgroup b - first[v] of the view v with first[v] <= b < first[v + 1]) and the offset
+// of each view's part array in the workspace, in ints.  Every view's part array and counts are what the single-view kernels write.
+constexpr int kViewMany = 32;             // 32 x 64 + 33 x 4 + 32 x 8 + 8 bytes of arguments: well inside the 4 KiB kernel-argument limit
+struct ViewManyP {
+    ViewP p[kViewMany];
+    int first[kViewMany + 1];
+    int n_views;
+    unsigned long part[kViewMany];
+};
+
+__global__ __launch_bounds__(kViewThreads) void view_count_many_kernel(ViewManyP a, const int* __restrict__ tiles, int n_tiles,
+                                                                       int* __restrict__ ws) {
+    __shared__ int s_cnt[kViewTileBatch][kViewWaves];
+    const int b = (int)blockIdx.x;
+    int v = 0;                                   // uniform over the workgroup: a scalar search of the prefix table
+    while (v + 1 < a.n_views && b >= a.first[v + 1]) ++v;
+    view_count_block(a.p[v], tiles, n_tiles, a.first[v + 1] - a.first[v], b - a.first[v], ws + a.part[v], s_cnt);
+}
+
+// One wave per (view, tile): workgroup v * n_tiles + t
+__global__ __launch_bounds__(kWave) void view_scan_many_kernel(ViewManyP a, int n_tiles, int* __restrict__ ws, int* __restrict__ counts) {
+    const int v = (int)blockIdx.x / n_tiles, t = (int)blockIdx.x - v * n_tiles;
+    const int n_blocks = a.first[v + 1] - a.first[v];
+    view_scan_row(ws + a.part[v] + (size_t)t * n_blocks, n_blocks, counts + blockIdx.x);
 }
 
 // The members of one tile in increasing q: position = offs[block] + members of the block before this one
@@ -244,6 +281,60 @@ extern "C" int ciaosr_view_count_i32(const double* m, int Hv, int Wv, const int*
                        (int*)workspace);
     hipLaunchKernelGGL(view_scan_kernel, dim3(n_tiles), dim3(kWave), 0, (hipStream_t)stream, (int*)workspace, n_blocks, counts);
     return launch_status("view_count");
+}
+
+extern "C" int ciaosr_view_count_many_max_views(void) { return kViewMany; }
+
+static inline size_t view_many_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// bytes in front of view `upto` (upto = n_views: the whole workspace); 0 for a list the count refuses
+static size_t view_many_offset(const int* sizes, int n_views, int n_tiles, int upto) {
+    if (!sizes || n_views <= 0 || n_tiles <= 0 || upto < 0 || upto > n_views) return 0;
+    size_t off = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t one = ciaosr_view_workspace_bytes(sizes[2 * v], sizes[2 * v + 1], n_tiles);
+        if (!one) return 0;
+        if (v == upto) break;
+        off += view_many_align(one);
+    }
+    return off;
+}
+
+extern "C" size_t ciaosr_view_many_workspace_bytes(const int* sizes, int n_views, int n_tiles) {
+    return view_many_offset(sizes, n_views, n_tiles, n_views);
+}
+
+extern "C" size_t ciaosr_view_many_workspace_offset(const int* sizes, int n_views, int n_tiles, int view) {
+    if (view < 0 || view >= n_views) return 0;
+    return view_many_offset(sizes, n_views, n_tiles, view);
+}
+
+extern "C" int ciaosr_view_count_many_i32(const double* m, const int* sizes, int n_views, const int* tiles, int n_tiles, int* counts,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(m && sizes && n_views > 0 && tiles && n_tiles > 0 && counts && workspace && aligned16(tiles));
+    CIAOSR_CHECK_ARG(((size_t)workspace & 3) == 0 && (long)n_views * n_tiles <= (long)INT_MAX);
+    for (int v = 0; v < n_views; ++v) CIAOSR_CHECK_ARG(view_ok(m + 6 * v, sizes[2 * v], sizes[2 * v + 1]));
+    const size_t need = ciaosr_view_many_workspace_bytes(sizes, n_views, n_tiles);
+    if (!need || workspace_bytes < need) return CIAOSR_ERR_WORKSPACE;
+    ProfScope prof("view_count_many", (hipStream_t)stream);
+    size_t off = 0;                              // bytes, of the whole list: a later group continues where the one before ended
+    for (int v0 = 0; v0 < n_views; v0 += kViewMany) {
+        ViewManyP a = {};
+        a.n_views = n_views - v0 < kViewMany ? n_views - v0 : kViewMany;
+        for (int k = 0; k < a.n_views; ++k) {
+            const int v = v0 + k;
+            a.p[k] = view_p(m + 6 * v, sizes[2 * v], sizes[2 * v + 1]);
+            a.first[k + 1] = a.first[k] + view_blocks(a.p[k].Q);
+            a.part[k] = off / sizeof(int);
+            off += view_many_align(ciaosr_view_workspace_bytes(sizes[2 * v], sizes[2 * v + 1], n_tiles));
+        }
+        for (int k = a.n_views; k < kViewMany; ++k) a.first[k + 1] = a.first[a.n_views];
+        hipLaunchKernelGGL(view_count_many_kernel, dim3(a.first[a.n_views]), dim3(kViewThreads), 0, (hipStream_t)stream, a, tiles, n_tiles,
+                           (int*)workspace);
+        hipLaunchKernelGGL(view_scan_many_kernel, dim3(a.n_views * n_tiles), dim3(kWave), 0, (hipStream_t)stream, a, n_tiles,
+                           (int*)workspace, counts + (size_t)v0 * n_tiles);
+    }
+    return launch_status("view_count_many");
 }
 
 extern "C" int ciaosr_view_select_f32(const double* m, int Hv, int Wv, const int* tile, int tile_index, int n_tiles, const void* workspace,

@@ -277,6 +277,25 @@ def view_count(m, hv, wv, tiles):
     return counts, ws
 
 
+def view_count_many(ms, sizes, tiles):
+    """`view_count` for a list of views in one go: ms V x 6 numbers, sizes V x (hv, wv), tiles as there -> (counts [V, n_tiles] int32 on
+    the device, ws, offsets).  `ws[offsets[v]:]` is view v's workspace for `view_select`; counts[v] and that workspace are bitwise what
+    `view_count` gives for the view alone.  One launch pair per `ciaosr_view_count_many_max_views()` views, nothing synchronises."""
+    require_gpu(tiles)
+    n_tiles, n_views = tiles.shape[0], len(ms)
+    if n_views < 1 or len(sizes) != n_views:
+        raise ValueError(f'view_count_many: {n_views} matrices, {len(sizes)} sizes')
+    lib = _lib.load()
+    flat = [v for m in ms for v in _m6(m)]
+    m_arr = (C.c_double * (6 * n_views))(*flat)
+    s_arr = (C.c_int * (2 * n_views))(*[int(v) for s in sizes for v in (s[0], s[1])])
+    ws = workspace(lib.ciaosr_view_many_workspace_bytes(s_arr, n_views, n_tiles), tiles.device, slot='view_many')
+    offsets = [lib.ciaosr_view_many_workspace_offset(s_arr, n_views, n_tiles, v) for v in range(n_views)]
+    counts = torch.empty(n_views, n_tiles, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_view_count_many_i32', m_arr, s_arr, n_views, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws, offsets
+
+
 def view_select(m, hv, wv, frame, index, n_tiles, ws, n):
     """The `n` members (view_count's number) of tile `index` = `frame`, in increasing query index: (q_index [n] int32, coord [n, 2],
     cell [n, 2] in the tile's frame).  No grid hint is registered: the head sees a caller's own list of coordinates."""

@@ -103,19 +103,31 @@ class LocalImplicitSRNet(nn.Module):
     def encode(self, x, options=None, q_plan=None):
         """The part of `forward` that depends on the LR batch only, once: trunk, then per item the head's per-image stages into a Scene
         (head_hip.PackedHead.prepare).  `q_plan`: the query count of the largest full render intended (default: the x4 grid).  An
-        extension, absent from the reference."""
+        extension, absent from the reference.  The two halves are callable on their own: `encode_trunk`, `encode_scenes`."""
+        x, feats, options = self.encode_trunk(x, options)
+        return self.encode_scenes(x, feats, options, q_plan)
+
+    @torch.no_grad()
+    def encode_trunk(self, x, options=None):
+        """The trunk half of `encode`: -> (x as the trunk read it, channels-last feature maps feats[b], the effective Options).  The
+        items of a batch share the trunk's launches where the trunk has a `forward_hwc_batch`; item b is bitwise the batch-1 call."""
         options = self.effective_options(options)
         enc = getattr(self, '_encoder_hip', None)
         if enc is None:
             raise CiaoSRHipError('encode needs a generator with a HIP trunk')
         self._require_hip_trunk(x)
         x = x.contiguous().float()
-        if q_plan is None:
-            q_plan = 16 * x.shape[-2] * x.shape[-1]
         if hasattr(enc, 'forward_hwc_batch'):
             feats = enc.forward_hwc_batch(x, options)
         else:
             feats = [enc.forward_hwc(x[b], options) for b in range(x.shape[0])]
+        return x, feats, options
+
+    @torch.no_grad()
+    def encode_scenes(self, x, feats, options, q_plan=None):
+        """The prepare half of `encode`: one Scene per item of `x` from its feature map (`encode_trunk`'s results, or slices of them)."""
+        if q_plan is None:
+            q_plan = 16 * x.shape[-2] * x.shape[-1]
         return EncodedFeatures([self._head.prepare(None, options, q_plan, feature_hwc=feats[b]) for b in range(x.shape[0])], x, options)
 
     @torch.no_grad()

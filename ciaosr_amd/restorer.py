@@ -405,7 +405,7 @@ class CiaoSR(BasicRestorer):
             ph, pw = patch.shape[-2:]
             return gen.encode(patch, opt, q_plan=max(1, round(ph * enc.max_scale) * round(pw * enc.max_scale)))
 
-        enc = EncodedImage(x, opt, max_scale, int(self.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build)
+        enc = EncodedImage(x, opt, max_scale, int(self.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build, tile=t)
         if not tile and max_scale is not None:
             for b in range(x.shape[0]):
                 enc.cache.get((b, None))
@@ -460,16 +460,9 @@ class CiaoSR(BasicRestorer):
         from . import scene as sc
         x = enc.x
         nb, _, h, w = x.shape
-        hv, wv = int(size[0]), int(size[1])
-        if hv < 1 or wv < 1:
-            raise ValueError(f'empty view grid {hv} x {wv}')
-        m = tuple(float(v) for v in matrix)
         tile = self.test_cfg.get('tile', None)
-        frames = sc.plan_view(h, w, tile, self.test_cfg.get('tile_overlap', None), bool(self.test_cfg.get('tile_any_scale', False)))
-        sc.view_cell(m, frames[0][2], frames[0][3])                      # ValueError: singular, or a cell >= 1
-        fill = tuple(float(v) for v in fill) if hasattr(fill, '__len__') else (float(fill),) * 3
-        if len(fill) != 3 or not all(0.0 <= v <= 1.0 for v in fill):
-            raise ValueError(f'fill is one number or three in [0, 1], got {fill}')
+        m, (hv, wv), fill, frames = sc.check_view(matrix, size, fill, h, w, tile, self.test_cfg.get('tile_overlap', None),
+                                                  bool(self.test_cfg.get('tile_any_scale', False)))
         if enc.max_scale is None:
             enc.max_scale = sc.view_max_scale(m)
         if enc.view_tiles is None:                                      # uploaded once per encoded image, not per view
@@ -498,6 +491,229 @@ class CiaoSR(BasicRestorer):
             from . import metrics_hip
             return metrics_hip.tensor2img_u8(out)
         return out
+
+    # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------
+    def _plan_many(self, enc, targets, count_views=True):
+        """Everything `render_many` / `prefetch` know before a scene is touched.  Validates every target (the single calls' ValueErrors,
+        before any device work), sets `enc.max_scale` where it is open, counts the members of ALL views in one `view_count_many` and
+        one device-to-host copy (none for grids alone) -- per call, not per batch item: the counts do not depend on the item.
+        -> dict: recs (per target), origins {tile index: (y0, x0) | None}, union, users, frames, ws, offsets."""
+        from . import scene as sc
+        x = enc.x
+        h, w = x.shape[-2:]
+        cfg = self.test_cfg
+        tile, overlap, any_scale = cfg.get('tile', None), cfg.get('tile_overlap', None), bool(cfg.get('tile_any_scale', False))
+        targets = list(targets)
+        if not targets:
+            raise ValueError('no targets: give a list of scene.Grid / scene.View')
+        recs, frames, need = [], None, 0.0
+        for tg in targets:
+            if isinstance(tg, sc.Grid):
+                ht, wt, win = tg.resolve(h, w)
+                tiles = None
+                if tile:
+                    tiles = sc.plan_window(h, w, tile, overlap, ht, wt, win, scale=cfg.get('scale', None), any_scale=any_scale)
+                recs.append(dict(kind='grid', ht=ht, wt=wt, win=win, tiles=tiles, size=(win[2], win[3])))
+                need = max(need, ht / h, wt / w)
+            elif isinstance(tg, sc.View):
+                m, size, fill, frames = tg.resolve(h, w, tile, overlap, any_scale)
+                recs.append(dict(kind='view', m=m, size=size, fill=fill))
+                need = max(need, sc.view_max_scale(m))
+            else:
+                raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
+        if enc.max_scale is None:
+            enc.max_scale = need
+        plan = dict(recs=recs, frames=frames, ws=None, offsets=None, origins={})
+        views = [r for r in recs if r['kind'] == 'view']
+        if views and not count_views:                                   # one frame: every view is its only user
+            for r in views:
+                r['counts'] = [1]
+            plan['origins'][0] = (0, 0) if tile else None
+        elif views:
+            if enc.view_tiles is None:                                  # uploaded once per encoded image
+                enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
+            counts, plan['ws'], plan['offsets'] = hip_ops.view_count_many([r['m'] for r in views], [r['size'] for r in views], enc.view_tiles)
+            counts = counts.tolist()                                    # the one synchronisation of the call
+            for v, r in enumerate(views):
+                r['v'], r['counts'] = v, counts[v]
+            plan['origins'].update({k: ((f[0], f[1]) if tile else None) for k, f in enumerate(frames)})
+        touched = []
+        for r in recs:
+            if r['kind'] == 'view':
+                touched.append([k for k, n in enumerate(r['counts']) if n])
+            elif r['tiles'] is None:
+                touched.append([0])
+                plan['origins'][0] = None
+            else:
+                r['by_index'] = {t['index']: t for t in r['tiles']}
+                touched.append(sorted(r['by_index']))
+                plan['origins'].update({t['index']: (t['y0'], t['x0']) for t in r['tiles']})
+        plan['union'], plan['users'] = sc.plan_union(touched)
+        return plan
+
+    def _scene_walk(self, enc, b, tiles, n_group, ahead):
+        """Yield (tile index, scene) for `tiles` (index -> origin in `origins`, given as a list of (index, origin)) of batch item b, in
+        order, each scene taken from the cache once.  The tiles missing from the cache are encoded in groups of `n_group`: one trunk call
+        per group (`encode_trunk` on the stacked patches), with `ahead` the next group's on the cached side stream under the current
+        group's prepares and queries (events, wait_stream and record_stream as `_clip_test_encoder_ahead`).  A scene is prepared from
+        its feature map right before it is yielded; only a group's feature maps are held, never its scenes."""
+        from . import scene as sc
+        gen, cache, x, t = self.generator, enc.cache, enc.x, enc.tile
+        opt = enc.options
+        origin_of = dict(tiles)
+        order = [k for k, _ in tiles]
+        key_of = {k: (b, origin_of[k]) for k in order}
+        groups = sc.group_missing(order, {k for k in order if key_of[k] in cache.entries}, n_group)
+        ahead = bool(ahead and len(groups) > 1 and x.is_cuda and trunk_batches(gen, opt))
+        if ahead:
+            cur = torch.cuda.current_stream(x.device)
+            self.prepare(opt)                                           # nothing the side stream reads is first packed there
+            side = self._tile_streams(1, x.device)[0]
+            side.wait_stream(cur)
+
+        def patch_of(k):
+            o = origin_of[k]
+            return x[b:b + 1] if o is None else x[b:b + 1, :, o[0]:o[0] + t, o[1]:o[1] + t]
+
+        def trunk(group):
+            if not ahead:
+                patches, feats, eff = gen.encode_trunk(torch.cat([patch_of(k) for k in group], 0).contiguous(), opt)
+                return patches, feats, eff, None
+            with torch.cuda.stream(side):
+                patches, feats, eff = gen.encode_trunk(torch.cat([patch_of(k) for k in group], 0).contiguous(), opt)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return patches, feats, eff, ev
+
+        where = {k: (g, j) for g, group in enumerate(groups) for j, k in enumerate(group)}
+        ready, g_next, nxt = {}, 0, None          # ready: the group in use -> (patches, feats, eff)
+        cache.hold = set(key_of.values())
+        try:
+            for k in order:
+                key = key_of[k]
+                cache.hold.discard(key)
+                if k not in where or key in cache.entries:
+                    yield k, cache.get(key)       # cached (a held entry the budget pushed out all the same is rebuilt on its own)
+                    continue
+                g, j = where[k]
+                if g not in ready:
+                    ready.clear()                 # the group before is done: its feature maps go
+                    if nxt is None:
+                        nxt = trunk(groups[g])
+                    patches, feats, eff, ev = nxt
+                    nxt, g_next = None, g + 1
+                    if ahead and g_next < len(groups):
+                        nxt = trunk(groups[g_next])          # queued behind group g's trunk, runs under group g's prepares and queries
+                    if ev is not None:
+                        cur.wait_event(ev)
+                        patches.record_stream(cur)
+                        for f in ([feats] if torch.is_tensor(feats) else feats):
+                            f.record_stream(cur)
+                    ready[g] = (patches, feats, eff)
+                patches, feats, eff = ready[g]
+                ph, pw = patches.shape[-2:]
+                cache.make_room()
+                scene = gen.encode_scenes(patches[j:j + 1], [feats[j]], eff,
+                                          q_plan=max(1, round(ph * enc.max_scale) * round(pw * enc.max_scale)))
+                yield k, cache.put(key, scene)
+        finally:
+            cache.hold = set()
+            if ahead:
+                cur.wait_stream(side)
+
+    def _group_size(self, enc):
+        """Tiles per trunk call of the scene builder: `tile_batch()` where the tile loops feed this trunk batches, else 1."""
+        return self.tile_batch(enc.options) if (enc.tile and trunk_batches(self.generator, enc.options)) else 1
+
+    @torch.no_grad()
+    def render_many(self, enc, targets, as_u8=False):
+        """Every target of the list -- scene.Grid(size, scale, window): `render`'s arguments, scene.View(matrix, size, fill):
+        `render_view`'s -- from ONE walk over the tile scenes: -> list of [B, 3, h, w], outs[k] bitwise what the single call returns on an
+        encode with the same max_scale under the same test_cfg (with `as_u8` the same uint8 image).  Per batch item the union of the
+        tiles the targets touch is walked in row-major order; each tile's scene is taken from the cache once and every target that
+        touches it is queried from it, in list order, into the target's own accumulators -- so each target sees its tiles in the
+        reference's blend order.  Coordinates are made right before the query that reads them, as `render` makes them (the 16-bit
+        head's grid-width hint is kept for the last 64 coordinate tensors only).  A call builds exactly the scenes of the union that the
+        cache lacks, under any budget that holds one scene (cached scenes the walk still needs are evicted last), from trunk features
+        made `tile_batch()` tiles per trunk call where the trunk batches tiles, with `test_cfg.encoder_ahead` (default on) the next
+        group's trunk on the cached side stream under the current group's heads.  All views are counted in one `view_count_many` and
+        one device-to-host copy per call (none for grids alone).  An image that is one frame (no `test_cfg.tile`, or an image no larger
+        than the tile) has no schedule to make: its targets are the single calls, in list order."""
+        x = enc.x
+        nb = x.shape[0]
+        gen = self.generator
+        one_frame = not enc.tile or tuple(x.shape[-2:]) == (enc.tile, enc.tile)
+        plan = self._plan_many(enc, targets, count_views=not one_frame)
+        recs = plan['recs']
+        if one_frame:
+            return [self.render(enc, size=(r['ht'], r['wt']), window=r['win'], as_u8=as_u8) if r['kind'] == 'grid' else
+                    self.render_view(enc, r['m'], r['size'], r['fill'], as_u8=as_u8) for r in recs]
+        frames, ws, offsets = plan['frames'], plan['ws'], plan['offsets']
+        walk = [(k, plan['origins'][k]) for k in plan['union']]
+        preds = [[] for _ in recs]
+        for b in range(nb):
+            acc = []
+            for r in recs:
+                hh, ww = r['size']
+                if r['kind'] == 'grid':
+                    E = torch.zeros(3, hh, ww, dtype=torch.float32, device=x.device)
+                    acc.append((E, torch.zeros_like(E)))
+                else:
+                    acc.append((torch.zeros(3, hh * ww, dtype=torch.float32, device=x.device),
+                                torch.zeros(hh * ww, dtype=torch.float32, device=x.device)))
+            for k, tile_scene in self._scene_walk(enc, b, walk, self._group_size(enc), self.test_cfg.get('encoder_ahead', True)):
+                for i in plan['users'][k]:
+                    r = recs[i]
+                    E, Wt = acc[i]
+                    if r['kind'] == 'grid':
+                        t = r['by_index'][k]
+                        wi0, wj0 = r['win'][:2]
+                        gh, gw, r0, r1, c0, c1, frame = t['grid']
+                        coord, cell = hip_ops.make_coord_cell_window(gh, gw, r0, r1, c0, c1, x.device, frame)
+                        out = gen.render(tile_scene, coord, cell)[0]
+                        hip_ops.tile_blend(E, Wt, out, t['a0'] - wi0, t['b0'] - wj0, t['a1'] - t['a0'], t['b1'] - t['b0'])
+                    else:
+                        (hv, wv), m, n = r['size'], r['m'], r['counts'][k]
+                        if n == hv * wv:                                # the tile owns the whole view: a grid, known to the head as one
+                            q_index = None
+                            coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frames[k], x.device)
+                        else:
+                            q_index, coord, cell = hip_ops.view_select(m, hv, wv, frames[k], k, len(frames), ws[offsets[r['v']]:], n)
+                        hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
+            for i, r in enumerate(recs):
+                E, Wt = acc[i]
+                preds[i].append(hip_ops.tile_finalize(E, Wt) if r['kind'] == 'grid' else
+                                hip_ops.view_finalize(E, Wt, r['fill'], self.rgb_mean, self.rgb_std))
+        outs = []
+        for r, ps in zip(recs, preds):
+            hh, ww = r['size']
+            out = torch.stack([hip_ops.denorm_clamp(p.contiguous(), hh, ww, self.rgb_mean, self.rgb_std) for p in ps])
+            if as_u8:
+                from . import metrics_hip
+                out = metrics_hip.tensor2img_u8(out)
+            outs.append(out)
+        return outs
+
+    @torch.no_grad()
+    def prefetch(self, enc, targets):
+        """Build the scenes `render_many(enc, targets)` would touch and the cache lacks, rendering nothing: the same plan and the same
+        batched builder, row-major per batch item, stopping before a build would exceed `scene_cache_mb` -- nothing is evicted.
+        -> the number of scenes built."""
+        plan = self._plan_many(enc, targets)
+        cache = enc.cache
+        built = 0
+        for b in range(enc.x.shape[0]):
+            missing = [(k, plan['origins'][k]) for k in plan['union'] if (b, plan['origins'][k]) not in cache.entries]
+            if missing and cache.room() is None:                        # the size of a scene is not known yet: the first one tells
+                for _ in self._scene_walk(enc, b, missing[:1], 1, False):
+                    built += 1
+                missing = missing[1:]
+            missing = missing[:cache.room() or 0]
+            for _ in self._scene_walk(enc, b, missing, self._group_size(enc), self.test_cfg.get('encoder_ahead', True)):
+                built += 1
+            if cache.room() == 0:
+                break
+        return built
 
     def _restore(self, lq, coord=None, cell=None, options=None):
         x = self.normalize(lq)

@@ -2,7 +2,8 @@
 
 Pure Python, no GPU: the window planner (which LR tiles a window of the HR grid touches, and which part of each), the least-recently-used
 cache that bounds the bytes of tile scenes kept alive, the record `CiaoSR.encode` returns, and the affine views of
-`CiaoSR.render_view` (their matrices, cells and tile lists).  The device work is in `PackedHead.prepare` / `query` (head_hip.py),
+`CiaoSR.render_view` (their matrices, cells and tile lists), and for `CiaoSR.render_many` the target records `Grid` / `View` and
+the tile-major plan (`plan_union`, `group_missing`).  The device work is in `PackedHead.prepare` / `query` (head_hip.py),
 `hip_ops.make_coord_cell_window` and the `hip_ops.view_*` wrappers.
 """
 import ctypes
@@ -157,10 +158,81 @@ def plan_view(h, w, tile=None, overlap=None, any_scale=False):
     return [(y0, x0, tile, tile) for y0 in tile_plan.tile_starts(h, tile, overlap) for x0 in tile_plan.tile_starts(w, tile, overlap)]
 
 
+def check_view(matrix, size, fill, h, w, tile=None, overlap=None, any_scale=False):
+    """The arguments of a view render, checked in `CiaoSR.render_view`'s order: -> (m, (hv, wv), fill3, frames) with m six floats, fill3
+    three floats in [0, 1] and frames = `plan_view`'s list.  ValueError for an empty grid, tiles without `tile_any_scale`, a singular
+    matrix, a cell >= 1 and a fill outside [0, 1]."""
+    hv, wv = int(size[0]), int(size[1])
+    if hv < 1 or wv < 1:
+        raise ValueError(f'empty view grid {hv} x {wv}')
+    m = tuple(float(v) for v in matrix)
+    frames = plan_view(h, w, tile, overlap, any_scale)
+    view_cell(m, frames[0][2], frames[0][3])                      # ValueError: singular, or a cell >= 1
+    fill = tuple(float(v) for v in fill) if hasattr(fill, '__len__') else (float(fill),) * 3
+    if len(fill) != 3 or not all(0.0 <= v <= 1.0 for v in fill):
+        raise ValueError(f'fill is one number or three in [0, 1], got {fill}')
+    return m, (hv, wv), fill, frames
+
+
+# ---- many targets from one walk over the tiles (CiaoSR.render_many / prefetch) --------------------------------------------------------
+class Grid:
+    """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render`."""
+    __slots__ = ('size', 'scale', 'window')
+
+    def __init__(self, size=None, scale=None, window=None):
+        self.size, self.scale, self.window = size, scale, window
+
+    def resolve(self, h, w):
+        """(ht, wt, (i0, j0, hh, ww)) on an h x w image, with `render`'s ValueErrors."""
+        ht, wt = target_size(h, w, self.size, self.scale)
+        return ht, wt, check_window(ht, wt, self.window)
+
+    def __repr__(self):
+        return f'Grid(size={self.size!r}, scale={self.scale!r}, window={self.window!r})'
+
+
+class View:
+    """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render_view`."""
+    __slots__ = ('matrix', 'size', 'fill')
+
+    def __init__(self, matrix, size, fill=0.0):
+        self.matrix, self.size, self.fill = matrix, size, fill
+
+    def resolve(self, h, w, tile=None, overlap=None, any_scale=False):
+        """`check_view` of the record: (m, (hv, wv), fill3, frames), with `render_view`'s ValueErrors."""
+        return check_view(self.matrix, self.size, self.fill, h, w, tile, overlap, any_scale)
+
+    def __repr__(self):
+        return f'View({self.matrix!r}, size={self.size!r}, fill={self.fill!r})'
+
+
+def plan_union(touched):
+    """touched[k]: the tile indices target k touches.  -> (union, users): the union in ascending (row-major) index order, and per tile
+    of it the targets that touch it, in list order.  Walking the union and serving users[tile] shows every target its own tiles in
+    ascending order: the reference's blend order."""
+    users = {}
+    for k, tiles in enumerate(touched):
+        for t in tiles:
+            users.setdefault(int(t), [])
+            if k not in users[int(t)]:
+                users[int(t)].append(k)
+    union = sorted(users)
+    return union, {t: users[t] for t in union}
+
+
+def group_missing(union, cached, n):
+    """The tiles of `union` (in its order) that are not in `cached`, cut into groups of `n` consecutive missing tiles (the last group may
+    be shorter): what one trunk call encodes."""
+    n = max(1, int(n))
+    missing = [t for t in union if t not in cached]
+    return [missing[i:i + n] for i in range(0, len(missing), n)]
+
+
 class SceneCache:
     """Least-recently-used cache of built scenes under a byte budget.  `build(key)` returns an object with `.nbytes`.  The entry `get`
     returns is never evicted by that call, so the smallest budget still works, by rebuilding; `builds` counts every build, rebuilt
-    entries included."""
+    entries included.  A caller that builds entries itself (several tiles' trunks in one call) asks `make_room()` before each build and
+    hands the entry to `put`: the same rule.  `hold`: keys a walk in progress still needs -- evicted only when nothing else is left."""
 
     def __init__(self, budget_bytes, build):
         self.budget = int(budget_bytes)
@@ -168,28 +240,41 @@ class SceneCache:
         self.entries = OrderedDict()
         self.nbytes = 0
         self.builds = 0
+        self.hold = set()
         self._last = 0                  # bytes of the last build: what the next one is expected to take (tiles are equally sized)
 
     def _evict(self, room, keep=None):
-        for key in list(self.entries):
-            if self.nbytes + room <= self.budget:
-                break
-            if key != keep:
-                self.nbytes -= self.entries.pop(key).nbytes
+        for held in (False, True):       # least recently used first; the keys on hold only after every other entry
+            for key in list(self.entries):
+                if self.nbytes + room <= self.budget:
+                    return
+                if key != keep and (key in self.hold) == held:
+                    self.nbytes -= self.entries.pop(key).nbytes
 
     def get(self, key):
         hit = self.entries.get(key)
         if hit is not None:
             self.entries.move_to_end(key)
             return hit
-        self._evict(self._last)          # before the build, so that the peak stays at the budget
-        hit = self.build(key)
+        self.make_room()
+        return self.put(key, self.build(key))
+
+    def make_room(self):
+        """Before a build, so that the peak stays at the budget: evict for an entry of the last build's size."""
+        self._evict(self._last)
+
+    def put(self, key, entry):
+        """Take a freshly built entry: counted in `builds`, never evicted by this call."""
         self.builds += 1
-        self._last = hit.nbytes
-        self.entries[key] = hit
-        self.nbytes += hit.nbytes
+        self._last = entry.nbytes
+        self.entries[key] = entry
+        self.nbytes += entry.nbytes
         self._evict(0, keep=key)
-        return hit
+        return entry
+
+    def room(self):
+        """How many more entries of the last build's size fit without evicting; None before the first build."""
+        return max(0, (self.budget - self.nbytes) // self._last) if self._last else None
 
     def clear(self):
         self.entries.clear()
@@ -200,8 +285,9 @@ class EncodedImage:
     """What `CiaoSR.encode` returns: the normalised LR batch, the Options and max_scale its scenes are planned with, and the scenes -- the
     whole image's (no `test_cfg.tile`), or a SceneCache of one per (batch item, LR tile), built when a render first touches the tile."""
 
-    def __init__(self, x, options, max_scale, budget_bytes, build):
+    def __init__(self, x, options, max_scale, budget_bytes, build, tile=None):
         self.x = x
+        self.tile = tile                # side of the LR tiles the scenes are keyed by (b, (y0, x0)); None: one scene per item, (b, None)
         self.options = options
         self.max_scale = max_scale
         self.cache = SceneCache(budget_bytes, build)

@@ -636,6 +636,18 @@ int ciaosr_view_coord_cell_f32(float* coord, float* cell, const double* m /*host
  * their member counts -- what select places a tile's members with; valid until the next count on the same workspace. */
 int ciaosr_view_count_i32(const double* m /*host [6]*/, int Hv, int Wv, const int* tiles, int n_tiles, int* counts, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* count for a list of views in one go: m [n_views][6] and sizes [n_views][2] = (Hv, Wv) on the host, the tiles as above.  One count
+ * launch covers the workgroups of every view (the views travel by value as kernel arguments: no staging copy, nothing allocated), one
+ * scan launch follows with a wave per (view, tile); a list longer than ciaosr_view_count_many_max_views() is further launch pairs on the
+ * same stream, without synchronisation.  counts [n_views][n_tiles] (device).  The workspace holds every view's single-view part array
+ * (the ciaosr_view_workspace_bytes layout) at ciaosr_view_many_workspace_offset(view), a multiple of 256 bytes: counts[v] and the part
+ * array of view v are bitwise what ciaosr_view_count_i32 writes for that view alone, and ciaosr_view_select_f32 runs unchanged on
+ * workspace + offset(view).  Sizes are 0 for a list the count refuses. */
+int ciaosr_view_count_many_max_views(void);
+size_t ciaosr_view_many_workspace_bytes(const int* sizes /*host [n_views][2]*/, int n_views, int n_tiles);
+size_t ciaosr_view_many_workspace_offset(const int* sizes /*host [n_views][2]*/, int n_views, int n_tiles, int view);
+int ciaosr_view_count_many_i32(const double* m /*host [n_views][6]*/, const int* sizes /*host [n_views][2]*/, int n_views, const int* tiles,
+                               int n_tiles, int* counts, void* workspace, size_t workspace_bytes, void* stream);
 /* select: the members of tile `tile_index` of the list count saw (`tile`: its four ints, host), in increasing q: q_index [n], coord and
  * cell [n][2] in the tile's frame, n = counts[tile_index] (nothing is written past n). */
 int ciaosr_view_select_f32(const double* m /*host [6]*/, int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles,

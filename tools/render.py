@@ -5,8 +5,9 @@
     python tools/render.py CONFIG CHECKPOINT IMAGE [--scale ...] --view CY CX ZOOM ANGLE --size H W [--view ... --size ...] --out DIR
 
 Config and checkpoint as for tools/test.py.  The trunk, cs_attn and the head's per-image tables run once (CiaoSR.encode); every
-scale is a CiaoSR.render from the kept scenes and is written to DIR/<image name>_x<S>.png, the image `restore` gives for that
-target under the same test_cfg.  The configs tile integer scales only (`clip_test`), so this tool turns on
+scale and view is a target of ONE CiaoSR.render_many -- a single walk over the tile scenes, each built once however many outputs touch
+it -- and is bitwise the image CiaoSR.render / render_view give for it.  A scale is written to DIR/<image name>_x<S>.png, the image
+`restore` gives for that target under the same test_cfg.  The configs tile integer scales only (`clip_test`), so this tool turns on
 `test_cfg.tile_any_scale` where the config sets `tile`: an image no larger than the tile is then the whole-image path, a larger
 one is tiled by tile_plan.  `--window` is in HR pixels of each scale's own grid; `--max-scale` sizes the scenes' plan (default: the
 largest --scale; without --scale the largest view ZOOM).  Every `--view` (repeatable; alone or alongside --scale) is a CiaoSR.render_view of
@@ -75,19 +76,16 @@ def main(argv=None):
     lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
     enc = model.encode(lq, max_scale=args.max_scale or max(args.scale or [v[2] for v in args.view]))
     name = os.path.splitext(os.path.basename(args.image))[0]
-    paths = []
-    for s in args.scale:
-        out = model.render(enc, scale=s, window=args.window)
-        paths.append(os.path.join(args.out, f'{name}_x{scale_tag(s)}.png'))
-        imwrite(metrics.tensor2img(out), paths[-1])
-        print(f'{paths[-1]}: {out.shape[-2]} x {out.shape[-1]}')
-    from ciaosr_amd.scene import view_matrix
+    from ciaosr_amd.scene import Grid, View, view_matrix
+    targets = [Grid(scale=s, window=args.window) for s in args.scale]
+    paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}.png') for s in args.scale]
     for k, (cy, cx, zoom, angle) in enumerate(args.view):
         size = args.size[k if len(args.size) > 1 else 0]
-        out = model.render_view(enc, view_matrix((cy, cx), zoom, angle, size), size)
+        targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}.png'))
-        imwrite(metrics.tensor2img(out), paths[-1])
-        print(f'{paths[-1]}: {out.shape[-2]} x {out.shape[-1]}')
+    for path, out in zip(paths, model.render_many(enc, targets)):      # one walk over the tile scenes for every output
+        imwrite(metrics.tensor2img(out), path)
+        print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
     return paths
 
 

@@ -12,36 +12,54 @@ whole-image test_cfg, scene planned for x4), per precision, three legs alternati
 synchronisations: an angle-0 view and a 30-degree view of `--view-size` (768) squared about the image centre at zoom x4, and the window
 render of that size from the same scene.  Per leg: wall time (mean, min, max over `--reps` rounds after two warm-up rounds, profiler
 off), and from one more round under hip_ops.profile the device time of the view kernels (count + select + blend + finalize), of the
-coordinate kernels and of the head query (every other launch of the call but denorm_clamp)."""
+coordinate kernels and of the head query (every other launch of the call but denorm_clamp).
+
+`--legs many` (profiles/render_many.txt, with `--out`) is the tiled image of bench.py -- LR 1356 x 2040, tile 192 / overlap 32,
+`tile_any_scale`: 9 x 13 = 117 tiles -- rendered at x2, x3.3 and x4 (full grids) from one encode, per precision and for two scene caches
+(the default `scene_cache_mb`, and one that holds every scene):
+  (a) three `render` calls in a row with the PARENT commit's package and library: a child process of this job on `--parent-root DIR`
+      (a built checkout of the parent commit), kept alive and told when to run a round, so that its rounds alternate with (b) and (c)
+  (b) one `render_many` of the three targets (this tree)
+  (c) `restore` at x4 (this tree), for scale
+One warm-up round of every leg, then `--reps` rounds in which the legs alternate; every round starts from a fresh `encode`, is timed
+between two device synchronisations, and reports `cache.builds`.  Without `--parent-root`, leg (a) runs this tree's `render` in the
+same process.  A second table: 16 views of `--view-size` squared along a pan across the image at x4, as 16 `render_view` calls and as
+one `render_many`: wall time and the number of synchronising device-to-host copies (counted around Tensor.tolist)."""
 import argparse
+import json
 import os
+import subprocess
 import sys
 import time
-
-import torch
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ciaosr_amd  # noqa: E402
-from ciaosr_amd import _lib, hip_ops  # noqa: E402
-from ciaosr_amd.config import Config  # noqa: E402
-from ciaosr_amd.init_utils import seeded_init_, synthetic_pair  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--sizes', default='192,48')
 ap.add_argument('--precisions', default='fp32,f16')
 ap.add_argument('--scales', default='4,2,3.3')
 ap.add_argument('--reps', type=int, default=5)
-ap.add_argument('--legs', default='scene', choices=('scene', 'view'))
+ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many'))
 ap.add_argument('--view-size', type=int, default=768)
+ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help='tree whose package and library run')
+ap.add_argument('--parent-root', default=None, help='--legs many: a built checkout of the parent commit for leg (a)')
+ap.add_argument('--worker', action='store_true', help='--legs many: serve leg (a) rounds on stdin / stdout (the parent-tree child)')
+ap.add_argument('--out', default=None, help='--legs many: also write the report to this file')
 args = ap.parse_args()
 
+sys.path.insert(0, os.path.abspath(args.root))
+import torch  # noqa: E402
+import ciaosr_amd  # noqa: E402
+from ciaosr_amd import _lib, hip_ops  # noqa: E402
+from ciaosr_amd.config import Config  # noqa: E402
+from ciaosr_amd.init_utils import seeded_init_, synthetic_pair  # noqa: E402
+
 dev = torch.device('cuda:0')
-cfg = Config.fromfile(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'configs',
+cfg = Config.fromfile(os.path.join(os.path.abspath(args.root), 'configs',
                                    '001_localimplicitsr_rdn_div2k_g1_c64b16_1000k_unfold_lec_mulwkv_res_nonlocal.py'))
 model = ciaosr_amd.build_model(cfg.model, train_cfg=None, test_cfg=dict(scale=4))
 seeded_init_(model, seed=0, gain=1.0)
 model = model.to(dev).eval()
-print(f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, reps {args.reps}')
+if not args.worker:
+    print(f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, reps {args.reps}')
 
 
 def timed(fn):
@@ -101,9 +119,171 @@ def view_legs():
         torch.cuda.empty_cache()
 
 
+MANY_LR, MANY_SCALES = (1356, 2040), (2.0, 3.3, 4.0)
+
+
+def many_cfg(precision, cache_mb):
+    cfg = dict(scale=4, tile=192, tile_overlap=32, tile_any_scale=True, precision=precision)
+    if cache_mb:
+        cfg['scene_cache_mb'] = int(cache_mb)
+    return cfg
+
+
+def three_renders(lq):
+    """Leg (a): encode, then one `render` per scale.  -> (wall ms, scene builds)"""
+    def run():
+        enc = model.encode(lq, max_scale=4)
+        for s in MANY_SCALES:
+            model.render(enc, scale=s)
+        return enc.cache.builds
+    return timed(run)
+
+
+def many_worker():
+    """The parent-tree child: `cfg <precision> <cache_mb or 0>` sets the test_cfg, `round` runs leg (a) once and answers one JSON line."""
+    lq = synthetic_pair(*MANY_LR, 4)[0].to(dev)
+    print(json.dumps(dict(version=_lib.load().ciaosr_version())), flush=True)
+    for line in sys.stdin:
+        cmd = line.split()
+        if not cmd or cmd[0] == 'quit':
+            break
+        if cmd[0] == 'cfg':
+            model.test_cfg = many_cfg(cmd[1], int(cmd[2]))
+            hip_ops.release_workspaces()
+            torch.cuda.empty_cache()
+            print(json.dumps(dict(ok=True)), flush=True)
+        elif cmd[0] == 'round':
+            ms, builds = three_renders(lq)
+            print(json.dumps(dict(ms=ms, builds=builds)), flush=True)
+
+
+def many_legs():
+    from ciaosr_amd.scene import Grid, View, view_matrix
+    lines = []
+
+    def say(text=''):
+        print(text, flush=True)
+        lines.append(text)
+
+    child = None
+    if args.parent_root:
+        child = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--legs', 'many', '--worker', '--root', args.parent_root],
+                                 stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+        def ask(cmd):
+            child.stdin.write(cmd + '\n')
+            child.stdin.flush()
+            answer = child.stdout.readline()
+            if not answer:
+                raise SystemExit(f'the parent-tree child ended (exit status {child.wait()})')
+            return json.loads(answer)
+        parent_version = json.loads(child.stdout.readline())['version']
+    lq = synthetic_pair(*MANY_LR, 4)[0].to(dev)
+    h, w = MANY_LR
+    n_tiles = len(ciaosr_amd.scene.plan_view(h, w, 192, 32, any_scale=True))
+    say(f'tools/scene_probe.py --legs many --reps {args.reps}: library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}; '
+        f'LR {h} x {w}, tile 192 / overlap 32 ({n_tiles} tiles), targets x2, x3.3, x4 full grids')
+    say('leg (a): ' + (f'three render calls, parent commit (library version {parent_version}) in a child process' if child else
+                      'three render calls, THIS tree in this process (no --parent-root given)'))
+    targets = [Grid(scale=s) for s in MANY_SCALES]
+
+    def leg_b():
+        def run():
+            enc = model.encode(lq, max_scale=4)
+            model.render_many(enc, targets)
+            return enc.cache.builds
+        return timed(run)
+
+    def leg_c():
+        return timed(lambda: model.restore(lq))[0], 0
+
+    def leg_a():
+        if child:
+            r = ask('round')
+            return r['ms'], r['builds']
+        return three_renders(lq)
+
+    legs = (('(a) 3 x render', leg_a), ('(b) render_many', leg_b), ('(c) restore x4', leg_c))
+    everything = 117 * 520                       # MiB: above 117 fp32 tile scenes of 491 MiB
+    for precision in args.precisions.split(','):
+        for cache_mb, label in ((0, 'default cache (4096 MiB)'), (everything, f'cache that holds everything ({everything} MiB)')):
+            model.test_cfg = many_cfg(precision, cache_mb)
+            if child:
+                ask(f'cfg {precision} {cache_mb}')
+            hip_ops.release_workspaces()
+            torch.cuda.empty_cache()
+            for _, fn in legs:                   # warm-up
+                fn()
+            times = {name: [] for name, _ in legs}
+            builds = {name: [] for name, _ in legs}
+            for _ in range(args.reps):
+                for name, fn in legs:
+                    ms, n = fn()
+                    times[name].append(ms)
+                    builds[name].append(n)
+            say(f'\n{precision}, {label}:')
+            for name, _ in legs:
+                v = times[name]
+                say(f'    {name:16s} wall mean {sum(v) / len(v):10.1f} ms  min {min(v):10.1f}  max {max(v):10.1f}   scene builds per round {sorted(set(builds[name]))}')
+            a, b = times['(a) 3 x render'], times['(b) render_many']
+            say(f'    render_many / three renders: {sum(b) / sum(a):.3f} of the means, {min(b) / min(a):.3f} of the minima')
+    if child:
+        child.stdin.write('quit\n')
+        child.stdin.flush()
+        child.wait(timeout=60)
+    # 16 views along a pan: synchronising copies
+    n = args.view_size
+    views = [View(view_matrix((h / 2, n / 8 + k * (w - n / 4) / 15), 4.0, 0, (n, n)), (n, n)) for k in range(16)]
+    copies = [0]
+    tolist = torch.Tensor.tolist
+
+    def counting(t):
+        copies[0] += int(t.is_cuda)
+        return tolist(t)
+
+    say(f'\n16 views of {n} x {n} along a pan at x4 (centre row {h / 2:g}, columns {n / 8:g} .. {w - n / 8:g}), fresh encode per round:')
+    for precision in args.precisions.split(','):
+        model.test_cfg = many_cfg(precision, 0)
+
+        def singles():
+            enc = model.encode(lq, max_scale=4)
+            for v in views:
+                model.render_view(enc, v.matrix, v.size)
+            return enc.cache.builds
+
+        def many():
+            enc = model.encode(lq, max_scale=4)
+            model.render_many(enc, views)
+            return enc.cache.builds
+        pan = (('16 x render_view', singles), ('render_many', many))
+        for _, fn in pan:
+            fn()
+        times = {name: [] for name, _ in pan}
+        seen = {}
+        for _ in range(args.reps):
+            for name, fn in pan:
+                copies[0] = 0
+                torch.Tensor.tolist = counting
+                try:
+                    ms, nb = timed(fn)
+                finally:
+                    torch.Tensor.tolist = tolist
+                times[name].append(ms)
+                seen[name] = (copies[0], nb)
+        for name, _ in pan:
+            v = times[name]
+            say(f'    {precision:5s} {name:17s} wall mean {sum(v) / len(v):9.1f} ms  min {min(v):9.1f}  max {max(v):9.1f}   '
+                f'synchronising copies {seen[name][0]}, scene builds {seen[name][1]}')
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 scales = [float(s) for s in args.scales.split(',')]
 if args.legs == 'view':
     view_legs()
+if args.legs == 'many':
+    many_worker() if args.worker else many_legs()
 for size in (int(v) for v in args.sizes.split(',') if args.legs == 'scene'):
     lq = synthetic_pair(size, size, 4)[0].to(dev)
     for precision in args.precisions.split(','):
