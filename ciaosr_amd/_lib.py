@@ -53,7 +53,7 @@ class OptionsT(C.Structure):
     _fields_ = [('head_route', C.c_int), ('csa_composed_min', C.c_int), ('dense_min_tiles', C.c_int),
                 ('scatter_small_max', C.c_int), ('kv_rows', C.c_int), ('decode_rows', C.c_int), ('bf16_single', C.c_int),
                 ('dense_direct', C.c_int), ('csa_scores_gemm', C.c_int), ('csa_attn_tile128', C.c_int), ('query_grid_w', C.c_int), ('f16_pairs', C.c_int),
-                ('csa_attn_v16', C.c_int), ('swin_h16', C.c_int), ('csa_block_mb', C.c_int)]
+                ('csa_attn_v16', C.c_int), ('edsr_resident', C.c_int), ('swin_h16', C.c_int), ('csa_block_mb', C.c_int)]
 
 
 HEAD_STAGED, HEAD_NO_LOGIT_TABLE, HEAD_TABLE_GEMM, HEAD_WIDE_WG, HEAD_TABLE_WINO2, HEAD_NO_CHAIN, HEAD_NO_DECODE_CHAIN = 1, 2, 4, 8, 16, 32, 64
@@ -171,6 +171,9 @@ SIGNATURES = {
     'ciaosr_rdn_forward_batch_f16': (_I, [_P, _I, _I, _I, C.POINTER(RdnWeightsT), _P, _O, _P, _S, _P]),
     'ciaosr_edsr_workspace_bytes': (_S, [_I, _I, C.POINTER(EdsrWeightsT)]),
     'ciaosr_edsr_forward_f32': (_I, [_P, _I, _I, C.POINTER(EdsrWeightsT), _P, _P, _S, _P]),
+    'ciaosr_edsr_workspace_bytes_batch': (_S, [_I, _I, _I, C.POINTER(EdsrWeightsT), _O]),
+    'ciaosr_edsr_route_code': (_I, [_I, _I, _I, C.POINTER(EdsrWeightsT), _O]),
+    'ciaosr_edsr_forward_batch_f32': (_I, [_P, _I, _I, _I, C.POINTER(EdsrWeightsT), _P, _O, _P, _S, _P]),
     'ciaosr_swinir_workspace_bytes': (_S, [_I, _I, C.POINTER(SwinirWeightsT)]),
     'ciaosr_swinir_forward_f32': (_I, [_P, _I, _I, C.POINTER(SwinirWeightsT), _P, _P, _S, _P]),
     'ciaosr_swinir_workspace_bytes_batch_f16': (_S, [_I, _I, _I, C.POINTER(SwinirWeightsT)]),

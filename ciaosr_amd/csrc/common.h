@@ -72,7 +72,7 @@ static inline bool options_ok(const ciaosr_options_t* o) {
            (o->decode_rows == 0 || o->decode_rows == 32 || o->decode_rows == 64) && (o->bf16_single == 0 || o->bf16_single == 1) &&
            (o->dense_direct >= 0 && o->dense_direct <= 2) && (o->csa_scores_gemm == 0 || o->csa_scores_gemm == 1) &&
            o->f16_pairs >= 0 && o->f16_pairs <= 3 && (o->csa_attn_v16 == 0 || o->csa_attn_v16 == 1) && o->csa_block_mb >= 0 &&
-           (o->swin_h16 == 0 || o->swin_h16 == 1);
+           (o->swin_h16 == 0 || o->swin_h16 == 1) && (o->edsr_resident == 0 || o->edsr_resident == 1);
 }
 
 }  // namespace ciaosr

@@ -14,6 +14,10 @@
 //   * per group a workgroup ingests 50 KB of patch + 147 KB of weights against 46k cycles of MFMA work (4.3 B/clk/CU);
 //   * the K-slices are summed through LDS once per layer, in a fixed order (deterministic).
 // Same MACs as the reference convolution, fp32 products and sums; only the summation order differs from conv_f32.hip.
+//
+// The kernel takes its input groups from any (pointer, ld, first column), writes to any (pointer, ld, column) and ends in one of two
+// epilogues (DenseEpi): the RDN dense layer is the relu form on one buffer; the EDSR trunk over tile batches (encoder.hip, a 64 -> 64
+// convolution = a one-group layer) uses both, the residual form in place on its running sum.
 
 #include "ops.h"
 
@@ -32,17 +36,29 @@ constexpr int FMT = 5;                       // 32-pixel MFMA tiles per workgrou
 constexpr size_t kDenseF32Lds = 2 * (size_t)FPATCH;   // 106 624 B >= K-slice reduction scratch (81 920 B)
 constexpr unsigned kOobDF = 0xFFFFFFF0u;
 
+// Every operand is n_img images of H x W pixel rows back to back, as (pointer, floats per row, first column).  An RDN dense layer reads
+// groups 0..l of its block buffer and writes group l + 1 of the same buffer; the EDSR trunk (encoder.hip) reads one group of one buffer and
+// writes another buffer or another group, with a residual that may be the destination itself.
 struct DenseF32P {
-    float* x; int ldx;                       // fp32 feature buffer [HW][ldx], 64-channel groups; read and written
+    const float* x; int ldx, col_in;         // source [n_img HW][ldx]: input group g = columns col_in + 64 g .. + 63 (buffer descriptor)
     unsigned x_bytes;
     int H, W, tiles_x;
-    int n_img;                               // images in the buffer (back to back); one workgroup walks its tile of every image
-    int groups;                              // input groups of this layer (l + 1)
+    int n_img;                               // images in the buffers (back to back); one workgroup walks its tile of every image
+    int groups;                              // input groups of this layer
     const float4* wf; int nj;                // fragments [2][nj][64 lanes] float4, nj = 9*cin/8
     const float* bias;                       // [64]
-    int col_out;
+    float* dst; int ld_dst, col_out;         // destination [n_img HW][ld_dst], 64 columns from col_out
+    const float* res; int ld_res, col_res;   // kDenseResidual: [n_img HW][ld_res], 64 columns from col_res; may be dst (in place)
+    float alpha;
 };
 
+// Epilogues, fp32, every operation rounded on its own (no FMA contraction):
+//   kDenseRelu      max(sum + bias, 0)
+//   kDenseResidual  res[pixel][co] + alpha * (sum + bias), no activation.  A workgroup reads `res` only at the pixels and channels it
+//                   writes, each by the lane that writes it, before the store: `res` may be the destination itself.
+enum DenseEpi { kDenseRelu = 0, kDenseResidual = 1 };
+
+template <int EPI>
 __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsf[];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
@@ -51,7 +67,7 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
     // weights and the halo patch of image i + 1 are requested during the last input group of image i, so only the first image pays
     // the cold start.  Per image the work, its order and hence the result are those of a single-image launch.
     const unsigned img_bytes = (unsigned)((size_t)p.H * p.W * p.ldx * 4);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
 
     // patch staging: thread -> 16-byte chunks t + 256 s  (pixel = chunk / 16, 16 chunks = 64 channels)
     unsigned goff[FLOADS];
@@ -63,7 +79,7 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
         const int py = px / FP, pxx = px - py * FP;
         const int gy = ty0 - 1 + py, gx = tx0 - 1 + pxx;
         const bool ok = c < FCHUNKS && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-        goff[s] = ok ? ((unsigned)(gy * p.W + gx) * (unsigned)p.ldx * 4u + (unsigned)part * 16u) : kOobDF;
+        goff[s] = ok ? ((unsigned)(gy * p.W + gx) * (unsigned)p.ldx * 4u + (unsigned)p.col_in * 4u + (unsigned)part * 16u) : kOobDF;
         loff[s] = c < FCHUNKS ? px * FPS + part * 16 : -1;
     }
     i32x4 P[FLOADS];
@@ -174,7 +190,7 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
     // K-slice reduction + epilogue of this image, one 32-channel half at a time through LDS (the scratch overlays both patch buffers:
     // the next image's patch stays in registers until it is done):
     // red[w][r][q][lane] = float4 of accumulator registers 4q..4q+3 (= channels 8q + 4lh .. +3 of pixel li of tile r)
-    float* const xi = p.x + (size_t)img * p.H * p.W * p.ldx;
+    const size_t row0 = (size_t)img * p.H * p.W;                 // first pixel row of this image in every operand
     float4* red = reinterpret_cast<float4*>(ldsf);
     for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
@@ -199,9 +215,17 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
             if (idx < FT * FT && y < p.H && x < p.W) {
                 const int co = 32 * nt + 8 * q + 4 * (ul >> 5);
                 const float4 b = *reinterpret_cast<const float4*>(p.bias + co);
-                v.x = fmaxf(v.x + b.x, 0.f); v.y = fmaxf(v.y + b.y, 0.f);
-                v.z = fmaxf(v.z + b.z, 0.f); v.w = fmaxf(v.w + b.w, 0.f);
-                *reinterpret_cast<float4*>(xi + ((size_t)y * p.W + x) * p.ldx + p.col_out + co) = v;
+                const size_t pix = row0 + (size_t)y * p.W + x;
+                if (EPI == kDenseRelu) {
+                    v.x = fmaxf(v.x + b.x, 0.f); v.y = fmaxf(v.y + b.y, 0.f);
+                    v.z = fmaxf(v.z + b.z, 0.f); v.w = fmaxf(v.w + b.w, 0.f);
+                } else {
+#pragma clang fp contract(off)
+                    const float4 rr = *reinterpret_cast<const float4*>(p.res + pix * p.ld_res + p.col_res + co);
+                    v.x = rr.x + p.alpha * (v.x + b.x); v.y = rr.y + p.alpha * (v.y + b.y);
+                    v.z = rr.z + p.alpha * (v.z + b.z); v.w = rr.w + p.alpha * (v.w + b.w);
+                }
+                *reinterpret_cast<float4*>(p.dst + pix * p.ld_dst + p.col_out + co) = v;
             }
         }
         __syncthreads();
@@ -217,23 +241,43 @@ __global__ __launch_bounds__(256) void dense_f32_kernel(DenseF32P p) {
 
 int dense_f32_tiles(int H, int W) { return ceil_div(H, FT) * ceil_div(W, FT); }
 
-// dense layer l of a block: input groups 0..l of X, output group l+1; X holds n_img images of H x W rows back to back
-int dense_layer_f32(float* X, int ldx, int H, int W, int l, const float* frag, const float* bias, int n_img, hipStream_t s) {
-    CIAOSR_CHECK_ARG(X && frag && bias && (ldx & 3) == 0 && aligned16(X) && aligned16(frag) && aligned16(bias));
-    const size_t x_bytes = (size_t)n_img * H * W * ldx * 4;
+// One 3x3 convolution 64 * groups -> 64 over n_img images of H x W pixels: source (src, ld_src, col_in), destination (dst, ld_dst, col_out),
+// epilogue `epi` (DenseEpi) with residual (res, ld_res, col_res) and alpha.  The source is addressed through a 32-bit buffer descriptor;
+// the destination and the residual through 64-bit pointers.  Source and destination columns must not overlap where they share a buffer
+// (a workgroup reads the halo of its neighbours' pixels).
+int dense_conv_f32(const float* src, int ld_src, int col_in, int groups, float* dst, int ld_dst, int col_out, const float* res, int ld_res,
+                   int col_res, int epi, float alpha, int H, int W, const float* frag, const float* bias, int n_img, hipStream_t s,
+                   const char* tag) {
+    CIAOSR_CHECK_ARG(src && dst && frag && bias && H > 0 && W > 0 && groups >= 1 && (epi == kDenseRelu || epi == kDenseResidual));
+    CIAOSR_CHECK_ARG((ld_src & 3) == 0 && (col_in & 3) == 0 && col_in >= 0 && col_in + 64 * groups <= ld_src && aligned16(src));
+    CIAOSR_CHECK_ARG((ld_dst & 3) == 0 && (col_out & 3) == 0 && col_out >= 0 && col_out + 64 <= ld_dst && aligned16(dst));
+    CIAOSR_CHECK_ARG(aligned16(frag) && aligned16(bias));
+    CIAOSR_CHECK_ARG(epi != kDenseResidual || (res && (ld_res & 3) == 0 && (col_res & 3) == 0 && col_res >= 0 && col_res + 64 <= ld_res && aligned16(res)));
+    // source and destination in one buffer: the output columns lie outside the input columns
+    CIAOSR_CHECK_ARG((const float*)dst != src || ld_dst != ld_src || col_out >= col_in + 64 * groups || col_out + 64 <= col_in);
+    const size_t x_bytes = (size_t)n_img * H * W * ld_src * 4;
     CIAOSR_CHECK_ARG(n_img >= 1 && x_bytes < 0xFFFFFF00ull);
     DenseF32P p;
-    p.x = X; p.ldx = ldx; p.x_bytes = (unsigned)x_bytes;
+    p.x = src; p.ldx = ld_src; p.col_in = col_in; p.x_bytes = (unsigned)x_bytes;
     p.H = H; p.W = W; p.tiles_x = ceil_div(W, FT);
     p.n_img = n_img;
-    p.groups = l + 1;
-    p.wf = reinterpret_cast<const float4*>(frag); p.nj = 9 * 64 * (l + 1) / 8;
+    p.groups = groups;
+    p.wf = reinterpret_cast<const float4*>(frag); p.nj = 9 * 64 * groups / 8;
     p.bias = bias;
-    p.col_out = 64 * (l + 1);
-    CIAOSR_BIG_LDS(dense_f32_kernel, kDenseF32Lds);
-    ProfScope prof("enc_dense_gather", s);
-    hipLaunchKernelGGL(dense_f32_kernel, dim3(dense_f32_tiles(H, W)), dim3(256), kDenseF32Lds, s, p);
+    p.dst = dst; p.ld_dst = ld_dst; p.col_out = col_out;
+    p.res = epi == kDenseResidual ? res : nullptr; p.ld_res = ld_res; p.col_res = col_res;
+    p.alpha = alpha;
+    if (epi == kDenseRelu) CIAOSR_BIG_LDS(dense_f32_kernel<kDenseRelu>, kDenseF32Lds);
+    else CIAOSR_BIG_LDS(dense_f32_kernel<kDenseResidual>, kDenseF32Lds);
+    ProfScope prof(tag, s);
+    if (epi == kDenseRelu) hipLaunchKernelGGL(dense_f32_kernel<kDenseRelu>, dim3(dense_f32_tiles(H, W)), dim3(256), kDenseF32Lds, s, p);
+    else hipLaunchKernelGGL(dense_f32_kernel<kDenseResidual>, dim3(dense_f32_tiles(H, W)), dim3(256), kDenseF32Lds, s, p);
     return launch_status("dense_f32");
+}
+
+// dense layer l of a block: input groups 0..l of X, output group l+1; X holds n_img images of H x W rows back to back
+int dense_layer_f32(float* X, int ldx, int H, int W, int l, const float* frag, const float* bias, int n_img, hipStream_t s) {
+    return dense_conv_f32(X, ldx, 0, l + 1, X, ldx, 64 * (l + 1), nullptr, 0, 0, kDenseRelu, 1.f, H, W, frag, bias, n_img, s, "enc_dense_gather");
 }
 
 }  // namespace ciaosr

@@ -19,6 +19,10 @@ int dense_scatter_small(float* X, int ldx, int H, int W, int step, int num_layer
 // dense_f32.hip
 int dense_f32_tiles(int H, int W);
 int dense_layer_f32(float* X, int ldx, int H, int W, int l, const float* frag, const float* bias, int n_img, hipStream_t s);
+// the same kernel with any source, destination and one of two epilogues: 0 = relu, 1 = res + alpha * (sum + bias)
+int dense_conv_f32(const float* src, int ld_src, int col_in, int groups, float* dst, int ld_dst, int col_out, const float* res, int ld_res,
+                   int col_res, int epi, float alpha, int H, int W, const float* frag, const float* bias, int n_img, hipStream_t s,
+                   const char* tag);
 
 __global__ void image_to_hwc4_kernel(const float* __restrict__ x, float* __restrict__ out, long HW) {
     // [3][H][W] -> [H*W][4] with a zero 4th channel (so the first conv moves float4 taps)
@@ -273,6 +277,89 @@ struct RdnCall : RdnBuffers {
     }
 };
 
+// ---- EDSR over tile batches (opt->edsr_resident).  edsr_batch_forward() checks its arguments, plans (edsr_plan), decides the route
+// (edsr_route: the only place that reads the option, the weights' presence and the map's size; it launches nothing), carves the workspace
+// (edsr_carve: the only list of buffers) and calls one function per stage:
+//   stage        launches in order (profiler tags)                                              scratch: reads -> writes
+//   stem         per image: image_to_hwc4, enc_patch_first, enc_conv_first                      x -> img4 -> rows -> first
+//   block b      enc_edsr_resident x 2, the whole batch in each: conv1 (relu), conv2 (residual, x (b = 0: first) -> X[:, 64..) -> X[:, :64)
+//                alpha = res_scale, in place on the running x)
+//   tail         enc_edsr_resident: conv_after_body, residual = first, alpha = 1                X[:, :64), first -> feat
+// X [B HW][128]: group 0 = the running x, group 1 = relu(conv1(x)).  A launch reads one group (with its halo) and writes the other group or
+// another buffer, so no workgroup writes what another reads; the residual is read by the lane that overwrites it, at that pixel alone.
+// Block 0 reads its source and residual from `first`, which nothing writes after the stem.  Route 0 (per image) is the body of
+// ciaosr_edsr_forward_f32, image after image.
+struct EdsrPlan {
+    int B, H, W, C, NB;
+    size_t HW, BHW;
+};
+static EdsrPlan edsr_plan(int B, int H, int W, const ciaosr_edsr_weights_t* w) {
+    EdsrPlan p = {B, H, W, w->mid_channels, w->num_blocks, (size_t)H * W, (size_t)B * H * W};
+    return p;
+}
+struct EdsrBuffers : EdsrPlan {
+    float *img4, *rows, *first, *X;
+};
+// The one list of carve-outs of the resident route, in carve order (as rdn_carve)
+template <class Take>
+static EdsrBuffers edsr_carve(const EdsrPlan& p, Take take) {
+    EdsrBuffers b = {p};
+    b.img4 = take(p.HW * 4); b.rows = take(p.HW * 36);          // first-conv temporaries, one image at a time
+    b.first = take(p.BHW * 64);
+    b.X = take(p.BHW * 128);
+    return b;
+}
+struct EdsrRoute {
+    bool resident;
+    int batch;             // resident: images per pass (B, or fewer where the batch buffer outgrows 32-bit offsets)
+};
+// What a call runs; launches nothing
+static EdsrRoute edsr_route(const EdsrPlan& p, const ciaosr_options_t* opt, const ciaosr_edsr_weights_t* w) {
+    EdsrRoute r = {false, 1};
+    if (!opt || opt->edsr_resident != 1 || p.C != 64 || p.NB < 1 || !w->conv1 || !w->conv2 || !w->conv_after_body.frag) return r;
+    for (int i = 0; i < p.NB; ++i)
+        if (!w->conv1[i].frag || !w->conv2[i].frag) return r;
+    const int min_tiles = opt->dense_min_tiles ? opt->dense_min_tiles : 128;
+    if (min_tiles < 0 || dense_f32_tiles(p.H, p.W) < min_tiles) return r;
+    // X [B HW][128] is the widest operand the kernel addresses through a 32-bit buffer descriptor: a batch that does not fit runs as
+    // sub-batches that do (same workgroups per image: still bitwise the one-image result); a single image that does not fit goes per image
+    const size_t img_bytes = p.HW * 128 * sizeof(float);
+    if (img_bytes >= 0xFFFFFF00ull) return r;
+    const size_t bmax = (size_t)(0xFFFFFF00ull - 1) / img_bytes;
+    r.resident = true;
+    r.batch = (size_t)p.B <= bmax ? p.B : (int)bmax;
+    return r;
+}
+static int edsr_args_ok(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt) {
+    CIAOSR_CHECK_ARG(w && B >= 1 && H > 0 && W > 0);
+    CIAOSR_CHECK_ARG(options_ok(opt));
+    const int C = w->mid_channels, NB = w->num_blocks;
+    CIAOSR_CHECK_ARG(C > 0 && C % 32 == 0 && NB >= 0 && (NB == 0 || (w->conv1 && w->conv2)));
+    CIAOSR_CHECK_ARG(conv_ok(w->conv_first, 3, C, 3) && conv_ok(w->conv_after_body, C, C, 3));
+    for (int i = 0; i < NB; ++i) CIAOSR_CHECK_ARG(conv_ok(w->conv1[i], C, C, 3) && conv_ok(w->conv2[i], C, C, 3));
+    return CIAOSR_OK;
+}
+
+struct EdsrCall : EdsrBuffers {
+    const ciaosr_edsr_weights_t* w; hipStream_t s;
+
+    int stem(const float* x_nchw) const {
+        for (int i = 0; i < B; ++i) RDN_RUN(first_conv(x_nchw + (size_t)i * 3 * HW, H, W, w->conv_first, img4, rows, first + (size_t)i * HW * 64, 64, s));
+        return CIAOSR_OK;
+    }
+    // ResidualBlockNoBN: x + conv2(relu(conv1(x))) * res_scale
+    int block(int b) const {
+        const float* x = b ? X : first;
+        const int ldx = b ? 128 : 64;
+        RDN_RUN(dense_conv_f32(x, ldx, 0, 1, X, 128, 64, nullptr, 0, 0, 0, 1.f, H, W, w->conv1[b].frag, w->conv1[b].bias, B, s, "enc_edsr_resident"));
+        return dense_conv_f32(X, 128, 64, 1, X, 128, 0, x, ldx, 0, 1, w->res_scale, H, W, w->conv2[b].frag, w->conv2[b].bias, B, s, "enc_edsr_resident");
+    }
+    int tail(float* feat_hwc) const {
+        return dense_conv_f32(X, 128, 0, 1, feat_hwc, 64, 0, first, 64, 0, 1, 1.f, H, W, w->conv_after_body.frag, w->conv_after_body.bias, B, s,
+                              "enc_edsr_resident");
+    }
+};
+
 }  // namespace ciaosr
 
 using namespace ciaosr;
@@ -396,4 +483,49 @@ extern "C" int ciaosr_edsr_forward_f32(const float* x_nchw, int H, int W, const 
     RUN(conv3(cur, C, H, W, w->conv_after_body, feat_hwc, C, first, C, CIAOSR_ACT_NONE, 1.f, part, pf, s));
 #undef RUN
     return CIAOSR_OK;
+}
+
+extern "C" size_t ciaosr_edsr_workspace_bytes_batch(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt) {
+    if (!w || B <= 0 || H <= 0 || W <= 0 || !options_ok(opt) || w->mid_channels <= 0 || w->num_blocks < 0) return 0;
+    EdsrPlan p = edsr_plan(B, H, W, w);
+    const EdsrRoute r = edsr_route(p, opt, w);
+    if (!r.resident) return ciaosr_edsr_workspace_bytes(H, W, w);      // the images go one after the other through one image's buffers
+    p = edsr_plan(r.batch, H, W, w);                                    // a pass at a time
+    size_t n = 0;
+    edsr_carve(p, [&](size_t floats) { n += floats; return (float*)nullptr; });
+    return n * sizeof(float) + 16 * 256;              // room for the 256-byte alignment of each carve-out
+}
+
+extern "C" int ciaosr_edsr_route_code(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt) {
+    const int rc = edsr_args_ok(B, H, W, w, opt);
+    if (rc != CIAOSR_OK) return rc;
+    const EdsrRoute r = edsr_route(edsr_plan(B, H, W, w), opt, w);
+    if (!r.resident) return 0;
+    return 1 | (r.batch < B ? r.batch << 8 : 0);
+}
+
+extern "C" int ciaosr_edsr_forward_batch_f32(const float* x_bchw, int B, int H, int W, const ciaosr_edsr_weights_t* w, float* feat_bhwc,
+                                             const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream_) {
+    CIAOSR_CHECK_ARG(x_bchw && feat_bhwc && workspace);
+    RDN_RUN(edsr_args_ok(B, H, W, w, opt));
+    if (workspace_bytes < ciaosr_edsr_workspace_bytes_batch(B, H, W, w, opt)) return CIAOSR_ERR_WORKSPACE;
+    const EdsrPlan p = edsr_plan(B, H, W, w);
+    const EdsrRoute r = edsr_route(p, opt, w);
+    if (!r.resident) {
+        for (int i = 0; i < B; ++i)
+            RDN_RUN(ciaosr_edsr_forward_f32(x_bchw + (size_t)i * 3 * p.HW, H, W, w, feat_bhwc + (size_t)i * p.HW * p.C, workspace, workspace_bytes, stream_));
+        return CIAOSR_OK;
+    }
+    for (int i = 0; i < B && r.batch < B; i += r.batch) {          // passes of r.batch images
+        const int nb = B - i < r.batch ? B - i : r.batch;
+        RDN_RUN(ciaosr_edsr_forward_batch_f32(x_bchw + (size_t)i * 3 * p.HW, nb, H, W, w, feat_bhwc + (size_t)i * p.HW * 64, opt, workspace, workspace_bytes,
+                                              stream_));
+    }
+    if (r.batch < B) return CIAOSR_OK;
+    Arena ar(workspace, workspace_bytes);
+    const EdsrCall c = {edsr_carve(p, [&](size_t floats) { return ar.take<float>(floats); }), w, (hipStream_t)stream_};
+    if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
+    RDN_RUN(c.stem(x_bchw));
+    for (int b = 0; b < p.NB; ++b) RDN_RUN(c.block(b));
+    return c.tail(feat_bhwc);
 }

@@ -1,4 +1,5 @@
-"""Weight packing + launch of the HIP encoder trunks (ciaosr_rdn_forward_f32 / ciaosr_edsr_forward_f32).
+"""Weight packing + launch of the HIP encoder trunks (ciaosr_rdn_forward_f32 / ciaosr_edsr_forward_f32; with `Options(edsr_resident=1)`
+the EDSR trunk over tile batches, ciaosr_edsr_forward_batch_f32).
 
 Conv weights [co][ci][a][b] are packed once to [co][(a*k+b)*ci' + ci] so that one tap of the
 channels-last map is contiguous in K (implicit-GEMM convolution, csrc/conv_f32.hip)."""
@@ -227,11 +228,14 @@ class PackedEncoder:
     @torch.no_grad()
     def forward_hwc_batch(self, x_bchw, options=None):
         """x [B,3,H,W] normalised LR crops of one size (GPU) -> features [B,H,W,C] channels-last, the B images sharing the
-        trunk's dense-layer launches (ciaosr_rdn_forward_batch_*; each image bitwise equal to a forward_hwc call)."""
+        trunk's dense-layer launches (ciaosr_rdn_forward_batch_*; EDSR under `Options(edsr_resident=1)`: ciaosr_edsr_forward_batch_f32;
+        each image bitwise equal to a forward_hwc call)."""
         B = x_bchw.shape[0]
+        opt = hip_ops.as_options(options)
+        if self.kind == 'edsr' and opt.edsr_resident:
+            return self._edsr_batch(x_bchw, opt)
         if self.kind != 'rdn' or B == 1:
             return torch.stack([self.forward_hwc(x_bchw[i], options) for i in range(B)])
-        opt = hip_ops.as_options(options)
         x_bchw = x_bchw.contiguous().float()
         hip_ops.require_gpu(x_bchw)
         _, _, H, W = x_bchw.shape
@@ -243,10 +247,25 @@ class PackedEncoder:
                   hip_ops.ptr(ws), ws.numel(), hip_ops.stream_ptr())
         return self._narrow(out)
 
+    def _edsr_batch(self, x_bchw, opt):
+        """The EDSR trunk of B crops through ciaosr_edsr_forward_batch_f32 (fp32 in every precision mode: the suffix stays f32)."""
+        x_bchw = x_bchw.contiguous().float()
+        hip_ops.require_gpu(x_bchw)
+        B, _, H, W = x_bchw.shape
+        st = self.struct(None)
+        nbytes = _lib.load().ciaosr_edsr_workspace_bytes_batch(B, H, W, C.byref(st), opt.c_arg())
+        ws = hip_ops.workspace(nbytes, x_bchw.device, slot='encoder')
+        out = torch.empty(B, H, W, st.mid_channels, dtype=torch.float32, device=x_bchw.device)
+        _lib.call('ciaosr_edsr_forward_batch_f32', hip_ops.ptr(x_bchw), B, H, W, C.byref(st), hip_ops.ptr(out), opt.c_arg(), hip_ops.ptr(ws),
+                  ws.numel(), hip_ops.stream_ptr())
+        return self._narrow(out)
+
     @torch.no_grad()
     def forward_hwc(self, x_chw, options=None):
         """x [3,H,W] normalised LR (GPU) -> feature [H,W,C] channels-last.  `options`: hip_ops.Options."""
         opt = hip_ops.as_options(options)
+        if self.kind == 'edsr' and opt.edsr_resident:
+            return self._edsr_batch(x_chw[None], opt)[0]
         x_chw = x_chw.contiguous().float()
         hip_ops.require_gpu(x_chw)
         _, H, W = x_chw.shape

@@ -376,7 +376,7 @@ class Options:
     the rest   fields of ciaosr_options_t (include/ciaosr_hip.h): result-equivalent route choices; 0 = default.
     Immutable; `replace()` returns a modified copy."""
     _C_FIELDS = ('head_route', 'csa_composed_min', 'dense_min_tiles', 'scatter_small_max', 'kv_rows', 'decode_rows', 'bf16_single', 'dense_direct', 'csa_scores_gemm', 'csa_attn_tile128', 'query_grid_w', 'f16_pairs',
-                 'csa_attn_v16', 'swin_h16', 'csa_block_mb')
+                 'csa_attn_v16', 'edsr_resident', 'swin_h16', 'csa_block_mb')
     _MODE_FIELDS = ('precision', 'f16_pairs', 'bf16_single')
     __slots__ = ('mode', 'precision') + _C_FIELDS + ('_c',)
 

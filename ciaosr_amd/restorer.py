@@ -123,6 +123,13 @@ def tile_grid(h, w, tile, overlap):
 # that chose a value); until such a run exists this is 4 -- 1.23 GiB of trunk workspace at that tile size.
 SWIN_TILE_BATCH = 4
 
+# Tiles per call of the EDSR trunk over tile batches (`hip_options.edsr_resident`) when `test_cfg.tile_batch` is not given: 8, the rule
+# of CiaoSR.tile_batch for a kernel whose workgroup covers 12 x 12 pixels (7 is for the 16 x 32-pixel kernels).
+# Was an unmeasured placeholder until tools/edsr_tile_probe.py timed the candidates 1, 4, 7, 8 at tile = 192 (profiles/edsr_resident.txt):
+# the fastest 6-tile restore (4, 168.79 ms) is 0.14 ms under 8 (168.93 ms) with a round-to-round spread of up to 0.84 ms, so it stays 8;
+# it changes only if a candidate beats 8 by more than the spread of such a run.
+EDSR_TILE_BATCH = 8
+
 
 def trunk_batches(generator, options):
     """Whether the tile loops feed this generator's trunk batches of tiles: it has a `forward_hwc_batch`, and -- where the trunk says
@@ -332,12 +339,16 @@ class CiaoSR(BasicRestorer):
         Default 7 where the trunk's dense layers run a kernel whose workgroup covers 16 x 32 pixels -- the F(4x4, 3x3) Winograd kernel
         of the fp32 trunk (dense_direct = 0) and, since round 6, the 16-bit dense kernel (dense_direct != 1): a 192 x 192 tile is 72
         workgroups / items, 8 tiles are 576 = 2.25 rounds of the 256 CUs (a third round at a quarter of the chip), 7 tiles are 504 =
-        1.97 -- else 8.  The SwinIR trunk (batched only under `hip_options.swin_h16`): SWIN_TILE_BATCH."""
+        1.97 -- else 8.  The SwinIR trunk (batched only under `hip_options.swin_h16`): SWIN_TILE_BATCH.  The EDSR trunk under
+        `hip_options.edsr_resident` (fp32 on the 12 x 12-pixel kernel in every precision mode): EDSR_TILE_BATCH."""
         v = self.test_cfg.get('tile_batch', None)
         if v is None:
             opt = self.options(options)
-            if hasattr(getattr(self.generator, '_encoder_hip', None), 'uses_h16'):
+            enc = getattr(self.generator, '_encoder_hip', None)
+            if hasattr(enc, 'uses_h16'):
                 return SWIN_TILE_BATCH
+            if getattr(enc, 'kind', None) == 'edsr' and opt.edsr_resident:
+                return EDSR_TILE_BATCH
             v = 7 if (opt.dense_direct == 0 if opt.mode.trunk is None else opt.dense_direct != 1) else 8
         return min(int(v or 1), 16)
 

@@ -138,6 +138,9 @@ typedef struct ciaosr_options {
     int csa_attn_v16;       /* _f32 cs_attn, composed tail, 64 channels: 0 (default) = attn.V on the four diagonal tap blocks
                              * (csa_attn_v4_f32.hip: K = 4 (Hp/2+3)(Wp/2+3) instead of 16 L; where the logit matrix -- under csa_block_mb: a band's -- is under 2 GiB);
                              * 1 = the 16C route of 16 offset columns.  Same products summed in another order */
+    int edsr_resident;      /* EDSR trunk, 0 or 1 (added in front of swin_h16; version 260), read by ciaosr_edsr_forward_batch_f32 and its two
+                             * companions alone: 0 (default) = the images one after the other through ciaosr_edsr_forward_f32; 1 = the body
+                             * convolutions of the whole batch on the halo-resident fp32 kernel where the route rule below that entry holds */
     int swin_h16;           /* SwinIR trunk, 0 or 1 (added in front of csa_block_mb, which stays the last field; version 240); READ ABOVE THE ABI (as query_grid_w is produced there): no entry point changes what it runs
                              * on it.  0 (default) = ciaosr_swinir_forward_f32 in every precision mode; 1 = the callers (PackedSwinIR, the
                              * restorer's tile loop) take ciaosr_swinir_forward_batch_f16 in the modes whose trunk element type is half
@@ -554,6 +557,28 @@ int ciaosr_rdn_forward_batch_f16(const float* x_nchw, int B, int H, int W, const
 size_t ciaosr_edsr_workspace_bytes(int H, int W, const ciaosr_edsr_weights_t* w);
 int ciaosr_edsr_forward_f32(const float* x_nchw, int H, int W, const ciaosr_edsr_weights_t* w, float* feat_hwc,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* B images of one size through the EDSR trunk in one call: x_bchw [B][3][H][W] -> feat_bhwc [B][H][W][mid_channels]; fp32 in every
+ * precision mode.  Two routes (ciaosr_edsr_route_code names the one a call takes and launches nothing):
+ *   0, per image: the B images one after the other through ciaosr_edsr_forward_f32's launches, bitwise that entry's result.  Always with
+ *      opt == NULL or opt->edsr_resident == 0.
+ *   1, resident: conv_first per image; then every body convolution and conv_after_body as ONE launch of the halo-resident fp32 kernel
+ *      (12x12-pixel workgroups, dense_f32.hip; profiler tag enc_edsr_resident) for the whole batch: 2 num_blocks + 1 launches per call
+ *      instead of per image.  Each image is computed by the workgroups, in the order, of a B = 1 call: bitwise equal to it.  Same products
+ *      as route 0 in another summation order.  Epilogues in fp32, every operation rounded on its own (no FMA): conv1 max(sum + bias, 0);
+ *      conv2 x + res_scale * (sum + bias), in place on x; conv_after_body first + 1 * (sum + bias).
+ * Route 1 applies iff ALL of: opt && opt->edsr_resident == 1; mid_channels == 64; num_blocks >= 1; every conv1[i], conv2[i] and
+ * conv_after_body has `frag` (ciaosr_pack_fragments_f32 of its [64][9 * 64] matrix); the map has at least opt->dense_min_tiles (0 = 128)
+ * tiles of 12x12 pixels; one image's [H W][128] fp32 buffer is under 4 GiB - 256 B (32-bit buffer offsets).  A batch whose [B H W][128]
+ * buffer is not runs as passes of as many images as fit.
+ * ciaosr_edsr_route_code: < 0 = the error the call would return for these arguments (pointers apart); else bits 0-7 = the route, and
+ * bits 8.. = the images per pass when route 1 runs the batch in more than one pass (0 = one pass of B).
+ * ciaosr_edsr_workspace_bytes_batch: what the call checks its workspace against (0 on a bad argument); equal to
+ * ciaosr_edsr_workspace_bytes for route 0. */
+size_t ciaosr_edsr_workspace_bytes_batch(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt /*host, may be NULL*/);
+int ciaosr_edsr_route_code(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt /*host, may be NULL*/);
+int ciaosr_edsr_forward_batch_f32(const float* x_bchw, int B, int H, int W, const ciaosr_edsr_weights_t* w, float* feat_bhwc,
+                                  const ciaosr_options_t* opt /*host, NULL = defaults*/, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 /* ---- SwinIR trunk: LocalImplicitSRSWINIR.gen_feature (net:475-525 over swinir_net.py) --------------------------
  * Token maps are [Hp*Wp][ld] with ld = embed_dim rounded up to 64 (Hp, Wp = H, W reflect-padded to window multiples,
