@@ -157,6 +157,7 @@ SIGNATURES = {
     'ciaosr_head_scene_bytes': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I, _O]),
     'ciaosr_head_prepare_workspace_bytes': (_S, [_I, _I, C.POINTER(HeadWeightsT), _I, _O]),
     'ciaosr_head_query_workspace_bytes': (_S, [C.POINTER(HeadSceneT), C.POINTER(HeadWeightsT), _I, _O]),
+    'ciaosr_head_query_flag_offset': (_I, [C.POINTER(HeadSceneT), C.POINTER(HeadWeightsT), _I, _O, C.POINTER(_S)]),
     **{'ciaosr_head_prepare_' + sfx: (_I, [_P, _I, _I, C.POINTER(HeadWeightsT), C.POINTER(CsAttnWeightsT), _I, _O, _P, _S,
                                           C.POINTER(HeadSceneT), _P, _S, _P]) for sfx in ('f32', 'bf16', 'f16')},
     **{'ciaosr_head_query_' + sfx: (_I, [_P, _S, C.POINTER(HeadSceneT), C.POINTER(HeadWeightsT), _P, _P, _P, _I, _I, _P, _O, _P, _S, _P])
@@ -191,6 +192,13 @@ SIGNATURES = {
     'ciaosr_view_many_workspace_offset': (_S, [C.POINTER(_I), _I, _I, _I]),
     'ciaosr_view_count_many_i32': (_I, [C.POINTER(C.c_double), C.POINTER(_I), _I, _P, _I, _P, _P, _S, _P]),
     'ciaosr_view_select_f32': (_I, [C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P, _P]),
+    'ciaosr_view_block_blocks': (_I, []),
+    'ciaosr_view_blocks_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_view_count_blocks_i32': (_I, [C.POINTER(C.c_double), _I, _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_view_blocks_many_workspace_bytes': (_S, [C.POINTER(_I), _I, _I]),
+    'ciaosr_view_blocks_many_workspace_offset': (_S, [C.POINTER(_I), _I, _I, _I]),
+    'ciaosr_view_count_blocks_many_i32': (_I, [C.POINTER(C.c_double), C.POINTER(_I), _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_view_select_blocks_f32': (_I, [C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P, _P]),
     'ciaosr_view_blend_f32': (_I, [_P, _P, _I, _P, _P, _I, _P]),
     'ciaosr_view_finalize_f32': (_I, [_P, _P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P]),
     'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),

@@ -603,6 +603,22 @@ extern "C" size_t ciaosr_head_query_workspace_bytes(const ciaosr_head_scene_t* d
     return head_split_bytes(p, scene_layout(r)).n[kQuery];
 }
 
+// Where head_carve puts chain_flag in the query workspace of this call: the same takes on an arena that starts at address 0
+extern "C" int ciaosr_head_query_flag_offset(const ciaosr_head_scene_t* desc, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt,
+                                             size_t* offset) {
+    CIAOSR_CHECK_ARG(offset);
+    HeadPlan p; HeadRoute r;
+    HEAD_RUN(scene_open(desc, w, Q, -1, opt, &p, &r));
+    const int step = r.fused ? p.qcf : p.qc;
+    const int nq_last = (int)(Q - ((long)(Q - 1) / step) * step);                 // the launch pair whose flag is left behind
+    if (!r.fused || r.kv(p, nq_last) != kHeadChain) return CIAOSR_ERR_UNSUPPORTED;
+    Arena ws(nullptr, ~(size_t)0);
+    Arena* const ar[3] = {nullptr, nullptr, &ws};
+    const HeadBuffers b = head_carve_split(p, scene_layout(r), ar);
+    *offset = (size_t)reinterpret_cast<uintptr_t>(b.chain_flag);
+    return CIAOSR_OK;
+}
+
 static int head_query(const void* scene, size_t scene_bytes, const ciaosr_head_scene_t* desc, const ciaosr_head_weights_t* w, const float* x_lr_nchw,
                       const float* coord, const float* cell, int Q, int chunk, float* rgb, const ciaosr_options_t* opt, void* workspace,
                       size_t workspace_bytes, void* stream_, Prec prec) {

@@ -38,6 +38,17 @@ class Scene:
         """(H, W) of the LR map."""
         return self.desc.H, self.desc.W
 
+    @property
+    def chained(self):
+        """Whether the scene's recorded route (ciaosr_head_route_code, bit 8) answers queries with the chained 16-bit kv kernel: the
+        kernel whose flag `PackedHead.query(..., return_flag=True)` returns, and the one a view's block list is made for."""
+        return route_chained(self.desc.route)
+
+
+def route_chained(code):
+    """Bit 8 of a ciaosr_head_route_code: the chained 16-bit kv kernel.  A negative code (a refusal) is no route at all."""
+    return code >= 0 and bool((code >> 8) & 1)
+
 
 class PackedHead:
     """Packed (device-order, contiguous fp32) copies of a LocalImplicitSRNet head's weights."""
@@ -408,9 +419,13 @@ class PackedHead:
         return Scene(buf, desc, opt, int(q_plan), keys, ev)
 
     @torch.no_grad()
-    def query(self, scene, x_lr_chw, coord, cell, chunk=None):
+    def query(self, scene, x_lr_chw, coord, cell, chunk=None, return_flag=False):
         """The per-query half of `forward` on a Scene: x_lr [3,H,W] or None, coord/cell [Q,2] -> rgb [Q,3].  Any Q, any number of times;
-        raises CiaoSRHipError when a weight the scene was built from has changed since."""
+        raises CiaoSRHipError when a weight the scene was built from has changed since.  `return_flag`: -> (rgb, flag), flag a 1-element
+        int32 device tensor cloned from the workspace on the query's stream (nothing synchronises until the caller reads it): 1 when the
+        chained 16-bit kv kernel met a row tile of 8 consecutive queries outside its 4 x 4 window of key pixels and the gated 128-row
+        kernel redid the launch, else 0.  A query of more than one launch pair (Q > 2^20) shows its LAST pair's flag only.
+        CiaoSRHipError (unsupported) when the scene's route has no chained kv kernel: `Scene.chained` tells beforehand."""
         if scene.keys != self._weights_key():
             raise _lib.CiaoSRHipError('stale scene: a weight of the head or of cs_attn changed after prepare; encode again')
         coord = coord.contiguous().float()
@@ -425,9 +440,14 @@ class PackedHead:
         nbytes = _lib.load().ciaosr_head_query_workspace_bytes(C.byref(scene.desc), C.byref(st), Q, opt.c_arg())
         ws = hip_ops.workspace(nbytes, coord.device)
         rgb = torch.empty(Q, 3, dtype=torch.float32, device=coord.device)
+        off = C.c_size_t(0)
+        if return_flag:                                                 # refused before anything is launched
+            _lib.call('ciaosr_head_query_flag_offset', C.byref(scene.desc), C.byref(st), Q, opt.c_arg(), C.byref(off))
         _lib.call('ciaosr_head_query_' + opt.suffix, hip_ops.ptr(scene.buf), scene.buf.numel(), C.byref(scene.desc), C.byref(st),
                   hip_ops.ptr(x_lr_chw), hip_ops.ptr(coord), hip_ops.ptr(cell), Q, int(chunk or 0), hip_ops.ptr(rgb), opt.c_arg(),
                   hip_ops.ptr(ws), ws.numel(), hip_ops.stream_ptr())
+        if return_flag:
+            return rgb, ws[off.value:off.value + 4].view(torch.int32).clone()
         return rgb
 
     @torch.no_grad()

@@ -308,8 +308,54 @@ def view_select(m, hv, wv, frame, index, n_tiles, ws, n):
     return q_index, coord, cell
 
 
+def view_count_blocks(m, hv, wv, tiles):
+    """`view_count` with the output grid cut into blocks 4 wide x 2 high (include/ciaosr_hip.h, "Members in blocks"): -> (counts
+    [n_tiles, 2] int32 on the device, rows (members, live blocks), ws); `ws` is what `view_select_blocks` places a tile's blocks with."""
+    require_gpu(tiles)
+    n_tiles = tiles.shape[0]
+    lib = _lib.load()
+    ws = workspace(lib.ciaosr_view_blocks_workspace_bytes(hv, wv, n_tiles), tiles.device, slot='view_blocks')
+    counts = torch.empty(n_tiles, 2, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_view_count_blocks_i32', _m6(m), hv, wv, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws
+
+
+def view_count_blocks_many(ms, sizes, tiles):
+    """`view_count_blocks` for a list of views, as `view_count_many`: -> (counts [V, n_tiles, 2] int32 on the device, ws, offsets);
+    counts[v] and `ws[offsets[v]:]` are bitwise what `view_count_blocks` gives for the view alone."""
+    require_gpu(tiles)
+    n_tiles, n_views = tiles.shape[0], len(ms)
+    if n_views < 1 or len(sizes) != n_views:
+        raise ValueError(f'view_count_blocks_many: {n_views} matrices, {len(sizes)} sizes')
+    lib = _lib.load()
+    flat = [v for m in ms for v in _m6(m)]
+    m_arr = (C.c_double * (6 * n_views))(*flat)
+    s_arr = (C.c_int * (2 * n_views))(*[int(v) for s in sizes for v in (s[0], s[1])])
+    ws = workspace(lib.ciaosr_view_blocks_many_workspace_bytes(s_arr, n_views, n_tiles), tiles.device, slot='view_blocks_many')
+    offsets = [lib.ciaosr_view_blocks_many_workspace_offset(s_arr, n_views, n_tiles, v) for v in range(n_views)]
+    counts = torch.empty(n_views, n_tiles, 2, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_view_count_blocks_many_i32', m_arr, s_arr, n_views, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws, offsets
+
+
+def view_select_blocks(m, hv, wv, frame, index, n_tiles, ws, n_blocks):
+    """The `n_blocks` live blocks (view_count_blocks' number) of tile `index` = `frame`, in increasing block index, eight entries each in
+    the order the chained 16-bit head kernel walks a row tile: (q_index [8 n_blocks] int32, coord, cell [8 n_blocks, 2]).  A pad -- no
+    member of the tile, or outside the grid -- has q_index -1 and the coordinate of its block's first member; `view_blend` skips it.
+    No grid hint is registered: eight consecutive entries are one row tile."""
+    n = 8 * n_blocks
+    q_index = torch.empty(n, dtype=torch.int32, device=ws.device)
+    coord = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    _window_width.pop((coord.data_ptr(), n), None)          # the allocator may hand out the address of a dead grid's coordinates
+    _lib.call('ciaosr_view_select_blocks_f32', _m6(m), hv, wv, _i4(frame), index, n_tiles, ptr(ws), ws.numel(), n_blocks, ptr(q_index),
+              ptr(coord), ptr(cell), stream_ptr())
+    return q_index, coord, cell
+
+
 def view_blend(E, Wt, q_index, rgb):
-    """E[:, q_index[s]] += rgb[s], Wt[q_index[s]] += 1 (E [3, Q], Wt [Q], rgb [n, 3]); q_index None: s itself."""
+    """E[:, q_index[s]] += rgb[s], Wt[q_index[s]] += 1 (E [3, Q], Wt [Q], rgb [n, 3]); q_index None: s itself.  An index outside
+    [0, Q) -- the -1 of a block list's pad -- is skipped."""
     require_gpu(E, Wt, q_index, rgb)
     if E.shape != (3, Wt.shape[0]) or rgb.dim() != 2 or rgb.shape[1] != 3 or (q_index is not None and q_index.shape != (rgb.shape[0],)):
         raise ValueError(f'view_blend: E {tuple(E.shape)}, Wt {tuple(Wt.shape)}, rgb {tuple(rgb.shape)} do not fit together')

@@ -131,14 +131,30 @@ class LocalImplicitSRNet(nn.Module):
         return EncodedFeatures([self._head.prepare(None, options, q_plan, feature_hwc=feats[b]) for b in range(x.shape[0])], x, options)
 
     @torch.no_grad()
-    def render(self, enc, coord, cell):
+    def render(self, enc, coord, cell, return_flags=False):
         """`forward(x, coord, cell, test_mode=True)` from an `encode` result: coord/cell [B,Q,2] (or [Q,2], shared by the batch) -> [B,Q,3],
-        for any Q, any number of times."""
-        outs = []
+        for any Q, any number of times.  `return_flags`: -> ([B,Q,3], [B] int32 on the device), per item the flag of
+        `PackedHead.query(..., return_flag=True)` (scenes on the chained 16-bit kv kernel only)."""
+        outs, flags = [], []
         for b, scene in enumerate(enc.scenes):
             cq, cl = (coord, cell) if coord.dim() == 2 else (coord[b], cell[b])
-            outs.append(self._head.query(scene, enc.x[b], cq, cl, self.eval_bsize))
+            out = self._head.query(scene, enc.x[b], cq, cl, self.eval_bsize, return_flag=return_flags)
+            if return_flags:
+                out, flag = out
+                flags.append(flag)
+            outs.append(out)
+        if return_flags:
+            return torch.stack(outs, 0), torch.cat(flags)
         return torch.stack(outs, 0)
+
+    def scene_chained(self, h, w, q_plan, options=None):
+        """Whether a scene of an h x w LR map planned for `q_plan` queries under `options` would answer queries with the chained 16-bit
+        kv kernel (ciaosr_head_route_code, bit 8; `Scene.chained` of the scene once built).  Launches nothing."""
+        from .head_hip import route_chained
+        try:
+            return route_chained(self._head.route_code(h, w, q_plan, self.effective_options(options)))
+        except CiaoSRHipError:
+            return False
 
     def effective_options(self, options=None):
         """The hip_ops.Options a call on THIS generator really runs with (subclasses may narrow what they accept)."""

@@ -480,19 +480,26 @@ class CiaoSR(BasicRestorer):
             enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
         gen = self.generator
         n_q = hv * wv
+        blocks = self._view_blocks(enc, m, frames)
         preds = []
         for b in range(nb):
-            counts, ws = hip_ops.view_count(m, hv, wv, enc.view_tiles)
-            counts = counts.tolist()                                    # the one synchronisation
+            if blocks:                                                  # per tile (members, live blocks of 4 x 2 output pixels)
+                counts, ws = hip_ops.view_count_blocks(m, hv, wv, enc.view_tiles)
+                counts = counts.tolist()                                # the one synchronisation
+            else:
+                counts, ws = hip_ops.view_count(m, hv, wv, enc.view_tiles)
+                counts = [(n, 0) for n in counts.tolist()]              # the one synchronisation
             E = torch.zeros(3, n_q, dtype=torch.float32, device=x.device)
             Wt = torch.zeros(n_q, dtype=torch.float32, device=x.device)
-            for k, (frame, n) in enumerate(zip(frames, counts)):        # the reference's blend order
+            for k, (frame, (n, n_blk)) in enumerate(zip(frames, counts)):        # the reference's blend order
                 if n == 0:
                     continue
                 tile_scene = enc.cache.get((b, (frame[0], frame[1]) if tile else None))
                 if n == n_q:                                            # the tile owns the whole view: a grid, known to the head as one
                     q_index = None
                     coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frame, x.device)
+                elif blocks:                                            # row tiles of the chained 16-bit kernel, pads at q_index -1
+                    q_index, coord, cell = hip_ops.view_select_blocks(m, hv, wv, frame, k, len(frames), ws, n_blk)
                 else:
                     q_index, coord, cell = hip_ops.view_select(m, hv, wv, frame, k, len(frames), ws, n)
                 hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
@@ -503,12 +510,26 @@ class CiaoSR(BasicRestorer):
             return metrics_hip.tensor2img_u8(out)
         return out
 
+    def _view_blocks(self, enc, m, frames):
+        """Whether the partial member lists of view `m` are selected in 4 x 2 blocks (`hip_ops.view_select_blocks`): `test_cfg.view_blocks`
+        is on, `scene.view_blocks_fit(m)` holds, and the route the tile scenes are planned under runs the chained 16-bit kv kernel --
+        the one kernel that walks 8 consecutive list entries as a row tile.  Elsewhere (fp32, f16x3, bf16x3, `head_route` bits that
+        disable the chain) the pads would only cost queries and the index-order list stays.  Pure host work; needs `enc.max_scale`."""
+        from . import scene as sc
+        if not self.test_cfg.get('view_blocks', False) or not sc.view_blocks_fit(m):
+            return False
+        th, tw = frames[0][2], frames[0][3]                             # every frame has the first one's size
+        q_plan = max(1, round(th * enc.max_scale) * round(tw * enc.max_scale))
+        return self.generator.scene_chained(th, tw, q_plan, enc.options)
+
     # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------
     def _plan_many(self, enc, targets, count_views=True):
         """Everything `render_many` / `prefetch` know before a scene is touched.  Validates every target (the single calls' ValueErrors,
         before any device work), sets `enc.max_scale` where it is open, counts the members of ALL views in one `view_count_many` and
         one device-to-host copy (none for grids alone) -- per call, not per batch item: the counts do not depend on the item.
-        -> dict: recs (per target), origins {tile index: (y0, x0) | None}, union, users, frames, ws, offsets."""
+        -> dict: recs (per target), origins {tile index: (y0, x0) | None}, union, users, frames.  A view's record holds its counts per
+        tile, `blocks` (selected in 4 x 2 blocks, `_view_blocks`; then also `n_blocks` per tile) and `ws`, its slice of the count's
+        workspace for the select."""
         from . import scene as sc
         x = enc.x
         h, w = x.shape[-2:]
@@ -534,7 +555,7 @@ class CiaoSR(BasicRestorer):
                 raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
         if enc.max_scale is None:
             enc.max_scale = need
-        plan = dict(recs=recs, frames=frames, ws=None, offsets=None, origins={})
+        plan = dict(recs=recs, frames=frames, origins={})
         views = [r for r in recs if r['kind'] == 'view']
         if views and not count_views:                                   # one frame: every view is its only user
             for r in views:
@@ -543,10 +564,28 @@ class CiaoSR(BasicRestorer):
         elif views:
             if enc.view_tiles is None:                                  # uploaded once per encoded image
                 enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
-            counts, plan['ws'], plan['offsets'] = hip_ops.view_count_many([r['m'] for r in views], [r['size'] for r in views], enc.view_tiles)
-            counts = counts.tolist()                                    # the one synchronisation of the call
-            for v, r in enumerate(views):
-                r['v'], r['counts'] = v, counts[v]
+            n_t = len(frames)
+            for r in views:
+                r['blocks'] = self._view_blocks(enc, r['m'], frames)
+            plain, blk = [r for r in views if not r['blocks']], [r for r in views if r['blocks']]
+            flat = []
+            if plain:
+                counts, ws, offsets = hip_ops.view_count_many([r['m'] for r in plain], [r['size'] for r in plain], enc.view_tiles)
+                flat.append(counts.flatten())
+                for v, r in enumerate(plain):
+                    r['ws'] = ws[offsets[v]:]
+            if blk:                                                     # per tile (members, live blocks of 4 x 2 output pixels)
+                counts, ws, offsets = hip_ops.view_count_blocks_many([r['m'] for r in blk], [r['size'] for r in blk], enc.view_tiles)
+                flat.append(counts.flatten())
+                for v, r in enumerate(blk):
+                    r['ws'] = ws[offsets[v]:]
+            flat = (flat[0] if len(flat) == 1 else torch.cat(flat)).tolist()          # the one synchronisation of the call
+            for v, r in enumerate(plain):
+                r['counts'] = flat[v * n_t:(v + 1) * n_t]
+            base = len(plain) * n_t
+            for v, r in enumerate(blk):
+                both = flat[base + 2 * v * n_t:base + 2 * (v + 1) * n_t]
+                r['counts'], r['n_blocks'] = both[0::2], both[1::2]
             plan['origins'].update({k: ((f[0], f[1]) if tile else None) for k, f in enumerate(frames)})
         touched = []
         for r in recs:
@@ -659,7 +698,7 @@ class CiaoSR(BasicRestorer):
         if one_frame:
             return [self.render(enc, size=(r['ht'], r['wt']), window=r['win'], as_u8=as_u8) if r['kind'] == 'grid' else
                     self.render_view(enc, r['m'], r['size'], r['fill'], as_u8=as_u8) for r in recs]
-        frames, ws, offsets = plan['frames'], plan['ws'], plan['offsets']
+        frames = plan['frames']
         walk = [(k, plan['origins'][k]) for k in plan['union']]
         preds = [[] for _ in recs]
         for b in range(nb):
@@ -688,8 +727,10 @@ class CiaoSR(BasicRestorer):
                         if n == hv * wv:                                # the tile owns the whole view: a grid, known to the head as one
                             q_index = None
                             coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frames[k], x.device)
+                        elif r['blocks']:                               # row tiles of the chained 16-bit kernel, pads at q_index -1
+                            q_index, coord, cell = hip_ops.view_select_blocks(m, hv, wv, frames[k], k, len(frames), r['ws'], r['n_blocks'][k])
                         else:
-                            q_index, coord, cell = hip_ops.view_select(m, hv, wv, frames[k], k, len(frames), ws[offsets[r['v']]:], n)
+                            q_index, coord, cell = hip_ops.view_select(m, hv, wv, frames[k], k, len(frames), r['ws'], n)
                         hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
             for i, r in enumerate(recs):
                 E, Wt = acc[i]

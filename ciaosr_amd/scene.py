@@ -2,9 +2,9 @@
 
 Pure Python, no GPU: the window planner (which LR tiles a window of the HR grid touches, and which part of each), the least-recently-used
 cache that bounds the bytes of tile scenes kept alive, the record `CiaoSR.encode` returns, and the affine views of
-`CiaoSR.render_view` (their matrices, cells and tile lists), and for `CiaoSR.render_many` the target records `Grid` / `View` and
-the tile-major plan (`plan_union`, `group_missing`).  The device work is in `PackedHead.prepare` / `query` (head_hip.py),
-`hip_ops.make_coord_cell_window` and the `hip_ops.view_*` wrappers.
+`CiaoSR.render_view` (their matrices, cells and tile lists, and `view_blocks_fit`: when a cut view may be queried in 4 x 2 blocks),
+and for `CiaoSR.render_many` the target records `Grid` / `View` and the tile-major plan (`plan_union`, `group_missing`).  The device
+work is in `PackedHead.prepare` / `query` (head_hip.py), `hip_ops.make_coord_cell_window` and the `hip_ops.view_*` wrappers.
 """
 import ctypes
 import math
@@ -141,6 +141,16 @@ def view_cell(matrix, th, tw):
 def view_max_scale(matrix):
     """Output pixels per LR pixel along the finer of the two LR axes: what `encode`'s max_scale is set to by a first view render."""
     return max(1.0 / math.hypot(matrix[0], matrix[1]), 1.0 / math.hypot(matrix[3], matrix[4]))
+
+
+def view_blocks_fit(matrix):
+    """Whether every 4 wide x 2 high block of output pixels of the view is a row tile the chained 16-bit head kernel answers on its own:
+    3 |m_yx| + |m_yy| <= 2 and 3 |m_xx| + |m_xy| <= 2.  The eight pixel centres of a block span 3 steps of u and 1 of v, so at most
+    that many LR pixels along each LR axis; the key samples sit within the same +-0.5 LR pixel of their query, so keys that lie no more
+    than 2 apart round into at most 4 distinct rows (columns): the kernel's 4 x 4 gather window.  True at any angle from
+    zoom 1.6 up (the worst angle is atan(1 / 3): sqrt(10) / zoom <= 2).  What `test_cfg.view_blocks` asks before it selects in blocks."""
+    m = [float(v) for v in matrix]
+    return 3.0 * abs(m[1]) + abs(m[0]) <= 2.0 and 3.0 * abs(m[4]) + abs(m[3]) <= 2.0
 
 
 def plan_view(h, w, tile=None, overlap=None, any_scale=False):

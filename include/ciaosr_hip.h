@@ -459,6 +459,14 @@ int ciaosr_head_route_code(int H, int W, const ciaosr_head_weights_t* w, int Q, 
 size_t ciaosr_head_scene_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt /*host, may be NULL*/);
 size_t ciaosr_head_prepare_workspace_bytes(int H, int W, const ciaosr_head_weights_t* w, int q_plan, const ciaosr_options_t* opt /*host, may be NULL*/);
 size_t ciaosr_head_query_workspace_bytes(const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt /*host, may be NULL*/);
+/* Where a query of Q queries keeps the flag of the chained 16-bit kv kernel: *offset = bytes from the start of the query workspace to one
+ * int32.  Each launch pair of a query (2^20 queries) clears it, and the chained kernel sets it to 1 when a row tile of 8 consecutive
+ * queries does not fit its 4 x 4 window of key pixels -- the whole launch is then redone by the gated 128-row kernel.  After a query
+ * the int holds the flag of its LAST launch pair only (one pair for Q <= 2^20).  Read it on the query's stream before the workspace is
+ * used again.  CIAOSR_ERR_UNSUPPORTED: the scene's route has no chained kv kernel (fp32, f16x3, head_route bits), nothing is ever
+ * written there; the other refusals are ciaosr_head_query_workspace_bytes' (which returns 0 for them).  Launches nothing, carves nothing. */
+int ciaosr_head_query_flag_offset(const ciaosr_head_scene_t* desc /*host*/, const ciaosr_head_weights_t* w, int Q, const ciaosr_options_t* opt /*host, may be NULL*/,
+                                  size_t* offset /*host, out*/);
 int ciaosr_head_prepare_f32(const float* feat_hwc, int H, int W, const ciaosr_head_weights_t* w, const ciaosr_csattn_weights_t* csattn, int q_plan,
                             const ciaosr_options_t* opt /*host, NULL = defaults*/, void* scene, size_t scene_bytes, ciaosr_head_scene_t* desc /*host, out*/,
                             void* workspace, size_t workspace_bytes, void* stream);
@@ -677,8 +685,34 @@ int ciaosr_view_count_many_i32(const double* m /*host [n_views][6]*/, const int*
  * cell [n][2] in the tile's frame, n = counts[tile_index] (nothing is written past n). */
 int ciaosr_view_select_f32(const double* m /*host [6]*/, int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles,
                            const void* workspace, size_t workspace_bytes, int n, int* q_index, float* coord, float* cell, void* stream);
+/* Members in blocks.  The output grid is cut into blocks 4 wide x 2 high, row-major over ceil(Hv / 2) x ceil(Wv / 4) blocks: block
+ * b = by * ceil(Wv / 4) + bx holds the output pixels (2 by + (e >> 2), 4 bx + (e & 3)), e = 0 .. 7 -- the eight queries the chained
+ * 16-bit head kernel walks as one row tile on a grid.  A block with at least one member of a tile is a live block of that tile.
+ * count_blocks: counts [n_tiles][2] (device) = (members, live blocks) of every tile; the member count is ciaosr_view_count_i32's.  One
+ * thread per block, ciaosr_view_block_blocks() blocks per workgroup; workspace (ciaosr_view_blocks_workspace_bytes, 4-byte aligned):
+ * per tile two rows of one int per workgroup, the exclusive scans of the member and of the live-block counts.  The _many form is
+ * ciaosr_view_count_many_i32's scheme (views by value, groups of ciaosr_view_count_many_max_views(), counts [n_views][n_tiles][2], view
+ * v's single-view workspace at ciaosr_view_blocks_many_workspace_offset).
+ * select_blocks: the live blocks of tile `tile_index` in increasing b, 8 entries each, entry e of a block at list position 8 r + e
+ * (r: the block's rank among the tile's live blocks): q_index [8 n_blocks], coord and cell [8 n_blocks][2], n_blocks = counts[tile][1].
+ * A member entry holds its q and exactly ciaosr_view_select_f32's coord and cell for that q.  Any other entry -- a pixel that is no
+ * member of the tile, or lies outside the output grid -- is a PAD: q_index = -1, coord and cell copied from the block's first member
+ * in entry order (so a pad adds no key pixel to the row tile); ciaosr_view_blend_f32 skips it.  The list can be longer than Hv Wv
+ * (small odd grids).  A row tile of the list fits the chained kernel's 4 x 4 window of key pixels for every translation iff
+ * 3 |m_yx| + |m_yy| <= 2 and 3 |m_xx| + |m_xy| <= 2: the caller's test, nothing here depends on it. */
+int ciaosr_view_block_blocks(void);
+size_t ciaosr_view_blocks_workspace_bytes(int Hv, int Wv, int n_tiles);
+int ciaosr_view_count_blocks_i32(const double* m /*host [6]*/, int Hv, int Wv, const int* tiles, int n_tiles, int* counts, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+size_t ciaosr_view_blocks_many_workspace_bytes(const int* sizes /*host [n_views][2]*/, int n_views, int n_tiles);
+size_t ciaosr_view_blocks_many_workspace_offset(const int* sizes /*host [n_views][2]*/, int n_views, int n_tiles, int view);
+int ciaosr_view_count_blocks_many_i32(const double* m /*host [n_views][6]*/, const int* sizes /*host [n_views][2]*/, int n_views,
+                                      const int* tiles, int n_tiles, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_view_select_blocks_f32(const double* m /*host [6]*/, int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles,
+                                  const void* workspace, size_t workspace_bytes, int n_blocks, int* q_index, float* coord, float* cell,
+                                  void* stream);
 /* blend: E[c][q_index[s]] += rgb[s][c], Wt[q_index[s]] += 1 for s < n; E [3][Q], Wt [Q].  q_index = NULL: s itself (a tile that owns the
- * whole view).  An index may appear once per call at most; one outside [0, Q) is skipped. */
+ * whole view; then n <= Q).  An index may appear once per call at most; one outside [0, Q) -- a pad of a block list -- is skipped. */
 int ciaosr_view_blend_f32(float* E, float* Wt, int Q, const int* q_index /*may be NULL*/, const float* rgb, int n, void* stream);
 /* finalize: out_q3[q][c] = E[c][q] / Wt[q] where Wt[q] > 0 (ciaosr_denorm_clamp_f32's input layout); elsewhere the value that
  * ciaosr_denorm_clamp_f32 with mean3 / std3 turns into fill3[c] (in [0, 1], the output's space) -- exactly, whenever some fp32 value

@@ -14,6 +14,8 @@ largest --scale; without --scale the largest view ZOOM).  Every `--view` (repeat
 ciaosr_amd.scene.view_matrix((CY, CX), ZOOM, ANGLE, (H, W)): an H x W picture whose centre looks at LR position (CY, CX) with ZOOM output
 pixels per LR pixel, turned by ANGLE degrees (positive: the picture turns clockwise), written to DIR/<image name>_view<k>.png, k = 0,
 1, ... in command-line order; one `--size` per `--view`, or a single one for all of them.  Pixels outside the image are black.
+`--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
+queried in 4 x 2 blocks of output pixels, which keeps the head on its chained kernel; other precisions are unaffected.
 """
 import argparse
 import os
@@ -36,6 +38,8 @@ def parse_args(argv=None):
     p.add_argument('--size', type=int, nargs=2, action='append', default=[], metavar=('H', 'W'), help='output size of each --view')
     p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
+    p.add_argument('--view-blocks', action='store_true',
+                   help='test_cfg.view_blocks: the 16-bit modes select a cut view\'s members in 4 x 2 blocks of output pixels (default off)')
     p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM)')
     p.add_argument('--out', required=True, help='output directory')
     args = p.parse_args(argv)
@@ -65,6 +69,8 @@ def main(argv=None):
         args.checkpoint = cfg.get('test_checkpoint_path')
     if args.precision:
         cfg.test_cfg['precision'] = args.precision
+    if args.view_blocks:
+        cfg.test_cfg['view_blocks'] = True
     if cfg.test_cfg.get('tile', None):
         cfg.test_cfg['tile_any_scale'] = True
     dev = torch.device('cuda', torch.cuda.current_device())

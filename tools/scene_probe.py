@@ -12,7 +12,11 @@ whole-image test_cfg, scene planned for x4), per precision, three legs alternati
 synchronisations: an angle-0 view and a 30-degree view of `--view-size` (768) squared about the image centre at zoom x4, and the window
 render of that size from the same scene.  Per leg: wall time (mean, min, max over `--reps` rounds after two warm-up rounds, profiler
 off), and from one more round under hip_ops.profile the device time of the view kernels (count + select + blend + finalize), of the
-coordinate kernels and of the head query (every other launch of the call but denorm_clamp).
+coordinate kernels and of the head query (every other launch of the call but denorm_clamp).  Two more legs alternate with these: the
+30-degree view with `test_cfg.view_blocks` off (the leg above, named again) and on.  For them a second table (with `--out` also written
+to that file: profiles/view_blocks.txt) holds per precision and leg the wall time, the head query's device time, the pad share
+8 * blocks / members - 1 of the block list, and the flag of the leg's head query (`PackedHead.query(..., return_flag=True)` on the
+list the leg selects: 1 = the chained 16-bit kernel gave the launch up to the gated 128-row kernel; n/a where no chained kernel runs).
 
 `--legs many` (profiles/render_many.txt, with `--out`) is the tiled image of bench.py -- LR 1356 x 2040, tile 192 / overlap 32,
 `tile_any_scale`: 9 x 13 = 117 tiles -- rendered at x2, x3.3 and x4 (full grids) from one encode, per precision and for two scene caches
@@ -42,7 +46,7 @@ ap.add_argument('--view-size', type=int, default=768)
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help='tree whose package and library run')
 ap.add_argument('--parent-root', default=None, help='--legs many: a built checkout of the parent commit for leg (a)')
 ap.add_argument('--worker', action='store_true', help='--legs many: serve leg (a) rounds on stdin / stdout (the parent-tree child)')
-ap.add_argument('--out', default=None, help='--legs many: also write the report to this file')
+ap.add_argument('--out', default=None, help='--legs many: also write the report to this file; --legs view: the view_blocks table')
 args = ap.parse_args()
 
 sys.path.insert(0, os.path.abspath(args.root))
@@ -82,8 +86,30 @@ def peak_of(fn, n=2):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
+def view_query_flag(enc, m, n, size, blocks):
+    """(flag, members, list length) of the head query a 30-degree leg makes: its member list of the one frame, selected as the leg does."""
+    frame = (0, 0, size, size)
+    tiles = torch.tensor([frame], dtype=torch.int32).to(dev)
+    scene = enc.cache.get((0, None))
+    if blocks:
+        counts, ws = hip_ops.view_count_blocks(m, n, n, tiles)
+        members, n_blk = counts.tolist()[0]
+        _, coord, cell = hip_ops.view_select_blocks(m, n, n, frame, 0, 1, ws, n_blk)
+    else:
+        counts, ws = hip_ops.view_count(m, n, n, tiles)
+        members = counts.tolist()[0]
+        _, coord, cell = hip_ops.view_select(m, n, n, frame, 0, 1, ws, members)
+    flag = 'n/a'
+    if scene.scenes[0].chained:
+        flag = str(int(model.generator.render(scene, coord, cell, return_flags=True)[1][0]))
+    return flag, members, coord.shape[0]
+
+
 def view_legs():
-    from ciaosr_amd.scene import view_matrix
+    from ciaosr_amd.scene import view_blocks_fit, view_matrix
+    report = [f'tools/scene_probe.py --legs view --reps {args.reps}: library version {_lib.load().ciaosr_version()}, '
+              f'{torch.cuda.get_device_name(0)}; the 30-degree view with test_cfg.view_blocks off and on, alternating with the other legs '
+              f'in one process (2 warm-up rounds, {args.reps} timed rounds)']
     size, n = int(args.sizes.split(',')[0]), args.view_size
     lq = synthetic_pair(size, size, 4)[0].to(dev)
     groups = (('view kernels', lambda k: k.startswith('view_') and k != 'view_coord_cell'),
@@ -93,8 +119,18 @@ def view_legs():
         model.test_cfg = dict(scale=4, precision=precision)
         enc = model.encode(lq)
         off = (size * 4 - n) // 2
+        m30 = view_matrix((size / 2, size / 2), 4.0, 30, (n, n))
+
+        def with_blocks():
+            model.test_cfg['view_blocks'] = True
+            try:
+                return model.render_view(enc, m30, (n, n))
+            finally:
+                model.test_cfg['view_blocks'] = False
+
         calls = {'view   0 deg': lambda: model.render_view(enc, view_matrix((size / 2, size / 2), 4.0, 0, (n, n)), (n, n)),
-                 'view  30 deg': lambda: model.render_view(enc, view_matrix((size / 2, size / 2), 4.0, 30, (n, n)), (n, n)),
+                 'view  30 deg': lambda: model.render_view(enc, m30, (n, n)),
+                 'view  30 blk': with_blocks,
                  'window render': lambda: model.render(enc, size=(size * 4, size * 4), window=(off, off, n, n))}
         a, b = calls['view   0 deg'](), calls['window render']()
         print(f'\n{size}x{size} LR, {precision}, {n} x {n} output at x4: angle-0 view against the window render: max |diff| = '
@@ -114,9 +150,22 @@ def view_legs():
             parts = ', '.join(f'{name} {sum(r["total_ms"] for kk, r in prof.items() if pick(kk)):8.3f} ms '
                               f'({sum(r["launches"] for kk, r in prof.items() if pick(kk))} launches)' for name, pick in groups)
             print(f'    {k:14s} wall mean {sum(v) / len(v):8.3f} ms  min {min(v):8.3f}  max {max(v):8.3f} | device: {parts}')
+            if k in ('view  30 deg', 'view  30 blk'):
+                blocks = k == 'view  30 blk' and view_blocks_fit(m30) and enc.cache.get((0, None)).scenes[0].chained
+                flag, members, length = view_query_flag(enc, m30, n, size, blocks)
+                head_ms = sum(r['total_ms'] for kk, r in prof.items() if groups[2][1](kk))
+                report.append(f'    {size}x{size} LR {precision:5s} {n} x {n} at x4, 30 deg, view_blocks {"on " if k.endswith("blk") else "off"}: '
+                              f'wall mean {sum(v) / len(v):8.3f} ms  min {min(v):8.3f}  max {max(v):8.3f} | head query {head_ms:8.3f} ms | '
+                              f'members {members}, list {length} ({"blocks" if blocks else "index order"}), pad share '
+                              f'{length / members - 1:.4f} | flag {flag}')
         del enc, calls
         hip_ops.release_workspaces()
         torch.cuda.empty_cache()
+    print()
+    print('\n'.join(report))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(report) + '\n')
 
 
 MANY_LR, MANY_SCALES = (1356, 2040), (2.0, 3.3, 4.0)
