@@ -206,6 +206,14 @@ SIGNATURES = {
     'ciaosr_tensor2img_u8': (_I, [_P, _I, _I, _P, _S, _P]),
     'ciaosr_psnr_ssim_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_psnr_ssim_u8': (_I, [_P, _S, _P, _S, _I, _I, _I, _I, _I, _P, _P, _S, _P]),
+    'ciaosr_png_rows_per_band': (_I, [_I, _I]),
+    'ciaosr_png_filter_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'ciaosr_deflate_huff_workspace_bytes': (_S, [_I]),
+    'ciaosr_deflate_huff_capacity_bytes': (_S, [_S, _I]),
+    'ciaosr_deflate_huff_u8': (_I, [_P, _P, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_capacity_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
 }
 
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)

@@ -1,0 +1,807 @@
+// PNG encoding of an 8-bit image on the device, opt-in through `test_cfg.gpu_png` (ciaosr_amd/png_hip.py): the scanline filter and a
+// literal-only dynamic-Huffman deflate coder.  The container (signature, IHDR, IDAT, IEND and the chunk CRCs) is put together by the host.
+//
+// Stage 1, png_filter_kernel: one workgroup owns a band of `rows_per_band` image rows.  Per row it evaluates the five PNG filters
+// (None, Sub, Up, Average, Paeth; 3 bytes per pixel, predecessors are the RAW pixels, the row above row 0 is zeros), picks the one whose
+// filtered bytes have the smallest sum of min(b, 256 - b) -- ties to the lowest number -- and writes the filter byte plus 3 W filtered
+// bytes in RGB order.  The same pass counts the band's 257-bin symbol histogram (256 literals + one end-of-block) in LDS and the band's
+// Adler-32 partial sums.
+//
+// Stage 2, four launches over a byte buffer split into bands:
+//   deflate_hist_kernel   the 257-bin histogram of every band (skipped when stage 1 made it);
+//   deflate_plan_kernel   one wave per band: code lengths <= 15 (an optimal Huffman code by the in-place minimum-redundancy construction
+//                         on the sorted counts, then the Kraft-sum repair when a length exceeds the limit), canonical codes, the block
+//                         header (code-length code <= 7 bits, with the run-length symbols 16 / 17 / 18) and the EXACT size of the band's
+//                         segment: histogram x lengths + header; Huffman form or, when that is not smaller, stored blocks;
+//   deflate_scan_kernel   one workgroup: prefix sum of the segment sizes -> 64-bit byte offsets and the total; for a zlib stream also
+//                         the 2-byte header and the Adler-32 combined from the band partials;
+//   deflate_pack_kernel   one workgroup per band writes its segment straight to its final offset.  Bits are gathered in an LDS window
+//                         with integer OR (independent of arrival order), a lane then owns whole 32-bit output words; a segment begins
+//                         and ends on a byte boundary, so the words it shares with its neighbours are written as single bytes and no
+//                         two workgroups ever write the same byte: the output is bitwise repeatable and needs no zeroed buffer.
+// A Huffman segment is one dynamic block (literals and end-of-block only, HDIST = 0 with its one distance code of length 0) followed by
+// an empty stored block, which byte-aligns it; only the last band's last block carries BFINAL.
+#include "ops.h"
+
+namespace ciaosr {
+namespace png {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kSyms = 257;                         // 256 literals + end-of-block
+constexpr int kStride = CIAOSR_PNG_HIST_STRIDE;    // u32 per band in histograms and code tables
+constexpr int kHdrWords = 64;                      // u32 per band for the packed block header
+constexpr int kMaxHdrBits = 32 * kHdrWords - 8;
+constexpr int kLitLimit = 15, kClLimit = 7;
+constexpr u32 kAdler = 65521u;
+constexpr u32 kStoredMax = 65535u;
+constexpr u64 kMaxBand = 1ull << 31;               // bytes per band: counts and their sums stay in 32 bits
+constexpr int kPerLane = 16;                       // symbols per lane and step of the packer
+constexpr int kChunk = kThreads * kPerLane;
+constexpr int kWin = 2048;                         // words of the packer's LDS window: 24 + 2040 header bits + 4096 x 15 < 65536
+
+static_assert(kStride >= kSyms, "histogram stride");
+
+// bands of a byte buffer: explicit offsets [nb + 1], or uniform bands of band_bytes (the last one shorter)
+struct Bands {
+    const u64* offs;
+    u64 band_bytes, total;
+    int nb;
+};
+__device__ __forceinline__ u64 band_begin(const Bands& b, int i) {
+    if (b.offs) return b.offs[i];
+    const u64 v = (u64)i * b.band_bytes;
+    return v < b.total ? v : b.total;
+}
+
+__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;
+}
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct FilterP {
+    const unsigned char* src;     // [H][pitch], 3 bytes per pixel
+    size_t pitch;
+    int H, W, bgr, R;
+    unsigned char* dst;           // [H][1 + 3 W]
+    u32* hist;                    // [nb][kStride]
+    u32* adler;                   // [nb][2]: the band's Adler-32 sums a, b taken from a = b = 0, mod 65521
+};
+
+__device__ __forceinline__ u32 cost8(u32 b) { return b < 128u ? b : 256u - b; }
+
+__device__ __forceinline__ void filters5(int v, int a, int b, int c, u32 f[5]) {
+    const int p = a + b - c;
+    const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+    const int pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+    f[0] = (u32)v;
+    f[1] = (u32)(v - a) & 255u;
+    f[2] = (u32)(v - b) & 255u;
+    f[3] = (u32)(v - ((a + b) >> 1)) & 255u;
+    f[4] = (u32)(v - pr) & 255u;
+}
+
+__global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
+    __shared__ u32 h[kWaves][kStride];
+    __shared__ u32 red[kWaves][5];
+    __shared__ u64 red64[kWaves][2];
+    __shared__ int s_best;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int band = blockIdx.x;
+    const int r0 = band * p.R, r1 = min(p.H, r0 + p.R);
+    for (int i = tid; i < kWaves * kStride; i += kThreads) (&h[0][0])[i] = 0u;
+    __syncthreads();
+    const u64 L = 3ull * (u64)p.W + 1ull;
+    const int s0 = p.bgr ? 2 : 0, s2 = p.bgr ? 0 : 2;
+    u32 A = 0u, B = 0u;                                   // thread 0: the band's Adler sums so far
+    for (int row = r0; row < r1; ++row) {
+        const unsigned char* cur = p.src + (size_t)row * p.pitch;
+        const unsigned char* up = row > 0 ? cur - p.pitch : nullptr;
+        u32 s[5] = {0u, 0u, 0u, 0u, 0u};
+        for (int x = tid; x < p.W; x += kThreads) {
+            const unsigned char* q = cur + 3 * (size_t)x;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int sc = c == 0 ? s0 : (c == 1 ? 1 : s2);
+                const int v = q[sc], a = x > 0 ? q[sc - 3] : 0;
+                const int b = up ? (up + 3 * (size_t)x)[sc] : 0, cc = (up && x > 0) ? (up + 3 * (size_t)x)[sc - 3] : 0;
+                u32 f[5];
+                filters5(v, a, b, cc, f);
+#pragma unroll
+                for (int k = 0; k < 5; ++k) s[k] += cost8(f[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const u32 t = wave_sum_u32(s[k]);
+            if (lane == 0) red[wave][k] = t;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int best = 0;
+            u32 bs = 0xffffffffu;
+            for (int k = 0; k < 5; ++k) {
+                u32 t = 0u;
+                for (int w = 0; w < kWaves; ++w) t += red[w][k];
+                if (t < bs) {                             // strict: ties go to the lowest filter number
+                    bs = t;
+                    best = k;
+                }
+            }
+            s_best = best;
+        }
+        __syncthreads();
+        const int best = s_best;
+        unsigned char* out = p.dst + (u64)row * L;
+        u64 a1 = 0ull, a2 = 0ull;
+        if (tid == 0) {
+            out[0] = (unsigned char)best;
+            atomicAdd(&h[0][best], 1u);
+            a1 = (u64)best;
+            a2 = L * (u64)best;
+        }
+        for (int x = tid; x < p.W; x += kThreads) {
+            const unsigned char* q = cur + 3 * (size_t)x;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int sc = c == 0 ? s0 : (c == 1 ? 1 : s2);
+                const int v = q[sc], a = x > 0 ? q[sc - 3] : 0;
+                const int b = up ? (up + 3 * (size_t)x)[sc] : 0, cc = (up && x > 0) ? (up + 3 * (size_t)x)[sc - 3] : 0;
+                u32 f[5];
+                filters5(v, a, b, cc, f);
+                const u32 fb = best == 0 ? f[0] : best == 1 ? f[1] : best == 2 ? f[2] : best == 3 ? f[3] : f[4];
+                const u64 j = 1ull + 3ull * (u64)x + (u64)c;
+                out[j] = (unsigned char)fb;
+                atomicAdd(&h[wave][fb], 1u);
+                a1 += fb;
+                a2 += (L - j) * (u64)fb;              // < 2^18 * 2^8 per byte, < 2^44 per row
+            }
+        }
+        a1 = wave_sum_u64(a1);
+        a2 = wave_sum_u64(a2);
+        if (lane == 0) {
+            red64[wave][0] = a1;
+            red64[wave][1] = a2;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            u64 t1 = 0ull, t2 = 0ull;
+            for (int w = 0; w < kWaves; ++w) {
+                t1 += red64[w][0];
+                t2 += red64[w][1];
+            }
+            B = (u32)(((u64)B + (L % kAdler) * (u64)A + t2 % kAdler) % kAdler);
+            A = (u32)(((u64)A + t1 % kAdler) % kAdler);
+        }
+        __syncthreads();                                   // red / red64 / s_best are rewritten by the next row
+    }
+    for (int i = tid; i < kSyms; i += kThreads) {
+        u32 t = i == 256 ? 1u : 0u;                        // one end-of-block per band
+        for (int w = 0; w < kWaves; ++w) t += h[w][i];
+        p.hist[(size_t)band * kStride + i] = t;
+    }
+    if (tid == 0) {
+        p.adler[2 * (size_t)band] = A;
+        p.adler[2 * (size_t)band + 1] = B;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct DeflateP {
+    const unsigned char* data;
+    Bands b;
+    u32* hist;                    // [nb][kStride]
+    u32* table;                   // [nb][kStride]: length << 16 | bit-reversed code
+    u32* hdr;                     // [nb][kHdrWords]: the dynamic block's header, bit 0 of word 0 first
+    u32* hdr_bits;                // [nb]
+    u32* mode;                    // [nb]: 1 Huffman, 0 stored
+    u64* seg_bytes;               // [nb]
+    u64* out_offs;                // [nb + 1]
+    u64 base;                     // offset of the first segment in out (2 behind a zlib header)
+    unsigned char* out;
+    const u32* adler;             // [nb][2] or null: zlib framing wanted
+    u64* total;                   // device: bytes written to out
+};
+
+__global__ __launch_bounds__(kThreads) void deflate_hist_kernel(DeflateP p) {
+    __shared__ u32 h[kWaves][kStride];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int band = blockIdx.x;
+    for (int i = tid; i < kWaves * kStride; i += kThreads) (&h[0][0])[i] = 0u;
+    __syncthreads();
+    const u64 d0 = band_begin(p.b, band), d1 = band_begin(p.b, band + 1);
+    for (u64 i = d0 + tid; i < d1; i += kThreads) atomicAdd(&h[wave][p.data[i]], 1u);
+    __syncthreads();
+    for (int i = tid; i < kSyms; i += kThreads) {
+        u32 t = i == 256 ? 1u : 0u;
+        for (int w = 0; w < kWaves; ++w) t += h[w][i];
+        p.hist[(size_t)band * kStride + i] = t;
+    }
+}
+
+// In-place minimum-redundancy code lengths of n >= 2 ascending weights (Moffat & Katajainen): key[i] becomes the depth of leaf i.
+__device__ void min_redundancy(u32* key, int n) {
+    key[0] += key[1];
+    int root = 0, leaf = 2;
+    for (int next = 1; next < n - 1; ++next) {
+        if (leaf >= n || key[root] < key[leaf]) {
+            key[next] = key[root];
+            key[root++] = (u32)next;
+        } else {
+            key[next] = key[leaf++];
+        }
+        if (leaf >= n || (root < next && key[root] < key[leaf])) {
+            key[next] += key[root];
+            key[root++] = (u32)next;
+        } else {
+            key[next] += key[leaf++];
+        }
+    }
+    key[n - 2] = 0u;
+    for (int next = n - 3; next >= 0; --next) key[next] = key[key[next]] + 1u;
+    int avbl = 1, used = 0, dpth = 0;
+    root = n - 2;
+    int next = n - 1;
+    while (avbl > 0) {
+        while (root >= 0 && (int)key[root] == dpth) {
+            ++used;
+            --root;
+        }
+        while (avbl > used) {
+            key[next--] = (u32)dpth;
+            --avbl;
+        }
+        avbl = 2 * used;
+        ++dpth;
+        used = 0;
+    }
+}
+
+// One wave: f[nsym] counts -> len[nsym] (0 for unused symbols), a complete prefix code with lengths <= limit.  key / ord: nsym entries
+// of LDS scratch, num: limit + 1 ints.  A single used symbol gets a one-bit code and an unused partner the other one (inflate refuses
+// an incomplete code-length code).
+__device__ void wave_code_lengths(const u32* f, int nsym, int limit, u32* key, unsigned short* ord, int* num, unsigned char* len) {
+    const int lane = threadIdx.x;
+    for (int i = lane; i < nsym; i += kWave) len[i] = 0;
+    for (int i = lane; i < nsym; i += kWave) {
+        const u32 fi = f[i];
+        if (!fi) continue;
+        int r = 0;                                          // rank by (count, symbol), ascending
+        for (int j = 0; j < nsym; ++j) {
+            const u32 fj = f[j];
+            r += (fj != 0u) && (fj < fi || (fj == fi && j < i));
+        }
+        key[r] = fi;
+        ord[r] = (unsigned short)i;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int n = 0;
+        for (int j = 0; j < nsym; ++j) n += f[j] != 0u;
+        if (n == 1) {
+            len[ord[0]] = 1;
+            len[ord[0] == 0 ? 1 : 0] = 1;
+        } else if (n >= 2) {
+            min_redundancy(key, n);
+            for (int l = 0; l <= limit; ++l) num[l] = 0;
+            for (int i = 0; i < n; ++i) num[min((int)key[i], limit)]++;
+            u32 total = 0u;
+            for (int l = limit; l > 0; --l) total += (u32)num[l] << (limit - l);
+            while (total != (1u << limit)) {                // over-subscribed by the clamp: lengthen the deepest shorter code
+                num[limit]--;
+                for (int l = limit - 1; l > 0; --l)
+                    if (num[l]) {
+                        num[l]--;
+                        num[l + 1] += 2;
+                        break;
+                    }
+                --total;
+            }
+            int j = n;                                      // the shortest codes to the most frequent symbols
+            for (int l = 1; l <= limit; ++l)
+                for (int k = num[l]; k > 0; --k) len[ord[--j]] = (unsigned char)l;
+        }
+    }
+    __syncthreads();
+}
+
+// lane 0: canonical codes of len[nsym], bit-reversed for LSB-first emission, as length << 16 | code
+__device__ void canonical_codes(const unsigned char* len, int nsym, int limit, int* num, u32* next, u32* out) {
+    for (int l = 0; l <= limit; ++l) num[l] = 0;
+    for (int i = 0; i < nsym; ++i) num[len[i]]++;
+    num[0] = 0;
+    u32 code = 0u;
+    for (int l = 1; l <= limit; ++l) {
+        code = (code + (u32)num[l - 1]) << 1;
+        next[l] = code;
+    }
+    for (int i = 0; i < nsym; ++i) {
+        const u32 l = len[i];
+        out[i] = l ? (l << 16 | (__brev(next[l]++) >> (32 - l))) : 0u;
+    }
+}
+
+struct BitSink {
+    u32* words;
+    u64 acc;
+    int nacc, w, bits;
+    __device__ void put(u32 v, int n) {
+        acc |= (u64)v << nacc;
+        nacc += n;
+        bits += n;
+        if (nacc >= 32) {
+            if (w < kHdrWords) words[w] = (u32)acc;
+            ++w;
+            acc >>= 32;
+            nacc -= 32;
+        }
+    }
+    __device__ void finish() {
+        for (; w < kHdrWords; ++w) {
+            words[w] = (u32)acc;
+            acc = 0ull;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kWave) void deflate_plan_kernel(DeflateP p) {
+    __shared__ u32 f[kStride];
+    __shared__ u32 key[kStride];
+    __shared__ unsigned short ord[kStride];
+    __shared__ unsigned char len[kStride];
+    __shared__ u32 code[kStride];
+    __shared__ int num[kLitLimit + 1];
+    __shared__ u32 next[kLitLimit + 1];
+    __shared__ unsigned short ent[kSyms + 1];              // code-length symbols: symbol | extra << 5
+    __shared__ u32 clf[19];
+    __shared__ unsigned char cll[19];
+    __shared__ u32 clc[19];
+    __shared__ int s_nent;
+    const int lane = threadIdx.x, band = blockIdx.x;
+    for (int i = lane; i < kSyms; i += kWave) f[i] = p.hist[(size_t)band * kStride + i];
+    __syncthreads();
+    wave_code_lengths(f, kSyms, kLitLimit, key, ord, num, len);
+    if (lane == 0) {
+        canonical_codes(len, kSyms, kLitLimit, num, next, code);
+        // the 258 code lengths (257 literal / length codes + the one distance code of length 0) in run-length symbols
+        for (int i = 0; i < 19; ++i) clf[i] = 0u;
+        int ne = 0, i = 0;
+        const int ncl = kSyms + 1;
+        while (i < ncl) {
+            const int v = i < kSyms ? len[i] : 0;
+            int run = 1;
+            while (i + run < ncl && (i + run < kSyms ? len[i + run] : 0) == v) ++run;
+            i += run;
+            if (v == 0) {
+                while (run > 0) {
+                    if (run >= 11) {
+                        const int t = min(run, 138);
+                        ent[ne++] = (unsigned short)(18 | (t - 11) << 5);
+                        clf[18]++;
+                        run -= t;
+                    } else if (run >= 3) {
+                        ent[ne++] = (unsigned short)(17 | (run - 3) << 5);
+                        clf[17]++;
+                        run = 0;
+                    } else {
+                        ent[ne++] = 0;
+                        clf[0]++;
+                        --run;
+                    }
+                }
+            } else {
+                ent[ne++] = (unsigned short)v;
+                clf[v]++;
+                --run;
+                while (run > 0) {
+                    if (run >= 3) {
+                        const int t = min(run, 6);
+                        ent[ne++] = (unsigned short)(16 | (t - 3) << 5);
+                        clf[16]++;
+                        run -= t;
+                    } else {
+                        ent[ne++] = (unsigned short)v;
+                        clf[v]++;
+                        --run;
+                    }
+                }
+            }
+        }
+        s_nent = ne;
+    }
+    __syncthreads();
+    wave_code_lengths(clf, 19, kClLimit, key, ord, num, cll);
+    if (lane == 0) {
+        canonical_codes(cll, 19, kClLimit, num, next, clc);
+        const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        int hclen = 4;
+        for (int k = 0; k < 19; ++k)
+            if (cll[order[k]]) hclen = max(hclen, k + 1);
+        BitSink s{p.hdr + (size_t)band * kHdrWords, 0ull, 0, 0, 0};
+        s.put(4u, 3);                                      // BFINAL 0, BTYPE 10 (dynamic)
+        s.put(0u, 5);                                      // HLIT: 257 codes
+        s.put(0u, 5);                                      // HDIST: 1 code
+        s.put((u32)(hclen - 4), 4);
+        for (int k = 0; k < hclen; ++k) s.put(cll[order[k]], 3);
+        const int ne = s_nent;
+        for (int k = 0; k < ne; ++k) {
+            const int sym = ent[k] & 31, extra = ent[k] >> 5;
+            s.put(clc[sym] & 0xffffu, (int)(clc[sym] >> 16));
+            if (sym == 16) s.put((u32)extra, 2);
+            if (sym == 17) s.put((u32)extra, 3);
+            if (sym == 18) s.put((u32)extra, 7);
+        }
+        s.finish();
+        u64 payload = 0ull;
+        for (int i = 0; i < kSyms; ++i) payload += (u64)f[i] * len[i];
+        const u64 n = band_begin(p.b, band + 1) - band_begin(p.b, band);
+        const u64 huff = ((u64)s.bits + payload + 3ull + 7ull) / 8ull + 4ull;     // + the empty stored block: 3 bits, pad, LEN, NLEN
+        const u64 stored = n + 5ull * ((n + kStoredMax - 1) / kStoredMax);
+        const bool use = huff < stored && s.bits <= kMaxHdrBits;
+        p.hdr_bits[band] = (u32)s.bits;
+        p.mode[band] = use ? 1u : 0u;
+        p.seg_bytes[band] = use ? huff : stored;
+    }
+    __syncthreads();
+    for (int i = lane; i < kSyms; i += kWave) p.table[(size_t)band * kStride + i] = code[i];
+}
+
+// one workgroup: lane t owns the bands [t * per, (t + 1) * per)
+__global__ __launch_bounds__(kThreads) void deflate_scan_kernel(DeflateP p) {
+    __shared__ u64 tot[kThreads];
+    __shared__ u32 ad[kThreads][3];
+    const int tid = threadIdx.x, nb = p.b.nb;
+    const int per = (nb + kThreads - 1) / kThreads;
+    const int i0 = min(nb, tid * per), i1 = min(nb, i0 + per);
+    u64 sum = 0ull;
+    u32 a = 0u, b = 0u, n = 0u;                            // Adler sums and length (mod 65521) of this lane's run of bands
+    for (int i = i0; i < i1; ++i) {
+        sum += p.seg_bytes[i];
+        if (p.adler) {
+            const u32 ni = (u32)((band_begin(p.b, i + 1) - band_begin(p.b, i)) % kAdler);
+            b = (u32)(((u64)b + (u64)p.adler[2 * (size_t)i + 1] + (u64)ni * a) % kAdler);
+            a = (a + p.adler[2 * (size_t)i]) % kAdler;
+            n = (n + ni) % kAdler;
+        }
+    }
+    tot[tid] = sum;
+    ad[tid][0] = a;
+    ad[tid][1] = b;
+    ad[tid][2] = n;
+    __syncthreads();
+    if (tid == 0) {
+        u64 run = p.base;
+        u32 ca = 0u, cb = 0u, cn = 0u;
+        for (int t = 0; t < kThreads; ++t) {
+            const u64 v = tot[t];
+            tot[t] = run;
+            run += v;
+            cb = (u32)(((u64)cb + ad[t][1] + (u64)ad[t][2] * ca) % kAdler);
+            ca = (ca + ad[t][0]) % kAdler;
+            cn = (cn + ad[t][2]) % kAdler;
+        }
+        p.out_offs[nb] = run;
+        if (p.adler) {                                      // zlib: CMF / FLG in front, Adler-32 (from a = 1, b = 0) behind, big-endian
+            const u32 fa = (1u + ca) % kAdler, fb = (cn + cb) % kAdler;
+            p.out[0] = 0x78;
+            p.out[1] = 0x01;
+            p.out[run + 0] = (unsigned char)(fb >> 8);
+            p.out[run + 1] = (unsigned char)fb;
+            p.out[run + 2] = (unsigned char)(fa >> 8);
+            p.out[run + 3] = (unsigned char)fa;
+            run += 4;
+        }
+        *p.total = run;
+    }
+    __syncthreads();
+    u64 off = tot[tid];
+    for (int i = i0; i < i1; ++i) {
+        p.out_offs[i] = off;
+        off += p.seg_bytes[i];
+    }
+}
+
+__device__ __forceinline__ void or_bits(u32* win, u32 pos, u32 v) {
+    const u64 x = (u64)v << (pos & 31u);
+    atomicOr(&win[pos >> 5], (u32)x);
+    if (x >> 32) atomicOr(&win[(pos >> 5) + 1], (u32)(x >> 32));
+}
+
+// words [0, nw) of the window, word w at byte abase + 4 (wdone + w) of out; only bytes in [lo, hi) are written
+__device__ __forceinline__ void flush_words(const u32* win, int nw, unsigned char* out, u64 abase, u64 wdone, u64 lo, u64 hi) {
+    for (int w = threadIdx.x; w < nw; w += kThreads) {
+        const u64 g = abase + 4ull * (wdone + (u64)w);
+        const u32 v = win[w];
+        if (g >= lo && g + 4 <= hi) {
+            *reinterpret_cast<u32*>(out + g) = v;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (g + k >= lo && g + k < hi) out[g + k] = (unsigned char)(v >> (8 * k));
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
+    __shared__ u32 win[kWin];
+    __shared__ u32 tab[kStride];
+    __shared__ u32 wsum[kWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int band = blockIdx.x;
+    const bool last = band == p.b.nb - 1;
+    const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
+    const u64 lo = p.out_offs[band], hi = p.out_offs[band + 1];
+    if (p.mode[band] == 0u) {                               // stored blocks of at most 65535 bytes: 5 framing bytes each
+        const u64 nblk = (n + kStoredMax - 1) / kStoredMax;
+        for (u64 j = tid; j < hi - lo; j += kThreads) {
+            const u64 blk = j / (kStoredMax + 5ull);
+            const u32 r = (u32)(j % (kStoredMax + 5ull));
+            const u64 left = n - blk * kStoredMax;
+            const u32 ln = left < kStoredMax ? (u32)left : kStoredMax;
+            unsigned char v;
+            if (r == 0) v = (last && blk == nblk - 1) ? 1 : 0;
+            else if (r == 1) v = (unsigned char)ln;
+            else if (r == 2) v = (unsigned char)(ln >> 8);
+            else if (r == 3) v = (unsigned char)~ln;
+            else if (r == 4) v = (unsigned char)(~ln >> 8);
+            else v = p.data[d0 + blk * kStoredMax + (r - 5)];
+            p.out[lo + j] = v;
+        }
+        return;
+    }
+    for (int i = tid; i < kSyms; i += kThreads) tab[i] = p.table[(size_t)band * kStride + i];
+    for (int i = tid; i < kWin; i += kThreads) win[i] = 0u;
+    __syncthreads();
+    const u64 abase = lo & ~3ull;                           // window word 0 is the aligned output word that holds the segment's first byte
+    u32 bitpos = (u32)(lo & 3ull) * 8u;
+    u64 wdone = 0ull;
+    {
+        const u32 hb = p.hdr_bits[band];
+        const int nw = (int)((hb + 31u) >> 5);
+        if (tid < nw) {
+            const u64 x = (u64)p.hdr[(size_t)band * kHdrWords + tid] << bitpos;
+            atomicOr(&win[tid], (u32)x);
+            if (x >> 32) atomicOr(&win[tid + 1], (u32)(x >> 32));
+        }
+        bitpos += hb;
+    }
+    __syncthreads();
+    for (u64 c0 = 0; c0 < n; c0 += kChunk) {
+        const u64 m0 = c0 + (u64)tid * kPerLane;
+        const int cnt = m0 >= n ? 0 : (n - m0 < (u64)kPerLane ? (int)(n - m0) : kPerLane);
+        u32 e[kPerLane];
+        u32 bits = 0u;
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) {
+            e[k] = k < cnt ? tab[p.data[d0 + m0 + k]] : 0u;
+            bits += e[k] >> 16;
+        }
+        u32 inc = bits;                                      // inclusive scan of the lanes' bit counts
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const u32 t = __shfl_up(inc, off, kWave);
+            if (lane >= off) inc += t;
+        }
+        if (lane == kWave - 1) wsum[wave] = inc;
+        __syncthreads();
+        u32 before = 0u, chunk_bits = 0u;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            if (w < wave) before += wsum[w];
+            chunk_bits += wsum[w];
+        }
+        u32 pos = bitpos + before + inc - bits;
+        int w = (int)(pos >> 5);
+        int nacc = (int)(pos & 31u);
+        u64 acc = 0ull;
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) {
+            acc |= (u64)(e[k] & 0xffffu) << nacc;
+            nacc += (int)(e[k] >> 16);
+            if (nacc >= 32) {
+                atomicOr(&win[w], (u32)acc);
+                ++w;
+                acc >>= 32;
+                nacc -= 32;
+            }
+        }
+        if (nacc > 0 && acc) atomicOr(&win[w], (u32)acc);
+        __syncthreads();
+        const u32 newpos = bitpos + chunk_bits;
+        const int nfull = (int)(newpos >> 5);
+        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
+        const u32 carry = win[nfull];
+        __syncthreads();
+        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
+        __syncthreads();
+        if (tid == 0) win[0] = carry;
+        __syncthreads();
+        wdone += (u64)nfull;
+        bitpos = newpos & 31u;
+    }
+    if (tid == 0) {
+        u32 pos = bitpos;
+        or_bits(win, pos, tab[256] & 0xffffu);
+        pos += tab[256] >> 16;
+        or_bits(win, pos, last ? 1u : 0u);               // the empty stored block: BFINAL, BTYPE 00, pad, LEN 0, NLEN 0xffff
+        pos = (pos + 3u + 7u) & ~7u;
+        or_bits(win, pos + 16u, 0xffffu);
+        bitpos = pos + 32u;
+        wsum[0] = bitpos;
+    }
+    __syncthreads();
+    flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
+}
+
+static inline int rows_per_band(int W, int rows) {
+    if (rows > 0) return rows;
+    const long L = 3L * W + 1;
+    const long r = (128L * 1024L) / L;                       // bands of about 128 KiB of filtered bytes
+    return (int)(r < 1 ? 1 : r);
+}
+
+struct Work {
+    u64* offs_in;
+    u32 *hist, *table, *hdr, *hdr_bits, *mode, *adler;
+    u64 *seg_bytes, *out_offs;
+    unsigned char* filtered;
+};
+static inline bool carve(void* ws, size_t bytes, int nb, size_t filtered_bytes, Work* w, size_t* used) {
+    Arena a(ws, bytes);
+    w->offs_in = a.take<u64>((size_t)nb + 1);
+    w->hist = a.take<u32>((size_t)nb * kStride);
+    w->table = a.take<u32>((size_t)nb * kStride);
+    w->hdr = a.take<u32>((size_t)nb * kHdrWords);
+    w->hdr_bits = a.take<u32>((size_t)nb);
+    w->mode = a.take<u32>((size_t)nb);
+    w->adler = a.take<u32>(2 * (size_t)nb);
+    w->seg_bytes = a.take<u64>((size_t)nb);
+    w->out_offs = a.take<u64>((size_t)nb + 1);
+    w->filtered = a.take<unsigned char>(filtered_bytes);
+    if (used) *used = a.off;
+    return a.ok;
+}
+static inline size_t work_bytes(int nb, size_t filtered_bytes) {
+    Work w;
+    size_t used = 0;
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    carve(origin, ~(size_t)0, nb, filtered_bytes, &w, &used);
+    return used;
+}
+
+static inline size_t capacity(size_t total, int nb, bool zlib) {
+    return total + 5 * (total / kStoredMax + (size_t)nb) + (zlib ? 6 : 0) + 8;
+}
+
+// plan, scan and pack of the bands described by p.b (histograms already in p.hist)
+static int run_deflate(DeflateP& p, hipStream_t s) {
+    {
+        ProfScope prof("deflate_plan", s);
+        hipLaunchKernelGGL(deflate_plan_kernel, dim3(p.b.nb), dim3(kWave), 0, s, p);
+        int rc = launch_status("deflate_plan");
+        if (rc) return rc;
+    }
+    {
+        ProfScope prof("deflate_scan", s);
+        hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
+        int rc = launch_status("deflate_scan");
+        if (rc) return rc;
+    }
+    ProfScope prof("deflate_pack", s);
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3(p.b.nb), dim3(kThreads), 0, s, p);
+    return launch_status("deflate_pack");
+}
+
+static int run_filter(const unsigned char* src, size_t pitch, int H, int W, int bgr, int R, unsigned char* dst, u32* hist, u32* adler,
+                      hipStream_t s) {
+    FilterP f{src, pitch, H, W, bgr, R, dst, hist, adler};
+    ProfScope prof("png_filter_u8", s);
+    hipLaunchKernelGGL(png_filter_kernel, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
+    return launch_status("png_filter_u8");
+}
+
+static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
+
+}  // namespace png
+}  // namespace ciaosr
+
+using namespace ciaosr;
+using namespace ciaosr::png;
+
+extern "C" int ciaosr_png_rows_per_band(int W, int rows_per_band_arg) {
+    if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
+    return rows_per_band(W, rows_per_band_arg);
+}
+
+extern "C" int ciaosr_png_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                    unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
+    CIAOSR_CHECK_ARG(src && dst && hist && adler && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(hist) & 3u) == 0 && (reinterpret_cast<uintptr_t>(adler) & 3u) == 0);
+    const int R = rows_per_band(W, rows_per_band_arg);
+    if ((u64)R * (3ull * W + 1) > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    return run_filter(src, pitch, H, W, bgr, R, dst, hist, adler, (hipStream_t)stream);
+}
+
+extern "C" size_t ciaosr_deflate_huff_workspace_bytes(int n_bands) {
+    if (n_bands <= 0) return 0;
+    return work_bytes(n_bands, 0);
+}
+
+extern "C" size_t ciaosr_deflate_huff_capacity_bytes(size_t total_bytes, int n_bands) {
+    if (n_bands <= 0) return 0;
+    return capacity(total_bytes, n_bands, false);
+}
+
+extern "C" int ciaosr_deflate_huff_u8(const unsigned char* data, const unsigned long long* band_offsets, int n_bands,
+                                      unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(data && band_offsets && out && seg_offsets && workspace && n_bands > 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(seg_offsets) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    for (int i = 0; i < n_bands; ++i) {
+        CIAOSR_CHECK_ARG(band_offsets[i + 1] > band_offsets[i]);            // an empty band has no histogram to code
+        if (band_offsets[i + 1] - band_offsets[i] > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    }
+    const u64 total = band_offsets[n_bands] - band_offsets[0];
+    if (out_capacity < capacity(total, n_bands, false)) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    if (workspace_bytes < work_bytes(n_bands, 0) || !carve(workspace, workspace_bytes, n_bands, 0, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(w.offs_in, band_offsets, ((size_t)n_bands + 1) * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess)
+        return CIAOSR_ERR_LAUNCH;
+    DeflateP p{data, Bands{w.offs_in, 0ull, 0ull, n_bands}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, seg_offsets, 0ull, out,
+               nullptr, seg_offsets + n_bands};
+    {
+        ProfScope prof("deflate_hist", s);
+        hipLaunchKernelGGL(deflate_hist_kernel, dim3(n_bands), dim3(kThreads), 0, s, p);
+        int rc = launch_status("deflate_hist");
+        if (rc) return rc;
+    }
+    return run_deflate(p, s);
+}
+
+extern "C" size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band_arg) {
+    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
+    const int R = rows_per_band(W, rows_per_band_arg);
+    return work_bytes(ceil_div(H, R), (size_t)H * (3 * (size_t)W + 1));
+}
+
+extern "C" size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band_arg) {
+    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
+    const int R = rows_per_band(W, rows_per_band_arg);
+    return capacity((size_t)H * (3 * (size_t)W + 1), ceil_div(H, R), true);
+}
+
+extern "C" int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                    unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    const int R = rows_per_band(W, rows_per_band_arg);
+    const u64 L = 3ull * W + 1;
+    if ((u64)R * L > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    const int nb = ceil_div(H, R);
+    const u64 total = (u64)H * L;
+    if (out_capacity < capacity(total, nb, true)) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_filter(src, pitch, H, W, bgr, R, w.filtered, w.hist, w.adler, s);
+    if (rc) return rc;
+    DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
+               out, w.adler, total_bytes};
+    return run_deflate(p, s);
+}

@@ -72,6 +72,11 @@ class BasicRestorer(nn.Module):
         """`test_cfg.gpu_metrics` (an extension; default off): quantise and evaluate on the device (ciaosr_amd/metrics_hip.py)."""
         return bool(self.test_cfg is not None and self.test_cfg.get('gpu_metrics', False))
 
+    def gpu_png(self):
+        """`test_cfg.gpu_png` (an extension; default off): saved images are quantised and PNG-encoded on the device
+        (ciaosr_amd/png_hip.py) instead of `imageio.imwrite`; the files decode to the same pixels."""
+        return bool(self.test_cfg is not None and self.test_cfg.get('gpu_png', False))
+
     def evaluate(self, output, gt, out_img=None):
         """PSNR/SSIM on uint8 BGR images as basic_restorer.py:101-124.  With `test_cfg.gpu_metrics` both tensors are quantised
         and compared on the device (`out_img`: the already quantised output, if the caller has it); the output must be there
@@ -842,7 +847,7 @@ class CiaoSR(BasicRestorer):
             shape = [lq.shape[0], pred.shape[2], pred.shape[3], 3]
             gt = gt.view(*shape).permute(0, 3, 1, 2).contiguous()
         out_img = None
-        if self.gpu_metrics() and save_image:
+        if (self.gpu_metrics() or self.gpu_png()) and save_image:
             from . import metrics_hip
             out_img = metrics_hip.tensor2img_u8(pred)              # quantised once, for the metrics and for the file
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
@@ -863,8 +868,12 @@ class CiaoSR(BasicRestorer):
                 save_path = osp.join(save_path, f'{folder_name}.png')
             else:
                 raise ValueError(f'iteration should be number or None, but got {type(iteration)}')
-            from .imageio import imwrite
-            imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(pred), save_path)
+            if self.gpu_png():
+                from .png_hip import imwrite_gpu
+                imwrite_gpu(out_img, save_path)
+            else:
+                from .imageio import imwrite
+                imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(pred), save_path)
         return results
 
     def init_weights(self, pretrained=None, strict=True):

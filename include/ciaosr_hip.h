@@ -756,6 +756,52 @@ size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int co
 int ciaosr_psnr_ssim_u8(const unsigned char* a, size_t pitch_a, const unsigned char* b, size_t pitch_b, int H, int W, int crop_border,
                         int convert_to_y, int want, double* result, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG encoding of 8-bit images (opt-in: test_cfg.gpu_png; replaces the host's PIL save on the --save-path / --out path) ---------
+ * Two stages, separately callable, and their composition.  Nothing here searches for LZ77 matches: the coder emits literals and
+ * end-of-block only.  Bands are coded independently, one workgroup each.  All byte offsets are 64-bit. */
+#define CIAOSR_PNG_HIST_STRIDE 260   /* unsigned ints per band in a histogram array: 256 literals, end-of-block, 3 unused */
+/* rows of one band for an image W pixels wide: rows_per_band if > 0, else the default -- bands of about 128 KiB of filtered bytes,
+ * max(1, 131072 / (3 W + 1)) rows.  0 for an invalid W. */
+int ciaosr_png_rows_per_band(int W, int rows_per_band);
+/* PNG scanline filter (colour type 2, 8 bits, no interlace, 3 bytes per pixel).  src[y * pitch + 3 x + c], pitch >= 3 W (a crop view of a
+ * larger image is fine); bgr = 1: the bytes of a pixel are B G R (ciaosr_tensor2img_u8's order), 0: R G B.  H, W <= 65535.
+ * dst: H rows of 1 + 3 W bytes: the filter type, then the filtered bytes in RGB order.  Per row the filter in {0 None, 1 Sub, 2 Up,
+ * 3 Average, 4 Paeth} whose filtered bytes have the smallest sum of (b < 128 ? b : 256 - b); ties go to the lowest number.  The
+ * predecessors are raw pixels (the row above row 0 is zeros), so rows and bands are independent.
+ * hist [n_bands][CIAOSR_PNG_HIST_STRIDE]: per band of rows_per_band rows (0 = default; n_bands = ceil(H / rows)) the count of every byte
+ * value of its part of dst, and 1 at index 256 (one end-of-block per band).
+ * adler [n_bands][2]: per band (sum of its bytes, sum over its bytes of byte * (bytes from it to the band's end)) mod 65521, i.e.
+ * the Adler-32 sums of the band from a = b = 0.  No workspace; bitwise repeatable. */
+int ciaosr_png_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* dst,
+                         unsigned int* hist, unsigned int* adler, void* stream);
+/* Raw deflate of a byte buffer, one segment per band, Huffman-coded literals only.  data: device bytes; band_offsets: HOST array of
+ * n_bands + 1 ascending byte offsets into data (band i = [band_offsets[i], band_offsets[i + 1])); an empty band is refused with
+ * CIAOSR_ERR_BAD_ARG before anything is launched; a band above 2^31 bytes is CIAOSR_ERR_UNSUPPORTED.  The offsets reach the device by
+ * hipMemcpyAsync on `stream`: keep the array valid until the stream has passed this call.
+ * A segment is ONE dynamic-Huffman block -- literal / length code lengths <= 15 (257 codes: no length symbols), code-length-code
+ * lengths <= 7, HDIST = 0 with its one distance code of length 0 -- followed by an empty stored block that byte-aligns it; or, when
+ * that would not be smaller, stored blocks of at most 65535 bytes (5 framing bytes each).  Only the last band's last block carries
+ * BFINAL, so the concatenation of the segments is one valid deflate stream.  Code lengths are built on the device, one wave per band.
+ * out: 4-byte aligned, out_capacity >= ciaosr_deflate_huff_capacity_bytes(total, n_bands) (the all-stored worst case), else
+ * CIAOSR_ERR_WORKSPACE; segment i is written to out[seg_offsets[i] .. seg_offsets[i + 1]), seg_offsets: n_bands + 1 values on the
+ * DEVICE, seg_offsets[0] = 0 and seg_offsets[n_bands] = the stream's size.  Segments go straight to their final place (their exact
+ * sizes follow from histogram x lengths + header before a bit is packed); a byte of out is written by one workgroup only and no
+ * floating point or order-dependent atomic is involved: two calls give identical bytes.  workspace: 8-byte aligned,
+ * ciaosr_deflate_huff_workspace_bytes(n_bands). */
+size_t ciaosr_deflate_huff_workspace_bytes(int n_bands);
+size_t ciaosr_deflate_huff_capacity_bytes(size_t total_bytes, int n_bands);
+int ciaosr_deflate_huff_u8(const unsigned char* data, const unsigned long long* band_offsets /*host*/, int n_bands, unsigned char* out,
+                           size_t out_capacity, unsigned long long* seg_offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* The composition: the zlib stream of a PNG's IDAT data.  out = 78 01, the deflate segments of the filtered bands (as
+ * ciaosr_png_filter_u8 and ciaosr_deflate_huff_u8 make them, with the filter's histograms), the Adler-32 of the filtered stream
+ * combined from the band partials (big-endian).  *total_bytes (DEVICE) = the stream's size.  The host reads that number, then the
+ * stream: two synchronising copies per image.  out 4-byte aligned with ciaosr_png_capacity_bytes(), workspace 8-byte aligned with
+ * ciaosr_png_workspace_bytes() (it holds the filtered image: H (3 W + 1) bytes, plus 2.4 KB per band); 0 = unsupported geometry. */
+size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band);
+int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                         size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

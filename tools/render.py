@@ -14,6 +14,8 @@ largest --scale; without --scale the largest view ZOOM).  Every `--view` (repeat
 ciaosr_amd.scene.view_matrix((CY, CX), ZOOM, ANGLE, (H, W)): an H x W picture whose centre looks at LR position (CY, CX) with ZOOM output
 pixels per LR pixel, turned by ANGLE degrees (positive: the picture turns clockwise), written to DIR/<image name>_view<k>.png, k = 0,
 1, ... in command-line order; one `--size` per `--view`, or a single one for all of them.  Pixels outside the image are black.
+`--gpu-png` sets `test_cfg.gpu_png`: every output is rendered as a uint8 image on the device and PNG-encoded there (ciaosr_amd/png_hip.py);
+the files decode to the pixels of the default run.
 `--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
 queried in 4 x 2 blocks of output pixels, which keeps the head on its chained kernel; other precisions are unaffected.
 """
@@ -40,6 +42,8 @@ def parse_args(argv=None):
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
     p.add_argument('--view-blocks', action='store_true',
                    help='test_cfg.view_blocks: the 16-bit modes select a cut view\'s members in 4 x 2 blocks of output pixels (default off)')
+    p.add_argument('--gpu-png', action='store_true',
+                   help='test_cfg.gpu_png: outputs are quantised and PNG-encoded on the GPU; no fp32 image crosses to the host (default off)')
     p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM)')
     p.add_argument('--out', required=True, help='output directory')
     args = p.parse_args(argv)
@@ -71,6 +75,8 @@ def main(argv=None):
         cfg.test_cfg['precision'] = args.precision
     if args.view_blocks:
         cfg.test_cfg['view_blocks'] = True
+    if args.gpu_png:
+        cfg.test_cfg['gpu_png'] = True
     if cfg.test_cfg.get('tile', None):
         cfg.test_cfg['tile_any_scale'] = True
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -89,9 +95,15 @@ def main(argv=None):
         size = args.size[k if len(args.size) > 1 else 0]
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}.png'))
-    for path, out in zip(paths, model.render_many(enc, targets)):      # one walk over the tile scenes for every output
-        imwrite(metrics.tensor2img(out), path)
-        print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
+    gpu_png = model.gpu_png()
+    for path, out in zip(paths, model.render_many(enc, targets, as_u8=gpu_png)):      # one walk over the tile scenes for every output
+        if gpu_png:
+            from ciaosr_amd.png_hip import imwrite_gpu
+            imwrite_gpu(out, path)                                     # uint8 [H, W, 3] BGR on the device
+            print(f'{path}: {out.shape[0]} x {out.shape[1]}')
+        else:
+            imwrite(metrics.tensor2img(out), path)
+            print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
     return paths
 
 

@@ -70,6 +70,8 @@ def parse_args(argv=None):
     p.add_argument('--gt-folder', default=None, help='override cfg.data.test.gt_folder')
     p.add_argument('--gpu-metrics', action='store_true',
                    help='test_cfg.gpu_metrics = True: quantise and evaluate PSNR / SSIM on the GPU (default: on the host)')
+    p.add_argument('--gpu-png', action='store_true',
+                   help='test_cfg.gpu_png = True: --save-path images are quantised and PNG-encoded on the GPU (default: PIL on the host)')
     return p.parse_args(argv)
 
 
@@ -77,6 +79,8 @@ def apply_overrides(cfg, args):
     """Command-line switches that end up in the loaded config (before the model is built from it)."""
     if args.gpu_metrics:
         cfg.test_cfg['gpu_metrics'] = True
+    if args.gpu_png:
+        cfg.test_cfg['gpu_png'] = True
     return cfg
 
 
@@ -151,15 +155,19 @@ def main(argv=None):
             out = hip_ops.denorm_clamp(pred[0].contiguous(), h, w, model.rgb_mean, model.rgb_std).unsqueeze(0)
             gt_img = gt.view(1, h, w, 3).permute(0, 3, 1, 2).contiguous()
             out_img = None
-            if save and model.gpu_metrics():
+            if save and (model.gpu_metrics() or model.gpu_png()):
                 from ciaosr_amd import metrics_hip
                 out_img = metrics_hip.tensor2img_u8(out)          # quantised once, for the metrics and for the file
             res = dict(eval_result=model.evaluate(out, gt_img, out_img))
             if save:
                 from ciaosr_amd.imageio import imwrite
                 name = os.path.splitext(os.path.basename(d['meta']['gt_path']))[0]
-                imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(out),
-                        os.path.join(args.save_path, f'{name}.png'))
+                if model.gpu_png():
+                    from ciaosr_amd.png_hip import imwrite_gpu
+                    imwrite_gpu(out_img, os.path.join(args.save_path, f'{name}.png'))
+                else:
+                    imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(out),
+                            os.path.join(args.save_path, f'{name}.png'))
         else:
             if world > 1 and i % world != rank:
                 continue
