@@ -21,6 +21,17 @@
 //                         two workgroups ever write the same byte: the output is bitwise repeatable and needs no zeroed buffer.
 // A Huffman segment is one dynamic block (literals and end-of-block only, HDIST = 0 with its one distance code of length 0) followed by
 // an empty stored block, which byte-aligns it; only the last band's last block carries BFINAL.
+//
+// Many crops of one image (ciaosr_png_encode_tiles_u8: the tiles of a pyramid level) run through the same stages in one set of launches.
+// The host builds a band table from the rects (per band: its tile, its rows, its 64-bit offset in the filtered streams; per tile: its
+// first band) and uploads it; png_filter_tiles_kernel filters each band as part of ITS crop (zeros left of the crop's first column and
+// above its first row), the plan and pack kernels run unchanged on the table's offsets (a tile's last band carries BFINAL), and
+// png_tiles_scan_kernel is the scan's segmented sibling: per tile 2 + segments + 4 bytes, a prefix sum over tiles, every band's offset,
+// every tile's header and its Adler-32 from its own bands' partials.  Each tile's stream is byte for byte the single call's on the crop.
+#include <climits>
+#include <cstring>
+#include <vector>
+
 #include "ops.h"
 
 namespace ciaosr {
@@ -69,6 +80,10 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+struct TileBand {
+    int tile, r0, r1, last;       // a band of the tile-batched form: rows [r0, r1) of tile `tile`; last: the tile's final band
+};
+
 struct FilterP {
     const unsigned char* src;     // [H][pitch], 3 bytes per pixel
     size_t pitch;
@@ -91,14 +106,14 @@ __device__ __forceinline__ void filters5(int v, int a, int b, int c, u32 f[5]) {
     f[4] = (u32)(v - pr) & 255u;
 }
 
-__global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
+// One workgroup, one band: rows [r0, r1) of the W pixels wide image at p.src (row 0 and column 0 have zeros for predecessors), written
+// from `dst` on; the band's histogram and Adler partials go to slot `band`.
+__device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, int r1, unsigned char* dst) {
     __shared__ u32 h[kWaves][kStride];
     __shared__ u32 red[kWaves][5];
     __shared__ u64 red64[kWaves][2];
     __shared__ int s_best;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int band = blockIdx.x;
-    const int r0 = band * p.R, r1 = min(p.H, r0 + p.R);
     for (int i = tid; i < kWaves * kStride; i += kThreads) (&h[0][0])[i] = 0u;
     __syncthreads();
     const u64 L = 3ull * (u64)p.W + 1ull;
@@ -142,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
         }
         __syncthreads();
         const int best = s_best;
-        unsigned char* out = p.dst + (u64)row * L;
+        unsigned char* out = dst + (u64)(row - r0) * L;
         u64 a1 = 0ull, a2 = 0ull;
         if (tid == 0) {
             out[0] = (unsigned char)best;
@@ -196,6 +211,33 @@ __global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
     }
 }
 
+__global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
+    const int band = blockIdx.x;
+    const int r0 = band * p.R, r1 = min(p.H, r0 + p.R);
+    filter_band(p, band, r0, r1, p.dst + (u64)r0 * (3ull * (u64)p.W + 1ull));
+}
+
+// The tile-batched form: band `blockIdx.x` of the table is rows [r0, r1) of tile `tile`, a crop y0, x0, h, w of the image.  The crop is
+// filtered as an image of its own -- the pixels left of its first column and above its first row are zeros, whatever the image holds
+// there -- into the stream at the band's offset.
+struct TileFilterP {
+    const unsigned char* src;     // [H][pitch]
+    size_t pitch;
+    int bgr;
+    const int* rects;             // [n_tiles][4]: y0, x0, h, w
+    const TileBand* bands;        // [nb]
+    const u64* offs;              // [nb + 1]: the bands in the filtered stream
+    unsigned char* dst;
+    u32 *hist, *adler;
+};
+__global__ __launch_bounds__(kThreads) void png_filter_tiles_kernel(TileFilterP t) {
+    const int band = blockIdx.x;
+    const TileBand b = t.bands[band];
+    const int* r = t.rects + 4 * (size_t)b.tile;
+    FilterP p{t.src + (size_t)r[0] * t.pitch + 3 * (size_t)r[1], t.pitch, r[2], r[3], t.bgr, 0, nullptr, t.hist, t.adler};
+    filter_band(p, band, b.r0, b.r1, t.dst + t.offs[band]);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct DeflateP {
     const unsigned char* data;
@@ -211,6 +253,7 @@ struct DeflateP {
     unsigned char* out;
     const u32* adler;             // [nb][2] or null: zlib framing wanted
     u64* total;                   // device: bytes written to out
+    const TileBand* tiles;        // [nb] or null: the bands of many streams (tiles); a tile's last band carries BFINAL
 };
 
 __global__ __launch_bounds__(kThreads) void deflate_hist_kernel(DeflateP p) {
@@ -511,6 +554,65 @@ __global__ __launch_bounds__(kThreads) void deflate_scan_kernel(DeflateP p) {
     }
 }
 
+// The scan of many streams: tile t owns the bands [first[t], first[t + 1]) and its stream is 2 header bytes, their segments, 4 bytes of
+// Adler-32.  One workgroup; lane k owns the tiles [k * per, (k + 1) * per) and walks their bands, so any number of tiles and any number
+// of bands per tile is covered.  Writes every tile's offset, header and Adler-32 (from its own bands' partials) and every band's offset.
+struct TileScanP {
+    const u64* offs;              // [nb + 1]: the bands in the filtered stream
+    const u32* first;             // [nt + 1]
+    const u64* seg_bytes;         // [nb]
+    const u32* adler;             // [nb][2]
+    u64* out_offs;                // [nb]
+    u64* tile_offs;               // [nt + 1]
+    unsigned char* out;
+    int nt;
+};
+__global__ __launch_bounds__(kThreads) void png_tiles_scan_kernel(TileScanP p) {
+    __shared__ u64 tot[kThreads];
+    const int tid = threadIdx.x, nt = p.nt;
+    const int per = (nt + kThreads - 1) / kThreads;
+    const int t0 = min(nt, tid * per), t1 = min(nt, t0 + per);
+    u64 sum = 0ull;
+    for (int t = t0; t < t1; ++t) {
+        sum += 6ull;
+        for (u32 i = p.first[t]; i < p.first[t + 1]; ++i) sum += p.seg_bytes[i];
+    }
+    tot[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        u64 run = 0ull;
+        for (int k = 0; k < kThreads; ++k) {
+            const u64 v = tot[k];
+            tot[k] = run;
+            run += v;
+        }
+        p.tile_offs[nt] = run;
+    }
+    __syncthreads();
+    u64 off = tot[tid];
+    for (int t = t0; t < t1; ++t) {
+        p.tile_offs[t] = off;
+        p.out[off] = 0x78;
+        p.out[off + 1] = 0x01;
+        u64 run = off + 2ull;
+        u32 a = 0u, b = 0u, n = 0u;
+        for (u32 i = p.first[t]; i < p.first[t + 1]; ++i) {
+            p.out_offs[i] = run;
+            run += p.seg_bytes[i];
+            const u32 ni = (u32)((p.offs[i + 1] - p.offs[i]) % kAdler);
+            b = (u32)(((u64)b + (u64)p.adler[2 * (size_t)i + 1] + (u64)ni * a) % kAdler);
+            a = (a + p.adler[2 * (size_t)i]) % kAdler;
+            n = (n + ni) % kAdler;
+        }
+        const u32 fa = (1u + a) % kAdler, fb = (n + b) % kAdler;        // from a = 1, b = 0, big-endian
+        p.out[run + 0] = (unsigned char)(fb >> 8);
+        p.out[run + 1] = (unsigned char)fb;
+        p.out[run + 2] = (unsigned char)(fa >> 8);
+        p.out[run + 3] = (unsigned char)fa;
+        off = run + 4ull;
+    }
+}
+
 __device__ __forceinline__ void or_bits(u32* win, u32 pos, u32 v) {
     const u64 x = (u64)v << (pos & 31u);
     atomicOr(&win[pos >> 5], (u32)x);
@@ -538,9 +640,9 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     __shared__ u32 wsum[kWaves];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int band = blockIdx.x;
-    const bool last = band == p.b.nb - 1;
+    const bool last = p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1;
     const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
-    const u64 lo = p.out_offs[band], hi = p.out_offs[band + 1];
+    const u64 lo = p.out_offs[band], hi = lo + p.seg_bytes[band];         // tiles: a trailer and a header lie before the next band
     if (p.mode[band] == 0u) {                               // stored blocks of at most 65535 bytes: 5 framing bytes each
         const u64 nblk = (n + kStoredMax - 1) / kStoredMax;
         for (u64 j = tid; j < hi - lo; j += kThreads) {
@@ -656,8 +758,7 @@ struct Work {
     u64 *seg_bytes, *out_offs;
     unsigned char* filtered;
 };
-static inline bool carve(void* ws, size_t bytes, int nb, size_t filtered_bytes, Work* w, size_t* used) {
-    Arena a(ws, bytes);
+static inline void carve_into(Arena& a, int nb, size_t filtered_bytes, Work* w) {
     w->offs_in = a.take<u64>((size_t)nb + 1);
     w->hist = a.take<u32>((size_t)nb * kStride);
     w->table = a.take<u32>((size_t)nb * kStride);
@@ -668,6 +769,10 @@ static inline bool carve(void* ws, size_t bytes, int nb, size_t filtered_bytes, 
     w->seg_bytes = a.take<u64>((size_t)nb);
     w->out_offs = a.take<u64>((size_t)nb + 1);
     w->filtered = a.take<unsigned char>(filtered_bytes);
+}
+static inline bool carve(void* ws, size_t bytes, int nb, size_t filtered_bytes, Work* w, size_t* used) {
+    Arena a(ws, bytes);
+    carve_into(a, nb, filtered_bytes, w);
     if (used) *used = a.off;
     return a.ok;
 }
@@ -711,6 +816,94 @@ static int run_filter(const unsigned char* src, size_t pitch, int H, int W, int 
 }
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
+
+// ---- many crops of one image -----------------------------------------------------------------------------------------------------
+// The band table of a list of rects, as the device reads it: one block of memory, [offs u64 (nb + 1)][bands TileBand nb]
+// [first u32 (nt + 1)][rects int 4 nt].
+struct TilePlan {
+    int rc;                       // CIAOSR_OK, or why the rects cannot be coded
+    int nt, nb;
+    u64 total;                    // bytes of all filtered streams
+    size_t capacity;              // bytes the streams can take at most
+    size_t o_bands, o_first, o_rects, table_bytes;
+};
+// `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
+static TilePlan plan_tiles(const int* rects, int n_tiles, int rows_arg, int H, int W, std::vector<unsigned char>* table) {
+    TilePlan t{};
+    t.rc = CIAOSR_ERR_BAD_ARG;
+    if (!rects || n_tiles < 1 || rows_arg < 0) return t;
+    u64 nb = 0, total = 0;
+    size_t cap = 0;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
+        if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
+        if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return t;
+        const u64 L = 3ull * w + 1;
+        const int R = rows_per_band(w, rows_arg);
+        if ((u64)R * L > kMaxBand) {
+            t.rc = CIAOSR_ERR_UNSUPPORTED;
+            return t;
+        }
+        nb += (u64)ceil_div(h, R);
+        total += (u64)h * L;
+        cap += capacity((size_t)h * L, ceil_div(h, R), true);
+    }
+    if (nb > (u64)INT_MAX / 2) {
+        t.rc = CIAOSR_ERR_UNSUPPORTED;
+        return t;
+    }
+    t.rc = CIAOSR_OK;
+    t.nt = n_tiles;
+    t.nb = (int)nb;
+    t.total = total;
+    t.capacity = cap;
+    t.o_bands = sizeof(u64) * ((size_t)nb + 1);
+    t.o_first = t.o_bands + sizeof(TileBand) * (size_t)nb;
+    t.o_rects = t.o_first + sizeof(u32) * ((size_t)n_tiles + 1);
+    t.table_bytes = t.o_rects + 4 * sizeof(int) * (size_t)n_tiles;
+    if (!table) return t;
+    table->resize(t.table_bytes);
+    u64* offs = reinterpret_cast<u64*>(table->data());
+    TileBand* bands = reinterpret_cast<TileBand*>(table->data() + t.o_bands);
+    u32* first = reinterpret_cast<u32*>(table->data() + t.o_first);
+    memcpy(table->data() + t.o_rects, rects, 4 * sizeof(int) * (size_t)n_tiles);
+    u64 off = 0;
+    int i = 0;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int h = rects[4 * k + 2], w = rects[4 * k + 3];
+        const u64 L = 3ull * w + 1;
+        const int R = rows_per_band(w, rows_arg);
+        first[k] = (u32)i;
+        for (int r0 = 0; r0 < h; r0 += R, ++i) {
+            const int r1 = r0 + R < h ? r0 + R : h;
+            offs[i] = off;
+            bands[i] = TileBand{k, r0, r1, r1 == h ? 1 : 0};
+            off += (u64)(r1 - r0) * L;
+        }
+    }
+    offs[i] = off;
+    first[n_tiles] = (u32)i;
+    return t;
+}
+
+struct TileWork {
+    Work w;
+    unsigned char* table;
+};
+static inline bool carve_tiles(void* ws, size_t bytes, const TilePlan& t, TileWork* w, size_t* used) {
+    Arena a(ws, bytes);
+    carve_into(a, t.nb, (size_t)t.total, &w->w);
+    w->table = a.take<unsigned char>(t.table_bytes);
+    if (used) *used = a.off;
+    return a.ok;
+}
+static inline size_t tile_work_bytes(const TilePlan& t) {
+    TileWork w;
+    size_t used = 0;
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    carve_tiles(origin, ~(size_t)0, t, &w, &used);
+    return used;
+}
 
 }  // namespace png
 }  // namespace ciaosr
@@ -804,4 +997,63 @@ extern "C" int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int 
     DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
                out, w.adler, total_bytes};
     return run_deflate(p, s);
+}
+
+extern "C" size_t ciaosr_png_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? tile_work_bytes(t) : 0;
+}
+
+extern "C" size_t ciaosr_png_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? t.capacity : 0;
+}
+
+extern "C" int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                          int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    std::vector<unsigned char> table;
+    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, H, W, &table);
+    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image
+    if (t.rc != CIAOSR_OK) return t.rc;
+    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
+    TileWork tw;
+    if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    const Work& w = tw.w;
+    hipStream_t s = (hipStream_t)stream;
+    // from pageable memory: the copy has left `table` when the call returns
+    if (hipMemcpyAsync(tw.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    const u64* offs = reinterpret_cast<const u64*>(tw.table);
+    const TileBand* bands = reinterpret_cast<const TileBand*>(tw.table + t.o_bands);
+    const u32* first = reinterpret_cast<const u32*>(tw.table + t.o_first);
+    const int* d_rects = reinterpret_cast<const int*>(tw.table + t.o_rects);
+    {
+        TileFilterP f{src, pitch, bgr, d_rects, bands, offs, w.filtered, w.hist, w.adler};
+        ProfScope prof("png_filter_tiles_u8", s);
+        hipLaunchKernelGGL(png_filter_tiles_kernel, dim3(t.nb), dim3(kThreads), 0, s, f);
+        int rc = launch_status("png_filter_tiles_u8");
+        if (rc) return rc;
+    }
+    DeflateP p{w.filtered, Bands{offs, 0ull, 0ull, t.nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 0ull, out,
+               w.adler, nullptr, bands};
+    {
+        ProfScope prof("deflate_plan", s);
+        hipLaunchKernelGGL(deflate_plan_kernel, dim3(t.nb), dim3(kWave), 0, s, p);
+        int rc = launch_status("deflate_plan");
+        if (rc) return rc;
+    }
+    {
+        TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
+        ProfScope prof("png_tiles_scan", s);
+        hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
+        int rc = launch_status("png_tiles_scan");
+        if (rc) return rc;
+    }
+    ProfScope prof("deflate_pack", s);
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3(t.nb), dim3(kThreads), 0, s, p);
+    return launch_status("deflate_pack");
 }

@@ -4,7 +4,8 @@ The device filters the scanlines (the usual minimum-sum-of-absolute-values rule,
 Huffman blocks of literals -- no LZ77 matches: on this content they gain nothing over filter + Huffman -- into one zlib stream.  The
 host only wraps that stream: signature, IHDR, IDAT chunks, IEND, with `zlib.crc32` for the chunk CRCs.  The files hold other bytes
 than Pillow's but decode to exactly the same pixels.  Two copies synchronise per image: the stream's size, then the stream.  There is
-no CPU fallback: a host array raises.
+no CPU fallback: a host array raises.  `encode_png_tiles` codes many crops of one image (the tiles of a pyramid level, pyramid.py) in
+one set of launches and two synchronising copies per call; each file is byte for byte the single call's on that crop.
 """
 import ctypes as C
 import os
@@ -138,6 +139,70 @@ def encode_png(img_u8_hwc, order='bgr', rows_per_band=0):
     (a crop view of a larger image).  `rows_per_band`: image rows per independently coded band, 0 = about 128 KiB of scanline bytes."""
     z = encode_zlib(img_u8_hwc, order, rows_per_band)
     return container(img_u8_hwc.shape[0], img_u8_hwc.shape[1], z)
+
+
+def check_rects(rects, h, w):
+    """[(y0, x0, h, w), ...] as ints; ValueError for an empty list, an empty rect or one that leaves the h x w image."""
+    out = []
+    for r in rects:
+        r = tuple(r)
+        if len(r) != 4 or any(int(v) != v for v in r):
+            raise ValueError(f'a rect is (y0, x0, h, w) in whole pixels, got {r!r}')
+        y0, x0, hh, ww = (int(v) for v in r)
+        if hh < 1 or ww < 1 or y0 < 0 or x0 < 0 or y0 + hh > h or x0 + ww > w:
+            raise ValueError(f'rect (y0, x0, h, w) = {(y0, x0, hh, ww)} is empty or outside the {h} x {w} image')
+        out.append((y0, x0, hh, ww))
+    if not out:
+        raise ValueError('no rects')
+    return out
+
+
+def encode_tiles_device(img, rects, order='bgr', rows_per_band=0):
+    """ciaosr_png_encode_tiles_u8 on the current stream, no synchronisation -> (streams uint8 [capacity], offsets int64 [n + 1]) on the
+    device: crop k's zlib stream is streams[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps."""
+    _check_image(img)
+    if order not in ORDERS:
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    rows = int(rows_per_band)
+    if rows < 0:
+        raise ValueError(f'rows_per_band={rows_per_band}')
+    h, w = img.shape[0], img.shape[1]
+    if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
+        raise CiaoSRHipError(f'encode_png_tiles: {h}x{w} is outside 1..{MAX_SIDE} per side')
+    rects = check_rects(rects, h, w)
+    n = len(rects)
+    dev = img.device
+    lib = _lib.load()
+    host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
+    cap = lib.ciaosr_png_tiles_capacity_bytes(host_rects, n, rows)
+    nbytes = lib.ciaosr_png_tiles_workspace_bytes(host_rects, n, rows)
+    if cap == 0 or nbytes == 0:
+        raise CiaoSRHipError(f'encode_png_tiles: unsupported geometry ({n} rects, rows_per_band={rows})')
+    ws = hip_ops.workspace(nbytes, dev, slot='png')
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _lib.call('ciaosr_png_encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, rows,
+              hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(offs), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    return out, offs
+
+
+def encode_zlib_tiles(img, rects, order='bgr', rows_per_band=0):
+    """The zlib streams of many crops (y0, x0, h, w) of one device image, from ONE set of launches -> list of bytes; stream k is byte
+    for byte `encode_zlib(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call, whatever the number of crops: the offsets
+    table, then the streams."""
+    out, offs = encode_tiles_device(img, rects, order, rows_per_band)
+    o = offs.cpu().tolist()                                 # copy 1: the offsets
+    raw = memoryview(out[:o[-1]].cpu().numpy())             # copy 2: the streams
+    return [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
+
+
+def encode_png_tiles(img_u8_hwc, rects, order='bgr', rows_per_band=0):
+    """PNG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] device image, coded together: file k
+    is byte for byte `encode_png(img[y0:y0 + h, x0:x0 + w], order, rows_per_band)`.  The rects may overlap.  A bad rect is a
+    ValueError before any device work; two synchronising copies per call."""
+    rects = list(rects)
+    zs = encode_zlib_tiles(img_u8_hwc, rects, order, rows_per_band)
+    return [container(int(r[2]), int(r[3]), z) for r, z in zip(rects, zs)]
 
 
 def imwrite_gpu(img_u8_hwc, path, order='bgr'):

@@ -1,0 +1,104 @@
+"""Deep Zoom tile pyramids (`<name>.dzi` + `<name>_files/<level>/<col>_<row>.png`, as OpenSeadragon and libvips read them) of an encoded
+scene.  The plan and the manifest are pure host code; `write_dzi` renders every level with `CiaoSR.render_pyramid` -- the levels at or
+above the LR size are the model's own answer at that size, all from one walk over the tile scenes -- and codes each level's tiles with
+ONE `png_hip.encode_png_tiles` call: two synchronising copies per level, whatever its number of tiles.
+
+Deep Zoom's rules: Lmax = ceil(log2(max(W, H))), levels 0..Lmax; level L is max(1, ceil(W / 2^(Lmax - L))) wide and as high by the same
+rule; on a level, column c spans [c T - (O if c > 0 else 0), min((c + 1) T + O, Wl)) for the tile size T and the overlap O, rows alike,
+ceil(Wl / T) columns.
+"""
+import os
+import time
+
+DZI_NS = 'http://schemas.microsoft.com/deepzoom/2008'
+
+
+def level_sizes(height, width):
+    """[(H_l, W_l)] of the levels 0..Lmax of a height x width image."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError(f'empty image {height} x {width}')
+    lmax = (max(width, height) - 1).bit_length()                # ceil(log2(.)), exact in integers
+    return [(max(1, (height + (1 << k) - 1) >> k), max(1, (width + (1 << k) - 1) >> k)) for k in range(lmax, -1, -1)]
+
+
+def _check_tiling(tile_size, overlap):
+    if int(tile_size) != tile_size or int(overlap) != overlap:
+        raise ValueError(f'tile_size={tile_size!r} and overlap={overlap!r} are whole pixels')
+    tile_size, overlap = int(tile_size), int(overlap)
+    if tile_size < 1 or overlap < 0 or overlap >= tile_size:
+        raise ValueError(f'tile_size={tile_size}, overlap={overlap}: need tile_size >= 1 and 0 <= overlap < tile_size')
+    return tile_size, overlap
+
+
+def spans(n, tile_size, overlap):
+    """[(start, length)] of the columns (or rows) of a level n pixels wide (high)."""
+    return [(c * tile_size - (overlap if c > 0 else 0),
+             min((c + 1) * tile_size + overlap, n) - (c * tile_size - (overlap if c > 0 else 0)))
+            for c in range(-(-n // tile_size))]
+
+
+def dzi_plan(height, width, tile_size=254, overlap=1):
+    """The levels of a height x width image, level 0 (1 x 1) first: [dict(level, height, width, tiles)], tiles = [(col, row, y0, x0, h, w)]
+    row-major."""
+    tile_size, overlap = _check_tiling(tile_size, overlap)
+    plan = []
+    for level, (hl, wl) in enumerate(level_sizes(height, width)):
+        cols, rows = spans(wl, tile_size, overlap), spans(hl, tile_size, overlap)
+        tiles = [(c, r, y0, x0, h, w) for r, (y0, h) in enumerate(rows) for c, (x0, w) in enumerate(cols)]
+        plan.append(dict(level=level, height=hl, width=wl, tiles=tiles))
+    return plan
+
+
+def dzi_manifest(height, width, tile_size=254, overlap=1):
+    """The `.dzi` file's XML for a height x width top level."""
+    tile_size, overlap = _check_tiling(tile_size, overlap)
+    if int(height) < 1 or int(width) < 1:
+        raise ValueError(f'empty image {height} x {width}')
+    return (f'<?xml version="1.0" encoding="UTF-8"?><Image xmlns="{DZI_NS}" Format="png" Overlap="{overlap}" TileSize="{tile_size}">'
+            f'<Size Width="{int(width)}" Height="{int(height)}"/></Image>')
+
+
+def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr'):
+    """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
+    returns them): one `encode_png_tiles` call per level.  -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
+    from .png_hip import encode_png_tiles
+    top = levels[-1]
+    plan = dzi_plan(top.shape[0], top.shape[1], tile_size, overlap)
+    if [(lv['height'], lv['width']) for lv in plan] != [(im.shape[0], im.shape[1]) for im in levels]:
+        raise ValueError(f'the images are not the levels of a {top.shape[0]} x {top.shape[1]} pyramid')
+    manifest = dzi_manifest(top.shape[0], top.shape[1], tile_size, overlap).encode()
+    os.makedirs(out_dir, exist_ok=True)
+    files, nbytes, t_enc, t_write = 1, len(manifest), 0.0, 0.0
+    with open(os.path.join(out_dir, f'{name}.dzi'), 'wb') as f:
+        f.write(manifest)
+    for lv, img in zip(plan, levels):
+        t0 = time.perf_counter()
+        pngs = encode_png_tiles(img, [t[2:] for t in lv['tiles']], order=order)
+        t1 = time.perf_counter()
+        folder = os.path.join(out_dir, f'{name}_files', str(lv['level']))
+        os.makedirs(folder, exist_ok=True)
+        for (col, row, *_), data in zip(lv['tiles'], pngs):
+            with open(os.path.join(folder, f'{col}_{row}.png'), 'wb') as f:
+                f.write(data)
+            nbytes += len(data)
+        files += len(pngs)
+        t_enc += t1 - t0
+        t_write += time.perf_counter() - t1
+    return dict(files=files, bytes=nbytes, encode_s=t_enc, write_s=t_write)
+
+
+def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, overlap=1, order='bgr'):
+    """`<out_dir>/<name>.dzi` and `<out_dir>/<name>_files/<level>/<col>_<row>.png` of the `size` / `scale` render of `enc` (an
+    `encode` result of `model`).  `order`: the byte order of the rendered images, 'bgr' as `render_pyramid` makes them.
+    -> dict: levels [(H_l, W_l)], model_levels (the levels rendered by the model; the ones below are Pillow-exact bicubic resizes of
+    the smallest of them), files, bytes, and the seconds spent in render_s (to the last launch, not synchronised), encode_s, write_s."""
+    _check_tiling(tile_size, overlap)
+    t0 = time.perf_counter()
+    levels = model.render_pyramid(enc, size=size, scale=scale)
+    render_s = time.perf_counter() - t0
+    h, w = enc.x.shape[-2:]
+    sizes = [(im.shape[0], im.shape[1]) for im in levels]
+    res = write_levels(levels, out_dir, name, tile_size, overlap, order)
+    res.update(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w], render_s=render_s)
+    return res

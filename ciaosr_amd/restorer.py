@@ -772,6 +772,38 @@ class CiaoSR(BasicRestorer):
                 break
         return built
 
+    # -- every level of a tile pyramid (pyramid.py) -------------------------------------------------------------------------------------
+    def _plan_pyramid(self, enc, size=None, scale=None):
+        """The level sizes of `render_pyramid` and the index of the smallest model level; its ValueErrors.  Pure host work."""
+        from . import pyramid
+        from . import scene as sc
+        nb, _, h, w = enc.x.shape
+        if nb != 1:
+            raise ValueError(f'render_pyramid takes one image, got a batch of {nb}')
+        ht, wt = sc.target_size(h, w, size, scale)
+        if ht < h or wt < w:
+            raise ValueError(f'the top level {ht} x {wt} is smaller than the LR image {h} x {w}: the model renders no scale below 1')
+        if self.test_cfg.get('tile', None) and not self.test_cfg.get('tile_any_scale', False):
+            raise ValueError('render_pyramid with test_cfg.tile needs test_cfg.tile_any_scale: the levels are not the integer-scale '
+                             'rectangles of clip_test')
+        sizes = pyramid.level_sizes(ht, wt)
+        return sizes, min(k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w)
+
+    @torch.no_grad()
+    def render_pyramid(self, enc, size=None, scale=None):
+        """The levels of the Deep Zoom pyramid (pyramid.py) whose top is the `size` / `scale` render of `enc`: list of uint8 [H_l, W_l, 3]
+        device images (`render(..., as_u8=True)`'s), level 0 (1 x 1) first.  A level at least as large as the LR image on both sides is a
+        model level: all of them are Grid(size=(H_l, W_l)) targets of ONE `render_many`, hence one walk over the tile scenes, and each is
+        bitwise `render(enc, size=(H_l, W_l), as_u8=True)`.  Every smaller level is `degrade.resize_bicubic_u8` -- Pillow's BICUBIC
+        resize, exactly -- of the smallest model level, each taken from it directly.  ValueError before any device work: a batch, a top
+        level below the LR size, `test_cfg.tile` without `tile_any_scale`, and whatever `scene.Grid` raises."""
+        from . import degrade
+        from . import scene as sc
+        sizes, first = self._plan_pyramid(enc, size, scale)
+        model_levels = self.render_many(enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
+        base = model_levels[0]
+        return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)
+
     def _restore(self, lq, coord=None, cell=None, options=None):
         x = self.normalize(lq)
         if self.test_cfg.get('tile', None) and self.test_cfg.get('tile_any_scale', False) and coord is not None:

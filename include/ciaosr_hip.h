@@ -801,6 +801,24 @@ size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band);
 size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band);
 int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
                          size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* Many crops of one image in one set of launches (tile pyramids: ciaosr_amd/pyramid.py).  rects: HOST array [n_tiles][4] = y0, x0, h, w,
+ * each non-empty and inside H x W; they may overlap.  Tile t's bytes out[tile_offs[t] : tile_offs[t + 1]] are one complete zlib stream,
+ * byte for byte what ciaosr_png_encode_u8 returns for the pitched crop src + y0 * pitch + 3 * x0, pitch, h, w with the same
+ * rows_per_band: the pixels left of a tile's first column and above its first row count as zeros, a tile's bands are
+ * ciaosr_png_rows_per_band(w, rows_per_band) of ITS rows, the stored fallback and BFINAL are decided per tile.  tile_offs (DEVICE,
+ * [n_tiles + 1], 8-byte aligned): tile_offs[0] = 0, the streams lie back to back without padding, tile_offs[n_tiles] is the total.  The
+ * host reads tile_offs, then the streams: two synchronising copies per call, whatever n_tiles.  The band table built from the rects
+ * (per band: tile, rows, 64-bit offset in the filtered streams) reaches the device by a copy on `stream` from pageable memory.  Four
+ * launches: filter, plan, a segmented scan (one workgroup; sizes, a prefix sum over tiles, every band's offset, each tile's header and
+ * its Adler-32 from its own bands' partials), pack.  No two workgroups write the same byte, the output is bitwise repeatable, nothing
+ * needs zeroing, nothing is allocated.  An empty rect, one that leaves the image, n_tiles < 1 or a null pointer: CIAOSR_ERR_BAD_ARG
+ * before any launch; a short out (ciaosr_png_tiles_capacity_bytes) or workspace (ciaosr_png_tiles_workspace_bytes: the filtered
+ * crops, 2.4 KB per band, the table): CIAOSR_ERR_WORKSPACE.  The two size functions return 0 for rects they cannot take. */
+size_t ciaosr_png_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                               int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

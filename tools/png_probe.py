@@ -8,7 +8,19 @@ device leg: `png_hip.imwrite_gpu(img, path)` (csrc/png_u8.hip + the container on
 Images: `init_utils.synthetic_gt` quantised by `tensor2img_u8`, as is ('smooth') and with 2 grey levels of noise ('noisy').  The legs
 alternate in one process; wall time runs from the device image (after a synchronize) to the closed file.  Device time per kernel comes
 from `hip_ops.profile` in a round of its own.  The files of both writers are decoded and compared, and their sizes recorded.
+
+    python tools/png_probe.py --leg tiles [--parent-root DIR] [--dzi] [--sizes 5424x8160] [--tile 254] [--overlap 1] [--out FILE]
+
+times the tiles of a pyramid's top level (ciaosr_amd/pyramid.py) and writes profiles/png_tiles.txt:
+(a) one `encode_png` per tile on the pitched crops -- with `--parent-root DIR` (a built checkout of the parent commit) from that tree's
+    library, in a child process that stays up for the whole run and takes its turn in every round; otherwise in this process;
+(b) one `encode_png_tiles` call;  (c) the whole image in one `encode_png`, for scale.
+Wall time runs from the device image (after a synchronize) to the bytes on the host; the legs alternate; kernel time is the sum over
+`hip_ops.profile` of a round of its own.  The files of (a) and (b) are compared byte for byte.  `--dzi` adds one full pyramid of the
+bench output (config 001, LR 1356 x 2040, x4) from a ready encode, split into render, encode and file writing.
 """
+import json
+import subprocess
 import argparse
 import os
 import statistics
@@ -34,15 +46,193 @@ def make_image(h, w, content, dev):
     return img.contiguous()
 
 
+def top_rects(h, w, tile, overlap):
+    """(y0, x0, h, w) of the tiles of a pyramid's top level (pyramid.dzi_plan's rule, restated: the parent tree has no pyramid.py)."""
+    def spans(n):
+        return [(c * tile - (overlap if c else 0), min((c + 1) * tile + overlap, n) - (c * tile - (overlap if c else 0)))
+                for c in range(-(-n // tile))]
+    return [(y0, x0, hh, ww) for y0, hh in spans(h) for x0, ww in spans(w)]
+
+
+class PerTile:
+    """Leg (a): one `encode_png` per rect, on the tree this process imports."""
+
+    def __init__(self):
+        self.img, self.rects = None, None
+
+    def setup(self, h, w, content, rects):
+        self.img = make_image(h, w, content, torch.device('cuda', torch.cuda.current_device()))
+        self.rects = [tuple(r) for r in rects]
+        torch.cuda.synchronize()
+        return True
+
+    def files(self):
+        from ciaosr_amd.png_hip import encode_png
+        return [encode_png(self.img[y0:y0 + h, x0:x0 + w]) for y0, x0, h, w in self.rects]
+
+    def round(self):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        self.files()
+        return time.perf_counter() - t0
+
+    def kernels(self):
+        from ciaosr_amd import hip_ops
+        with hip_ops.profile():
+            self.files()
+        prof = hip_ops.profile.results()
+        return dict(ms=sum(v['total_ms'] for v in prof.values()), launches=sum(v['launches'] for v in prof.values()))
+
+    def digest(self):
+        import hashlib
+        return hashlib.sha256(b''.join(self.files())).hexdigest()
+
+    def header(self):
+        from ciaosr_amd import _lib
+        return dict(version=_lib.load().ciaosr_version(), tiles_entry_point=hasattr(_lib.load(), 'ciaosr_png_encode_tiles_u8'))
+
+
+def serve():
+    """The parent-tree child: one JSON line per command line {cmd, args}; EOF ends it."""
+    leg = PerTile()
+    for line in sys.stdin:
+        req = json.loads(line)
+        print(json.dumps(getattr(leg, req['cmd'])(*req.get('args', []))), flush=True)
+    return 0
+
+
+class Child:
+    def __init__(self, root):
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--worker', '--root', os.path.abspath(root)], stdin=subprocess.PIPE,
+                                  stdout=subprocess.PIPE, text=True)
+
+    def __getattr__(self, cmd):
+        def ask(*args):
+            self.p.stdin.write(json.dumps(dict(cmd=cmd, args=list(args))) + '\n')
+            self.p.stdin.flush()
+            line = self.p.stdout.readline()
+            if not line:
+                raise SystemExit(f'parent-tree child ended (exit status {self.p.wait()}) at {cmd!r}')
+            return json.loads(line)
+        return ask
+
+    def close(self):
+        self.p.stdin.close()
+        self.p.wait(timeout=60)
+
+
+def stats(t):
+    return f'mean {statistics.mean(t):.4f}, min {min(t):.4f}, max {max(t):.4f}  [{" ".join(f"{v:.4f}" for v in t)}]'
+
+
+def tiles_leg(args, say):
+    import hashlib
+    from ciaosr_amd import hip_ops
+    from ciaosr_amd.png_hip import encode_png, encode_png_tiles
+    dev = torch.device('cuda', torch.cuda.current_device())
+    a = Child(args.parent_root) if args.parent_root else PerTile()
+    where = 'parent commit, child process' if args.parent_root else 'this tree, this process'
+    if args.parent_root:
+        say(f'leg (a) runs the parent tree\'s library: {a.header()}')
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        rects = top_rects(h, w, args.tile, args.overlap)
+        for content in args.contents:
+            img = make_image(h, w, content, dev)
+            a.setup(h, w, content, rects)
+            torch.cuda.synchronize()
+            legs = {'b': lambda: encode_png_tiles(img, rects), 'c': lambda: encode_png(img)}
+            times = dict(a=[], b=[], c=[])
+            for r in range(args.warmup + args.rounds):
+                took = dict(a=a.round())
+                for name in ('b', 'c'):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    legs[name]()
+                    took[name] = time.perf_counter() - t0
+                if r >= args.warmup:
+                    for k, v in took.items():
+                        times[k].append(v)
+                print(f'  {size} {content} round {r}: ' + ', '.join(f'({k}) {v:.4f} s' for k, v in took.items()), flush=True)
+            kern = dict(a=a.kernels())
+            for name in ('b', 'c'):
+                with hip_ops.profile():
+                    out = legs[name]()
+                prof = hip_ops.profile.results()
+                kern[name] = dict(ms=sum(v['total_ms'] for v in prof.values()), launches=sum(v['launches'] for v in prof.values()))
+                if name == 'b':
+                    same = hashlib.sha256(b''.join(out)).hexdigest() == a.digest()
+                    nbytes = sum(len(f) for f in out)
+                    detail = ', '.join(f'{k} {v["total_ms"]:.3f}' for k, v in sorted(prof.items()))
+            say(f'{h} x {w} {content}, top level at {args.tile}+{args.overlap}: {len(rects)} tiles, {nbytes} bytes of files; '
+                f'(a) and (b) byte for byte identical: {same}')
+            say(f'  (a) encode_png per tile ({where}) wall s: {stats(times["a"])}; kernels {kern["a"]["ms"]:.3f} ms in {kern["a"]["launches"]} launches')
+            say(f'  (b) encode_png_tiles, one call wall s: {stats(times["b"])}; kernels {kern["b"]["ms"]:.3f} ms in {kern["b"]["launches"]} launches')
+            say(f'  (c) encode_png, whole image   wall s: {stats(times["c"])}; kernels {kern["c"]["ms"]:.3f} ms in {kern["c"]["launches"]} launches')
+            gap = statistics.mean(times['a']) - statistics.mean(times['b'])
+            spread = max(max(times[k]) - min(times[k]) for k in ('a', 'b'))
+            say(f'  (a) - (b) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                f'{"one call faster beyond the spread" if gap > spread else "NOT separated"}; '
+                f'ratio {statistics.mean(times["a"]) / statistics.mean(times["b"]):.1f}x')
+            say(f'  (b) kernels, ms: {detail}')
+            del img
+    if args.parent_root:
+        a.close()
+    if args.dzi:
+        dzi_leg(args, say)
+
+
+def dzi_leg(args, say):
+    """One full pyramid of the bench output from a ready encode: render (synchronised), encode, file writing."""
+    import ciaosr_amd
+    from ciaosr_amd.config import Config
+    from ciaosr_amd.init_utils import seeded_init_, synthetic_pair
+    from ciaosr_amd.pyramid import write_levels
+    dev = torch.device('cuda', torch.cuda.current_device())
+    cfg = Config.fromfile(os.path.join(REPO, 'configs', '001_localimplicitsr_edsr_div2k_g1_c64b16_1000k_unfold_lec_mulwkv_res_nonlocal.py'))
+    cfg.test_cfg['tile_any_scale'] = True
+    model = ciaosr_amd.build_model(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
+    seeded_init_(model, seed=0, gain=1.25, head_gain=6 ** 0.5)
+    model = model.to(dev).eval()
+    lq = synthetic_pair(1356, 2040, 4)[0].to(dev)
+    enc = model.encode(lq, max_scale=4)
+    torch.cuda.synchronize()
+    with tempfile.TemporaryDirectory() as tmp:
+        t0 = time.perf_counter()
+        levels = model.render_pyramid(enc, scale=4)
+        torch.cuda.synchronize()
+        render_s = time.perf_counter() - t0
+        res = write_levels(levels, tmp, 'bench', args.tile, args.overlap)
+    h, w = lq.shape[-2:]
+    n_model = sum(1 for im in levels if im.shape[0] >= h and im.shape[1] >= w)
+    say(f'write_dzi of the bench output (LR {h} x {w}, x4, {args.tile}+{args.overlap}; fp32, tile 192 / 32 with tile_any_scale; one run, scenes built '
+        f'during the render): {len(levels)} levels, {n_model} from the model, {res["files"]} files, {res["bytes"]} bytes; render {render_s:.3f} s '
+        f'({enc.cache.builds} scene builds), encode {res["encode_s"]:.3f} s, file writing {res["write_s"]:.3f} s')
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--sizes', nargs='+', default=['5424x8160', '768x768'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles'])
+    p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
+    p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
+    p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
+    p.add_argument('--dzi', action='store_true', help='tiles: also one full write_dzi of the bench output')
+    p.add_argument('--tile', type=int, default=254)
+    p.add_argument('--overlap', type=int, default=1)
+    p.add_argument('--sizes', nargs='+', default=None)
     p.add_argument('--contents', nargs='+', default=['smooth', 'noisy'], choices=['smooth', 'noisy'])
     p.add_argument('--warmup', type=int, default=2)
     p.add_argument('--rounds', type=int, default=5)
-    p.add_argument('--out', default=os.path.join(REPO, 'profiles', 'png_gpu.txt'))
+    p.add_argument('--out', default=None)
     p.add_argument('--append', action='store_true', help='add to --out instead of replacing it (a run split over several calls)')
     args = p.parse_args(argv)
+    if args.root:
+        sys.path.insert(0, args.root)
+    if args.worker:
+        return serve()
+    tiles = args.leg == 'tiles'
+    args.sizes = args.sizes or (['5424x8160'] if tiles else ['5424x8160', '768x768'])
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_gpu.txt')
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -53,10 +243,12 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    say(f'tools/png_probe.py --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
+    say(f'tools/png_probe.py{" --leg tiles" if tiles else ""} --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
         f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, {os.cpu_count()} host CPUs visible')
+    if tiles:
+        tiles_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
-        for size in args.sizes:
+        for size in ([] if tiles else args.sizes):
             h, w = (int(v) for v in size.split('x'))
             for content in args.contents:
                 img = make_image(h, w, content, dev)

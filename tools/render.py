@@ -18,6 +18,10 @@ pixels per LR pixel, turned by ANGLE degrees (positive: the picture turns clockw
 the files decode to the pixels of the default run.
 `--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
 queried in 4 x 2 blocks of output pixels, which keeps the head on its chained kernel; other precisions are unaffected.
+`--dzi SCALE [--dzi-tile 254] [--dzi-overlap 1]` also writes the Deep Zoom pyramid of the SCALE render (ciaosr_amd/pyramid.py): DIR/<image
+name>.dzi and DIR/<image name>_files/<level>/<col>_<row>.png, every level at or above the LR size rendered by the model from the same
+encode, each level's tiles PNG-encoded on the device in one call (always the device encoder, with or without `--gpu-png`); alone or next
+to --scale / --view outputs, which it does not change.  `--max-scale` then defaults to cover SCALE as well.
 """
 import argparse
 import os
@@ -44,11 +48,15 @@ def parse_args(argv=None):
                    help='test_cfg.view_blocks: the 16-bit modes select a cut view\'s members in 4 x 2 blocks of output pixels (default off)')
     p.add_argument('--gpu-png', action='store_true',
                    help='test_cfg.gpu_png: outputs are quantised and PNG-encoded on the GPU; no fp32 image crosses to the host (default off)')
-    p.add_argument('--max-scale', type=float, default=None, help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM)')
+    p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
+    p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
+    p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
+    p.add_argument('--max-scale', type=float, default=None,
+                   help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM; with --dzi at least its SCALE)')
     p.add_argument('--out', required=True, help='output directory')
     args = p.parse_args(argv)
-    if not args.scale and not args.view:
-        p.error('give --scale, --view or both')
+    if not args.scale and not args.view and args.dzi is None:
+        p.error('give --scale, --view, --dzi or several of them')
     if args.view and len(args.size) not in (1, len(args.view)):
         p.error('give one --size H W per --view, or a single one for all views')
     if args.size and not args.view:
@@ -86,7 +94,10 @@ def main(argv=None):
     model = model.to(dev).eval()
 
     lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
-    enc = model.encode(lq, max_scale=args.max_scale or max(args.scale or [v[2] for v in args.view]))
+    wanted = args.scale or [v[2] for v in args.view]
+    if args.dzi is not None:
+        wanted = wanted + [args.dzi]
+    enc = model.encode(lq, max_scale=args.max_scale or max(wanted))
     name = os.path.splitext(os.path.basename(args.image))[0]
     from ciaosr_amd.scene import Grid, View, view_matrix
     targets = [Grid(scale=s, window=args.window) for s in args.scale]
@@ -96,7 +107,8 @@ def main(argv=None):
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}.png'))
     gpu_png = model.gpu_png()
-    for path, out in zip(paths, model.render_many(enc, targets, as_u8=gpu_png)):      # one walk over the tile scenes for every output
+    outs = model.render_many(enc, targets, as_u8=gpu_png) if targets else []         # one walk over the tile scenes for every output
+    for path, out in zip(paths, outs):
         if gpu_png:
             from ciaosr_amd.png_hip import imwrite_gpu
             imwrite_gpu(out, path)                                     # uint8 [H, W, 3] BGR on the device
@@ -104,6 +116,12 @@ def main(argv=None):
         else:
             imwrite(metrics.tensor2img(out), path)
             print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
+    if args.dzi is not None:
+        from ciaosr_amd.pyramid import write_dzi
+        res = write_dzi(model, enc, args.out, name, scale=args.dzi, tile_size=args.dzi_tile, overlap=args.dzi_overlap)
+        top = res['levels'][-1]
+        print(f"{os.path.join(args.out, name + '.dzi')}: {top[0]} x {top[1]}, {len(res['levels'])} levels ({len(res['model_levels'])} from the "
+              f"model), {res['files']} files, {res['bytes']} bytes")
     return paths
 
 
