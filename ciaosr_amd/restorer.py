@@ -5,6 +5,7 @@ mmedited/models/restorers/ciaosr.py:36-58 (`__init__`), :111-203 (`forward_test`
 (`clip_test`).  Normalisation, tile blending and de-normalisation run as HIP kernels; tiles are
 the unit sharded across GPUs (ciaosr_amd/tile_shard.py).  Training entry points are out of scope.
 """
+import contextlib
 import math
 import numbers
 import os.path as osp
@@ -12,7 +13,7 @@ import os.path as osp
 import torch
 import torch.nn as nn
 
-from . import hip_ops, metrics
+from . import hip_ops, metrics, scene, scene_render
 from .registry import build_backbone, build_loss
 
 
@@ -136,6 +137,12 @@ SWIN_TILE_BATCH = 4
 EDSR_TILE_BATCH = 8
 
 
+def effective_options(generator, options):
+    """The options this generator really runs with: what `generator.forward` would turn `options` into, so that a tile loop that calls
+    the trunk and the head itself shows both the same options."""
+    return generator.effective_options(options) if hasattr(generator, 'effective_options') else options
+
+
 def trunk_batches(generator, options):
     """Whether the tile loops feed this generator's trunk batches of tiles: it has a `forward_hwc_batch`, and -- where the trunk says
     so itself (PackedSwinIR.batches: only the opt-in f16-linear trunk shares launches) -- the options make it batch.  The options are
@@ -145,9 +152,7 @@ def trunk_batches(generator, options):
         return False
     if not hasattr(enc, 'batches'):
         return True
-    if hasattr(generator, 'effective_options'):
-        options = generator.effective_options(options)
-    return enc.batches(options)
+    return enc.batches(effective_options(generator, options))
 
 
 class CiaoSR(BasicRestorer):
@@ -196,14 +201,25 @@ class CiaoSR(BasicRestorer):
         cell = cell.unsqueeze(0).expand(n, -1, 2)
         return self.generator(patch, coord, cell, test_mode=True, options=self.options(options)), (th, tw)
 
+    def trunk_tiles(self, x_norm, origins, tile, options):
+        """The trunk half of `run_tiles`, for a tile loop that runs the heads itself (`head_tile`): the stacked crops through one trunk
+        call under the generator's `effective_options` -> (patches [n, 3, tile, tile], channels-last feature maps [n, tile, tile, C])."""
+        patches = torch.cat([x_norm[..., hi:hi + tile, wi:wi + tile] for (hi, wi) in origins], 0).contiguous().float()
+        return patches, self.generator._encoder_hip.forward_hwc_batch(patches, options)
+
+    def head_tile(self, patch, feat, sf, options):
+        """The head of one tile from its crop [3, th, tw] and feature map: -> ([th*sf * tw*sf, 3], (th*sf, tw*sf)), bitwise run_tile's."""
+        gen = self.generator
+        th, tw = round(patch.shape[-2] * sf), round(patch.shape[-1] * sf)
+        coord, cell = hip_ops.make_coord_cell(th, tw, patch.device)
+        return gen._head.forward(None, patch, coord, cell, gen.eval_bsize, feature_hwc=feat, options=options), (th, tw)
+
     def prepare(self, options=None):
         """Pack every weight the call's precision reads NOW, on the current stream (idempotent; re-packs only what changed) --
         including the 16-bit fragment copies of a 'bf16' / 'f16' call, which are otherwise packed lazily on first use.
         The tile loop runs tiles on several streams: nothing a tile reads may be first built on another tile's stream."""
-        opt = self.options(options)
         gen = self.generator
-        if hasattr(gen, 'effective_options'):
-            opt = gen.effective_options(opt)
+        opt = effective_options(gen, self.options(options))
         head = getattr(gen, '_head', None)
         enc = getattr(gen, '_encoder_hip', None)
         if enc is not None and enc.supported():
@@ -226,7 +242,7 @@ class CiaoSR(BasicRestorer):
         bitwise the single-stream result.  `tile_streams` is off by default because per-kernel event timings (bench.py's
         roofline leg, rocprof) are meaningless while two streams share the chip.
 
-        `test_cfg.encoder_ahead` (default TRUE since round 5, see `_clip_test_encoder_ahead`) DOES put a second stream under an
+        `test_cfg.encoder_ahead` (default TRUE since round 5, see `trunk_ahead`) DOES put a second stream under an
         image of more than `tile_batch` tiles: the next batch's trunk runs on a cached side stream (fork / join by events,
         `record_stream` on the hand-over buffers, two batches of feature maps live).  Bitwise the one-stream image; set
         `test_cfg.encoder_ahead = False` for per-kernel timing, rocprof attribution of a multi-batch image, or when calling under
@@ -242,13 +258,19 @@ class CiaoSR(BasicRestorer):
                 trunk_batches(self.generator, self.options(options))):
             # `test_cfg.tile_batch` (an extension; default 7 or 8, see tile_batch()) consecutive tiles share the encoder's dense-layer launches; every tile
             # is bitwise the one-at-a-time result and the blend order is the reference's
-            if self.test_cfg.get('encoder_ahead', True) and len(origins) > n_batch and getattr(self.generator, '_head', None) is not None:
-                return self._clip_test_encoder_ahead(img_lq, tile, origins, n_batch, sf, E, Wt, options)
-            for i0 in range(0, len(origins), n_batch):
-                group = origins[i0:i0 + n_batch]
-                outs, (th, tw) = self.run_tiles(img_lq, group, tile, sf, options)
-                for (hi, wi), out in zip(group, outs):
-                    hip_ops.tile_blend(E[0], Wt[0], out.contiguous(), hi * sf, wi * sf, th, tw)
+            gen = self.generator
+            opt = effective_options(gen, self.options(options))      # the trunk and the head see the same options
+            gen._require_hip_trunk(img_lq)                           # an uncovered trunk raises CiaoSRHipError here, not a C-level argument error
+            groups = [origins[i0:i0 + n_batch] for i0 in range(0, len(origins), n_batch)]
+            ahead = bool(self.test_cfg.get('encoder_ahead', True)) and len(groups) > 1
+            with contextlib.closing(self.trunk_ahead(groups, lambda group: self.trunk_tiles(img_lq, group, tile, opt), ahead, opt,
+                                                     img_lq.device)) as trunks:
+                for group in groups:
+                    patches, feats = next(trunks)
+                    for j, (hi, wi) in enumerate(group):
+                        out, (th, tw) = self.head_tile(patches[j], feats[j], sf, opt)
+                        hip_ops.tile_blend(E[0], Wt[0], out.contiguous(), hi * sf, wi * sf, th, tw)
+                    del patches, feats                               # before the next trunk is launched: two groups' feature maps live, not three
             return torch.stack([hip_ops.tile_finalize(E[0], Wt[0])])
         if tile_fn is not None or n_streams <= 1 or len(origins) < 2 or not img_lq.is_cuda:
             for (hi, wi) in origins:
@@ -288,49 +310,47 @@ class CiaoSR(BasicRestorer):
             cur.wait_stream(st)
         return torch.stack([hip_ops.tile_finalize(E[bi], Wt[bi]) for bi in range(b)])
 
-    def _clip_test_encoder_ahead(self, img_lq, tile, origins, n_batch, sf, E, Wt, options):
-        """`test_cfg.encoder_ahead` (an extension; ON by default since round 5 for images of more than one tile batch -- a product default is
-        not chosen for the profiler's convenience: bench.py times its step with it and takes its per-kernel event timings in a separate
-        pass with `encoder_ahead = False`, where no second stream shares the chip): the RDN trunk of tile batch k + 1 runs on a side stream
-        UNDER the heads of batch k (cs_attn + fused head kernels, the caller's stream).  The trunk's 130 strictly dependent launches per batch
-        and the heads' long MFMA kernels fill each other's ramp / drain / memory phases.  Same kernels on the same data in the same
-        per-tile order: the image is bitwise the default path's."""
-        gen = self.generator
-        opt = self.options(options)
-        if hasattr(gen, 'effective_options'):
-            opt = gen.effective_options(opt)                 # what gen.forward would run with: the trunk and the head see the same options
-        gen._require_hip_trunk(img_lq)                       # an uncovered trunk raises CiaoSRHipError here, not a C-level argument error
-        enc = gen._encoder_hip
-        dev = img_lq.device
-        cur = torch.cuda.current_stream(dev)
-        self.prepare(opt)
-        th = tw = round(tile * sf)
-        coord, cell = hip_ops.make_coord_cell(th, tw, dev)
-        side = self._tile_streams(1, dev)[0]
+    def trunk_ahead(self, groups, trunk, ahead, options, device):
+        """The one trunk-ahead pipeline of the tile loops: yield `trunk(group)` -- a tuple of the tensors (or lists of tensors) a group's trunk hands over to its heads --
+        for every group of `groups`, in order; a group's trunk is first launched when the group is first asked for.  Without `ahead`
+        that is all, on the caller's stream.  With `ahead` (`test_cfg.encoder_ahead`, an extension; ON by default since round 5 for more
+        than one group) the trunk of group g + 1 is queued on the cached side stream right behind group g's, so it runs UNDER the heads
+        of group g (cs_attn + fused head kernels, or a scene's prepares and queries) on the caller's stream: the trunk's 130 strictly
+        dependent launches per group and the heads' long MFMA kernels fill each other's ramp / drain / memory phases.  `prepare(options)`
+        runs first, so that nothing the side stream reads is first packed there; the side stream forks from the caller's, which waits
+        on each group's event, every handed-over tensor gets `record_stream`, and the caller's stream joins the side stream when the
+        generator ends or is closed.  Same kernels on the same data in the same per-tile order: bitwise the one-stream result."""
+        if not ahead:
+            for group in groups:
+                yield trunk(group)
+            return
+        cur = torch.cuda.current_stream(device)
+        self.prepare(options)
+        side = self._tile_streams(1, device)[0]
         side.wait_stream(cur)
-        groups = [origins[i0:i0 + n_batch] for i0 in range(0, len(origins), n_batch)]
 
-        def trunk(group):
+        def launch(group):
             with torch.cuda.stream(side):
-                patches = torch.cat([img_lq[..., hi:hi + tile, wi:wi + tile] for (hi, wi) in group], 0).contiguous().float()
-                feats = enc.forward_hwc_batch(patches, opt)
+                out = trunk(group)
                 ev = torch.cuda.Event()
                 ev.record(side)
-            return patches, feats, ev
+            return out, ev
 
-        nxt = trunk(groups[0])
-        for k, group in enumerate(groups):
-            patches, feats, ev = nxt
-            if k + 1 < len(groups):
-                nxt = trunk(groups[k + 1])                       # queued behind batch k's trunk, runs under batch k's heads
+        def take(out, ev):              # a function of its own: no local of the generator keeps a tensor of a finished group alive
             cur.wait_event(ev)
-            patches.record_stream(cur)
-            feats.record_stream(cur)
-            for j, (hi, wi) in enumerate(group):
-                out = gen._head.forward(None, patches[j], coord, cell, gen.eval_bsize, feature_hwc=feats[j], options=opt)
-                hip_ops.tile_blend(E[0], Wt[0], out.contiguous(), hi * sf, wi * sf, th, tw)
-        cur.wait_stream(side)
-        return torch.stack([hip_ops.tile_finalize(E[0], Wt[0])])
+            for t in out:               # tensors, or lists of them: consumed on the caller's stream
+                for u in ([t] if torch.is_tensor(t) else t):
+                    u.record_stream(cur)
+            return out
+
+        try:
+            nxt = None
+            for g, group in enumerate(groups):
+                out, ev = nxt or launch(group)
+                nxt = launch(groups[g + 1]) if g + 1 < len(groups) else None      # queued behind group g's trunk, runs under group g's heads
+                yield take(out, ev)
+        finally:
+            cur.wait_stream(side)
 
     def _tile_streams(self, n, device):
         key = (n, device.index)
@@ -397,7 +417,7 @@ class CiaoSR(BasicRestorer):
                 hip_ops.tile_blend(E[bi], Wt[bi], out[bi].contiguous(), t['i0'], t['j0'], t['i1'] - t['i0'], t['j1'] - t['j0'])
         return torch.stack([hip_ops.tile_finalize(E[bi], Wt[bi]) for bi in range(b)])
 
-    # -- encode once, render any scale or window (an extension, absent from the reference) ---------------------------------------------
+    # -- encode once, render any scale, window or view (an extension, absent from the reference): scene_render.py ----------------------
     @torch.no_grad()
     def encode(self, lq, options=None, max_scale=None):
         """Everything `restore` computes from the LR image alone, kept: -> scene.EncodedImage for `render`.  Without `test_cfg.tile` the
@@ -405,63 +425,14 @@ class CiaoSR(BasicRestorer):
         render, from its scale).  With `test_cfg.tile` one scene per LR tile, each built when a render first touches the tile and held
         under `test_cfg.scene_cache_mb` (default 4096) MiB, least recently used first out.  `max_scale` sizes the plan of every scene:
         the full (tile) grid at that scale is the largest render whose route is `restore`'s own (include/ciaosr_hip.h, q_plan)."""
-        from .scene import EncodedImage
-        opt = self.options(options)
-        x = self.normalize(lq)
-        gen = self.generator
-        if max_scale is None:
-            max_scale = self.test_cfg.get('scale', None)
-        tile = self.test_cfg.get('tile', None)
-        h, w = x.shape[-2:]
-        t = min(tile, h, w) if tile else None
-
-        def build(key):
-            b, origin = key
-            patch = x[b:b + 1] if origin is None else x[b:b + 1, :, origin[0]:origin[0] + t, origin[1]:origin[1] + t].contiguous()
-            ph, pw = patch.shape[-2:]
-            return gen.encode(patch, opt, q_plan=max(1, round(ph * enc.max_scale) * round(pw * enc.max_scale)))
-
-        enc = EncodedImage(x, opt, max_scale, int(self.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build, tile=t)
-        if not tile and max_scale is not None:
-            for b in range(x.shape[0]):
-                enc.cache.get((b, None))
-        return enc
+        return scene_render.encode(self, lq, options, max_scale)
 
     @torch.no_grad()
     def render(self, enc, size=None, scale=None, window=None, as_u8=False):
         """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
         round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,
         or with `as_u8` the metrics_hip.tensor2img_u8 image of it.  Only the LR tiles whose HR rectangle meets the window are touched."""
-        from . import scene as sc
-        x = enc.x
-        nb, _, h, w = x.shape
-        ht, wt = sc.target_size(h, w, size, scale)
-        wi0, wj0, wh, ww = sc.check_window(ht, wt, window)
-        if enc.max_scale is None:
-            enc.max_scale = max(ht / h, wt / w)
-        gen = self.generator
-        tile = self.test_cfg.get('tile', None)
-        if not tile:
-            coord, cell = hip_ops.make_coord_cell_window(ht, wt, wi0, wi0 + wh, wj0, wj0 + ww, x.device)
-            preds = [gen.render(enc.cache.get((b, None)), coord, cell)[0] for b in range(nb)]
-        else:
-            tiles = sc.plan_window(h, w, tile, self.test_cfg.get('tile_overlap', None), ht, wt, (wi0, wj0, wh, ww),
-                                   scale=self.test_cfg.get('scale', None), any_scale=bool(self.test_cfg.get('tile_any_scale', False)))
-            preds = []
-            for b in range(nb):
-                E = torch.zeros(3, wh, ww, dtype=torch.float32, device=x.device)
-                Wt = torch.zeros_like(E)
-                for t in tiles:              # the reference's blend order
-                    gh, gw, r0, r1, c0, c1, frame = t['grid']
-                    coord, cell = hip_ops.make_coord_cell_window(gh, gw, r0, r1, c0, c1, x.device, frame)
-                    out = gen.render(enc.cache.get((b, (t['y0'], t['x0']))), coord, cell)[0]
-                    hip_ops.tile_blend(E, Wt, out, t['a0'] - wi0, t['b0'] - wj0, t['a1'] - t['a0'], t['b1'] - t['b0'])
-                preds.append(hip_ops.tile_finalize(E, Wt))
-        out = torch.stack([hip_ops.denorm_clamp(p.contiguous(), wh, ww, self.rgb_mean, self.rgb_std) for p in preds])
-        if as_u8:
-            from . import metrics_hip
-            return metrics_hip.tensor2img_u8(out)
-        return out
+        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.Grid(size, scale, window)])[0], as_u8)
 
     @torch.no_grad()
     def render_view(self, enc, matrix, size, fill=0.0, as_u8=False):
@@ -473,212 +444,7 @@ class CiaoSR(BasicRestorer):
         `test_cfg.tile_any_scale`.  Per batch item ONE device-to-host copy -- the tiles' member counts, which size the per-tile query
         lists -- is the only synchronisation of a view render.  An axis-aligned view is not bitwise the window `render` shows (its
         coordinates differ by up to 2^-22, see `scene.view_of_window`)."""
-        from . import scene as sc
-        x = enc.x
-        nb, _, h, w = x.shape
-        tile = self.test_cfg.get('tile', None)
-        m, (hv, wv), fill, frames = sc.check_view(matrix, size, fill, h, w, tile, self.test_cfg.get('tile_overlap', None),
-                                                  bool(self.test_cfg.get('tile_any_scale', False)))
-        if enc.max_scale is None:
-            enc.max_scale = sc.view_max_scale(m)
-        if enc.view_tiles is None:                                      # uploaded once per encoded image, not per view
-            enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
-        gen = self.generator
-        n_q = hv * wv
-        blocks = self._view_blocks(enc, m, frames)
-        preds = []
-        for b in range(nb):
-            if blocks:                                                  # per tile (members, live blocks of 4 x 2 output pixels)
-                counts, ws = hip_ops.view_count_blocks(m, hv, wv, enc.view_tiles)
-                counts = counts.tolist()                                # the one synchronisation
-            else:
-                counts, ws = hip_ops.view_count(m, hv, wv, enc.view_tiles)
-                counts = [(n, 0) for n in counts.tolist()]              # the one synchronisation
-            E = torch.zeros(3, n_q, dtype=torch.float32, device=x.device)
-            Wt = torch.zeros(n_q, dtype=torch.float32, device=x.device)
-            for k, (frame, (n, n_blk)) in enumerate(zip(frames, counts)):        # the reference's blend order
-                if n == 0:
-                    continue
-                tile_scene = enc.cache.get((b, (frame[0], frame[1]) if tile else None))
-                if n == n_q:                                            # the tile owns the whole view: a grid, known to the head as one
-                    q_index = None
-                    coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frame, x.device)
-                elif blocks:                                            # row tiles of the chained 16-bit kernel, pads at q_index -1
-                    q_index, coord, cell = hip_ops.view_select_blocks(m, hv, wv, frame, k, len(frames), ws, n_blk)
-                else:
-                    q_index, coord, cell = hip_ops.view_select(m, hv, wv, frame, k, len(frames), ws, n)
-                hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
-            preds.append(hip_ops.view_finalize(E, Wt, fill, self.rgb_mean, self.rgb_std))
-        out = torch.stack([hip_ops.denorm_clamp(p, hv, wv, self.rgb_mean, self.rgb_std) for p in preds])
-        if as_u8:
-            from . import metrics_hip
-            return metrics_hip.tensor2img_u8(out)
-        return out
-
-    def _view_blocks(self, enc, m, frames):
-        """Whether the partial member lists of view `m` are selected in 4 x 2 blocks (`hip_ops.view_select_blocks`): `test_cfg.view_blocks`
-        is on, `scene.view_blocks_fit(m)` holds, and the route the tile scenes are planned under runs the chained 16-bit kv kernel --
-        the one kernel that walks 8 consecutive list entries as a row tile.  Elsewhere (fp32, f16x3, bf16x3, `head_route` bits that
-        disable the chain) the pads would only cost queries and the index-order list stays.  Pure host work; needs `enc.max_scale`."""
-        from . import scene as sc
-        if not self.test_cfg.get('view_blocks', False) or not sc.view_blocks_fit(m):
-            return False
-        th, tw = frames[0][2], frames[0][3]                             # every frame has the first one's size
-        q_plan = max(1, round(th * enc.max_scale) * round(tw * enc.max_scale))
-        return self.generator.scene_chained(th, tw, q_plan, enc.options)
-
-    # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------
-    def _plan_many(self, enc, targets, count_views=True):
-        """Everything `render_many` / `prefetch` know before a scene is touched.  Validates every target (the single calls' ValueErrors,
-        before any device work), sets `enc.max_scale` where it is open, counts the members of ALL views in one `view_count_many` and
-        one device-to-host copy (none for grids alone) -- per call, not per batch item: the counts do not depend on the item.
-        -> dict: recs (per target), origins {tile index: (y0, x0) | None}, union, users, frames.  A view's record holds its counts per
-        tile, `blocks` (selected in 4 x 2 blocks, `_view_blocks`; then also `n_blocks` per tile) and `ws`, its slice of the count's
-        workspace for the select."""
-        from . import scene as sc
-        x = enc.x
-        h, w = x.shape[-2:]
-        cfg = self.test_cfg
-        tile, overlap, any_scale = cfg.get('tile', None), cfg.get('tile_overlap', None), bool(cfg.get('tile_any_scale', False))
-        targets = list(targets)
-        if not targets:
-            raise ValueError('no targets: give a list of scene.Grid / scene.View')
-        recs, frames, need = [], None, 0.0
-        for tg in targets:
-            if isinstance(tg, sc.Grid):
-                ht, wt, win = tg.resolve(h, w)
-                tiles = None
-                if tile:
-                    tiles = sc.plan_window(h, w, tile, overlap, ht, wt, win, scale=cfg.get('scale', None), any_scale=any_scale)
-                recs.append(dict(kind='grid', ht=ht, wt=wt, win=win, tiles=tiles, size=(win[2], win[3])))
-                need = max(need, ht / h, wt / w)
-            elif isinstance(tg, sc.View):
-                m, size, fill, frames = tg.resolve(h, w, tile, overlap, any_scale)
-                recs.append(dict(kind='view', m=m, size=size, fill=fill))
-                need = max(need, sc.view_max_scale(m))
-            else:
-                raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
-        if enc.max_scale is None:
-            enc.max_scale = need
-        plan = dict(recs=recs, frames=frames, origins={})
-        views = [r for r in recs if r['kind'] == 'view']
-        if views and not count_views:                                   # one frame: every view is its only user
-            for r in views:
-                r['counts'] = [1]
-            plan['origins'][0] = (0, 0) if tile else None
-        elif views:
-            if enc.view_tiles is None:                                  # uploaded once per encoded image
-                enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(x.device)
-            n_t = len(frames)
-            for r in views:
-                r['blocks'] = self._view_blocks(enc, r['m'], frames)
-            plain, blk = [r for r in views if not r['blocks']], [r for r in views if r['blocks']]
-            flat = []
-            if plain:
-                counts, ws, offsets = hip_ops.view_count_many([r['m'] for r in plain], [r['size'] for r in plain], enc.view_tiles)
-                flat.append(counts.flatten())
-                for v, r in enumerate(plain):
-                    r['ws'] = ws[offsets[v]:]
-            if blk:                                                     # per tile (members, live blocks of 4 x 2 output pixels)
-                counts, ws, offsets = hip_ops.view_count_blocks_many([r['m'] for r in blk], [r['size'] for r in blk], enc.view_tiles)
-                flat.append(counts.flatten())
-                for v, r in enumerate(blk):
-                    r['ws'] = ws[offsets[v]:]
-            flat = (flat[0] if len(flat) == 1 else torch.cat(flat)).tolist()          # the one synchronisation of the call
-            for v, r in enumerate(plain):
-                r['counts'] = flat[v * n_t:(v + 1) * n_t]
-            base = len(plain) * n_t
-            for v, r in enumerate(blk):
-                both = flat[base + 2 * v * n_t:base + 2 * (v + 1) * n_t]
-                r['counts'], r['n_blocks'] = both[0::2], both[1::2]
-            plan['origins'].update({k: ((f[0], f[1]) if tile else None) for k, f in enumerate(frames)})
-        touched = []
-        for r in recs:
-            if r['kind'] == 'view':
-                touched.append([k for k, n in enumerate(r['counts']) if n])
-            elif r['tiles'] is None:
-                touched.append([0])
-                plan['origins'][0] = None
-            else:
-                r['by_index'] = {t['index']: t for t in r['tiles']}
-                touched.append(sorted(r['by_index']))
-                plan['origins'].update({t['index']: (t['y0'], t['x0']) for t in r['tiles']})
-        plan['union'], plan['users'] = sc.plan_union(touched)
-        return plan
-
-    def _scene_walk(self, enc, b, tiles, n_group, ahead):
-        """Yield (tile index, scene) for `tiles` (index -> origin in `origins`, given as a list of (index, origin)) of batch item b, in
-        order, each scene taken from the cache once.  The tiles missing from the cache are encoded in groups of `n_group`: one trunk call
-        per group (`encode_trunk` on the stacked patches), with `ahead` the next group's on the cached side stream under the current
-        group's prepares and queries (events, wait_stream and record_stream as `_clip_test_encoder_ahead`).  A scene is prepared from
-        its feature map right before it is yielded; only a group's feature maps are held, never its scenes."""
-        from . import scene as sc
-        gen, cache, x, t = self.generator, enc.cache, enc.x, enc.tile
-        opt = enc.options
-        origin_of = dict(tiles)
-        order = [k for k, _ in tiles]
-        key_of = {k: (b, origin_of[k]) for k in order}
-        groups = sc.group_missing(order, {k for k in order if key_of[k] in cache.entries}, n_group)
-        ahead = bool(ahead and len(groups) > 1 and x.is_cuda and trunk_batches(gen, opt))
-        if ahead:
-            cur = torch.cuda.current_stream(x.device)
-            self.prepare(opt)                                           # nothing the side stream reads is first packed there
-            side = self._tile_streams(1, x.device)[0]
-            side.wait_stream(cur)
-
-        def patch_of(k):
-            o = origin_of[k]
-            return x[b:b + 1] if o is None else x[b:b + 1, :, o[0]:o[0] + t, o[1]:o[1] + t]
-
-        def trunk(group):
-            if not ahead:
-                patches, feats, eff = gen.encode_trunk(torch.cat([patch_of(k) for k in group], 0).contiguous(), opt)
-                return patches, feats, eff, None
-            with torch.cuda.stream(side):
-                patches, feats, eff = gen.encode_trunk(torch.cat([patch_of(k) for k in group], 0).contiguous(), opt)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            return patches, feats, eff, ev
-
-        where = {k: (g, j) for g, group in enumerate(groups) for j, k in enumerate(group)}
-        ready, g_next, nxt = {}, 0, None          # ready: the group in use -> (patches, feats, eff)
-        cache.hold = set(key_of.values())
-        try:
-            for k in order:
-                key = key_of[k]
-                cache.hold.discard(key)
-                if k not in where or key in cache.entries:
-                    yield k, cache.get(key)       # cached (a held entry the budget pushed out all the same is rebuilt on its own)
-                    continue
-                g, j = where[k]
-                if g not in ready:
-                    ready.clear()                 # the group before is done: its feature maps go
-                    if nxt is None:
-                        nxt = trunk(groups[g])
-                    patches, feats, eff, ev = nxt
-                    nxt, g_next = None, g + 1
-                    if ahead and g_next < len(groups):
-                        nxt = trunk(groups[g_next])          # queued behind group g's trunk, runs under group g's prepares and queries
-                    if ev is not None:
-                        cur.wait_event(ev)
-                        patches.record_stream(cur)
-                        for f in ([feats] if torch.is_tensor(feats) else feats):
-                            f.record_stream(cur)
-                    ready[g] = (patches, feats, eff)
-                patches, feats, eff = ready[g]
-                ph, pw = patches.shape[-2:]
-                cache.make_room()
-                scene = gen.encode_scenes(patches[j:j + 1], [feats[j]], eff,
-                                          q_plan=max(1, round(ph * enc.max_scale) * round(pw * enc.max_scale)))
-                yield k, cache.put(key, scene)
-        finally:
-            cache.hold = set()
-            if ahead:
-                cur.wait_stream(side)
-
-    def _group_size(self, enc):
-        """Tiles per trunk call of the scene builder: `tile_batch()` where the tile loops feed this trunk batches, else 1."""
-        return self.tile_batch(enc.options) if (enc.tile and trunk_batches(self.generator, enc.options)) else 1
+        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.View(matrix, size, fill)])[0], as_u8)
 
     @torch.no_grad()
     def render_many(self, enc, targets, as_u8=False):
@@ -694,100 +460,14 @@ class CiaoSR(BasicRestorer):
         group's trunk on the cached side stream under the current group's heads.  All views are counted in one `view_count_many` and
         one device-to-host copy per call (none for grids alone).  An image that is one frame (no `test_cfg.tile`, or an image no larger
         than the tile) has no schedule to make: its targets are the single calls, in list order."""
-        x = enc.x
-        nb = x.shape[0]
-        gen = self.generator
-        one_frame = not enc.tile or tuple(x.shape[-2:]) == (enc.tile, enc.tile)
-        plan = self._plan_many(enc, targets, count_views=not one_frame)
-        recs = plan['recs']
-        if one_frame:
-            return [self.render(enc, size=(r['ht'], r['wt']), window=r['win'], as_u8=as_u8) if r['kind'] == 'grid' else
-                    self.render_view(enc, r['m'], r['size'], r['fill'], as_u8=as_u8) for r in recs]
-        frames = plan['frames']
-        walk = [(k, plan['origins'][k]) for k in plan['union']]
-        preds = [[] for _ in recs]
-        for b in range(nb):
-            acc = []
-            for r in recs:
-                hh, ww = r['size']
-                if r['kind'] == 'grid':
-                    E = torch.zeros(3, hh, ww, dtype=torch.float32, device=x.device)
-                    acc.append((E, torch.zeros_like(E)))
-                else:
-                    acc.append((torch.zeros(3, hh * ww, dtype=torch.float32, device=x.device),
-                                torch.zeros(hh * ww, dtype=torch.float32, device=x.device)))
-            for k, tile_scene in self._scene_walk(enc, b, walk, self._group_size(enc), self.test_cfg.get('encoder_ahead', True)):
-                for i in plan['users'][k]:
-                    r = recs[i]
-                    E, Wt = acc[i]
-                    if r['kind'] == 'grid':
-                        t = r['by_index'][k]
-                        wi0, wj0 = r['win'][:2]
-                        gh, gw, r0, r1, c0, c1, frame = t['grid']
-                        coord, cell = hip_ops.make_coord_cell_window(gh, gw, r0, r1, c0, c1, x.device, frame)
-                        out = gen.render(tile_scene, coord, cell)[0]
-                        hip_ops.tile_blend(E, Wt, out, t['a0'] - wi0, t['b0'] - wj0, t['a1'] - t['a0'], t['b1'] - t['b0'])
-                    else:
-                        (hv, wv), m, n = r['size'], r['m'], r['counts'][k]
-                        if n == hv * wv:                                # the tile owns the whole view: a grid, known to the head as one
-                            q_index = None
-                            coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frames[k], x.device)
-                        elif r['blocks']:                               # row tiles of the chained 16-bit kernel, pads at q_index -1
-                            q_index, coord, cell = hip_ops.view_select_blocks(m, hv, wv, frames[k], k, len(frames), r['ws'], r['n_blocks'][k])
-                        else:
-                            q_index, coord, cell = hip_ops.view_select(m, hv, wv, frames[k], k, len(frames), r['ws'], n)
-                        hip_ops.view_blend(E, Wt, q_index, gen.render(tile_scene, coord, cell)[0])
-            for i, r in enumerate(recs):
-                E, Wt = acc[i]
-                preds[i].append(hip_ops.tile_finalize(E, Wt) if r['kind'] == 'grid' else
-                                hip_ops.view_finalize(E, Wt, r['fill'], self.rgb_mean, self.rgb_std))
-        outs = []
-        for r, ps in zip(recs, preds):
-            hh, ww = r['size']
-            out = torch.stack([hip_ops.denorm_clamp(p.contiguous(), hh, ww, self.rgb_mean, self.rgb_std) for p in ps])
-            if as_u8:
-                from . import metrics_hip
-                out = metrics_hip.tensor2img_u8(out)
-            outs.append(out)
-        return outs
+        return scene_render.render_many(self, enc, targets, as_u8)
 
     @torch.no_grad()
     def prefetch(self, enc, targets):
         """Build the scenes `render_many(enc, targets)` would touch and the cache lacks, rendering nothing: the same plan and the same
         batched builder, row-major per batch item, stopping before a build would exceed `scene_cache_mb` -- nothing is evicted.
         -> the number of scenes built."""
-        plan = self._plan_many(enc, targets)
-        cache = enc.cache
-        built = 0
-        for b in range(enc.x.shape[0]):
-            missing = [(k, plan['origins'][k]) for k in plan['union'] if (b, plan['origins'][k]) not in cache.entries]
-            if missing and cache.room() is None:                        # the size of a scene is not known yet: the first one tells
-                for _ in self._scene_walk(enc, b, missing[:1], 1, False):
-                    built += 1
-                missing = missing[1:]
-            missing = missing[:cache.room() or 0]
-            for _ in self._scene_walk(enc, b, missing, self._group_size(enc), self.test_cfg.get('encoder_ahead', True)):
-                built += 1
-            if cache.room() == 0:
-                break
-        return built
-
-    # -- every level of a tile pyramid (pyramid.py) -------------------------------------------------------------------------------------
-    def _plan_pyramid(self, enc, size=None, scale=None):
-        """The level sizes of `render_pyramid` and the index of the smallest model level; its ValueErrors.  Pure host work."""
-        from . import pyramid
-        from . import scene as sc
-        nb, _, h, w = enc.x.shape
-        if nb != 1:
-            raise ValueError(f'render_pyramid takes one image, got a batch of {nb}')
-        ht, wt = sc.target_size(h, w, size, scale)
-        if ht < h or wt < w:
-            raise ValueError(f'the top level {ht} x {wt} is smaller than the LR image {h} x {w}: the model renders no scale below 1')
-        if self.test_cfg.get('tile', None) and not self.test_cfg.get('tile_any_scale', False):
-            raise ValueError('render_pyramid with test_cfg.tile needs test_cfg.tile_any_scale: the levels are not the integer-scale '
-                             'rectangles of clip_test')
-        sizes = pyramid.level_sizes(ht, wt)
-        return sizes, min(k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w)
+        return scene_render.prefetch(self, enc, targets)
 
     @torch.no_grad()
     def render_pyramid(self, enc, size=None, scale=None):
@@ -797,12 +477,10 @@ class CiaoSR(BasicRestorer):
         bitwise `render(enc, size=(H_l, W_l), as_u8=True)`.  Every smaller level is `degrade.resize_bicubic_u8` -- Pillow's BICUBIC
         resize, exactly -- of the smallest model level, each taken from it directly.  ValueError before any device work: a batch, a top
         level below the LR size, `test_cfg.tile` without `tile_any_scale`, and whatever `scene.Grid` raises."""
-        from . import degrade
-        from . import scene as sc
-        sizes, first = self._plan_pyramid(enc, size, scale)
-        model_levels = self.render_many(enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
-        base = model_levels[0]
-        return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)
+        return scene_render.render_pyramid(self, enc, size, scale)
+
+    def _plan_pyramid(self, enc, size=None, scale=None):
+        return scene_render.plan_pyramid(self, enc, size, scale)
 
     def _restore(self, lq, coord=None, cell=None, options=None):
         x = self.normalize(lq)

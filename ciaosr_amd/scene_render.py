@@ -1,0 +1,326 @@
+"""The scene renderer behind CiaoSR.encode / render / render_view / render_many / prefetch / render_pyramid (an extension, absent from the
+reference): the device side of scene.py.  A target -- `scene.Grid` or `scene.View`, resolved into a `GridTarget` or a `ViewTarget` --
+knows the tiles it touches, its accumulators, how to query one tile's scene into them and how to finish them; the single calls take the
+scenes from the cache tile by tile, `render_many` and `prefetch` from one walk over the union of the tiles (`scene_walk`), whose missing
+scenes are built from batched trunk calls on `CiaoSR.trunk_ahead`.  Every function takes the restorer first."""
+import torch
+
+from . import hip_ops
+from . import scene as sc
+
+
+def q_plan(ph, pw, s):
+    """The query count a scene of a ph x pw LR map is planned for: its full grid at scale `s` (include/ciaosr_hip.h, q_plan)."""
+    return max(1, round(ph * s) * round(pw * s))
+
+
+def _crop(x, b, origin, t):
+    """Item b of the normalised batch, or its t x t tile at `origin`."""
+    return x[b:b + 1] if origin is None else x[b:b + 1, :, origin[0]:origin[0] + t, origin[1]:origin[1] + t]
+
+
+def encode(r, lq, options=None, max_scale=None):
+    opt = r.options(options)
+    x = r.normalize(lq)
+    gen = r.generator
+    if max_scale is None:
+        max_scale = r.test_cfg.get('scale', None)
+    tile = r.test_cfg.get('tile', None)
+    t = min(tile, *x.shape[-2:]) if tile else None
+
+    def build(key):
+        patch = _crop(x, *key, t).contiguous()
+        return gen.encode(patch, opt, q_plan=q_plan(*patch.shape[-2:], enc.max_scale))
+
+    enc = sc.EncodedImage(x, opt, max_scale, int(r.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build, tile=t)
+    if not tile and max_scale is not None:
+        for b in range(x.shape[0]):
+            enc.cache.get((b, None))
+    return enc
+
+
+# -- targets ----------------------------------------------------------------------------------------------------------------------------
+class GridTarget:
+    """A resolved scene.Grid: the window `win` of the ht x wt grid.  `tiles`: index -> `scene.plan_window`'s record of every LR tile the
+    window touches; None without `test_cfg.tile`, where the whole image is the one frame and `render_whole` is the render."""
+
+    def __init__(self, cfg, h, w, ht, wt, win):
+        self.ht, self.wt, self.win, self.size = ht, wt, win, (win[2], win[3])
+        self.max_scale = max(ht / h, wt / w)
+        self.tiles = None
+        if cfg.get('tile', None):
+            self.tiles = {t['index']: t for t in sc.plan_window(
+                h, w, cfg.get('tile'), cfg.get('tile_overlap', None), ht, wt, win, scale=cfg.get('scale', None),
+                any_scale=bool(cfg.get('tile_any_scale', False)))}
+
+    def touched(self):
+        """{tile index: origin}, row-major: the reference's blend order."""
+        return {0: None} if self.tiles is None else {k: (t['y0'], t['x0']) for k, t in self.tiles.items()}
+
+    def render_whole(self, r, enc):
+        """The render where `tiles` is None: a scene's prediction of the window's grid is the window, nothing is blended; the items of
+        a batch share the coordinates."""
+        wi0, wj0, wh, ww = self.win
+        coord, cell = hip_ops.make_coord_cell_window(self.ht, self.wt, wi0, wi0 + wh, wj0, wj0 + ww, enc.x.device)
+        return [hip_ops.denorm_clamp(r.generator.render(enc.cache.get((b, None)), coord, cell)[0].contiguous(), wh, ww, r.rgb_mean, r.rgb_std)
+                for b in range(enc.x.shape[0])]
+
+    def alloc(self, device):
+        E = torch.zeros(3, *self.size, dtype=torch.float32, device=device)
+        return E, torch.zeros_like(E)
+
+    def query(self, gen, k, tile_scene, acc):
+        """Tile k's part of the window from its scene, blended into `acc`.  Coordinates are made right before the query that reads them
+        (the 16-bit head's grid-width hint is kept for the last 64 coordinate tensors only)."""
+        t = self.tiles[k]
+        gh, gw, r0, r1, c0, c1, frame = t['grid']
+        coord, cell = hip_ops.make_coord_cell_window(gh, gw, r0, r1, c0, c1, tile_scene.x.device, frame)
+        out = gen.render(tile_scene, coord, cell)[0]
+        hip_ops.tile_blend(*acc, out, t['a0'] - self.win[0], t['b0'] - self.win[1], t['a1'] - t['a0'], t['b1'] - t['b0'])
+
+    def finish(self, r, acc):
+        return hip_ops.denorm_clamp(hip_ops.tile_finalize(*acc).contiguous(), *self.size, r.rgb_mean, r.rgb_std)
+
+
+class ViewTarget:
+    """A resolved scene.View: matrix `m`, output `size`, `fill`, and the frames (y0, x0, th, tw) its queries are sorted into.  `count`
+    (or `count_views`, for many at once) gives it `counts`, the members per frame, `n_blocks` (the live 4 x 2 blocks per frame where
+    the member lists are selected in blocks, `view_blocks`; else None) and `ws`, the count's workspace for the select."""
+
+    def __init__(self, cfg, m, size, fill, frames):
+        self.m, self.size, self.fill, self.frames = m, size, fill, frames
+        self.max_scale = sc.view_max_scale(m)
+        self.tiled = bool(cfg.get('tile', None))
+        self.counts = self.n_blocks = self.ws = None
+
+    def count(self, r, enc):
+        """Count this view alone: the ONE device-to-host copy, and the only synchronisation, of a single view render of a batch item."""
+        hv, wv = self.size
+        if view_blocks(r, enc, self.m, self.frames):                    # per tile (members, live blocks of 4 x 2 output pixels)
+            counts, self.ws = hip_ops.view_count_blocks(self.m, hv, wv, _view_tiles(enc, self.frames))
+            both = counts.tolist()
+            self.counts, self.n_blocks = [n for n, _ in both], [n_blk for _, n_blk in both]
+        else:
+            counts, self.ws = hip_ops.view_count(self.m, hv, wv, _view_tiles(enc, self.frames))
+            self.counts = counts.tolist()
+
+    def touched(self):
+        """{frame index: origin} of the frames with a member, row-major: a frame without one is neither built nor queried."""
+        return {k: ((f[0], f[1]) if self.tiled else None) for k, (f, n) in enumerate(zip(self.frames, self.counts)) if n}
+
+    def alloc(self, device):
+        n_q = self.size[0] * self.size[1]
+        return torch.zeros(3, n_q, dtype=torch.float32, device=device), torch.zeros(n_q, dtype=torch.float32, device=device)
+
+    def query(self, gen, k, tile_scene, acc):
+        """Frame k's members from its scene, blended into `acc`."""
+        (hv, wv), m, frame, n = self.size, self.m, self.frames[k], self.counts[k]
+        if n == hv * wv:                                                # the tile owns the whole view: a grid, known to the head as one
+            q_index = None
+            coord, cell = hip_ops.make_coord_cell_view(m, hv, wv, frame, tile_scene.x.device)
+        elif self.n_blocks is not None:                                 # row tiles of the chained 16-bit kernel, pads at q_index -1
+            q_index, coord, cell = hip_ops.view_select_blocks(m, hv, wv, frame, k, len(self.frames), self.ws, self.n_blocks[k])
+        else:
+            q_index, coord, cell = hip_ops.view_select(m, hv, wv, frame, k, len(self.frames), self.ws, n)
+        hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell)[0])
+
+    def finish(self, r, acc):
+        return hip_ops.denorm_clamp(hip_ops.view_finalize(*acc, self.fill, r.rgb_mean, r.rgb_std), *self.size, r.rgb_mean, r.rgb_std)
+
+
+def view_blocks(r, enc, m, frames):
+    """Whether the partial member lists of view `m` are selected in 4 x 2 blocks (`hip_ops.view_select_blocks`): `test_cfg.view_blocks`
+    is on, `scene.view_blocks_fit(m)` holds, and the route the tile scenes are planned under runs the chained 16-bit kv kernel --
+    the one kernel that walks 8 consecutive list entries as a row tile.  Elsewhere (fp32, f16x3, bf16x3, `head_route` bits that
+    disable the chain) the pads would only cost queries and the index-order list stays.  Pure host work; needs `enc.max_scale`."""
+    if not r.test_cfg.get('view_blocks', False) or not sc.view_blocks_fit(m):
+        return False
+    th, tw = frames[0][2], frames[0][3]                                 # every frame has the first one's size
+    return r.generator.scene_chained(th, tw, q_plan(th, tw, enc.max_scale), enc.options)
+
+
+def _view_tiles(enc, frames):
+    if enc.view_tiles is None:                                          # uploaded once per encoded image, not per view
+        enc.view_tiles = torch.tensor(frames, dtype=torch.int32).to(enc.x.device)
+    return enc.view_tiles
+
+
+def count_views(r, enc, views):
+    """`ViewTarget.count` for ALL views of a `render_many` / `prefetch` in one `view_count_many` (and one `view_count_blocks_many` for
+    those selected in blocks) and one device-to-host copy -- per call, not per batch item: the counts do not depend on the item."""
+    frames = views[0].frames                                            # the image's: the same for every view
+    n_t = len(frames)
+    plain, blk = [], []
+    for v in views:
+        (blk if view_blocks(r, enc, v.m, frames) else plain).append(v)
+    flat = []
+    for group, count in ((plain, hip_ops.view_count_many), (blk, hip_ops.view_count_blocks_many)):
+        if group:
+            counts, ws, offsets = count([v.m for v in group], [v.size for v in group], _view_tiles(enc, frames))
+            flat.append(counts.flatten())
+            for v, off in zip(group, offsets):
+                v.ws = ws[off:]
+    flat = (flat[0] if len(flat) == 1 else torch.cat(flat)).tolist()    # the one synchronisation of the call
+    for i, v in enumerate(plain):
+        v.counts = flat[i * n_t:(i + 1) * n_t]
+    base = len(plain) * n_t
+    for i, v in enumerate(blk):                                         # per tile (members, live blocks of 4 x 2 output pixels)
+        both = flat[base + 2 * i * n_t:base + 2 * (i + 1) * n_t]
+        v.counts, v.n_blocks = both[0::2], both[1::2]
+
+
+def resolve(r, enc, targets):
+    """`scene.Grid` / `scene.View` records -> GridTarget / ViewTarget, with the single calls' ValueErrors, before any device work; sets
+    `enc.max_scale` where it is open: the largest any target needs."""
+    cfg = r.test_cfg
+    h, w = enc.x.shape[-2:]
+    tile, overlap, any_scale = cfg.get('tile', None), cfg.get('tile_overlap', None), bool(cfg.get('tile_any_scale', False))
+    targets = list(targets)
+    if not targets:
+        raise ValueError('no targets: give a list of scene.Grid / scene.View')
+    out = []
+    for tg in targets:
+        if isinstance(tg, sc.Grid):
+            out.append(GridTarget(cfg, h, w, *tg.resolve(h, w)))
+        elif isinstance(tg, sc.View):
+            out.append(ViewTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale)))
+        else:
+            raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
+    if enc.max_scale is None:
+        enc.max_scale = max(tg.max_scale for tg in out)
+    return out
+
+
+def _stacked(outs, as_u8):
+    out = torch.stack(outs)
+    if as_u8:
+        from . import metrics_hip
+        return metrics_hip.tensor2img_u8(out)
+    return out
+
+
+# -- one target: scenes from the cache, tile by tile ------------------------------------------------------------------------------------
+def render_one(r, enc, tg, as_u8=False):
+    """The single calls `render` / `render_view`, of a resolved target: per batch item, every scene taken with `enc.cache.get` when its
+    tile's turn comes -- no walk, no batched trunk, no side stream."""
+    if isinstance(tg, GridTarget) and tg.tiles is None:
+        return _stacked(tg.render_whole(r, enc), as_u8)
+    outs = []
+    for b in range(enc.x.shape[0]):
+        if isinstance(tg, ViewTarget):
+            tg.count(r, enc)
+        acc = tg.alloc(enc.x.device)
+        for k, origin in tg.touched().items():
+            tg.query(r.generator, k, enc.cache.get((b, origin)), acc)
+        outs.append(tg.finish(r, acc))
+    return _stacked(outs, as_u8)
+
+
+# -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------------
+def plan_many(r, enc, targets):
+    """Everything `render_many` / `prefetch` know before a scene is touched: -> (the resolved targets, walk, users).  walk: the union
+    of the tiles the targets touch as [(tile index, origin)], row-major; users[tile index]: the targets that touch it, in list order."""
+    tgs = resolve(r, enc, targets)
+    views = [tg for tg in tgs if isinstance(tg, ViewTarget)]
+    if views:
+        count_views(r, enc, views)
+    origins = {}
+    for tg in tgs:
+        origins.update(tg.touched())
+    union, users = sc.plan_union([list(tg.touched()) for tg in tgs])
+    return tgs, [(k, origins[k]) for k in union], users
+
+
+def scene_walk(r, enc, b, tiles):
+    """Yield (tile index, scene) for `tiles`, a list of (tile index, origin), of batch item b, in order, each scene taken from the cache
+    once.  The tiles missing from the cache are encoded in groups: `tile_batch()` tiles per trunk call (`encode_trunk` on the stacked
+    patches) where the tile loops feed this trunk batches, else one; with `test_cfg.encoder_ahead` (default on) the next group's trunk
+    runs on the side stream under the current group's prepares and queries (`CiaoSR.trunk_ahead`).  A scene is prepared from its
+    feature map right before it is yielded; only a group's feature maps are held, never its scenes."""
+    from .restorer import effective_options, trunk_batches           # (restorer.py imports this module)
+    gen, cache, x, opt = r.generator, enc.cache, enc.x, enc.options
+    batches = bool(enc.tile and trunk_batches(gen, opt))
+    origin_of = dict(tiles)
+    order = [k for k, _ in tiles]
+    key_of = {k: (b, origin_of[k]) for k in order}
+    groups = sc.group_missing(order, {k for k in order if key_of[k] in cache.entries}, r.tile_batch(opt) if batches else 1)
+    where = {k: (g, j) for g, group in enumerate(groups) for j, k in enumerate(group)}
+    eff = effective_options(gen, opt)
+    ahead = bool(r.test_cfg.get('encoder_ahead', True) and len(groups) > 1 and x.is_cuda and batches)
+    trunks = r.trunk_ahead(groups, lambda group: gen.encode_trunk(
+        torch.cat([_crop(x, b, origin_of[k], enc.tile) for k in group], 0).contiguous(), opt)[:2], ahead, opt, x.device)
+    g_ready, ready = -1, None                     # the group in use and its (patches, feats)
+    cache.hold = set(key_of.values())
+    try:
+        for k in order:
+            key = key_of[k]
+            cache.hold.discard(key)
+            if k not in where or key in cache.entries:
+                yield k, cache.get(key)           # cached (a held entry the budget pushed out all the same is rebuilt on its own)
+                continue
+            g, j = where[k]
+            if g != g_ready:
+                ready = None                      # the group before is done: its feature maps go before the next trunk is launched
+                g_ready, ready = g, next(trunks)
+            cache.make_room()                 # (`ready` alone names the group's patches and feature maps: they go with it)
+            scene = gen.encode_scenes(ready[0][j:j + 1], [ready[1][j]], eff, q_plan=q_plan(*ready[0].shape[-2:], enc.max_scale))
+            yield k, cache.put(key, scene)
+    finally:
+        cache.hold = set()
+        trunks.close()
+
+
+def render_many(r, enc, targets, as_u8=False):
+    x = enc.x
+    if not enc.tile or tuple(x.shape[-2:]) == (enc.tile, enc.tile):     # one frame: no schedule to make
+        return [render_one(r, enc, tg, as_u8) for tg in resolve(r, enc, targets)]
+    tgs, walk, users = plan_many(r, enc, targets)
+    outs = [[] for _ in tgs]
+    for b in range(x.shape[0]):
+        acc = [tg.alloc(x.device) for tg in tgs]
+        for k, tile_scene in scene_walk(r, enc, b, walk):
+            for i in users[k]:
+                tgs[i].query(r.generator, k, tile_scene, acc[i])
+        for i, tg in enumerate(tgs):
+            outs[i].append(tg.finish(r, acc[i]))
+    return [_stacked(o, as_u8) for o in outs]
+
+
+def prefetch(r, enc, targets):
+    _, walk, _ = plan_many(r, enc, targets)
+    cache = enc.cache
+    built = 0
+    for b in range(enc.x.shape[0]):
+        missing = [(k, origin) for k, origin in walk if (b, origin) not in cache.entries]
+        if missing and cache.room() is None:                            # the size of a scene is not known yet: the first one tells
+            built += sum(1 for _ in scene_walk(r, enc, b, missing[:1]))
+            missing = missing[1:]
+        built += sum(1 for _ in scene_walk(r, enc, b, missing[:cache.room() or 0]))
+        if cache.room() == 0:
+            break
+    return built
+
+
+# -- every level of a tile pyramid (pyramid.py) -----------------------------------------------------------------------------------------
+def plan_pyramid(r, enc, size=None, scale=None):
+    """The level sizes of `render_pyramid` and the index of the smallest model level; its ValueErrors.  Pure host work."""
+    from . import pyramid
+    nb, _, h, w = enc.x.shape
+    if nb != 1:
+        raise ValueError(f'render_pyramid takes one image, got a batch of {nb}')
+    ht, wt = sc.target_size(h, w, size, scale)
+    if ht < h or wt < w:
+        raise ValueError(f'the top level {ht} x {wt} is smaller than the LR image {h} x {w}: the model renders no scale below 1')
+    if r.test_cfg.get('tile', None) and not r.test_cfg.get('tile_any_scale', False):
+        raise ValueError('render_pyramid with test_cfg.tile needs test_cfg.tile_any_scale: the levels are not the integer-scale '
+                         'rectangles of clip_test')
+    sizes = pyramid.level_sizes(ht, wt)
+    return sizes, min(k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w)
+
+
+def render_pyramid(r, enc, size=None, scale=None):
+    from . import degrade
+    sizes, first = plan_pyramid(r, enc, size, scale)
+    model_levels = render_many(r, enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
+    base = model_levels[0]
+    return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)

@@ -39,7 +39,7 @@ import weakref
 import torch
 import torch.distributed as dist
 
-from .restorer import tile_grid, trunk_batches
+from .restorer import effective_options, tile_grid, trunk_batches
 
 
 def rccl_env_defaults(env=None):
@@ -386,15 +386,12 @@ def clip_test_distributed(restorer, x_norm, rank=None, world=None, group=None, g
         return out
 
     # Tile batching (restorer.clip_test's `test_cfg.tile_batch`): this rank's next B tiles go through the encoder in ONE call (shared
-    # dense-layer launches, encoder_hip.forward_hwc_batch: every feature map bitwise the single-tile one); the head then runs tile by
-    # tile in the driver's order, so sends, receives and the blend order are unchanged.
+    # dense-layer launches, `CiaoSR.trunk_tiles`: every feature map bitwise the single-tile one); the head then runs tile by tile
+    # (`CiaoSR.head_tile`) in the driver's order, so sends, receives and the blend order are unchanged.
     gen = restorer.generator
     enc = getattr(gen, '_encoder_hip', None)
     n_batch = restorer.tile_batch(opt)
-    if hasattr(gen, 'effective_options'):
-        opt_eff = gen.effective_options(opt)                  # what gen.forward would run with
-    else:
-        opt_eff = opt
+    opt_eff = effective_options(gen, opt)                     # what gen.forward would run with
     if (n_batch > 1 and x_norm.is_cuda and x_norm.shape[0] == 1 and enc is not None and trunk_batches(gen, opt)
             and enc.supported() and getattr(gen, '_head', None) is not None):
         tile_sz, origins = tile_grid(x_norm.shape[-2], x_norm.shape[-1], cfg.get('tile'), cfg.get('tile_overlap'))
@@ -406,15 +403,9 @@ def clip_test_distributed(restorer, x_norm, rank=None, world=None, group=None, g
         def tile_fn(hi, wi, tile):                            # noqa: F811 - the batched variant replaces the one above
             if (hi, wi) not in cache:
                 grp = mine[pos[(hi, wi)]:pos[(hi, wi)] + n_batch]
-                patches = torch.cat([x_norm[..., h0:h0 + tile, w0:w0 + tile] for (h0, w0) in grp], 0).contiguous().float()
-                feats = enc.forward_hwc_batch(patches, opt_eff)
-                for j, o in enumerate(grp):
-                    cache[o] = (patches[j], feats[j])
-            patch, feat = cache.pop((hi, wi))
-            th, tw = round(patch.shape[-2] * sf), round(patch.shape[-1] * sf)
-            coord, cell = hip_ops.make_coord_cell(th, tw, patch.device)
-            out = gen._head.forward(None, patch, coord, cell, gen.eval_bsize, feature_hwc=feat, options=opt_eff)
-            return out.unsqueeze(0)
+                for o, patch, feat in zip(grp, *restorer.trunk_tiles(x_norm, grp, tile, opt_eff)):
+                    cache[o] = (patch, feat)
+            return restorer.head_tile(*cache.pop((hi, wi)), sf, opt_eff)[0].unsqueeze(0)
 
     def blend_fn(E, Wt, out, y0, x0, th, tw):
         for bi in range(E.shape[0]):

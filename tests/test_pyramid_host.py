@@ -118,10 +118,11 @@ def test_render_pyramid_refuses_before_any_device_work(tmp_path):
             pyramid.write_dzi(model, enc, str(tmp_path / 'never'), 'x', scale=2, tile_size=t, overlap=o)
     assert not (tmp_path / 'never').exists()
     # the plan: levels of the top size, the model levels are those that cover the LR image
-    sizes, first = model._plan_pyramid(enc, scale=4)
+    from ciaosr_amd import scene_render
+    sizes, first = scene_render.plan_pyramid(model, enc, scale=4)
     assert sizes == pyramid.level_sizes(4 * h, 4 * w) and sizes[-1] == (4 * h, 4 * w)
     assert [s for s in sizes if s[0] >= h and s[1] >= w] == sizes[first:] and len(sizes) - first == 3
-    assert model._plan_pyramid(enc, scale=1) == (pyramid.level_sizes(h, w), len(pyramid.level_sizes(h, w)) - 1)
+    assert scene_render.plan_pyramid(model, enc, scale=1) == (pyramid.level_sizes(h, w), len(pyramid.level_sizes(h, w)) - 1)
 
 
 def test_cli_flags_reach_write_dzi(monkeypatch, tmp_path):

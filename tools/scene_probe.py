@@ -30,6 +30,7 @@ between two device synchronisations, and reports `cache.builds`.  Without `--par
 same process.  A second table: 16 views of `--view-size` squared along a pan across the image at x4, as 16 `render_view` calls and as
 one `render_many`: wall time and the number of synchronising device-to-host copies (counted around Tensor.tolist)."""
 import argparse
+import gc
 import json
 import os
 import subprocess
@@ -67,6 +68,7 @@ if not args.worker:
 
 
 def timed(fn):
+    gc.collect()                # an encode result is a reference cycle: a dropped round's scenes go now, not at the collector's next full pass
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     out = fn()
