@@ -49,6 +49,31 @@ Measured on an MI355X (profiles/trunk_exact.txt), worst |got - want| over the ru
   generic route at mid 32 (1), the (131, 253) map on the default route (1), EDSR per image (8), EDSR resident (8):   0.0 on every run --
   bitwise the float64 answer; no route needed a non-zero bound and no kernel or packing defect was found.  test_the_bound_has_teeth: one
   probe tap zeroed in the model moves every dense route 9 output units (1.3e-3 of the output scale) away from the unchanged answer.
+
+The 16-bit RDN trunk modes ('bf16', 'bf16-single', 'f16', 'f16-pairs'; rounding points: see H16 below).  Every tensor those modes round
+to bf16 / half is such a number on the probe and NB = 2 fixtures already -- block inputs, feeder outputs, the weights 9 * 2^-j, the ternary
+lff weights and the probe's output under 'f16' -- so `check_exact_h16` asserts that and the same condition, and fx.want, the same object,
+is the answer of every 16-bit route: test_trunk_h16_exact_gpu.py asserts torch.equal.  Such weights have no lo half; `split_probe`
+multiplies the probe's weights by 1 + s 2^-8 (hi + lo == w in both types, lo != 0 on every tap, half subnormals among them), with the
+condition asserted for the hi products, the lo products and both in one sum, and a second answer (`want_single`) for the mode that
+multiplies by hi alone.  'f16' is left out of the split fixtures (its fusion rounds the probe's output, which needs more than 11 bits
+there); 'bf16-single' meets the condition on them at the full 16 taps per row.  `H16_MUTATIONS`: what a dropped or misplaced lo
+fragment and a skipped 16-bit write of the fusion epilogue do to the float64 answer.
+
+Host figures of the 16-bit cases (test_trunk_h16_exact_host.py; worst log2(sum |addends| / q) over every case of h16_cases, < 22 asserted):
+  probes, every mode            direct 9 cin sum 8.3 (no lo);  lff + residual 11.1;  gff.1 + residual 13.3
+  NB = 2, every mode            direct 8.8;  lff + residual 11.8;  gff.1 + residual 13.8
+  split probes, bf16            hi 12.3, lo 7.9, hi + lo 16.3;  lff + residual 19.1;  gff.1 + residual 21.4
+  split probes, f16-pairs       hi 13.3, lo 5.1, hi + lo 16.3;  lff + residual 19.1;  gff.1 + residual 21.4
+  split probes, bf16-single     hi 12.3;  lff + residual 15.1;  gff.1 + residual 17.4
+Mutations of the reference (split probes 0, 3, 7 on (21, 37); one output unit 2^-12 / 2^-16 / 2^-16): one lo fragment's worth of one
+output row dropped 14 / 7 / 7 units in bf16 and 2 / 1 / 1 in half; two lo taps swapped 42 / 14 / 14 and 6 / 2 / 2; the 16-bit write of
+block 1's input skipped at one pixel column (NB = 2) 2348 units.
+
+Measured on an MI355X (profiles/trunk_h16_exact.txt), |got - want| of test_trunk_h16_exact_gpu.py: 0.0 on all 154 runs -- dense_h16_kernel<LO>
+(72 unsplit, 9 split), dense_h16_dma_kernel (10), dense_h16_wide_kernel<LO, 1> (37, 9), <LO, 2> (8, 9), in both element types, with
+cast_group_h16_kernel and, under 'f16', the fusion on gemm_h16.hip in each: bitwise the float64 answer, no defect found.  A model whose
+probe lo pack lacks one fragment's worth of one row is 7 (bf16) / 1 (half) output units off on each of the three cuts.
 """
 import math
 from collections import namedtuple
@@ -121,26 +146,30 @@ def conv_terms(x, w, b, skip=None):
     N, _, H, W_ = x.shape
     co, k = w.shape[0], w.shape[-1]
     p = k // 2
-    xp = F.pad(x, (p, p, p, p))
+    cs = w.flatten(2).any(2).any(0).nonzero().flatten().tolist()              # the input channels some tap reads: the others are not copied
+    at = {c: i for i, c in enumerate(cs)}
+    xp = F.pad(x if len(cs) == x.shape[1] else x[:, cs], (p, p, p, p))
     xa = xp.abs()
     y = b.view(1, co, 1, 1).expand(N, co, H, W_).clone()
     ya = y.abs()
     for o, c, a, bb in w.nonzero().tolist():
         v = float(w[o, c, a, bb])
-        t = v * xp[:, c, a:a + H, bb:bb + W_]
         if skip is not None and (o, c, a, bb) == tuple(skip[:4]):
-            t = t.clone()
+            t = v * xp[:, at[c], a:a + H, bb:bb + W_]
             t[:, :, skip[4]] = 0.0
-        y[:, o] += t
-        ya[:, o] += abs(v) * xa[:, c, a:a + H, bb:bb + W_]
+            y[:, o] += t
+        else:
+            y[:, o].add_(xp[:, at[c], a:a + H, bb:bb + W_], alpha=v)
+        ya[:, o].add_(xa[:, at[c], a:a + H, bb:bb + W_], alpha=abs(v))
     return y, ya
 
 
-def _check_direct(fig, stage, x, w, b, y_abs, group, res=None, alpha=1.0, where=''):
-    """The direct sum of a convolution (any order, any split) and its fused epilogue  res + alpha * (sum + bias)."""
+def _check_direct(fig, stage, x, w, b, y_abs, group, res=None, alpha=1.0, where='', units=None):
+    """The direct sum of a convolution (any order, any split) and its fused epilogue  res + alpha * (sum + bias).  `units`: unit_of of
+    each input group where the caller has them already."""
     q = math.inf
     for g0 in range(0, w.shape[1], group):
-        qw, qx = unit_of(w[:, g0:g0 + group]), unit_of(x[:, g0:g0 + group])
+        qw, qx = unit_of(w[:, g0:g0 + group]), units[g0 // group] if units else unit_of(x[:, g0:g0 + group])
         if math.isfinite(qw) and math.isfinite(qx):
             q = min(q, qw * qx)
     assert _multiple(b, q), f'{stage} {where}: the bias is not a multiple of the unit {q}'
@@ -200,16 +229,71 @@ def _check_wino(fig, m, x, w, b, y_direct, where=''):
 
 
 # ------------------------------------------------------------------------------------------------
+# the 16-bit trunk modes
+# ------------------------------------------------------------------------------------------------
+# The rounding points of a 16-bit RDN trunk mode, restated from the header of independent_refs.rdn_trunk_16bit_emulation and from
+# rdn_route / block_dense / block_fuse of csrc/encoder.hip (h = the mode's element type, bf16 or IEEE half):
+#   every mode    each block's input (group 0 of the 16-bit rows Xb: cast_group) and every dense layer's output (the layer's own 16-bit
+#                 write beside its fp32 one) are rounded to h before a dense layer reads them; the dense weights are packed as
+#                 hi = h(w), lo = h(w - hi); products exact, accumulation, bias and ReLU in fp32; stem, gff and all residual sums fp32.
+#   pairs         'bf16', 'f16-pairs': every dense product is taken with hi and with lo, as separate MFMAs into one fp32 sum.
+#   single        'bf16-single', 'f16': hi alone; the lo pack is not read.
+#   lff16         'f16' alone: the local fusion reads the SAME 16-bit rows -- the last layer's output included, which nothing else reads
+#                 in 16 bits -- with weights h(w_lff), fp32 accumulation, bias and fp32 residual; its epilogue writes the block's output
+#                 in fp32 and, rounded to h, as group 0 of the next block's 16-bit rows (no cast_group after block 0).  The other
+#                 three modes fuse in fp32 on the fp32 layer outputs with the fp32 weights.
+H16 = namedtuple('H16', 'mode half pairs lff16')
+H16_MODES = {m: H16(m, 'bf16' if m.startswith('bf16') else 'f16', m in ('bf16', 'f16-pairs'), m == 'f16') for m in ('bf16', 'bf16-single', 'f16', 'f16-pairs')}
+
+
+def round16(t, half):
+    """t (fp32 numbers held in float64) rounded to bf16 / IEEE half, in float64."""
+    return t.float().to(torch.bfloat16 if half == 'bf16' else torch.float16).double()
+
+
+def split16(w, half):
+    """hi = h(w), lo = h(w - hi): the weight pair of the fragment pack."""
+    hi = round16(w, half)
+    return hi, round16(w - hi, half)
+
+
+def _is16(t, half, what):
+    bad = round16(t, half) != t
+    assert not bad.any(), f'{what}: {int(bad.sum())} of {t.numel()} values are not {half} numbers (e.g. {t[bad][0].item()!r})'
+
+
+def _h16_weights(fig, t, w, b, h16, C, where, units):
+    """The weights a dense layer of that mode multiplies by; with `fig`, condition (b) on the direct 9 cin sums for the hi and the lo
+    products on their own (a kernel accumulates them as separate MFMAs, in any order and any K split) and for both in one sum."""
+    hi, lo = split16(w, h16.half)
+    if not h16.pairs:
+        lo = torch.zeros_like(lo)
+    if fig is not None:                   # (the input groups: rdn_eval asserts each as it is made)
+        if h16.pairs:
+            assert torch.equal(hi + lo, w), f'{where}: hi + lo is not the weight'
+        if lo.any():                      # (no lo: hi is the weight, and the caller's 'dense.direct' is the hi sum)
+            a_hi, a_lo = conv_terms(t, hi, b)[1], conv_terms(t, lo, torch.zeros_like(b))[1]
+            _check_direct(fig, 'dense.hi', t, hi, b, a_hi, C, where=where, units=units)
+            _check_direct(fig, 'dense.lo', t, lo, torch.zeros_like(b), a_lo, C, where=where, units=units)
+            _check_direct(fig, 'dense.hi+lo', t, torch.cat([hi, lo], 0), b, a_hi + a_lo, C, where=where, units=units)
+            fig['lo.taps'] = fig.get('lo.taps', 0) + int((lo != 0).sum())
+    return hi + lo
+
+
+# ------------------------------------------------------------------------------------------------
 # the float64 trunks
 # ------------------------------------------------------------------------------------------------
 def _conv(P, name):
     return P[name + '.weight'].double(), P[name + '.bias'].double()
 
 
-def rdn_eval(P, x, fig=None, wino=True, mutate=None):
+def rdn_eval(P, x, fig=None, wino=True, mutate=None, h16=None):
     """The RDN trunk of ciaosr_oracle.rdn_features in float64, convolution by convolution over the non-zero taps.  `fig`: a Figures to
     run check_exact's assertions into (`wino`: the dense layers in both Winograd forms too).  `mutate` = (kind, ...) applies one
-    reference mutation to the LAST block's probe layer: ('seam', col) | ('swap', c1, c2) | ('lastrow',)."""
+    reference mutation to the LAST block's probe layer: ('seam', col) | ('swap', c1, c2) | ('lastrow',); or ('stale16', col): in every
+    block after the first, the 16-bit rows keep the previous block's input at pixel column col (see H16_MUTATIONS).  `h16`: an H16 --
+    the dense layers multiply by the weights that 16-bit mode multiplies by (hi + lo, or hi alone), and `fig` also takes
+    check_exact_h16's assertions."""
     x = x.double()
     C = P['sfe1.weight'].shape[0]
     nb = 1 + max(int(k.split('.')[1]) for k in P if k.startswith('rdbs.'))
@@ -223,11 +307,20 @@ def rdn_eval(P, x, fig=None, wino=True, mutate=None):
     h, a = conv_terms(s1, w, b)
     if chk:
         _check_direct(fig, 'stem', s1, w, b, a, C, where='sfe2')
-    local = []
+    local, h_before = [], None
     for blk in range(nb):
         t = h
+        if mutate is not None and mutate[0] == 'stale16' and blk > 0:
+            t = h.clone()
+            t[:, :, :, mutate[1]] = h_before[:, :, :, mutate[1]]
+        h_before = h
+        units = [unit_of(t)] if chk else None          # unit_of of each input group of the block's dense layers
+        if chk and h16 is not None:        # group 0 of the 16-bit rows: cast_group, or (lff16, blk > 0) the previous block's epilogue
+            _is16(h, h16.half, f'block {blk} input')
         for l in range(nl):
             w, b = _conv(P, f'rdbs.{blk}.layers.{l}.conv')
+            if h16 is not None:
+                w = _h16_weights(fig, t, w, b, h16, C, f'block {blk} layer {l}', units)
             tin, skip, probe = t, None, (blk == nb - 1 and l == nl - 1)
             if mutate is not None and probe:
                 if mutate[0] == 'swap':
@@ -243,15 +336,20 @@ def rdn_eval(P, x, fig=None, wino=True, mutate=None):
                 y[:, :, -1] = 0.0
             if chk:
                 where = f'block {blk} layer {l}'
-                _check_direct(fig, 'dense.direct', t, w, b, a, C, where=where)
+                _check_direct(fig, 'dense.direct', t, w, b, a, C, where=where, units=units)
+                units.append(unit_of(torch.relu(y)))
                 if wino:
                     _check_wino(fig, 2, t, w, b, y, where)
                     _check_wino(fig, 4, t, w, b, y, where)
                 fig['dense.alive'] = min(fig.get('dense.alive', 1.0), (y > 0).double().mean().item())
+                if h16 is not None and (l < nl - 1 or h16.lff16):       # the 16-bit copy of the output that a later layer or lff16 reads
+                    _is16(torch.relu(y), h16.half, f'block {blk} layer {l} output')
             t = torch.cat([t, torch.relu(y)], 1)
         if chk:
             fig[f'block{blk}.in.max'] = max(fig.get(f'block{blk}.in.max', 0.0), h.abs().max().item())
         w, b = _conv(P, f'rdbs.{blk}.lff')
+        if chk and h16 is not None and h16.lff16:                       # cast_weights: the local fusion multiplies by half(w)
+            _is16(w, h16.half, f'block {blk} lff weights')
         y, a = conv_terms(t, w, b)
         if chk:
             _check_direct(fig, 'lff', t, w, b, a, C, res=h, where=f'block {blk}')
@@ -486,6 +584,150 @@ def edsr(hw, B=1):
             assert torch.equal(_params_cache['edsr'][0][k].double(), v), k
     P, psi = _params_cache['edsr']
     return _fixture('edsr', 'edsr', P, psi, hw, B, EDSR_RES_SCALE)
+
+
+# ------------------------------------------------------------------------------------------------
+# the 16-bit trunk modes: fixtures, the condition, mutations, cases
+# ------------------------------------------------------------------------------------------------
+SPLIT = 2.0 ** -8               # 2^-9: probe 7 misses the condition at gff.1 (22.09 bits); 2^-7: every half `lo` is zero
+_single_cache, _h16_memo = {}, {}
+
+
+def _probe_name(P):
+    nb = 1 + max(int(k.split('.')[1]) for k in P if k.startswith('rdbs.'))
+    nl = 1 + max(int(k.split('.')[3]) for k in P if k.startswith('rdbs.0.layers.'))
+    return f'rdbs.{nb - 1}.layers.{nl - 1}.conv.weight'
+
+
+def split_probe(l, hw=(21, 37), B=1):
+    """probe(l, ...) with every weight of the probe layer multiplied by 1 + s * 2^-8, s = +-1 per tap from a seeded generator: neither a
+    bf16 nor a half number, but hi + lo == w exactly in both types and lo != 0 on every tap (half: the lo of the 9/256 taps is the
+    subnormal 2^-16).  `want` is the float64 evaluation with those weights -- the answer of the pair modes 'bf16' and 'f16-pairs';
+    want_single(fx, half) is the answer of a mode that multiplies by hi alone ('bf16-single').  Mode 'f16' is left out of this fixture:
+    its local fusion reads the probe's output rounded to half, and those values (multiples of 2^-16 up to a few units) need more than
+    the 11 bits of a half significand."""
+    key = ('split', l)
+    if key not in _params_cache:
+        P, psi = _rdn_params32(('probe', l), l + 1, 1, 64)
+        g = torch.Generator().manual_seed(977 + l)
+        name = _probe_name(P)
+        w = P[name].double()
+        ws = w * (1.0 + (torch.randint(0, 2, w.shape, generator=g) * 2 - 1).double() * SPLIT)
+        assert torch.equal(ws.float().double(), ws)
+        _params_cache[key] = (dict(P, **{name: ws.float()}), psi)
+    P, psi = _params_cache[key]
+    return _fixture('rdn', f'split{l}', P, psi, hw, B)
+
+
+def want_single(fx, half):
+    """The float64 evaluation of a split fixture with the probe weights rounded once to the element type: what a mode that ignores `lo`
+    computes."""
+    key = (fx.name, fx.hw, fx.B, half)
+    if key not in _single_cache:
+        name = _probe_name(fx.params)
+        _single_cache[key] = rdn_eval(dict(fx.params, **{name: round16(fx.params[name].double(), half).float()}), fx.x)
+    return _single_cache[key]
+
+
+def h16_answer(fx, mode):
+    """The float64 answer of a 16-bit trunk mode on a fixture: fx.want itself, but want_single where hi alone is not the weight."""
+    h = H16_MODES[mode]
+    return want_single(fx, h.half) if fx.name.startswith('split') and not h.pairs else fx.want
+
+
+def check_exact_h16(fx, mode):
+    """check_exact for a 16-bit trunk mode (rounding points: see H16).  Re-evaluates the fixture in float64 with the weights that mode
+    multiplies by and asserts  (a) every tensor a route of the mode rounds to its element type is such a number already: each block's
+    input (group 0 of the 16-bit rows, which under 'f16' the previous block's fusion epilogue writes), every dense-layer output a later
+    layer or the 16-bit fusion reads, the dense weights as hi + lo (pairs) or hi alone, the fusion weights under 'f16';  (b) the condition
+    (addends multiples of one power of two q, sum |addends| < 2^22 q) on the direct 9 cin sums with the hi weights, with the lo weights
+    and with both in one sum;  (c) the same for stem, lff, gff and the residual epilogues as in check_exact.  Returns the figures."""
+    h = H16_MODES[mode]
+    split = fx.name.startswith('split')
+    assert fx.kind == 'rdn' and fx.params['sfe1.weight'].shape[0] == 64 and not (split and h.lff16)
+    # (an unsplit fixture has no lo: the two bf16 modes multiply by the same weights and round the same tensors -- one evaluation)
+    key = (fx.name, fx.hw, fx.B, h.half, h.lff16, h.pairs and split)
+    if not split and not h.lff16 and (key[:4] + (True, False)) in _h16_memo:
+        key = key[:4] + (True, False)          # ... and what 'f16' asserts on it contains what 'f16-pairs' needs
+    if key not in _h16_memo:
+        fig = Figures()
+        got = rdn_eval(fx.params, fx.x, fig, wino=False, h16=h)
+        assert torch.equal(got, h16_answer(fx, mode))
+        _h16_memo[key] = fig
+    fig = Figures(_h16_memo[key])
+    for k, w in fx.params.items():
+        if '.layers.' in k and k.endswith('.weight') and not (split and k == _probe_name(fx.params)):
+            _is16(w.double(), h.half, k)                              # hi alone is the weight
+    assert torch.equal(fx.x, fx.x.round()) and fx.x.abs().max() <= 1
+    return fig
+
+
+def lo_mutated(fx, half, kind, row=5):
+    """The parameters of a split fixture with the `lo` halves of output row `row` of the probe changed as a kernel defect would (K order
+    of the fragment pack: k = (a * 3 + b) * cin + ci): 'drop' -- one fragment's worth, the 16 consecutive K indices around the row's
+    first tap, zero;  'swap' -- the lo halves of the row's first two taps with opposite lo exchanged."""
+    name = _probe_name(fx.params)
+    w = fx.params[name].double()
+    hi, lo = split16(w, half)
+    assert torch.equal(hi + lo, w)
+    co, cin = w.shape[:2]
+    lo_k = lo.permute(0, 2, 3, 1).reshape(co, -1).clone()
+    taps = lo_k[row].nonzero().flatten().tolist()
+    if kind == 'drop':
+        k0 = taps[0] // 16 * 16
+        lo_k[row, k0:k0 + 16] = 0.0
+    else:
+        k1, k2 = next((a, b) for a in taps for b in taps if lo_k[row, b] == -lo_k[row, a])     # (same magnitude: input groups of one unit)
+        lo_k[row, k1], lo_k[row, k2] = lo_k[row, k2].clone(), lo_k[row, k1].clone()
+    wm = hi + lo_k.view(co, 3, 3, cin).permute(0, 3, 1, 2)
+    assert torch.equal(wm.float().double(), wm) and not torch.equal(wm, w)
+    return dict(fx.params, **{name: wm.float()})
+
+
+STALE_COLUMN = 18
+# reference mutations of the 16-bit routes: name -> function of (probe, element type) -> (fixture, mutated float64 answer)
+H16_MUTATIONS = {
+    "one lo fragment's worth of taps dropped (16 consecutive K indices of one output row)":
+        lambda l, half: (split_probe(l), rdn_eval(lo_mutated(split_probe(l), half, 'drop'), split_probe(l).x)),
+    'two lo taps of one output row swapped':
+        lambda l, half: (split_probe(l), rdn_eval(lo_mutated(split_probe(l), half, 'swap'), split_probe(l).x)),
+    f"the fusion epilogue's 16-bit write of block 1's input skipped at pixel column {STALE_COLUMN} (the rows keep block 0's input there)":
+        lambda l, half: (two_blocks(), rdn_eval(two_blocks().params, two_blocks().x, mutate=('stale16', STALE_COLUMN))),
+}
+
+# the cases of test_trunk_h16_exact_gpu.py (test_trunk_h16_exact_host.py runs check_exact_h16 on every (fixture, mode) of them)
+H16_ALL = tuple(H16_MODES)
+H16_SINGLE = ('f16', 'bf16-single')                       # no lo pack: a batch takes dense_h16_dma_kernel on the 12 x 12 route
+H16_SPLIT = ('bf16', 'f16-pairs', 'bf16-single')
+H16_SMALL_MAPS = [(12, 12), (13, 25), (21, 37), (7, 30)]   # one 12 x 12 tile; one-pixel remainders; ragged; lower than a tile
+H16_WIDE_MAPS = [(64, 256), (65, 225), (17, 1000)]         # 32 whole 16 x 32 tiles; one-row and one-column remainders; a strip
+H16_WIDE2 = ((81, 257), 3)                                 # 162 tiles of 16 x 32 in the launch: the 16 x 32 tile shape (R = 2)
+H16Case = namedtuple('H16Case', 'fixture l hw B direct modes kernel')
+
+
+def h16_cases():
+    """kernel: '12x12' = dense_h16_kernel, 'dma' = dense_h16_dma_kernel where the mode has no lo pack (dense_h16_kernel<true> else),
+    'wide1' / 'wide2' = dense_h16_wide_kernel<LO, R>."""
+    out = []
+    for hw in H16_SMALL_MAPS:
+        out += [H16Case('probe', l, hw, 1, 1, H16_ALL, '12x12') for l in (range(8) if hw == (21, 37) else (0, 1, 7))]
+    out.append(H16Case('nb2', None, (21, 37), 1, 1, H16_ALL, '12x12'))
+    out += [H16Case('probe', l, hw, 3, 1, H16_SINGLE, 'dma') for hw in ((21, 37), (13, 25)) for l in (0, 7)]
+    out.append(H16Case('nb2', None, (21, 37), 3, 1, H16_SINGLE, 'dma'))
+    out += [H16Case('probe', l, hw, 1, 0, H16_ALL, 'wide1') for hw in H16_WIDE_MAPS for l in (0, 3, 7)]
+    out += [H16Case('probe', l, H16_WIDE2[0], H16_WIDE2[1], 0, H16_ALL, 'wide2') for l in (0, 7)]
+    for hw, B, direct, kernel in (((21, 37), 1, 1, '12x12'), ((65, 225), 1, 0, 'wide1'), H16_WIDE2 + (0, 'wide2')):
+        out += [H16Case('split', l, hw, B, direct, H16_SPLIT, kernel) for l in (0, 3, 7)]
+    out.append(H16Case('nb2', None, (65, 225), 2, 0, ('f16',), 'wide1'))       # the fusion epilogue's 16-bit write feeds block 1
+    return out
+
+
+def h16_fixture(c):
+    return two_blocks(c.hw, c.B) if c.fixture == 'nb2' else (split_probe if c.fixture == 'split' else probe)(c.l, c.hw, c.B)
+
+
+def h16_id(c):
+    return f"{c.fixture}{'' if c.l is None else c.l}-{c.hw[0]}x{c.hw[1]}-b{c.B}-{c.kernel}"
 
 
 # the cases of test_trunk_exact_gpu.py (test_trunk_exact_host.py runs check_exact on every one of them)

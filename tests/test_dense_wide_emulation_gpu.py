@@ -20,7 +20,9 @@ in bf16 needed the measured max bound the 12 x 12 kernels set (BATCH_FLIP_MAX be
 both routes).  All four modes matched the emulation; no kernel change was needed.
 
 Both cuts carry the profile tag `enc_dense_<type>`; that both really ran shows in their results not being bitwise equal.
-That the emulation is sharp (one dropped halo column of one tap moves it by far more than the bound) is test_reference_sharpness.py's."""
+That the emulation is sharp (one dropped halo column of one tap moves it by far more than the bound) is test_reference_sharpness.py's.
+What the deeper-trunk yardstick (HIP against HIP) cannot bound -- layer 7 of a block, the `lo` fragments, the f16 fusion epilogue, the
+second image of a batch slice -- test_trunk_h16_exact_gpu.py holds bitwise to a float64 answer on exact-arithmetic fixtures."""
 import pytest
 import torch
 
