@@ -1,0 +1,795 @@
+// Baseline JPEG encoding of an 8-bit image on the device (ciaosr_amd/jpeg_hip.py): libjpeg's integer pipeline as Pillow drives it, so
+// that the files are byte for byte `PIL.Image.save(format='JPEG', quality=q, subsampling=0 | 2)`'s (DESIGN 4.1i-d holds the contract).
+// The device makes the entropy-coded scan, stuffed and padded; the host wraps it in the header (which depends on h, w, quality and
+// subsampling only) and EOI.
+//
+// One image and many crops of one image run through the same eight launches; the host uploads one table (constants of the quality,
+// the tiles, the chunks: `mcus_per_chunk` MCUs of ONE tile each) and every kernel but the two scans has one workgroup per chunk:
+//   jpeg_coef    8 lanes per block: lane r converts the 8 samples of row r (colour conversion, 4:2:0 box filter, edge replication as
+//                clamped coordinates of the crop), runs the row pass of jfdctint, the block is transposed through LDS, lane c runs the
+//                column pass, quantises and writes int16 coefficients in zigzag order, blocks in scan order.  A dummy luma block of
+//                4:2:0 is computed from the block whose DC it repeats, its AC zeroed.
+//   jpeg_count   one lane per block: the block's code length in bits; its DC difference reads the previous block's quantised DC of the
+//                same component, so nothing is carried from block to block.  The lengths are summed per chunk.
+//   jpeg_scan    one workgroup: prefix sum of the chunks' bits, per tile its unstuffed bytes and a 4-byte aligned place in the
+//                unstuffed buffer, per chunk its bit offset, the byte range it owns there and the pad mask of a tile's last byte.
+//   jpeg_zero    zeroes the unstuffed buffer up to the total that the scan found.
+//   jpeg_pack    one lane per block: a workgroup scan of the lengths gives the block's bit offset; the lane shifts its codes into a
+//                64-bit accumulator, MSB first, and writes whole 32-bit words.  Blocks do not begin on byte boundaries: the first and
+//                the last word of a block go through atomicOr on the zeroed buffer, the words between them belong to the block alone.
+//                Integer OR does not depend on arrival order.
+//   jpeg_ffcount per chunk the 0xFF bytes of its byte range (the byte that holds a chunk's first bit belongs to the chunk before).
+//   jpeg_scan2   one workgroup: prefix sum of bytes + 0xFF counts -> every chunk's final offset, the tiles' offsets, the total.
+//   jpeg_stuff   copies the bytes to their final place with a 0x00 after every 0xFF; a tile's last byte is padded with 1-bits.
+// No floating point anywhere; the bytes do not depend on mcus_per_chunk, on the stream or on what else is in the list.
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "ops.h"
+
+namespace ciaosr {
+namespace jpeg {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kBlocksPerStep = kThreads / 8;       // coefficient kernel: 8 lanes per block
+constexpr int kHuff = 272;                         // per table class: 256 AC entries by (run << 4 | size), then 12 DC entries by size
+constexpr u64 kBlockBytes = 208;                   // 64 coefficients x (16-bit code + 10 extra bits): the most a block can take
+constexpr int kStuffPerLane = 16;                  // bytes per lane and step of the stuffing kernels
+constexpr int kZeroGroups = 1024;
+
+struct Consts {
+    int qdiv[2][64];                               // 8 x quantisation table, natural order; [0] luma, [1] chroma
+    u32 huff[2][kHuff];                            // length << 16 | code
+    int zig_of_nat[64];                            // position in zigzag order of the natural index row * 8 + column
+};
+struct TileT {
+    int y0, x0, h, w;
+    int mx, nmcu;                                  // MCUs per row, MCUs
+    u32 first_chunk, block0;                       // its first chunk, its first block in scan order
+};
+struct ChunkT {
+    int tile, mcu0, mcu1, pad_;
+};
+
+static const unsigned char kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+                                            69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55,  64,
+                                            81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+static const unsigned char kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                              99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                              99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// Annex K "typical" Huffman tables: code counts per length 1..16, then the symbols in code order
+static const unsigned char kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+static const unsigned char kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+static const unsigned char kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa}};
+
+static void canonical(const unsigned char* bits, const unsigned char* vals, u32* by_symbol) {
+    u32 code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < bits[len - 1]; ++i, ++k, ++code) by_symbol[vals[k]] = ((u32)len << 16) | code;
+        code <<= 1;
+    }
+}
+
+static void make_consts(int quality, Consts* c) {
+    memset(c, 0, sizeof(*c));
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) {
+        const int base[2] = {kBaseLuma[i], kBaseChroma[i]};
+        for (int t = 0; t < 2; ++t) {
+            int q = (base[t] * s + 50) / 100;
+            q = q < 1 ? 1 : (q > 255 ? 255 : q);
+            c->qdiv[t][i] = 8 * q;
+        }
+    }
+    static const unsigned char dc_vals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+    for (int t = 0; t < 2; ++t) {
+        canonical(kAcBits[t], kAcVals[t], c->huff[t]);
+        canonical(kDcBits[t], dc_vals, c->huff[t] + 256);
+    }
+    int k = 0;                                              // the zigzag walk over the anti-diagonals
+    for (int d = 0; d < 15; ++d)
+        for (int i = 0; i < 8; ++i) {
+            const int r = (d & 1) ? i : 7 - i, col = d - r;  // odd diagonals run down, even ones up
+            if (col < 0 || col > 7) continue;
+            c->zig_of_nat[r * 8 + col] = k++;
+        }
+}
+
+// ---- device helpers --------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;
+}
+
+// sum of v over the workgroup, in every lane
+__device__ __forceinline__ u64 wg_sum_u64(u64 v, u64* red /* LDS [kWaves] */) {
+    const int tid = threadIdx.x;
+    v = wave_sum_u64(v);
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    u64 s = 0ull;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) s += red[w];
+    return s;
+}
+
+// exclusive prefix sum of v over the workgroup's lanes; *total = the sum
+__device__ __forceinline__ u32 wg_scan_u32(u32 v, u32* wsum /* LDS [kWaves] */, u32* total) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    u32 inc = v;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const u32 t = __shfl_up(inc, off, kWave);
+        if (lane >= off) inc += t;
+    }
+    __syncthreads();
+    if (lane == kWave - 1) wsum[wave] = inc;
+    __syncthreads();
+    u32 before = 0u, all = 0u;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (w < wave) before += wsum[w];
+        all += wsum[w];
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+// One workgroup: out[i] = sum of in[0 .. i) for i in [0, n], lane t owning a run of ceil(n / kThreads) elements.
+__device__ __forceinline__ void wg_prefix_u64(const u64* in, u64* out, int n, u64* tot /* LDS [kThreads] */) {
+    const int tid = threadIdx.x;
+    const int per = (n + kThreads - 1) / kThreads;
+    const int i0 = min(n, tid * per), i1 = min(n, i0 + per);
+    u64 sum = 0ull;
+    for (int i = i0; i < i1; ++i) sum += in[i];
+    __syncthreads();
+    tot[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        u64 run = 0ull;
+        for (int t = 0; t < kThreads; ++t) {
+            const u64 v = tot[t];
+            tot[t] = run;
+            run += v;
+        }
+        out[n] = run;
+    }
+    __syncthreads();
+    u64 off = tot[tid];
+    for (int i = i0; i < i1; ++i) {
+        const u64 v = in[i];
+        out[i] = off;
+        off += v;
+    }
+    __syncthreads();
+}
+
+// ---- coefficients ----------------------------------------------------------------------------------------------------------------
+struct Params {
+    const unsigned char* src;     // [H][pitch], 3 bytes per pixel
+    size_t pitch;
+    int bgr, sub420, nt, nc;
+    const Consts* consts;
+    const TileT* tiles;
+    const ChunkT* chunks;
+    short* coef;                  // [blocks][64], zigzag order, blocks in scan order
+    u32* block_bits;              // [blocks]
+    u64* chunk_bits;              // [nc]
+    u64* chunk_sum;               // [nc + 1]: prefix sum of chunk_bits
+    u64* chunk_bitoff;            // [nc]: the chunk's first bit in the unstuffed buffer
+    u64* chunk_b0;                // [nc]: the unstuffed bytes [b0, b1) that the chunk owns
+    u64* chunk_b1;
+    u32* chunk_pad;               // [nc]: 1-bits to OR into byte b1 - 1 (a tile's last byte), else 0
+    u64* chunk_out;               // [nc]: bytes + 0xFF count of the chunk, then (in place) its final offset; [nc] = the total
+    u64* tile_ubase;              // [nt]: the tile's first byte in the unstuffed buffer (4-byte aligned)
+    u64* utotal;                  // [1]: bytes of the unstuffed buffer in use (a multiple of 4)
+    u32* ubuf;                    // the unstuffed streams
+    unsigned char* out;
+    u64* tile_offs;               // [nt + 1]
+    u64* total;                   // optional: tile_offs[nt] once more
+};
+
+constexpr int kF0_298 = 2446, kF0_390 = 3196, kF0_541 = 4433, kF0_765 = 6270, kF0_899 = 7373, kF1_175 = 9633, kF1_501 = 12299,
+              kF1_847 = 15137, kF1_961 = 16069, kF2_053 = 16819, kF2_562 = 20995, kF3_072 = 25172;
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// jfdctint's 8-point pass; FIRST: the row pass (outputs scaled up by 2^2), else the column pass
+template <bool FIRST>
+__device__ __forceinline__ void dct8(int d[8]) {
+    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    constexpr int n = FIRST ? 11 : 15;
+    d[0] = FIRST ? (t10 + t11) << 2 : descale(t10 + t11, 2);
+    d[4] = FIRST ? (t10 - t11) << 2 : descale(t10 - t11, 2);
+    int z1 = (t12 + t13) * kF0_541;
+    d[2] = descale(z1 + t13 * kF0_765, n);
+    d[6] = descale(z1 - t12 * kF1_847, n);
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * kF1_175;
+    const int a4 = t4 * kF0_298, a5 = t5 * kF2_053, a6 = t6 * kF3_072, a7 = t7 * kF1_501;
+    z1 *= -kF0_899;
+    z2 *= -kF2_562;
+    z3 = z3 * -kF1_961 + z5;
+    z4 = z4 * -kF0_390 + z5;
+    d[7] = descale(a4 + z1 + z3, n);
+    d[5] = descale(a5 + z2 + z4, n);
+    d[3] = descale(a6 + z2 + z3, n);
+    d[1] = descale(a7 + z1 + z4, n);
+}
+
+// component `comp` of the pixel at q (3 bytes)
+__device__ __forceinline__ int ycc(const unsigned char* q, int bgr, int comp) {
+    const int r = q[bgr ? 2 : 0], g = q[1], b = q[bgr ? 0 : 2];
+    if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    if (comp == 1) return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_coef_kernel(Params p) {
+    __shared__ int xpose[kBlocksPerStep][8][9];
+    __shared__ int qdiv[2][64];
+    __shared__ int zig[64];
+    const int tid = threadIdx.x, slot = tid >> 3, l8 = tid & 7;
+    if (tid < 128) qdiv[tid >> 6][tid & 63] = p.consts->qdiv[tid >> 6][tid & 63];
+    if (tid < 64) zig[tid] = p.consts->zig_of_nat[tid];
+    const ChunkT ch = p.chunks[blockIdx.x];
+    const TileT t = p.tiles[ch.tile];
+    const int bpm = p.sub420 ? 6 : 3;
+    const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
+    const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
+    const unsigned char* org = p.src + (size_t)t.y0 * p.pitch + 3 * (size_t)t.x0;
+    const int nby = (t.h + 7) >> 3, nbx = (t.w + 7) >> 3;
+    __syncthreads();
+    for (int j0 = 0; j0 < nblk; j0 += kBlocksPerStep) {
+        const int j = j0 + slot;
+        const bool active = j < nblk;
+        int comp = 0;
+        bool dummy = false;
+        int d[8];
+        if (active) {
+            const int mcu = ch.mcu0 + j / bpm, k = j % bpm;
+            const int my = mcu / t.mx, mxi = mcu % t.mx;
+            if (!p.sub420 || k < 4) {                      // a full-resolution block
+                int by = my, bx = mxi;
+                comp = k;
+                if (p.sub420) {
+                    comp = 0;
+                    int kk = k;                             // a dummy block repeats the nearest real block before it in the MCU
+                    while (kk > 0 && (2 * my + (kk >> 1) >= nby || 2 * mxi + (kk & 1) >= nbx)) --kk;
+                    dummy = kk != k;
+                    by = 2 * my + (kk >> 1);
+                    bx = 2 * mxi + (kk & 1);
+                }
+                const unsigned char* row = org + (size_t)min(by * 8 + l8, t.h - 1) * p.pitch;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) d[i] = ycc(row + 3 * (size_t)min(bx * 8 + i, t.w - 1), p.bgr, comp) - 128;
+            } else {                                        // 4:2:0 chroma: rows to even, columns to 16 k, halve, rows to 8 k
+                comp = k - 3;
+                const int h2 = (t.h + 1) >> 1;
+                const int i2 = min(my * 8 + l8, h2 - 1);
+                const unsigned char* ra = org + (size_t)min(2 * i2, t.h - 1) * p.pitch;
+                const unsigned char* rb = org + (size_t)min(2 * i2 + 1, t.h - 1) * p.pitch;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int jx = mxi * 8 + i;
+                    const size_t xa = 3 * (size_t)min(2 * jx, t.w - 1), xb = 3 * (size_t)min(2 * jx + 1, t.w - 1);
+                    const int sum = ycc(ra + xa, p.bgr, comp) + ycc(ra + xb, p.bgr, comp) + ycc(rb + xa, p.bgr, comp) + ycc(rb + xb, p.bgr, comp);
+                    d[i] = ((sum + 1 + (i & 1)) >> 2) - 128;
+                }
+            }
+            dct8<true>(d);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xpose[slot][l8][i] = d[i];
+        }
+        __syncthreads();
+        if (active) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d[i] = xpose[slot][i][l8];
+            dct8<false>(d);
+            short* dst = p.coef + (base + (u64)j) * 64ull;
+            const int* qd = qdiv[comp ? 1 : 0];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int nat = i * 8 + l8;
+                const int div = qd[nat];
+                const int a = abs(d[i]);
+                int q = (a + (div >> 1)) / div;
+                if (d[i] < 0) q = -q;
+                if (dummy && nat != 0) q = 0;
+                dst[zig[nat]] = (short)q;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- entropy coding --------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bit_length(int a) { return 32 - __clz(a); }       // a >= 0; 0 -> 0
+
+// Walks one block: e.put(value, length) for the DC difference and every AC code with its extra bits appended.
+template <typename E>
+__device__ __forceinline__ void code_block(const short* cf, int pred, const u32* tab /* [kHuff] */, E& e) {
+    const uint4* v4 = reinterpret_cast<const uint4*>(cf);
+    int run = 0;
+#pragma unroll 1
+    for (int g = 0; g < 8; ++g) {
+        const uint4 q = v4[g];
+        const u32 w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            int v = (int)(short)(w[i >> 1] >> (16 * (i & 1)));
+            const bool dc = g == 0 && i == 0;
+            if (dc) v -= pred;
+            if (v == 0 && !dc) {
+                ++run;
+                continue;
+            }
+            const int n = bit_length(abs(v));
+            const u32 extra = (u32)(v < 0 ? v + (1 << n) - 1 : v) & ((1u << n) - 1u);
+            u32 ent;
+            if (dc) {
+                ent = tab[256 + n];
+            } else {
+                while (run > 15) {
+                    const u32 z = tab[0xf0];
+                    e.put(z & 0xffffu, (int)(z >> 16));
+                    run -= 16;
+                }
+                ent = tab[(run << 4) | n];
+                run = 0;
+            }
+            e.put(((ent & 0xffffu) << n) | extra, (int)(ent >> 16) + n);
+        }
+    }
+    if (run > 0) {
+        const u32 z = tab[0x00];
+        e.put(z & 0xffffu, (int)(z >> 16));
+    }
+}
+
+struct Counter {
+    u32 bits;
+    __device__ __forceinline__ void put(u32, int len) { bits += (u32)len; }
+};
+
+// MSB-first packer into 32-bit words of the zeroed buffer: the first word it writes and its last, partial one are shared with the
+// neighbouring blocks (atomicOr), the words between belong to this block alone.  A byte stream: word w holds bytes 4 w .. 4 w + 3.
+struct Packer {
+    u32* buf;
+    u64 w;
+    u64 acc;
+    int nacc;
+    bool first;
+    __device__ __forceinline__ void put(u32 val, int len) {            // 1 <= len <= 27, nacc < 32
+        acc |= (u64)val << (64 - nacc - len);
+        nacc += len;
+        if (nacc >= 32) {
+            const u32 word = __builtin_bswap32((u32)(acc >> 32));
+            if (first) {
+                atomicOr(&buf[w], word);
+                first = false;
+            } else {
+                buf[w] = word;
+            }
+            ++w;
+            acc <<= 32;
+            nacc -= 32;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (nacc > 0) atomicOr(&buf[w], __builtin_bswap32((u32)(acc >> 32)));
+    }
+};
+
+// the quantised DC that block j of the chunk's tile predicts from: the previous block of its component in scan order, 0 at the start
+__device__ __forceinline__ int dc_pred(const Params& p, const TileT& t, u64 blk) {
+    const int bpm = p.sub420 ? 6 : 3;
+    const u64 rel = blk - t.block0;
+    const int k = (int)(rel % bpm);
+    const u64 mcu = rel / bpm;
+    u64 prev;
+    if (p.sub420 && k > 0 && k < 4) {
+        prev = blk - 1;
+    } else {
+        if (mcu == 0) return 0;
+        prev = (p.sub420 && k == 0) ? blk - 3 : blk - bpm;
+    }
+    return (int)p.coef[prev * 64ull];
+}
+
+__device__ __forceinline__ int table_of(const Params& p, const TileT& t, u64 blk) {
+    const int bpm = p.sub420 ? 6 : 3;
+    const int k = (int)((blk - t.block0) % bpm);
+    return p.sub420 ? (k < 4 ? 0 : 1) : (k == 0 ? 0 : 1);
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_count_kernel(Params p) {
+    __shared__ u32 tab[2][kHuff];
+    __shared__ u64 red[kWaves];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = (&p.consts->huff[0][0])[i];
+    const ChunkT ch = p.chunks[blockIdx.x];
+    const TileT t = p.tiles[ch.tile];
+    const int bpm = p.sub420 ? 6 : 3;
+    const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
+    const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
+    __syncthreads();
+    u64 sum = 0ull;
+    for (int j = tid; j < nblk; j += kThreads) {
+        const u64 blk = base + (u64)j;
+        Counter c{0u};
+        code_block(p.coef + blk * 64ull, dc_pred(p, t, blk), tab[table_of(p, t, blk)], c);
+        p.block_bits[blk] = c.bits;
+        sum += c.bits;
+    }
+    sum = wg_sum_u64(sum, red);
+    if (tid == 0) p.chunk_bits[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_scan_kernel(Params p) {
+    __shared__ u64 tot[kThreads];
+    const int tid = threadIdx.x, nt = p.nt, nc = p.nc;
+    wg_prefix_u64(p.chunk_bits, p.chunk_sum, nc, tot);
+    // tiles: bytes of each unstuffed stream, placed at multiples of 4
+    {
+        const int per = (nt + kThreads - 1) / kThreads;
+        const int t0 = min(nt, tid * per), t1 = min(nt, t0 + per);
+        u64 sum = 0ull;
+        for (int t = t0; t < t1; ++t) {
+            const u32 c0 = p.tiles[t].first_chunk, c1 = t + 1 < nt ? p.tiles[t + 1].first_chunk : (u32)nc;
+            const u64 bits = p.chunk_sum[c1] - p.chunk_sum[c0];
+            sum += (((bits + 7ull) >> 3) + 3ull) & ~3ull;
+        }
+        tot[tid] = sum;
+        __syncthreads();
+        if (tid == 0) {
+            u64 run = 0ull;
+            for (int k = 0; k < kThreads; ++k) {
+                const u64 v = tot[k];
+                tot[k] = run;
+                run += v;
+            }
+            *p.utotal = run;
+        }
+        __syncthreads();
+        u64 off = tot[tid];
+        for (int t = t0; t < t1; ++t) {
+            const u32 c0 = p.tiles[t].first_chunk, c1 = t + 1 < nt ? p.tiles[t + 1].first_chunk : (u32)nc;
+            const u64 bits = p.chunk_sum[c1] - p.chunk_sum[c0];
+            p.tile_ubase[t] = off;
+            off += (((bits + 7ull) >> 3) + 3ull) & ~3ull;
+        }
+        __syncthreads();
+    }
+    for (int c = tid; c < nc; c += kThreads) {
+        const int t = p.chunks[c].tile;
+        const u32 c0 = p.tiles[t].first_chunk, c1 = t + 1 < nt ? p.tiles[t + 1].first_chunk : (u32)nc;
+        const u64 rel0 = p.chunk_sum[c] - p.chunk_sum[c0], rel1 = p.chunk_sum[c + 1] - p.chunk_sum[c0];
+        const u64 ub = p.tile_ubase[t];
+        p.chunk_bitoff[c] = ub * 8ull + rel0;
+        p.chunk_b0[c] = ub + ((rel0 + 7ull) >> 3);
+        p.chunk_b1[c] = ub + ((rel1 + 7ull) >> 3);
+        p.chunk_pad[c] = ((u32)c + 1u == c1 && (rel1 & 7ull)) ? (0xffu >> (u32)(rel1 & 7ull)) : 0u;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_zero_kernel(Params p) {
+    const u64 words = *p.utotal >> 2;
+    for (u64 i = (u64)blockIdx.x * kThreads + threadIdx.x; i < words; i += (u64)gridDim.x * kThreads) p.ubuf[i] = 0u;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(Params p) {
+    __shared__ u32 tab[2][kHuff];
+    __shared__ u32 wsum[kWaves];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = (&p.consts->huff[0][0])[i];
+    const ChunkT ch = p.chunks[blockIdx.x];
+    const TileT t = p.tiles[ch.tile];
+    const int bpm = p.sub420 ? 6 : 3;
+    const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
+    const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
+    u64 pos = p.chunk_bitoff[blockIdx.x];
+    __syncthreads();
+    for (int j0 = 0; j0 < nblk; j0 += kThreads) {
+        const int j = j0 + tid;
+        const u64 blk = base + (u64)j;
+        const u32 bits = j < nblk ? p.block_bits[blk] : 0u;
+        u32 step_bits;
+        const u32 before = wg_scan_u32(bits, wsum, &step_bits);
+        if (j < nblk) {
+            const u64 at = pos + before;
+            Packer pk{p.ubuf, at >> 5, 0ull, (int)(at & 31ull), true};
+            code_block(p.coef + blk * 64ull, dc_pred(p, t, blk), tab[table_of(p, t, blk)], pk);
+            pk.finish();
+        }
+        pos += step_bits;
+    }
+}
+
+// byte i of the unstuffed buffer as the chunk that owns it sees it
+__device__ __forceinline__ u32 ubyte(const unsigned char* u, u64 i, u64 b1, u32 pad) {
+    u32 v = u[i];
+    if (i + 1 == b1) v |= pad;
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_ffcount_kernel(Params p) {
+    __shared__ u64 red[kWaves];
+    const int c = blockIdx.x;
+    const u64 b0 = p.chunk_b0[c], b1 = p.chunk_b1[c];
+    const u32 pad = p.chunk_pad[c];
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(p.ubuf);
+    u64 n = 0ull;
+    for (u64 i = b0 + threadIdx.x; i < b1; i += kThreads) n += ubyte(u, i, b1, pad) == 0xffu ? 1ull : 0ull;
+    n = wg_sum_u64(n, red);
+    if (threadIdx.x == 0) p.chunk_out[c] = (b1 - b0) + n;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_scan2_kernel(Params p) {
+    __shared__ u64 tot[kThreads];
+    const int tid = threadIdx.x, nt = p.nt, nc = p.nc;
+    wg_prefix_u64(p.chunk_out, p.chunk_out, nc, tot);
+    for (int t = tid; t <= nt; t += kThreads) p.tile_offs[t] = p.chunk_out[t < nt ? p.tiles[t].first_chunk : (u32)nc];
+    if (tid == 0 && p.total) *p.total = p.chunk_out[nc];
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_stuff_kernel(Params p) {
+    __shared__ u32 wsum[kWaves];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const u64 b0 = p.chunk_b0[c], b1 = p.chunk_b1[c];
+    const u32 pad = p.chunk_pad[c];
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(p.ubuf);
+    u64 o = p.chunk_out[c];
+    for (u64 s0 = b0; s0 < b1; s0 += (u64)kThreads * kStuffPerLane) {
+        const u64 i0 = s0 + (u64)tid * kStuffPerLane;
+        u32 v[kStuffPerLane];
+        u32 n = 0u, ff = 0u;
+#pragma unroll
+        for (int k = 0; k < kStuffPerLane; ++k) {
+            const bool in = i0 + k < b1;
+            v[k] = in ? ubyte(u, i0 + k, b1, pad) : 0u;
+            n += in ? 1u : 0u;
+            ff += v[k] == 0xffu ? 1u : 0u;
+        }
+        u32 step_total;
+        const u32 before = wg_scan_u32(n + ff, wsum, &step_total);
+        unsigned char* dst = p.out + o + before;
+#pragma unroll
+        for (int k = 0; k < kStuffPerLane; ++k) {
+            if ((u32)k < n) {
+                *dst++ = (unsigned char)v[k];
+                if (v[k] == 0xffu) *dst++ = 0;
+            }
+        }
+        o += step_total;
+    }
+}
+
+// ---- the host's plan -------------------------------------------------------------------------------------------------------------
+static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
+
+static inline int default_mcus(int sub420) { return sub420 ? 128 : 256; }     // 768 blocks per chunk
+
+// The table as the device reads it, one block of memory: [Consts][tiles TileT nt][chunks ChunkT nc].
+struct Plan {
+    int rc;                       // CIAOSR_OK, or why the rects cannot be coded
+    int nt, nc;
+    u64 blocks;
+    size_t capacity;              // the stuffed worst case: 2 x 208 bytes per block
+    size_t ubytes;                // the unstuffed worst case, every tile rounded up to 4 bytes
+    size_t o_tiles, o_chunks, table_bytes;
+};
+// `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
+static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcus_arg, int H, int W, std::vector<unsigned char>* table) {
+    Plan t{};
+    t.rc = CIAOSR_ERR_BAD_ARG;
+    if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || (sub420 != 0 && sub420 != 1)) return t;
+    const int per = mcus_arg > 0 ? mcus_arg : default_mcus(sub420);
+    const int bpm = sub420 ? 6 : 3, side = sub420 ? 16 : 8;
+    u64 nc = 0, blocks = 0;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
+        if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
+        if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return t;
+        const u64 nmcu = (u64)ceil_div(h, side) * (u64)ceil_div(w, side);
+        nc += (nmcu + per - 1) / per;
+        blocks += nmcu * bpm;
+    }
+    if (nc > (u64)INT_MAX / 2 || blocks > (u64)INT_MAX) {
+        t.rc = CIAOSR_ERR_UNSUPPORTED;
+        return t;
+    }
+    t.rc = CIAOSR_OK;
+    t.nt = n_tiles;
+    t.nc = (int)nc;
+    t.blocks = blocks;
+    t.capacity = (size_t)(2 * kBlockBytes * blocks);
+    t.ubytes = (size_t)(kBlockBytes * blocks) + 4 * (size_t)n_tiles;
+    t.o_tiles = sizeof(Consts);
+    t.o_chunks = t.o_tiles + sizeof(TileT) * (size_t)n_tiles;
+    t.table_bytes = t.o_chunks + sizeof(ChunkT) * (size_t)nc;
+    if (!table) return t;
+    table->resize(t.table_bytes);
+    make_consts(quality, reinterpret_cast<Consts*>(table->data()));
+    TileT* tiles = reinterpret_cast<TileT*>(table->data() + t.o_tiles);
+    ChunkT* chunks = reinterpret_cast<ChunkT*>(table->data() + t.o_chunks);
+    u32 c = 0, blk = 0;
+    for (int k = 0; k < n_tiles; ++k) {
+        const int h = rects[4 * k + 2], w = rects[4 * k + 3];
+        const int mx = ceil_div(w, side), nmcu = mx * ceil_div(h, side);
+        tiles[k] = TileT{rects[4 * k], rects[4 * k + 1], h, w, mx, nmcu, c, blk};
+        for (int m = 0; m < nmcu; m += per, ++c) chunks[c] = ChunkT{k, m, m + per < nmcu ? m + per : nmcu, 0};
+        blk += (u32)nmcu * (u32)bpm;
+    }
+    return t;
+}
+
+struct Work {
+    unsigned char* table;
+    short* coef;
+    u32 *block_bits, *chunk_pad, *ubuf;
+    u64 *chunk_bits, *chunk_sum, *chunk_bitoff, *chunk_b0, *chunk_b1, *chunk_out, *tile_ubase, *utotal, *offs2;
+};
+static inline bool carve(void* ws, size_t bytes, const Plan& t, Work* w, size_t* used) {
+    Arena a(ws, bytes);
+    const size_t nc = (size_t)t.nc;
+    w->table = a.take<unsigned char>(t.table_bytes);
+    w->coef = a.take<short>(64 * (size_t)t.blocks);
+    w->block_bits = a.take<u32>((size_t)t.blocks);
+    w->chunk_pad = a.take<u32>(nc);
+    w->chunk_bits = a.take<u64>(nc);
+    w->chunk_sum = a.take<u64>(nc + 1);
+    w->chunk_bitoff = a.take<u64>(nc);
+    w->chunk_b0 = a.take<u64>(nc);
+    w->chunk_b1 = a.take<u64>(nc);
+    w->chunk_out = a.take<u64>(nc + 1);
+    w->tile_ubase = a.take<u64>((size_t)t.nt);
+    w->utotal = a.take<u64>(1);
+    w->offs2 = a.take<u64>(2);
+    w->ubuf = a.take<u32>((t.ubytes + 3) / 4);
+    if (used) *used = a.off;
+    return a.ok;
+}
+static inline size_t work_bytes(const Plan& t) {
+    Work w;
+    size_t used = 0;
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    carve(origin, ~(size_t)0, t, &w, &used);
+    return used;
+}
+
+template <typename K>
+static int launch(const char* tag, K kernel, int grid, const Params& p, hipStream_t s) {
+    ProfScope prof(tag, s);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, p);
+    return launch_status(tag);
+}
+
+// every check that the host can make comes before the first launch
+static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int sub420,
+                  int mcus, unsigned char* out, size_t out_capacity, u64* tile_offs, u64* total, void* workspace, size_t workspace_bytes,
+                  hipStream_t s) {
+    std::vector<unsigned char> table;
+    const Plan t = plan(rects, n_tiles, quality, sub420, mcus, H, W, &table);
+    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image; quality; subsampling
+    if (t.rc != CIAOSR_OK) return t.rc;
+    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    if (workspace_bytes < work_bytes(t) || !carve(workspace, workspace_bytes, t, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    // from pageable memory: the copy has left `table` when the call returns
+    if (hipMemcpyAsync(w.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    Params p{};
+    p.src = src;
+    p.pitch = pitch;
+    p.bgr = bgr;
+    p.sub420 = sub420;
+    p.nt = t.nt;
+    p.nc = t.nc;
+    p.consts = reinterpret_cast<const Consts*>(w.table);
+    p.tiles = reinterpret_cast<const TileT*>(w.table + t.o_tiles);
+    p.chunks = reinterpret_cast<const ChunkT*>(w.table + t.o_chunks);
+    p.coef = w.coef;
+    p.block_bits = w.block_bits;
+    p.chunk_bits = w.chunk_bits;
+    p.chunk_sum = w.chunk_sum;
+    p.chunk_bitoff = w.chunk_bitoff;
+    p.chunk_b0 = w.chunk_b0;
+    p.chunk_b1 = w.chunk_b1;
+    p.chunk_pad = w.chunk_pad;
+    p.chunk_out = w.chunk_out;
+    p.tile_ubase = w.tile_ubase;
+    p.utotal = w.utotal;
+    p.ubuf = w.ubuf;
+    p.out = out;
+    p.tile_offs = tile_offs ? tile_offs : w.offs2;
+    p.total = total;
+    int rc;
+    if ((rc = launch("jpeg_coef", jpeg_coef_kernel, t.nc, p, s))) return rc;
+    if ((rc = launch("jpeg_count", jpeg_count_kernel, t.nc, p, s))) return rc;
+    if ((rc = launch("jpeg_scan", jpeg_scan_kernel, 1, p, s))) return rc;
+    const u64 zero_groups = (t.ubytes / 4 + kThreads - 1) / kThreads;
+    if ((rc = launch("jpeg_zero", jpeg_zero_kernel, (int)(zero_groups < (u64)kZeroGroups ? zero_groups : (u64)kZeroGroups), p, s))) return rc;
+    if ((rc = launch("jpeg_pack", jpeg_pack_kernel, t.nc, p, s))) return rc;
+    if ((rc = launch("jpeg_ffcount", jpeg_ffcount_kernel, t.nc, p, s))) return rc;
+    if ((rc = launch("jpeg_scan2", jpeg_scan2_kernel, 1, p, s))) return rc;
+    return launch("jpeg_stuff", jpeg_stuff_kernel, t.nc, p, s);
+}
+
+}  // namespace jpeg
+}  // namespace ciaosr
+
+using namespace ciaosr;
+using namespace ciaosr::jpeg;
+
+// the ABI's subsampling code -> 0 (4:4:4), 1 (4:2:0), -1 (unknown)
+static inline int sub_of(int subsampling) { return subsampling == CIAOSR_JPEG_444 ? 0 : (subsampling == CIAOSR_JPEG_420 ? 1 : -1); }
+
+extern "C" size_t ciaosr_jpeg_tiles_workspace_bytes(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
+    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? work_bytes(t) : 0;
+}
+
+extern "C" size_t ciaosr_jpeg_tiles_capacity_bytes(const int* rects, int n_tiles, int subsampling) {
+    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), 0, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? t.capacity : 0;
+}
+
+extern "C" size_t ciaosr_jpeg_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk) {
+    const int rect[4] = {0, 0, H, W};
+    return ciaosr_jpeg_tiles_workspace_bytes(rect, 1, subsampling, mcus_per_chunk);
+}
+
+extern "C" size_t ciaosr_jpeg_capacity_bytes(int H, int W, int subsampling) {
+    const int rect[4] = {0, 0, H, W};
+    return ciaosr_jpeg_tiles_capacity_bytes(rect, 1, subsampling);
+}
+
+extern "C" int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                           int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
+                                           unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
+    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, tile_offs, nullptr,
+                  workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
+                                     int mcus_per_chunk, unsigned char* out, size_t out_capacity, unsigned long long* total_bytes,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
+    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    const int rect[4] = {0, 0, H, W};
+    return encode(src, pitch, H, W, bgr, rect, 1, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, nullptr, total_bytes, workspace,
+                  workspace_bytes, (hipStream_t)stream);
+}

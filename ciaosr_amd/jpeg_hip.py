@@ -1,0 +1,176 @@
+"""Baseline JPEG files written from uint8 images on the MI355X (csrc/jpeg_u8.hip), byte for byte Pillow's.
+
+The device runs libjpeg's integer pipeline as `PIL.Image.save(format='JPEG', quality=q, subsampling=0 | 2)` drives it -- colour
+conversion, 4:2:0 box filter, "islow" DCT, quantisation, the Annex K Huffman codes, 0xFF stuffing, padding -- and returns the
+entropy-coded scan.  The host only wraps it: `header(h, w, quality, subsampling)` in front (SOI, APP0, two DQT, SOF0, four DHT, the
+SOS header; it depends on nothing else), EOI behind.  DESIGN 4.1i-d holds the contract.  Two copies synchronise per call: the sizes,
+then the bytes.  There is no CPU fallback: a host array raises.  `encode_jpeg_tiles` codes many crops of one image (the tiles of a
+pyramid level, pyramid.py) in one set of launches; each file is byte for byte the single call's on that crop.
+"""
+import ctypes as C
+import os
+import struct
+
+import torch
+
+from . import _lib, hip_ops
+from ._lib import CiaoSRHipError
+from .metrics_hip import _check_image
+from .png_hip import MAX_SIDE, ORDERS, check_rects
+
+SUBSAMPLINGS = {'444': 0, '420': 2}        # CIAOSR_JPEG_444 / CIAOSR_JPEG_420: Pillow's `subsampling=` numbers
+EOI = b'\xff\xd9'
+
+# Annex K base quantisation tables, natural (row-major) order
+BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+             18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
+             103, 99)
+BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99) + (99,) * 36
+# natural index of the k-th coefficient in zigzag order
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
+          57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# Annex K "typical" Huffman tables as a DHT segment holds them, in the file's order: (class << 4 | id, code counts per length 1..16,
+# symbols in code order)
+HUFFMAN = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91,
+      0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a,
+      0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53,
+      0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79,
+      0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5,
+      0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9,
+      0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2,
+      0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14,
+      0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17,
+      0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a,
+      0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78,
+      0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7,
+      0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2,
+      0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+)
+
+
+def check_params(quality, subsampling):
+    """(quality as int, the ABI's subsampling code); ValueError otherwise."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f'quality is a whole number in 1..100, got {quality!r}')
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be '444' or '420', got {subsampling!r}")
+    return int(quality), SUBSAMPLINGS[subsampling]
+
+
+def quant_tables(quality):
+    """(luma, chroma): 64 values each, natural order -- libjpeg's quality scaling of the Annex K tables."""
+    s = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(tuple(min(max((b * s + 50) // 100, 1), 255) for b in base) for base in (BASE_LUMA, BASE_CHROMA))
+
+
+def header(h, w, quality, subsampling):
+    """The file from SOI up to and including the SOS header, as Pillow writes it for an h x w RGB image."""
+    quality, _ = check_params(quality, subsampling)
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
+    parts = [b'\xff\xd8', b'\xff\xe0', struct.pack('>H5sBBBHHBB', 16, b'JFIF\0', 1, 1, 0, 1, 1, 0, 0)]
+    for k, q in enumerate(quant_tables(quality)):
+        parts += [b'\xff\xdb', struct.pack('>HB', 67, k), bytes(q[i] for i in ZIGZAG)]
+    parts += [b'\xff\xc0', struct.pack('>HBHHB', 17, 8, h, w, 3), bytes((1, 0x22 if subsampling == '420' else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))]
+    for tc_th, bits, vals in HUFFMAN:
+        parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), tc_th), bytes(bits), bytes(vals)]
+    parts += [b'\xff\xda', struct.pack('>HB', 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3f, 0))]
+    return b''.join(parts)
+
+
+def _check(img, quality, subsampling, order, mcus_per_chunk, what):
+    """The argument checks of every entry point, before any device work -> (h, w, quality, subsampling code, mcus_per_chunk)."""
+    quality, sub = check_params(quality, subsampling)
+    if order not in ORDERS:
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    if int(mcus_per_chunk) != mcus_per_chunk or mcus_per_chunk < 0:
+        raise ValueError(f'mcus_per_chunk={mcus_per_chunk!r}')
+    _check_image(img)
+    h, w = img.shape[0], img.shape[1]
+    if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
+        raise CiaoSRHipError(f'{what}: {h}x{w} is outside 1..{MAX_SIDE} per side')
+    return h, w, quality, sub, int(mcus_per_chunk)
+
+
+def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None):
+    """ciaosr_jpeg_encode_tiles_u8 on the current stream, no synchronisation -> (scans uint8 [capacity], offsets int64 [n + 1]) on the
+    device: crop k's entropy-coded scan is scans[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps.  `out`, `capacity`: a buffer of
+    the caller's and the size to declare for it (default: `ciaosr_jpeg_tiles_capacity_bytes`, the worst case)."""
+    h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
+    rects = check_rects(rects, h, w)
+    n = len(rects)
+    dev = img.device
+    lib = _lib.load()
+    host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
+    cap = lib.ciaosr_jpeg_tiles_capacity_bytes(host_rects, n, sub)
+    nbytes = lib.ciaosr_jpeg_tiles_workspace_bytes(host_rects, n, sub, mcus)
+    if cap == 0 or nbytes == 0:
+        raise CiaoSRHipError(f'encode_jpeg_tiles: unsupported geometry ({n} rects, mcus_per_chunk={mcus})')
+    ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _lib.call('ciaosr_jpeg_encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, quality, sub,
+              mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
+              C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    return out, offs
+
+
+def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+    """The entropy-coded scans of many crops (y0, x0, h, w) of one device image, from ONE set of launches -> list of bytes; scan k is
+    byte for byte `encode_scan(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call: the offsets table, then the bytes."""
+    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk)
+    o = offs.cpu().tolist()                                 # copy 1: the offsets
+    raw = memoryview(out[:o[-1]].cpu().numpy())             # copy 2: the scans
+    return [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
+
+
+def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+    """The entropy-coded scan of the image, stuffed and padded (the file between the SOS header and EOI), made on the device -> bytes.
+    Synchronises twice: size, then bytes."""
+    h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')
+    dev = img.device
+    lib = _lib.load()
+    cap = lib.ciaosr_jpeg_capacity_bytes(h, w, sub)
+    nbytes = lib.ciaosr_jpeg_workspace_bytes(h, w, sub, mcus)
+    if cap == 0 or nbytes == 0:
+        raise CiaoSRHipError(f'encode_jpeg: unsupported geometry {h}x{w}, mcus_per_chunk={mcus}')
+    ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.call('ciaosr_jpeg_encode_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], quality, sub, mcus,
+              hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(total), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    n = int(total.item())                                   # copy 1: the size
+    return out[:n].cpu().numpy().tobytes()                  # copy 2: the scan
+
+
+def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+    """JPEG file (bytes) of a uint8 [H, W, 3] device image, byte for byte `PIL.Image.save(format='JPEG', quality=quality,
+    subsampling=0 or 2)` of the same pixels; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
+    larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it."""
+    scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
+    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling) + scan + EOI
+
+
+def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+    """JPEG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] device image, coded together: file k
+    is byte for byte `encode_jpeg(img[y0:y0 + h, x0:x0 + w], ...)`.  The rects may overlap.  A bad rect, quality or subsampling is a
+    ValueError before any device work; two synchronising copies per call."""
+    rects = list(rects)
+    scans = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
+    return [header(int(r[2]), int(r[3]), quality, subsampling) + s + EOI for r, s in zip(rects, scans)]
+
+
+def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr'):
+    """`imageio.imwrite` as JPEG for an image that is already on the device: encode there, write the file here."""
+    data = encode_jpeg(img_u8_hwc, quality, subsampling, order)
+    os.makedirs(os.path.dirname(os.path.abspath(path)) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)

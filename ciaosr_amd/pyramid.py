@@ -1,7 +1,8 @@
 """Deep Zoom tile pyramids (`<name>.dzi` + `<name>_files/<level>/<col>_<row>.png`, as OpenSeadragon and libvips read them) of an encoded
 scene.  The plan and the manifest are pure host code; `write_dzi` renders every level with `CiaoSR.render_pyramid` -- the levels at or
 above the LR size are the model's own answer at that size, all from one walk over the tile scenes -- and codes each level's tiles with
-ONE `png_hip.encode_png_tiles` call: two synchronising copies per level, whatever its number of tiles.
+ONE `png_hip.encode_png_tiles` call: two synchronising copies per level, whatever its number of tiles.  `fmt='jpg'` writes
+`<col>_<row>.jpg` tiles through one `jpeg_hip.encode_jpeg_tiles` call per level instead, and `Format="jpg"` in the manifest.
 
 Deep Zoom's rules: Lmax = ceil(log2(max(W, H))), levels 0..Lmax; level L is max(1, ceil(W / 2^(Lmax - L))) wide and as high by the same
 rule; on a level, column c spans [c T - (O if c > 0 else 0), min((c + 1) T + O, Wl)) for the tile size T and the overlap O, rows alike,
@@ -50,36 +51,57 @@ def dzi_plan(height, width, tile_size=254, overlap=1):
     return plan
 
 
-def dzi_manifest(height, width, tile_size=254, overlap=1):
-    """The `.dzi` file's XML for a height x width top level."""
+FORMATS = ('png', 'jpg')
+
+
+def _check_format(fmt):
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt must be 'png' or 'jpg', got {fmt!r}")
+    return fmt
+
+
+def dzi_manifest(height, width, tile_size=254, overlap=1, fmt='png'):
+    """The `.dzi` file's XML for a height x width top level whose tiles are `fmt` files."""
     tile_size, overlap = _check_tiling(tile_size, overlap)
+    _check_format(fmt)
     if int(height) < 1 or int(width) < 1:
         raise ValueError(f'empty image {height} x {width}')
-    return (f'<?xml version="1.0" encoding="UTF-8"?><Image xmlns="{DZI_NS}" Format="png" Overlap="{overlap}" TileSize="{tile_size}">'
+    return (f'<?xml version="1.0" encoding="UTF-8"?><Image xmlns="{DZI_NS}" Format="{fmt}" Overlap="{overlap}" TileSize="{tile_size}">'
             f'<Size Width="{int(width)}" Height="{int(height)}"/></Image>')
 
 
-def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr'):
+def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90, subsampling='444'):
     """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
-    returns them): one `encode_png_tiles` call per level.  -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
-    from .png_hip import encode_png_tiles
+    returns them): one `encode_png_tiles` call per level, or for `fmt='jpg'` one `encode_jpeg_tiles` call with `quality` and
+    `subsampling`.  -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
+    if _check_format(fmt) == 'jpg':
+        from .jpeg_hip import check_params, encode_jpeg_tiles
+        check_params(quality, subsampling)
+
+        def encode(img, rects):
+            return encode_jpeg_tiles(img, rects, quality=quality, subsampling=subsampling, order=order)
+    else:
+        from .png_hip import encode_png_tiles
+
+        def encode(img, rects):
+            return encode_png_tiles(img, rects, order=order)
     top = levels[-1]
     plan = dzi_plan(top.shape[0], top.shape[1], tile_size, overlap)
     if [(lv['height'], lv['width']) for lv in plan] != [(im.shape[0], im.shape[1]) for im in levels]:
         raise ValueError(f'the images are not the levels of a {top.shape[0]} x {top.shape[1]} pyramid')
-    manifest = dzi_manifest(top.shape[0], top.shape[1], tile_size, overlap).encode()
+    manifest = dzi_manifest(top.shape[0], top.shape[1], tile_size, overlap, fmt).encode()
     os.makedirs(out_dir, exist_ok=True)
     files, nbytes, t_enc, t_write = 1, len(manifest), 0.0, 0.0
     with open(os.path.join(out_dir, f'{name}.dzi'), 'wb') as f:
         f.write(manifest)
     for lv, img in zip(plan, levels):
         t0 = time.perf_counter()
-        pngs = encode_png_tiles(img, [t[2:] for t in lv['tiles']], order=order)
+        pngs = encode(img, [t[2:] for t in lv['tiles']])
         t1 = time.perf_counter()
         folder = os.path.join(out_dir, f'{name}_files', str(lv['level']))
         os.makedirs(folder, exist_ok=True)
         for (col, row, *_), data in zip(lv['tiles'], pngs):
-            with open(os.path.join(folder, f'{col}_{row}.png'), 'wb') as f:
+            with open(os.path.join(folder, f'{col}_{row}.{fmt}'), 'wb') as f:
                 f.write(data)
             nbytes += len(data)
         files += len(pngs)
@@ -88,17 +110,22 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr'):
     return dict(files=files, bytes=nbytes, encode_s=t_enc, write_s=t_write)
 
 
-def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, overlap=1, order='bgr'):
+def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90,
+              subsampling='444'):
     """`<out_dir>/<name>.dzi` and `<out_dir>/<name>_files/<level>/<col>_<row>.png` of the `size` / `scale` render of `enc` (an
-    `encode` result of `model`).  `order`: the byte order of the rendered images, 'bgr' as `render_pyramid` makes them.
+    `encode` result of `model`).  `order`: the byte order of the rendered images, 'bgr' as `render_pyramid` makes them.  `fmt='jpg'`:
+    `.jpg` tiles at `quality` (1..100) and `subsampling` ('444' or '420'), byte for byte Pillow's files of the same pixels.
     -> dict: levels [(H_l, W_l)], model_levels (the levels rendered by the model; the ones below are Pillow-exact bicubic resizes of
     the smallest of them), files, bytes, and the seconds spent in render_s (to the last launch, not synchronised), encode_s, write_s."""
     _check_tiling(tile_size, overlap)
+    if _check_format(fmt) == 'jpg':
+        from .jpeg_hip import check_params
+        check_params(quality, subsampling)
     t0 = time.perf_counter()
     levels = model.render_pyramid(enc, size=size, scale=scale)
     render_s = time.perf_counter() - t0
     h, w = enc.x.shape[-2:]
     sizes = [(im.shape[0], im.shape[1]) for im in levels]
-    res = write_levels(levels, out_dir, name, tile_size, overlap, order)
+    res = write_levels(levels, out_dir, name, tile_size, overlap, order, fmt, quality, subsampling)
     res.update(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w], render_s=render_s)
     return res

@@ -820,6 +820,43 @@ int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, in
                                int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Baseline JPEG encoding of 8-bit images (ciaosr_amd/jpeg_hip.py; DESIGN 4.1i-d holds the format contract) ----------------------
+ * The device makes the entropy-coded data of ONE interleaved scan of a baseline file -- libjpeg's integer pipeline as Pillow drives
+ * it: 16-bit fixed-point RGB -> YCbCr, 4:4:4 or 4:2:0 with the h2v2 box filter, the "islow" forward DCT, the Annex K tables scaled by
+ * `quality` (1..100), the Annex K Huffman codes, no restart markers -- with a 0x00 after every 0xFF and the last byte padded with
+ * 1-bits.  The host wraps it: SOI, APP0, two DQT, SOF0, four DHT and the SOS header in front (they depend on h, w, quality and
+ * subsampling only), EOI behind.  The file is then byte for byte PIL.Image.save(format='JPEG', quality=, subsampling=)'s.
+ * src[y * pitch + 3 x + c], pitch >= 3 W (a crop view is fine); bgr as for the PNG entry points; H, W <= 65535.
+ * mcus_per_chunk: MCUs (8 x 8 pixels in 4:4:4, 16 x 16 in 4:2:0) that one workgroup codes; 0 = the library's choice (768 blocks).
+ * The bytes do not depend on it, nor on the stream, nor -- for tiles -- on what else is in the list.  All arithmetic is integer.
+ * Sizes: a block takes at most 208 bytes before stuffing (64 x (16-bit code + 10 bits)) and twice that after;
+ * ciaosr_jpeg_capacity_bytes returns that WORST CASE, 416 bytes per block of the scan (dummy blocks included), so that nothing can
+ * ever be written at or beyond out_capacity; a shorter out, or a workspace below ciaosr_jpeg_workspace_bytes (int16 coefficients,
+ * 4 bytes per block, the unstuffed stream's worst case, 52 bytes per chunk, the table: 16 per chunk, 32 per tile) is CIAOSR_ERR_WORKSPACE before any launch.
+ * quality outside 1..100, a subsampling other than the two below, a null pointer, an empty rect or one that leaves the image:
+ * CIAOSR_ERR_BAD_ARG before any launch.  The size functions return 0 for what they cannot take.
+ * *total_bytes (DEVICE, 8-byte aligned) = the scan's size; the host reads it, then the bytes: two synchronising copies per call.
+ * Eight launches per call whatever the number of tiles: coefficients, code lengths, a scan, zeroing of the unstuffed buffer, pack,
+ * 0xFF count, a scan, stuffing.  The table of constants, tiles and chunks reaches the device by a copy on `stream` from pageable
+ * memory.  The workspace is 8-byte aligned; nothing is allocated. */
+#define CIAOSR_JPEG_444 0   /* Pillow's subsampling=0 */
+#define CIAOSR_JPEG_420 2   /* Pillow's subsampling=2 */
+size_t ciaosr_jpeg_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_capacity_bytes(int H, int W, int subsampling);
+int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
+                          int mcus_per_chunk, unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* Many crops of one image in one set of launches.  rects: HOST array [n_tiles][4] = y0, x0, h, w as for ciaosr_png_encode_tiles_u8.
+ * A crop is an image of its own: its MCU grid starts at its origin, its edges repeat ITS last column and row whatever the image holds
+ * beyond them, its DC predictors start at 0.  Tile t's scan is out[tile_offs[t] : tile_offs[t + 1]], byte for byte what
+ * ciaosr_jpeg_encode_u8 gives for the pitched crop; tile_offs (DEVICE, [n_tiles + 1], 8-byte aligned): tile_offs[0] = 0, the scans lie
+ * back to back, tile_offs[n_tiles] is the total.  The host reads tile_offs, then the bytes. */
+size_t ciaosr_jpeg_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int subsampling);
+int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
+                                unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

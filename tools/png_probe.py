@@ -18,6 +18,15 @@ times the tiles of a pyramid's top level (ciaosr_amd/pyramid.py) and writes prof
 Wall time runs from the device image (after a synchronize) to the bytes on the host; the legs alternate; kernel time is the sum over
 `hip_ops.profile` of a round of its own.  The files of (a) and (b) are compared byte for byte.  `--dzi` adds one full pyramid of the
 bench output (config 001, LR 1356 x 2040, x4) from a ready encode, split into render, encode and file writing.
+
+    python tools/png_probe.py --leg jpeg [--sizes 5424x8160 768x768] [--quality 90] [--tile 254] [--overlap 1] [--out FILE]
+
+times the JPEG encoder (ciaosr_amd/jpeg_hip.py) and writes profiles/jpeg_gpu.txt.  Per image and subsampling ('444', '420'):
+(a) `encode_jpeg` on the device;  (b) the device-to-host copy followed by `PIL.Image.save` as JPEG into memory;  (c) `encode_png` on the
+device.  For images larger than one tile also the top-level tiles: (d) one `encode_jpeg_tiles` call against (e) one `encode_jpeg` per
+tile.  Wall time runs from the device image (after a synchronize) to the bytes on the host; the legs alternate in one process; kernel
+time by tag comes from `hip_ops.profile` in a round of its own.  The files of (a) and (b), and of (d) and (e), are compared byte for
+byte, and the sizes of the JPEG, device PNG and Pillow PNG files are recorded.
 """
 import json
 import subprocess
@@ -210,15 +219,85 @@ def dzi_leg(args, say):
         f'({enc.cache.builds} scene builds), encode {res["encode_s"]:.3f} s, file writing {res["write_s"]:.3f} s')
 
 
+def jpeg_leg(args, say):
+    import io
+    from PIL import Image
+    from ciaosr_amd import hip_ops
+    from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
+    from ciaosr_amd.png_hip import encode_png
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def pil_file(img, fmt, **kw):
+        bio = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(img.cpu().numpy()[:, :, ::-1])).save(bio, format=fmt, **kw)
+        return bio.getvalue()
+
+    def kernels(fn):
+        with hip_ops.profile():
+            fn()
+        prof = hip_ops.profile.results()
+        return (f'{sum(v["total_ms"] for v in prof.values()):.3f} ms in {sum(v["launches"] for v in prof.values())} launches: '
+                + ', '.join(f'{k} {v["total_ms"]:.3f}' for k, v in sorted(prof.items())))
+
+    def run(legs):
+        times = {k: [] for k in legs}
+        for r in range(args.warmup + args.rounds):
+            for name, fn in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                if r >= args.warmup:
+                    times[name].append(time.perf_counter() - t0)
+        return times
+
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        rects = top_rects(h, w, args.tile, args.overlap)
+        for content in args.contents:
+            img = make_image(h, w, content, dev)
+            torch.cuda.synchronize()
+            png_dev, png_pil = len(encode_png(img)), len(pil_file(img, 'PNG'))
+            for sub in ('444', '420'):
+                legs = {'a': lambda: encode_jpeg(img, args.quality, sub), 'b': lambda: pil_file(img, 'JPEG', quality=args.quality, subsampling=SUBSAMPLINGS[sub]),
+                        'c': lambda: encode_png(img)}
+                times = run(legs)
+                mine, pil = legs['a'](), legs['b']()
+                say(f'{h} x {w} {content}, quality {args.quality}, {sub}: device file is Pillow\'s byte for byte: {mine == pil}; bytes JPEG {len(mine)}, '
+                    f'device PNG {png_dev}, Pillow PNG {png_pil}')
+                say(f'  (a) encode_jpeg on the device      wall s: {stats(times["a"])}')
+                say(f'  (b) copy to the host + PIL JPEG    wall s: {stats(times["b"])}')
+                say(f'  (c) encode_png on the device       wall s: {stats(times["c"])}')
+                gap = statistics.mean(times['b']) - statistics.mean(times['a'])
+                spread = max(max(times[k]) - min(times[k]) for k in ('a', 'b'))
+                say(f'  (b) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                    f'{"device encoder faster beyond the spread" if gap > spread else ("host encoder faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                    f'ratio (b) / (a) {statistics.mean(times["b"]) / statistics.mean(times["a"]):.2f}x')
+                say(f'  (a) kernels: {kernels(legs["a"])}')
+                say(f'  (c) kernels: {kernels(legs["c"])}')
+                if len(rects) > 1:
+                    legs = {'d': lambda: encode_jpeg_tiles(img, rects, args.quality, sub),
+                            'e': lambda: [encode_jpeg(img[y0:y0 + hh, x0:x0 + ww], args.quality, sub) for y0, x0, hh, ww in rects]}
+                    times = run(legs)
+                    one, each = legs['d'](), legs['e']()
+                    say(f'  top level at {args.tile}+{args.overlap}: {len(rects)} tiles, {sum(len(f) for f in one)} bytes of files; (d) and (e) byte for byte '
+                        f'identical: {one == each}')
+                    say(f'  (d) encode_jpeg_tiles, one call    wall s: {stats(times["d"])}')
+                    say(f'  (e) encode_jpeg per tile           wall s: {stats(times["e"])}')
+                    say(f'  ratio (e) / (d) {statistics.mean(times["e"]) / statistics.mean(times["d"]):.1f}x')
+                    say(f'  (d) kernels: {kernels(legs["d"])}')
+            del img
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
     p.add_argument('--dzi', action='store_true', help='tiles: also one full write_dzi of the bench output')
     p.add_argument('--tile', type=int, default=254)
     p.add_argument('--overlap', type=int, default=1)
+    p.add_argument('--quality', type=int, default=90, help='jpeg: the quality of every JPEG file')
     p.add_argument('--sizes', nargs='+', default=None)
     p.add_argument('--contents', nargs='+', default=['smooth', 'noisy'], choices=['smooth', 'noisy'])
     p.add_argument('--warmup', type=int, default=2)
@@ -231,8 +310,9 @@ def main(argv=None):
     if args.worker:
         return serve()
     tiles = args.leg == 'tiles'
+    jpeg = args.leg == 'jpeg'
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['5424x8160', '768x768'])
-    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_gpu.txt')
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -243,12 +323,14 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    say(f'tools/png_probe.py{" --leg tiles" if tiles else ""} --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
+    say(f'tools/png_probe.py{" --leg " + args.leg if tiles or jpeg else ""} --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
         f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, {os.cpu_count()} host CPUs visible')
     if tiles:
         tiles_leg(args, say)
+    if jpeg:
+        jpeg_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
-        for size in ([] if tiles else args.sizes):
+        for size in ([] if tiles or jpeg else args.sizes):
             h, w = (int(v) for v in size.split('x'))
             for content in args.contents:
                 img = make_image(h, w, content, dev)

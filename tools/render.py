@@ -22,6 +22,9 @@ queried in 4 x 2 blocks of output pixels, which keeps the head on its chained ke
 name>.dzi and DIR/<image name>_files/<level>/<col>_<row>.png, every level at or above the LR size rendered by the model from the same
 encode, each level's tiles PNG-encoded on the device in one call (always the device encoder, with or without `--gpu-png`); alone or next
 to --scale / --view outputs, which it does not change.  `--max-scale` then defaults to cover SCALE as well.
+`--jpeg Q [--jpeg-subsampling 444|420]` writes baseline JPEG files of quality Q instead: DIR/<image name>_x<S>.jpg, _view<k>.jpg and, with
+--dzi, `<col>_<row>.jpg` tiles under a manifest that says Format="jpg".  Every output is rendered as a uint8 image on the device (as for
+`--gpu-png`) and coded there (ciaosr_amd/jpeg_hip.py); the files are byte for byte what Pillow saves for the same pixels.
 """
 import argparse
 import os
@@ -48,6 +51,9 @@ def parse_args(argv=None):
                    help='test_cfg.view_blocks: the 16-bit modes select a cut view\'s members in 4 x 2 blocks of output pixels (default off)')
     p.add_argument('--gpu-png', action='store_true',
                    help='test_cfg.gpu_png: outputs are quantised and PNG-encoded on the GPU; no fp32 image crosses to the host (default off)')
+    p.add_argument('--jpeg', type=int, default=None, metavar='Q',
+                   help='write JPEG files of quality Q (1..100), coded on the GPU, instead of PNG files (default: PNG)')
+    p.add_argument('--jpeg-subsampling', choices=['444', '420'], default='444', help='chroma subsampling of --jpeg (default 444)')
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
@@ -61,7 +67,16 @@ def parse_args(argv=None):
         p.error('give one --size H W per --view, or a single one for all views')
     if args.size and not args.view:
         p.error('--size belongs to --view')
+    if args.jpeg is not None and not 1 <= args.jpeg <= 100:
+        p.error('--jpeg takes a quality in 1..100')
     return args
+
+
+def output_format(args):
+    """What the flags ask the writers for: dict(fmt, ext) and, for JPEG, quality and subsampling."""
+    if args.jpeg is None:
+        return dict(fmt='png', ext='.png')
+    return dict(fmt='jpg', ext='.jpg', quality=args.jpeg, subsampling=args.jpeg_subsampling)
 
 
 def scale_tag(s):
@@ -100,16 +115,24 @@ def main(argv=None):
     enc = model.encode(lq, max_scale=args.max_scale or max(wanted))
     name = os.path.splitext(os.path.basename(args.image))[0]
     from ciaosr_amd.scene import Grid, View, view_matrix
+    form = output_format(args)
+    coding = {k: form[k] for k in ('quality', 'subsampling') if k in form}
+    dzi_format = dict(fmt='jpg', **coding) if form['fmt'] == 'jpg' else {}           # without --jpeg write_dzi is called as before
     targets = [Grid(scale=s, window=args.window) for s in args.scale]
-    paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}.png') for s in args.scale]
+    paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}{form["ext"]}') for s in args.scale]
     for k, (cy, cx, zoom, angle) in enumerate(args.view):
         size = args.size[k if len(args.size) > 1 else 0]
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
-        paths.append(os.path.join(args.out, f'{name}_view{k}.png'))
+        paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
-    outs = model.render_many(enc, targets, as_u8=gpu_png) if targets else []         # one walk over the tile scenes for every output
+    as_u8 = gpu_png or form['fmt'] == 'jpg'
+    outs = model.render_many(enc, targets, as_u8=as_u8) if targets else []           # one walk over the tile scenes for every output
     for path, out in zip(paths, outs):
-        if gpu_png:
+        if form['fmt'] == 'jpg':
+            from ciaosr_amd.jpeg_hip import imwrite_gpu_jpeg
+            imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR on the device
+            print(f'{path}: {out.shape[0]} x {out.shape[1]}')
+        elif gpu_png:
             from ciaosr_amd.png_hip import imwrite_gpu
             imwrite_gpu(out, path)                                     # uint8 [H, W, 3] BGR on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
@@ -118,7 +141,7 @@ def main(argv=None):
             print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
     if args.dzi is not None:
         from ciaosr_amd.pyramid import write_dzi
-        res = write_dzi(model, enc, args.out, name, scale=args.dzi, tile_size=args.dzi_tile, overlap=args.dzi_overlap)
+        res = write_dzi(model, enc, args.out, name, scale=args.dzi, tile_size=args.dzi_tile, overlap=args.dzi_overlap, **dzi_format)
         top = res['levels'][-1]
         print(f"{os.path.join(args.out, name + '.dzi')}: {top[0]} x {top[1]}, {len(res['levels'])} levels ({len(res['model_levels'])} from the "
               f"model), {res['files']} files, {res['bytes']} bytes")
