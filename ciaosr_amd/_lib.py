@@ -120,6 +120,7 @@ SIGNATURES = {
     'ciaosr_make_coord_cell_f32': (_I, [_P, _P, _I, _I, _P]),
     'ciaosr_make_coord_cell_window_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     'ciaosr_fragment_floats': (_S, [_I, _I]),
+    'ciaosr_head_decode_rows': (_I, [_I, _I]),
     'ciaosr_pack_fragments_f32': (_I, [_P, _I, _I, _I, _P, _P]),
     'ciaosr_cs_attn_f16': (_I, [_P, _I, _I, _I, C.POINTER(CsAttnWeightsT), _P, _I, _O, _P, _S, _P]),
     'ciaosr_fragment_bf16_bytes': (_S, [_I, _I]),

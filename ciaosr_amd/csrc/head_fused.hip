@@ -134,9 +134,12 @@ __device__ __forceinline__ float4 wload4(__amdgpu_buffer_rsrc_t rsrc, unsigned l
     return make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
 }
 
-template <int MT, int NT, int NJ>
+//   under_first: requests of the caller's that go out behind those of step 0 -- younger than the weight stages 0 .. 2, so the counted waits
+//   of steps 0 .. 2 do not wait for them and they have three steps of MFMAs to arrive (vector memory returns in order)
+struct NoRequests { __device__ __forceinline__ void operator()() const {} };
+template <int MT, int NT, int NJ, class F = NoRequests>
 __device__ __forceinline__ void mma_pass_u(const float* xa, __amdgpu_buffer_rsrc_t wrs, unsigned lane16, unsigned s_off,
-                                           unsigned tile_stride_bytes, f32x16 (&acc)[MT][NT]) {
+                                           unsigned tile_stride_bytes, f32x16 (&acc)[MT][NT], F under_first = F()) {
     static_assert(NJ >= 2, "at least two k-chunks");
     float4 fb[3][NT], fa[2][MT];
 #pragma unroll
@@ -156,6 +159,7 @@ __device__ __forceinline__ void mma_pass_u(const float* xa, __amdgpu_buffer_rsrc
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi) fa[(j + 1) & 1][mi] = *reinterpret_cast<const float4*>(xa + mi * 32 * FLD + 8 * (j + 1));
         }
+        if (j == 0) under_first();
         // component-major: consecutive MFMAs go to different accumulators wherever the pass has more than one
 #define CIAOSR_MMA_C(c)                                                                                                          \
         _Pragma("unroll") for (int ni = 0; ni < NT; ++ni)                                                                        \
@@ -230,27 +234,40 @@ __device__ __forceinline__ void hidden_layer(float* X, const void* __restrict__ 
 }
 
 
+// Layer-0 rows from the hoisted table.  Thread t handles float4 column (t & 63) of rows w + 4 s (w = t >> 6: a wave works on whole rows, so
+// the key pixel and the four coordinate terms of a row are wave-uniform).  All 8 MT table rows of a thread are requested before the first
+// FMA -- through a buffer descriptor, the row's byte offset in the SCALAR offset and the lane's column in one VGPR -- so a row build costs
+// one trip to the table instead of 8 MT dependent ones (the rolled loop waited vmcnt(0) per row).  table_bytes = H W FH floats.
 template <int MT>
-__device__ __forceinline__ void build_rows(float* X, const FusedChain& c, const int* s_kpix, const float* s_t4, int t) {
-    // 64 rows x 64 float4: thread handles float4 column (t & 63) of rows (t >> 6) + 4*s
-    const int n4 = t & 63;
-    float4 tw[4];
+__device__ __forceinline__ void build_rows(float* X, const FusedChain& c, unsigned table_bytes, const int* s_kpix, const float* s_t4, int w, int lane) {
+    constexpr int NR = 8 * MT;
+    const __amdgpu_buffer_rsrc_t rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c.table), 0, table_bytes, 0x00020000);
+    float4 tw[4];                            // the layer's four coordinate columns of this thread's 4 units (L2 hits: requested first)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) tw[e] = *reinterpret_cast<const float4*>(c.tail + (size_t)(4 * n4 + e) * c.ld_tail);
+    for (int e = 0; e < 4; ++e) tw[e] = *reinterpret_cast<const float4*>(c.tail + (size_t)(4 * lane + e) * c.ld_tail);
+    int kp[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) kp[i] = __builtin_amdgcn_readfirstlane(s_kpix[w + 4 * i]);
+    float4 tv[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) tv[i] = wload4(rs_t, (unsigned)lane * 16u, (unsigned)kp[i] * (unsigned)(FH * 4));
+    float4 t4[NR];                                                                 // rel_y rel_x scale_y scale_x
+#pragma unroll
+    for (int i = 0; i < NR; ++i) t4[i] = *reinterpret_cast<const float4*>(s_t4 + 4 * (w + 4 * i));
+    __builtin_amdgcn_sched_barrier(0);       // every request above is out before the first FMA (hipcc else keeps five in flight)
     // the four coordinate terms as PACKED fp32 FMAs on column pairs (round 4): 8 + 4 instead of 16 + 4 VALU instructions per float4, the same
     // FMA chain per element (tv + w_ry ry, + w_rx rx, + w_sy sy, + w_sx sx); broadcast / same-lane source selections only (Makefile)
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 wy01 = {tw[0].x, tw[1].x}, wy23 = {tw[2].x, tw[3].x}, wx01 = {tw[0].y, tw[1].y}, wx23 = {tw[2].y, tw[3].y};
     const f32x2 vy01 = {tw[0].z, tw[1].z}, vy23 = {tw[2].z, tw[3].z}, vx01 = {tw[0].w, tw[1].w}, vx23 = {tw[2].w, tw[3].w};
-    for (int r = t >> 6; r < 32 * MT; r += 4) {
-        const float4 tv = reinterpret_cast<const float4*>(c.table + (size_t)s_kpix[r] * FH)[n4];
-        const float4 t4 = *reinterpret_cast<const float4*>(s_t4 + 4 * r);        // rel_y rel_x scale_y scale_x
-        const f32x2 ry = {t4.x, t4.x}, rx = {t4.y, t4.y}, sy = {t4.z, t4.z}, sx = {t4.w, t4.w};
-        f32x2 a = __builtin_elementwise_fma(wy01, ry, f32x2{tv.x, tv.y}), b = __builtin_elementwise_fma(wy23, ry, f32x2{tv.z, tv.w});
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const f32x2 ry = {t4[i].x, t4[i].x}, rx = {t4[i].y, t4[i].y}, sy = {t4[i].z, t4[i].z}, sx = {t4[i].w, t4[i].w};
+        f32x2 a = __builtin_elementwise_fma(wy01, ry, f32x2{tv[i].x, tv[i].y}), b = __builtin_elementwise_fma(wy23, ry, f32x2{tv[i].z, tv[i].w});
         a = __builtin_elementwise_fma(wx01, rx, a); b = __builtin_elementwise_fma(wx23, rx, b);
         a = __builtin_elementwise_fma(vy01, sy, a); b = __builtin_elementwise_fma(vy23, sy, b);
         a = __builtin_elementwise_fma(vx01, sx, a); b = __builtin_elementwise_fma(vx23, sx, b);
-        *reinterpret_cast<float4*>(X + r * FLD + 4 * n4) = make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(b.x, 0.f), fmaxf(b.y, 0.f));
+        *reinterpret_cast<float4*>(X + (w + 4 * i) * FLD + 4 * lane) = make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(b.x, 0.f), fmaxf(b.y, 0.f));
     }
 }
 
@@ -273,6 +290,7 @@ __global__ __launch_bounds__(256, 2) void head_kv_fused_kernel(FusedKVP p) {
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int li = lane & 31, lh = lane >> 5;
     const int qbase = blockIdx.x * (BM / 4);          // local query index of row 0
+    const unsigned table_bytes = (unsigned)(p.H * p.W) * (unsigned)(FH * 4);      // the layer-0 tables: one FH-wide row per LR pixel
     HPROBE(0);
 
     // ---- index math: one thread per row (ciaosr_net.py:145-193) ---------------------------------
@@ -311,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void head_kv_fused_kernel(FusedKVP p) {
 
     // ================= phi_k =====================================================================
     HPROBE(1);
-    build_rows<MT>(X, p.k, s_kpix, s_t4, t);
+    build_rows<MT>(X, p.k, table_bytes, s_kpix, s_t4, w, lane);
     __syncthreads();
     HPROBE(2);
     for (int l = 0; l < p.k.n_hidden; ++l) {
@@ -418,7 +436,7 @@ __global__ __launch_bounds__(256, 2) void head_kv_fused_kernel(FusedKVP p) {
 
     // ================= phi_v =====================================================================
     HPROBE(4);
-    build_rows<MT>(X, p.v, s_kpix, s_t4, t);   // all waves are past their last read of X (barrier above)
+    build_rows<MT>(X, p.v, table_bytes, s_kpix, s_t4, w, lane);   // all waves are past their last read of X (barrier above)
     __syncthreads();
     HPROBE(5);
     for (int l = 0; l < p.v.n_hidden; ++l) {
@@ -509,13 +527,15 @@ __global__ __launch_bounds__(256, 2) void head_decode_fused_kernel(FusedQP p) {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Z), 0, (unsigned)((size_t)p.nq * p.ldz * 4), 0x00020000);
     f32x16 acc[MT][2];
     bias_acc<MT>(acc, p.bias_in, w, lh);
-    for (int k0 = 0; k0 < p.Dv; k0 += FH) {
-        const int kc = min(FH, p.Dv - k0);          // multiple of 8
-        if (k0 > 0) __syncthreads();                 // previous chunk fully consumed
-        {   // stage the 64 x 256 chunk of Z: 16 float4 per thread, all requested before the first LDS store, through a
-            // buffer descriptor (a guarded load inside a load -> store loop costs one HBM round trip per iteration)
-            const int c4 = (t & 63) * 4;
-            float4 zv[BM / 4];
+    // the 64 (32) x 256 chunk of Z: BM / 4 float4 per thread, all requested before the first LDS store, through a buffer descriptor (a
+    // guarded load inside a load -> store loop costs one HBM round trip per iteration)
+    const int c4 = (t & 63) * 4;
+    float4 zv[BM / 4];
+    if constexpr (MT == 1) {
+        // 32 queries (small launches): request, store, barrier, MFMA pass, chunk by chunk
+        for (int k0 = 0; k0 < p.Dv; k0 += FH) {
+            const int kc = min(FH, p.Dv - k0);          // multiple of 8
+            if (k0 > 0) __syncthreads();                 // previous chunk fully consumed
 #pragma unroll
             for (int i = 0; i < BM / 4; ++i) {
                 const int ql = qbase + (t >> 6) + 4 * i;
@@ -523,17 +543,58 @@ __global__ __launch_bounds__(256, 2) void head_decode_fused_kernel(FusedQP p) {
             }
 #pragma unroll
             for (int i = 0; i < BM / 4; ++i) *reinterpret_cast<float4*>(X + ((t >> 6) + 4 * i) * FLD + c4) = zv[i];
+            __syncthreads();
+            const unsigned s_in = ((unsigned)(2 * w) * (unsigned)p.nj_in + (unsigned)(k0 >> 3)) * 1024u;
+            if (kc == FH)
+                mma_pass_u<MT, 2, FNJ>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc);
+            else if (kc == FH / 2)
+                mma_pass_u<MT, 2, FNJ / 2>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc);
+            else
+                mma_pass<MT, 2>(X + li * FLD + 4 * lh,
+                            reinterpret_cast<const float4*>(p.frag_in) + ((size_t)(2 * w) * p.nj_in + (k0 >> 3)) * 64 + lane,
+                            kc >> 3, (long)p.nj_in * 64, acc);
         }
-        __syncthreads();
-        const unsigned s_in = ((unsigned)(2 * w) * (unsigned)p.nj_in + (unsigned)(k0 >> 3)) * 1024u;
-        if (kc == FH)
-            mma_pass_u<MT, 2, FNJ>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc);
-        else if (kc == FH / 2)
-            mma_pass_u<MT, 2, FNJ / 2>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc);
-        else
-            mma_pass<MT, 2>(X + li * FLD + 4 * lh,
-                        reinterpret_cast<const float4*>(p.frag_in) + ((size_t)(2 * w) * p.nj_in + (k0 >> 3)) * 64 + lane,
-                        kc >> 3, (long)p.nj_in * 64, acc);
+    } else {
+        // 64 queries: chunk c + 1 is requested into registers under the MFMA pass of chunk c (behind that pass's first weight stages) and
+        // stored behind the next chunk barrier.  LDS limits this form to two workgroups per CU, so the 64 registers cost no residency; at
+        // 32 queries they cost the fourth workgroup and the kernel measured slower (round 6).
+        auto request_z = [&](int k0) {
+            // a wave stages whole rows: the row's offset is scalar.  The range check of a raw buffer leaves the scalar offset out, so a row
+            // past the launch reads the launch's last row instead (its result is never stored); columns past the chunk read zeros
+            const int kc = min(FH, p.Dv - k0);
+#pragma unroll
+            for (int i = 0; i < BM / 4; ++i) {
+                const int ql = min(qbase + w + 4 * i, p.nq - 1);
+                zv[i] = wload4(rs_zin, c4 < kc ? (unsigned)c4 * 4u : kOobF, ((unsigned)ql * (unsigned)p.ldz + (unsigned)k0) * 4u);
+            }
+        };
+        auto store_z = [&](int k0) {
+            if (k0 > 0) __syncthreads();                 // previous chunk fully consumed
+#pragma unroll
+            for (int i = 0; i < BM / 4; ++i) *reinterpret_cast<float4*>(X + (w + 4 * i) * FLD + c4) = zv[i];
+            __syncthreads();
+        };
+        request_z(0);
+        // the full chunks in a loop of their own: one MFMA pass form in it, so the accumulators stay in place around the loop (with the
+        // three forms in one loop hipcc kept two copies of them: 189 registers, and scratch once zv stays live under the pass)
+        int k0 = 0;
+        for (; k0 + FH <= p.Dv; k0 += FH) {
+            store_z(k0);
+            const unsigned s_in = ((unsigned)(2 * w) * (unsigned)p.nj_in + (unsigned)(k0 >> 3)) * 1024u;
+            mma_pass_u<MT, 2, FNJ>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc,
+                                   [&]() { if (k0 + FH < p.Dv) request_z(k0 + FH); });
+        }
+        if (k0 < p.Dv) {                                 // the last, narrower chunk (a multiple of 8 columns)
+            const int kc = p.Dv - k0;
+            store_z(k0);
+            const unsigned s_in = ((unsigned)(2 * w) * (unsigned)p.nj_in + (unsigned)(k0 >> 3)) * 1024u;
+            if (kc == FH / 2)
+                mma_pass_u<MT, 2, FNJ / 2>(X + li * FLD + 4 * lh, frag_rsrc(p.frag_in), (unsigned)lane * 16u, s_in, (unsigned)p.nj_in * 1024u, acc);
+            else
+                mma_pass<MT, 2>(X + li * FLD + 4 * lh,
+                            reinterpret_cast<const float4*>(p.frag_in) + ((size_t)(2 * w) * p.nj_in + (k0 >> 3)) * 64 + lane,
+                            kc >> 3, (long)p.nj_in * 64, acc);
+        }
     }
     __syncthreads();
     store_relu_tile<MT>(X, acc, w, li, lh);
@@ -621,12 +682,16 @@ int head_kv_fused(const FusedKVP& p, hipStream_t s) {
     return launch_status("head_kv_fused");
 }
 
+// Queries per decode workgroup: decode_rows = 32 or 64 as asked, 0 by launch size.  32-query workgroups (four per CU) overlap each other's
+// staging and epilogues and win on small launches (C2: 0.36 -> 0.29 ms); 64-query ones stream every weight fragment to two row tiles
+// (8 instead of 16 B/clk per CU against the 21 B/clk an L2 delivers) and fetch the next chunk of Z under the MFMAs, which pays once the
+// launch fills the chip a few times over -- the same threshold as head_kv_fused's: 2048 workgroups of 64.
+int decode_rows_for(int asked, int nq) { return asked == 64 || (asked != 32 && ceil_div(nq, 64) >= 2048) ? 64 : 32; }
+
 int head_decode_fused(const FusedQP& p, hipStream_t s) {
     CIAOSR_BIG_LDS(head_decode_fused_kernel<2>, (size_t)64 * FLD * sizeof(float));
     CIAOSR_BIG_LDS(head_decode_fused_kernel<1>, (size_t)32 * FLD * sizeof(float));
-    // 32-query workgroups by default (four per CU; measured better than 64-query ones at C2 and at the 192 tile: 0.36 -> 0.29 ms,
-    // 3.93 -> 3.83 ms), like the phi_k/phi_v kernel
-    const int rows = p.rows_per_wg == 64 ? 64 : 32;   // 64: experiments (ciaosr_options_t.decode_rows)
+    const int rows = decode_rows_for(p.rows_per_wg, p.nq);
     ProfScope prof("head_decode_fused", s);
     if (rows == 64)
         hipLaunchKernelGGL(head_decode_fused_kernel<2>, dim3(ceil_div(p.nq, 64)), dim3(256), (size_t)64 * FLD * sizeof(float), s, p);
@@ -640,6 +705,8 @@ int head_decode_fused(const FusedQP& p, hipStream_t s) {
 using namespace ciaosr;
 
 extern "C" size_t ciaosr_fragment_floats(int N, int K) { return fragment_floats(N, K); }
+
+extern "C" int ciaosr_head_decode_rows(int decode_rows, int nq) { return decode_rows_for(decode_rows, nq); }
 
 extern "C" int ciaosr_pack_fragments_f32(const float* W, int ld, int N, int K, float* out, void* stream) {
     CIAOSR_CHECK_ARG(W && out && N > 0 && K > 0 && ld >= K);

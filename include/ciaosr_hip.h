@@ -115,7 +115,7 @@ typedef struct ciaosr_options {
     int scatter_small_max;  /* RDN trunk: largest map (pixels) for the small-map dense-block kernels; 0 = default (18432),
                              * < 0 = never */
     int kv_rows;            /* fp32 fused head: (query, sample) rows per workgroup, 32 or 64; 0 = automatic (64 from 32768 queries) */
-    int decode_rows;        /* fp32 fused decode: queries per workgroup, 32 (default) or 64 */
+    int decode_rows;        /* fp32 fused decode: queries per workgroup, 32 or 64; 0 = automatic (64 from 131072 queries) */
     int bf16_single;        /* 0 or 1: selects a precision mode (table above) */
     int dense_direct;       /* _f32 RDN trunk, big maps: 0 (default) = dense layers in Winograd form -- F(4x4, 3x3) when ciaosr_conv_t.frag_wino4
                              * is given, else F(2x2, 3x3) when frag_wino is (fp32 arithmetic on transformed operands: not bitwise a direct
@@ -255,6 +255,8 @@ typedef struct ciaosr_mlp {
 /* MFMA fragment packing of a Linear weight W[N][ld] (K valid columns): out[nt][j][lane][4] with
  * lane (i = lane&31, h = lane>>5) holding W[32nt+i][8j+4h .. 8j+4h+3]; zero padded. */
 size_t ciaosr_fragment_floats(int N, int K);
+/* Queries per workgroup of the fp32 fused decode kernel for a launch of nq queries under decode_rows (host; launches nothing): 32 or 64. */
+int ciaosr_head_decode_rows(int decode_rows, int nq);
 int ciaosr_pack_fragments_f32(const float* W, int ld, int N, int K, float* out, void* stream);
 
 /* bf16 fragment packing: out[nt][ks][lane][8 bf16], lane (i = lane&31, g = lane>>5) holds
