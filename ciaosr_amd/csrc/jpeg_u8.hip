@@ -21,6 +21,13 @@
 //   jpeg_ffcount per chunk the 0xFF bytes of its byte range (the byte that holds a chunk's first bit belongs to the chunk before).
 //   jpeg_scan2   one workgroup: prefix sum of bytes + 0xFF counts -> every chunk's final offset, the tiles' offsets, the total.
 //   jpeg_stuff   copies the bytes to their final place with a 0x00 after every 0xFF; a tile's last byte is padded with 1-bits.
+// With optimised Huffman tables (the ciaosr_jpeg_opt_* entry points: Pillow's optimize=True files) two launches follow jpeg_coef, and
+// jpeg_count / jpeg_pack read the tile's own code tables where they otherwise read the Annex K constants:
+//   jpeg_hist    one lane per block, the same block walk: the chunk's symbols counted per table in LDS (4 x 256), the bins that are
+//                not zero added to the tile's histograms with integer atomicAdd (zeroed by a memset on the stream in every call).
+//   jpeg_tables  one workgroup per tile, one wave per table: libjpeg's rule -- merge the two smallest frequencies (ties to the larger
+//                index) with a pseudo-symbol that reserves the all-ones code, limit the lengths to 16, order the symbols by the
+//                size they had BEFORE limiting -- gives the DHT record for the host and the length << 16 | code table for the scan.
 // No floating point anywhere; the bytes do not depend on mcus_per_chunk, on the stream or on what else is in the list.
 #include <climits>
 #include <cstring>
@@ -41,6 +48,12 @@ constexpr int kHuff = 272;                         // per table class: 256 AC en
 constexpr u64 kBlockBytes = 208;                   // 64 coefficients x (16-bit code + 10 extra bits): the most a block can take
 constexpr int kStuffPerLane = 16;                  // bytes per lane and step of the stuffing kernels
 constexpr int kZeroGroups = 1024;
+// optimised coding: the four tables of a file in the order of its DHT segments -- DC luma, AC luma, DC chroma, AC chroma
+constexpr int kTables = 4;
+constexpr int kDhtRecord = CIAOSR_JPEG_DHT_RECORD_BYTES;   // 16 counts, 256 symbols (padded with zeros)
+constexpr int kMaxDepth = 64;                      // code sizes before limiting: a depth d needs Fibonacci(d + 2) symbols, so < 44 below the limit
+constexpr u64 kFreqLimit = 1000000000ull;          // a crop is refused when 64 x its blocks reaches this
+constexpr u64 kOptBlockBits = 16 + 11 + 63 * (16 + 10);   // 1665: what a block can take with arbitrary codes of up to 16 bits
 
 struct Consts {
     int qdiv[2][64];                               // 8 x quantisation table, natural order; [0] luma, [1] chroma
@@ -211,6 +224,10 @@ struct Params {
     unsigned char* out;
     u64* tile_offs;               // [nt + 1]
     u64* total;                   // optional: tile_offs[nt] once more
+    // optimised coding only (null otherwise)
+    u32* tile_hist;               // [nt][4][256]: symbol counts per table, in the file's order of tables (kTables)
+    u32* tile_huff;               // [nt][2][kHuff]: the tile's code tables in the layout of Consts::huff
+    unsigned char* dht;          // [nt][4][kDhtRecord]: the tables as DHT segments hold them
 };
 
 constexpr int kF0_298 = 2446, kF0_390 = 3196, kF0_541 = 4433, kF0_765 = 6270, kF0_899 = 7373, kF1_175 = 9633, kF1_501 = 12299,
@@ -333,9 +350,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_coef_kernel(Params p) {
 // ---- entropy coding --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int bit_length(int a) { return 32 - __clz(a); }       // a >= 0; 0 -> 0
 
-// Walks one block: e.put(value, length) for the DC difference and every AC code with its extra bits appended.
-template <typename E>
-__device__ __forceinline__ void code_block(const short* cf, int pred, const u32* tab /* [kHuff] */, E& e) {
+// Walks one block: s.symbol(index, extra, n) for the DC difference (index 256 + n) and every AC symbol (index run << 4 | n; ZRL and
+// EOB with n = 0), `extra` being the n bits that follow the symbol's code.
+template <typename S>
+__device__ __forceinline__ void walk_block(const short* cf, int pred, S& s) {
     const uint4* v4 = reinterpret_cast<const uint4*>(cf);
     int run = 0;
 #pragma unroll 1
@@ -353,25 +371,35 @@ __device__ __forceinline__ void code_block(const short* cf, int pred, const u32*
             }
             const int n = bit_length(abs(v));
             const u32 extra = (u32)(v < 0 ? v + (1 << n) - 1 : v) & ((1u << n) - 1u);
-            u32 ent;
             if (dc) {
-                ent = tab[256 + n];
+                s.symbol(256 + n, extra, n);
             } else {
                 while (run > 15) {
-                    const u32 z = tab[0xf0];
-                    e.put(z & 0xffffu, (int)(z >> 16));
+                    s.symbol(0xf0, 0u, 0);
                     run -= 16;
                 }
-                ent = tab[(run << 4) | n];
+                s.symbol((run << 4) | n, extra, n);
                 run = 0;
             }
-            e.put(((ent & 0xffffu) << n) | extra, (int)(ent >> 16) + n);
         }
     }
-    if (run > 0) {
-        const u32 z = tab[0x00];
-        e.put(z & 0xffffu, (int)(z >> 16));
+    if (run > 0) s.symbol(0x00, 0u, 0);
+}
+
+// e.put(value, length) for every symbol of the block, its code from `tab` with the extra bits appended
+template <typename E>
+struct Coder {
+    const u32* tab;                // [kHuff]
+    E& e;
+    __device__ __forceinline__ void symbol(int index, u32 extra, int n) {
+        const u32 ent = tab[index];
+        e.put(((ent & 0xffffu) << n) | extra, (int)(ent >> 16) + n);
     }
+};
+template <typename E>
+__device__ __forceinline__ void code_block(const short* cf, int pred, const u32* tab /* [kHuff] */, E& e) {
+    Coder<E> c{tab, e};
+    walk_block(cf, pred, c);
 }
 
 struct Counter {
@@ -434,8 +462,9 @@ __global__ __launch_bounds__(kThreads) void jpeg_count_kernel(Params p) {
     __shared__ u32 tab[2][kHuff];
     __shared__ u64 red[kWaves];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = (&p.consts->huff[0][0])[i];
     const ChunkT ch = p.chunks[blockIdx.x];
+    const u32* huff = p.tile_huff ? p.tile_huff + (size_t)ch.tile * (2 * kHuff) : &p.consts->huff[0][0];
+    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = huff[i];
     const TileT t = p.tiles[ch.tile];
     const int bpm = p.sub420 ? 6 : 3;
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
@@ -451,6 +480,162 @@ __global__ __launch_bounds__(kThreads) void jpeg_count_kernel(Params p) {
     }
     sum = wg_sum_u64(sum, red);
     if (tid == 0) p.chunk_bits[blockIdx.x] = sum;
+}
+
+// ---- optimised coding: the tile's histograms and its tables -------------------------------------------------------------------------
+struct Tally {
+    u32* dc;                       // LDS [256] each: the DC and the AC histogram of the block's table class
+    u32* ac;
+    __device__ __forceinline__ void symbol(int index, u32, int) { atomicAdd(index >= 256 ? &dc[index - 256] : &ac[index], 1u); }
+};
+
+// One workgroup per chunk: the symbols of its blocks counted in LDS, the bins that are not zero added to the tile's histograms (zeroed
+// on the stream before every call).  Integer addition: the sums do not depend on the order of arrival.
+__global__ __launch_bounds__(kThreads) void jpeg_hist_kernel(Params p) {
+    __shared__ u32 hist[kTables][256];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kTables * 256; i += kThreads) (&hist[0][0])[i] = 0u;
+    const ChunkT ch = p.chunks[blockIdx.x];
+    const TileT t = p.tiles[ch.tile];
+    const int bpm = p.sub420 ? 6 : 3;
+    const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
+    const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
+    __syncthreads();
+    for (int j = tid; j < nblk; j += kThreads) {
+        const u64 blk = base + (u64)j;
+        const int cls = table_of(p, t, blk);
+        Tally ta{hist[2 * cls], hist[2 * cls + 1]};
+        walk_block(p.coef + blk * 64ull, dc_pred(p, t, blk), ta);
+    }
+    __syncthreads();
+    u32* dst = p.tile_hist + (size_t)ch.tile * (kTables * 256);
+    for (int i = tid; i < kTables * 256; i += kThreads) {
+        const u32 v = (&hist[0][0])[i];
+        if (v) atomicAdd(&dst[i], v);
+    }
+}
+
+__device__ __forceinline__ u64 wave_min_u64(u64 v) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const u64 o = __shfl_xor(v, off, kWave);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// One workgroup per tile, wave k makes table k (kTables) from its histogram by libjpeg's rule.  Lane l holds the symbols
+// 4 l .. 4 l + 3, lane 0 also the pseudo-symbol 256 of frequency 1 that reserves the all-ones code.  A group of merged symbols is named
+// by the one index that carries its frequency; the smaller of two groups is found as the wave's minimum of frequency << 9 | (256 - index):
+// by frequency, ties to the larger index.  Integer only.
+__global__ __launch_bounds__(kThreads) void jpeg_tables_kernel(Params p) {
+    __shared__ u32 size_of[kTables][256];          // code size before limiting per symbol; later the symbol's length << 16 | code
+    __shared__ u32 nbits[kTables][kMaxDepth];      // symbols per code size
+    __shared__ unsigned char vals[kTables][256];   // the symbols in code order
+    const int tid = threadIdx.x, k = tid >> 6, lane = tid & 63, tile = blockIdx.x;
+    const u32* hist = p.tile_hist + ((size_t)tile * kTables + k) * 256;
+    constexpr u64 kNone = ~0ull;
+    u32 freq[5], size[5];
+    int index[5], group[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        index[s] = s < 4 ? 4 * lane + s : 256 + lane;      // slot 4 is a symbol in lane 0 only
+        freq[s] = s < 4 ? hist[index[s]] : (lane == 0 ? 1u : 0u);
+        size[s] = 0u;
+        group[s] = index[s];
+    }
+    for (;;) {
+        u64 key[5], k1 = kNone, k2 = kNone;
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            key[s] = freq[s] ? ((u64)freq[s] << 9) | (u64)(u32)(256 - index[s]) : kNone;
+            k1 = key[s] < k1 ? key[s] : k1;
+        }
+        const u64 m1 = wave_min_u64(k1);
+#pragma unroll
+        for (int s = 0; s < 5; ++s)
+            if (key[s] != m1 && key[s] < k2) k2 = key[s];
+        const u64 m2 = wave_min_u64(k2);
+        if (m2 == kNone) break;                             // one group is left
+        const int c1 = 256 - (int)(m1 & 511ull), c2 = 256 - (int)(m2 & 511ull);
+        const u32 sum = (u32)(m1 >> 9) + (u32)(m2 >> 9);
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            if (index[s] == c1) freq[s] = sum;
+            if (index[s] == c2) freq[s] = 0u;
+            if (group[s] == c1 || group[s] == c2) {
+                ++size[s];
+                group[s] = c1;
+            }
+        }
+    }
+    if (lane < kMaxDepth) nbits[k][lane] = 0u;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) size_of[k][index[s]] = size[s];
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 5; ++s)
+        if (size[s]) atomicAdd(&nbits[k][min(size[s], (u32)(kMaxDepth - 1))], 1u);
+    __syncthreads();
+    if (lane == 0) {                                        // limiting to 16 bits, then the reserved code leaves
+        u32* b = nbits[k];
+        for (int i = kMaxDepth - 1; i > 16; --i)
+            while (b[i] >= 2u) {
+                int j = i - 2;
+                while (j > 0 && b[j] == 0u) --j;
+                if (j == 0) break;
+                b[i] -= 2u;
+                b[i - 1] += 1u;
+                b[j + 1] += 2u;
+                b[j] -= 1u;
+            }
+        int i = 16;
+        while (i > 0 && b[i] == 0u) --i;
+        if (i > 0) b[i] -= 1u;
+    }
+    // the code order: by size BEFORE limiting, then by symbol; the place of a symbol is the number of symbols before it
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const u32 c = size[s];
+        if (c == 0u) continue;
+        int before = 0;
+        for (int j = 0; j < 256; ++j) {
+            const u32 cj = size_of[k][j];
+            before += (cj != 0u && (cj < c || (cj == c && j < index[s]))) ? 1 : 0;
+        }
+        vals[k][before] = (unsigned char)index[s];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 4; ++s) size_of[k][index[s]] = 0u;
+    __syncthreads();
+    if (lane == 0) {                                        // canonical codes from the counts and that order
+        u32 code = 0u;
+        int at = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (u32 i = 0; i < nbits[k][len] && at < 256; ++i, ++at, ++code) size_of[k][vals[k][at]] = ((u32)len << 16) | code;
+            code <<= 1;
+        }
+    }
+    __syncthreads();
+    // the tile's code tables as jpeg_count and jpeg_pack read them: per class 256 AC entries by symbol, then the DC entries by size
+    u32* tab = p.tile_huff +((size_t)tile * 2 + (k >> 1)) * kHuff;
+    if (k & 1) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) tab[index[s]] = size_of[k][index[s]];
+    } else if (lane < kHuff - 256) {
+        tab[256 + lane] = size_of[k][lane];
+    }
+    // the DHT record: 16 counts, then the symbols, zeros behind the last
+    unsigned char* rec = p.dht + ((size_t)tile * kTables + k) * kDhtRecord;
+    int count = 0;
+    for (int len = 1; len <= 16; ++len) count += (int)nbits[k][len];
+    if (lane < 16) rec[lane] = (unsigned char)nbits[k][lane + 1];
+    u32 word = 0u;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+        if (index[s] < count) word |= (u32)vals[k][index[s]] << (8 * s);
+    reinterpret_cast<u32*>(rec + 16)[lane] = word;
 }
 
 __global__ __launch_bounds__(kThreads) void jpeg_scan_kernel(Params p) {
@@ -509,8 +694,9 @@ __global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(Params p) {
     __shared__ u32 tab[2][kHuff];
     __shared__ u32 wsum[kWaves];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = (&p.consts->huff[0][0])[i];
     const ChunkT ch = p.chunks[blockIdx.x];
+    const u32* huff = p.tile_huff ? p.tile_huff + (size_t)ch.tile * (2 * kHuff) : &p.consts->huff[0][0];
+    for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = huff[i];
     const TileT t = p.tiles[ch.tile];
     const int bpm = p.sub420 ? 6 : 3;
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
@@ -601,19 +787,23 @@ static inline int default_mcus(int sub420) { return sub420 ? 128 : 256; }     //
 struct Plan {
     int rc;                       // CIAOSR_OK, or why the rects cannot be coded
     int nt, nc;
+    bool opt;                     // optimised Huffman tables
     u64 blocks;
-    size_t capacity;              // the stuffed worst case: 2 x 208 bytes per block
+    size_t capacity;              // the stuffed worst case: 2 x 208 bytes per block (optimised: 2 x ceil(1665 x blocks / 8) per tile)
     size_t ubytes;                // the unstuffed worst case, every tile rounded up to 4 bytes
     size_t o_tiles, o_chunks, table_bytes;
 };
 // `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
-static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcus_arg, int H, int W, std::vector<unsigned char>* table) {
+static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcus_arg, int H, int W, std::vector<unsigned char>* table,
+                 bool opt = false) {
     Plan t{};
+    t.opt = opt;
     t.rc = CIAOSR_ERR_BAD_ARG;
     if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || (sub420 != 0 && sub420 != 1)) return t;
     const int per = mcus_arg > 0 ? mcus_arg : default_mcus(sub420);
     const int bpm = sub420 ? 6 : 3, side = sub420 ? 16 : 8;
-    u64 nc = 0, blocks = 0;
+    u64 nc = 0, blocks = 0, opt_bytes = 0;
+    bool too_many = false;                                  // optimised: a crop at the frequency limit
     for (int k = 0; k < n_tiles; ++k) {
         const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
         if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
@@ -621,8 +811,10 @@ static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcu
         const u64 nmcu = (u64)ceil_div(h, side) * (u64)ceil_div(w, side);
         nc += (nmcu + per - 1) / per;
         blocks += nmcu * bpm;
+        too_many = too_many || 64ull * nmcu * bpm >= kFreqLimit;
+        opt_bytes += (kOptBlockBits * nmcu * bpm + 7ull) / 8ull;
     }
-    if (nc > (u64)INT_MAX / 2 || blocks > (u64)INT_MAX) {
+    if (nc > (u64)INT_MAX / 2 || blocks > (u64)INT_MAX || (opt && too_many)) {
         t.rc = CIAOSR_ERR_UNSUPPORTED;
         return t;
     }
@@ -632,6 +824,10 @@ static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcu
     t.blocks = blocks;
     t.capacity = (size_t)(2 * kBlockBytes * blocks);
     t.ubytes = (size_t)(kBlockBytes * blocks) + 4 * (size_t)n_tiles;
+    if (opt) {
+        t.capacity = (size_t)(2 * opt_bytes);
+        t.ubytes = (size_t)opt_bytes + 4 * (size_t)n_tiles;
+    }
     t.o_tiles = sizeof(Consts);
     t.o_chunks = t.o_tiles + sizeof(TileT) * (size_t)n_tiles;
     t.table_bytes = t.o_chunks + sizeof(ChunkT) * (size_t)nc;
@@ -654,7 +850,7 @@ static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcu
 struct Work {
     unsigned char* table;
     short* coef;
-    u32 *block_bits, *chunk_pad, *ubuf;
+    u32 *block_bits, *chunk_pad, *ubuf, *tile_hist, *tile_huff;
     u64 *chunk_bits, *chunk_sum, *chunk_bitoff, *chunk_b0, *chunk_b1, *chunk_out, *tile_ubase, *utotal, *offs2;
 };
 static inline bool carve(void* ws, size_t bytes, const Plan& t, Work* w, size_t* used) {
@@ -674,6 +870,11 @@ static inline bool carve(void* ws, size_t bytes, const Plan& t, Work* w, size_t*
     w->utotal = a.take<u64>(1);
     w->offs2 = a.take<u64>(2);
     w->ubuf = a.take<u32>((t.ubytes + 3) / 4);
+    w->tile_hist = w->tile_huff = nullptr;
+    if (t.opt) {
+        w->tile_hist = a.take<u32>((size_t)t.nt * kTables * 256);
+        w->tile_huff = a.take<u32>((size_t)t.nt * 2 * kHuff);
+    }
     if (used) *used = a.off;
     return a.ok;
 }
@@ -695,9 +896,10 @@ static int launch(const char* tag, K kernel, int grid, const Params& p, hipStrea
 // every check that the host can make comes before the first launch
 static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int sub420,
                   int mcus, unsigned char* out, size_t out_capacity, u64* tile_offs, u64* total, void* workspace, size_t workspace_bytes,
-                  hipStream_t s) {
+                  hipStream_t s, unsigned char* dht = nullptr /* optimised tables: [n_tiles][4][kDhtRecord] */) {
     std::vector<unsigned char> table;
-    const Plan t = plan(rects, n_tiles, quality, sub420, mcus, H, W, &table);
+    const bool opt = dht != nullptr;
+    const Plan t = plan(rects, n_tiles, quality, sub420, mcus, H, W, &table, opt);
     CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image; quality; subsampling
     if (t.rc != CIAOSR_OK) return t.rc;
     if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
@@ -730,8 +932,17 @@ static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr,
     p.out = out;
     p.tile_offs = tile_offs ? tile_offs : w.offs2;
     p.total = total;
+    p.tile_hist = w.tile_hist;
+    p.tile_huff = w.tile_huff;
+    p.dht = dht;
     int rc;
+    // the workspace holds what the last call left: the histograms start from zero in every call
+    if (opt && hipMemsetAsync(w.tile_hist, 0, sizeof(u32) * (size_t)t.nt * kTables * 256, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
     if ((rc = launch("jpeg_coef", jpeg_coef_kernel, t.nc, p, s))) return rc;
+    if (opt) {
+        if ((rc = launch("jpeg_hist", jpeg_hist_kernel, t.nc, p, s))) return rc;
+        if ((rc = launch("jpeg_tables", jpeg_tables_kernel, t.nt, p, s))) return rc;
+    }
     if ((rc = launch("jpeg_count", jpeg_count_kernel, t.nc, p, s))) return rc;
     if ((rc = launch("jpeg_scan", jpeg_scan_kernel, 1, p, s))) return rc;
     const u64 zero_groups = (t.ubytes / 4 + kThreads - 1) / kThreads;
@@ -792,4 +1003,49 @@ extern "C" int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int
     const int rect[4] = {0, 0, H, W};
     return encode(src, pitch, H, W, bgr, rect, 1, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, nullptr, total_bytes, workspace,
                   workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- optimised Huffman tables ---------------------------------------------------------------------------------------------------------
+extern "C" size_t ciaosr_jpeg_opt_result_bytes(int n_tiles) {
+    return n_tiles < 1 ? 0 : 8 * ((size_t)n_tiles + 1) + (size_t)kTables * kDhtRecord * (size_t)n_tiles;
+}
+
+extern "C" size_t ciaosr_jpeg_opt_tiles_workspace_bytes(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
+    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk, 0, 0, nullptr, true);
+    return t.rc == CIAOSR_OK ? work_bytes(t) : 0;
+}
+
+extern "C" size_t ciaosr_jpeg_opt_tiles_capacity_bytes(const int* rects, int n_tiles, int subsampling) {
+    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), 0, 0, 0, nullptr, true);
+    return t.rc == CIAOSR_OK ? t.capacity : 0;
+}
+
+extern "C" size_t ciaosr_jpeg_opt_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk) {
+    const int rect[4] = {0, 0, H, W};
+    return ciaosr_jpeg_opt_tiles_workspace_bytes(rect, 1, subsampling, mcus_per_chunk);
+}
+
+extern "C" size_t ciaosr_jpeg_opt_capacity_bytes(int H, int W, int subsampling) {
+    const int rect[4] = {0, 0, H, W};
+    return ciaosr_jpeg_opt_tiles_capacity_bytes(rect, 1, subsampling);
+}
+
+extern "C" int ciaosr_jpeg_opt_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                               int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
+                                               void* result, void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
+    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(result) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    u64* offs = static_cast<u64*>(result);
+    return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, offs, nullptr, workspace,
+                  workspace_bytes, (hipStream_t)stream, reinterpret_cast<unsigned char*>(offs + n_tiles + 1));
+}
+
+extern "C" int ciaosr_jpeg_opt_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
+                                         int mcus_per_chunk, unsigned char* out, size_t out_capacity, void* result, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    const int rect[4] = {0, 0, H, W};
+    return ciaosr_jpeg_opt_encode_tiles_u8(src, pitch, H, W, bgr, rect, 1, quality, subsampling, mcus_per_chunk, out, out_capacity, result,
+                                           workspace, workspace_bytes, stream);
 }

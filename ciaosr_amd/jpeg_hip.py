@@ -6,6 +6,11 @@ entropy-coded scan.  The host only wraps it: `header(h, w, quality, subsampling)
 SOS header; it depends on nothing else), EOI behind.  DESIGN 4.1i-d holds the contract.  Two copies synchronise per call: the sizes,
 then the bytes.  There is no CPU fallback: a host array raises.  `encode_jpeg_tiles` codes many crops of one image (the tiles of a
 pyramid level, pyramid.py) in one set of launches; each file is byte for byte the single call's on that crop.
+
+`optimize=True` writes Pillow's `optimize=True` files instead (libjpeg's optimize_coding): the same coefficients and symbols, coded with
+four Huffman tables derived per file from the histograms of its own symbols.  The device counts the symbols, makes the tables by
+libjpeg's rule and codes with them; the tables come back as DHT records in the buffer that holds the sizes, so a call still
+synchronises twice, and `header(..., tables=)` writes them into the file's four DHT segments.
 """
 import ctypes as C
 import os
@@ -64,22 +69,58 @@ def check_params(quality, subsampling):
     return int(quality), SUBSAMPLINGS[subsampling]
 
 
+FREQUENCY_LIMIT = 1_000_000_000            # optimised coding: a crop is refused when 64 x (blocks of its scan) reaches this
+DHT_RECORD_BYTES = 272                     # CIAOSR_JPEG_DHT_RECORD_BYTES: 16 counts, 256 symbols padded with zeros
+TABLE_IDS = tuple(t[0] for t in HUFFMAN)   # class << 4 | id of the four DHT segments, in the file's order
+
+
+def check_optimize(optimize):
+    """`optimize` is a bool; ValueError otherwise (before any device work)."""
+    if not isinstance(optimize, bool):
+        raise ValueError(f'optimize is True or False, got {optimize!r}')
+    return optimize
+
+
+def scan_block_count(h, w, subsampling):
+    """Blocks of the scan of an h x w image: all components, the dummy blocks of 4:2:0 included."""
+    if subsampling == '420':
+        return 6 * -(-h // 16) * -(-w // 16)
+    return 3 * -(-h // 8) * -(-w // 8)
+
+
+def check_frequency_limit(h, w, subsampling):
+    """Optimised coding counts symbols in 32 bits and follows libjpeg only below its sentinel frequency: a crop whose scan could hold
+    FREQUENCY_LIMIT symbols (64 per block) is a ValueError."""
+    blocks = scan_block_count(h, w, subsampling)
+    if 64 * blocks >= FREQUENCY_LIMIT:
+        raise ValueError(f'optimize=True: {h} x {w} in {subsampling} has {blocks} blocks; 64 x blocks must stay below {FREQUENCY_LIMIT}')
+    return blocks
+
+
 def quant_tables(quality):
     """(luma, chroma): 64 values each, natural order -- libjpeg's quality scaling of the Annex K tables."""
     s = 5000 // quality if quality < 50 else 200 - 2 * quality
     return tuple(tuple(min(max((b * s + 50) // 100, 1), 255) for b in base) for base in (BASE_LUMA, BASE_CHROMA))
 
 
-def header(h, w, quality, subsampling):
-    """The file from SOI up to and including the SOS header, as Pillow writes it for an h x w RGB image."""
+def header(h, w, quality, subsampling, tables=None):
+    """The file from SOI up to and including the SOS header, as Pillow writes it for an h x w RGB image.  `tables`: four (counts,
+    symbols) pairs in the file's order (DC luma, AC luma, DC chroma, AC chroma) for the DHT segments of an optimised file -- 16 counts
+    per code length 1..16 and exactly sum(counts) symbols each; None: the Annex K tables."""
     quality, _ = check_params(quality, subsampling)
+    huffman = HUFFMAN
+    if tables is not None:
+        tables = [(tuple(int(c) for c in counts), tuple(int(v) for v in symbols)) for counts, symbols in tables]
+        if len(tables) != 4 or any(len(c) != 16 or len(v) != sum(c) or not 1 <= len(v) <= 256 for c, v in tables):
+            raise ValueError('tables: four (16 counts, sum(counts) symbols) pairs')
+        huffman = tuple((tc_th, c, v) for tc_th, (c, v) in zip(TABLE_IDS, tables))
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
     parts = [b'\xff\xd8', b'\xff\xe0', struct.pack('>H5sBBBHHBB', 16, b'JFIF\0', 1, 1, 0, 1, 1, 0, 0)]
     for k, q in enumerate(quant_tables(quality)):
         parts += [b'\xff\xdb', struct.pack('>HB', 67, k), bytes(q[i] for i in ZIGZAG)]
     parts += [b'\xff\xc0', struct.pack('>HBHHB', 17, 8, h, w, 3), bytes((1, 0x22 if subsampling == '420' else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))]
-    for tc_th, bits, vals in HUFFMAN:
+    for tc_th, bits, vals in huffman:
         parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), tc_th), bytes(bits), bytes(vals)]
     parts += [b'\xff\xda', struct.pack('>HB', 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3f, 0))]
     return b''.join(parts)
@@ -99,42 +140,73 @@ def _check(img, quality, subsampling, order, mcus_per_chunk, what):
     return h, w, quality, sub, int(mcus_per_chunk)
 
 
-def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None):
+def split_result(result, n):
+    """The host copy (a sequence of int64) of an optimised call's result -> (offsets [n + 1], tables): tables[k] holds crop k's four
+    (counts, symbols) pairs as `header(..., tables=)` takes them."""
+    raw = bytes(memoryview(result.numpy()).cast('B')) if isinstance(result, torch.Tensor) else bytes(result)
+    offsets = list(struct.unpack(f'<{n + 1}q', raw[:8 * (n + 1)]))
+    tables = []
+    for k in range(4 * n):
+        rec = raw[8 * (n + 1) + DHT_RECORD_BYTES * k:8 * (n + 1) + DHT_RECORD_BYTES * (k + 1)]
+        tables.append((tuple(rec[:16]), tuple(rec[16:16 + sum(rec[:16])])))
+    return offsets, [tables[4 * k:4 * k + 4] for k in range(n)]
+
+
+def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None, optimize=False):
     """ciaosr_jpeg_encode_tiles_u8 on the current stream, no synchronisation -> (scans uint8 [capacity], offsets int64 [n + 1]) on the
     device: crop k's entropy-coded scan is scans[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps.  `out`, `capacity`: a buffer of
-    the caller's and the size to declare for it (default: `ciaosr_jpeg_tiles_capacity_bytes`, the worst case)."""
+    the caller's and the size to declare for it (default: `ciaosr_jpeg_tiles_capacity_bytes`, the worst case).
+    `optimize=True`: ciaosr_jpeg_opt_encode_tiles_u8 -> (scans, result int64 [n + 1 + 136 n]): the offsets, then the crops' DHT records
+    (`split_result` takes the host copy apart); the default capacity is `ciaosr_jpeg_opt_tiles_capacity_bytes`."""
+    check_optimize(optimize)
     h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
     rects = check_rects(rects, h, w)
     n = len(rects)
+    if optimize:
+        for r in rects:
+            check_frequency_limit(r[2], r[3], subsampling)
     dev = img.device
     lib = _lib.load()
     host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
-    cap = lib.ciaosr_jpeg_tiles_capacity_bytes(host_rects, n, sub)
-    nbytes = lib.ciaosr_jpeg_tiles_workspace_bytes(host_rects, n, sub, mcus)
+    opt = 'opt_' if optimize else ''
+    cap = getattr(lib, f'ciaosr_jpeg_{opt}tiles_capacity_bytes')(host_rects, n, sub)
+    nbytes = getattr(lib, f'ciaosr_jpeg_{opt}tiles_workspace_bytes')(host_rects, n, sub, mcus)
     if cap == 0 or nbytes == 0:
         raise CiaoSRHipError(f'encode_jpeg_tiles: unsupported geometry ({n} rects, mcus_per_chunk={mcus})')
     ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
     if out is None:
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    _lib.call('ciaosr_jpeg_encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, quality, sub,
+    offs = torch.empty(lib.ciaosr_jpeg_opt_result_bytes(n) // 8 if optimize else n + 1, dtype=torch.int64, device=dev)
+    _lib.call(f'ciaosr_jpeg_{opt}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, quality, sub,
               mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
               C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     return out, offs
 
 
-def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
     """The entropy-coded scans of many crops (y0, x0, h, w) of one device image, from ONE set of launches -> list of bytes; scan k is
-    byte for byte `encode_scan(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call: the offsets table, then the bytes."""
-    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk)
-    o = offs.cpu().tolist()                                 # copy 1: the offsets
+    byte for byte `encode_scan(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call: the offsets table, then the bytes.
+    `optimize=True` -> (scans, tables): tables[k] holds the four (counts, symbols) pairs that scan k is coded with; the first copy
+    brings the offsets and the tables."""
+    rects = list(rects)
+    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize)
+    tables = None
+    if optimize:
+        o, tables = split_result(offs.cpu(), len(rects))             # copy 1: the offsets and the tables
+    else:
+        o = offs.cpu().tolist()                             # copy 1: the offsets
     raw = memoryview(out[:o[-1]].cpu().numpy())             # copy 2: the scans
-    return [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
+    scans = [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
+    return (scans, tables) if optimize else scans
 
 
-def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
     """The entropy-coded scan of the image, stuffed and padded (the file between the SOS header and EOI), made on the device -> bytes.
-    Synchronises twice: size, then bytes."""
+    Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes."""
+    if check_optimize(optimize):
+        h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
+        scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=True)
+        return scans[0], tables[0]
     h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')
     dev = img.device
     lib = _lib.load()
@@ -151,26 +223,35 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the scan
 
 
-def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
     """JPEG file (bytes) of a uint8 [H, W, 3] device image, byte for byte `PIL.Image.save(format='JPEG', quality=quality,
     subsampling=0 or 2)` of the same pixels; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
-    larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it."""
-    scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
-    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling) + scan + EOI
+    larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it.
+    `optimize=True`: byte for byte `PIL.Image.save(..., optimize=True)`: Huffman tables made for this file on the device."""
+    tables = None
+    if check_optimize(optimize):
+        scan, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=True)
+    else:
+        scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
+    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, tables) + scan + EOI
 
 
-def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0):
+def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
     """JPEG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] device image, coded together: file k
     is byte for byte `encode_jpeg(img[y0:y0 + h, x0:x0 + w], ...)`.  The rects may overlap.  A bad rect, quality or subsampling is a
-    ValueError before any device work; two synchronising copies per call."""
+    ValueError before any device work; two synchronising copies per call.  `optimize=True`: every file with its own Huffman tables,
+    byte for byte Pillow's `optimize=True` file of the crop; still ten launches and two copies whatever the number of crops."""
     rects = list(rects)
+    if check_optimize(optimize):
+        scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=True)
+        return [header(int(r[2]), int(r[3]), quality, subsampling, t) + s + EOI for r, s, t in zip(rects, scans, tables)]
     scans = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
     return [header(int(r[2]), int(r[3]), quality, subsampling) + s + EOI for r, s in zip(rects, scans)]
 
 
-def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr'):
+def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr', optimize=False):
     """`imageio.imwrite` as JPEG for an image that is already on the device: encode there, write the file here."""
-    data = encode_jpeg(img_u8_hwc, quality, subsampling, order)
+    data = encode_jpeg(img_u8_hwc, quality, subsampling, order, optimize=optimize)
     os.makedirs(os.path.dirname(os.path.abspath(path)) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)

@@ -858,6 +858,38 @@ size_t ciaosr_jpeg_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, 
 int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
                                 int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                 unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+/* The same files with OPTIMISED Huffman tables (Pillow's optimize=True, libjpeg's optimize_coding): everything up to the
+ * quantised coefficients and the symbols of the scan is as above; the four Huffman tables are derived per crop from the histograms
+ * of the symbols its scan emits (dummy blocks count; Cb and Cr share two tables), by libjpeg's rule with its tie-breaks and its
+ * limiting to 16 bits.  Ten launches per call whatever the number of tiles -- the eight above with jpeg_hist and jpeg_tables between
+ * the coefficients and the code lengths -- and one memset of the histograms on `stream`.
+ * `result` (DEVICE, 8-byte aligned, ciaosr_jpeg_opt_result_bytes(n_tiles) = 8 (n_tiles + 1) + 1088 n_tiles bytes) receives BOTH the
+ * offsets and the tables, so that the host still reads twice per call (result, then the scans):
+ *   bytes [0, 8 (n_tiles + 1))            unsigned long long tile_offs[n_tiles + 1], as above
+ *   then per tile t, per table k = 0..3   one record of CIAOSR_JPEG_DHT_RECORD_BYTES = 272 bytes at 8 (n_tiles + 1) + 272 (4 t + k):
+ *                                         16 bytes: the number of codes of length 1..16; 256 bytes: the symbols in code order, of which
+ *                                         the first sum(counts) are valid, the rest 0.
+ * k is the file's order of DHT segments: 0 DC luma (0x00), 1 AC luma (0x10), 2 DC chroma (0x01), 3 AC chroma (0x11); a segment's
+ * payload is its class/id byte, the 16 counts and exactly sum(counts) symbols.  ciaosr_jpeg_opt_encode_u8 is the call for ONE rect
+ * (0, 0, H, W): its result holds tile_offs[2] = {0, total} and four records, 16 + 1088 bytes.
+ * Sizes: with arbitrary codes of up to 16 bits a block takes at most 16 + 11 bits of DC and 63 x (16 + 10) bits of AC = 1665 bits (the
+ * Annex K codes: 1658), so the capacity functions below return sum over the crops of 2 x ceil(1665 x blocks / 8) and the workspace
+ * holds ceil(1665 x blocks / 8) bytes of unstuffed stream per crop, 4 KB of histograms and 2176 bytes of code tables per tile on top
+ * of the rest.  A crop whose scan has 64 x blocks >= 1 000 000 000 (all components, dummy blocks included) is refused: the size
+ * functions return 0, the calls CIAOSR_ERR_UNSUPPORTED before any launch (libjpeg's search never selects a larger frequency; below
+ * the limit 32-bit counters suffice).  Every other refusal is as above. */
+#define CIAOSR_JPEG_DHT_RECORD_BYTES 272
+size_t ciaosr_jpeg_opt_result_bytes(int n_tiles);
+size_t ciaosr_jpeg_opt_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_opt_capacity_bytes(int H, int W, int subsampling);
+int ciaosr_jpeg_opt_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
+                              int mcus_per_chunk, unsigned char* out, size_t out_capacity, void* result, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t ciaosr_jpeg_opt_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_opt_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int subsampling);
+int ciaosr_jpeg_opt_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                    int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
+                                    void* result, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

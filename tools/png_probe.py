@@ -27,6 +27,15 @@ device.  For images larger than one tile also the top-level tiles: (d) one `enco
 tile.  Wall time runs from the device image (after a synchronize) to the bytes on the host; the legs alternate in one process; kernel
 time by tag comes from `hip_ops.profile` in a round of its own.  The files of (a) and (b), and of (d) and (e), are compared byte for
 byte, and the sizes of the JPEG, device PNG and Pillow PNG files are recorded.
+
+    python tools/png_probe.py --leg jpeg-opt [--sizes 5424x8160 768x768] [--quality 90] [--tile 254] [--overlap 1] [--out FILE]
+
+times JPEG files with optimised Huffman tables (`optimize=True`) on the 'noisy' images and writes profiles/jpeg_opt.txt.  Per image and
+subsampling: (a) `encode_jpeg(optimize=True)`;  (b) the same call with `optimize=False`;  (c) the device-to-host copy followed by
+`PIL.Image.save(optimize=True)` into memory.  For images larger than one tile also the top-level tiles: (d) one
+`encode_jpeg_tiles(optimize=True)` call, (e) the same with `optimize=False`, (f) the copy followed by one optimised Pillow file per tile.
+Timing as for `--leg jpeg`, and the device legs once more alternating without the Pillow leg; the files of (a) and (c), and of (d) and (f), are compared byte for byte; the sizes of both modes and the
+kernel times by tag (jpeg_hist and jpeg_tables among them) are recorded.
 """
 import json
 import subprocess
@@ -219,36 +228,45 @@ def dzi_leg(args, say):
         f'({enc.cache.builds} scene builds), encode {res["encode_s"]:.3f} s, file writing {res["write_s"]:.3f} s')
 
 
-def jpeg_leg(args, say):
+def pil_file(img, fmt, **kw):
+    """The Pillow file (bytes) of a uint8 [H, W, 3] BGR device image: the copy to the host, then the encoder."""
     import io
     from PIL import Image
+    bio = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(img.cpu().numpy()[:, :, ::-1])).save(bio, format=fmt, **kw)
+    return bio.getvalue()
+
+
+def kernels(fn):
+    """One profiled call of fn: total kernel time, launches, and the time of every tag."""
     from ciaosr_amd import hip_ops
+    with hip_ops.profile():
+        fn()
+    prof = hip_ops.profile.results()
+    return (f'{sum(v["total_ms"] for v in prof.values()):.3f} ms in {sum(v["launches"] for v in prof.values())} launches: '
+            + ', '.join(f'{k} {v["total_ms"]:.3f}' for k, v in sorted(prof.items())))
+
+
+def run_legs(args, legs):
+    """{name: wall seconds of the timed rounds}; the legs alternate within every round."""
+    times = {k: [] for k in legs}
+    for r in range(args.warmup + args.rounds):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            if r >= args.warmup:
+                times[name].append(time.perf_counter() - t0)
+    return times
+
+
+def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
     dev = torch.device('cuda', torch.cuda.current_device())
 
-    def pil_file(img, fmt, **kw):
-        bio = io.BytesIO()
-        Image.fromarray(np.ascontiguousarray(img.cpu().numpy()[:, :, ::-1])).save(bio, format=fmt, **kw)
-        return bio.getvalue()
-
-    def kernels(fn):
-        with hip_ops.profile():
-            fn()
-        prof = hip_ops.profile.results()
-        return (f'{sum(v["total_ms"] for v in prof.values()):.3f} ms in {sum(v["launches"] for v in prof.values())} launches: '
-                + ', '.join(f'{k} {v["total_ms"]:.3f}' for k, v in sorted(prof.items())))
-
     def run(legs):
-        times = {k: [] for k in legs}
-        for r in range(args.warmup + args.rounds):
-            for name, fn in legs.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                fn()
-                if r >= args.warmup:
-                    times[name].append(time.perf_counter() - t0)
-        return times
+        return run_legs(args, legs)
 
     for size in args.sizes:
         h, w = (int(v) for v in size.split('x'))
@@ -288,9 +306,70 @@ def jpeg_leg(args, say):
             del img
 
 
+def jpeg_opt_leg(args, say):
+    import io
+    import PIL.ImageFile
+    from PIL import Image
+    from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
+    dev = torch.device('cuda', torch.cuda.current_device())
+    PIL.ImageFile.MAXBLOCK = 1 << 26          # Pillow codes an optimised file into one buffer and refuses what does not fit its default
+
+    def pil_tiles(img, rects, sub):
+        host = np.ascontiguousarray(img.cpu().numpy()[:, :, ::-1])
+        files = []
+        for y0, x0, hh, ww in rects:
+            bio = io.BytesIO()
+            Image.fromarray(host[y0:y0 + hh, x0:x0 + ww]).save(bio, format='JPEG', quality=args.quality, subsampling=SUBSAMPLINGS[sub], optimize=True)
+            files.append(bio.getvalue())
+        return files
+
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        rects = top_rects(h, w, args.tile, args.overlap)
+        img = make_image(h, w, 'noisy', dev)
+        torch.cuda.synchronize()
+        for sub in ('444', '420'):
+            legs = {'a': lambda: encode_jpeg(img, args.quality, sub, optimize=True), 'b': lambda: encode_jpeg(img, args.quality, sub),
+                    'c': lambda: pil_file(img, 'JPEG', quality=args.quality, subsampling=SUBSAMPLINGS[sub], optimize=True)}
+            times = run_legs(args, legs)
+            mine, plain, pil = legs['a'](), legs['b'](), legs['c']()
+            say(f'{h} x {w} noisy, quality {args.quality}, {sub}: optimised device file is Pillow\'s optimize=True file byte for byte: {mine == pil}; '
+                f'bytes optimised {len(mine)}, Annex K tables {len(plain)}, ratio {len(mine) / len(plain):.4f}')
+            say(f'  (a) encode_jpeg(optimize=True)         wall s: {stats(times["a"])}')
+            say(f'  (b) encode_jpeg(optimize=False)        wall s: {stats(times["b"])}')
+            say(f'  (c) copy to the host + PIL optimize    wall s: {stats(times["c"])}')
+            say(f'  ratios of the means: (a) / (b) {statistics.mean(times["a"]) / statistics.mean(times["b"]):.2f}x, '
+                f'(c) / (a) {statistics.mean(times["c"]) / statistics.mean(times["a"]):.2f}x')
+            # in the rotation above (a) runs right after the Pillow leg and its host buffers: the two device legs once more, by themselves
+            pair = run_legs(args, {k: legs[k] for k in ('a', 'b')})
+            say(f'  (a), (b) alternating without (c)       wall s: (a) {stats(pair["a"])}')
+            say(f'                                                 (b) {stats(pair["b"])}')
+            say(f'  (a) kernels: {kernels(legs["a"])}')
+            say(f'  (b) kernels: {kernels(legs["b"])}')
+            if len(rects) > 1:
+                legs = {'d': lambda: encode_jpeg_tiles(img, rects, args.quality, sub, optimize=True),
+                        'e': lambda: encode_jpeg_tiles(img, rects, args.quality, sub), 'f': lambda: pil_tiles(img, rects, sub)}
+                times = run_legs(args, legs)
+                one, plain, pil = legs['d'](), legs['e'](), legs['f']()
+                say(f'  top level at {args.tile}+{args.overlap}: {len(rects)} tiles; (d) and (f) byte for byte identical: {one == pil}; bytes of files '
+                    f'optimised {sum(len(f) for f in one)}, Annex K tables {sum(len(f) for f in plain)}, '
+                    f'ratio {sum(len(f) for f in one) / sum(len(f) for f in plain):.4f}')
+                say(f'  (d) encode_jpeg_tiles(optimize=True)   wall s: {stats(times["d"])}')
+                say(f'  (e) encode_jpeg_tiles(optimize=False)  wall s: {stats(times["e"])}')
+                say(f'  (f) copy + PIL optimize per tile       wall s: {stats(times["f"])}')
+                say(f'  ratios of the means: (d) / (e) {statistics.mean(times["d"]) / statistics.mean(times["e"]):.2f}x, '
+                    f'(f) / (d) {statistics.mean(times["f"]) / statistics.mean(times["d"]):.2f}x')
+                pair = run_legs(args, {k: legs[k] for k in ('d', 'e')})
+                say(f'  (d), (e) alternating without (f)       wall s: (d) {stats(pair["d"])}')
+                say(f'                                                 (e) {stats(pair["e"])}')
+                say(f'  (d) kernels: {kernels(legs["d"])}')
+                say(f'  (e) kernels: {kernels(legs["e"])}')
+        del img
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -310,9 +389,11 @@ def main(argv=None):
     if args.worker:
         return serve()
     tiles = args.leg == 'tiles'
-    jpeg = args.leg == 'jpeg'
+    jpeg = args.leg in ('jpeg', 'jpeg-opt')
+    if args.leg == 'jpeg-opt':
+        args.contents = ['noisy']
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['5424x8160', '768x768'])
-    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -327,8 +408,10 @@ def main(argv=None):
         f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, {os.cpu_count()} host CPUs visible')
     if tiles:
         tiles_leg(args, say)
-    if jpeg:
+    if args.leg == 'jpeg':
         jpeg_leg(args, say)
+    if args.leg == 'jpeg-opt':
+        jpeg_opt_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
         for size in ([] if tiles or jpeg else args.sizes):
             h, w = (int(v) for v in size.split('x'))
