@@ -231,6 +231,13 @@ SIGNATURES = {
     'ciaosr_jpeg_opt_tiles_workspace_bytes': (_S, [_P, _I, _I, _I]),
     'ciaosr_jpeg_opt_tiles_capacity_bytes': (_S, [_P, _I, _I]),
     'ciaosr_jpeg_opt_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_jpeg_prog_result_bytes': (_S, [_I]),
+    'ciaosr_jpeg_prog_workspace_bytes': (_S, [_I, _I, _I, _I]),
+    'ciaosr_jpeg_prog_capacity_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_jpeg_prog_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_jpeg_prog_tiles_workspace_bytes': (_S, [_P, _I, _I, _I]),
+    'ciaosr_jpeg_prog_tiles_capacity_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_jpeg_prog_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
 }
 
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)

@@ -11,6 +11,11 @@ pyramid level, pyramid.py) in one set of launches; each file is byte for byte th
 four Huffman tables derived per file from the histograms of its own symbols.  The device counts the symbols, makes the tables by
 libjpeg's rule and codes with them; the tables come back as DHT records in the buffer that holds the sizes, so a call still
 synchronises twice, and `header(..., tables=)` writes them into the file's four DHT segments.
+
+`progressive=True` writes Pillow's `progressive=True` files (csrc/jpeg_prog_u8.hip): the same coefficients in the ten
+scans of libjpeg's progressive script, every scan with a table made from its own symbols -- Pillow writes the same bytes with and
+without `optimize=True`, so `optimize` does not matter then.  The device returns the ten scans of every crop and their ten tables in
+the same two copies; `assemble_progressive` writes the SOF2 header and the DHT and SOS headers between them.
 """
 import ctypes as C
 import os
@@ -81,6 +86,20 @@ def check_optimize(optimize):
     return optimize
 
 
+# progressive files: the ten scans (component: None = Y, Cb, Cr interleaved, else 0 Y / 1 Cb / 2 Cr; Ss, Se, Ah, Al), Cr before Cb ...
+SCAN_SCRIPT = ((None, 0, 0, 0, 1), (0, 1, 5, 0, 2), (2, 1, 63, 0, 1), (1, 1, 63, 0, 1), (0, 6, 63, 0, 2), (0, 1, 63, 2, 1),
+               (None, 0, 0, 1, 0), (2, 1, 63, 1, 0), (1, 1, 63, 1, 0), (0, 1, 63, 1, 0))
+# ... and class << 4 | id of the ten DHT segments in the file's order: two in front of scan 1, one in front of every AC scan
+PROGRESSIVE_TABLE_IDS = (0x00, 0x01, 0x10, 0x11, 0x11, 0x10, 0x10, 0x11, 0x11, 0x10)
+
+
+def check_progressive(progressive):
+    """`progressive` is a bool; ValueError otherwise (before any device work)."""
+    if not isinstance(progressive, bool):
+        raise ValueError(f'progressive is True or False, got {progressive!r}')
+    return progressive
+
+
 def scan_block_count(h, w, subsampling):
     """Blocks of the scan of an h x w image: all components, the dummy blocks of 4:2:0 included."""
     if subsampling == '420':
@@ -103,6 +122,54 @@ def quant_tables(quality):
     return tuple(tuple(min(max((b * s + 50) // 100, 1), 255) for b in base) for base in (BASE_LUMA, BASE_CHROMA))
 
 
+def _frame(h, w, quality, subsampling, sof):
+    """SOI, APP0, the two DQT segments and the frame header under the marker `sof`."""
+    parts = [b'\xff\xd8', b'\xff\xe0', struct.pack('>H5sBBBHHBB', 16, b'JFIF\0', 1, 1, 0, 1, 1, 0, 0)]
+    for k, q in enumerate(quant_tables(quality)):
+        parts += [b'\xff\xdb', struct.pack('>HB', 67, k), bytes(q[i] for i in ZIGZAG)]
+    parts += [sof, struct.pack('>HBHHB', 17, 8, h, w, 3), bytes((1, 0x22 if subsampling == '420' else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))]
+    return b''.join(parts)
+
+
+def progressive_header(h, w, quality, subsampling):
+    """A progressive file up to its first scan's DHT segments: SOI, APP0, two DQT, SOF2 (SOF0's payload)."""
+    quality, _ = check_params(quality, subsampling)
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
+    return _frame(h, w, quality, subsampling, b'\xff\xc2')
+
+
+def scan_header(s, tables):
+    """What a progressive file holds in front of the entropy-coded data of scan s = 0..9: the DHT segments of the tables the scan is
+    coded with (`tables`: the file's ten (counts, symbols) pairs in the order of PROGRESSIVE_TABLE_IDS), then the SOS header."""
+    comp, ss, se, ah, al = SCAN_SCRIPT[s]
+    if comp is None:
+        slots = (0, 1) if ah == 0 else ()
+        selectors = (1, 0x00, 2, 0x10, 3, 0x10) if ah == 0 else (1, 0x00, 2, 0x00, 3, 0x00)
+    else:
+        slots = (s + 1 if s < 6 else s,)                    # scan 7 (s = 6) has no table
+        selectors = (comp + 1, 0 if comp == 0 else 1)
+    parts = []
+    for k in slots:
+        counts, vals = tables[k]
+        if len(counts) != 16 or len(vals) != sum(counts) or not 1 <= len(vals) <= 256:
+            raise ValueError('tables: (16 counts, sum(counts) symbols) pairs')
+        parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), PROGRESSIVE_TABLE_IDS[k]), bytes(counts), bytes(vals)]
+    n = len(selectors) // 2
+    parts += [b'\xff\xda', struct.pack('>HB', 6 + 2 * n, n), bytes(selectors), bytes((ss, se, (ah << 4) | al))]
+    return b''.join(parts)
+
+
+def assemble_progressive(h, w, quality, subsampling, scans, tables):
+    """The progressive file of an h x w image from its ten entropy-coded scans and its ten tables."""
+    if len(scans) != len(SCAN_SCRIPT) or len(tables) != len(PROGRESSIVE_TABLE_IDS):
+        raise ValueError('a progressive file has ten scans and ten tables')
+    parts = [progressive_header(h, w, quality, subsampling)]
+    for s, data in enumerate(scans):
+        parts += [scan_header(s, tables), data]
+    return b''.join(parts) + EOI
+
+
 def header(h, w, quality, subsampling, tables=None):
     """The file from SOI up to and including the SOS header, as Pillow writes it for an h x w RGB image.  `tables`: four (counts,
     symbols) pairs in the file's order (DC luma, AC luma, DC chroma, AC chroma) for the DHT segments of an optimised file -- 16 counts
@@ -116,10 +183,7 @@ def header(h, w, quality, subsampling, tables=None):
         huffman = tuple((tc_th, c, v) for tc_th, (c, v) in zip(TABLE_IDS, tables))
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
-    parts = [b'\xff\xd8', b'\xff\xe0', struct.pack('>H5sBBBHHBB', 16, b'JFIF\0', 1, 1, 0, 1, 1, 0, 0)]
-    for k, q in enumerate(quant_tables(quality)):
-        parts += [b'\xff\xdb', struct.pack('>HB', 67, k), bytes(q[i] for i in ZIGZAG)]
-    parts += [b'\xff\xc0', struct.pack('>HBHHB', 17, 8, h, w, 3), bytes((1, 0x22 if subsampling == '420' else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))]
+    parts = [_frame(h, w, quality, subsampling, b'\xff\xc0')]
     for tc_th, bits, vals in huffman:
         parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), tc_th), bytes(bits), bytes(vals)]
     parts += [b'\xff\xda', struct.pack('>HB', 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3f, 0))]
@@ -152,23 +216,40 @@ def split_result(result, n):
     return offsets, [tables[4 * k:4 * k + 4] for k in range(n)]
 
 
-def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None, optimize=False):
+def split_progressive_result(result, n):
+    """The host copy of a progressive call's result -> (offsets [10 n + 1], tables): scan s of crop k lies at offsets[10 k + s] ..
+    offsets[10 k + s + 1], tables[k] holds crop k's ten (counts, symbols) pairs in the order of PROGRESSIVE_TABLE_IDS."""
+    raw = bytes(memoryview(result.numpy()).cast('B')) if isinstance(result, torch.Tensor) else bytes(result)
+    ns = len(SCAN_SCRIPT)
+    offsets = list(struct.unpack(f'<{ns * n + 1}q', raw[:8 * (ns * n + 1)]))
+    tables = []
+    for k in range(ns * n):
+        rec = raw[8 * (ns * n + 1) + DHT_RECORD_BYTES * k:8 * (ns * n + 1) + DHT_RECORD_BYTES * (k + 1)]
+        tables.append((tuple(rec[:16]), tuple(rec[16:16 + sum(rec[:16])])))
+    return offsets, [tables[ns * k:ns * k + ns] for k in range(n)]
+
+
+def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None, optimize=False,
+                        progressive=False):
     """ciaosr_jpeg_encode_tiles_u8 on the current stream, no synchronisation -> (scans uint8 [capacity], offsets int64 [n + 1]) on the
     device: crop k's entropy-coded scan is scans[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps.  `out`, `capacity`: a buffer of
     the caller's and the size to declare for it (default: `ciaosr_jpeg_tiles_capacity_bytes`, the worst case).
     `optimize=True`: ciaosr_jpeg_opt_encode_tiles_u8 -> (scans, result int64 [n + 1 + 136 n]): the offsets, then the crops' DHT records
-    (`split_result` takes the host copy apart); the default capacity is `ciaosr_jpeg_opt_tiles_capacity_bytes`."""
+    (`split_result` takes the host copy apart); the default capacity is `ciaosr_jpeg_opt_tiles_capacity_bytes`.
+    `progressive=True` (whatever `optimize` is): ciaosr_jpeg_prog_encode_tiles_u8 -> (scans, result int64 [10 n + 1 + 340 n]): the
+    offsets of the crops' ten scans each, then their ten DHT records each (`split_progressive_result`)."""
     check_optimize(optimize)
+    check_progressive(progressive)
     h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
     rects = check_rects(rects, h, w)
     n = len(rects)
-    if optimize:
+    if optimize or progressive:
         for r in rects:
             check_frequency_limit(r[2], r[3], subsampling)
     dev = img.device
     lib = _lib.load()
     host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
-    opt = 'opt_' if optimize else ''
+    opt = 'prog_' if progressive else ('opt_' if optimize else '')
     cap = getattr(lib, f'ciaosr_jpeg_{opt}tiles_capacity_bytes')(host_rects, n, sub)
     nbytes = getattr(lib, f'ciaosr_jpeg_{opt}tiles_workspace_bytes')(host_rects, n, sub, mcus)
     if cap == 0 or nbytes == 0:
@@ -176,20 +257,27 @@ def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', 
     ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
     if out is None:
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    offs = torch.empty(lib.ciaosr_jpeg_opt_result_bytes(n) // 8 if optimize else n + 1, dtype=torch.int64, device=dev)
+    words = getattr(lib, f'ciaosr_jpeg_{opt}result_bytes')(n) // 8 if opt else n + 1
+    offs = torch.empty(words, dtype=torch.int64, device=dev)
     _lib.call(f'ciaosr_jpeg_{opt}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, quality, sub,
               mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
               C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     return out, offs
 
 
-def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
+def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """The entropy-coded scans of many crops (y0, x0, h, w) of one device image, from ONE set of launches -> list of bytes; scan k is
     byte for byte `encode_scan(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call: the offsets table, then the bytes.
     `optimize=True` -> (scans, tables): tables[k] holds the four (counts, symbols) pairs that scan k is coded with; the first copy
-    brings the offsets and the tables."""
+    brings the offsets and the tables.  `progressive=True` -> (scans, tables): scans[k] holds crop k's TEN scans, tables[k] its ten
+    tables, as `assemble_progressive` takes them."""
     rects = list(rects)
-    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize)
+    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=progressive)
+    if progressive:
+        ns = len(SCAN_SCRIPT)
+        o, tables = split_progressive_result(offs.cpu(), len(rects))   # copy 1: the offsets and the tables
+        raw = memoryview(out[:o[-1]].cpu().numpy())                     # copy 2: the scans
+        return [[bytes(raw[o[ns * k + s]:o[ns * k + s + 1]]) for s in range(ns)] for k in range(len(rects))], tables
     tables = None
     if optimize:
         o, tables = split_result(offs.cpu(), len(rects))             # copy 1: the offsets and the tables
@@ -200,10 +288,16 @@ def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_pe
     return (scans, tables) if optimize else scans
 
 
-def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
+def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """The entropy-coded scan of the image, stuffed and padded (the file between the SOS header and EOI), made on the device -> bytes.
-    Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes."""
-    if check_optimize(optimize):
+    Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes.
+    `progressive=True` -> (the file's ten scans, its ten tables)."""
+    check_optimize(optimize)
+    if check_progressive(progressive):
+        h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
+        scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
+        return scans[0], tables[0]
+    if optimize:
         h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
         scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=True)
         return scans[0], tables[0]
@@ -223,35 +317,45 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the scan
 
 
-def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
+def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """JPEG file (bytes) of a uint8 [H, W, 3] device image, byte for byte `PIL.Image.save(format='JPEG', quality=quality,
     subsampling=0 or 2)` of the same pixels; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
     larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it.
-    `optimize=True`: byte for byte `PIL.Image.save(..., optimize=True)`: Huffman tables made for this file on the device."""
+    `optimize=True`: byte for byte `PIL.Image.save(..., optimize=True)`: Huffman tables made for this file on the device.
+    `progressive=True`: byte for byte `PIL.Image.save(..., progressive=True)`, whatever `optimize` is."""
     tables = None
-    if check_optimize(optimize):
+    check_optimize(optimize)
+    if check_progressive(progressive):
+        scans, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
+        return assemble_progressive(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, scans, tables)
+    if optimize:
         scan, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=True)
     else:
         scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
     return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, tables) + scan + EOI
 
 
-def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False):
+def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """JPEG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] device image, coded together: file k
     is byte for byte `encode_jpeg(img[y0:y0 + h, x0:x0 + w], ...)`.  The rects may overlap.  A bad rect, quality or subsampling is a
     ValueError before any device work; two synchronising copies per call.  `optimize=True`: every file with its own Huffman tables,
-    byte for byte Pillow's `optimize=True` file of the crop; still ten launches and two copies whatever the number of crops."""
+    byte for byte Pillow's `optimize=True` file of the crop; still ten launches and two copies whatever the number of crops.
+    `progressive=True`: every file Pillow's `progressive=True` file of the crop; thirteen launches and two copies."""
     rects = list(rects)
-    if check_optimize(optimize):
+    check_optimize(optimize)
+    if check_progressive(progressive):
+        scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
+        return [assemble_progressive(int(r[2]), int(r[3]), quality, subsampling, s, t) for r, s, t in zip(rects, scans, tables)]
+    if optimize:
         scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=True)
         return [header(int(r[2]), int(r[3]), quality, subsampling, t) + s + EOI for r, s, t in zip(rects, scans, tables)]
     scans = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
     return [header(int(r[2]), int(r[3]), quality, subsampling) + s + EOI for r, s in zip(rects, scans)]
 
 
-def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr', optimize=False):
+def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr', optimize=False, progressive=False):
     """`imageio.imwrite` as JPEG for an image that is already on the device: encode there, write the file here."""
-    data = encode_jpeg(img_u8_hwc, quality, subsampling, order, optimize=optimize)
+    data = encode_jpeg(img_u8_hwc, quality, subsampling, order, optimize=optimize, progressive=progressive)
     os.makedirs(os.path.dirname(os.path.abspath(path)) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)

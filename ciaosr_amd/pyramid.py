@@ -70,15 +70,18 @@ def dzi_manifest(height, width, tile_size=254, overlap=1, fmt='png'):
             f'<Size Width="{int(width)}" Height="{int(height)}"/></Image>')
 
 
-def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90, subsampling='444', optimize=False):
+def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90, subsampling='444', optimize=False,
+                 progressive=False):
     """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
     returns them): one `encode_png_tiles` call per level, or for `fmt='jpg'` one `encode_jpeg_tiles` call with `quality` and
-    `subsampling` (`optimize=True`: every tile with Huffman tables of its own).  -> dict(files, bytes, encode_s, write_s); the
-    manifest counts as a file."""
+    `subsampling` (`optimize=True`: every tile with Huffman tables of its own; `progressive=True`: every tile a progressive file).
+    -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
     if _check_format(fmt) == 'jpg':
-        from .jpeg_hip import check_optimize, check_params, encode_jpeg_tiles
+        from .jpeg_hip import check_optimize, check_params, check_progressive, encode_jpeg_tiles
         check_params(quality, subsampling)
         coding = dict(optimize=True) if check_optimize(optimize) else {}       # without it encode_jpeg_tiles is called as before
+        if check_progressive(progressive):
+            coding['progressive'] = True
 
         def encode(img, rects):
             return encode_jpeg_tiles(img, rects, quality=quality, subsampling=subsampling, order=order, **coding)
@@ -113,23 +116,26 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
 
 
 def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90,
-              subsampling='444', optimize=False):
+              subsampling='444', optimize=False, progressive=False):
     """`<out_dir>/<name>.dzi` and `<out_dir>/<name>_files/<level>/<col>_<row>.png` of the `size` / `scale` render of `enc` (an
     `encode` result of `model`).  `order`: the byte order of the rendered images, 'bgr' as `render_pyramid` makes them.  `fmt='jpg'`:
     `.jpg` tiles at `quality` (1..100) and `subsampling` ('444' or '420'), byte for byte Pillow's files of the same pixels; with
-    `optimize=True` Pillow's `optimize=True` files (per-tile Huffman tables; the manifest is the same).
+    `optimize=True` Pillow's `optimize=True` files (per-tile Huffman tables; the manifest is the same), with `progressive=True` Pillow's
+    `progressive=True` files (the manifest is the same).
     -> dict: levels [(H_l, W_l)], model_levels (the levels rendered by the model; the ones below are Pillow-exact bicubic resizes of
     the smallest of them), files, bytes, and the seconds spent in render_s (to the last launch, not synchronised), encode_s, write_s."""
     _check_tiling(tile_size, overlap)
     if _check_format(fmt) == 'jpg':
-        from .jpeg_hip import check_optimize, check_params
+        from .jpeg_hip import check_optimize, check_params, check_progressive
         check_params(quality, subsampling)
         check_optimize(optimize)
+        check_progressive(progressive)
     t0 = time.perf_counter()
     levels = model.render_pyramid(enc, size=size, scale=scale)
     render_s = time.perf_counter() - t0
     h, w = enc.x.shape[-2:]
     sizes = [(im.shape[0], im.shape[1]) for im in levels]
-    res = write_levels(levels, out_dir, name, tile_size, overlap, order, fmt, quality, subsampling, optimize)
+    coding = dict(progressive=True) if progressive else {}                     # without it write_levels is called as before
+    res = write_levels(levels, out_dir, name, tile_size, overlap, order, fmt, quality, subsampling, optimize, **coding)
     res.update(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w], render_s=render_s)
     return res

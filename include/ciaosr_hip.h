@@ -890,6 +890,36 @@ size_t ciaosr_jpeg_opt_tiles_capacity_bytes(const int* rects /*host*/, int n_til
 int ciaosr_jpeg_opt_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
                                     int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                     void* result, void* workspace, size_t workspace_bytes, void* stream);
+/* PROGRESSIVE files (Pillow's progressive=True, with or without optimize=True; csrc/jpeg_prog_u8.hip): the same
+ * quantised coefficients, coded by libjpeg's progressive entropy coder in the ten scans of its default script for YCbCr, every scan
+ * with a Huffman table made from its own symbols by the rule above.  The device makes the ten entropy-coded scans of every crop, each
+ * stuffed and padded on its own; the host writes SOI, APP0, two DQT and SOF2, then in front of every scan its DHT segments and its
+ * SOS header, and EOI behind the last.  The argument lists are those of the ciaosr_jpeg_opt_* entries.
+ * `result` (DEVICE, 8-byte aligned, ciaosr_jpeg_prog_result_bytes(n_tiles) = 8 (10 n_tiles + 1) + 2720 n_tiles bytes):
+ *   bytes [0, 8 (10 n_tiles + 1))         unsigned long long offs[10 n_tiles + 1]: scan s = 0..9 of crop t is
+ *                                         out[offs[10 t + s] : offs[10 t + s + 1]]; offs[0] = 0, no gaps
+ *   then per crop t, per table k = 0..9   one record of CIAOSR_JPEG_DHT_RECORD_BYTES as above, in the file's order of DHT segments:
+ *                                         DC 0 (0x00) and DC 1 (0x01) in front of scan 1, then the AC table of scans 2, 3, 4, 5, 6,
+ *                                         8, 9, 10 (0x10 for a luma scan, 0x11 for a chroma scan; scan 7 has none).
+ * Scans: 1 DC of Y, Cb, Cr interleaved (Al 1); 2 Y 1..5 (Al 2); 3 Cr 1..63 (Al 1); 4 Cb 1..63 (Al 1); 5 Y 6..63 (Al 2);
+ * 6 Y 1..63 (Ah 2, Al 1); 7 DC refinement of all three (Ah 1, Al 0); 8 Cr, 9 Cb, 10 Y 1..63 (Ah 1, Al 0).
+ * Sizes: with arbitrary codes of up to 16 bits a block takes at most 27 bits in scan 1, 1 bit in scan 7, 26 x (Se - Ss + 1) + 60 bits in
+ * a first AC scan and 17 x 63 + 60 in an AC refinement; ciaosr_jpeg_prog_capacity_bytes is twice the sum over the ten scans of
+ * ceil(bits x blocks of the scan / 8) (DC scans: all blocks, dummy ones included; AC scans: the component's real blocks), so that
+ * nothing can be written at or beyond out_capacity.  The workspace holds that sum once more, the coefficients, and about 29 bytes per
+ * block and scan.  Thirteen launches and one memset on `stream` per call whatever the number of crops.  Refusals as above, the limit of
+ * 64 x blocks < 1 000 000 000 per crop included. */
+size_t ciaosr_jpeg_prog_result_bytes(int n_tiles);
+size_t ciaosr_jpeg_prog_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_prog_capacity_bytes(int H, int W, int subsampling);
+int ciaosr_jpeg_prog_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
+                               int mcus_per_chunk, unsigned char* out, size_t out_capacity, void* result, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t ciaosr_jpeg_prog_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int subsampling, int mcus_per_chunk);
+size_t ciaosr_jpeg_prog_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int subsampling);
+int ciaosr_jpeg_prog_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                     int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
+                                     void* result, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,16 @@ subsampling: (a) `encode_jpeg(optimize=True)`;  (b) the same call with `optimize
 `encode_jpeg_tiles(optimize=True)` call, (e) the same with `optimize=False`, (f) the copy followed by one optimised Pillow file per tile.
 Timing as for `--leg jpeg`, and the device legs once more alternating without the Pillow leg; the files of (a) and (c), and of (d) and (f), are compared byte for byte; the sizes of both modes and the
 kernel times by tag (jpeg_hist and jpeg_tables among them) are recorded.
+
+    python tools/png_probe.py --leg jpeg-prog [--sizes 5424x8160 768x768] [--quality 90] [--tile 254] [--overlap 1] [--out FILE]
+
+times progressive JPEG files (`progressive=True`) and writes profiles/jpeg_prog.txt.  Per image -- the 'noisy' image of every size and,
+for sizes larger than one tile, a flat image of the same size, whose every AC scan is ONE chain of EOB runs that a single lane walks
+(the worst case of prog_runs) -- and subsampling: (a) `encode_jpeg(progressive=True)`;  (b) `encode_jpeg(optimize=True)`;  (c) the
+device-to-host copy followed by `PIL.Image.save(progressive=True)` into memory.  For the noisy image also the top-level tiles as one
+call: (d) `encode_jpeg_tiles(progressive=True)`, (e) `encode_jpeg_tiles(optimize=True)`, (f) the copy followed by one progressive Pillow
+file per tile.  Protocol as for `--leg jpeg-opt`; the files of (a) and (c), and of (d) and (f), are compared byte for byte; the sizes of
+the progressive and the optimised baseline files and the kernel times by tag (prog_runs among them) are recorded.
 """
 import json
 import subprocess
@@ -367,9 +377,67 @@ def jpeg_opt_leg(args, say):
         del img
 
 
+def jpeg_prog_leg(args, say):
+    import io
+    import PIL.ImageFile
+    from PIL import Image
+    from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
+    dev = torch.device('cuda', torch.cuda.current_device())
+    PIL.ImageFile.MAXBLOCK = 1 << 26          # Pillow codes a progressive file into one buffer and refuses what does not fit its default
+
+    def pil_tiles(img, rects, sub):
+        host = np.ascontiguousarray(img.cpu().numpy()[:, :, ::-1])
+        files = []
+        for y0, x0, hh, ww in rects:
+            bio = io.BytesIO()
+            Image.fromarray(host[y0:y0 + hh, x0:x0 + ww]).save(bio, format='JPEG', quality=args.quality, subsampling=SUBSAMPLINGS[sub], progressive=True)
+            files.append(bio.getvalue())
+        return files
+
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        rects = top_rects(h, w, args.tile, args.overlap)
+        for content in (['noisy', 'flat'] if len(rects) > 1 else ['noisy']):
+            img = torch.full((h, w, 3), 77, dtype=torch.uint8, device=dev) if content == 'flat' else make_image(h, w, 'noisy', dev)
+            torch.cuda.synchronize()
+            for sub in ('444', '420'):
+                legs = {'a': lambda: encode_jpeg(img, args.quality, sub, progressive=True), 'b': lambda: encode_jpeg(img, args.quality, sub, optimize=True),
+                        'c': lambda: pil_file(img, 'JPEG', quality=args.quality, subsampling=SUBSAMPLINGS[sub], progressive=True)}
+                times = run_legs(args, legs)
+                mine, base, pil = legs['a'](), legs['b'](), legs['c']()
+                say(f'{h} x {w} {content}, quality {args.quality}, {sub}: progressive device file is Pillow\'s progressive=True file byte for byte: '
+                    f'{mine == pil}; bytes progressive {len(mine)}, optimised baseline {len(base)}, ratio {len(mine) / len(base):.4f}')
+                say(f'  (a) encode_jpeg(progressive=True)      wall s: {stats(times["a"])}')
+                say(f'  (b) encode_jpeg(optimize=True)         wall s: {stats(times["b"])}')
+                say(f'  (c) copy to the host + PIL progressive wall s: {stats(times["c"])}')
+                say(f'  ratios of the means: (a) / (b) {statistics.mean(times["a"]) / statistics.mean(times["b"]):.2f}x, '
+                    f'(c) / (a) {statistics.mean(times["c"]) / statistics.mean(times["a"]):.2f}x')
+                pair = run_legs(args, {k: legs[k] for k in ('a', 'b')})
+                say(f'  (a), (b) alternating without (c)       wall s: (a) {stats(pair["a"])}')
+                say(f'                                                 (b) {stats(pair["b"])}')
+                say(f'  (a) kernels: {kernels(legs["a"])}')
+                say(f'  (b) kernels: {kernels(legs["b"])}')
+                if len(rects) > 1 and content == 'noisy':
+                    legs = {'d': lambda: encode_jpeg_tiles(img, rects, args.quality, sub, progressive=True),
+                            'e': lambda: encode_jpeg_tiles(img, rects, args.quality, sub, optimize=True), 'f': lambda: pil_tiles(img, rects, sub)}
+                    times = run_legs(args, legs)
+                    one, base, pil = legs['d'](), legs['e'](), legs['f']()
+                    say(f'  top level at {args.tile}+{args.overlap}: {len(rects)} tiles; (d) and (f) byte for byte identical: {one == pil}; bytes of files '
+                        f'progressive {sum(len(f) for f in one)}, optimised baseline {sum(len(f) for f in base)}, '
+                        f'ratio {sum(len(f) for f in one) / sum(len(f) for f in base):.4f}')
+                    say(f'  (d) encode_jpeg_tiles(progressive=True) wall s: {stats(times["d"])}')
+                    say(f'  (e) encode_jpeg_tiles(optimize=True)    wall s: {stats(times["e"])}')
+                    say(f'  (f) copy + PIL progressive per tile     wall s: {stats(times["f"])}')
+                    say(f'  ratios of the means: (d) / (e) {statistics.mean(times["d"]) / statistics.mean(times["e"]):.2f}x, '
+                        f'(f) / (d) {statistics.mean(times["f"]) / statistics.mean(times["d"]):.2f}x')
+                    say(f'  (d) kernels: {kernels(legs["d"])}')
+                    say(f'  (e) kernels: {kernels(legs["e"])}')
+            del img
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -389,11 +457,11 @@ def main(argv=None):
     if args.worker:
         return serve()
     tiles = args.leg == 'tiles'
-    jpeg = args.leg in ('jpeg', 'jpeg-opt')
-    if args.leg == 'jpeg-opt':
+    jpeg = args.leg in ('jpeg', 'jpeg-opt', 'jpeg-prog')
+    if args.leg in ('jpeg-opt', 'jpeg-prog'):
         args.contents = ['noisy']
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['5424x8160', '768x768'])
-    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -412,6 +480,8 @@ def main(argv=None):
         jpeg_leg(args, say)
     if args.leg == 'jpeg-opt':
         jpeg_opt_leg(args, say)
+    if args.leg == 'jpeg-prog':
+        jpeg_prog_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
         for size in ([] if tiles or jpeg else args.sizes):
             h, w = (int(v) for v in size.split('x'))

@@ -27,6 +27,8 @@ to --scale / --view outputs, which it does not change.  `--max-scale` then defau
 `--gpu-png`) and coded there (ciaosr_amd/jpeg_hip.py); the files are byte for byte what Pillow saves for the same pixels.
 `--jpeg-optimize` (only with --jpeg) gives every .jpg of the run Huffman tables of its own, made on the device: Pillow's `optimize=True`
 files, smaller, the same pixels; the manifest does not change.
+`--jpeg-progressive` (only with --jpeg) writes every .jpg of the run as a progressive file, coded on the device: Pillow's
+`progressive=True` files, the same pixels in ten scans from coarse to fine; the manifest does not change.
 """
 import argparse
 import os
@@ -58,6 +60,8 @@ def parse_args(argv=None):
     p.add_argument('--jpeg-subsampling', choices=['444', '420'], default='444', help='chroma subsampling of --jpeg (default 444)')
     p.add_argument('--jpeg-optimize', action='store_true',
                    help='with --jpeg: per-file Huffman tables made on the GPU, the files of Pillow\'s optimize=True (default off)')
+    p.add_argument('--jpeg-progressive', action='store_true',
+                   help='with --jpeg: progressive files coded on the GPU, the files of Pillow\'s progressive=True (default off)')
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
@@ -75,16 +79,21 @@ def parse_args(argv=None):
         p.error('--jpeg takes a quality in 1..100')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
+    if args.jpeg_progressive and args.jpeg is None:
+        p.error('--jpeg-progressive belongs to --jpeg')
     return args
 
 
 def output_format(args):
-    """What the flags ask the writers for: dict(fmt, ext) and, for JPEG, quality and subsampling, with --jpeg-optimize also optimize=True."""
+    """What the flags ask the writers for: dict(fmt, ext) and, for JPEG, quality and subsampling, with --jpeg-optimize also optimize=True, with
+    --jpeg-progressive also progressive=True."""
     if args.jpeg is None:
         return dict(fmt='png', ext='.png')
     form = dict(fmt='jpg', ext='.jpg', quality=args.jpeg, subsampling=args.jpeg_subsampling)
     if args.jpeg_optimize:
         form['optimize'] = True
+    if args.jpeg_progressive:
+        form['progressive'] = True
     return form
 
 
@@ -125,7 +134,7 @@ def main(argv=None):
     name = os.path.splitext(os.path.basename(args.image))[0]
     from ciaosr_amd.scene import Grid, View, view_matrix
     form = output_format(args)
-    coding = {k: form[k] for k in ('quality', 'subsampling', 'optimize') if k in form}
+    coding = {k: form[k] for k in ('quality', 'subsampling', 'optimize', 'progressive') if k in form}
     dzi_format = dict(fmt='jpg', **coding) if form['fmt'] == 'jpg' else {}           # without --jpeg write_dzi is called as before
     targets = [Grid(scale=s, window=args.window) for s in args.scale]
     paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}{form["ext"]}') for s in args.scale]
