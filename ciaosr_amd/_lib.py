@@ -207,6 +207,8 @@ SIGNATURES = {
     'ciaosr_tensor2img_u8': (_I, [_P, _I, _I, _P, _S, _P]),
     'ciaosr_psnr_ssim_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_psnr_ssim_u8': (_I, [_P, _S, _P, _S, _I, _I, _I, _I, _I, _P, _P, _S, _P]),
+    'ciaosr_niqe_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_niqe_moments_u8': (_I, [_P, _S, _I, _I, _I, _P, _P, _P, _P, _S, _P]),
     'ciaosr_png_rows_per_band': (_I, [_I, _I]),
     'ciaosr_png_filter_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _P, _P]),
     'ciaosr_deflate_huff_workspace_bytes': (_S, [_I]),

@@ -25,6 +25,17 @@ __device__ __forceinline__ float div_rn(float a, float b) {
     return a / b;
 }
 
+// Luma of the evaluation metrics (metrics_u8.hip, niqe_f32.hip), pixel packed b | g << 8 | r << 16:
+// mmcv.bgr2ycbcr(img / 255, y_only=True) * 255 in fp32, one rounding per operation
+__device__ __forceinline__ float y_of_bgr(unsigned int bgr) {
+    const float b = div_rn((float)(bgr & 255u), 255.0f);
+    const float g = div_rn((float)((bgr >> 8) & 255u), 255.0f);
+    const float r = div_rn((float)((bgr >> 16) & 255u), 255.0f);
+    float y = add_rn(add_rn(mul_rn(b, 24.966f), mul_rn(g, 128.553f)), mul_rn(r, 65.481f));
+    y = add_rn(y, 16.0f);
+    return mul_rn(div_rn(y, 255.0f), 255.0f);
+}
+
 // F.grid_sample(mode='nearest', align_corners=False) source index on an axis of n samples:
 // u = (c + 1) * (n / 2) - 0.5 (three roundings), idx = round-half-even(u).   (ciaosr_net.py:145)
 __device__ __forceinline__ int nearest_index(float c, int n) {

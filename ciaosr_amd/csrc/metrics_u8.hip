@@ -82,15 +82,7 @@ struct MetricsP {
     double* result;               // [3][4]
 };
 
-// mmcv.bgr2ycbcr(img / 255, y_only=True) * 255 in fp32, one rounding per operation
-__device__ __forceinline__ float y_of_bgr(unsigned int bgr) {
-    const float b = div_rn((float)(bgr & 255u), 255.0f);
-    const float g = div_rn((float)((bgr >> 8) & 255u), 255.0f);
-    const float r = div_rn((float)((bgr >> 16) & 255u), 255.0f);
-    float y = add_rn(add_rn(mul_rn(b, 24.966f), mul_rn(g, 128.553f)), mul_rn(r, 65.481f));
-    y = add_rn(y, 16.0f);
-    return mul_rn(div_rn(y, 255.0f), 255.0f);
-}
+// y_of_bgr (index_math.h): mmcv.bgr2ycbcr(img / 255, y_only=True) * 255 in fp32, shared with niqe_f32.hip
 
 // pixel (row, col) of the CROPPED image: the three bytes packed b | g << 8 | r << 16 (kY) or the byte of channel ch; 0 outside
 template <bool kY>

@@ -78,16 +78,49 @@ class BasicRestorer(nn.Module):
         (ciaosr_amd/png_hip.py) instead of `imageio.imwrite`; the files decode to the same pixels."""
         return bool(self.test_cfg is not None and self.test_cfg.get('gpu_png', False))
 
+    def niqe_params(self):
+        """`test_cfg.niqe_params` (an extension; default absent): the pristine NIQE model, an .npz path or a mapping
+        (ciaosr_amd/niqe_hip.py), loaded once.  With it 'NIQE' may stand in `test_cfg.metrics`; without it that name is the KeyError
+        of any unknown metric."""
+        src = self.test_cfg.get('niqe_params', None) if self.test_cfg is not None else None
+        if src is None:
+            return None
+        cached = self.__dict__.get('_niqe_loaded')
+        if cached is None or cached[0] is not src:
+            from . import niqe_hip
+            cached = self.__dict__['_niqe_loaded'] = (src, niqe_hip.load_params(src))
+        return cached[1]
+
+    def needs_gt(self):
+        """Whether `test_cfg.metrics` holds a metric that compares with a ground truth (every one but NIQE under `niqe_params`)."""
+        names = list(self.test_cfg.get('metrics', None) or []) if self.test_cfg is not None else []
+        return any(not (m == 'NIQE' and self.niqe_params() is not None) for m in names)
+
     def evaluate(self, output, gt, out_img=None):
         """PSNR/SSIM on uint8 BGR images as basic_restorer.py:101-124.  With `test_cfg.gpu_metrics` both tensors are quantised
         and compared on the device (`out_img`: the already quantised output, if the caller has it); the output must be there
-        -- no fallback -- and a GT on the host is moved."""
+        -- no fallback -- and a GT on the host is moved.  With `test_cfg.niqe_params`, 'NIQE' in `test_cfg.metrics` is the blind score
+        of the quantised output (Y channel, `test_cfg.crop_border`), always computed on the device; `gt` may then be None if no other
+        metric is asked for.  The result keeps the order of `test_cfg.metrics`."""
+        names = list(self.test_cfg.metrics)
+        params = self.niqe_params() if 'NIQE' in names else None
+        if params is None:
+            return self._evaluate_reference(names, output, gt, out_img)
+        from . import metrics_hip, niqe_hip
+        if out_img is None:
+            out_img = metrics_hip.tensor2img_u8(output)        # a host tensor raises CiaoSRHipError: NIQE has no host path
+        rest = [m for m in names if m != 'NIQE']
+        res = self._evaluate_reference(rest, output, gt, out_img) if rest else {}
+        res['NIQE'] = niqe_hip.niqe_u8(out_img, params, self.test_cfg.crop_border, 'y')
+        return {metric: res[metric] for metric in names}
+
+    def _evaluate_reference(self, names, output, gt, out_img=None):
         if self.gpu_metrics():
-            return self._evaluate_gpu(output, gt, out_img)
+            return self._evaluate_gpu(names, output, gt, out_img)
         crop_border = self.test_cfg.crop_border
         out_img, gt_img = metrics.tensor2img(output), metrics.tensor2img(gt)
         res = {}
-        for metric in self.test_cfg.metrics:
+        for metric in names:
             fn = self.allowed_metrics[metric]
             if 'convert_to' in self.test_cfg:
                 res[metric] = fn(out_img, gt_img, crop_border=crop_border, convert_to=self.test_cfg.convert_to)
@@ -95,9 +128,8 @@ class BasicRestorer(nn.Module):
                 res[metric] = fn(out_img, gt_img, crop_border)
         return res
 
-    def _evaluate_gpu(self, output, gt, out_img=None):
+    def _evaluate_gpu(self, names, output, gt, out_img=None):
         from . import metrics_hip
-        names = list(self.test_cfg.metrics)
         for metric in names:
             self.allowed_metrics[metric]                       # an unknown name fails as on the host path
         if not output.is_cuda:
@@ -561,7 +593,7 @@ class CiaoSR(BasicRestorer):
             from . import metrics_hip
             out_img = metrics_hip.tensor2img_u8(pred)              # quantised once, for the metrics and for the file
         if self.test_cfg is not None and self.test_cfg.get('metrics', None):
-            assert gt is not None, 'evaluation with metrics must have gt images.'
+            assert gt is not None or not self.needs_gt(), 'evaluation with metrics must have gt images.'
             results = dict(eval_result=self.evaluate(pred, gt, out_img))
         else:
             results = dict(lq=lq.cpu(), output=pred.cpu())

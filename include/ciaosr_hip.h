@@ -758,6 +758,22 @@ size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int co
 int ciaosr_psnr_ssim_u8(const unsigned char* a, size_t pitch_a, const unsigned char* b, size_t pitch_b, int H, int W, int crop_border,
                         int convert_to_y, int want, double* result, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- NIQE of an 8-bit image: the image work of niqe / niqe_core (mmedited/core/evaluation/metrics.py:340-532) -----------------------
+ * img [H][W][3] BGR bytes with a row pitch (>= 3 W).  Y = round_half_even(mmcv.bgr2ycbcr(img / 255, y_only=True) * 255) of the image
+ * without crop_border pixels on every side, cropped to whole 96x96 blocks; per scale (1, and 2 after MATLAB's antialiased bicubic
+ * imresize by 0.5) the MSCN map (x - mu) / (sqrt|filter(x^2) - mu^2| + 1) with `window` (49 doubles on the DEVICE, row-major 7x7,
+ * applied as scipy's convolve(mode='nearest')); per 96x96 / 48x48 block five maps -- the block and its products with itself rolled
+ * (np.roll, wrapping inside the block) by [0,1], [1,0], [1,1], [1,-1] -- each reduced to six sums.
+ * moments: doubles on the DEVICE, [scale 0..1][block][map 0..4][count of v < 0, sum v^2 over v < 0, count of v > 0, sum v^2 over
+ * v > 0, sum |v|, sum v^2]; blocks = floor((H - 2 crop) / 96) * floor((W - 2 crop) / 96) in the reference's order: block
+ * (row i, column j) at j * rows + i.  luma_out: optional fp32 [H - 2 crop][W - 2 crop], the rounded Y plane (NULL = not wanted).
+ * Maps and sums are fp64; five launches for any size, no atomics: bitwise reproducible, independent of the pitch.
+ * workspace: 256-byte aligned, ciaosr_niqe_workspace_bytes() (0 = unsupported geometry); fully rewritten by every call.
+ * CIAOSR_ERR_UNSUPPORTED: H or W > 65535, or no whole block after the crop. */
+size_t ciaosr_niqe_workspace_bytes(int H, int W, int crop_border);
+int ciaosr_niqe_moments_u8(const unsigned char* img, size_t pitch, int H, int W, int crop_border, const double* window,
+                           double* moments, float* luma_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- PNG encoding of 8-bit images (opt-in: test_cfg.gpu_png; replaces the host's PIL save on the --save-path / --out path) ---------
  * Two stages, separately callable, and their composition.  Nothing here searches for LZ77 matches: the coder emits literals and
  * end-of-block only.  Bands are coded independently, one workgroup each.  All byte offsets are 64-bit. */

@@ -29,6 +29,10 @@ to --scale / --view outputs, which it does not change.  `--max-scale` then defau
 files, smaller, the same pixels; the manifest does not change.
 `--jpeg-progressive` (only with --jpeg) writes every .jpg of the run as a progressive file, coded on the device: Pillow's
 `progressive=True` files, the same pixels in ten scans from coarse to fine; the manifest does not change.
+`--niqe PARAMS` scores every --scale and --view output with NIQE under the pristine model PARAMS (the reference's niqe_pris_params.npz;
+ciaosr_amd/niqe_hip.py): computed on the device from the 8-bit image, before any encoding, Y channel, no border cropped.  The values are
+printed and written to DIR/niqe.json as {file name: value}; an output too small for two 96x96 blocks gets null.  Pyramid tiles are not
+scored, and no output changes.
 """
 import argparse
 import os
@@ -65,6 +69,8 @@ def parse_args(argv=None):
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
+    p.add_argument('--niqe', default=None, metavar='PARAMS',
+                   help='score every --scale / --view output with NIQE on the GPU under the pristine model PARAMS (.npz); writes niqe.json')
     p.add_argument('--max-scale', type=float, default=None,
                    help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM; with --dzi at least its SCALE)')
     p.add_argument('--out', required=True, help='output directory')
@@ -145,7 +151,20 @@ def main(argv=None):
     gpu_png = model.gpu_png()
     as_u8 = gpu_png or form['fmt'] == 'jpg'
     outs = model.render_many(enc, targets, as_u8=as_u8) if targets else []           # one walk over the tile scenes for every output
+    scores = {}
+    if args.niqe and targets:
+        from ciaosr_amd import niqe_hip
+        from ciaosr_amd.metrics_hip import tensor2img_u8
+        params = niqe_hip.load_params(args.niqe)
     for path, out in zip(paths, outs):
+        if args.niqe:
+            img = out if as_u8 else tensor2img_u8(out)                 # the bytes the file holds (bitwise metrics.tensor2img)
+            try:
+                niqe_hip.geometry(img.shape[0], img.shape[1])
+                scores[os.path.basename(path)] = niqe_hip.niqe_u8(img, params)
+            except ValueError:                                         # fewer than two blocks (or fewer than two without a NaN)
+                scores[os.path.basename(path)] = None
+            print(f'{path}: NIQE {scores[os.path.basename(path)]}')
         if form['fmt'] == 'jpg':
             from ciaosr_amd.jpeg_hip import imwrite_gpu_jpeg
             imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR on the device
@@ -157,6 +176,11 @@ def main(argv=None):
         else:
             imwrite(metrics.tensor2img(out), path)
             print(f'{path}: {out.shape[-2]} x {out.shape[-1]}')
+    if args.niqe and targets:
+        import json
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, 'niqe.json'), 'w') as f:
+            json.dump(scores, f, indent=1)
     if args.dzi is not None:
         from ciaosr_amd.pyramid import write_dzi
         res = write_dzi(model, enc, args.out, name, scale=args.dzi, tile_size=args.dzi_tile, overlap=args.dzi_overlap, **dzi_format)

@@ -72,6 +72,9 @@ def parse_args(argv=None):
                    help='test_cfg.gpu_metrics = True: quantise and evaluate PSNR / SSIM on the GPU (default: on the host)')
     p.add_argument('--gpu-png', action='store_true',
                    help='test_cfg.gpu_png = True: --save-path images are quantised and PNG-encoded on the GPU (default: PIL on the host)')
+    p.add_argument('--niqe', default=None, metavar='PARAMS',
+                   help='test_cfg.niqe_params = PARAMS (the pristine model, niqe_pris_params.npz) and \'NIQE\' appended to test_cfg.metrics: '
+                        'the blind score of every output, computed on the GPU (default: not computed)')
     return p.parse_args(argv)
 
 
@@ -81,6 +84,10 @@ def apply_overrides(cfg, args):
         cfg.test_cfg['gpu_metrics'] = True
     if args.gpu_png:
         cfg.test_cfg['gpu_png'] = True
+    if args.niqe:
+        cfg.test_cfg['niqe_params'] = args.niqe
+        names = list(cfg.test_cfg.get('metrics', None) or [])
+        cfg.test_cfg['metrics'] = names if 'NIQE' in names else names + ['NIQE']
     return cfg
 
 
