@@ -220,6 +220,16 @@ SIGNATURES = {
     'ciaosr_png_tiles_workspace_bytes': (_S, [_P, _I, _I]),
     'ciaosr_png_tiles_capacity_bytes': (_S, [_P, _I, _I]),
     'ciaosr_png_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_tensor2img_bgra_u8': (_I, [_P, _P, _I, _I, _P, _S, _P]),
+    'ciaosr_pack_bgra_u8': (_I, [_P, _S, _P, _S, _I, _I, _P, _S, _P]),
+    'ciaosr_png_rgba_rows_per_band': (_I, [_I, _I]),
+    'ciaosr_png_rgba_filter_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'ciaosr_png_rgba_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_rgba_capacity_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_rgba_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_rgba_tiles_workspace_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_rgba_tiles_capacity_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_rgba_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
     'ciaosr_jpeg_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_jpeg_capacity_bytes': (_S, [_I, _I, _I]),
     'ciaosr_jpeg_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),

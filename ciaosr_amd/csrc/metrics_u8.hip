@@ -68,6 +68,57 @@ __global__ __launch_bounds__(kQThreads) void tensor2img_u8_kernel(QuantP p) {
     }
 }
 
+// RGBA: the colour bytes of item 0 and, as alpha, the integer luma of item 1's bytes.  The weights sum to 2^14, so a grey v, v, v is v.
+__device__ __forceinline__ unsigned int alpha_of_bgr(unsigned int b, unsigned int g, unsigned int r) {
+    return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
+}
+
+__device__ __forceinline__ void store_bgra(unsigned char* out, int x, unsigned int word, int vec) {
+    if (vec) {
+        reinterpret_cast<unsigned int*>(out)[x] = word;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[4 * (size_t)x + k] = (unsigned char)(word >> (8 * k));
+    }
+}
+
+struct QuantAP {
+    const float* colour;          // [3][H][W] RGB
+    const float* alpha;           // [3][H][W] RGB: the alpha plane as the model rendered it, three times
+    unsigned char* dst;           // [H][pitch] B G R A bytes
+    size_t pitch;
+    int H, W;
+    int vec;                      // one 32-bit store per pixel (dst and pitch 4-byte aligned)
+};
+
+__global__ __launch_bounds__(kQThreads) void tensor2img_bgra_u8_kernel(QuantAP p) {
+    const int y = blockIdx.y, x = blockIdx.x * kQThreads + threadIdx.x;
+    if (x >= p.W) return;
+    const size_t plane = (size_t)p.H * p.W, i = (size_t)y * p.W + x;
+    const unsigned int b = quant8(p.colour[2 * plane + i]), g = quant8(p.colour[plane + i]), r = quant8(p.colour[i]);
+    const unsigned int a = alpha_of_bgr(quant8(p.alpha[2 * plane + i]), quant8(p.alpha[plane + i]), quant8(p.alpha[i]));
+    store_bgra(p.dst + (size_t)y * p.pitch, x, b | g << 8 | r << 16 | a << 24, p.vec);
+}
+
+struct PackAP {
+    const unsigned char* bgr;     // [H][pitch_bgr] B G R
+    const unsigned char* grey;    // [H][pitch_grey] B G R of the alpha image
+    size_t pitch_bgr, pitch_grey;
+    unsigned char* dst;           // [H][pitch] B G R A
+    size_t pitch;
+    int H, W;
+    int vec;
+};
+
+__global__ __launch_bounds__(kQThreads) void pack_bgra_u8_kernel(PackAP p) {
+    const int y = blockIdx.y, x = blockIdx.x * kQThreads + threadIdx.x;
+    if (x >= p.W) return;
+    const unsigned char* c = p.bgr + (size_t)y * p.pitch_bgr + 3 * (size_t)x;
+    const unsigned char* q = p.grey + (size_t)y * p.pitch_grey + 3 * (size_t)x;
+    const unsigned int a = alpha_of_bgr(q[0], q[1], q[2]);
+    store_bgra(p.dst + (size_t)y * p.pitch, x, (unsigned int)c[0] | (unsigned int)c[1] << 8 | (unsigned int)c[2] << 16 | a << 24, p.vec);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct MetricsP {
     const unsigned char* a;
@@ -273,6 +324,33 @@ extern "C" int ciaosr_tensor2img_u8(const float* src_chw, int H, int W, unsigned
     ProfScope prof("tensor2img_u8", s);
     hipLaunchKernelGGL(tensor2img_u8_kernel, dim3(ceil_div(p.vec ? W / 4 : W, kQThreads), H), dim3(kQThreads), 0, s, p);
     return launch_status("tensor2img_u8");
+}
+
+static inline int bgra_vec(const unsigned char* dst, size_t pitch) {
+    return (reinterpret_cast<uintptr_t>(dst) & 3u) == 0 && (pitch & 3u) == 0;
+}
+
+extern "C" int ciaosr_tensor2img_bgra_u8(const float* colour_chw, const float* alpha_chw, int H, int W, unsigned char* dst,
+                                         size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(colour_chw && alpha_chw && dst && H > 0 && W > 0 && dst_pitch >= 4 * (size_t)W);
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    QuantAP p{colour_chw, alpha_chw, dst, dst_pitch, H, W, bgra_vec(dst, dst_pitch)};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("tensor2img_bgra_u8", s);
+    hipLaunchKernelGGL(tensor2img_bgra_u8_kernel, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("tensor2img_bgra_u8");
+}
+
+extern "C" int ciaosr_pack_bgra_u8(const unsigned char* bgr, size_t pitch, const unsigned char* grey_bgr, size_t pitch_grey, int H, int W,
+                                   unsigned char* dst, size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(bgr && grey_bgr && dst && H > 0 && W > 0);
+    CIAOSR_CHECK_ARG(pitch >= 3 * (size_t)W && pitch_grey >= 3 * (size_t)W && dst_pitch >= 4 * (size_t)W);
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    PackAP p{bgr, grey_bgr, pitch, pitch_grey, dst, dst_pitch, H, W, bgra_vec(dst, dst_pitch)};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("pack_bgra_u8", s);
+    hipLaunchKernelGGL(pack_bgra_u8_kernel, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("pack_bgra_u8");
 }
 
 extern "C" size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int convert_to_y) {

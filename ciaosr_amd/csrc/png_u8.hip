@@ -5,7 +5,8 @@
 // (None, Sub, Up, Average, Paeth; 3 bytes per pixel, predecessors are the RAW pixels, the row above row 0 is zeros), picks the one whose
 // filtered bytes have the smallest sum of min(b, 256 - b) -- ties to the lowest number -- and writes the filter byte plus 3 W filtered
 // bytes in RGB order.  The same pass counts the band's 257-bin symbol histogram (256 literals + one end-of-block) in LDS and the band's
-// Adler-32 partial sums.
+// Adler-32 partial sums.  filter_band is a template over the bytes per pixel: 3 (colour type 2) and 4 (colour type 6, the ciaosr_png_rgba_*
+// entry points: rows of 1 + 4 W bytes in R G B A order, the left predecessor four bytes back, a pixel read as ONE aligned 32-bit word).
 //
 // Stage 2, four launches over a byte buffer split into bands:
 //   deflate_hist_kernel   the 257-bin histogram of every band (skipped when stage 1 made it);
@@ -85,10 +86,10 @@ struct TileBand {
 };
 
 struct FilterP {
-    const unsigned char* src;     // [H][pitch], 3 bytes per pixel
+    const unsigned char* src;     // [H][pitch], 3 or 4 bytes per pixel (the kernel's template argument)
     size_t pitch;
     int H, W, bgr, R;
-    unsigned char* dst;           // [H][1 + 3 W]
+    unsigned char* dst;           // [H][1 + bytes per pixel * W]
     u32* hist;                    // [nb][kStride]
     u32* adler;                   // [nb][2]: the band's Adler-32 sums a, b taken from a = b = 0, mod 65521
 };
@@ -106,8 +107,43 @@ __device__ __forceinline__ void filters5(int v, int a, int b, int c, u32 f[5]) {
     f[4] = (u32)(v - pr) & 255u;
 }
 
-// One workgroup, one band: rows [r0, r1) of the W pixels wide image at p.src (row 0 and column 0 have zeros for predecessors), written
-// from `dst` on; the band's histogram and Adler partials go to slot `band`.
+// The pixel at column x of row `cur` in stream order (R G B, then A): v its bytes, a those of the pixel to the left, b of the pixel above
+// (`up`, null for the image's first row), c of the pixel above left; zeros where the image ends.  Four bytes per pixel are ONE aligned
+// 32-bit load per pixel (the host checks src and pitch); three are single bytes.
+template <int BPP>
+__device__ __forceinline__ void load_pixel(const unsigned char* cur, const unsigned char* up, int x, int bgr, int v[BPP], int a[BPP],
+                                           int b[BPP], int c[BPP]) {
+    const int s0 = bgr ? 2 : 0, s2 = bgr ? 0 : 2;
+    if constexpr (BPP == 4) {
+        const u32* q = reinterpret_cast<const u32*>(cur) + x;
+        const u32* qu = reinterpret_cast<const u32*>(up) + x;
+        const u32 pv = q[0], pa = x > 0 ? q[-1] : 0u;
+        const u32 pb = up ? qu[0] : 0u, pc = (up && x > 0) ? qu[-1] : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int sh = 8 * (k == 0 ? s0 : (k == 2 ? s2 : k));
+            v[k] = (int)(pv >> sh & 255u);
+            a[k] = (int)(pa >> sh & 255u);
+            b[k] = (int)(pb >> sh & 255u);
+            c[k] = (int)(pc >> sh & 255u);
+        }
+    } else {
+        const unsigned char* q = cur + 3 * (size_t)x;
+        const unsigned char* qu = up + 3 * (size_t)x;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int sc = k == 0 ? s0 : (k == 1 ? 1 : s2);
+            v[k] = q[sc];
+            a[k] = x > 0 ? q[sc - 3] : 0;
+            b[k] = up ? qu[sc] : 0;
+            c[k] = (up && x > 0) ? qu[sc - 3] : 0;
+        }
+    }
+}
+
+// One workgroup, one band: rows [r0, r1) of the W pixels wide image at p.src, BPP bytes per pixel (row 0 and column 0 have zeros for
+// predecessors), written from `dst` on; the band's histogram and Adler partials go to slot `band`.
+template <int BPP>
 __device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, int r1, unsigned char* dst) {
     __shared__ u32 h[kWaves][kStride];
     __shared__ u32 red[kWaves][5];
@@ -116,22 +152,19 @@ __device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i < kWaves * kStride; i += kThreads) (&h[0][0])[i] = 0u;
     __syncthreads();
-    const u64 L = 3ull * (u64)p.W + 1ull;
-    const int s0 = p.bgr ? 2 : 0, s2 = p.bgr ? 0 : 2;
+    const u64 L = (u64)BPP * (u64)p.W + 1ull;
     u32 A = 0u, B = 0u;                                   // thread 0: the band's Adler sums so far
     for (int row = r0; row < r1; ++row) {
         const unsigned char* cur = p.src + (size_t)row * p.pitch;
         const unsigned char* up = row > 0 ? cur - p.pitch : nullptr;
         u32 s[5] = {0u, 0u, 0u, 0u, 0u};
         for (int x = tid; x < p.W; x += kThreads) {
-            const unsigned char* q = cur + 3 * (size_t)x;
+            int v[BPP], a[BPP], b[BPP], cc[BPP];
+            load_pixel<BPP>(cur, up, x, p.bgr, v, a, b, cc);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int sc = c == 0 ? s0 : (c == 1 ? 1 : s2);
-                const int v = q[sc], a = x > 0 ? q[sc - 3] : 0;
-                const int b = up ? (up + 3 * (size_t)x)[sc] : 0, cc = (up && x > 0) ? (up + 3 * (size_t)x)[sc - 3] : 0;
+            for (int c = 0; c < BPP; ++c) {
                 u32 f[5];
-                filters5(v, a, b, cc, f);
+                filters5(v[c], a[c], b[c], cc[c], f);
 #pragma unroll
                 for (int k = 0; k < 5; ++k) s[k] += cost8(f[k]);
             }
@@ -166,20 +199,18 @@ __device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, 
             a2 = L * (u64)best;
         }
         for (int x = tid; x < p.W; x += kThreads) {
-            const unsigned char* q = cur + 3 * (size_t)x;
+            int v[BPP], a[BPP], b[BPP], cc[BPP];
+            load_pixel<BPP>(cur, up, x, p.bgr, v, a, b, cc);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int sc = c == 0 ? s0 : (c == 1 ? 1 : s2);
-                const int v = q[sc], a = x > 0 ? q[sc - 3] : 0;
-                const int b = up ? (up + 3 * (size_t)x)[sc] : 0, cc = (up && x > 0) ? (up + 3 * (size_t)x)[sc - 3] : 0;
+            for (int c = 0; c < BPP; ++c) {
                 u32 f[5];
-                filters5(v, a, b, cc, f);
+                filters5(v[c], a[c], b[c], cc[c], f);
                 const u32 fb = best == 0 ? f[0] : best == 1 ? f[1] : best == 2 ? f[2] : best == 3 ? f[3] : f[4];
-                const u64 j = 1ull + 3ull * (u64)x + (u64)c;
+                const u64 j = 1ull + (u64)BPP * (u64)x + (u64)c;
                 out[j] = (unsigned char)fb;
                 atomicAdd(&h[wave][fb], 1u);
                 a1 += fb;
-                a2 += (L - j) * (u64)fb;              // < 2^18 * 2^8 per byte, < 2^44 per row
+                a2 += (L - j) * (u64)fb;              // < 2^19 * 2^8 per byte, < 2^45 per row
             }
         }
         a1 = wave_sum_u64(a1);
@@ -211,10 +242,11 @@ __device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, 
     }
 }
 
+template <int BPP>
 __global__ __launch_bounds__(kThreads) void png_filter_kernel(FilterP p) {
     const int band = blockIdx.x;
     const int r0 = band * p.R, r1 = min(p.H, r0 + p.R);
-    filter_band(p, band, r0, r1, p.dst + (u64)r0 * (3ull * (u64)p.W + 1ull));
+    filter_band<BPP>(p, band, r0, r1, p.dst + (u64)r0 * ((u64)BPP * (u64)p.W + 1ull));
 }
 
 // The tile-batched form: band `blockIdx.x` of the table is rows [r0, r1) of tile `tile`, a crop y0, x0, h, w of the image.  The crop is
@@ -230,12 +262,13 @@ struct TileFilterP {
     unsigned char* dst;
     u32 *hist, *adler;
 };
+template <int BPP>
 __global__ __launch_bounds__(kThreads) void png_filter_tiles_kernel(TileFilterP t) {
     const int band = blockIdx.x;
     const TileBand b = t.bands[band];
     const int* r = t.rects + 4 * (size_t)b.tile;
-    FilterP p{t.src + (size_t)r[0] * t.pitch + 3 * (size_t)r[1], t.pitch, r[2], r[3], t.bgr, 0, nullptr, t.hist, t.adler};
-    filter_band(p, band, b.r0, b.r1, t.dst + t.offs[band]);
+    FilterP p{t.src + (size_t)r[0] * t.pitch + BPP * (size_t)r[1], t.pitch, r[2], r[3], t.bgr, 0, nullptr, t.hist, t.adler};
+    filter_band<BPP>(p, band, b.r0, b.r1, t.dst + t.offs[band]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -745,9 +778,9 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
 }
 
-static inline int rows_per_band(int W, int rows) {
+static inline int rows_per_band(int W, int rows, int bpp) {
     if (rows > 0) return rows;
-    const long L = 3L * W + 1;
+    const long L = (long)bpp * W + 1;
     const long r = (128L * 1024L) / L;                       // bands of about 128 KiB of filtered bytes
     return (int)(r < 1 ? 1 : r);
 }
@@ -807,15 +840,25 @@ static int run_deflate(DeflateP& p, hipStream_t s) {
     return launch_status("deflate_pack");
 }
 
-static int run_filter(const unsigned char* src, size_t pitch, int H, int W, int bgr, int R, unsigned char* dst, u32* hist, u32* adler,
-                      hipStream_t s) {
+static int run_filter(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int R, unsigned char* dst, u32* hist,
+                      u32* adler, hipStream_t s) {
     FilterP f{src, pitch, H, W, bgr, R, dst, hist, adler};
-    ProfScope prof("png_filter_u8", s);
-    hipLaunchKernelGGL(png_filter_kernel, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
-    return launch_status("png_filter_u8");
+    const char* name = bpp == 4 ? "png_rgba_filter_u8" : "png_filter_u8";
+    ProfScope prof(name, s);
+    if (bpp == 4)
+        hipLaunchKernelGGL(png_filter_kernel<4>, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
+    else
+        hipLaunchKernelGGL(png_filter_kernel<3>, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
+    return launch_status(name);
 }
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
+
+// what the filter asks of a source: rows of at least bpp W bytes; four bytes per pixel are read as aligned 32-bit words
+static inline bool source_ok(int bpp, const unsigned char* src, size_t pitch, int W) {
+    if (!src || pitch < (size_t)bpp * (size_t)W) return false;
+    return bpp != 4 || ((reinterpret_cast<uintptr_t>(src) & 3u) == 0 && (pitch & 3u) == 0);
+}
 
 // ---- many crops of one image -----------------------------------------------------------------------------------------------------
 // The band table of a list of rects, as the device reads it: one block of memory, [offs u64 (nb + 1)][bands TileBand nb]
@@ -828,7 +871,7 @@ struct TilePlan {
     size_t o_bands, o_first, o_rects, table_bytes;
 };
 // `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
-static TilePlan plan_tiles(const int* rects, int n_tiles, int rows_arg, int H, int W, std::vector<unsigned char>* table) {
+static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg, int H, int W, std::vector<unsigned char>* table) {
     TilePlan t{};
     t.rc = CIAOSR_ERR_BAD_ARG;
     if (!rects || n_tiles < 1 || rows_arg < 0) return t;
@@ -838,8 +881,8 @@ static TilePlan plan_tiles(const int* rects, int n_tiles, int rows_arg, int H, i
         const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
         if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
         if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return t;
-        const u64 L = 3ull * w + 1;
-        const int R = rows_per_band(w, rows_arg);
+        const u64 L = (u64)bpp * w + 1;
+        const int R = rows_per_band(w, rows_arg, bpp);
         if ((u64)R * L > kMaxBand) {
             t.rc = CIAOSR_ERR_UNSUPPORTED;
             return t;
@@ -871,8 +914,8 @@ static TilePlan plan_tiles(const int* rects, int n_tiles, int rows_arg, int H, i
     int i = 0;
     for (int k = 0; k < n_tiles; ++k) {
         const int h = rects[4 * k + 2], w = rects[4 * k + 3];
-        const u64 L = 3ull * w + 1;
-        const int R = rows_per_band(w, rows_arg);
+        const u64 L = (u64)bpp * w + 1;
+        const int R = rows_per_band(w, rows_arg, bpp);
         first[k] = (u32)i;
         for (int r0 = 0; r0 < h; r0 += R, ++i) {
             const int r1 = r0 + R < h ? r0 + R : h;
@@ -911,19 +954,122 @@ static inline size_t tile_work_bytes(const TilePlan& t) {
 using namespace ciaosr;
 using namespace ciaosr::png;
 
+// ---- the entry points' bodies, for 3 (R G B) or 4 (R G B A) bytes per pixel --------------------------------------------------------
+static int filter_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg, unsigned char* dst,
+                        unsigned int* hist, unsigned int* adler, void* stream) {
+    CIAOSR_CHECK_ARG(dst && hist && adler && image_ok(H, W) && source_ok(bpp, src, pitch, W));
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(hist) & 3u) == 0 && (reinterpret_cast<uintptr_t>(adler) & 3u) == 0);
+    const int R = rows_per_band(W, rows_per_band_arg, bpp);
+    if ((u64)R * ((u64)bpp * W + 1) > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    return run_filter(bpp, src, pitch, H, W, bgr, R, dst, hist, adler, (hipStream_t)stream);
+}
+
+static size_t workspace_entry(int bpp, int H, int W, int rows_per_band_arg) {
+    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
+    const int R = rows_per_band(W, rows_per_band_arg, bpp);
+    return work_bytes(ceil_div(H, R), (size_t)H * ((size_t)bpp * (size_t)W + 1));
+}
+
+static size_t capacity_entry(int bpp, int H, int W, int rows_per_band_arg) {
+    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
+    const int R = rows_per_band(W, rows_per_band_arg, bpp);
+    return capacity((size_t)H * ((size_t)bpp * (size_t)W + 1), ceil_div(H, R), true);
+}
+
+static int encode_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg, unsigned char* out,
+                        size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(out && total_bytes && workspace && image_ok(H, W) && source_ok(bpp, src, pitch, W));
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    const int R = rows_per_band(W, rows_per_band_arg, bpp);
+    const u64 L = (u64)bpp * W + 1;
+    if ((u64)R * L > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    const int nb = ceil_div(H, R);
+    const u64 total = (u64)H * L;
+    if (out_capacity < capacity(total, nb, true)) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = run_filter(bpp, src, pitch, H, W, bgr, R, w.filtered, w.hist, w.adler, s);
+    if (rc) return rc;
+    DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
+               out, w.adler, total_bytes};
+    return run_deflate(p, s);
+}
+
+static int encode_tiles_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                              int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && source_ok(bpp, src, pitch, W));
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    std::vector<unsigned char> table;
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, H, W, &table);
+    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image
+    if (t.rc != CIAOSR_OK) return t.rc;
+    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
+    TileWork tw;
+    if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    const Work& w = tw.w;
+    hipStream_t s = (hipStream_t)stream;
+    // from pageable memory: the copy has left `table` when the call returns
+    if (hipMemcpyAsync(tw.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    const u64* offs = reinterpret_cast<const u64*>(tw.table);
+    const TileBand* bands = reinterpret_cast<const TileBand*>(tw.table + t.o_bands);
+    const u32* first = reinterpret_cast<const u32*>(tw.table + t.o_first);
+    const int* d_rects = reinterpret_cast<const int*>(tw.table + t.o_rects);
+    {
+        TileFilterP f{src, pitch, bgr, d_rects, bands, offs, w.filtered, w.hist, w.adler};
+        const char* name = bpp == 4 ? "png_rgba_filter_tiles_u8" : "png_filter_tiles_u8";
+        ProfScope prof(name, s);
+        if (bpp == 4)
+            hipLaunchKernelGGL(png_filter_tiles_kernel<4>, dim3(t.nb), dim3(kThreads), 0, s, f);
+        else
+            hipLaunchKernelGGL(png_filter_tiles_kernel<3>, dim3(t.nb), dim3(kThreads), 0, s, f);
+        int rc = launch_status(name);
+        if (rc) return rc;
+    }
+    DeflateP p{w.filtered, Bands{offs, 0ull, 0ull, t.nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 0ull, out,
+               w.adler, nullptr, bands};
+    {
+        ProfScope prof("deflate_plan", s);
+        hipLaunchKernelGGL(deflate_plan_kernel, dim3(t.nb), dim3(kWave), 0, s, p);
+        int rc = launch_status("deflate_plan");
+        if (rc) return rc;
+    }
+    {
+        TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
+        ProfScope prof("png_tiles_scan", s);
+        hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
+        int rc = launch_status("png_tiles_scan");
+        if (rc) return rc;
+    }
+    ProfScope prof("deflate_pack", s);
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3(t.nb), dim3(kThreads), 0, s, p);
+    return launch_status("deflate_pack");
+}
+
 extern "C" int ciaosr_png_rows_per_band(int W, int rows_per_band_arg) {
     if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
-    return rows_per_band(W, rows_per_band_arg);
+    return rows_per_band(W, rows_per_band_arg, 3);
+}
+
+extern "C" int ciaosr_png_rgba_rows_per_band(int W, int rows_per_band_arg) {
+    if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
+    return rows_per_band(W, rows_per_band_arg, 4);
 }
 
 extern "C" int ciaosr_png_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                     unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
-    CIAOSR_CHECK_ARG(src && dst && hist && adler && image_ok(H, W) && pitch >= 3 * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(hist) & 3u) == 0 && (reinterpret_cast<uintptr_t>(adler) & 3u) == 0);
-    const int R = rows_per_band(W, rows_per_band_arg);
-    if ((u64)R * (3ull * W + 1) > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
-    return run_filter(src, pitch, H, W, bgr, R, dst, hist, adler, (hipStream_t)stream);
+    return filter_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler, stream);
+}
+
+extern "C" int ciaosr_png_rgba_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                         unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
+    return filter_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler, stream);
 }
 
 extern "C" size_t ciaosr_deflate_huff_workspace_bytes(int n_bands) {
@@ -964,96 +1110,55 @@ extern "C" int ciaosr_deflate_huff_u8(const unsigned char* data, const unsigned 
     return run_deflate(p, s);
 }
 
-extern "C" size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band_arg) {
-    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
-    const int R = rows_per_band(W, rows_per_band_arg);
-    return work_bytes(ceil_div(H, R), (size_t)H * (3 * (size_t)W + 1));
-}
-
-extern "C" size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band_arg) {
-    if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
-    const int R = rows_per_band(W, rows_per_band_arg);
-    return capacity((size_t)H * (3 * (size_t)W + 1), ceil_div(H, R), true);
-}
+extern "C" size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg); }
+extern "C" size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(3, H, W, rows_per_band_arg); }
+extern "C" size_t ciaosr_png_rgba_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(4, H, W, rows_per_band_arg); }
+extern "C" size_t ciaosr_png_rgba_capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(4, H, W, rows_per_band_arg); }
 
 extern "C" int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                     unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= 3 * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    const int R = rows_per_band(W, rows_per_band_arg);
-    const u64 L = 3ull * W + 1;
-    if ((u64)R * L > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
-    const int nb = ceil_div(H, R);
-    const u64 total = (u64)H * L;
-    if (out_capacity < capacity(total, nb, true)) return CIAOSR_ERR_WORKSPACE;
-    Work w;
-    if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = run_filter(src, pitch, H, W, bgr, R, w.filtered, w.hist, w.adler, s);
-    if (rc) return rc;
-    DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
-               out, w.adler, total_bytes};
-    return run_deflate(p, s);
+    return encode_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ciaosr_png_rgba_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                         unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    return encode_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+}
+
+static size_t tiles_workspace_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? tile_work_bytes(t) : 0;
+}
+static size_t tiles_capacity_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? t.capacity : 0;
 }
 
 extern "C" size_t ciaosr_png_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? tile_work_bytes(t) : 0;
+    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg);
 }
-
 extern "C" size_t ciaosr_png_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? t.capacity : 0;
+    return tiles_capacity_entry(3, rects, n_tiles, rows_per_band_arg);
+}
+extern "C" size_t ciaosr_png_rgba_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg);
+}
+extern "C" size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_capacity_entry(4, rects, n_tiles, rows_per_band_arg);
 }
 
 extern "C" int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                           int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    std::vector<unsigned char> table;
-    const TilePlan t = plan_tiles(rects, n_tiles, rows_per_band_arg, H, W, &table);
-    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image
-    if (t.rc != CIAOSR_OK) return t.rc;
-    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
-    TileWork tw;
-    if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) return CIAOSR_ERR_WORKSPACE;
-    const Work& w = tw.w;
-    hipStream_t s = (hipStream_t)stream;
-    // from pageable memory: the copy has left `table` when the call returns
-    if (hipMemcpyAsync(tw.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    const u64* offs = reinterpret_cast<const u64*>(tw.table);
-    const TileBand* bands = reinterpret_cast<const TileBand*>(tw.table + t.o_bands);
-    const u32* first = reinterpret_cast<const u32*>(tw.table + t.o_first);
-    const int* d_rects = reinterpret_cast<const int*>(tw.table + t.o_rects);
-    {
-        TileFilterP f{src, pitch, bgr, d_rects, bands, offs, w.filtered, w.hist, w.adler};
-        ProfScope prof("png_filter_tiles_u8", s);
-        hipLaunchKernelGGL(png_filter_tiles_kernel, dim3(t.nb), dim3(kThreads), 0, s, f);
-        int rc = launch_status("png_filter_tiles_u8");
-        if (rc) return rc;
-    }
-    DeflateP p{w.filtered, Bands{offs, 0ull, 0ull, t.nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 0ull, out,
-               w.adler, nullptr, bands};
-    {
-        ProfScope prof("deflate_plan", s);
-        hipLaunchKernelGGL(deflate_plan_kernel, dim3(t.nb), dim3(kWave), 0, s, p);
-        int rc = launch_status("deflate_plan");
-        if (rc) return rc;
-    }
-    {
-        TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
-        ProfScope prof("png_tiles_scan", s);
-        hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
-        int rc = launch_status("png_tiles_scan");
-        if (rc) return rc;
-    }
-    ProfScope prof("deflate_pack", s);
-    hipLaunchKernelGGL(deflate_pack_kernel, dim3(t.nb), dim3(kThreads), 0, s, p);
-    return launch_status("deflate_pack");
+    return encode_tiles_entry(3, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
+}
+
+extern "C" int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                               int rows_per_band_arg, unsigned char* out, size_t out_capacity,
+                                               unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_tiles_entry(4, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
 }

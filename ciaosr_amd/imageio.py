@@ -13,6 +13,15 @@ def imread_rgb01(path):
     return torch.from_numpy(img).permute(2, 0, 1).contiguous()
 
 
+def imread_rgba01(path):
+    """-> (float32 tensor [4,H,W] in [0,1], R G B A, not premultiplied; opaque): the file through Pillow's convert('RGBA') -- RGBA, LA,
+    palette files with a tRNS chunk; a file without transparency gets alpha 1.  `opaque`: every alpha byte is 255."""
+    from PIL import Image
+    img = np.asarray(Image.open(path).convert('RGBA'), dtype=np.uint8)
+    opaque = bool((img[:, :, 3] == 255).all())
+    return torch.from_numpy(img.astype(np.float32) / 255.0).permute(2, 0, 1).contiguous(), opaque
+
+
 def imread_u8(path):
     """-> HxWx3 uint8 RGB array: LoadImageFromFile(flag='color', channel_order='rgb') before any conversion."""
     from PIL import Image

@@ -32,6 +32,40 @@ def tensor2img_u8(t):
     return img
 
 
+def tensor2img_bgra_u8(out2):
+    """The 8-bit image of an RGBA render: [2, 3, H, W] = (colour, alpha as grey), RGB in [0, 1] -> uint8 [H, W, 4] with bytes B G R A.
+    B G R are `tensor2img_u8`'s bytes of item 0; with (B, G, R) = `tensor2img_u8`'s bytes of item 1,
+    A = (4899 R + 9617 G + 1868 B + 8192) >> 14.  One pass."""
+    if not isinstance(out2, torch.Tensor) or out2.dim() != 4 or out2.shape[0] != 2 or out2.shape[1] != 3:
+        shape = tuple(out2.shape) if isinstance(out2, torch.Tensor) else type(out2).__name__
+        raise ValueError(f'tensor2img_bgra_u8 expects [2, 3, H, W] (colour, alpha as grey), got {shape}')
+    t = out2.detach().float().contiguous()
+    hip_ops.require_gpu(t)
+    h, w = t.shape[2], t.shape[3]
+    img = torch.empty((h, w, 4), dtype=torch.uint8, device=t.device)
+    _lib.call('ciaosr_tensor2img_bgra_u8', hip_ops.ptr(t[0]), hip_ops.ptr(t[1]), h, w, hip_ops.ptr(img), C.c_size_t(img.stride(0)),
+              hip_ops.stream_ptr(t.device))
+    return img
+
+
+def pack_bgra_u8(bgr_u8, grey_u8):
+    """uint8 [H, W, 4] B G R A from two uint8 [H, W, 3] BGR device images: the colour bytes of the first, the alpha
+    (4899 R + 9617 G + 1868 B + 8192) >> 14 of the second's.  Rows may be pitched."""
+    for img in (bgr_u8, grey_u8):
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+            what = f'{img.dtype} {tuple(img.shape)}' if isinstance(img, torch.Tensor) else type(img).__name__
+            raise ValueError(f'pack_bgra_u8 expects two uint8 [H, W, 3] images, got {what}')
+    if bgr_u8.shape != grey_u8.shape:
+        raise ValueError(f'pack_bgra_u8: the images differ in size, {tuple(bgr_u8.shape)} and {tuple(grey_u8.shape)}')
+    _check_image(bgr_u8)
+    _check_image(grey_u8)
+    h, w = bgr_u8.shape[0], bgr_u8.shape[1]
+    img = torch.empty((h, w, 4), dtype=torch.uint8, device=bgr_u8.device)
+    _lib.call('ciaosr_pack_bgra_u8', hip_ops.ptr(bgr_u8), C.c_size_t(bgr_u8.stride(0)), hip_ops.ptr(grey_u8), C.c_size_t(grey_u8.stride(0)),
+              h, w, hip_ops.ptr(img), C.c_size_t(img.stride(0)), hip_ops.stream_ptr(bgr_u8.device))
+    return img
+
+
 def _check_image(img):
     if not isinstance(img, torch.Tensor):
         raise CiaoSRHipError(f'expected a uint8 HxWx3 cuda tensor, got {type(img).__name__}')

@@ -6,6 +6,9 @@ host only wraps that stream: signature, IHDR, IDAT chunks, IEND, with `zlib.crc3
 than Pillow's but decode to exactly the same pixels.  Two copies synchronise per image: the stream's size, then the stream.  There is
 no CPU fallback: a host array raises.  `encode_png_tiles` codes many crops of one image (the tiles of a pyramid level, pyramid.py) in
 one set of launches and two synchronising copies per call; each file is byte for byte the single call's on that crop.
+
+A uint8 [H, W, 4] image (`order` 'bgra', as `metrics_hip.tensor2img_bgra_u8` makes it, or 'rgba') goes through the four-byte-per-pixel
+siblings of the same calls and becomes a colour type 6 file; every entry point here takes either kind.
 """
 import ctypes as C
 import os
@@ -16,7 +19,6 @@ import torch
 
 from . import _lib, hip_ops
 from ._lib import CiaoSRHipError
-from .metrics_hip import _check_image
 
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 IDAT_MAX = (1 << 31) - 1                   # a chunk's length field is below 2^31
@@ -24,6 +26,37 @@ HIST_STRIDE = 260                          # CIAOSR_PNG_HIST_STRIDE
 ADLER = 65521
 MAX_SIDE = 65535
 ORDERS = {'bgr': 1, 'rgb': 0}
+ORDERS_RGBA = {'bgra': 1, 'rgba': 0}
+COLOUR_TYPES = {3: 2, 4: 6}                # bytes per pixel -> IHDR colour type
+_ABI = {3: 'ciaosr_png_', 4: 'ciaosr_png_rgba_'}
+
+
+def _pitch(img):
+    """Bytes from one row to the next; a one-row image has no next row, and torch may report any stride for it."""
+    return img.stride(0) if img.shape[0] > 1 else img.shape[1] * img.shape[2]
+
+
+def _check_image(img, order):
+    """The image rules of this module: a uint8 [H, W, 3] or [H, W, 4] device tensor with packed pixels (rows may be pitched) and an
+    `order` of its channel count -> (channels, the ABI's bgr flag).  A wrong order is a ValueError before the device is looked at."""
+    if not isinstance(img, torch.Tensor):
+        raise CiaoSRHipError(f'expected a uint8 HxWx3 or HxWx4 cuda tensor, got {type(img).__name__}')
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] not in (3, 4):
+        raise CiaoSRHipError(f'expected a uint8 HxWx3 or HxWx4 image, got {img.dtype} {tuple(img.shape)}')
+    ch = img.shape[2]
+    orders = ORDERS if ch == 3 else ORDERS_RGBA
+    if order not in orders:
+        raise ValueError(f"order of a {ch}-channel image must be {' or '.join(repr(o) for o in orders)}, got {order!r}")
+    if not img.is_cuda:
+        hip_ops.require_gpu(img)              # raises: no CPU fallback
+    h, w = img.shape[0], img.shape[1]                  # (the stride of a dimension of size 1 means nothing: torch keeps any)
+    if img.stride(2) != 1 or (w > 1 and img.stride(1) != ch) or (h > 1 and img.stride(0) < ch * w):
+        raise CiaoSRHipError(f'expected HWC rows of {ch}*W contiguous bytes (a crop of a larger image is fine)')
+    if ch == 4 and (_pitch(img) % 4 or img.data_ptr() % 4):
+        raise CiaoSRHipError('a 4-channel image is read in 32-bit words: its first byte and its row pitch must be multiples of 4')
+    if img.device.index != torch.cuda.current_device():
+        raise CiaoSRHipError(f'image on cuda:{img.device.index} but the current device is cuda:{torch.cuda.current_device()}')
+    return ch, orders[order]
 
 
 def chunk(tag, data):
@@ -31,12 +64,14 @@ def chunk(tag, data):
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(data, zlib.crc32(tag)) & 0xffffffff)
 
 
-def container(h, w, zstream, idat_max=IDAT_MAX):
-    """The PNG file of an h x w 8-bit RGB image whose IDAT data is `zstream` (a zlib stream of the filtered scanlines), split into
-    IDAT chunks of at most `idat_max` bytes."""
+def container(h, w, zstream, idat_max=IDAT_MAX, channels=3):
+    """The PNG file of an h x w 8-bit RGB (`channels=4`: RGBA, colour type 6) image whose IDAT data is `zstream` (a zlib stream of the
+    filtered scanlines), split into IDAT chunks of at most `idat_max` bytes."""
     if not (0 < idat_max <= IDAT_MAX):
         raise ValueError(f'idat_max={idat_max}')
-    parts = [SIGNATURE, chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))]
+    if channels not in COLOUR_TYPES:
+        raise ValueError(f'channels={channels!r}: 3 (RGB) or 4 (RGBA)')
+    parts = [SIGNATURE, chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, COLOUR_TYPES[channels], 0, 0, 0))]
     view = memoryview(zstream)
     for i in range(0, max(len(view), 1), idat_max):
         parts.append(chunk(b'IDAT', bytes(view[i:i + idat_max])))
@@ -62,28 +97,27 @@ def zlib_stream(segments, partials):
 
 
 def _geometry(img, order, rows_per_band):
-    _check_image(img)
-    if order not in ORDERS:
-        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    """-> (h, w, rows per band, bands, channels, bgr flag)"""
+    ch, bgr = _check_image(img, order)
     h, w = img.shape[0], img.shape[1]
     rows = int(rows_per_band)
     if rows < 0:
         raise ValueError(f'rows_per_band={rows_per_band}')
     if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
         raise CiaoSRHipError(f'encode_png: {h}x{w} is outside 1..{MAX_SIDE} per side')
-    rows = _lib.load().ciaosr_png_rows_per_band(w, rows)
-    return h, w, rows, -(-h // rows)
+    rows = getattr(_lib.load(), _ABI[ch] + 'rows_per_band')(w, rows)
+    return h, w, rows, -(-h // rows), ch, bgr
 
 
 def filter_u8(img, order='bgr', rows_per_band=0):
-    """Stage 1 alone: (scanline stream uint8 [H * (1 + 3 W)], histograms int32 [bands, 260], Adler partials int32 [bands, 2]) on the
-    device; no synchronisation."""
-    h, w, rows, nb = _geometry(img, order, rows_per_band)
+    """Stage 1 alone: (scanline stream uint8 [H * (1 + C W)], histograms int32 [bands, 260], Adler partials int32 [bands, 2]) on the
+    device, C = 3 or 4 channels; no synchronisation."""
+    h, w, rows, nb, ch, bgr = _geometry(img, order, rows_per_band)
     dev = img.device
-    stream = torch.empty(h * (3 * w + 1), dtype=torch.uint8, device=dev)
+    stream = torch.empty(h * (ch * w + 1), dtype=torch.uint8, device=dev)
     hist = torch.empty((nb, HIST_STRIDE), dtype=torch.int32, device=dev)
     adler = torch.empty((nb, 2), dtype=torch.int32, device=dev)
-    _lib.call('ciaosr_png_filter_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], rows, hip_ops.ptr(stream),
+    _lib.call(_ABI[ch] + 'filter_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, rows, hip_ops.ptr(stream),
               hip_ops.ptr(hist), hip_ops.ptr(adler), hip_ops.stream_ptr(dev))
     return stream, hist, adler
 
@@ -118,17 +152,17 @@ def deflate_huff(data, band_offsets):
 
 def encode_zlib(img, order='bgr', rows_per_band=0):
     """The zlib stream of the image's filtered scanlines, made on the device -> bytes.  Synchronises twice: size, then stream."""
-    h, w, rows, nb = _geometry(img, order, rows_per_band)
+    h, w, rows, nb, ch, bgr = _geometry(img, order, rows_per_band)
     dev = img.device
     lib = _lib.load()
-    cap = lib.ciaosr_png_capacity_bytes(h, w, rows)
-    nbytes = lib.ciaosr_png_workspace_bytes(h, w, rows)
+    cap = getattr(lib, _ABI[ch] + 'capacity_bytes')(h, w, rows)
+    nbytes = getattr(lib, _ABI[ch] + 'workspace_bytes')(h, w, rows)
     if cap == 0 or nbytes == 0:
         raise CiaoSRHipError(f'encode_png: unsupported geometry {h}x{w}, rows_per_band={rows}')
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call('ciaosr_png_encode_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], rows, hip_ops.ptr(out),
+    _lib.call(_ABI[ch] + 'encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, rows, hip_ops.ptr(out),
               C.c_size_t(cap), hip_ops.ptr(total), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     n = int(total.item())                                   # copy 1: the size
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the stream
@@ -136,9 +170,10 @@ def encode_zlib(img, order='bgr', rows_per_band=0):
 
 def encode_png(img_u8_hwc, order='bgr', rows_per_band=0):
     """PNG file (bytes) of a uint8 [H, W, 3] device image; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched
-    (a crop view of a larger image).  `rows_per_band`: image rows per independently coded band, 0 = about 128 KiB of scanline bytes."""
+    (a crop view of a larger image).  `rows_per_band`: image rows per independently coded band, 0 = about 128 KiB of scanline bytes.
+    A [H, W, 4] image with `order` 'bgra' (as `tensor2img_bgra_u8` makes it) or 'rgba' gives an RGBA file."""
     z = encode_zlib(img_u8_hwc, order, rows_per_band)
-    return container(img_u8_hwc.shape[0], img_u8_hwc.shape[1], z)
+    return container(img_u8_hwc.shape[0], img_u8_hwc.shape[1], z, channels=img_u8_hwc.shape[2])
 
 
 def check_rects(rects, h, w):
@@ -160,9 +195,7 @@ def check_rects(rects, h, w):
 def encode_tiles_device(img, rects, order='bgr', rows_per_band=0):
     """ciaosr_png_encode_tiles_u8 on the current stream, no synchronisation -> (streams uint8 [capacity], offsets int64 [n + 1]) on the
     device: crop k's zlib stream is streams[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps."""
-    _check_image(img)
-    if order not in ORDERS:
-        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    ch, bgr = _check_image(img, order)
     rows = int(rows_per_band)
     if rows < 0:
         raise ValueError(f'rows_per_band={rows_per_band}')
@@ -174,14 +207,14 @@ def encode_tiles_device(img, rects, order='bgr', rows_per_band=0):
     dev = img.device
     lib = _lib.load()
     host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
-    cap = lib.ciaosr_png_tiles_capacity_bytes(host_rects, n, rows)
-    nbytes = lib.ciaosr_png_tiles_workspace_bytes(host_rects, n, rows)
+    cap = getattr(lib, _ABI[ch] + 'tiles_capacity_bytes')(host_rects, n, rows)
+    nbytes = getattr(lib, _ABI[ch] + 'tiles_workspace_bytes')(host_rects, n, rows)
     if cap == 0 or nbytes == 0:
         raise CiaoSRHipError(f'encode_png_tiles: unsupported geometry ({n} rects, rows_per_band={rows})')
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    _lib.call('ciaosr_png_encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, rows,
+    _lib.call(_ABI[ch] + 'encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, host_rects, n, rows,
               hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(offs), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     return out, offs
 
@@ -197,12 +230,12 @@ def encode_zlib_tiles(img, rects, order='bgr', rows_per_band=0):
 
 
 def encode_png_tiles(img_u8_hwc, rects, order='bgr', rows_per_band=0):
-    """PNG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] device image, coded together: file k
-    is byte for byte `encode_png(img[y0:y0 + h, x0:x0 + w], order, rows_per_band)`.  The rects may overlap.  A bad rect is a
+    """PNG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] (or [H, W, 4]) device image, coded
+    together: file k is byte for byte `encode_png(img[y0:y0 + h, x0:x0 + w], order, rows_per_band)`.  The rects may overlap.  A bad rect is a
     ValueError before any device work; two synchronising copies per call."""
     rects = list(rects)
     zs = encode_zlib_tiles(img_u8_hwc, rects, order, rows_per_band)
-    return [container(int(r[2]), int(r[3]), z) for r, z in zip(rects, zs)]
+    return [container(int(r[2]), int(r[3]), z, channels=img_u8_hwc.shape[2]) for r, z in zip(rects, zs)]
 
 
 def imwrite_gpu(img_u8_hwc, path, order='bgr'):

@@ -2,7 +2,9 @@
 scene.  The plan and the manifest are pure host code; `write_dzi` renders every level with `CiaoSR.render_pyramid` -- the levels at or
 above the LR size are the model's own answer at that size, all from one walk over the tile scenes -- and codes each level's tiles with
 ONE `png_hip.encode_png_tiles` call: two synchronising copies per level, whatever its number of tiles.  `fmt='jpg'` writes
-`<col>_<row>.jpg` tiles through one `jpeg_hip.encode_jpeg_tiles` call per level instead, and `Format="jpg"` in the manifest.
+`<col>_<row>.jpg` tiles through one `jpeg_hip.encode_jpeg_tiles` call per level instead, and `Format="jpg"` in the manifest.  The levels
+of an RGBA encode (`CiaoSR.encode_rgba`) are uint8 [H_l, W_l, 4] images and become RGBA PNG tiles under the same manifest; JPEG has no
+alpha, so `fmt='jpg'` refuses them.
 
 Deep Zoom's rules: Lmax = ceil(log2(max(W, H))), levels 0..Lmax; level L is max(1, ceil(W / 2^(Lmax - L))) wide and as high by the same
 rule; on a level, column c spans [c T - (O if c > 0 else 0), min((c + 1) T + O, Wl)) for the tile size T and the overlap O, rows alike,
@@ -75,7 +77,14 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
     """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
     returns them): one `encode_png_tiles` call per level, or for `fmt='jpg'` one `encode_jpeg_tiles` call with `quality` and
     `subsampling` (`optimize=True`: every tile with Huffman tables of its own; `progressive=True`: every tile a progressive file).
+    Four-channel levels ([H_l, W_l, 4], bytes B G R A for `order` 'bgr' / 'bgra', R G B A for 'rgb' / 'rgba') are written as RGBA PNG
+    tiles; with `fmt='jpg'` they are a ValueError before any device work.
     -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
+    rgba = any(getattr(im, 'dim', lambda: 0)() == 3 and im.shape[2] == 4 for im in levels)
+    if rgba:
+        if _check_format(fmt) == 'jpg':
+            raise ValueError("fmt='jpg' cannot hold the alpha channel of four-channel levels: write them with fmt='png'")
+        order = {'bgr': 'bgra', 'rgb': 'rgba'}.get(order, order)
     if _check_format(fmt) == 'jpg':
         from .jpeg_hip import check_optimize, check_params, check_progressive, encode_jpeg_tiles
         check_params(quality, subsampling)
@@ -125,6 +134,8 @@ def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, o
     -> dict: levels [(H_l, W_l)], model_levels (the levels rendered by the model; the ones below are Pillow-exact bicubic resizes of
     the smallest of them), files, bytes, and the seconds spent in render_s (to the last launch, not synchronised), encode_s, write_s."""
     _check_tiling(tile_size, overlap)
+    if _check_format(fmt) == 'jpg' and getattr(enc, 'alpha', False):
+        raise ValueError("fmt='jpg' cannot hold the alpha channel of an RGBA encode: write the pyramid with fmt='png'")
     if _check_format(fmt) == 'jpg':
         from .jpeg_hip import check_optimize, check_params, check_progressive
         check_params(quality, subsampling)

@@ -460,6 +460,18 @@ class CiaoSR(BasicRestorer):
         return scene_render.encode(self, lq, options, max_scale)
 
     @torch.no_grad()
+    def encode_rgba(self, lq4, options=None, max_scale=None):
+        """`encode` of an RGBA image [1, 4, h, w] (float, R G B A in [0, 1]) as a batch of two: item 0 the colour as stored (not
+        premultiplied, whatever lies under transparent pixels), item 1 the alpha plane in all three channels; both go through the same
+        model, options, tiling and scenes, and `enc.alpha` is set.  Every render of such an encode returns with `as_u8` ONE uint8
+        [H, W, 4] device image, bytes B G R A (`metrics_hip.tensor2img_bgra_u8`: the colour bytes are `tensor2img_u8`'s of item 0,
+        bitwise the render of the colour image alone; A = (4899 R + 9617 G + 1868 B + 8192) >> 14 of item 1's bytes), and without it
+        the fp32 batch of two (colour, alpha as grey).  Outside a view the alpha item is 0 and the colour item the caller's `fill`.
+        `render_pyramid` resizes colour and alpha separately below the LR size (not Pillow's premultiplied RGBA resize).  A tensor
+        that is not [1, 4, h, w] is a ValueError."""
+        return scene_render.encode_rgba(self, lq4, options, max_scale)
+
+    @torch.no_grad()
     def render(self, enc, size=None, scale=None, window=None, as_u8=False):
         """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
         round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,

@@ -302,6 +302,7 @@ class EncodedImage:
         self.max_scale = max_scale
         self.cache = SceneCache(budget_bytes, build)
         self.view_tiles = None          # render_view's frame list on the device, uploaded by the first view render
+        self.alpha = False              # CiaoSR.encode_rgba: the batch is (colour, alpha as grey) of ONE RGBA image
 
     @property
     def shape(self):

@@ -39,6 +39,32 @@ def encode(r, lq, options=None, max_scale=None):
     return enc
 
 
+def encode_rgba(r, lq4, options=None, max_scale=None):
+    """`encode` of the two-item batch of an RGBA image [1, 4, h, w]: item 0 the colour as stored (not premultiplied), item 1 the alpha
+    plane in all three channels; `enc.alpha` marks it for the renders."""
+    if not isinstance(lq4, torch.Tensor) or lq4.dim() != 4 or lq4.shape[0] != 1 or lq4.shape[1] != 4:
+        shape = tuple(lq4.shape) if isinstance(lq4, torch.Tensor) else type(lq4).__name__
+        raise ValueError(f'encode_rgba expects one RGBA image [1, 4, h, w], got {shape}')
+    enc = encode(r, torch.cat([lq4[:, :3], lq4[:, 3:4].expand(-1, 3, -1, -1)], 0), options, max_scale)
+    enc.alpha = True
+    return enc
+
+
+ALPHA_FILL = (0.0, 0.0, 0.0)                  # outside a view the alpha item is 0: transparent
+
+
+def is_alpha(enc):
+    """Whether `enc` is an `encode_rgba` result (any other record, a test's stand-in included, is not)."""
+    return bool(getattr(enc, 'alpha', False))
+
+
+def _finish(tg, r, enc, b, acc):
+    """`tg.finish` of batch item b: the alpha item of an RGBA encode ends a view with ALPHA_FILL instead of the caller's fill."""
+    if is_alpha(enc) and b == 1 and isinstance(tg, ViewTarget):
+        return tg.finish(r, acc, ALPHA_FILL)
+    return tg.finish(r, acc)
+
+
 # -- targets ----------------------------------------------------------------------------------------------------------------------------
 class GridTarget:
     """A resolved scene.Grid: the window `win` of the ht x wt grid.  `tiles`: index -> `scene.plan_window`'s record of every LR tile the
@@ -124,8 +150,10 @@ class ViewTarget:
             q_index, coord, cell = hip_ops.view_select(m, hv, wv, frame, k, len(self.frames), self.ws, n)
         hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell)[0])
 
-    def finish(self, r, acc):
-        return hip_ops.denorm_clamp(hip_ops.view_finalize(*acc, self.fill, r.rgb_mean, r.rgb_std), *self.size, r.rgb_mean, r.rgb_std)
+    def finish(self, r, acc, fill=None):
+        """`fill`: the item's own (None: the view's)."""
+        fill = self.fill if fill is None else fill
+        return hip_ops.denorm_clamp(hip_ops.view_finalize(*acc, fill, r.rgb_mean, r.rgb_std), *self.size, r.rgb_mean, r.rgb_std)
 
 
 def view_blocks(r, enc, m, frames):
@@ -191,11 +219,12 @@ def resolve(r, enc, targets):
     return out
 
 
-def _stacked(outs, as_u8):
+def _stacked(outs, as_u8, alpha=False):
+    """The items' outputs as one tensor; with `as_u8` the 8-bit image: BGR, or BGRA of the (colour, alpha) pair of an RGBA encode."""
     out = torch.stack(outs)
     if as_u8:
         from . import metrics_hip
-        return metrics_hip.tensor2img_u8(out)
+        return metrics_hip.tensor2img_bgra_u8(out) if alpha else metrics_hip.tensor2img_u8(out)
     return out
 
 
@@ -204,7 +233,7 @@ def render_one(r, enc, tg, as_u8=False):
     """The single calls `render` / `render_view`, of a resolved target: per batch item, every scene taken with `enc.cache.get` when its
     tile's turn comes -- no walk, no batched trunk, no side stream."""
     if isinstance(tg, GridTarget) and tg.tiles is None:
-        return _stacked(tg.render_whole(r, enc), as_u8)
+        return _stacked(tg.render_whole(r, enc), as_u8, is_alpha(enc))
     outs = []
     for b in range(enc.x.shape[0]):
         if isinstance(tg, ViewTarget):
@@ -212,8 +241,8 @@ def render_one(r, enc, tg, as_u8=False):
         acc = tg.alloc(enc.x.device)
         for k, origin in tg.touched().items():
             tg.query(r.generator, k, enc.cache.get((b, origin)), acc)
-        outs.append(tg.finish(r, acc))
-    return _stacked(outs, as_u8)
+        outs.append(_finish(tg, r, enc, b, acc))
+    return _stacked(outs, as_u8, is_alpha(enc))
 
 
 # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------------
@@ -282,8 +311,8 @@ def render_many(r, enc, targets, as_u8=False):
             for i in users[k]:
                 tgs[i].query(r.generator, k, tile_scene, acc[i])
         for i, tg in enumerate(tgs):
-            outs[i].append(tg.finish(r, acc[i]))
-    return [_stacked(o, as_u8) for o in outs]
+            outs[i].append(_finish(tg, r, enc, b, acc[i]))
+    return [_stacked(o, as_u8, is_alpha(enc)) for o in outs]
 
 
 def prefetch(r, enc, targets):
@@ -306,7 +335,7 @@ def plan_pyramid(r, enc, size=None, scale=None):
     """The level sizes of `render_pyramid` and the index of the smallest model level; its ValueErrors.  Pure host work."""
     from . import pyramid
     nb, _, h, w = enc.x.shape
-    if nb != 1:
+    if nb != (2 if is_alpha(enc) else 1):
         raise ValueError(f'render_pyramid takes one image, got a batch of {nb}')
     ht, wt = sc.target_size(h, w, size, scale)
     if ht < h or wt < w:
@@ -323,4 +352,12 @@ def render_pyramid(r, enc, size=None, scale=None):
     sizes, first = plan_pyramid(r, enc, size, scale)
     model_levels = render_many(r, enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
     base = model_levels[0]
-    return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)
+    if not is_alpha(enc):
+        return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)
+    # RGBA: colour and alpha are resized on their own (Pillow's resize of the RGB image and of the A band, NOT its premultiplied
+    # resize of an RGBA image), then packed
+    from . import metrics_hip
+    colour, grey = base[:, :, :3].contiguous(), base[:, :, 3:4].expand(-1, -1, 3).contiguous()
+    small = [metrics_hip.pack_bgra_u8(degrade.resize_bicubic_u8(colour, (wl, hl)), degrade.resize_bicubic_u8(grey, (wl, hl)))
+             for hl, wl in sizes[:first]]
+    return small + list(model_levels)

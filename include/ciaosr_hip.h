@@ -838,6 +838,41 @@ int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, in
                                int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- RGBA: 8-bit images with an alpha channel, and their PNG files (colour type 6; version 320) -------------------------
+ * An RGBA render is a render of two batch items: the colour image, and the alpha plane copied into three channels.  The colour bytes
+ * of a pixel are ciaosr_tensor2img_u8's of item 0; with (B, G, R) = ciaosr_tensor2img_u8's bytes of item 1, its alpha is
+ * A = (4899 R + 9617 G + 1868 B + 8192) >> 14 in integers (the weights sum to 16384: a grey v, v, v gives v).
+ * colour_chw, alpha_chw: fp32 [3][H][W] RGB -> dst[y * dst_pitch + 4 x + c] bytes in B G R A order, in one pass; every byte by
+ * ciaosr_tensor2img_u8's rule (one fp32 multiply, round half to even, clamp, NaN -> 0).  dst_pitch >= 4 W (a 4-byte aligned dst and
+ * pitch get one 32-bit store per pixel; any other is written in single bytes).  H <= 65535. */
+int ciaosr_tensor2img_bgra_u8(const float* colour_chw, const float* alpha_chw, int H, int W, unsigned char* dst, size_t dst_pitch,
+                              void* stream);
+/* The same packing from two 8-bit images (the resized pyramid levels): bgr [H][W][3] B G R with `pitch` >= 3 W gives B G R, grey_bgr
+ * likewise with `pitch_grey` gives A by the formula above.  dst as above. */
+int ciaosr_pack_bgra_u8(const unsigned char* bgr, size_t pitch, const unsigned char* grey_bgr, size_t pitch_grey, int H, int W,
+                        unsigned char* dst, size_t dst_pitch, void* stream);
+/* The four-byte-per-pixel siblings of the PNG calls above, with the same arguments and contracts; where those say 3 W these say 4 W.
+ * rows of one band: rows_per_band if > 0, else max(1, 131072 / (4 W + 1)).  src[y * pitch + 4 x + c], pitch >= 4 W, src and pitch
+ * 4-byte ALIGNED (a pixel is one 32-bit load; a crop view of an aligned image is aligned) else CIAOSR_ERR_BAD_ARG; bgr = 1: the bytes
+ * of a pixel are B G R A (ciaosr_tensor2img_bgra_u8's order), 0: R G B A.  A row of dst is 1 + 4 W bytes: the filter type, then the
+ * filtered bytes in R G B A order.  The left predecessor of a byte is the same channel of the pixel before it (four bytes back), the
+ * upper one the same byte of the row above; zeros stand left of column 0 and above row 0, of a crop too.  The filter choice, the
+ * histogram, the Adler partials and the plan, scan and pack stages are the three-byte calls' own on the longer rows.  Tile t of
+ * ciaosr_png_rgba_encode_tiles_u8 is byte for byte ciaosr_png_rgba_encode_u8 of the pitched crop src + y0 * pitch + 4 * x0: four
+ * launches and two synchronising copies, whatever n_tiles.  The host wraps a stream with IHDR colour type 6. */
+int ciaosr_png_rgba_rows_per_band(int W, int rows_per_band);
+int ciaosr_png_rgba_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* dst,
+                              unsigned int* hist, unsigned int* adler, void* stream);
+size_t ciaosr_png_rgba_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png_rgba_capacity_bytes(int H, int W, int rows_per_band);
+int ciaosr_png_rgba_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                              size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t ciaosr_png_rgba_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                    int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Baseline JPEG encoding of 8-bit images (ciaosr_amd/jpeg_hip.py; DESIGN 4.1i-d holds the format contract) ----------------------
  * The device makes the entropy-coded data of ONE interleaved scan of a baseline file -- libjpeg's integer pipeline as Pillow drives
  * it: 16-bit fixed-point RGB -> YCbCr, 4:4:4 or 4:2:0 with the h2v2 box filter, the "islow" forward DCT, the Annex K tables scaled by

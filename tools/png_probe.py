@@ -46,6 +46,16 @@ device-to-host copy followed by `PIL.Image.save(progressive=True)` into memory. 
 call: (d) `encode_jpeg_tiles(progressive=True)`, (e) `encode_jpeg_tiles(optimize=True)`, (f) the copy followed by one progressive Pillow
 file per tile.  Protocol as for `--leg jpeg-opt`; the files of (a) and (c), and of (d) and (f), are compared byte for byte; the sizes of
 the progressive and the optimised baseline files and the kernel times by tag (prog_runs among them) are recorded.
+
+    python tools/png_probe.py --leg rgba [--sizes 768x768 5424x8160] [--out FILE]
+
+RGBA files (colour type 6) from uint8 [H, W, 4] B G R A device images: (a) `png_hip.encode_png(img, 'bgra')` against (b) the copy to the
+host + `PIL.Image.save` of the same RGBA pixels.  Cases: the first size as a 'view' (noisy colour, alpha 255 inside a rectangle turned by
+30 degrees and 0 in the corners outside it), every other size with a 'noisy' alpha (uniform random bytes) and with a 'sprite' alpha (an
+ellipse with soft edges: about 70 % of the pixels fully transparent; the colour under them stays, as a render leaves it; 'sprite0' is
+the same image with that colour set to 0, as many files store it: the case the literal-only coder is worst at).  Wall time
+runs from the device image (after a synchronize) to the file's bytes on the host; the legs alternate; the file sizes of both and the
+kernel times of (a) are recorded.  Default --out: profiles/png_rgba.txt.
 """
 import json
 import subprocess
@@ -270,6 +280,63 @@ def run_legs(args, legs):
     return times
 
 
+def rgba_cases(h, w, first, dev):
+    """[(name, uint8 [h, w, 4] B G R A device image)]: 'view' for the first size, else 'noisy' and 'sprite' alphas over the noisy colour."""
+    from ciaosr_amd.metrics_hip import pack_bgra_u8
+    colour = make_image(h, w, 'noisy', dev)
+    y = (torch.arange(h, dtype=torch.float32, device=dev) + 0.5 - h / 2)[:, None]
+    x = (torch.arange(w, dtype=torch.float32, device=dev) + 0.5 - w / 2)[None, :]
+
+    def with_alpha(a):
+        return pack_bgra_u8(colour, a.to(torch.uint8)[:, :, None].expand(-1, -1, 3).contiguous())
+    if first:
+        c, s_ = 0.8660254, 0.5                                          # a rectangle of 0.7 h x 0.7 w turned by 30 degrees
+        u, v = c * y + s_ * x, -s_ * y + c * x
+        return [('view', with_alpha(((u.abs() < 0.35 * h) & (v.abs() < 0.35 * w)) * 255))]
+    g = torch.Generator(device='cpu').manual_seed(h * 11 + w)
+    noisy = torch.randint(0, 256, (h, w), generator=g, dtype=torch.int16).to(dev)
+    r = ((y / (0.309 * h)) ** 2 + (x / (0.309 * w)) ** 2).sqrt()       # pi * 0.309^2 = 0.30 of the pixels lie inside
+    sprite = ((1.0 - r) * (0.309 * min(h, w)) / 8.0 + 0.5).clamp(0, 1).mul(255).round()      # an edge eight pixels wide
+    cleared = with_alpha(sprite)
+    cleared[:, :, :3] *= (cleared[:, :, 3:4] != 0)                      # the colour under fully transparent pixels set to 0, as many files store it
+    return [('noisy', with_alpha(noisy)), ('sprite', with_alpha(sprite)), ('sprite0', cleared)]
+
+
+def rgba_leg(args, say):
+    import io
+    from PIL import Image
+    from ciaosr_amd.png_hip import encode_png
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def pil_rgba(img):
+        bio = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(img.cpu().numpy()[:, :, [2, 1, 0, 3]]), 'RGBA').save(bio, format='PNG')
+        return bio.getvalue()
+
+    for k, size in enumerate(args.sizes):
+        h, w = (int(v) for v in size.split('x'))
+        for name, img in rgba_cases(h, w, k == 0 and 'view' in args.rgba_cases, dev):
+            if name not in args.rgba_cases:
+                continue
+            torch.cuda.synchronize()
+            legs = {'a': lambda: encode_png(img, 'bgra'), 'b': lambda: pil_rgba(img)}
+            times = run_legs(args, legs)
+            mine, pil = legs['a'](), legs['b']()
+            same = np.array_equal(np.asarray(Image.open(io.BytesIO(mine))), np.asarray(Image.open(io.BytesIO(pil))))
+            a = img[:, :, 3]
+            say(f'{h} x {w} {name}: alpha 0 on {(a == 0).float().mean().item():.3f}, 255 on {(a == 255).float().mean().item():.3f} of the pixels; '
+                f'decoded pixels identical: {same}; file bytes device {len(mine)}, Pillow {len(pil)} ({len(mine) / len(pil):.4f})')
+            say(f'  (a) encode_png(bgra) on the device  wall s: {stats(times["a"])}')
+            say(f'  (b) copy to the host + PIL save     wall s: {stats(times["b"])}')
+            gap = statistics.mean(times['b']) - statistics.mean(times['a'])
+            spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', 'b'))
+            say(f'  (b) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                f'{"device encoder faster beyond the spread" if gap > spread else ("host encoder faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                f'ratio (b) / (a) {statistics.mean(times["b"]) / statistics.mean(times["a"]):.2f}x')
+            say(f'  (a) kernels: {kernels(legs["a"])}')
+            del img
+
+
 def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
@@ -437,7 +504,7 @@ def jpeg_prog_leg(args, say):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -447,6 +514,8 @@ def main(argv=None):
     p.add_argument('--quality', type=int, default=90, help='jpeg: the quality of every JPEG file')
     p.add_argument('--sizes', nargs='+', default=None)
     p.add_argument('--contents', nargs='+', default=['smooth', 'noisy'], choices=['smooth', 'noisy'])
+    p.add_argument('--rgba-cases', nargs='+', default=['view', 'noisy', 'sprite', 'sprite0'], choices=['view', 'noisy', 'sprite', 'sprite0'],
+                   help='rgba: the cases to run (view on the first size, the others on every later size)')
     p.add_argument('--warmup', type=int, default=2)
     p.add_argument('--rounds', type=int, default=5)
     p.add_argument('--out', default=None)
@@ -460,8 +529,9 @@ def main(argv=None):
     jpeg = args.leg in ('jpeg', 'jpeg-opt', 'jpeg-prog')
     if args.leg in ('jpeg-opt', 'jpeg-prog'):
         args.contents = ['noisy']
-    args.sizes = args.sizes or (['5424x8160'] if tiles else ['5424x8160', '768x768'])
-    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
+    rgba = args.leg == 'rgba'
+    args.sizes = args.sizes or (['5424x8160'] if tiles else ['768x768', '5424x8160'] if rgba else ['5424x8160', '768x768'])
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -472,10 +542,12 @@ def main(argv=None):
         print(s, flush=True)
         lines.append(s)
 
-    say(f'tools/png_probe.py{" --leg " + args.leg if tiles or jpeg else ""} --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
+    say(f'tools/png_probe.py{" --leg " + args.leg if tiles or jpeg or rgba else ""} --sizes {" ".join(args.sizes)} --contents {" ".join(args.contents)} --warmup {args.warmup} --rounds {args.rounds}: '
         f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, {os.cpu_count()} host CPUs visible')
     if tiles:
         tiles_leg(args, say)
+    if rgba:
+        rgba_leg(args, say)
     if args.leg == 'jpeg':
         jpeg_leg(args, say)
     if args.leg == 'jpeg-opt':
@@ -483,7 +555,7 @@ def main(argv=None):
     if args.leg == 'jpeg-prog':
         jpeg_prog_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
-        for size in ([] if tiles or jpeg else args.sizes):
+        for size in ([] if tiles or jpeg or rgba else args.sizes):
             h, w = (int(v) for v in size.split('x'))
             for content in args.contents:
                 img = make_image(h, w, content, dev)

@@ -33,6 +33,13 @@ files, smaller, the same pixels; the manifest does not change.
 ciaosr_amd/niqe_hip.py): computed on the device from the 8-bit image, before any encoding, Y channel, no border cropped.  The values are
 printed and written to DIR/niqe.json as {file name: value}; an output too small for two 96x96 blocks gets null.  Pyramid tiles are not
 scored, and no output changes.
+`--alpha` keeps the file's transparency: the image is read as RGBA (RGBA, LA and palette files with a tRNS chunk), encoded as a batch of
+two -- the colour as stored and the alpha plane as a grey image, both through the same model (CiaoSR.encode_rgba) -- and every --scale,
+--view and --dzi output is rendered as a uint8 B G R A image on the device and written as an RGBA PNG by the device coder (as --jpeg
+forces the device path, with or without --gpu-png).  The colour bytes are those of the run without the flag on the colour image; alpha is
+the integer luma of the rendered alpha image; outside a view the pixels are transparent (A = 0).  `--niqe` scores the colour part.  A
+file without a transparent pixel is reported in one line and takes the plain path: its outputs are byte for byte those of the run
+without the flag.  Not with --jpeg: JPEG files have no alpha.
 """
 import argparse
 import os
@@ -66,6 +73,8 @@ def parse_args(argv=None):
                    help='with --jpeg: per-file Huffman tables made on the GPU, the files of Pillow\'s optimize=True (default off)')
     p.add_argument('--jpeg-progressive', action='store_true',
                    help='with --jpeg: progressive files coded on the GPU, the files of Pillow\'s progressive=True (default off)')
+    p.add_argument('--alpha', action='store_true',
+                   help='keep the transparency of the input: alpha goes through the model as a grey image, outputs are RGBA PNG files (default off)')
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
@@ -83,6 +92,8 @@ def parse_args(argv=None):
         p.error('--size belongs to --view')
     if args.jpeg is not None and not 1 <= args.jpeg <= 100:
         p.error('--jpeg takes a quality in 1..100')
+    if args.alpha and args.jpeg is not None:
+        p.error('--alpha writes RGBA PNG files: JPEG has no alpha channel, drop --jpeg')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
     if args.jpeg_progressive and args.jpeg is None:
@@ -113,7 +124,7 @@ def main(argv=None):
     from ciaosr_amd import metrics
     from ciaosr_amd.checkpoint import load_checkpoint
     from ciaosr_amd.config import Config
-    from ciaosr_amd.imageio import imread_rgb01, imwrite
+    from ciaosr_amd.imageio import imread_rgb01, imread_rgba01, imwrite
 
     cfg = Config.fromfile(args.config)
     if args.checkpoint in (None, 'None'):
@@ -132,11 +143,20 @@ def main(argv=None):
         load_checkpoint(model, args.checkpoint, map_location='cpu')
     model = model.to(dev).eval()
 
-    lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
+    alpha = False
+    if args.alpha:
+        lq4, opaque = imread_rgba01(args.image)
+        if opaque:
+            print(f'{args.image}: no transparent pixel, --alpha changes nothing')
+        alpha = not opaque
     wanted = args.scale or [v[2] for v in args.view]
     if args.dzi is not None:
         wanted = wanted + [args.dzi]
-    enc = model.encode(lq, max_scale=args.max_scale or max(wanted))
+    if alpha:
+        enc = model.encode_rgba(lq4.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted))
+    else:
+        lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
+        enc = model.encode(lq, max_scale=args.max_scale or max(wanted))
     name = os.path.splitext(os.path.basename(args.image))[0]
     from ciaosr_amd.scene import Grid, View, view_matrix
     form = output_format(args)
@@ -149,7 +169,7 @@ def main(argv=None):
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
-    as_u8 = gpu_png or form['fmt'] == 'jpg'
+    as_u8 = gpu_png or form['fmt'] == 'jpg' or alpha
     outs = model.render_many(enc, targets, as_u8=as_u8) if targets else []           # one walk over the tile scenes for every output
     scores = {}
     if args.niqe and targets:
@@ -159,6 +179,8 @@ def main(argv=None):
     for path, out in zip(paths, outs):
         if args.niqe:
             img = out if as_u8 else tensor2img_u8(out)                 # the bytes the file holds (bitwise metrics.tensor2img)
+            if alpha:
+                img = img[:, :, :3].contiguous()                       # the colour part: tensor2img_u8 of item 0
             try:
                 niqe_hip.geometry(img.shape[0], img.shape[1])
                 scores[os.path.basename(path)] = niqe_hip.niqe_u8(img, params)
@@ -169,6 +191,10 @@ def main(argv=None):
             from ciaosr_amd.jpeg_hip import imwrite_gpu_jpeg
             imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
+        elif alpha:
+            from ciaosr_amd.png_hip import imwrite_gpu
+            imwrite_gpu(out, path, order='bgra')                       # uint8 [H, W, 4] B G R A on the device
+            print(f'{path}: {out.shape[0]} x {out.shape[1]} RGBA')
         elif gpu_png:
             from ciaosr_amd.png_hip import imwrite_gpu
             imwrite_gpu(out, path)                                     # uint8 [H, W, 3] BGR on the device
