@@ -230,6 +230,17 @@ SIGNATURES = {
     'ciaosr_png_rgba_tiles_workspace_bytes': (_S, [_P, _I, _I]),
     'ciaosr_png_rgba_tiles_capacity_bytes': (_S, [_P, _I, _I]),
     'ciaosr_png_rgba_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    # the match coder (png_hip matches=True): the same arguments; capacities are the literal coder's
+    'ciaosr_png_lz_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_lz_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_lz_tiles_workspace_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_lz_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_rgba_lz_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_rgba_lz_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_rgba_lz_tiles_workspace_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_rgba_lz_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_deflate_lz_workspace_bytes': (_S, [_S, _I]),
+    'ciaosr_deflate_lz_u8': (_I, [_P, _P, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
     'ciaosr_jpeg_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_jpeg_capacity_bytes': (_S, [_I, _I, _I]),
     'ciaosr_jpeg_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),

@@ -1,5 +1,6 @@
 // PNG encoding of an 8-bit image on the device, opt-in through `test_cfg.gpu_png` (ciaosr_amd/png_hip.py): the scanline filter and a
-// literal-only dynamic-Huffman deflate coder.  The container (signature, IHDR, IDAT, IEND and the chunk CRCs) is put together by the host.
+// literal-only dynamic-Huffman deflate coder; the *_lz_* entry points add LZ77 matches from a fixed set of distances (further down:
+// "LZ77 matches"), and without them nothing here runs differently.  The container (signature, IHDR, IDAT, IEND and the chunk CRCs) is put together by the host.
 //
 // Stage 1, png_filter_kernel: one workgroup owns a band of `rows_per_band` image rows.  Per row it evaluates the five PNG filters
 // (None, Sub, Up, Average, Paeth; 3 bytes per pixel, predecessors are the RAW pixels, the row above row 0 is zeros), picks the one whose
@@ -676,7 +677,8 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     const bool last = p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1;
     const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
     const u64 lo = p.out_offs[band], hi = lo + p.seg_bytes[band];         // tiles: a trailer and a header lie before the next band
-    if (p.mode[band] == 0u) {                               // stored blocks of at most 65535 bytes: 5 framing bytes each
+    if (p.mode[band] == 2u) return;                         // a band in match mode (the lz entry points only) is deflate_lz_pack_kernel's
+    if (p.mode[band] == 0u) {                              // stored blocks of at most 65535 bytes: 5 framing bytes each
         const u64 nblk = (n + kStoredMax - 1) / kStoredMax;
         for (u64 j = tid; j < hi - lo; j += kThreads) {
             const u64 blk = j / (kStoredMax + 5ull);
@@ -778,6 +780,551 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
 }
 
+// ---- LZ77 matches (opt-in: the *_lz_* entry points) ------------------------------------------------------------------------------
+// The contract, which tests/png_match_ref.py restates: a band is parsed in chunks of 4096 bytes counted from its start.  At position i
+// the candidate distances are D = (1, 2, 3, 4, 6, 8, 12, 16, line - bpp, line, line + bpp), line the scanline length (line = 0: the first
+// eight only); a candidate above 32768 or above i's offset in the band is skipped, so nothing is read from before the band.  The length
+// for d is the run of data[i + j] == data[i + j - d], capped at 258 and at the end of the chunk (and so of the band); the longest
+// candidate wins, ties go to the earliest in D, and it is a match iff its length is >= 8.  The parse is greedy from every chunk's start.
+//
+//   deflate_lz_match_kernel  one workgroup per chunk.  The chunk and its 16 predecessors are staged in LDS (the three line distances
+//                            read global memory).  Per candidate a 4096-bit equality mask is built with one ballot per wave and pass;
+//                            the run at i is a count of trailing ones over at most six words.  next[i] = i + (match ? length : 1);
+//                            what the greedy walk visits is what is reachable from position 0, marked by pointer doubling (at most
+//                            12 rounds, ended as soon as next^(2^k)[0] is the chunk's end).  The visited positions' tokens -- 16 bits:
+//                            a literal is its byte, a match 0x8000 | index into D << 9 | length - 3 -- are compacted with a prefix sum
+//                            to the chunk's slot (2 bytes per filtered byte at most) and counted in LDS, then added to the band's
+//                            286 + 30 histogram with integer atomics (order-independent; the table is zeroed by a memset).
+//   deflate_lz_plan_kernel   one wave per band, after deflate_plan_kernel: both codes by the same construction, HLIT / HDIST trimmed,
+//                            one run-length coded sequence of code lengths, a single used distance symbol alone with length 1, the
+//                            exact size; the band goes to match mode (mode 2) iff that is SMALLER than what deflate_plan_kernel chose.
+//   deflate_lz_pack_kernel   one workgroup per band in match mode: as deflate_pack_kernel, over tokens.  A token is at most 48 bits,
+//                            put in two parts of at most 20 and 28; a chunk's tokens cover at most 4096 bytes at no more than 15 bits
+//                            per byte (a match: 48 bits for 8 bytes or more), so with the header flushed on its own the window bound
+//                            is the literal coder's: 31 + 4096 x 15 < 65536 bits.
+constexpr int kLzChunk = 4096;                     // bytes per parse chunk
+constexpr int kLzPer = kLzChunk / kThreads;        // positions per lane
+constexpr int kLzCand = 11, kLzNear = 8;
+constexpr int kLzMin = 8, kLzMax = 258;
+constexpr int kLzLit = 286, kLzDist = 30;
+constexpr int kLzStride = 320;                     // u32 per band: 286 literal / length entries, then 30 distance entries
+constexpr int kLzHdrWords = 144;                   // 14 + 19 x 3 + 316 x (7 + 7) bits at most
+constexpr int kLzMaskWords = kLzChunk / 64;
+static_assert(kLzPer == kPerLane && kLzChunk == kChunk, "the packer takes a chunk's tokens in one step");
+static_assert(kLzStride >= kLzLit + kLzDist && 32 * kLzHdrWords >= 14 + 57 + (kLzLit + kLzDist) * 14, "lz tables");
+static_assert(31 + kLzChunk * kLitLimit < 32 * (kWin - 1) && kLzHdrWords + 2 < kWin, "packer window");
+
+struct LzP {
+    const unsigned char* data;
+    Bands b;
+    const TileBand* tiles;        // with rects: the line of a band is its tile's, 1 + bpp w
+    const int* rects;
+    u64 line;                     // otherwise: every band's line, 0 = none
+    int bpp;
+    u64 base0;                    // the first band's offset in data: token slots are counted from there
+    const u32* chunk_first;       // [nb + 1] first chunk of every band, or null: uniform bands of cpb chunks
+    u32 cpb;
+    unsigned short* tok;          // [total]: a chunk's tokens start at its first byte's offset
+    u32* cnt;                     // [chunks]
+    u32* hist;                    // [nb][kLzStride], zeroed before deflate_lz_match_kernel
+    u32* table;                   // [nb][kLzStride]: length << 16 | bit-reversed code
+    u32* hdr;                     // [nb][kLzHdrWords]
+    u32* hdr_bits;                // [nb]
+    u32* mode;                    // [nb]: deflate_plan_kernel's choice, 2 where matches are smaller
+    u64* seg_bytes;               // [nb]
+    const u64* out_offs;
+    unsigned char* out;
+};
+
+__device__ __forceinline__ u64 lz_line(const LzP& p, int band) {
+    return p.tiles ? 1ull + (u64)p.bpp * (u64)p.rects[4 * (size_t)p.tiles[band].tile + 3] : p.line;
+}
+// candidate c of a band with scanline length `line`: its distance, 0 when there is none
+__device__ __forceinline__ u32 lz_distance(int c, u64 line, int bpp) {
+    const u32 near[kLzNear] = {1u, 2u, 3u, 4u, 6u, 8u, 12u, 16u};
+    if (c < kLzNear) return near[c];
+    if (line == 0ull) return 0u;
+    const u64 d = c == kLzNear ? line - (u64)bpp : (c == kLzNear + 1 ? line : line + (u64)bpp);
+    return d > 32768ull ? 0u : (u32)d;
+}
+// RFC 1951, 3.2.5: length 3..258 -> symbol, extra bits and their value
+__device__ __forceinline__ void lz_length_code(int length, int* sym, int* nx, u32* xv) {
+    const u32 l = (u32)(length - 3);
+    if (length == kLzMax) {
+        *sym = 285, *nx = 0, *xv = 0u;
+    } else if (l < 8u) {
+        *sym = 257 + (int)l, *nx = 0, *xv = 0u;
+    } else {
+        const int e = 29 - __clz((int)l);                   // floor(log2 l) - 2
+        *sym = 261 + 4 * e + (int)(l >> e & 3u), *nx = e, *xv = l & ((1u << e) - 1u);
+    }
+}
+__device__ __forceinline__ void lz_distance_code(u32 d, int* sym, int* nx, u32* xv) {
+    const u32 v = d - 1u;
+    if (v < 4u) {
+        *sym = (int)v, *nx = 0, *xv = 0u;
+    } else {
+        const int e = 30 - __clz((int)v);                   // floor(log2 v) - 1
+        *sym = 2 * (e + 1) + (int)(v >> e & 1u), *nx = e, *xv = v & ((1u << e) - 1u);
+    }
+}
+__device__ __forceinline__ int lz_length_extra(int sym) { return sym < 265 || sym == 285 ? 0 : (sym - 261) >> 2; }
+__device__ __forceinline__ int lz_distance_extra(int sym) { return sym < 4 ? 0 : (sym >> 1) - 1; }
+
+// the band and the chunk of workgroup `blk`; false: the block has no chunk (uniform bands: the last band is shorter)
+__device__ __forceinline__ bool lz_locate(const LzP& p, u32 blk, int* band, u64* c0) {
+    if (!p.chunk_first) {
+        *band = (int)(blk / p.cpb);
+        *c0 = (u64)(blk % p.cpb) * kLzChunk;
+        return *c0 < band_begin(p.b, *band + 1) - band_begin(p.b, *band);
+    }
+    int lo = 0, hi = p.b.nb - 1;                            // the last band whose first chunk is <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.chunk_first[mid] <= blk) lo = mid;
+        else hi = mid - 1;
+    }
+    *band = lo;
+    *c0 = (u64)(blk - p.chunk_first[lo]) * kLzChunk;
+    return true;
+}
+
+// trailing ones of the mask from bit i on, at most kLzMax
+__device__ __forceinline__ int lz_run(const u64* m, int i) {
+    int w = i >> 6;
+    const int b = i & 63;
+    const u64 x = ~(m[w] >> b);                             // the zeros shifted in end the run at the word's end
+    int r = x ? __ffsll((long long)x) - 1 : 64;
+    if (r < 64 - b) return r;
+    r = 64 - b;
+    while (r < kLzMax && ++w < kLzMaskWords) {
+        const u64 y = ~m[w];
+        if (y) {
+            r += __ffsll((long long)y) - 1;
+            break;
+        }
+        r += 64;
+    }
+    return min(r, kLzMax);
+}
+
+__global__ __launch_bounds__(kThreads) void deflate_lz_match_kernel(LzP p) {
+    __shared__ unsigned char s[16 + kLzChunk];
+    __shared__ u64 mask[kLzCand][kLzMaskWords];
+    __shared__ unsigned short nxt[kLzChunk + 1];
+    __shared__ unsigned short tokv[kLzChunk];
+    __shared__ unsigned char reach[kLzChunk + 1];
+    __shared__ u32 h[kLzStride];
+    __shared__ u32 dist[kLzCand];
+    __shared__ u32 wsum[kWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int band;
+    u64 c0;
+    if (!lz_locate(p, blockIdx.x, &band, &c0)) return;
+    const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
+    const int m = (int)(n - c0 < (u64)kLzChunk ? n - c0 : (u64)kLzChunk);
+    const unsigned char* src = p.data + d0 + c0;            // src[-k] is inside the band for k <= c0
+    if (tid < kLzCand) dist[tid] = lz_distance(tid, lz_line(p, band), p.bpp);
+    for (int i = tid; i < kLzStride; i += kThreads) h[i] = 0u;
+    for (int i = tid; i < 16 + kLzChunk; i += kThreads) {
+        const int k = i - 16;
+        s[i] = (k < m && (k >= 0 || (u64)(-k) <= c0)) ? src[k] : 0;
+    }
+    __syncthreads();
+    // equality masks: word 4 k + wave of candidate c holds positions 256 k + 64 wave + lane
+    for (int k = 0; k < kLzPer; ++k) {
+        const int i = k * kThreads + tid;
+        const u32 v = s[16 + i];
+        const u64 at = c0 + (u64)i;                          // i's offset from the band's start
+#pragma unroll
+        for (int c = 0; c < kLzCand; ++c) {
+            const u32 d = dist[c];
+            bool eq = false;
+            if (i < m && d != 0u && (u64)d <= at) eq = v == (c < kLzNear ? (u32)s[16 + i - (int)d] : (u32)src[(long)i - (long)d]);
+            const u64 bal = __ballot(eq);
+            if (lane == 0) mask[c][k * kWaves + wave] = bal;
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < kLzPer; ++k) {
+        const int i = k * kThreads + tid;
+        int best = 0, bc = 0;
+#pragma unroll
+        for (int c = 0; c < kLzCand; ++c) {
+            const int r = lz_run(mask[c], i);
+            if (r > best) {                                  // strict: ties go to the earliest candidate
+                best = r;
+                bc = c;
+            }
+        }
+        const bool match = best >= kLzMin;
+        nxt[i] = (unsigned short)min(m, i + (match ? best : 1));
+        tokv[i] = match ? (unsigned short)(0x8000 | bc << 9 | (best - 3)) : (unsigned short)s[16 + i];
+        reach[i] = i == 0;
+    }
+    if (tid == 0) {
+        nxt[kLzChunk] = (unsigned short)m;
+        reach[kLzChunk] = 0;
+    }
+    __syncthreads();
+    // what the greedy walk from 0 visits: after round r every position within 2^(r + 1) - 1 steps is marked and nxt is next^(2^(r + 1))
+    for (int round = 0; round < 12; ++round) {
+        for (int k = 0; k < kLzPer; ++k) {
+            const int i = k * kThreads + tid;
+            if (i < m && reach[i]) reach[nxt[i]] = 1;        // a mark seen early is a position the walk visits all the same
+        }
+        unsigned short j2[kLzPer];
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) {
+            const int i = k * kThreads + tid;
+            j2[k] = i < m ? nxt[nxt[i]] : (unsigned short)m;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) {
+            const int i = k * kThreads + tid;
+            if (i < m) nxt[i] = j2[k];
+        }
+        __syncthreads();
+        if (nxt[0] == m) break;                              // the walk ends within the steps already marked (uniform: one LDS word)
+    }
+    // compaction: lane t owns positions [16 t, 16 t + 16)
+    u32 mine = 0u;
+#pragma unroll
+    for (int k = 0; k < kLzPer; ++k) {
+        const int i = tid * kLzPer + k;
+        mine |= (i < m && reach[i]) ? 1u << k : 0u;
+    }
+    const u32 cntl = (u32)__popc(mine);
+    u32 inc = cntl;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const u32 t = __shfl_up(inc, off, kWave);
+        if (lane >= off) inc += t;
+    }
+    if (lane == kWave - 1) wsum[wave] = inc;
+    __syncthreads();
+    u32 before = 0u, total = 0u;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (w < wave) before += wsum[w];
+        total += wsum[w];
+    }
+    unsigned short* out = p.tok + (d0 - p.base0) + c0;       // total <= m tokens
+    u32 at = before + inc - cntl;
+#pragma unroll
+    for (int k = 0; k < kLzPer; ++k) {
+        if (!(mine >> k & 1u)) continue;
+        const u32 t = tokv[tid * kLzPer + k];
+        out[at++] = (unsigned short)t;
+        if (t & 0x8000u) {
+            int sym, nx;
+            u32 xv;
+            lz_length_code((int)(t & 0x1ffu) + 3, &sym, &nx, &xv);
+            atomicAdd(&h[sym], 1u);
+            lz_distance_code(dist[t >> 9 & 15u], &sym, &nx, &xv);
+            atomicAdd(&h[kLzLit + sym], 1u);
+        } else {
+            atomicAdd(&h[t], 1u);
+        }
+    }
+    if (tid == 0) p.cnt[blockIdx.x] = total;
+    __syncthreads();
+    for (int i = tid; i < kLzStride; i += kThreads)
+        if (h[i]) atomicAdd(&p.hist[(size_t)band * kLzStride + i], h[i]);
+}
+
+struct LzSink {
+    u32* words;
+    u64 acc;
+    int nacc, w, bits;
+    __device__ void put(u32 v, int n) {
+        acc |= (u64)v << nacc;
+        nacc += n;
+        bits += n;
+        if (nacc >= 32) {
+            if (w < kLzHdrWords) words[w] = (u32)acc;
+            ++w;
+            acc >>= 32;
+            nacc -= 32;
+        }
+    }
+    __device__ void finish() {
+        for (; w < kLzHdrWords; ++w) {
+            words[w] = (u32)acc;
+            acc = 0ull;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kWave) void deflate_lz_plan_kernel(LzP p) {
+    __shared__ u32 f[kLzStride];
+    __shared__ u32 key[kLzLit];
+    __shared__ unsigned short ord[kLzLit];
+    __shared__ unsigned char len[kLzStride];                // literal / length lengths, then distance lengths at kLzLit
+    __shared__ u32 code[kLzStride];
+    __shared__ int num[kLitLimit + 1];
+    __shared__ u32 next[kLitLimit + 1];
+    __shared__ unsigned char seq[kLzLit + kLzDist];
+    __shared__ unsigned short ent[kLzLit + kLzDist];        // code-length symbols: symbol | extra << 5
+    __shared__ u32 clf[19];
+    __shared__ unsigned char cll[19];
+    __shared__ u32 clc[19];
+    __shared__ int s_nent, s_hlit, s_hdist;
+    const int lane = threadIdx.x, band = blockIdx.x;
+    for (int i = lane; i < kLzStride; i += kWave) {
+        u32 v = i < kLzLit + kLzDist ? p.hist[(size_t)band * kLzStride + i] : 0u;
+        if (i == 256) v += 1u;                              // one end-of-block per band
+        f[i] = v;
+    }
+    __syncthreads();
+    int nd = 0;
+    for (int i = 0; i < kLzDist; ++i) nd += f[kLzLit + i] != 0u;
+    if (nd == 0) return;                                    // no match in the band: the literal coder's block is never larger (uniform)
+    wave_code_lengths(f, kLzLit, kLitLimit, key, ord, num, len);
+    wave_code_lengths(f + kLzLit, kLzDist, kLitLimit, key, ord, num, len + kLzLit);
+    if (lane == 0) {
+        if (nd == 1) len[kLzLit + (ord[0] == 0 ? 1 : 0)] = 0;    // a single distance symbol stands alone: the one incomplete code allowed
+        canonical_codes(len, kLzLit, kLitLimit, num, next, code);
+        canonical_codes(len + kLzLit, kLzDist, kLitLimit, num, next, code + kLzLit);
+        int hlit = 257, hdist = 1;
+        for (int i = 257; i < kLzLit; ++i)
+            if (len[i]) hlit = i + 1;
+        for (int i = 1; i < kLzDist; ++i)
+            if (len[kLzLit + i]) hdist = i + 1;
+        const int ncl = hlit + hdist;
+        for (int i = 0; i < hlit; ++i) seq[i] = len[i];
+        for (int i = 0; i < hdist; ++i) seq[hlit + i] = len[kLzLit + i];
+        for (int i = 0; i < 19; ++i) clf[i] = 0u;
+        int ne = 0, i = 0;
+        while (i < ncl) {
+            const int v = seq[i];
+            int run = 1;
+            while (i + run < ncl && seq[i + run] == v) ++run;
+            i += run;
+            if (v == 0) {
+                while (run > 0) {
+                    if (run >= 11) {
+                        const int t = min(run, 138);
+                        ent[ne++] = (unsigned short)(18 | (t - 11) << 5);
+                        clf[18]++;
+                        run -= t;
+                    } else if (run >= 3) {
+                        ent[ne++] = (unsigned short)(17 | (run - 3) << 5);
+                        clf[17]++;
+                        run = 0;
+                    } else {
+                        ent[ne++] = 0;
+                        clf[0]++;
+                        --run;
+                    }
+                }
+            } else {
+                ent[ne++] = (unsigned short)v;
+                clf[v]++;
+                --run;
+                while (run > 0) {
+                    if (run >= 3) {
+                        const int t = min(run, 6);
+                        ent[ne++] = (unsigned short)(16 | (t - 3) << 5);
+                        clf[16]++;
+                        run -= t;
+                    } else {
+                        ent[ne++] = (unsigned short)v;
+                        clf[v]++;
+                        --run;
+                    }
+                }
+            }
+        }
+        s_nent = ne;
+        s_hlit = hlit;
+        s_hdist = hdist;
+    }
+    __syncthreads();
+    wave_code_lengths(clf, 19, kClLimit, key, ord, num, cll);
+    if (lane == 0) {
+        canonical_codes(cll, 19, kClLimit, num, next, clc);
+        const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        int hclen = 4;
+        for (int k = 0; k < 19; ++k)
+            if (cll[order[k]]) hclen = max(hclen, k + 1);
+        LzSink s{p.hdr + (size_t)band * kLzHdrWords, 0ull, 0, 0, 0};
+        s.put(4u, 3);                                      // BFINAL 0, BTYPE 10 (dynamic)
+        s.put((u32)(s_hlit - 257), 5);
+        s.put((u32)(s_hdist - 1), 5);
+        s.put((u32)(hclen - 4), 4);
+        for (int k = 0; k < hclen; ++k) s.put(cll[order[k]], 3);
+        const int ne = s_nent;
+        for (int k = 0; k < ne; ++k) {
+            const int sym = ent[k] & 31, extra = ent[k] >> 5;
+            s.put(clc[sym] & 0xffffu, (int)(clc[sym] >> 16));
+            if (sym == 16) s.put((u32)extra, 2);
+            if (sym == 17) s.put((u32)extra, 3);
+            if (sym == 18) s.put((u32)extra, 7);
+        }
+        s.finish();
+        u64 payload = 0ull;
+        for (int i = 0; i < kLzLit; ++i) payload += (u64)f[i] * (u64)(len[i] + lz_length_extra(i));
+        for (int i = 0; i < kLzDist; ++i) payload += (u64)f[kLzLit + i] * (u64)(len[kLzLit + i] + lz_distance_extra(i));
+        const u64 lz = ((u64)s.bits + payload + 3ull + 7ull) / 8ull + 4ull;       // + the empty stored block, as the literal coder's
+        p.hdr_bits[band] = (u32)s.bits;
+        if (lz < p.seg_bytes[band]) {                       // a tie stays with deflate_plan_kernel's choice
+            p.mode[band] = 2u;
+            p.seg_bytes[band] = lz;
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < kLzStride; i += kWave) p.table[(size_t)band * kLzStride + i] = code[i];
+}
+
+__global__ __launch_bounds__(kThreads) void deflate_lz_pack_kernel(LzP p) {
+    __shared__ u32 win[kWin];
+    __shared__ u32 tab[kLzStride];
+    __shared__ u32 dcode[kLzCand], dbits[kLzCand];          // per candidate: distance code with its extra bits behind, and the bit count
+    __shared__ u32 wsum[kWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int band = blockIdx.x;
+    if (p.mode[band] != 2u) return;
+    const bool last = p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1;
+    const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
+    const u64 lo = p.out_offs[band], hi = lo + p.seg_bytes[band];
+    for (int i = tid; i < kLzStride; i += kThreads) tab[i] = p.table[(size_t)band * kLzStride + i];
+    for (int i = tid; i < kWin; i += kThreads) win[i] = 0u;
+    __syncthreads();
+    if (tid < kLzCand) {
+        const u32 d = lz_distance(tid, lz_line(p, band), p.bpp);
+        u32 v = 0u, nb = 0u;
+        if (d) {
+            int sym, nx;
+            u32 xv;
+            lz_distance_code(d, &sym, &nx, &xv);
+            const u32 e = tab[kLzLit + sym];
+            v = (e & 0xffffu) | xv << (e >> 16);
+            nb = (e >> 16) + (u32)nx;
+        }
+        dcode[tid] = v;
+        dbits[tid] = nb;
+    }
+    const u64 abase = lo & ~3ull;
+    u32 bitpos = (u32)(lo & 3ull) * 8u;
+    u64 wdone = 0ull;
+    {                                                       // the header, flushed on its own: the window then holds one chunk's bits
+        const u32 hb = p.hdr_bits[band];
+        const int nw = (int)((hb + 31u) >> 5);
+        if (tid < nw) {
+            const u64 x = (u64)p.hdr[(size_t)band * kLzHdrWords + tid] << bitpos;
+            atomicOr(&win[tid], (u32)x);
+            if (x >> 32) atomicOr(&win[tid + 1], (u32)(x >> 32));
+        }
+        __syncthreads();
+        const u32 newpos = bitpos + hb;
+        const int nfull = (int)(newpos >> 5);
+        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
+        const u32 carry = win[nfull];
+        __syncthreads();
+        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
+        __syncthreads();
+        if (tid == 0) win[0] = carry;
+        __syncthreads();
+        wdone += (u64)nfull;
+        bitpos = newpos & 31u;
+    }
+    const u32 chunk0 = p.chunk_first ? p.chunk_first[band] : (u32)band * p.cpb;
+    const unsigned short* toks = p.tok + (d0 - p.base0);
+    u32 ch = 0u;
+    for (u64 c0 = 0; c0 < n; c0 += kLzChunk, ++ch) {
+        const int ntok = (int)p.cnt[chunk0 + ch];
+        const int m0 = tid * kPerLane;
+        const int cnt = m0 >= ntok ? 0 : min(ntok - m0, kPerLane);
+        u32 t[kPerLane];
+        u32 bits = 0u;
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) {
+            t[k] = k < cnt ? (u32)toks[c0 + m0 + k] : 0xffffffffu;
+            if (k < cnt) {
+                if (t[k] & 0x8000u) {
+                    int sym, nx;
+                    u32 xv;
+                    lz_length_code((int)(t[k] & 0x1ffu) + 3, &sym, &nx, &xv);
+                    bits += (tab[sym] >> 16) + (u32)nx + dbits[t[k] >> 9 & 15u];
+                } else {
+                    bits += tab[t[k]] >> 16;
+                }
+            }
+        }
+        u32 inc = bits;
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const u32 v = __shfl_up(inc, off, kWave);
+            if (lane >= off) inc += v;
+        }
+        if (lane == kWave - 1) wsum[wave] = inc;
+        __syncthreads();
+        u32 before = 0u, chunk_bits = 0u;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            if (w < wave) before += wsum[w];
+            chunk_bits += wsum[w];
+        }
+        u32 pos = bitpos + before + inc - bits;
+        int w = (int)(pos >> 5);
+        int nacc = (int)(pos & 31u);
+        u64 acc = 0ull;
+        auto put = [&](u32 v, u32 nb) {                      // nb <= 28 behind nacc < 32
+            acc |= (u64)v << nacc;
+            nacc += (int)nb;
+            if (nacc >= 32) {
+                atomicOr(&win[w], (u32)acc);
+                ++w;
+                acc >>= 32;
+                nacc -= 32;
+            }
+        };
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) {
+            if (k >= cnt) continue;
+            if (t[k] & 0x8000u) {
+                int sym, nx;
+                u32 xv;
+                lz_length_code((int)(t[k] & 0x1ffu) + 3, &sym, &nx, &xv);
+                const u32 e = tab[sym];
+                put((e & 0xffffu) | xv << (e >> 16), (e >> 16) + (u32)nx);
+                const u32 c = t[k] >> 9 & 15u;
+                put(dcode[c], dbits[c]);
+            } else {
+                const u32 e = tab[t[k]];
+                put(e & 0xffffu, e >> 16);
+            }
+        }
+        if (nacc > 0 && acc) atomicOr(&win[w], (u32)acc);
+        __syncthreads();
+        const u32 newpos = bitpos + chunk_bits;
+        const int nfull = (int)(newpos >> 5);
+        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
+        const u32 carry = win[nfull];
+        __syncthreads();
+        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
+        __syncthreads();
+        if (tid == 0) win[0] = carry;
+        __syncthreads();
+        wdone += (u64)nfull;
+        bitpos = newpos & 31u;
+    }
+    if (tid == 0) {
+        u32 pos = bitpos;
+        or_bits(win, pos, tab[256] & 0xffffu);
+        pos += tab[256] >> 16;
+        or_bits(win, pos, last ? 1u : 0u);               // the empty stored block: BFINAL, BTYPE 00, pad, LEN 0, NLEN 0xffff
+        pos = (pos + 3u + 7u) & ~7u;
+        or_bits(win, pos + 16u, 0xffffu);
+        bitpos = pos + 32u;
+        wsum[0] = bitpos;
+    }
+    __syncthreads();
+    flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
+}
+
 static inline int rows_per_band(int W, int rows, int bpp) {
     if (rows > 0) return rows;
     const long L = (long)bpp * W + 1;
@@ -819,6 +1366,83 @@ static inline size_t work_bytes(int nb, size_t filtered_bytes) {
 
 static inline size_t capacity(size_t total, int nb, bool zlib) {
     return total + 5 * (total / kStoredMax + (size_t)nb) + (zlib ? 6 : 0) + 8;
+}
+
+// what the match coder keeps beside the literal coder's Work, carved behind it: the literal coder's layout does not move
+struct LzWork {
+    u32 *hist, *table, *hdr, *hdr_bits, *cnt, *chunk_first;
+    unsigned short* tok;
+};
+static inline void carve_lz(Arena& a, int nb, size_t chunks, size_t total, LzWork* w) {
+    w->hist = a.take<u32>((size_t)nb * kLzStride);
+    w->table = a.take<u32>((size_t)nb * kLzStride);
+    w->hdr = a.take<u32>((size_t)nb * kLzHdrWords);
+    w->hdr_bits = a.take<u32>((size_t)nb);
+    w->cnt = a.take<u32>(chunks);
+    w->chunk_first = a.take<u32>((size_t)nb + 1);
+    w->tok = a.take<unsigned short>(total);
+}
+static inline bool carve_with_lz(void* ws, size_t bytes, int nb, size_t filtered_bytes, size_t chunks, size_t total, Work* w, LzWork* lz,
+                                 size_t* used) {
+    Arena a(ws, bytes);
+    carve_into(a, nb, filtered_bytes, w);
+    carve_lz(a, nb, chunks, total, lz);
+    if (used) *used = a.off;
+    return a.ok;
+}
+static inline size_t lz_work_bytes(int nb, size_t filtered_bytes, size_t chunks, size_t total) {
+    Work w;
+    LzWork lz;
+    size_t used = 0;
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    carve_with_lz(origin, ~(size_t)0, nb, filtered_bytes, chunks, total, &w, &lz, &used);
+    return used;
+}
+static inline u64 lz_chunks_of(u64 bytes) { return (bytes + kLzChunk - 1) / kLzChunk; }
+
+// the match coder's launches around the literal coder's plan: p holds the bands and the literal histograms, q the rest.  `scan` runs
+// between the plans and the packers (the single stream's scan or the tiles').
+template <typename Scan>
+static int run_deflate_lz(DeflateP& p, LzP& q, int nb, size_t chunks, Scan scan, hipStream_t s) {
+    if (hipMemsetAsync(q.hist, 0, (size_t)nb * kLzStride * sizeof(u32), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    {
+        ProfScope prof("deflate_lz_match", s);
+        hipLaunchKernelGGL(deflate_lz_match_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, s, q);
+        int rc = launch_status("deflate_lz_match");
+        if (rc) return rc;
+    }
+    {
+        ProfScope prof("deflate_plan", s);
+        hipLaunchKernelGGL(deflate_plan_kernel, dim3(nb), dim3(kWave), 0, s, p);
+        int rc = launch_status("deflate_plan");
+        if (rc) return rc;
+    }
+    {
+        ProfScope prof("deflate_lz_plan", s);
+        hipLaunchKernelGGL(deflate_lz_plan_kernel, dim3(nb), dim3(kWave), 0, s, q);
+        int rc = launch_status("deflate_lz_plan");
+        if (rc) return rc;
+    }
+    int rc = scan();
+    if (rc) return rc;
+    {
+        ProfScope prof("deflate_pack", s);
+        hipLaunchKernelGGL(deflate_pack_kernel, dim3(nb), dim3(kThreads), 0, s, p);
+        rc = launch_status("deflate_pack");
+        if (rc) return rc;
+    }
+    ProfScope prof("deflate_lz_pack", s);
+    hipLaunchKernelGGL(deflate_lz_pack_kernel, dim3(nb), dim3(kThreads), 0, s, q);
+    return launch_status("deflate_lz_pack");
+}
+static LzP lz_params(const DeflateP& p, const LzWork& lz, u64 line, int bpp, u64 base0, const u32* chunk_first, u32 cpb) {
+    return LzP{p.data, p.b, p.tiles, nullptr, line, bpp, base0, chunk_first, cpb, lz.tok, lz.cnt, lz.hist, lz.table, lz.hdr, lz.hdr_bits,
+               p.mode, p.seg_bytes, p.out_offs, p.out};
+}
+static int scan_single(DeflateP& p, hipStream_t s) {
+    ProfScope prof("deflate_scan", s);
+    hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
+    return launch_status("deflate_scan");
 }
 
 // plan, scan and pack of the bands described by p.b (histograms already in p.hist)
@@ -869,13 +1493,16 @@ struct TilePlan {
     u64 total;                    // bytes of all filtered streams
     size_t capacity;              // bytes the streams can take at most
     size_t o_bands, o_first, o_rects, table_bytes;
+    u64 chunks;                   // parse chunks of all bands; with `lz` the table ends with [chunk_first u32 (nb + 1)] at o_chunks
+    size_t o_chunks;
 };
 // `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
-static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg, int H, int W, std::vector<unsigned char>* table) {
+static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg, int H, int W, std::vector<unsigned char>* table,
+                           bool lz = false) {
     TilePlan t{};
     t.rc = CIAOSR_ERR_BAD_ARG;
     if (!rects || n_tiles < 1 || rows_arg < 0) return t;
-    u64 nb = 0, total = 0;
+    u64 nb = 0, total = 0, chunks = 0;
     size_t cap = 0;
     for (int k = 0; k < n_tiles; ++k) {
         const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
@@ -888,10 +1515,11 @@ static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg,
             return t;
         }
         nb += (u64)ceil_div(h, R);
+        chunks += (u64)(h / R) * lz_chunks_of((u64)R * L) + lz_chunks_of((u64)(h % R) * L);
         total += (u64)h * L;
         cap += capacity((size_t)h * L, ceil_div(h, R), true);
     }
-    if (nb > (u64)INT_MAX / 2) {
+    if (nb > (u64)INT_MAX / 2 || (lz && chunks > (u64)INT_MAX)) {
         t.rc = CIAOSR_ERR_UNSUPPORTED;
         return t;
     }
@@ -904,6 +1532,9 @@ static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg,
     t.o_first = t.o_bands + sizeof(TileBand) * (size_t)nb;
     t.o_rects = t.o_first + sizeof(u32) * ((size_t)n_tiles + 1);
     t.table_bytes = t.o_rects + 4 * sizeof(int) * (size_t)n_tiles;
+    t.chunks = chunks;
+    t.o_chunks = t.table_bytes;
+    if (lz) t.table_bytes += sizeof(u32) * ((size_t)nb + 1);
     if (!table) return t;
     table->resize(t.table_bytes);
     u64* offs = reinterpret_cast<u64*>(table->data());
@@ -926,6 +1557,11 @@ static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg,
     }
     offs[i] = off;
     first[n_tiles] = (u32)i;
+    if (lz) {
+        u32* cf = reinterpret_cast<u32*>(table->data() + t.o_chunks);
+        cf[0] = 0u;
+        for (int j = 0; j < i; ++j) cf[j + 1] = cf[j] + (u32)lz_chunks_of(offs[j + 1] - offs[j]);
+    }
     return t;
 }
 
@@ -939,6 +1575,22 @@ static inline bool carve_tiles(void* ws, size_t bytes, const TilePlan& t, TileWo
     w->table = a.take<unsigned char>(t.table_bytes);
     if (used) *used = a.off;
     return a.ok;
+}
+static inline bool carve_tiles_lz(void* ws, size_t bytes, const TilePlan& t, TileWork* w, LzWork* lz, size_t* used) {
+    Arena a(ws, bytes);
+    carve_into(a, t.nb, (size_t)t.total, &w->w);
+    w->table = a.take<unsigned char>(t.table_bytes);
+    carve_lz(a, t.nb, (size_t)t.chunks, (size_t)t.total, lz);
+    if (used) *used = a.off;
+    return a.ok;
+}
+static inline size_t tile_work_bytes_lz(const TilePlan& t) {
+    TileWork w;
+    LzWork lz;
+    size_t used = 0;
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    carve_tiles_lz(origin, ~(size_t)0, t, &w, &lz, &used);
+    return used;
 }
 static inline size_t tile_work_bytes(const TilePlan& t) {
     TileWork w;
@@ -965,10 +1617,14 @@ static int filter_entry(int bpp, const unsigned char* src, size_t pitch, int H, 
     return run_filter(bpp, src, pitch, H, W, bgr, R, dst, hist, adler, (hipStream_t)stream);
 }
 
-static size_t workspace_entry(int bpp, int H, int W, int rows_per_band_arg) {
+static size_t workspace_entry(int bpp, int H, int W, int rows_per_band_arg, bool lz = false) {
     if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
     const int R = rows_per_band(W, rows_per_band_arg, bpp);
-    return work_bytes(ceil_div(H, R), (size_t)H * ((size_t)bpp * (size_t)W + 1));
+    const size_t L = (size_t)bpp * (size_t)W + 1, total = (size_t)H * L;
+    const int nb = ceil_div(H, R);
+    if (!lz) return work_bytes(nb, total);
+    if ((u64)R * L > kMaxBand) return 0;
+    return lz_work_bytes(nb, total, (size_t)nb * (size_t)lz_chunks_of((u64)R * L), total);
 }
 
 static size_t capacity_entry(int bpp, int H, int W, int rows_per_band_arg) {
@@ -978,7 +1634,8 @@ static size_t capacity_entry(int bpp, int H, int W, int rows_per_band_arg) {
 }
 
 static int encode_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg, unsigned char* out,
-                        size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+                        size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                        bool lz = false) {
     CIAOSR_CHECK_ARG(out && total_bytes && workspace && image_ok(H, W) && source_ok(bpp, src, pitch, W));
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0);
@@ -990,29 +1647,46 @@ static int encode_entry(int bpp, const unsigned char* src, size_t pitch, int H, 
     const u64 total = (u64)H * L;
     if (out_capacity < capacity(total, nb, true)) return CIAOSR_ERR_WORKSPACE;
     Work w;
-    if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    LzWork lw;
+    const u64 cpb = lz_chunks_of((u64)R * L);
+    const size_t chunks = (size_t)nb * (size_t)cpb;
+    if (lz) {
+        if (workspace_bytes < lz_work_bytes(nb, total, chunks, total) ||
+            !carve_with_lz(workspace, workspace_bytes, nb, total, chunks, total, &w, &lw, nullptr))
+            return CIAOSR_ERR_WORKSPACE;
+    } else if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) {
+        return CIAOSR_ERR_WORKSPACE;
+    }
     hipStream_t s = (hipStream_t)stream;
     int rc = run_filter(bpp, src, pitch, H, W, bgr, R, w.filtered, w.hist, w.adler, s);
     if (rc) return rc;
     DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
                out, w.adler, total_bytes};
-    return run_deflate(p, s);
+    if (!lz) return run_deflate(p, s);
+    LzP q = lz_params(p, lw, L, bpp, 0ull, nullptr, (u32)cpb);
+    return run_deflate_lz(p, q, nb, chunks, [&] { return scan_single(p, s); }, s);
 }
 
 static int encode_tiles_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                               int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+                              void* workspace, size_t workspace_bytes, void* stream, bool lz = false) {
     CIAOSR_CHECK_ARG(rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && source_ok(bpp, src, pitch, W));
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
     std::vector<unsigned char> table;
-    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, H, W, &table);
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, H, W, &table, lz);
     CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image
     if (t.rc != CIAOSR_OK) return t.rc;
     if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
     TileWork tw;
-    if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) return CIAOSR_ERR_WORKSPACE;
+    LzWork lw;
+    if (lz) {
+        if (workspace_bytes < tile_work_bytes_lz(t) || !carve_tiles_lz(workspace, workspace_bytes, t, &tw, &lw, nullptr))
+            return CIAOSR_ERR_WORKSPACE;
+    } else if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) {
+        return CIAOSR_ERR_WORKSPACE;
+    }
     const Work& w = tw.w;
     hipStream_t s = (hipStream_t)stream;
     // from pageable memory: the copy has left `table` when the call returns
@@ -1034,6 +1708,17 @@ static int encode_tiles_entry(int bpp, const unsigned char* src, size_t pitch, i
     }
     DeflateP p{w.filtered, Bands{offs, 0ull, 0ull, t.nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 0ull, out,
                w.adler, nullptr, bands};
+    if (lz) {
+        LzP q = lz_params(p, lw, 0ull, bpp, 0ull, reinterpret_cast<const u32*>(tw.table + t.o_chunks), 0u);
+        q.rects = d_rects;
+        auto scan = [&] {
+            TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
+            ProfScope prof("png_tiles_scan", s);
+            hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
+            return launch_status("png_tiles_scan");
+        };
+        return run_deflate_lz(p, q, t.nb, (size_t)t.chunks, scan, s);
+    }
     {
         ProfScope prof("deflate_plan", s);
         hipLaunchKernelGGL(deflate_plan_kernel, dim3(t.nb), dim3(kWave), 0, s, p);
@@ -1127,9 +1812,10 @@ extern "C" int ciaosr_png_rgba_encode_u8(const unsigned char* src, size_t pitch,
     return encode_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
 }
 
-static size_t tiles_workspace_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
-    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? tile_work_bytes(t) : 0;
+static size_t tiles_workspace_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg, bool lz = false) {
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr, lz);
+    if (t.rc != CIAOSR_OK) return 0;
+    return lz ? tile_work_bytes_lz(t) : tile_work_bytes(t);
 }
 static size_t tiles_capacity_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
     const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
@@ -1161,4 +1847,94 @@ extern "C" int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t 
                                                unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
     return encode_tiles_entry(4, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
                               workspace_bytes, stream);
+}
+
+// ---- the match coder's entry points: the same arguments, the same capacities, a larger workspace ----------------------------------
+extern "C" size_t ciaosr_png_lz_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg, true); }
+extern "C" size_t ciaosr_png_rgba_lz_workspace_bytes(int H, int W, int rows_per_band_arg) {
+    return workspace_entry(4, H, W, rows_per_band_arg, true);
+}
+
+extern "C" int ciaosr_png_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                       unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return encode_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream,
+                        true);
+}
+
+extern "C" int ciaosr_png_rgba_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                            unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return encode_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream,
+                        true);
+}
+
+extern "C" size_t ciaosr_png_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg, true);
+}
+extern "C" size_t ciaosr_png_rgba_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg, true);
+}
+
+extern "C" int ciaosr_png_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                             int rows_per_band_arg, unsigned char* out, size_t out_capacity,
+                                             unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_tiles_entry(3, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream, true);
+}
+
+extern "C" int ciaosr_png_rgba_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects,
+                                                  int n_tiles, int rows_per_band_arg, unsigned char* out, size_t out_capacity,
+                                                  unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_tiles_entry(4, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream, true);
+}
+
+// every band has at most ceil(bytes / 4096) <= bytes / 4096 + 1 chunks
+static inline size_t lz_chunk_bound(size_t total_bytes, int n_bands) { return total_bytes / kLzChunk + (size_t)n_bands; }
+
+extern "C" size_t ciaosr_deflate_lz_workspace_bytes(size_t total_bytes, int n_bands) {
+    if (n_bands <= 0 || total_bytes < (size_t)n_bands || lz_chunk_bound(total_bytes, n_bands) > (size_t)INT_MAX) return 0;
+    return lz_work_bytes(n_bands, 0, lz_chunk_bound(total_bytes, n_bands), total_bytes);
+}
+
+extern "C" int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* band_offsets, int n_bands, int line, int bpp,
+                                    unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    CIAOSR_CHECK_ARG(data && band_offsets && out && seg_offsets && workspace && n_bands > 0);
+    CIAOSR_CHECK_ARG(line >= 0 && bpp >= 1 && (line == 0 || line > bpp));                     // line - bpp is a distance: >= 1
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(seg_offsets) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    for (int i = 0; i < n_bands; ++i) {
+        CIAOSR_CHECK_ARG(band_offsets[i + 1] > band_offsets[i]);
+        if (band_offsets[i + 1] - band_offsets[i] > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+    }
+    const u64 total = band_offsets[n_bands] - band_offsets[0];
+    const size_t bound = lz_chunk_bound(total, n_bands);
+    if (bound > (size_t)INT_MAX) return CIAOSR_ERR_UNSUPPORTED;
+    if (out_capacity < capacity(total, n_bands, false)) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    LzWork lw;
+    if (workspace_bytes < lz_work_bytes(n_bands, 0, bound, total) ||
+        !carve_with_lz(workspace, workspace_bytes, n_bands, 0, bound, total, &w, &lw, nullptr))
+        return CIAOSR_ERR_WORKSPACE;
+    std::vector<u32> first((size_t)n_bands + 1);
+    first[0] = 0u;
+    for (int i = 0; i < n_bands; ++i) first[i + 1] = first[i] + (u32)lz_chunks_of(band_offsets[i + 1] - band_offsets[i]);
+    hipStream_t s = (hipStream_t)stream;
+    // from pageable memory: both copies have left the host arrays when the calls return
+    if (hipMemcpyAsync(w.offs_in, band_offsets, ((size_t)n_bands + 1) * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess)
+        return CIAOSR_ERR_LAUNCH;
+    if (hipMemcpyAsync(lw.chunk_first, first.data(), first.size() * sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess)
+        return CIAOSR_ERR_LAUNCH;
+    DeflateP p{data, Bands{w.offs_in, 0ull, 0ull, n_bands}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, seg_offsets, 0ull, out,
+               nullptr, seg_offsets + n_bands};
+    {
+        ProfScope prof("deflate_hist", s);
+        hipLaunchKernelGGL(deflate_hist_kernel, dim3(n_bands), dim3(kThreads), 0, s, p);
+        int rc = launch_status("deflate_hist");
+        if (rc) return rc;
+    }
+    LzP q = lz_params(p, lw, (u64)line, bpp, band_offsets[0], lw.chunk_first, 0u);
+    return run_deflate_lz(p, q, n_bands, (size_t)first[n_bands], [&] { return scan_single(p, s); }, s);
 }

@@ -1,11 +1,17 @@
 """PNG files written from uint8 images on the MI355X (csrc/png_u8.hip), opt-in through `test_cfg.gpu_png`.
 
 The device filters the scanlines (the usual minimum-sum-of-absolute-values rule, per row) and codes them band by band with dynamic
-Huffman blocks of literals -- no LZ77 matches: on this content they gain nothing over filter + Huffman -- into one zlib stream.  The
-host only wraps that stream: signature, IHDR, IDAT chunks, IEND, with `zlib.crc32` for the chunk CRCs.  The files hold other bytes
-than Pillow's but decode to exactly the same pixels.  Two copies synchronise per image: the stream's size, then the stream.  There is
-no CPU fallback: a host array raises.  `encode_png_tiles` codes many crops of one image (the tiles of a pyramid level, pyramid.py) in
-one set of launches and two synchronising copies per call; each file is byte for byte the single call's on that crop.
+Huffman blocks of literals -- by default no LZ77 matches: on photographic content they gain nothing over filter + Huffman -- into one
+zlib stream.  The host only wraps that stream: signature, IHDR, IDAT chunks, IEND, with `zlib.crc32` for the chunk CRCs.  The files
+hold other bytes than Pillow's but decode to exactly the same pixels.  Two copies synchronise per image: the stream's size, then the
+stream.  There is no CPU fallback: a host array raises.  `encode_png_tiles` codes many crops of one image (the tiles of a pyramid
+level, pyramid.py) in one set of launches and two synchronising copies per call; each file is byte for byte the single call's on that
+crop.
+
+`matches=True` (every entry point; off by default, and then every byte is as before) lets a band use LZ77 matches from a fixed set of
+distances -- 1, 2, 3, 4, 6, 8, 12, 16 and the scanline length L = 1 + C W with L - C and L + C, lengths of 8 to 258 inside chunks of
+4096 bytes, greedy -- where that makes the band smaller: flat regions (a fill, a transparent surround) then cost a few bits per 258
+bytes and not one bit per byte, and no file gets larger.
 
 A uint8 [H, W, 4] image (`order` 'bgra', as `metrics_hip.tensor2img_bgra_u8` makes it, or 'rgba') goes through the four-byte-per-pixel
 siblings of the same calls and becomes a colour type 6 file; every entry point here takes either kind.
@@ -29,6 +35,12 @@ ORDERS = {'bgr': 1, 'rgb': 0}
 ORDERS_RGBA = {'bgra': 1, 'rgba': 0}
 COLOUR_TYPES = {3: 2, 4: 6}                # bytes per pixel -> IHDR colour type
 _ABI = {3: 'ciaosr_png_', 4: 'ciaosr_png_rgba_'}
+
+
+def _check_matches(matches):
+    if not isinstance(matches, bool):
+        raise ValueError(f'matches must be True or False, got {matches!r}')
+    return 'lz_' if matches else ''
 
 
 def _pitch(img):
@@ -122,9 +134,14 @@ def filter_u8(img, order='bgr', rows_per_band=0):
     return stream, hist, adler
 
 
-def deflate_huff(data, band_offsets):
+def deflate_huff(data, band_offsets, matches=False, line=0, bpp=1):
     """Stage 2 alone: raw deflate of the device byte tensor `data`, one segment per band [band_offsets[i], band_offsets[i + 1]) ->
-    list of `bytes`, whose concatenation is one deflate stream.  An empty band raises before anything is launched."""
+    list of `bytes`, whose concatenation is one deflate stream.  An empty band raises before anything is launched.  `matches=True`:
+    the match coder, with the candidate distances `line - bpp`, `line`, `line + bpp` beside the near ones (`line=0`: without)."""
+    _check_matches(matches)
+    line, bpp = int(line), int(bpp)
+    if matches and (line < 0 or bpp < 1 or 0 < line <= bpp):
+        raise ValueError(f'line={line}, bpp={bpp}: line is 0 or above bpp >= 1')
     if not isinstance(data, torch.Tensor) or not data.is_cuda:
         raise CiaoSRHipError('deflate_huff expects a uint8 cuda tensor (no CPU fallback)')
     if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
@@ -138,41 +155,50 @@ def deflate_huff(data, band_offsets):
     dev = data.device
     lib = _lib.load()
     cap = lib.ciaosr_deflate_huff_capacity_bytes(C.c_size_t(max(offs[-1] - offs[0], 0)), nb)
-    nbytes = lib.ciaosr_deflate_huff_workspace_bytes(nb)
+    if matches:
+        nbytes = lib.ciaosr_deflate_lz_workspace_bytes(C.c_size_t(max(offs[-1] - offs[0], 0)), nb)
+    else:
+        nbytes = lib.ciaosr_deflate_huff_workspace_bytes(nb)
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     seg = torch.empty(nb + 1, dtype=torch.int64, device=dev)
     host_offs = (C.c_ulonglong * (nb + 1))(*offs)
-    _lib.call('ciaosr_deflate_huff_u8', hip_ops.ptr(data), host_offs, nb, hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(seg),
-              hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    if matches:
+        _lib.call('ciaosr_deflate_lz_u8', hip_ops.ptr(data), host_offs, nb, line, bpp, hip_ops.ptr(out), C.c_size_t(cap),
+                  hip_ops.ptr(seg), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    else:
+        _lib.call('ciaosr_deflate_huff_u8', hip_ops.ptr(data), host_offs, nb, hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(seg),
+                  hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     so = seg.cpu().tolist()
     raw = out[:so[-1]].cpu().numpy().tobytes()
     return [raw[so[i]:so[i + 1]] for i in range(nb)]
 
 
-def encode_zlib(img, order='bgr', rows_per_band=0):
+def encode_zlib(img, order='bgr', rows_per_band=0, matches=False):
     """The zlib stream of the image's filtered scanlines, made on the device -> bytes.  Synchronises twice: size, then stream."""
+    lz = _check_matches(matches)
     h, w, rows, nb, ch, bgr = _geometry(img, order, rows_per_band)
     dev = img.device
     lib = _lib.load()
     cap = getattr(lib, _ABI[ch] + 'capacity_bytes')(h, w, rows)
-    nbytes = getattr(lib, _ABI[ch] + 'workspace_bytes')(h, w, rows)
+    nbytes = getattr(lib, _ABI[ch] + lz + 'workspace_bytes')(h, w, rows)
     if cap == 0 or nbytes == 0:
         raise CiaoSRHipError(f'encode_png: unsupported geometry {h}x{w}, rows_per_band={rows}')
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call(_ABI[ch] + 'encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, rows, hip_ops.ptr(out),
+    _lib.call(_ABI[ch] + lz + 'encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, rows, hip_ops.ptr(out),
               C.c_size_t(cap), hip_ops.ptr(total), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     n = int(total.item())                                   # copy 1: the size
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the stream
 
 
-def encode_png(img_u8_hwc, order='bgr', rows_per_band=0):
+def encode_png(img_u8_hwc, order='bgr', rows_per_band=0, matches=False):
     """PNG file (bytes) of a uint8 [H, W, 3] device image; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched
     (a crop view of a larger image).  `rows_per_band`: image rows per independently coded band, 0 = about 128 KiB of scanline bytes.
-    A [H, W, 4] image with `order` 'bgra' (as `tensor2img_bgra_u8` makes it) or 'rgba' gives an RGBA file."""
-    z = encode_zlib(img_u8_hwc, order, rows_per_band)
+    A [H, W, 4] image with `order` 'bgra' (as `tensor2img_bgra_u8` makes it) or 'rgba' gives an RGBA file.
+    `matches=True`: bands may use LZ77 matches (see the module's text); the file is never larger and decodes to the same pixels."""
+    z = encode_zlib(img_u8_hwc, order, rows_per_band, matches)
     return container(img_u8_hwc.shape[0], img_u8_hwc.shape[1], z, channels=img_u8_hwc.shape[2])
 
 
@@ -192,9 +218,10 @@ def check_rects(rects, h, w):
     return out
 
 
-def encode_tiles_device(img, rects, order='bgr', rows_per_band=0):
+def encode_tiles_device(img, rects, order='bgr', rows_per_band=0, matches=False):
     """ciaosr_png_encode_tiles_u8 on the current stream, no synchronisation -> (streams uint8 [capacity], offsets int64 [n + 1]) on the
     device: crop k's zlib stream is streams[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps."""
+    lz = _check_matches(matches)
     ch, bgr = _check_image(img, order)
     rows = int(rows_per_band)
     if rows < 0:
@@ -208,39 +235,40 @@ def encode_tiles_device(img, rects, order='bgr', rows_per_band=0):
     lib = _lib.load()
     host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
     cap = getattr(lib, _ABI[ch] + 'tiles_capacity_bytes')(host_rects, n, rows)
-    nbytes = getattr(lib, _ABI[ch] + 'tiles_workspace_bytes')(host_rects, n, rows)
+    nbytes = getattr(lib, _ABI[ch] + lz + 'tiles_workspace_bytes')(host_rects, n, rows)
     if cap == 0 or nbytes == 0:
         raise CiaoSRHipError(f'encode_png_tiles: unsupported geometry ({n} rects, rows_per_band={rows})')
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    _lib.call(_ABI[ch] + 'encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, host_rects, n, rows,
+    _lib.call(_ABI[ch] + lz + 'encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, bgr, host_rects, n, rows,
               hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(offs), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     return out, offs
 
 
-def encode_zlib_tiles(img, rects, order='bgr', rows_per_band=0):
+def encode_zlib_tiles(img, rects, order='bgr', rows_per_band=0, matches=False):
     """The zlib streams of many crops (y0, x0, h, w) of one device image, from ONE set of launches -> list of bytes; stream k is byte
     for byte `encode_zlib(img[y0:y0 + h, x0:x0 + w], ...)`.  Synchronises twice per call, whatever the number of crops: the offsets
     table, then the streams."""
-    out, offs = encode_tiles_device(img, rects, order, rows_per_band)
+    out, offs = encode_tiles_device(img, rects, order, rows_per_band, matches)
     o = offs.cpu().tolist()                                 # copy 1: the offsets
     raw = memoryview(out[:o[-1]].cpu().numpy())             # copy 2: the streams
     return [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
 
 
-def encode_png_tiles(img_u8_hwc, rects, order='bgr', rows_per_band=0):
+def encode_png_tiles(img_u8_hwc, rects, order='bgr', rows_per_band=0, matches=False):
     """PNG files (list of bytes) of the crops `rects` = [(y0, x0, h, w), ...] of a uint8 [H, W, 3] (or [H, W, 4]) device image, coded
-    together: file k is byte for byte `encode_png(img[y0:y0 + h, x0:x0 + w], order, rows_per_band)`.  The rects may overlap.  A bad rect is a
+    together: file k is byte for byte `encode_png(img[y0:y0 + h, x0:x0 + w], order, rows_per_band, matches)`.  The rects may overlap.  A bad rect is a
     ValueError before any device work; two synchronising copies per call."""
+    _check_matches(matches)
     rects = list(rects)
-    zs = encode_zlib_tiles(img_u8_hwc, rects, order, rows_per_band)
+    zs = encode_zlib_tiles(img_u8_hwc, rects, order, rows_per_band, matches)
     return [container(int(r[2]), int(r[3]), z, channels=img_u8_hwc.shape[2]) for r, z in zip(rects, zs)]
 
 
-def imwrite_gpu(img_u8_hwc, path, order='bgr'):
+def imwrite_gpu(img_u8_hwc, path, order='bgr', matches=False):
     """`imageio.imwrite` for an image that is already on the device: encode there, write the file here."""
-    data = encode_png(img_u8_hwc, order)
+    data = encode_png(img_u8_hwc, order, matches=matches)
     os.makedirs(os.path.dirname(os.path.abspath(path)) or '.', exist_ok=True)
     with open(path, 'wb') as f:
         f.write(data)

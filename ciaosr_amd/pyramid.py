@@ -62,6 +62,14 @@ def _check_format(fmt):
     return fmt
 
 
+def _check_matches(matches, fmt):
+    if not isinstance(matches, bool):
+        raise ValueError(f'matches must be True or False, got {matches!r}')
+    if matches and _check_format(fmt) == 'jpg':
+        raise ValueError("matches=True is the PNG coder's option: not with fmt='jpg'")
+    return matches
+
+
 def dzi_manifest(height, width, tile_size=254, overlap=1, fmt='png'):
     """The `.dzi` file's XML for a height x width top level whose tiles are `fmt` files."""
     tile_size, overlap = _check_tiling(tile_size, overlap)
@@ -73,13 +81,15 @@ def dzi_manifest(height, width, tile_size=254, overlap=1, fmt='png'):
 
 
 def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90, subsampling='444', optimize=False,
-                 progressive=False):
+                 progressive=False, matches=False):
     """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
     returns them): one `encode_png_tiles` call per level, or for `fmt='jpg'` one `encode_jpeg_tiles` call with `quality` and
     `subsampling` (`optimize=True`: every tile with Huffman tables of its own; `progressive=True`: every tile a progressive file).
     Four-channel levels ([H_l, W_l, 4], bytes B G R A for `order` 'bgr' / 'bgra', R G B A for 'rgb' / 'rgba') are written as RGBA PNG
-    tiles; with `fmt='jpg'` they are a ValueError before any device work.
+    tiles; with `fmt='jpg'` they are a ValueError before any device work.  `matches=True` (only `fmt='png'`, else a ValueError): the
+    tiles are coded with `encode_png_tiles(..., matches=True)` -- flat and transparent tiles get far smaller, none gets larger.
     -> dict(files, bytes, encode_s, write_s); the manifest counts as a file."""
+    _check_matches(matches, fmt)
     rgba = any(getattr(im, 'dim', lambda: 0)() == 3 and im.shape[2] == 4 for im in levels)
     if rgba:
         if _check_format(fmt) == 'jpg':
@@ -96,9 +106,10 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
             return encode_jpeg_tiles(img, rects, quality=quality, subsampling=subsampling, order=order, **coding)
     else:
         from .png_hip import encode_png_tiles
+        lz = dict(matches=True) if matches else {}                             # without it encode_png_tiles is called as before
 
         def encode(img, rects):
-            return encode_png_tiles(img, rects, order=order)
+            return encode_png_tiles(img, rects, order=order, **lz)
     top = levels[-1]
     plan = dzi_plan(top.shape[0], top.shape[1], tile_size, overlap)
     if [(lv['height'], lv['width']) for lv in plan] != [(im.shape[0], im.shape[1]) for im in levels]:
@@ -125,15 +136,16 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
 
 
 def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, overlap=1, order='bgr', fmt='png', quality=90,
-              subsampling='444', optimize=False, progressive=False):
+              subsampling='444', optimize=False, progressive=False, matches=False):
     """`<out_dir>/<name>.dzi` and `<out_dir>/<name>_files/<level>/<col>_<row>.png` of the `size` / `scale` render of `enc` (an
     `encode` result of `model`).  `order`: the byte order of the rendered images, 'bgr' as `render_pyramid` makes them.  `fmt='jpg'`:
     `.jpg` tiles at `quality` (1..100) and `subsampling` ('444' or '420'), byte for byte Pillow's files of the same pixels; with
     `optimize=True` Pillow's `optimize=True` files (per-tile Huffman tables; the manifest is the same), with `progressive=True` Pillow's
-    `progressive=True` files (the manifest is the same).
+    `progressive=True` files (the manifest is the same).  `matches=True` (only `fmt='png'`): the match coder of png_hip for every tile.
     -> dict: levels [(H_l, W_l)], model_levels (the levels rendered by the model; the ones below are Pillow-exact bicubic resizes of
     the smallest of them), files, bytes, and the seconds spent in render_s (to the last launch, not synchronised), encode_s, write_s."""
     _check_tiling(tile_size, overlap)
+    _check_matches(matches, fmt)
     if _check_format(fmt) == 'jpg' and getattr(enc, 'alpha', False):
         raise ValueError("fmt='jpg' cannot hold the alpha channel of an RGBA encode: write the pyramid with fmt='png'")
     if _check_format(fmt) == 'jpg':
@@ -147,6 +159,8 @@ def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, o
     h, w = enc.x.shape[-2:]
     sizes = [(im.shape[0], im.shape[1]) for im in levels]
     coding = dict(progressive=True) if progressive else {}                     # without it write_levels is called as before
+    if matches:
+        coding['matches'] = True
     res = write_levels(levels, out_dir, name, tile_size, overlap, order, fmt, quality, subsampling, optimize, **coding)
     res.update(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w], render_s=render_s)
     return res

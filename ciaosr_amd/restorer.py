@@ -78,6 +78,11 @@ class BasicRestorer(nn.Module):
         (ciaosr_amd/png_hip.py) instead of `imageio.imwrite`; the files decode to the same pixels."""
         return bool(self.test_cfg is not None and self.test_cfg.get('gpu_png', False))
 
+    def gpu_png_matches(self):
+        """`test_cfg.gpu_png_matches` (an extension; default off, read only with `gpu_png`): the device PNG coder may use LZ77 matches
+        (`png_hip.encode_png(..., matches=True)`): smaller files for flat regions, the same pixels."""
+        return bool(self.gpu_png() and self.test_cfg.get('gpu_png_matches', False))
+
     def niqe_params(self):
         """`test_cfg.niqe_params` (an extension; default absent): the pristine NIQE model, an .npz path or a mapping
         (ciaosr_amd/niqe_hip.py), loaded once.  With it 'NIQE' may stand in `test_cfg.metrics`; without it that name is the KeyError
@@ -624,7 +629,7 @@ class CiaoSR(BasicRestorer):
                 raise ValueError(f'iteration should be number or None, but got {type(iteration)}')
             if self.gpu_png():
                 from .png_hip import imwrite_gpu
-                imwrite_gpu(out_img, save_path)
+                imwrite_gpu(out_img, save_path, matches=self.gpu_png_matches())
             else:
                 from .imageio import imwrite
                 imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(pred), save_path)

@@ -872,6 +872,42 @@ size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects /*host*/, int n_til
 int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
                                     int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                     void* workspace, size_t workspace_bytes, void* stream);
+/* LZ77 matches, opt-in (version 330; png_hip `matches=True`; DESIGN 4.1i-b3 holds the contract).  The *_lz_* entry points take the
+ * arguments of their namesakes above and give streams that decode to the same bytes; out needs the same capacity (stored blocks stay
+ * a candidate), the workspace is larger (16 bits of token per filtered byte): ciaosr_png[_rgba]_lz_workspace_bytes and
+ * ciaosr_png[_rgba]_lz_tiles_workspace_bytes, 0 = unsupported geometry.  Per band the filtered bytes are parsed greedily in chunks of
+ * 4096 bytes counted from the band's start.  Candidate distances at a position, in this order: 1, 2, 3, 4, 6, 8, 12, 16, L - bpp, L,
+ * L + bpp with L = 1 + bpp W the scanline length (of the tile, for tiles); one above 32768 or above the position's offset in its band
+ * is skipped, so no match reads before its band and bands (and tiles) stay independent.  The length for a distance is the run of equal
+ * bytes, capped at 258 and at the end of the chunk; the longest candidate wins, ties go to the earliest, and it is taken iff its length
+ * is >= 8, else the byte is a literal.  A band is ONE dynamic block with a literal / length code of up to 286 symbols and a distance code
+ * of up to 30 (both by the literal coder's construction, lengths <= 15, HLIT / HDIST trimmed, a single used distance symbol alone with
+ * length 1), followed by the empty stored block -- where that is SMALLER than what the literal coder makes of the band (its Huffman
+ * block or stored blocks), else that segment, byte for byte.  So no segment and no stream is longer than its namesake's.  The bytes
+ * are bitwise repeatable.  Launches per call, whatever the number of bands or tiles: the filter, a memset of the match histograms,
+ * deflate_lz_match, deflate_plan, deflate_lz_plan, the scan, deflate_pack, deflate_lz_pack; two synchronising copies as before.
+ * ciaosr_deflate_lz_u8 is ciaosr_deflate_huff_u8 with matches: line = L (0: the eight near distances only) and bpp >= 1 with
+ * line = 0 or line > bpp, else CIAOSR_ERR_BAD_ARG before any launch; out needs ciaosr_deflate_huff_capacity_bytes(total, n_bands),
+ * the workspace ciaosr_deflate_lz_workspace_bytes(total, n_bands) with total = band_offsets[n_bands] - band_offsets[0]. */
+size_t ciaosr_png_lz_workspace_bytes(int H, int W, int rows_per_band);
+int ciaosr_png_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                            size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t ciaosr_png_lz_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                  int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+size_t ciaosr_png_rgba_lz_workspace_bytes(int H, int W, int rows_per_band);
+int ciaosr_png_rgba_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                                 size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+size_t ciaosr_png_rgba_lz_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png_rgba_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/,
+                                       int n_tiles, int rows_per_band, unsigned char* out, size_t out_capacity,
+                                       unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+size_t ciaosr_deflate_lz_workspace_bytes(size_t total_bytes, int n_bands);
+int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* band_offsets /*host*/, int n_bands, int line, int bpp,
+                         unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- Baseline JPEG encoding of 8-bit images (ciaosr_amd/jpeg_hip.py; DESIGN 4.1i-d holds the format contract) ----------------------
  * The device makes the entropy-coded data of ONE interleaved scan of a baseline file -- libjpeg's integer pipeline as Pillow drives

@@ -56,6 +56,14 @@ ellipse with soft edges: about 70 % of the pixels fully transparent; the colour 
 the same image with that colour set to 0, as many files store it: the case the literal-only coder is worst at).  Wall time
 runs from the device image (after a synchronize) to the file's bytes on the host; the legs alternate; the file sizes of both and the
 kernel times of (a) are recorded.  Default --out: profiles/png_rgba.txt.
+
+    python tools/png_probe.py --leg matches [--sizes 768x768 5424x8160] [--out FILE]
+
+The opt-in match coder: (a) `encode_png(img, order)`, the literal coder;  (b) `encode_png(img, order, matches=True)`;  (c) the copy to the
+host + `PIL.Image.save`.  Inputs: the first size as the RGBA 'view' with the fill 0 outside it, as a render leaves it; every later size
+as that view, the three other `--rgba-cases` and the smooth and noisy RGB images.  Legs alternating in one process, 2 warm-up + 5
+timed rounds; the file bytes of all three and both device coders' kernel times (a profiled call of their own) are recorded.  Default
+--out: profiles/png_matches.txt.
 """
 import json
 import subprocess
@@ -337,6 +345,61 @@ def rgba_leg(args, say):
             del img
 
 
+def matches_leg(args, say):
+    """The literal coder, the match coder (`matches=True`) and copy + PIL save, alternating in one process: file bytes of all three,
+    wall times, and both device coders' kernel times from a profiled call of their own.  Inputs: the RGBA view at the first size, the
+    four RGBA cases and the smooth and noisy RGB images at every later size."""
+    import io
+    from PIL import Image
+    from ciaosr_amd.png_hip import encode_png
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def pil_rgba(img):
+        bio = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(img.cpu().numpy()[:, :, [2, 1, 0, 3]]), 'RGBA').save(bio, format='PNG')
+        return bio.getvalue()
+
+    def view(h, w):
+        img = rgba_cases(h, w, True, dev)[0][1]
+        img[:, :, :3] *= (img[:, :, 3:4] != 0)                             # outside a view a render holds the fill, 0
+        return img
+
+    def cases(k, h, w):
+        if 'view' in args.rgba_cases:
+            yield 'view, fill 0', 'bgra', view(h, w)
+        if k == 0:
+            return
+        for name in ('noisy', 'sprite', 'sprite0'):
+            if name in args.rgba_cases:
+                yield (name, 'bgra', dict(rgba_cases(h, w, False, dev))[name])
+        for content in args.contents:
+            yield ('RGB ' + content, 'bgr', make_image(h, w, content, dev))
+
+    for k, size in enumerate(args.sizes):
+        h, w = (int(v) for v in size.split('x'))
+        for name, order, img in cases(k, h, w):
+            torch.cuda.synchronize()
+            legs = {'a': lambda: encode_png(img, order), 'b': lambda: encode_png(img, order, matches=True),
+                    'c': (lambda: pil_rgba(img)) if order == 'bgra' else (lambda: pil_file(img, 'PNG'))}
+            times = run_legs(args, legs)
+            lit, lz, pil = legs['a'](), legs['b'](), legs['c']()
+            same = np.array_equal(np.asarray(Image.open(io.BytesIO(lz))), np.asarray(Image.open(io.BytesIO(pil))))
+            say(f'{h} x {w} {name}: decoded pixels identical: {same}; file bytes literals {len(lit)}, matches {len(lz)}, Pillow {len(pil)}; '
+                f'matches / literals {len(lz) / len(lit):.4f}, matches / Pillow {len(lz) / len(pil):.4f}, literals / Pillow {len(lit) / len(pil):.4f}')
+            say(f'  (a) encode_png on the device            wall s: {stats(times["a"])}')
+            say(f'  (b) encode_png(matches=True)            wall s: {stats(times["b"])}')
+            say(f'  (c) copy to the host + PIL save         wall s: {stats(times["c"])}')
+            gap = statistics.mean(times['b']) - statistics.mean(times['a'])
+            spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', 'b'))
+            say(f'  (b) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                f'{"matches slower beyond the spread" if gap > spread else ("matches faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                f'ratio (b) / (a) {statistics.mean(times["b"]) / statistics.mean(times["a"]):.2f}x, '
+                f'(c) / (b) {statistics.mean(times["c"]) / statistics.mean(times["b"]):.1f}x')
+            say(f'  (a) kernels: {kernels(legs["a"])}')
+            say(f'  (b) kernels: {kernels(legs["b"])}')
+            del img
+
+
 def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
@@ -504,7 +567,7 @@ def jpeg_prog_leg(args, say):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -529,9 +592,9 @@ def main(argv=None):
     jpeg = args.leg in ('jpeg', 'jpeg-opt', 'jpeg-prog')
     if args.leg in ('jpeg-opt', 'jpeg-prog'):
         args.contents = ['noisy']
-    rgba = args.leg == 'rgba'
+    rgba = args.leg in ('rgba', 'matches')
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['768x768', '5424x8160'] if rgba else ['5424x8160', '768x768'])
-    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
+    args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_matches.txt' if args.leg == 'matches' else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
     from ciaosr_amd.imageio import imread_u8, imwrite
     from ciaosr_amd.png_hip import imwrite_gpu
@@ -546,8 +609,10 @@ def main(argv=None):
         f'library version {_lib.load().ciaosr_version()}, {torch.cuda.get_device_name(0)}, {os.cpu_count()} host CPUs visible')
     if tiles:
         tiles_leg(args, say)
-    if rgba:
+    if args.leg == 'rgba':
         rgba_leg(args, say)
+    if args.leg == 'matches':
+        matches_leg(args, say)
     if args.leg == 'jpeg':
         jpeg_leg(args, say)
     if args.leg == 'jpeg-opt':

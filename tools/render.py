@@ -40,6 +40,8 @@ forces the device path, with or without --gpu-png).  The colour bytes are those 
 the integer luma of the rendered alpha image; outside a view the pixels are transparent (A = 0).  `--niqe` scores the colour part.  A
 file without a transparent pixel is reported in one line and takes the plain path: its outputs are byte for byte those of the run
 without the flag.  Not with --jpeg: JPEG files have no alpha.
+`--png-matches` (only with --gpu-png or --alpha, never with --jpeg) lets the device PNG coder use LZ77 matches for every .png of the run,
+pyramid tiles included: transparent and filled regions then cost next to nothing, and no file gets larger (png_hip `matches=True`).
 """
 import argparse
 import os
@@ -66,6 +68,8 @@ def parse_args(argv=None):
                    help='test_cfg.view_blocks: the 16-bit modes select a cut view\'s members in 4 x 2 blocks of output pixels (default off)')
     p.add_argument('--gpu-png', action='store_true',
                    help='test_cfg.gpu_png: outputs are quantised and PNG-encoded on the GPU; no fp32 image crosses to the host (default off)')
+    p.add_argument('--png-matches', action='store_true',
+                   help='with --gpu-png or --alpha: the device PNG coder may use LZ77 matches, for every .png of the run (default off)')
     p.add_argument('--jpeg', type=int, default=None, metavar='Q',
                    help='write JPEG files of quality Q (1..100), coded on the GPU, instead of PNG files (default: PNG)')
     p.add_argument('--jpeg-subsampling', choices=['444', '420'], default='444', help='chroma subsampling of --jpeg (default 444)')
@@ -94,6 +98,10 @@ def parse_args(argv=None):
         p.error('--jpeg takes a quality in 1..100')
     if args.alpha and args.jpeg is not None:
         p.error('--alpha writes RGBA PNG files: JPEG has no alpha channel, drop --jpeg')
+    if args.png_matches and args.jpeg is not None:
+        p.error('--png-matches is the PNG coder\'s option: drop --jpeg')
+    if args.png_matches and not (args.gpu_png or args.alpha):
+        p.error('--png-matches belongs to --gpu-png or --alpha, whose files the device codes')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
     if args.jpeg_progressive and args.jpeg is None:
@@ -162,6 +170,8 @@ def main(argv=None):
     form = output_format(args)
     coding = {k: form[k] for k in ('quality', 'subsampling', 'optimize', 'progressive') if k in form}
     dzi_format = dict(fmt='jpg', **coding) if form['fmt'] == 'jpg' else {}           # without --jpeg write_dzi is called as before
+    lz = dict(matches=True) if args.png_matches else {}                              # without --png-matches every writer is called as before
+    dzi_format.update(lz)
     targets = [Grid(scale=s, window=args.window) for s in args.scale]
     paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}{form["ext"]}') for s in args.scale]
     for k, (cy, cx, zoom, angle) in enumerate(args.view):
@@ -193,11 +203,11 @@ def main(argv=None):
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
         elif alpha:
             from ciaosr_amd.png_hip import imwrite_gpu
-            imwrite_gpu(out, path, order='bgra')                       # uint8 [H, W, 4] B G R A on the device
+            imwrite_gpu(out, path, order='bgra', **lz)                 # uint8 [H, W, 4] B G R A on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]} RGBA')
         elif gpu_png:
             from ciaosr_amd.png_hip import imwrite_gpu
-            imwrite_gpu(out, path)                                     # uint8 [H, W, 3] BGR on the device
+            imwrite_gpu(out, path, **lz)                               # uint8 [H, W, 3] BGR on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
         else:
             imwrite(metrics.tensor2img(out), path)

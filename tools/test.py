@@ -72,6 +72,8 @@ def parse_args(argv=None):
                    help='test_cfg.gpu_metrics = True: quantise and evaluate PSNR / SSIM on the GPU (default: on the host)')
     p.add_argument('--gpu-png', action='store_true',
                    help='test_cfg.gpu_png = True: --save-path images are quantised and PNG-encoded on the GPU (default: PIL on the host)')
+    p.add_argument('--gpu-png-matches', action='store_true',
+                   help='test_cfg.gpu_png = test_cfg.gpu_png_matches = True: as --gpu-png, and the coder may use LZ77 matches (smaller files)')
     p.add_argument('--niqe', default=None, metavar='PARAMS',
                    help='test_cfg.niqe_params = PARAMS (the pristine model, niqe_pris_params.npz) and \'NIQE\' appended to test_cfg.metrics: '
                         'the blind score of every output, computed on the GPU (default: not computed)')
@@ -82,8 +84,10 @@ def apply_overrides(cfg, args):
     """Command-line switches that end up in the loaded config (before the model is built from it)."""
     if args.gpu_metrics:
         cfg.test_cfg['gpu_metrics'] = True
-    if args.gpu_png:
+    if args.gpu_png or args.gpu_png_matches:
         cfg.test_cfg['gpu_png'] = True
+    if args.gpu_png_matches:
+        cfg.test_cfg['gpu_png_matches'] = True
     if args.niqe:
         cfg.test_cfg['niqe_params'] = args.niqe
         names = list(cfg.test_cfg.get('metrics', None) or [])
@@ -171,7 +175,7 @@ def main(argv=None):
                 name = os.path.splitext(os.path.basename(d['meta']['gt_path']))[0]
                 if model.gpu_png():
                     from ciaosr_amd.png_hip import imwrite_gpu
-                    imwrite_gpu(out_img, os.path.join(args.save_path, f'{name}.png'))
+                    imwrite_gpu(out_img, os.path.join(args.save_path, f'{name}.png'), matches=model.gpu_png_matches())
                 else:
                     imwrite(out_img.cpu().numpy() if out_img is not None else metrics.tensor2img(out),
                             os.path.join(args.save_path, f'{name}.png'))
