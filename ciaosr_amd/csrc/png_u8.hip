@@ -30,6 +30,17 @@
 // above its first row), the plan and pack kernels run unchanged on the table's offsets (a tile's last band carries BFINAL), and
 // png_tiles_scan_kernel is the scan's segmented sibling: per tile 2 + segments + 4 bytes, a prefix sum over tiles, every band's offset,
 // every tile's header and its Adler-32 from its own bands' partials.  Each tile's stream is byte for byte the single call's on the crop.
+//
+// What the literal coder and the match coder share on the device: wave_code_lengths and canonical_codes (both codes of both planners),
+// BitSink<kWords>, code_length_runs and put_block_header (a dynamic block's header), and the packers' Segment, or_header, advance_window,
+// block_exclusive, finish_segment and flush_words; each packer keeps its own symbol loop.
+//
+// The host side ("the host side", below the kernels): a call names what it keeps in its workspace as a Layout, carve() is the one list of
+// those pieces and work_bytes() the same function over a fake origin, so the exported sizes are what the drivers carve.  Parameter
+// structs are filled by named assignment (deflate_params, lz_params; an LzP carries the DeflateP it extends), launch() is ProfScope +
+// launch + launch_status, and run_deflate() is the one launch sequence -- plan, scan, pack, and around them the match coder's memset,
+// parse, plan and packer when an LzP is given -- for encode_entry, encode_tiles_entry and deflate_entry.  The extern "C" exports are
+// one-line forwards to these bodies, in one block at the end.
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -56,7 +67,7 @@ constexpr int kPerLane = 16;                       // symbols per lane and step 
 constexpr int kChunk = kThreads * kPerLane;
 constexpr int kWin = 2048;                         // words of the packer's LDS window: 24 + 2040 header bits + 4096 x 15 < 65536
 
-static_assert(kStride >= kSyms, "histogram stride");
+static_assert(kStride > kSyms, "histogram stride; the planner keeps the one distance code's length behind the 257 others");
 
 // bands of a byte buffer: explicit offsets [nb + 1], or uniform bands of band_bytes (the last one shorter)
 struct Bands {
@@ -408,6 +419,8 @@ __device__ void canonical_codes(const unsigned char* len, int nsym, int limit, i
     }
 }
 
+// A block header of at most kWords words, bit 0 of word 0 first; `bits` counts on past the end, so that the planner sees an overflow.
+template <int kWords>
 struct BitSink {
     u32* words;
     u64 acc;
@@ -417,19 +430,92 @@ struct BitSink {
         nacc += n;
         bits += n;
         if (nacc >= 32) {
-            if (w < kHdrWords) words[w] = (u32)acc;
+            if (w < kWords) words[w] = (u32)acc;
             ++w;
             acc >>= 32;
             nacc -= 32;
         }
     }
     __device__ void finish() {
-        for (; w < kHdrWords; ++w) {
+        for (; w < kWords; ++w) {
             words[w] = (u32)acc;
             acc = 0ull;
         }
     }
 };
+
+// lane 0: the ncl code lengths seq[] of a dynamic block in the run-length symbols of RFC 1951, 3.2.7 -> the number of entries;
+// ent[] (ncl entries at most) takes symbol | extra << 5, clf[19] the counts of the symbols (16: repeat the last length 3..6 times,
+// 17 / 18: 3..10 / 11..138 zeros).
+__device__ int code_length_runs(const unsigned char* seq, int ncl, unsigned short* ent, u32* clf) {
+    for (int i = 0; i < 19; ++i) clf[i] = 0u;
+    int ne = 0, i = 0;
+    while (i < ncl) {
+        const int v = seq[i];
+        int run = 1;
+        while (i + run < ncl && seq[i + run] == v) ++run;
+        i += run;
+        if (v == 0) {
+            while (run > 0) {
+                if (run >= 11) {
+                    const int t = min(run, 138);
+                    ent[ne++] = (unsigned short)(18 | (t - 11) << 5);
+                    clf[18]++;
+                    run -= t;
+                } else if (run >= 3) {
+                    ent[ne++] = (unsigned short)(17 | (run - 3) << 5);
+                    clf[17]++;
+                    run = 0;
+                } else {
+                    ent[ne++] = 0;
+                    clf[0]++;
+                    --run;
+                }
+            }
+        } else {
+            ent[ne++] = (unsigned short)v;
+            clf[v]++;
+            --run;
+            while (run > 0) {
+                if (run >= 3) {
+                    const int t = min(run, 6);
+                    ent[ne++] = (unsigned short)(16 | (t - 3) << 5);
+                    clf[16]++;
+                    run -= t;
+                } else {
+                    ent[ne++] = (unsigned short)v;
+                    clf[v]++;
+                    --run;
+                }
+            }
+        }
+    }
+    return ne;
+}
+
+// lane 0: a dynamic block's header: BFINAL 0, BTYPE 10, HLIT, HDIST, HCLEN, the code-length code (lengths cll[19], codes clc[19]) and
+// the ne entries of code_length_runs; the rest of the sink's words are zeroed.
+template <int kWords>
+__device__ void put_block_header(BitSink<kWords>& s, int hlit, int hdist, const unsigned char* cll, const u32* clc,
+                                 const unsigned short* ent, int ne) {
+    const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    int hclen = 4;
+    for (int k = 0; k < 19; ++k)
+        if (cll[order[k]]) hclen = max(hclen, k + 1);
+    s.put(4u, 3);                                          // BFINAL 0, BTYPE 10 (dynamic)
+    s.put((u32)(hlit - 257), 5);
+    s.put((u32)(hdist - 1), 5);
+    s.put((u32)(hclen - 4), 4);
+    for (int k = 0; k < hclen; ++k) s.put(cll[order[k]], 3);
+    for (int k = 0; k < ne; ++k) {
+        const int sym = ent[k] & 31, extra = ent[k] >> 5;
+        s.put(clc[sym] & 0xffffu, (int)(clc[sym] >> 16));
+        if (sym == 16) s.put((u32)extra, 2);
+        if (sym == 17) s.put((u32)extra, 3);
+        if (sym == 18) s.put((u32)extra, 7);
+    }
+    s.finish();
+}
 
 __global__ __launch_bounds__(kWave) void deflate_plan_kernel(DeflateP p) {
     __shared__ u32 f[kStride];
@@ -450,75 +536,15 @@ __global__ __launch_bounds__(kWave) void deflate_plan_kernel(DeflateP p) {
     wave_code_lengths(f, kSyms, kLitLimit, key, ord, num, len);
     if (lane == 0) {
         canonical_codes(len, kSyms, kLitLimit, num, next, code);
-        // the 258 code lengths (257 literal / length codes + the one distance code of length 0) in run-length symbols
-        for (int i = 0; i < 19; ++i) clf[i] = 0u;
-        int ne = 0, i = 0;
-        const int ncl = kSyms + 1;
-        while (i < ncl) {
-            const int v = i < kSyms ? len[i] : 0;
-            int run = 1;
-            while (i + run < ncl && (i + run < kSyms ? len[i + run] : 0) == v) ++run;
-            i += run;
-            if (v == 0) {
-                while (run > 0) {
-                    if (run >= 11) {
-                        const int t = min(run, 138);
-                        ent[ne++] = (unsigned short)(18 | (t - 11) << 5);
-                        clf[18]++;
-                        run -= t;
-                    } else if (run >= 3) {
-                        ent[ne++] = (unsigned short)(17 | (run - 3) << 5);
-                        clf[17]++;
-                        run = 0;
-                    } else {
-                        ent[ne++] = 0;
-                        clf[0]++;
-                        --run;
-                    }
-                }
-            } else {
-                ent[ne++] = (unsigned short)v;
-                clf[v]++;
-                --run;
-                while (run > 0) {
-                    if (run >= 3) {
-                        const int t = min(run, 6);
-                        ent[ne++] = (unsigned short)(16 | (t - 3) << 5);
-                        clf[16]++;
-                        run -= t;
-                    } else {
-                        ent[ne++] = (unsigned short)v;
-                        clf[v]++;
-                        --run;
-                    }
-                }
-            }
-        }
-        s_nent = ne;
+        len[kSyms] = 0;                                    // the 258 code lengths: 257 literal / length codes + the one distance code of length 0
+        s_nent = code_length_runs(len, kSyms + 1, ent, clf);
     }
     __syncthreads();
     wave_code_lengths(clf, 19, kClLimit, key, ord, num, cll);
     if (lane == 0) {
         canonical_codes(cll, 19, kClLimit, num, next, clc);
-        const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int hclen = 4;
-        for (int k = 0; k < 19; ++k)
-            if (cll[order[k]]) hclen = max(hclen, k + 1);
-        BitSink s{p.hdr + (size_t)band * kHdrWords, 0ull, 0, 0, 0};
-        s.put(4u, 3);                                      // BFINAL 0, BTYPE 10 (dynamic)
-        s.put(0u, 5);                                      // HLIT: 257 codes
-        s.put(0u, 5);                                      // HDIST: 1 code
-        s.put((u32)(hclen - 4), 4);
-        for (int k = 0; k < hclen; ++k) s.put(cll[order[k]], 3);
-        const int ne = s_nent;
-        for (int k = 0; k < ne; ++k) {
-            const int sym = ent[k] & 31, extra = ent[k] >> 5;
-            s.put(clc[sym] & 0xffffu, (int)(clc[sym] >> 16));
-            if (sym == 16) s.put((u32)extra, 2);
-            if (sym == 17) s.put((u32)extra, 3);
-            if (sym == 18) s.put((u32)extra, 7);
-        }
-        s.finish();
+        BitSink<kHdrWords> s{p.hdr + (size_t)band * kHdrWords, 0ull, 0, 0, 0};
+        put_block_header(s, kSyms, 1, cll, clc, ent, s_nent);
         u64 payload = 0ull;
         for (int i = 0; i < kSyms; ++i) payload += (u64)f[i] * len[i];
         const u64 n = band_begin(p.b, band + 1) - band_begin(p.b, band);
@@ -668,18 +694,102 @@ __device__ __forceinline__ void flush_words(const u32* win, int nw, unsigned cha
     }
 }
 
+// ---- what the two packers share.  A packer's place in its segment: bytes [lo, hi) of out; window word 0 is the aligned output word at
+// byte abase + 4 wdone, and its first `bitpos` (< 32, between two steps) bits are taken.
+struct Segment {
+    unsigned char* out;
+    u64 lo, hi, abase, wdone;
+    u32 bitpos;
+};
+__device__ __forceinline__ Segment segment_of(const DeflateP& p, int band) {
+    Segment g;
+    g.out = p.out;
+    g.lo = p.out_offs[band];
+    g.hi = g.lo + p.seg_bytes[band];                       // tiles: a trailer and a header lie before the next band
+    g.abase = g.lo & ~3ull;
+    g.wdone = 0ull;
+    g.bitpos = (u32)(g.lo & 3ull) * 8u;
+    return g;
+}
+__device__ __forceinline__ bool last_band(const DeflateP& p, int band) { return p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1; }
+
+// the hb bits of a band's header, ORed into the zeroed window behind the bits taken
+__device__ __forceinline__ void or_header(u32* win, const Segment& g, const u32* hdr, u32 hb) {
+    const int tid = threadIdx.x, nw = (int)((hb + 31u) >> 5);
+    if (tid < nw) {
+        const u64 x = (u64)hdr[tid] << g.bitpos;
+        atomicOr(&win[tid], (u32)x);
+        if (x >> 32) atomicOr(&win[tid + 1], (u32)(x >> 32));
+    }
+}
+
+// All lanes, behind a barrier after the last OR: `nbits` more bits are in the window.  Its full words are flushed, the word in
+// progress becomes word 0 and the rest is cleared for the next step.
+__device__ __forceinline__ void advance_window(u32* win, Segment& g, u32 nbits) {
+    const u32 newpos = g.bitpos + nbits;
+    const int nfull = (int)(newpos >> 5);
+    flush_words(win, nfull, g.out, g.abase, g.wdone, g.lo, g.hi);
+    const u32 carry = win[nfull];
+    __syncthreads();
+    for (int i = threadIdx.x; i <= nfull; i += kThreads) win[i] = 0u;
+    __syncthreads();
+    if (threadIdx.x == 0) win[0] = carry;
+    __syncthreads();
+    g.wdone += (u64)nfull;
+    g.bitpos = newpos & 31u;
+}
+
+// All lanes: the sum of `bits` over the lanes before this one, and over the whole workgroup in *total.  wsum: kWaves words of LDS, free
+// again after the caller's next barrier.
+__device__ __forceinline__ u32 block_exclusive(u32 bits, u32* wsum, u32* total) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    u32 inc = bits;                                          // inclusive scan of the lanes' bit counts
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const u32 t = __shfl_up(inc, off, kWave);
+        if (lane >= off) inc += t;
+    }
+    if (lane == kWave - 1) wsum[wave] = inc;
+    __syncthreads();
+    u32 before = 0u, all = 0u;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (w < wave) before += wsum[w];
+        all += wsum[w];
+    }
+    *total = all;
+    return before + inc - bits;
+}
+
+// The end of a Huffman segment: the end-of-block code `eob` (length << 16 | code) and the empty stored block that byte-aligns it, then
+// the flush of what the window holds.
+__device__ __forceinline__ void finish_segment(u32* win, const Segment& g, u32 eob, bool last, u32* wsum) {
+    if (threadIdx.x == 0) {
+        u32 pos = g.bitpos;
+        or_bits(win, pos, eob & 0xffffu);
+        pos += eob >> 16;
+        or_bits(win, pos, last ? 1u : 0u);               // the empty stored block: BFINAL, BTYPE 00, pad, LEN 0, NLEN 0xffff
+        pos = (pos + 3u + 7u) & ~7u;
+        or_bits(win, pos + 16u, 0xffffu);
+        wsum[0] = pos + 32u;
+    }
+    __syncthreads();
+    flush_words(win, (int)((wsum[0] + 31u) >> 5), g.out, g.abase, g.wdone, g.lo, g.hi);
+}
+
 __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     __shared__ u32 win[kWin];
     __shared__ u32 tab[kStride];
     __shared__ u32 wsum[kWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int band = blockIdx.x;
-    const bool last = p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1;
+    const bool last = last_band(p, band);
     const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
-    const u64 lo = p.out_offs[band], hi = lo + p.seg_bytes[band];         // tiles: a trailer and a header lie before the next band
+    Segment g = segment_of(p, band);
     if (p.mode[band] == 2u) return;                         // a band in match mode (the lz entry points only) is deflate_lz_pack_kernel's
     if (p.mode[band] == 0u) {                              // stored blocks of at most 65535 bytes: 5 framing bytes each
         const u64 nblk = (n + kStoredMax - 1) / kStoredMax;
+        const u64 lo = g.lo, hi = g.hi;
         for (u64 j = tid; j < hi - lo; j += kThreads) {
             const u64 blk = j / (kStoredMax + 5ull);
             const u32 r = (u32)(j % (kStoredMax + 5ull));
@@ -699,19 +809,9 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
     for (int i = tid; i < kSyms; i += kThreads) tab[i] = p.table[(size_t)band * kStride + i];
     for (int i = tid; i < kWin; i += kThreads) win[i] = 0u;
     __syncthreads();
-    const u64 abase = lo & ~3ull;                           // window word 0 is the aligned output word that holds the segment's first byte
-    u32 bitpos = (u32)(lo & 3ull) * 8u;
-    u64 wdone = 0ull;
-    {
-        const u32 hb = p.hdr_bits[band];
-        const int nw = (int)((hb + 31u) >> 5);
-        if (tid < nw) {
-            const u64 x = (u64)p.hdr[(size_t)band * kHdrWords + tid] << bitpos;
-            atomicOr(&win[tid], (u32)x);
-            if (x >> 32) atomicOr(&win[tid + 1], (u32)(x >> 32));
-        }
-        bitpos += hb;
-    }
+    const u32 hb = p.hdr_bits[band];                        // the header stays in the window: the first chunk's bits follow it
+    or_header(win, g, p.hdr + (size_t)band * kHdrWords, hb);
+    g.bitpos += hb;
     __syncthreads();
     for (u64 c0 = 0; c0 < n; c0 += kChunk) {
         const u64 m0 = c0 + (u64)tid * kPerLane;
@@ -723,21 +823,8 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
             e[k] = k < cnt ? tab[p.data[d0 + m0 + k]] : 0u;
             bits += e[k] >> 16;
         }
-        u32 inc = bits;                                      // inclusive scan of the lanes' bit counts
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const u32 t = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += t;
-        }
-        if (lane == kWave - 1) wsum[wave] = inc;
-        __syncthreads();
-        u32 before = 0u, chunk_bits = 0u;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w < wave) before += wsum[w];
-            chunk_bits += wsum[w];
-        }
-        u32 pos = bitpos + before + inc - bits;
+        u32 chunk_bits;
+        const u32 pos = g.bitpos + block_exclusive(bits, wsum, &chunk_bits);
         int w = (int)(pos >> 5);
         int nacc = (int)(pos & 31u);
         u64 acc = 0ull;
@@ -754,30 +841,9 @@ __global__ __launch_bounds__(kThreads) void deflate_pack_kernel(DeflateP p) {
         }
         if (nacc > 0 && acc) atomicOr(&win[w], (u32)acc);
         __syncthreads();
-        const u32 newpos = bitpos + chunk_bits;
-        const int nfull = (int)(newpos >> 5);
-        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
-        const u32 carry = win[nfull];
-        __syncthreads();
-        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
-        __syncthreads();
-        if (tid == 0) win[0] = carry;
-        __syncthreads();
-        wdone += (u64)nfull;
-        bitpos = newpos & 31u;
+        advance_window(win, g, chunk_bits);
     }
-    if (tid == 0) {
-        u32 pos = bitpos;
-        or_bits(win, pos, tab[256] & 0xffffu);
-        pos += tab[256] >> 16;
-        or_bits(win, pos, last ? 1u : 0u);               // the empty stored block: BFINAL, BTYPE 00, pad, LEN 0, NLEN 0xffff
-        pos = (pos + 3u + 7u) & ~7u;
-        or_bits(win, pos + 16u, 0xffffu);
-        bitpos = pos + 32u;
-        wsum[0] = bitpos;
-    }
-    __syncthreads();
-    flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
+    finish_segment(win, g, tab[256], last, wsum);
 }
 
 // ---- LZ77 matches (opt-in: the *_lz_* entry points) ------------------------------------------------------------------------------
@@ -815,29 +881,25 @@ static_assert(kLzStride >= kLzLit + kLzDist && 32 * kLzHdrWords >= 14 + 57 + (kL
 static_assert(31 + kLzChunk * kLitLimit < 32 * (kWin - 1) && kLzHdrWords + 2 < kWin, "packer window");
 
 struct LzP {
-    const unsigned char* data;
-    Bands b;
-    const TileBand* tiles;        // with rects: the line of a band is its tile's, 1 + bpp w
-    const int* rects;
+    DeflateP d;                   // the literal coder's call: data, bands and tiles; mode and seg_bytes hold deflate_plan_kernel's choice
+                                  // (mode 2 where matches are smaller); out_offs and out as the scan left them
+    const int* rects;             // with d.tiles: the line of a band is its tile's, 1 + bpp w
     u64 line;                     // otherwise: every band's line, 0 = none
     int bpp;
     u64 base0;                    // the first band's offset in data: token slots are counted from there
     const u32* chunk_first;       // [nb + 1] first chunk of every band, or null: uniform bands of cpb chunks
     u32 cpb;
+    u32 chunks;                   // parse chunks of all bands: the workgroups of deflate_lz_match_kernel
     unsigned short* tok;          // [total]: a chunk's tokens start at its first byte's offset
     u32* cnt;                     // [chunks]
     u32* hist;                    // [nb][kLzStride], zeroed before deflate_lz_match_kernel
     u32* table;                   // [nb][kLzStride]: length << 16 | bit-reversed code
     u32* hdr;                     // [nb][kLzHdrWords]
     u32* hdr_bits;                // [nb]
-    u32* mode;                    // [nb]: deflate_plan_kernel's choice, 2 where matches are smaller
-    u64* seg_bytes;               // [nb]
-    const u64* out_offs;
-    unsigned char* out;
 };
 
 __device__ __forceinline__ u64 lz_line(const LzP& p, int band) {
-    return p.tiles ? 1ull + (u64)p.bpp * (u64)p.rects[4 * (size_t)p.tiles[band].tile + 3] : p.line;
+    return p.d.tiles ? 1ull + (u64)p.bpp * (u64)p.rects[4 * (size_t)p.d.tiles[band].tile + 3] : p.line;
 }
 // candidate c of a band with scanline length `line`: its distance, 0 when there is none
 __device__ __forceinline__ u32 lz_distance(int c, u64 line, int bpp) {
@@ -876,9 +938,9 @@ __device__ __forceinline__ bool lz_locate(const LzP& p, u32 blk, int* band, u64*
     if (!p.chunk_first) {
         *band = (int)(blk / p.cpb);
         *c0 = (u64)(blk % p.cpb) * kLzChunk;
-        return *c0 < band_begin(p.b, *band + 1) - band_begin(p.b, *band);
+        return *c0 < band_begin(p.d.b, *band + 1) - band_begin(p.d.b, *band);
     }
-    int lo = 0, hi = p.b.nb - 1;                            // the last band whose first chunk is <= blk
+    int lo = 0, hi = p.d.b.nb - 1;                            // the last band whose first chunk is <= blk
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (p.chunk_first[mid] <= blk) lo = mid;
@@ -921,9 +983,9 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_match_kernel(LzP p) {
     int band;
     u64 c0;
     if (!lz_locate(p, blockIdx.x, &band, &c0)) return;
-    const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
+    const u64 d0 = band_begin(p.d.b, band), n = band_begin(p.d.b, band + 1) - d0;
     const int m = (int)(n - c0 < (u64)kLzChunk ? n - c0 : (u64)kLzChunk);
-    const unsigned char* src = p.data + d0 + c0;            // src[-k] is inside the band for k <= c0
+    const unsigned char* src = p.d.data + d0 + c0;            // src[-k] is inside the band for k <= c0
     if (tid < kLzCand) dist[tid] = lz_distance(tid, lz_line(p, band), p.bpp);
     for (int i = tid; i < kLzStride; i += kThreads) h[i] = 0u;
     for (int i = tid; i < 16 + kLzChunk; i += kThreads) {
@@ -1034,29 +1096,6 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_match_kernel(LzP p) {
         if (h[i]) atomicAdd(&p.hist[(size_t)band * kLzStride + i], h[i]);
 }
 
-struct LzSink {
-    u32* words;
-    u64 acc;
-    int nacc, w, bits;
-    __device__ void put(u32 v, int n) {
-        acc |= (u64)v << nacc;
-        nacc += n;
-        bits += n;
-        if (nacc >= 32) {
-            if (w < kLzHdrWords) words[w] = (u32)acc;
-            ++w;
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-    __device__ void finish() {
-        for (; w < kLzHdrWords; ++w) {
-            words[w] = (u32)acc;
-            acc = 0ull;
-        }
-    }
-};
-
 __global__ __launch_bounds__(kWave) void deflate_lz_plan_kernel(LzP p) {
     __shared__ u32 f[kLzStride];
     __shared__ u32 key[kLzLit];
@@ -1092,52 +1131,9 @@ __global__ __launch_bounds__(kWave) void deflate_lz_plan_kernel(LzP p) {
             if (len[i]) hlit = i + 1;
         for (int i = 1; i < kLzDist; ++i)
             if (len[kLzLit + i]) hdist = i + 1;
-        const int ncl = hlit + hdist;
         for (int i = 0; i < hlit; ++i) seq[i] = len[i];
         for (int i = 0; i < hdist; ++i) seq[hlit + i] = len[kLzLit + i];
-        for (int i = 0; i < 19; ++i) clf[i] = 0u;
-        int ne = 0, i = 0;
-        while (i < ncl) {
-            const int v = seq[i];
-            int run = 1;
-            while (i + run < ncl && seq[i + run] == v) ++run;
-            i += run;
-            if (v == 0) {
-                while (run > 0) {
-                    if (run >= 11) {
-                        const int t = min(run, 138);
-                        ent[ne++] = (unsigned short)(18 | (t - 11) << 5);
-                        clf[18]++;
-                        run -= t;
-                    } else if (run >= 3) {
-                        ent[ne++] = (unsigned short)(17 | (run - 3) << 5);
-                        clf[17]++;
-                        run = 0;
-                    } else {
-                        ent[ne++] = 0;
-                        clf[0]++;
-                        --run;
-                    }
-                }
-            } else {
-                ent[ne++] = (unsigned short)v;
-                clf[v]++;
-                --run;
-                while (run > 0) {
-                    if (run >= 3) {
-                        const int t = min(run, 6);
-                        ent[ne++] = (unsigned short)(16 | (t - 3) << 5);
-                        clf[16]++;
-                        run -= t;
-                    } else {
-                        ent[ne++] = (unsigned short)v;
-                        clf[v]++;
-                        --run;
-                    }
-                }
-            }
-        }
-        s_nent = ne;
+        s_nent = code_length_runs(seq, hlit + hdist, ent, clf);
         s_hlit = hlit;
         s_hdist = hdist;
     }
@@ -1145,33 +1141,16 @@ __global__ __launch_bounds__(kWave) void deflate_lz_plan_kernel(LzP p) {
     wave_code_lengths(clf, 19, kClLimit, key, ord, num, cll);
     if (lane == 0) {
         canonical_codes(cll, 19, kClLimit, num, next, clc);
-        const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int hclen = 4;
-        for (int k = 0; k < 19; ++k)
-            if (cll[order[k]]) hclen = max(hclen, k + 1);
-        LzSink s{p.hdr + (size_t)band * kLzHdrWords, 0ull, 0, 0, 0};
-        s.put(4u, 3);                                      // BFINAL 0, BTYPE 10 (dynamic)
-        s.put((u32)(s_hlit - 257), 5);
-        s.put((u32)(s_hdist - 1), 5);
-        s.put((u32)(hclen - 4), 4);
-        for (int k = 0; k < hclen; ++k) s.put(cll[order[k]], 3);
-        const int ne = s_nent;
-        for (int k = 0; k < ne; ++k) {
-            const int sym = ent[k] & 31, extra = ent[k] >> 5;
-            s.put(clc[sym] & 0xffffu, (int)(clc[sym] >> 16));
-            if (sym == 16) s.put((u32)extra, 2);
-            if (sym == 17) s.put((u32)extra, 3);
-            if (sym == 18) s.put((u32)extra, 7);
-        }
-        s.finish();
+        BitSink<kLzHdrWords> s{p.hdr + (size_t)band * kLzHdrWords, 0ull, 0, 0, 0};
+        put_block_header(s, s_hlit, s_hdist, cll, clc, ent, s_nent);
         u64 payload = 0ull;
         for (int i = 0; i < kLzLit; ++i) payload += (u64)f[i] * (u64)(len[i] + lz_length_extra(i));
         for (int i = 0; i < kLzDist; ++i) payload += (u64)f[kLzLit + i] * (u64)(len[kLzLit + i] + lz_distance_extra(i));
         const u64 lz = ((u64)s.bits + payload + 3ull + 7ull) / 8ull + 4ull;       // + the empty stored block, as the literal coder's
         p.hdr_bits[band] = (u32)s.bits;
-        if (lz < p.seg_bytes[band]) {                       // a tie stays with deflate_plan_kernel's choice
-            p.mode[band] = 2u;
-            p.seg_bytes[band] = lz;
+        if (lz < p.d.seg_bytes[band]) {                       // a tie stays with deflate_plan_kernel's choice
+            p.d.mode[band] = 2u;
+            p.d.seg_bytes[band] = lz;
         }
     }
     __syncthreads();
@@ -1183,12 +1162,12 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_pack_kernel(LzP p) {
     __shared__ u32 tab[kLzStride];
     __shared__ u32 dcode[kLzCand], dbits[kLzCand];          // per candidate: distance code with its extra bits behind, and the bit count
     __shared__ u32 wsum[kWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int band = blockIdx.x;
-    if (p.mode[band] != 2u) return;
-    const bool last = p.tiles ? p.tiles[band].last != 0 : band == p.b.nb - 1;
-    const u64 d0 = band_begin(p.b, band), n = band_begin(p.b, band + 1) - d0;
-    const u64 lo = p.out_offs[band], hi = lo + p.seg_bytes[band];
+    if (p.d.mode[band] != 2u) return;
+    const bool last = last_band(p.d, band);
+    const u64 d0 = band_begin(p.d.b, band), n = band_begin(p.d.b, band + 1) - d0;
+    Segment g = segment_of(p.d, band);
     for (int i = tid; i < kLzStride; i += kThreads) tab[i] = p.table[(size_t)band * kLzStride + i];
     for (int i = tid; i < kWin; i += kThreads) win[i] = 0u;
     __syncthreads();
@@ -1206,30 +1185,10 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_pack_kernel(LzP p) {
         dcode[tid] = v;
         dbits[tid] = nb;
     }
-    const u64 abase = lo & ~3ull;
-    u32 bitpos = (u32)(lo & 3ull) * 8u;
-    u64 wdone = 0ull;
-    {                                                       // the header, flushed on its own: the window then holds one chunk's bits
-        const u32 hb = p.hdr_bits[band];
-        const int nw = (int)((hb + 31u) >> 5);
-        if (tid < nw) {
-            const u64 x = (u64)p.hdr[(size_t)band * kLzHdrWords + tid] << bitpos;
-            atomicOr(&win[tid], (u32)x);
-            if (x >> 32) atomicOr(&win[tid + 1], (u32)(x >> 32));
-        }
-        __syncthreads();
-        const u32 newpos = bitpos + hb;
-        const int nfull = (int)(newpos >> 5);
-        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
-        const u32 carry = win[nfull];
-        __syncthreads();
-        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
-        __syncthreads();
-        if (tid == 0) win[0] = carry;
-        __syncthreads();
-        wdone += (u64)nfull;
-        bitpos = newpos & 31u;
-    }
+    const u32 hb = p.hdr_bits[band];                        // the header, flushed on its own: the window then holds one chunk's bits
+    or_header(win, g, p.hdr + (size_t)band * kLzHdrWords, hb);
+    __syncthreads();
+    advance_window(win, g, hb);
     const u32 chunk0 = p.chunk_first ? p.chunk_first[band] : (u32)band * p.cpb;
     const unsigned short* toks = p.tok + (d0 - p.base0);
     u32 ch = 0u;
@@ -1253,21 +1212,8 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_pack_kernel(LzP p) {
                 }
             }
         }
-        u32 inc = bits;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const u32 v = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += v;
-        }
-        if (lane == kWave - 1) wsum[wave] = inc;
-        __syncthreads();
-        u32 before = 0u, chunk_bits = 0u;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w < wave) before += wsum[w];
-            chunk_bits += wsum[w];
-        }
-        u32 pos = bitpos + before + inc - bits;
+        u32 chunk_bits;
+        const u32 pos = g.bitpos + block_exclusive(bits, wsum, &chunk_bits);
         int w = (int)(pos >> 5);
         int nacc = (int)(pos & 31u);
         u64 acc = 0ull;
@@ -1299,181 +1245,182 @@ __global__ __launch_bounds__(kThreads) void deflate_lz_pack_kernel(LzP p) {
         }
         if (nacc > 0 && acc) atomicOr(&win[w], (u32)acc);
         __syncthreads();
-        const u32 newpos = bitpos + chunk_bits;
-        const int nfull = (int)(newpos >> 5);
-        flush_words(win, nfull, p.out, abase, wdone, lo, hi);
-        const u32 carry = win[nfull];
-        __syncthreads();
-        for (int i = tid; i <= nfull; i += kThreads) win[i] = 0u;
-        __syncthreads();
-        if (tid == 0) win[0] = carry;
-        __syncthreads();
-        wdone += (u64)nfull;
-        bitpos = newpos & 31u;
+        advance_window(win, g, chunk_bits);
     }
-    if (tid == 0) {
-        u32 pos = bitpos;
-        or_bits(win, pos, tab[256] & 0xffffu);
-        pos += tab[256] >> 16;
-        or_bits(win, pos, last ? 1u : 0u);               // the empty stored block: BFINAL, BTYPE 00, pad, LEN 0, NLEN 0xffff
-        pos = (pos + 3u + 7u) & ~7u;
-        or_bits(win, pos + 16u, 0xffffu);
-        bitpos = pos + 32u;
-        wsum[0] = bitpos;
-    }
-    __syncthreads();
-    flush_words(win, (int)((wsum[0] + 31u) >> 5), p.out, abase, wdone, lo, hi);
+    finish_segment(win, g, tab[256], last, wsum);
 }
 
+// ---- the host side -----------------------------------------------------------------------------------------------------------------
 static inline int rows_per_band(int W, int rows, int bpp) {
     if (rows > 0) return rows;
     const long L = (long)bpp * W + 1;
     const long r = (128L * 1024L) / L;                       // bands of about 128 KiB of filtered bytes
     return (int)(r < 1 ? 1 : r);
 }
+static inline size_t capacity(size_t total, int nb, bool zlib) {
+    return total + 5 * (total / kStoredMax + (size_t)nb) + (zlib ? 6 : 0) + 8;
+}
+static inline u64 lz_chunks_of(u64 bytes) { return (bytes + kLzChunk - 1) / kLzChunk; }
 
+// What a call keeps in its workspace.  Callers allocate what work_bytes returns for a Layout and the drivers carve the same Layout up:
+// one list of pieces, in one order, for every entry point.
+struct Layout {
+    int nb;                       // bands
+    size_t filtered;              // bytes of filtered scanlines; 0: the caller's own bytes are coded
+    size_t table;                 // bytes of the tiles' band table, or 0
+    size_t chunks, tokens;        // the match coder's parse chunks and token slots, or 0 and 0: no match coder
+};
 struct Work {
     u64* offs_in;
     u32 *hist, *table, *hdr, *hdr_bits, *mode, *adler;
     u64 *seg_bytes, *out_offs;
     unsigned char* filtered;
-};
-static inline void carve_into(Arena& a, int nb, size_t filtered_bytes, Work* w) {
-    w->offs_in = a.take<u64>((size_t)nb + 1);
-    w->hist = a.take<u32>((size_t)nb * kStride);
-    w->table = a.take<u32>((size_t)nb * kStride);
-    w->hdr = a.take<u32>((size_t)nb * kHdrWords);
-    w->hdr_bits = a.take<u32>((size_t)nb);
-    w->mode = a.take<u32>((size_t)nb);
-    w->adler = a.take<u32>(2 * (size_t)nb);
-    w->seg_bytes = a.take<u64>((size_t)nb);
-    w->out_offs = a.take<u64>((size_t)nb + 1);
-    w->filtered = a.take<unsigned char>(filtered_bytes);
-}
-static inline bool carve(void* ws, size_t bytes, int nb, size_t filtered_bytes, Work* w, size_t* used) {
-    Arena a(ws, bytes);
-    carve_into(a, nb, filtered_bytes, w);
-    if (used) *used = a.off;
-    return a.ok;
-}
-static inline size_t work_bytes(int nb, size_t filtered_bytes) {
-    Work w;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve(origin, ~(size_t)0, nb, filtered_bytes, &w, &used);
-    return used;
-}
-
-static inline size_t capacity(size_t total, int nb, bool zlib) {
-    return total + 5 * (total / kStoredMax + (size_t)nb) + (zlib ? 6 : 0) + 8;
-}
-
-// what the match coder keeps beside the literal coder's Work, carved behind it: the literal coder's layout does not move
-struct LzWork {
-    u32 *hist, *table, *hdr, *hdr_bits, *cnt, *chunk_first;
+    unsigned char* band_table;
+    u32 *lz_hist, *lz_table, *lz_hdr, *lz_hdr_bits, *cnt, *chunk_first;
     unsigned short* tok;
 };
-static inline void carve_lz(Arena& a, int nb, size_t chunks, size_t total, LzWork* w) {
-    w->hist = a.take<u32>((size_t)nb * kLzStride);
-    w->table = a.take<u32>((size_t)nb * kLzStride);
-    w->hdr = a.take<u32>((size_t)nb * kLzHdrWords);
-    w->hdr_bits = a.take<u32>((size_t)nb);
-    w->cnt = a.take<u32>(chunks);
-    w->chunk_first = a.take<u32>((size_t)nb + 1);
-    w->tok = a.take<unsigned short>(total);
+// The literal coder's arrays, then the band table, then the match coder's: what a call adds lies behind what every call has, so the
+// literal coder's layout is the same in all of them.
+static void carve(Arena& a, const Layout& l, Work* w) {
+    const size_t nb = (size_t)l.nb;
+    *w = Work{};
+    w->offs_in = a.take<u64>(nb + 1);
+    w->hist = a.take<u32>(nb * kStride);
+    w->table = a.take<u32>(nb * kStride);
+    w->hdr = a.take<u32>(nb * kHdrWords);
+    w->hdr_bits = a.take<u32>(nb);
+    w->mode = a.take<u32>(nb);
+    w->adler = a.take<u32>(2 * nb);
+    w->seg_bytes = a.take<u64>(nb);
+    w->out_offs = a.take<u64>(nb + 1);
+    w->filtered = a.take<unsigned char>(l.filtered);
+    if (l.table) w->band_table = a.take<unsigned char>(l.table);
+    if (!l.chunks) return;
+    w->lz_hist = a.take<u32>(nb * kLzStride);
+    w->lz_table = a.take<u32>(nb * kLzStride);
+    w->lz_hdr = a.take<u32>(nb * kLzHdrWords);
+    w->lz_hdr_bits = a.take<u32>(nb);
+    w->cnt = a.take<u32>(l.chunks);
+    w->chunk_first = a.take<u32>(nb + 1);
+    w->tok = a.take<unsigned short>(l.tokens);
 }
-static inline bool carve_with_lz(void* ws, size_t bytes, int nb, size_t filtered_bytes, size_t chunks, size_t total, Work* w, LzWork* lz,
-                                 size_t* used) {
+static size_t work_bytes(const Layout& l) {
+    static char origin[1];                                   // offsets only: nothing is dereferenced
+    Arena a(origin, ~(size_t)0);
+    Work w;
+    carve(a, l, &w);
+    return a.off;
+}
+// false: `bytes` is less than work_bytes(l)
+static bool carve_workspace(void* ws, size_t bytes, const Layout& l, Work* w) {
     Arena a(ws, bytes);
-    carve_into(a, nb, filtered_bytes, w);
-    carve_lz(a, nb, chunks, total, lz);
-    if (used) *used = a.off;
+    carve(a, l, w);
     return a.ok;
 }
-static inline size_t lz_work_bytes(int nb, size_t filtered_bytes, size_t chunks, size_t total) {
-    Work w;
-    LzWork lz;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve_with_lz(origin, ~(size_t)0, nb, filtered_bytes, chunks, total, &w, &lz, &used);
-    return used;
-}
-static inline u64 lz_chunks_of(u64 bytes) { return (bytes + kLzChunk - 1) / kLzChunk; }
 
-// the match coder's launches around the literal coder's plan: p holds the bands and the literal histograms, q the rest.  `scan` runs
-// between the plans and the packers (the single stream's scan or the tiles').
+// one image (or the crops of one): nb bands over `total` filtered bytes; chunks: the match coder's parse chunks, 0 without it
+static Layout image_layout(int nb, size_t total, size_t chunks) {
+    Layout l{};
+    l.nb = nb;
+    l.filtered = total;
+    l.chunks = chunks;
+    l.tokens = chunks ? total : 0;
+    return l;
+}
+// every band has at most ceil(bytes / 4096) <= bytes / 4096 + 1 chunks
+static inline size_t lz_chunk_bound(size_t total_bytes, int n_bands) { return total_bytes / kLzChunk + (size_t)n_bands; }
+// nb bands of the caller's own `total` bytes
+static Layout bands_layout(int nb, size_t total, bool lz) {
+    Layout l{};
+    l.nb = nb;
+    l.chunks = lz ? lz_chunk_bound(total, nb) : 0;
+    l.tokens = lz ? total : 0;
+    return l;
+}
+
+static Bands uniform_bands(u64 band_bytes, u64 total, int nb) {
+    Bands b{};
+    b.band_bytes = band_bytes;
+    b.total = total;
+    b.nb = nb;
+    return b;
+}
+static Bands listed_bands(const u64* offs, int nb) {
+    Bands b{};
+    b.offs = offs;
+    b.nb = nb;
+    return b;
+}
+// A call's DeflateP over its workspace.  Where the result goes is the caller's to name: out, base, adler and total (a single stream),
+// tiles, and out_offs where the caller keeps them itself.
+static DeflateP deflate_params(const unsigned char* data, const Bands& b, const Work& w) {
+    DeflateP p{};
+    p.data = data;
+    p.b = b;
+    p.hist = w.hist;
+    p.table = w.table;
+    p.hdr = w.hdr;
+    p.hdr_bits = w.hdr_bits;
+    p.mode = w.mode;
+    p.seg_bytes = w.seg_bytes;
+    p.out_offs = w.out_offs;
+    return p;
+}
+// The match coder's LzP beside a finished p.  The caller names the lines (line, or rects with p.tiles), bpp, base0 and the chunks
+// (chunk_first or cpb, and their number).
+static LzP lz_params(const DeflateP& p, const Work& w) {
+    LzP q{};
+    q.d = p;
+    q.tok = w.tok;
+    q.cnt = w.cnt;
+    q.hist = w.lz_hist;
+    q.table = w.lz_table;
+    q.hdr = w.lz_hdr;
+    q.hdr_bits = w.lz_hdr_bits;
+    return q;
+}
+
+template <typename P>
+static int launch(const char* name, void (*kernel)(P), size_t grid, int threads, hipStream_t s, const P& p) {
+    ProfScope prof(name, s);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), 0, s, p);
+    return launch_status(name);
+}
+
+// The coder's launches over the bands of p (histograms already in p.hist): plan, scan, pack.  With the match coder (q, null without
+// it) the parse goes first and its plan and its packer follow the literal coder's.  `scan` runs between the plans and the packers:
+// the single stream's scan or the tiles'.
 template <typename Scan>
-static int run_deflate_lz(DeflateP& p, LzP& q, int nb, size_t chunks, Scan scan, hipStream_t s) {
-    if (hipMemsetAsync(q.hist, 0, (size_t)nb * kLzStride * sizeof(u32), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    {
-        ProfScope prof("deflate_lz_match", s);
-        hipLaunchKernelGGL(deflate_lz_match_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, s, q);
-        int rc = launch_status("deflate_lz_match");
-        if (rc) return rc;
+static int run_deflate(const DeflateP& p, const LzP* q, Scan scan, hipStream_t s) {
+    const int nb = p.b.nb;
+    int rc = CIAOSR_OK;
+    if (q) {
+        if (hipMemsetAsync(q->hist, 0, (size_t)nb * kLzStride * sizeof(u32), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+        rc = launch("deflate_lz_match", deflate_lz_match_kernel, q->chunks, kThreads, s, *q);
     }
-    {
-        ProfScope prof("deflate_plan", s);
-        hipLaunchKernelGGL(deflate_plan_kernel, dim3(nb), dim3(kWave), 0, s, p);
-        int rc = launch_status("deflate_plan");
-        if (rc) return rc;
-    }
-    {
-        ProfScope prof("deflate_lz_plan", s);
-        hipLaunchKernelGGL(deflate_lz_plan_kernel, dim3(nb), dim3(kWave), 0, s, q);
-        int rc = launch_status("deflate_lz_plan");
-        if (rc) return rc;
-    }
-    int rc = scan();
-    if (rc) return rc;
-    {
-        ProfScope prof("deflate_pack", s);
-        hipLaunchKernelGGL(deflate_pack_kernel, dim3(nb), dim3(kThreads), 0, s, p);
-        rc = launch_status("deflate_pack");
-        if (rc) return rc;
-    }
-    ProfScope prof("deflate_lz_pack", s);
-    hipLaunchKernelGGL(deflate_lz_pack_kernel, dim3(nb), dim3(kThreads), 0, s, q);
-    return launch_status("deflate_lz_pack");
-}
-static LzP lz_params(const DeflateP& p, const LzWork& lz, u64 line, int bpp, u64 base0, const u32* chunk_first, u32 cpb) {
-    return LzP{p.data, p.b, p.tiles, nullptr, line, bpp, base0, chunk_first, cpb, lz.tok, lz.cnt, lz.hist, lz.table, lz.hdr, lz.hdr_bits,
-               p.mode, p.seg_bytes, p.out_offs, p.out};
-}
-static int scan_single(DeflateP& p, hipStream_t s) {
-    ProfScope prof("deflate_scan", s);
-    hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
-    return launch_status("deflate_scan");
-}
-
-// plan, scan and pack of the bands described by p.b (histograms already in p.hist)
-static int run_deflate(DeflateP& p, hipStream_t s) {
-    {
-        ProfScope prof("deflate_plan", s);
-        hipLaunchKernelGGL(deflate_plan_kernel, dim3(p.b.nb), dim3(kWave), 0, s, p);
-        int rc = launch_status("deflate_plan");
-        if (rc) return rc;
-    }
-    {
-        ProfScope prof("deflate_scan", s);
-        hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(kThreads), 0, s, p);
-        int rc = launch_status("deflate_scan");
-        if (rc) return rc;
-    }
-    ProfScope prof("deflate_pack", s);
-    hipLaunchKernelGGL(deflate_pack_kernel, dim3(p.b.nb), dim3(kThreads), 0, s, p);
-    return launch_status("deflate_pack");
+    if (!rc) rc = launch("deflate_plan", deflate_plan_kernel, nb, kWave, s, p);
+    if (!rc && q) rc = launch("deflate_lz_plan", deflate_lz_plan_kernel, nb, kWave, s, *q);
+    if (!rc) rc = scan();
+    if (!rc) rc = launch("deflate_pack", deflate_pack_kernel, nb, kThreads, s, p);
+    if (!rc && q) rc = launch("deflate_lz_pack", deflate_lz_pack_kernel, nb, kThreads, s, *q);
+    return rc;
 }
 
 static int run_filter(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int R, unsigned char* dst, u32* hist,
                       u32* adler, hipStream_t s) {
-    FilterP f{src, pitch, H, W, bgr, R, dst, hist, adler};
-    const char* name = bpp == 4 ? "png_rgba_filter_u8" : "png_filter_u8";
-    ProfScope prof(name, s);
-    if (bpp == 4)
-        hipLaunchKernelGGL(png_filter_kernel<4>, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
-    else
-        hipLaunchKernelGGL(png_filter_kernel<3>, dim3(ceil_div(H, R)), dim3(kThreads), 0, s, f);
-    return launch_status(name);
+    FilterP f{};
+    f.src = src;
+    f.pitch = pitch;
+    f.H = H;
+    f.W = W;
+    f.bgr = bgr;
+    f.R = R;
+    f.dst = dst;
+    f.hist = hist;
+    f.adler = adler;
+    const int nb = ceil_div(H, R);
+    return bpp == 4 ? launch("png_rgba_filter_u8", png_filter_kernel<4>, nb, kThreads, s, f)
+                    : launch("png_filter_u8", png_filter_kernel<3>, nb, kThreads, s, f);
 }
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
@@ -1564,40 +1511,10 @@ static TilePlan plan_tiles(int bpp, const int* rects, int n_tiles, int rows_arg,
     }
     return t;
 }
-
-struct TileWork {
-    Work w;
-    unsigned char* table;
-};
-static inline bool carve_tiles(void* ws, size_t bytes, const TilePlan& t, TileWork* w, size_t* used) {
-    Arena a(ws, bytes);
-    carve_into(a, t.nb, (size_t)t.total, &w->w);
-    w->table = a.take<unsigned char>(t.table_bytes);
-    if (used) *used = a.off;
-    return a.ok;
-}
-static inline bool carve_tiles_lz(void* ws, size_t bytes, const TilePlan& t, TileWork* w, LzWork* lz, size_t* used) {
-    Arena a(ws, bytes);
-    carve_into(a, t.nb, (size_t)t.total, &w->w);
-    w->table = a.take<unsigned char>(t.table_bytes);
-    carve_lz(a, t.nb, (size_t)t.chunks, (size_t)t.total, lz);
-    if (used) *used = a.off;
-    return a.ok;
-}
-static inline size_t tile_work_bytes_lz(const TilePlan& t) {
-    TileWork w;
-    LzWork lz;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve_tiles_lz(origin, ~(size_t)0, t, &w, &lz, &used);
-    return used;
-}
-static inline size_t tile_work_bytes(const TilePlan& t) {
-    TileWork w;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve_tiles(origin, ~(size_t)0, t, &w, &used);
-    return used;
+static Layout tile_layout(const TilePlan& t, bool lz) {
+    Layout l = image_layout(t.nb, (size_t)t.total, lz ? (size_t)t.chunks : 0);
+    l.table = t.table_bytes;
+    return l;
 }
 
 }  // namespace png
@@ -1606,7 +1523,12 @@ static inline size_t tile_work_bytes(const TilePlan& t) {
 using namespace ciaosr;
 using namespace ciaosr::png;
 
-// ---- the entry points' bodies, for 3 (R G B) or 4 (R G B A) bytes per pixel --------------------------------------------------------
+// ---- the entry points' bodies, for 3 (R G B) or 4 (R G B A) bytes per pixel; lz: the match coder's entry points -------------------
+static int rows_per_band_entry(int bpp, int W, int rows_per_band_arg) {
+    if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
+    return rows_per_band(W, rows_per_band_arg, bpp);
+}
+
 static int filter_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg, unsigned char* dst,
                         unsigned int* hist, unsigned int* adler, void* stream) {
     CIAOSR_CHECK_ARG(dst && hist && adler && image_ok(H, W) && source_ok(bpp, src, pitch, W));
@@ -1617,14 +1539,14 @@ static int filter_entry(int bpp, const unsigned char* src, size_t pitch, int H, 
     return run_filter(bpp, src, pitch, H, W, bgr, R, dst, hist, adler, (hipStream_t)stream);
 }
 
-static size_t workspace_entry(int bpp, int H, int W, int rows_per_band_arg, bool lz = false) {
+static size_t workspace_entry(int bpp, int H, int W, int rows_per_band_arg, bool lz) {
     if (!image_ok(H, W) || rows_per_band_arg < 0) return 0;
     const int R = rows_per_band(W, rows_per_band_arg, bpp);
     const size_t L = (size_t)bpp * (size_t)W + 1, total = (size_t)H * L;
     const int nb = ceil_div(H, R);
-    if (!lz) return work_bytes(nb, total);
+    if (!lz) return work_bytes(image_layout(nb, total, 0));
     if ((u64)R * L > kMaxBand) return 0;
-    return lz_work_bytes(nb, total, (size_t)nb * (size_t)lz_chunks_of((u64)R * L), total);
+    return work_bytes(image_layout(nb, total, (size_t)nb * (size_t)lz_chunks_of((u64)R * L)));
 }
 
 static size_t capacity_entry(int bpp, int H, int W, int rows_per_band_arg) {
@@ -1633,9 +1555,9 @@ static size_t capacity_entry(int bpp, int H, int W, int rows_per_band_arg) {
     return capacity((size_t)H * ((size_t)bpp * (size_t)W + 1), ceil_div(H, R), true);
 }
 
-static int encode_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg, unsigned char* out,
-                        size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                        bool lz = false) {
+static int encode_entry(int bpp, bool lz, const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                        unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes,
+                        void* stream) {
     CIAOSR_CHECK_ARG(out && total_bytes && workspace && image_ok(H, W) && source_ok(bpp, src, pitch, W));
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0);
@@ -1646,30 +1568,38 @@ static int encode_entry(int bpp, const unsigned char* src, size_t pitch, int H, 
     const int nb = ceil_div(H, R);
     const u64 total = (u64)H * L;
     if (out_capacity < capacity(total, nb, true)) return CIAOSR_ERR_WORKSPACE;
-    Work w;
-    LzWork lw;
     const u64 cpb = lz_chunks_of((u64)R * L);
     const size_t chunks = (size_t)nb * (size_t)cpb;
-    if (lz) {
-        if (workspace_bytes < lz_work_bytes(nb, total, chunks, total) ||
-            !carve_with_lz(workspace, workspace_bytes, nb, total, chunks, total, &w, &lw, nullptr))
-            return CIAOSR_ERR_WORKSPACE;
-    } else if (workspace_bytes < work_bytes(nb, total) || !carve(workspace, workspace_bytes, nb, total, &w, nullptr)) {
-        return CIAOSR_ERR_WORKSPACE;
-    }
+    Work w;
+    if (!carve_workspace(workspace, workspace_bytes, image_layout(nb, total, lz ? chunks : 0), &w)) return CIAOSR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     int rc = run_filter(bpp, src, pitch, H, W, bgr, R, w.filtered, w.hist, w.adler, s);
     if (rc) return rc;
-    DeflateP p{w.filtered, Bands{nullptr, (u64)R * L, total, nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 2ull,
-               out, w.adler, total_bytes};
-    if (!lz) return run_deflate(p, s);
-    LzP q = lz_params(p, lw, L, bpp, 0ull, nullptr, (u32)cpb);
-    return run_deflate_lz(p, q, nb, chunks, [&] { return scan_single(p, s); }, s);
+    DeflateP p = deflate_params(w.filtered, uniform_bands((u64)R * L, total, nb), w);
+    p.base = 2ull;
+    p.out = out;
+    p.adler = w.adler;
+    p.total = total_bytes;
+    LzP q = lz_params(p, w);
+    q.line = L;
+    q.bpp = bpp;
+    q.cpb = (u32)cpb;
+    q.chunks = (u32)chunks;
+    return run_deflate(p, lz ? &q : nullptr, [&] { return launch("deflate_scan", deflate_scan_kernel, 1, kThreads, s, p); }, s);
 }
 
-static int encode_tiles_entry(int bpp, const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
-                              int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
-                              void* workspace, size_t workspace_bytes, void* stream, bool lz = false) {
+static size_t tiles_workspace_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg, bool lz) {
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr, lz);
+    return t.rc == CIAOSR_OK ? work_bytes(tile_layout(t, lz)) : 0;
+}
+static size_t tiles_capacity_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
+    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
+    return t.rc == CIAOSR_OK ? t.capacity : 0;
+}
+
+static int encode_tiles_entry(int bpp, bool lz, const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects,
+                              int n_tiles, int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                              void* workspace, size_t workspace_bytes, void* stream) {
     CIAOSR_CHECK_ARG(rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && source_ok(bpp, src, pitch, W));
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && rows_per_band_arg >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0);
@@ -1679,157 +1609,166 @@ static int encode_tiles_entry(int bpp, const unsigned char* src, size_t pitch, i
     CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image
     if (t.rc != CIAOSR_OK) return t.rc;
     if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
-    TileWork tw;
-    LzWork lw;
-    if (lz) {
-        if (workspace_bytes < tile_work_bytes_lz(t) || !carve_tiles_lz(workspace, workspace_bytes, t, &tw, &lw, nullptr))
-            return CIAOSR_ERR_WORKSPACE;
-    } else if (workspace_bytes < tile_work_bytes(t) || !carve_tiles(workspace, workspace_bytes, t, &tw, nullptr)) {
-        return CIAOSR_ERR_WORKSPACE;
-    }
-    const Work& w = tw.w;
+    Work w;
+    if (!carve_workspace(workspace, workspace_bytes, tile_layout(t, lz), &w)) return CIAOSR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // from pageable memory: the copy has left `table` when the call returns
-    if (hipMemcpyAsync(tw.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    const u64* offs = reinterpret_cast<const u64*>(tw.table);
-    const TileBand* bands = reinterpret_cast<const TileBand*>(tw.table + t.o_bands);
-    const u32* first = reinterpret_cast<const u32*>(tw.table + t.o_first);
-    const int* d_rects = reinterpret_cast<const int*>(tw.table + t.o_rects);
-    {
-        TileFilterP f{src, pitch, bgr, d_rects, bands, offs, w.filtered, w.hist, w.adler};
-        const char* name = bpp == 4 ? "png_rgba_filter_tiles_u8" : "png_filter_tiles_u8";
-        ProfScope prof(name, s);
-        if (bpp == 4)
-            hipLaunchKernelGGL(png_filter_tiles_kernel<4>, dim3(t.nb), dim3(kThreads), 0, s, f);
-        else
-            hipLaunchKernelGGL(png_filter_tiles_kernel<3>, dim3(t.nb), dim3(kThreads), 0, s, f);
-        int rc = launch_status(name);
-        if (rc) return rc;
-    }
-    DeflateP p{w.filtered, Bands{offs, 0ull, 0ull, t.nb}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, w.out_offs, 0ull, out,
-               w.adler, nullptr, bands};
-    if (lz) {
-        LzP q = lz_params(p, lw, 0ull, bpp, 0ull, reinterpret_cast<const u32*>(tw.table + t.o_chunks), 0u);
-        q.rects = d_rects;
-        auto scan = [&] {
-            TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
-            ProfScope prof("png_tiles_scan", s);
-            hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
-            return launch_status("png_tiles_scan");
-        };
-        return run_deflate_lz(p, q, t.nb, (size_t)t.chunks, scan, s);
-    }
-    {
-        ProfScope prof("deflate_plan", s);
-        hipLaunchKernelGGL(deflate_plan_kernel, dim3(t.nb), dim3(kWave), 0, s, p);
-        int rc = launch_status("deflate_plan");
-        if (rc) return rc;
-    }
-    {
-        TileScanP sp{offs, first, w.seg_bytes, w.adler, w.out_offs, tile_offs, out, t.nt};
-        ProfScope prof("png_tiles_scan", s);
-        hipLaunchKernelGGL(png_tiles_scan_kernel, dim3(1), dim3(kThreads), 0, s, sp);
-        int rc = launch_status("png_tiles_scan");
-        if (rc) return rc;
-    }
-    ProfScope prof("deflate_pack", s);
-    hipLaunchKernelGGL(deflate_pack_kernel, dim3(t.nb), dim3(kThreads), 0, s, p);
-    return launch_status("deflate_pack");
+    if (hipMemcpyAsync(w.band_table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    const u64* offs = reinterpret_cast<const u64*>(w.band_table);
+    const TileBand* bands = reinterpret_cast<const TileBand*>(w.band_table + t.o_bands);
+    const int* d_rects = reinterpret_cast<const int*>(w.band_table + t.o_rects);
+    TileFilterP f{};
+    f.src = src;
+    f.pitch = pitch;
+    f.bgr = bgr;
+    f.rects = d_rects;
+    f.bands = bands;
+    f.offs = offs;
+    f.dst = w.filtered;
+    f.hist = w.hist;
+    f.adler = w.adler;
+    int rc = bpp == 4 ? launch("png_rgba_filter_tiles_u8", png_filter_tiles_kernel<4>, t.nb, kThreads, s, f)
+                      : launch("png_filter_tiles_u8", png_filter_tiles_kernel<3>, t.nb, kThreads, s, f);
+    if (rc) return rc;
+    DeflateP p = deflate_params(w.filtered, listed_bands(offs, t.nb), w);
+    p.out = out;
+    p.adler = w.adler;
+    p.tiles = bands;
+    LzP q = lz_params(p, w);
+    q.rects = d_rects;
+    q.bpp = bpp;
+    q.chunk_first = reinterpret_cast<const u32*>(w.band_table + t.o_chunks);
+    q.chunks = (u32)t.chunks;
+    TileScanP sp{};
+    sp.offs = offs;
+    sp.first = reinterpret_cast<const u32*>(w.band_table + t.o_first);
+    sp.seg_bytes = w.seg_bytes;
+    sp.adler = w.adler;
+    sp.out_offs = w.out_offs;
+    sp.tile_offs = tile_offs;
+    sp.out = out;
+    sp.nt = t.nt;
+    return run_deflate(p, lz ? &q : nullptr, [&] { return launch("png_tiles_scan", png_tiles_scan_kernel, 1, kThreads, s, sp); }, s);
 }
 
-extern "C" int ciaosr_png_rows_per_band(int W, int rows_per_band_arg) {
-    if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
-    return rows_per_band(W, rows_per_band_arg, 3);
+// ---- raw deflate of the caller's bytes in explicit bands -----------------------------------------------------------------------------
+static size_t deflate_workspace_entry(size_t total_bytes, int n_bands, bool lz) {
+    if (n_bands <= 0) return 0;
+    if (lz && (total_bytes < (size_t)n_bands || lz_chunk_bound(total_bytes, n_bands) > (size_t)INT_MAX)) return 0;
+    return work_bytes(bands_layout(n_bands, total_bytes, lz));
+}
+static size_t deflate_capacity_entry(size_t total_bytes, int n_bands) { return n_bands <= 0 ? 0 : capacity(total_bytes, n_bands, false); }
+
+// line, bpp: the match coder's (lz) only
+static int deflate_entry(bool lz, const unsigned char* data, const unsigned long long* band_offsets, int n_bands, int line, int bpp,
+                         unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    CIAOSR_CHECK_ARG(data && band_offsets && out && seg_offsets && workspace && n_bands > 0);
+    if (lz) CIAOSR_CHECK_ARG(line >= 0 && bpp >= 1 && (line == 0 || line > bpp));             // line - bpp is a distance: >= 1
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(seg_offsets) & 7u) == 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    std::vector<u32> first((size_t)n_bands + 1, 0u);          // the first parse chunk of every band
+    for (int i = 0; i < n_bands; ++i) {
+        CIAOSR_CHECK_ARG(band_offsets[i + 1] > band_offsets[i]);            // an empty band has no histogram to code
+        if (band_offsets[i + 1] - band_offsets[i] > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
+        first[i + 1] = first[i] + (u32)lz_chunks_of(band_offsets[i + 1] - band_offsets[i]);
+    }
+    const u64 total = band_offsets[n_bands] - band_offsets[0];
+    const Layout l = bands_layout(n_bands, total, lz);
+    if (l.chunks > (size_t)INT_MAX) return CIAOSR_ERR_UNSUPPORTED;
+    if (out_capacity < capacity(total, n_bands, false)) return CIAOSR_ERR_WORKSPACE;
+    Work w;
+    if (!carve_workspace(workspace, workspace_bytes, l, &w)) return CIAOSR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    // from pageable memory: both copies have left the host arrays when the calls return
+    if (hipMemcpyAsync(w.offs_in, band_offsets, ((size_t)n_bands + 1) * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess)
+        return CIAOSR_ERR_LAUNCH;
+    if (lz && hipMemcpyAsync(w.chunk_first, first.data(), first.size() * sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess)
+        return CIAOSR_ERR_LAUNCH;
+    DeflateP p = deflate_params(data, listed_bands(w.offs_in, n_bands), w);
+    p.out_offs = seg_offsets;
+    p.out = out;
+    p.total = seg_offsets + n_bands;
+    int rc = launch("deflate_hist", deflate_hist_kernel, n_bands, kThreads, s, p);
+    if (rc) return rc;
+    LzP q = lz_params(p, w);
+    q.line = (u64)line;
+    q.bpp = bpp;
+    q.base0 = band_offsets[0];
+    q.chunk_first = w.chunk_first;
+    q.chunks = first[n_bands];
+    return run_deflate(p, lz ? &q : nullptr, [&] { return launch("deflate_scan", deflate_scan_kernel, 1, kThreads, s, p); }, s);
 }
 
-extern "C" int ciaosr_png_rgba_rows_per_band(int W, int rows_per_band_arg) {
-    if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
-    return rows_per_band(W, rows_per_band_arg, 4);
-}
+// ---- the exports: the scanline filter alone, raw deflate alone, then the encoders as RGB / RGBA x literals / matches (lz) ----------
+extern "C" int ciaosr_png_rows_per_band(int W, int rows_per_band_arg) { return rows_per_band_entry(3, W, rows_per_band_arg); }
+extern "C" int ciaosr_png_rgba_rows_per_band(int W, int rows_per_band_arg) { return rows_per_band_entry(4, W, rows_per_band_arg); }
 
 extern "C" int ciaosr_png_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                     unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
     return filter_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler, stream);
 }
-
 extern "C" int ciaosr_png_rgba_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                          unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
     return filter_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler, stream);
 }
 
-extern "C" size_t ciaosr_deflate_huff_workspace_bytes(int n_bands) {
-    if (n_bands <= 0) return 0;
-    return work_bytes(n_bands, 0);
-}
-
-extern "C" size_t ciaosr_deflate_huff_capacity_bytes(size_t total_bytes, int n_bands) {
-    if (n_bands <= 0) return 0;
-    return capacity(total_bytes, n_bands, false);
-}
-
+extern "C" size_t ciaosr_deflate_huff_workspace_bytes(int n_bands) { return deflate_workspace_entry(0, n_bands, false); }
+extern "C" size_t ciaosr_deflate_lz_workspace_bytes(size_t total_bytes, int n_bands) { return deflate_workspace_entry(total_bytes, n_bands, true); }
+extern "C" size_t ciaosr_deflate_huff_capacity_bytes(size_t total_bytes, int n_bands) { return deflate_capacity_entry(total_bytes, n_bands); }
 extern "C" int ciaosr_deflate_huff_u8(const unsigned char* data, const unsigned long long* band_offsets, int n_bands,
                                       unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(data && band_offsets && out && seg_offsets && workspace && n_bands > 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(seg_offsets) & 7u) == 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    for (int i = 0; i < n_bands; ++i) {
-        CIAOSR_CHECK_ARG(band_offsets[i + 1] > band_offsets[i]);            // an empty band has no histogram to code
-        if (band_offsets[i + 1] - band_offsets[i] > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
-    }
-    const u64 total = band_offsets[n_bands] - band_offsets[0];
-    if (out_capacity < capacity(total, n_bands, false)) return CIAOSR_ERR_WORKSPACE;
-    Work w;
-    if (workspace_bytes < work_bytes(n_bands, 0) || !carve(workspace, workspace_bytes, n_bands, 0, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemcpyAsync(w.offs_in, band_offsets, ((size_t)n_bands + 1) * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess)
-        return CIAOSR_ERR_LAUNCH;
-    DeflateP p{data, Bands{w.offs_in, 0ull, 0ull, n_bands}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, seg_offsets, 0ull, out,
-               nullptr, seg_offsets + n_bands};
-    {
-        ProfScope prof("deflate_hist", s);
-        hipLaunchKernelGGL(deflate_hist_kernel, dim3(n_bands), dim3(kThreads), 0, s, p);
-        int rc = launch_status("deflate_hist");
-        if (rc) return rc;
-    }
-    return run_deflate(p, s);
+    return deflate_entry(false, data, band_offsets, n_bands, 0, 1, out, out_capacity, seg_offsets, workspace, workspace_bytes, stream);
+}
+extern "C" int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* band_offsets, int n_bands, int line, int bpp,
+                                    unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    return deflate_entry(true, data, band_offsets, n_bands, line, bpp, out, out_capacity, seg_offsets, workspace, workspace_bytes, stream);
 }
 
-extern "C" size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg); }
+extern "C" size_t ciaosr_png_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg, false); }
+extern "C" size_t ciaosr_png_rgba_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(4, H, W, rows_per_band_arg, false); }
+extern "C" size_t ciaosr_png_lz_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg, true); }
+extern "C" size_t ciaosr_png_rgba_lz_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(4, H, W, rows_per_band_arg, true); }
 extern "C" size_t ciaosr_png_capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(3, H, W, rows_per_band_arg); }
-extern "C" size_t ciaosr_png_rgba_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(4, H, W, rows_per_band_arg); }
 extern "C" size_t ciaosr_png_rgba_capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(4, H, W, rows_per_band_arg); }
 
 extern "C" int ciaosr_png_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                     unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    return encode_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+    return encode_entry(3, false, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
 }
-
 extern "C" int ciaosr_png_rgba_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
                                          unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-    return encode_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+    return encode_entry(4, false, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
 }
-
-static size_t tiles_workspace_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg, bool lz = false) {
-    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr, lz);
-    if (t.rc != CIAOSR_OK) return 0;
-    return lz ? tile_work_bytes_lz(t) : tile_work_bytes(t);
+extern "C" int ciaosr_png_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                       unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return encode_entry(3, true, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
 }
-static size_t tiles_capacity_entry(int bpp, const int* rects, int n_tiles, int rows_per_band_arg) {
-    const TilePlan t = plan_tiles(bpp, rects, n_tiles, rows_per_band_arg, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? t.capacity : 0;
+extern "C" int ciaosr_png_rgba_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                            unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return encode_entry(4, true, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ciaosr_png_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg);
+    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg, false);
+}
+extern "C" size_t ciaosr_png_rgba_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg, false);
+}
+extern "C" size_t ciaosr_png_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg, true);
+}
+extern "C" size_t ciaosr_png_rgba_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg, true);
 }
 extern "C" size_t ciaosr_png_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
     return tiles_capacity_entry(3, rects, n_tiles, rows_per_band_arg);
-}
-extern "C" size_t ciaosr_png_rgba_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg);
 }
 extern "C" size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
     return tiles_capacity_entry(4, rects, n_tiles, rows_per_band_arg);
@@ -1838,103 +1777,24 @@ extern "C" size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects, int n_t
 extern "C" int ciaosr_png_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                           int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-    return encode_tiles_entry(3, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+    return encode_tiles_entry(3, false, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
                               workspace_bytes, stream);
 }
-
 extern "C" int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                                int rows_per_band_arg, unsigned char* out, size_t out_capacity,
                                                unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
-    return encode_tiles_entry(4, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+    return encode_tiles_entry(4, false, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
                               workspace_bytes, stream);
 }
-
-// ---- the match coder's entry points: the same arguments, the same capacities, a larger workspace ----------------------------------
-extern "C" size_t ciaosr_png_lz_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(3, H, W, rows_per_band_arg, true); }
-extern "C" size_t ciaosr_png_rgba_lz_workspace_bytes(int H, int W, int rows_per_band_arg) {
-    return workspace_entry(4, H, W, rows_per_band_arg, true);
-}
-
-extern "C" int ciaosr_png_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
-                                       unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-    return encode_entry(3, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream,
-                        true);
-}
-
-extern "C" int ciaosr_png_rgba_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
-                                            unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-    return encode_entry(4, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream,
-                        true);
-}
-
-extern "C" size_t ciaosr_png_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    return tiles_workspace_entry(3, rects, n_tiles, rows_per_band_arg, true);
-}
-extern "C" size_t ciaosr_png_rgba_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
-    return tiles_workspace_entry(4, rects, n_tiles, rows_per_band_arg, true);
-}
-
 extern "C" int ciaosr_png_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                              int rows_per_band_arg, unsigned char* out, size_t out_capacity,
                                              unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
-    return encode_tiles_entry(3, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
-                              workspace_bytes, stream, true);
+    return encode_tiles_entry(3, true, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
 }
-
 extern "C" int ciaosr_png_rgba_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects,
                                                   int n_tiles, int rows_per_band_arg, unsigned char* out, size_t out_capacity,
                                                   unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
-    return encode_tiles_entry(4, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
-                              workspace_bytes, stream, true);
-}
-
-// every band has at most ceil(bytes / 4096) <= bytes / 4096 + 1 chunks
-static inline size_t lz_chunk_bound(size_t total_bytes, int n_bands) { return total_bytes / kLzChunk + (size_t)n_bands; }
-
-extern "C" size_t ciaosr_deflate_lz_workspace_bytes(size_t total_bytes, int n_bands) {
-    if (n_bands <= 0 || total_bytes < (size_t)n_bands || lz_chunk_bound(total_bytes, n_bands) > (size_t)INT_MAX) return 0;
-    return lz_work_bytes(n_bands, 0, lz_chunk_bound(total_bytes, n_bands), total_bytes);
-}
-
-extern "C" int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* band_offsets, int n_bands, int line, int bpp,
-                                    unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(data && band_offsets && out && seg_offsets && workspace && n_bands > 0);
-    CIAOSR_CHECK_ARG(line >= 0 && bpp >= 1 && (line == 0 || line > bpp));                     // line - bpp is a distance: >= 1
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(seg_offsets) & 7u) == 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    for (int i = 0; i < n_bands; ++i) {
-        CIAOSR_CHECK_ARG(band_offsets[i + 1] > band_offsets[i]);
-        if (band_offsets[i + 1] - band_offsets[i] > kMaxBand) return CIAOSR_ERR_UNSUPPORTED;
-    }
-    const u64 total = band_offsets[n_bands] - band_offsets[0];
-    const size_t bound = lz_chunk_bound(total, n_bands);
-    if (bound > (size_t)INT_MAX) return CIAOSR_ERR_UNSUPPORTED;
-    if (out_capacity < capacity(total, n_bands, false)) return CIAOSR_ERR_WORKSPACE;
-    Work w;
-    LzWork lw;
-    if (workspace_bytes < lz_work_bytes(n_bands, 0, bound, total) ||
-        !carve_with_lz(workspace, workspace_bytes, n_bands, 0, bound, total, &w, &lw, nullptr))
-        return CIAOSR_ERR_WORKSPACE;
-    std::vector<u32> first((size_t)n_bands + 1);
-    first[0] = 0u;
-    for (int i = 0; i < n_bands; ++i) first[i + 1] = first[i] + (u32)lz_chunks_of(band_offsets[i + 1] - band_offsets[i]);
-    hipStream_t s = (hipStream_t)stream;
-    // from pageable memory: both copies have left the host arrays when the calls return
-    if (hipMemcpyAsync(w.offs_in, band_offsets, ((size_t)n_bands + 1) * sizeof(u64), hipMemcpyHostToDevice, s) != hipSuccess)
-        return CIAOSR_ERR_LAUNCH;
-    if (hipMemcpyAsync(lw.chunk_first, first.data(), first.size() * sizeof(u32), hipMemcpyHostToDevice, s) != hipSuccess)
-        return CIAOSR_ERR_LAUNCH;
-    DeflateP p{data, Bands{w.offs_in, 0ull, 0ull, n_bands}, w.hist, w.table, w.hdr, w.hdr_bits, w.mode, w.seg_bytes, seg_offsets, 0ull, out,
-               nullptr, seg_offsets + n_bands};
-    {
-        ProfScope prof("deflate_hist", s);
-        hipLaunchKernelGGL(deflate_hist_kernel, dim3(n_bands), dim3(kThreads), 0, s, p);
-        int rc = launch_status("deflate_hist");
-        if (rc) return rc;
-    }
-    LzP q = lz_params(p, lw, (u64)line, bpp, band_offsets[0], lw.chunk_first, 0u);
-    return run_deflate_lz(p, q, n_bands, (size_t)first[n_bands], [&] { return scan_single(p, s); }, s);
+    return encode_tiles_entry(4, true, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
 }

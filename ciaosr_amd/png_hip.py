@@ -108,15 +108,21 @@ def zlib_stream(segments, partials):
     return b'\x78\x01' + b''.join(segments) + struct.pack('>I', adler32_combine(partials))
 
 
-def _geometry(img, order, rows_per_band):
-    """-> (h, w, rows per band, bands, channels, bgr flag)"""
+def _checked(img, order, rows_per_band, what='encode_png'):
+    """The checks of every encoder -> (h, w, rows_per_band as an int, 0 = the default, channels, bgr flag)"""
     ch, bgr = _check_image(img, order)
     h, w = img.shape[0], img.shape[1]
     rows = int(rows_per_band)
     if rows < 0:
         raise ValueError(f'rows_per_band={rows_per_band}')
     if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
-        raise CiaoSRHipError(f'encode_png: {h}x{w} is outside 1..{MAX_SIDE} per side')
+        raise CiaoSRHipError(f'{what}: {h}x{w} is outside 1..{MAX_SIDE} per side')
+    return h, w, rows, ch, bgr
+
+
+def _geometry(img, order, rows_per_band):
+    """-> (h, w, rows per band, bands, channels, bgr flag)"""
+    h, w, rows, ch, bgr = _checked(img, order, rows_per_band)
     rows = getattr(_lib.load(), _ABI[ch] + 'rows_per_band')(w, rows)
     return h, w, rows, -(-h // rows), ch, bgr
 
@@ -154,21 +160,18 @@ def deflate_huff(data, band_offsets, matches=False, line=0, bpp=1):
         raise ValueError(f'band offsets {offs[:4]}... do not lie inside the {data.numel()} bytes')
     dev = data.device
     lib = _lib.load()
-    cap = lib.ciaosr_deflate_huff_capacity_bytes(C.c_size_t(max(offs[-1] - offs[0], 0)), nb)
-    if matches:
-        nbytes = lib.ciaosr_deflate_lz_workspace_bytes(C.c_size_t(max(offs[-1] - offs[0], 0)), nb)
-    else:
-        nbytes = lib.ciaosr_deflate_huff_workspace_bytes(nb)
+    total = C.c_size_t(max(offs[-1] - offs[0], 0))
+    cap = lib.ciaosr_deflate_huff_capacity_bytes(total, nb)
+    nbytes = lib.ciaosr_deflate_lz_workspace_bytes(total, nb) if matches else lib.ciaosr_deflate_huff_workspace_bytes(nb)
     ws = hip_ops.workspace(nbytes, dev, slot='png')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     seg = torch.empty(nb + 1, dtype=torch.int64, device=dev)
     host_offs = (C.c_ulonglong * (nb + 1))(*offs)
-    if matches:
-        _lib.call('ciaosr_deflate_lz_u8', hip_ops.ptr(data), host_offs, nb, line, bpp, hip_ops.ptr(out), C.c_size_t(cap),
-                  hip_ops.ptr(seg), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
-    else:
-        _lib.call('ciaosr_deflate_huff_u8', hip_ops.ptr(data), host_offs, nb, hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(seg),
-                  hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    args = [hip_ops.ptr(data), host_offs, nb, hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(seg), hip_ops.ptr(ws), C.c_size_t(nbytes),
+            hip_ops.stream_ptr(dev)]
+    if matches:                                             # the same call with the scanline behind the bands
+        args[3:3] = [line, bpp]
+    _lib.call('ciaosr_deflate_lz_u8' if matches else 'ciaosr_deflate_huff_u8', *args)
     so = seg.cpu().tolist()
     raw = out[:so[-1]].cpu().numpy().tobytes()
     return [raw[so[i]:so[i + 1]] for i in range(nb)]
@@ -222,13 +225,7 @@ def encode_tiles_device(img, rects, order='bgr', rows_per_band=0, matches=False)
     """ciaosr_png_encode_tiles_u8 on the current stream, no synchronisation -> (streams uint8 [capacity], offsets int64 [n + 1]) on the
     device: crop k's zlib stream is streams[offsets[k]:offsets[k + 1]], offsets[0] = 0, no gaps."""
     lz = _check_matches(matches)
-    ch, bgr = _check_image(img, order)
-    rows = int(rows_per_band)
-    if rows < 0:
-        raise ValueError(f'rows_per_band={rows_per_band}')
-    h, w = img.shape[0], img.shape[1]
-    if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
-        raise CiaoSRHipError(f'encode_png_tiles: {h}x{w} is outside 1..{MAX_SIDE} per side')
+    h, w, rows, ch, bgr = _checked(img, order, rows_per_band, 'encode_png_tiles')
     rects = check_rects(rects, h, w)
     n = len(rects)
     dev = img.device
