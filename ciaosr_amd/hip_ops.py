@@ -235,6 +235,42 @@ def tile_finalize(E, Wt):
     return out
 
 
+# ---- self-ensemble (include/ciaosr_hip.h, "self-ensemble"; ids and windows: scene.dihedral_ids / dihedral_window) ----------------------
+def _planes(x, what):
+    require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise CiaoSRHipError(f'{what}: expected a float32 tensor [..., h, w], got {x.dtype} {tuple(x.shape)}')
+    planes = 1
+    for n in x.shape[:-2]:
+        planes *= int(n)
+    return planes
+
+
+def dihedral(x, k):
+    """T_k of the last two axes of x [..., h, w]: k & 1 flips the columns, then k & 2 the rows, then k & 4 transposes -> a new tensor
+    [..., h, w], or [..., w, h] when k & 4 (ciaosr_dihedral_f32)."""
+    planes = _planes(x, 'dihedral')
+    h, w = x.shape[-2:]
+    k = int(k)
+    out = torch.empty(*x.shape[:-2], *((w, h) if k & 4 else (h, w)), dtype=torch.float32, device=x.device)
+    _lib.call('ciaosr_dihedral_f32', ptr(x), ptr(out), planes, h, w, k, stream_ptr())
+    return out
+
+
+def dihedral_accum(acc, src, k, first, divisor=0.0):
+    """acc [..., h, w] = (0 if first else acc) + U_k(src), U_k the inverse of `dihedral`'s T_k (src [..., w, h] when k & 4); with
+    divisor > 0 the sum is then divided by it.  In place; `first` never reads acc (ciaosr_dihedral_accum_f32)."""
+    planes = _planes(acc, 'dihedral_accum')
+    _planes(src, 'dihedral_accum')
+    h, w = acc.shape[-2:]
+    k = int(k)
+    want = tuple(acc.shape[:-2]) + ((w, h) if k & 4 else (h, w))
+    if tuple(src.shape) != want:
+        raise ValueError(f'dihedral_accum: member {k} of an accumulator {tuple(acc.shape)} is {want}, got {tuple(src.shape)}')
+    _lib.call('ciaosr_dihedral_accum_f32', ptr(acc), ptr(src), planes, h, w, k, int(bool(first)), float(divisor), stream_ptr())
+    return acc
+
+
 # ---- affine views of an encoded scene (include/ciaosr_hip.h, "views"; the definition and the host helpers: scene.py) -------------------
 def _m6(m):
     m = [float(v) for v in m]

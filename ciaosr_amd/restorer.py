@@ -427,13 +427,52 @@ class CiaoSR(BasicRestorer):
             return hip_ops.DEFAULT_OPTIONS
         return hip_ops.Options(prec or 'fp32', **extra)          # 'fp32' | 'bf16' | 'f16' | 'f16-pairs'
 
+    def ensemble_ids(self, self_ensemble=None):
+        """The member ids a call runs with: `scene.dihedral_ids` of the explicit argument, or of `test_cfg.self_ensemble` (an extension;
+        default off) when the argument is None; None = off (pass False to turn a configured ensemble off for one call).  ValueError
+        for anything that is neither True nor a sequence of distinct ids in 0..7."""
+        if self_ensemble is None and self.test_cfg is not None:
+            self_ensemble = self.test_cfg.get('self_ensemble', None)
+        return scene.dihedral_ids(self_ensemble)
+
     @torch.no_grad()
-    def restore(self, lq, coord=None, cell=None, options=None):
+    def restore(self, lq, coord=None, cell=None, options=None, self_ensemble=None):
         """forward_test body from normalised LR on device to de-normalised, clamped output
         [B,3,round(h*s),round(w*s)] on device (ciaosr.py:142-169) -- the timed region of bench.py.
         `options` / `test_cfg.precision = 'bf16'` (an extension, absent from the reference) runs the dense layers
-        with bf16 MFMA inputs; the default is the exact-fp32 path."""
+        with bf16 MFMA inputs; the default is the exact-fp32 path.
+        `self_ensemble` (default `test_cfg.self_ensemble`; an extension, default off): True, or a sequence of distinct ids in 0..7 --
+        the geometric self-ensemble, `restore_ensemble`."""
+        ids = self.ensemble_ids(self_ensemble)
+        if ids is not None:
+            return self.restore_ensemble(lq, coord, cell, ids, self.options(options))
         return self._restore(lq, coord, cell, self.options(options))
+
+    def restore_ensemble(self, lq, coord, cell, ids, options):
+        """The mean over the members `ids` (scene.py, "self-ensemble"): member k is `_restore(T_k(lq), coord_k, cell_k)` -- the plain
+        restore of the flipped / transposed image under the same test_cfg and options, de-normalised and clamped; coord_k, cell_k are
+        the caller's tensors for k < 4 (the grid is the same) and `hip_ops.make_coord_cell(Wt, Ht)` for k & 4, (Ht, Wt) the target
+        size `_restore` derives.  The members are mapped back and summed in fp32 in the order given, one rounded add each, and the
+        sum is divided by their number, once (`hip_ops.dihedral_accum`).  One accumulator the size of the output; a member's output
+        is consumed before the next member runs."""
+        lq = lq.contiguous().float()
+        hip_ops.require_gpu(lq)
+        ih, iw = lq.shape[-2:]
+        if coord is not None:
+            s = math.sqrt(coord.shape[1] / (ih * iw))                 # `_restore`'s own size rule
+            ht, wt = round(ih * s), round(iw * s)
+        acc = None
+        for i, k in enumerate(ids):
+            ck, cl = coord, cell
+            if (k & 4) and coord is not None:
+                ck, cl = (t.unsqueeze(0).expand(lq.shape[0], -1, 2) for t in hip_ops.make_coord_cell(wt, ht, lq.device))
+            out = self._restore(hip_ops.dihedral(lq, k), ck, cl, options)
+            if acc is None:
+                oh, ow = out.shape[-2:]
+                acc = torch.empty(*out.shape[:2], *((ow, oh) if k & 4 else (oh, ow)), dtype=torch.float32, device=out.device)
+            hip_ops.dihedral_accum(acc, out, k, first=(i == 0), divisor=float(len(ids)) if i == len(ids) - 1 else 0.0)
+            del out
+        return acc
 
     @torch.no_grad()
     def clip_test_any_scale(self, img_lq, ht, wt, options=None):
@@ -456,16 +495,19 @@ class CiaoSR(BasicRestorer):
 
     # -- encode once, render any scale, window or view (an extension, absent from the reference): scene_render.py ----------------------
     @torch.no_grad()
-    def encode(self, lq, options=None, max_scale=None):
+    def encode(self, lq, options=None, max_scale=None, self_ensemble=None):
         """Everything `restore` computes from the LR image alone, kept: -> scene.EncodedImage for `render`.  Without `test_cfg.tile` the
         whole image's trunk and head scene, built here when `max_scale` is known (the argument, else `test_cfg.scale`; else at the first
         render, from its scale).  With `test_cfg.tile` one scene per LR tile, each built when a render first touches the tile and held
         under `test_cfg.scene_cache_mb` (default 4096) MiB, least recently used first out.  `max_scale` sizes the plan of every scene:
-        the full (tile) grid at that scale is the largest render whose route is `restore`'s own (include/ciaosr_hip.h, q_plan)."""
-        return scene_render.encode(self, lq, options, max_scale)
+        the full (tile) grid at that scale is the largest render whose route is `restore`'s own (include/ciaosr_hip.h, q_plan).
+        `self_ensemble` (default `test_cfg.self_ensemble`, as `restore`): -> scene.EnsembleEncoded, one plain encode per member T_k(lq),
+        `scene_cache_mb` split evenly over them; `render` / `render_many` of it give the windows of `restore(..., self_ensemble=ids)`,
+        bitwise.  `render_view`, `View` targets, `render_pyramid` and `prefetch` refuse such a record (ValueError)."""
+        return scene_render.encode(self, lq, options, max_scale, self_ensemble)
 
     @torch.no_grad()
-    def encode_rgba(self, lq4, options=None, max_scale=None):
+    def encode_rgba(self, lq4, options=None, max_scale=None, self_ensemble=None):
         """`encode` of an RGBA image [1, 4, h, w] (float, R G B A in [0, 1]) as a batch of two: item 0 the colour as stored (not
         premultiplied, whatever lies under transparent pixels), item 1 the alpha plane in all three channels; both go through the same
         model, options, tiling and scenes, and `enc.alpha` is set.  Every render of such an encode returns with `as_u8` ONE uint8
@@ -473,14 +515,17 @@ class CiaoSR(BasicRestorer):
         bitwise the render of the colour image alone; A = (4899 R + 9617 G + 1868 B + 8192) >> 14 of item 1's bytes), and without it
         the fp32 batch of two (colour, alpha as grey).  Outside a view the alpha item is 0 and the colour item the caller's `fill`.
         `render_pyramid` resizes colour and alpha separately below the LR size (not Pillow's premultiplied RGBA resize).  A tensor
-        that is not [1, 4, h, w] is a ValueError."""
-        return scene_render.encode_rgba(self, lq4, options, max_scale)
+        that is not [1, 4, h, w] is a ValueError, and so is `self_ensemble` (the argument or `test_cfg.self_ensemble`): RGBA encodes have
+        no ensemble."""
+        return scene_render.encode_rgba(self, lq4, options, max_scale, self_ensemble)
 
     @torch.no_grad()
     def render(self, enc, size=None, scale=None, window=None, as_u8=False):
         """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
         round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,
         or with `as_u8` the metrics_hip.tensor2img_u8 image of it.  Only the LR tiles whose HR rectangle meets the window are touched."""
+        if scene_render.is_ensemble(enc):
+            return scene_render.render_ensemble(self, enc, [scene.Grid(size, scale, window)], as_u8)[0]
         return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.Grid(size, scale, window)])[0], as_u8)
 
     @torch.no_grad()
@@ -493,6 +538,7 @@ class CiaoSR(BasicRestorer):
         `test_cfg.tile_any_scale`.  Per batch item ONE device-to-host copy -- the tiles' member counts, which size the per-tile query
         lists -- is the only synchronisation of a view render.  An axis-aligned view is not bitwise the window `render` shows (its
         coordinates differ by up to 2^-22, see `scene.view_of_window`)."""
+        scene_render.refuse_ensemble(enc, 'render_view')
         return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.View(matrix, size, fill)])[0], as_u8)
 
     @torch.no_grad()
@@ -554,7 +600,10 @@ class CiaoSR(BasicRestorer):
         """Capture `restore(lq)` (a few hundred short launches for a 48x48 tile) into one hipGraph and return a
         callable `run(new_lq=None) -> output` that replays it; input and output live in static buffers.  All
         kernels are launched on torch's current stream, workspaces are allocated during the warm-up calls, and
-        nothing in the path synchronises, so the whole step is capturable."""
+        nothing in the path synchronises, so the whole step is capturable.  Not with `test_cfg.self_ensemble` (ValueError): the ensemble
+        is not captured."""
+        if self.ensemble_ids() is not None:
+            raise ValueError('graphed_restore does not capture a self-ensemble: turn test_cfg.self_ensemble off, or call restore')
         static_lq = lq.clone()
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()

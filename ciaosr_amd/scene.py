@@ -8,6 +8,7 @@ work is in `PackedHead.prepare` / `query` (head_hip.py), `hip_ops.make_coord_cel
 """
 import ctypes
 import math
+import numbers
 from collections import OrderedDict
 
 from . import tile_plan
@@ -79,6 +80,39 @@ def plan_window(h, w, tile, overlap, ht, wt, window=None, scale=None, any_scale=
                 grid = (tile * scale, tile * scale, a0 - i0, a1 - i0, b0 - j0, b1 - j0, None)
             out.append(dict(index=ny * len(xs) + nx, y0=y0, x0=x0, th=tile, tw=tile, a0=a0, a1=a1, b0=b0, b1=b1, grid=grid))
     return out
+
+
+# ---- self-ensemble (include/ciaosr_hip.h, "self-ensemble") ---------------------------------------------------------------------------
+# Member k in 0..7 is the model's answer for T_k(lq): k & 1 flips the columns, then k & 2 the rows, then k & 4 transposes the two axes;
+# the answers are mapped back by U_k, the inverse, and averaged in member order (hip_ops.dihedral / dihedral_accum).
+def dihedral_ids(value):
+    """`self_ensemble` as a tuple of member ids: True -> (0, .., 7); a sequence of distinct ints in 0..7 -> itself, in its order;
+    False / None -> None (off).  Anything else -- duplicates, an id outside 0..7, a string, a float, an empty sequence -- is a
+    ValueError.  Pure host work: called before any device work."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return tuple(range(8))
+    if isinstance(value, (str, bytes)) or not hasattr(value, '__iter__'):
+        raise ValueError(f'self_ensemble is True (all eight members) or a sequence of distinct ids in 0..7, got {value!r}')
+    ids = list(value)
+    if not ids or any(isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k <= 7 for k in ids) or len(set(ids)) != len(ids):
+        raise ValueError(f'self_ensemble is True (all eight members) or a sequence of distinct ids in 0..7, got {value!r}')
+    return tuple(int(k) for k in ids)
+
+
+def dihedral_window(k, ht, wt, window=None):
+    """The window (i0, j0, hh, ww) of an ht x wt grid as member k sees it: -> (ht_k, wt_k, window_k) with
+    U_k(T_k(A)[window_k]) == A[window] for every A [ht, wt].  Column flip: j0' = wt - j0 - ww; row flip: i0' = ht - i0 - hh;
+    transpose: both pairs swapped.  `window` None: the whole grid."""
+    i0, j0, hh, ww = check_window(ht, wt, window)
+    if k & 1:
+        j0 = wt - j0 - ww
+    if k & 2:
+        i0 = ht - i0 - hh
+    if k & 4:
+        return wt, ht, (j0, i0, ww, hh)
+    return ht, wt, (i0, j0, hh, ww)
 
 
 # ---- affine views (include/ciaosr_hip.h, "views") ------------------------------------------------------------------------------------
@@ -311,3 +345,23 @@ class EncodedImage:
     @property
     def scene_bytes(self):
         return self.cache.nbytes
+
+
+class EnsembleEncoded:
+    """What `CiaoSR.encode(..., self_ensemble=...)` returns: `members[i]` is the plain `encode` of T_k(lq), k = `ids[i]`, each with an
+    even share of `test_cfg.scene_cache_mb`; `shape` is the ORIGINAL image's.  `render` / `render_many` render every member's
+    transformed window and average them back (hip_ops.dihedral_accum); views, pyramids and prefetch are refused."""
+
+    def __init__(self, ids, members, shape):
+        self.ids = tuple(ids)
+        self.members = list(members)
+        self._shape = tuple(shape)
+        self.alpha = False
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def scene_bytes(self):
+        return sum(m.scene_bytes for m in self.members)

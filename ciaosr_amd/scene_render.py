@@ -19,7 +19,12 @@ def _crop(x, b, origin, t):
     return x[b:b + 1] if origin is None else x[b:b + 1, :, origin[0]:origin[0] + t, origin[1]:origin[1] + t]
 
 
-def encode(r, lq, options=None, max_scale=None):
+def encode(r, lq, options=None, max_scale=None, self_ensemble=None, budget_bytes=None):
+    """`self_ensemble` (None: `test_cfg.self_ensemble`): with members, the ensemble record of `encode_ensemble`.  `budget_bytes`: the
+    scene budget of this encode (None: `test_cfg.scene_cache_mb`, default 4096 MiB)."""
+    ids = r.ensemble_ids(self_ensemble)
+    if ids is not None:
+        return encode_ensemble(r, lq, ids, options, max_scale)
     opt = r.options(options)
     x = r.normalize(lq)
     gen = r.generator
@@ -32,22 +37,85 @@ def encode(r, lq, options=None, max_scale=None):
         patch = _crop(x, *key, t).contiguous()
         return gen.encode(patch, opt, q_plan=q_plan(*patch.shape[-2:], enc.max_scale))
 
-    enc = sc.EncodedImage(x, opt, max_scale, int(r.test_cfg.get('scene_cache_mb', None) or 4096) << 20, build, tile=t)
+    if budget_bytes is None:
+        budget_bytes = _scene_budget(r)
+    enc = sc.EncodedImage(x, opt, max_scale, int(budget_bytes), build, tile=t)
     if not tile and max_scale is not None:
         for b in range(x.shape[0]):
             enc.cache.get((b, None))
     return enc
 
 
-def encode_rgba(r, lq4, options=None, max_scale=None):
+def _scene_budget(r):
+    return int(r.test_cfg.get('scene_cache_mb', None) or 4096) << 20
+
+
+def encode_rgba(r, lq4, options=None, max_scale=None, self_ensemble=None):
     """`encode` of the two-item batch of an RGBA image [1, 4, h, w]: item 0 the colour as stored (not premultiplied), item 1 the alpha
-    plane in all three channels; `enc.alpha` marks it for the renders."""
+    plane in all three channels; `enc.alpha` marks it for the renders.  Not with `self_ensemble` (ValueError)."""
     if not isinstance(lq4, torch.Tensor) or lq4.dim() != 4 or lq4.shape[0] != 1 or lq4.shape[1] != 4:
         shape = tuple(lq4.shape) if isinstance(lq4, torch.Tensor) else type(lq4).__name__
         raise ValueError(f'encode_rgba expects one RGBA image [1, 4, h, w], got {shape}')
-    enc = encode(r, torch.cat([lq4[:, :3], lq4[:, 3:4].expand(-1, 3, -1, -1)], 0), options, max_scale)
+    if r.ensemble_ids(self_ensemble) is not None:
+        raise ValueError('encode_rgba has no self-ensemble: encode the colour image with self_ensemble, or turn the option off')
+    enc = encode(r, torch.cat([lq4[:, :3], lq4[:, 3:4].expand(-1, 3, -1, -1)], 0), options, max_scale, self_ensemble=False)
     enc.alpha = True
     return enc
+
+
+# -- self-ensemble: one plain encode per member, renders averaged back --------------------------------------------------------------------
+def encode_ensemble(r, lq, ids, options=None, max_scale=None):
+    """scene.EnsembleEncoded of the members `ids`: member k is the plain `encode` of T_k(lq) (hip_ops.dihedral), each under an even
+    share of the scene budget."""
+    lq = lq.contiguous().float()
+    budget = _scene_budget(r) // len(ids)
+    members = [encode(r, hip_ops.dihedral(lq, k), options, max_scale, self_ensemble=False, budget_bytes=budget) for k in ids]
+    return sc.EnsembleEncoded(ids, members, lq.shape[-2:])
+
+
+def is_ensemble(enc):
+    return isinstance(enc, sc.EnsembleEncoded)
+
+
+def refuse_ensemble(enc, what):
+    """ValueError, before any device work, for the calls an ensemble record does not serve."""
+    if is_ensemble(enc):
+        raise ValueError(f'{what} is not defined for a self-ensemble encode (members {enc.ids}): render grids with render / render_many, '
+                         f'or encode without self_ensemble')
+
+
+def render_ensemble(r, enc, targets, as_u8=False, many=False):
+    """The `scene.Grid` targets of an ensemble record: member k renders the `scene.dihedral_window` of each target from its own scenes
+    (`many`: all of them in one `render_many` per member, else the single call), and the results are averaged back in member order by
+    `hip_ops.dihedral_accum` into one fp32 accumulator per target -- bitwise the window of `restore(..., self_ensemble=enc.ids)`.
+    Quantised once, after the mean, with `as_u8`.  A `scene.View` is a ValueError."""
+    targets = list(targets)
+    if not targets:
+        raise ValueError('no targets: give a list of scene.Grid')
+    for tg in targets:
+        if isinstance(tg, sc.View):
+            refuse_ensemble(enc, 'a view')
+        if not isinstance(tg, sc.Grid):
+            raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
+    h, w = enc.shape
+    resolved = [tg.resolve(h, w) for tg in targets]                   # render's ValueErrors, before any device work
+    n = len(enc.ids)
+    accs = [None] * len(targets)
+    for i, (k, member) in enumerate(zip(enc.ids, enc.members)):
+        grids = []
+        for ht, wt, win in resolved:
+            ht_k, wt_k, win_k = sc.dihedral_window(k, ht, wt, win)
+            grids.append(sc.Grid(size=(ht_k, wt_k), window=win_k))
+        outs = render_many(r, member, grids) if many else [render_one(r, member, tg) for tg in resolve(r, member, grids)]
+        for j, out in enumerate(outs):
+            if accs[j] is None:
+                accs[j] = torch.empty(*out.shape[:2], *resolved[j][2][2:], dtype=torch.float32, device=out.device)
+            hip_ops.dihedral_accum(accs[j], out, k, first=(i == 0), divisor=float(n) if i == n - 1 else 0.0)
+        del outs
+    if as_u8:
+        from . import metrics_hip
+        return [metrics_hip.tensor2img_u8(acc) for acc in accs]
+    return accs
 
 
 ALPHA_FILL = (0.0, 0.0, 0.0)                  # outside a view the alpha item is 0: transparent
@@ -300,6 +368,8 @@ def scene_walk(r, enc, b, tiles):
 
 
 def render_many(r, enc, targets, as_u8=False):
+    if is_ensemble(enc):
+        return render_ensemble(r, enc, targets, as_u8, many=True)
     x = enc.x
     if not enc.tile or tuple(x.shape[-2:]) == (enc.tile, enc.tile):     # one frame: no schedule to make
         return [render_one(r, enc, tg, as_u8) for tg in resolve(r, enc, targets)]
@@ -316,6 +386,7 @@ def render_many(r, enc, targets, as_u8=False):
 
 
 def prefetch(r, enc, targets):
+    refuse_ensemble(enc, 'prefetch')
     _, walk, _ = plan_many(r, enc, targets)
     cache = enc.cache
     built = 0
@@ -334,6 +405,7 @@ def prefetch(r, enc, targets):
 def plan_pyramid(r, enc, size=None, scale=None):
     """The level sizes of `render_pyramid` and the index of the smallest model level; its ValueErrors.  Pure host work."""
     from . import pyramid
+    refuse_ensemble(enc, 'render_pyramid')
     nb, _, h, w = enc.x.shape
     if nb != (2 if is_alpha(enc) else 1):
         raise ValueError(f'render_pyramid takes one image, got a batch of {nb}')

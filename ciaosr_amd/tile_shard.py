@@ -365,6 +365,12 @@ def sharded_clip_test(img_shape, tile, overlap, sf, tile_fn, blend_fn, finalize_
     return result
 
 
+def refuse_self_ensemble(restorer):
+    """The multi-rank paths shard ONE plain restore: `test_cfg.self_ensemble` is refused, not silently dropped."""
+    if restorer.ensemble_ids() is not None:
+        raise ValueError('test_cfg.self_ensemble is not supported on the multi-rank path (tile_shard): run it in a single process')
+
+
 def clip_test_distributed(restorer, x_norm, rank=None, world=None, group=None, gather_to_all=False, options=None, stats=None,
                           rank0_share=None, loopback=False):
     """Tile-sharded counterpart of CiaoSR.clip_test on the GPUs of one node.
@@ -375,6 +381,7 @@ def clip_test_distributed(restorer, x_norm, rank=None, world=None, group=None, g
     rank = dist.get_rank(group) if rank is None else rank
     world = dist.get_world_size(group) if world is None else world
     cfg = restorer.test_cfg
+    refuse_self_ensemble(restorer)
     sf = cfg.get('scale')
     opt = restorer.options(options)
     if rank0_share is None:
@@ -503,6 +510,7 @@ def predict_query_sharded(restorer, x_norm, coord, cell, rank=None, world=None, 
     """Whole-image (single tile) counterpart of CiaoSR generator(x, coord, cell, test_mode=True) over the GPUs of a node."""
     rank = dist.get_rank(group) if rank is None else rank
     world = dist.get_world_size(group) if world is None else world
+    refuse_self_ensemble(restorer)
     gen = restorer.generator
     opt = restorer.options(options)
 

@@ -722,6 +722,21 @@ int ciaosr_view_blend_f32(float* E, float* Wt, int Q, const int* q_index /*may b
 int ciaosr_view_finalize_f32(const float* E, const float* Wt, float* out_q3, int Q, const float* fill3 /*host*/, const float* mean3 /*host*/,
                              const float* std3 /*host*/, void* stream);
 
+/* ---- self-ensemble: the eight flips and transposes of an image, and the mean through their inverses (an extension, absent from the
+ * reference) ---------------------------------------------------------------------------------------------------------------------------
+ * k in 0..7.  T_k acts on the last two axes of [planes][H][W]: k & 1: flip the columns; then k & 2: flip the rows; then k & 4: transpose
+ * the two axes.  U_k is its inverse: transpose if k & 4, then flip the rows if k & 2, then flip the columns if k & 1.  T_0 is the identity.
+ * Pure data movement, fp32, bitwise repeatable; nothing is allocated or synchronised.  Both entries refuse, before any launch, with
+ * CIAOSR_ERR_BAD_ARG: k outside 0..7, a non-positive size, a null pointer, dst == src / acc == src, a negative or non-finite divisor
+ * (and, CIAOSR_ERR_UNSUPPORTED, an image of more than 2^31 - 1 workgroups: rows x ceil(W / 1024), or 64 x 64 tiles). */
+/* dst = T_k(src): src [planes][H][W], dst [planes][H][W], or [planes][W][H] when k & 4 */
+int ciaosr_dihedral_f32(const float* src, float* dst, int planes, int H, int W, int k, void* stream);
+/* acc = (first ? 0 : acc) + U_k(src), one correctly rounded fp32 add per element; then, with divisor > 0, acc = acc / divisor, one
+ * correctly rounded division.  acc [planes][H][W] in the ORIGINAL orientation, src in member orientation ([planes][W][H] when k & 4).
+ * With `first` acc is never read: the caller needs no memset.  The self-ensemble mean of members k_0 .. k_{n-1} is n calls in member
+ * order, `first` on the first and divisor = n on the last. */
+int ciaosr_dihedral_accum_f32(float* acc, const float* src, int planes, int H, int W, int k, int first, float divisor, void* stream);
+
 /* ---- test data: GT -> LR degradation (configs/001_*.py, val_scale > 4) ---------------------- */
 /* Pillow-exact bicubic resample of an 8-bit RGB image, PIL Image.resize((Wo, Ho), BICUBIC) -- the resize of mmedit's
  * RandomDownSampling (mmcv.imresize, backend 'pillow').  src[y * pitch + 3 x + c] (bytes), the top-left H x W of a possibly wider

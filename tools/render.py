@@ -40,6 +40,10 @@ forces the device path, with or without --gpu-png).  The colour bytes are those 
 the integer luma of the rendered alpha image; outside a view the pixels are transparent (A = 0).  `--niqe` scores the colour part.  A
 file without a transparent pixel is reported in one line and takes the plain path: its outputs are byte for byte those of the run
 without the flag.  Not with --jpeg: JPEG files have no alpha.
+`--self-ensemble` makes every --scale output (with or without --window) the geometric self-ensemble: the image is encoded once per flip /
+transpose (8 members, `CiaoSR.encode(..., self_ensemble=True)`), every member renders its own transformed window and the results are mapped
+back and averaged on the device in fp32 -- the image `CiaoSR.restore(..., self_ensemble=True)` gives, quantised once after the mean.  Eight
+times the work and scene memory of the plain run.  Not with --view, --dzi or --alpha (an argparse error).
 `--png-matches` (only with --gpu-png or --alpha, never with --jpeg) lets the device PNG coder use LZ77 matches for every .png of the run,
 pyramid tiles included: transparent and filled regions then cost next to nothing, and no file gets larger (png_hip `matches=True`).
 """
@@ -84,6 +88,9 @@ def parse_args(argv=None):
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
     p.add_argument('--niqe', default=None, metavar='PARAMS',
                    help='score every --scale / --view output with NIQE on the GPU under the pristine model PARAMS (.npz); writes niqe.json')
+    p.add_argument('--self-ensemble', action='store_true',
+                   help='every --scale output is the mean over the 8 flips and transposes of the input, mapped back (8 encodes; not with '
+                        '--view, --dzi or --alpha; default off)')
     p.add_argument('--max-scale', type=float, default=None,
                    help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM; with --dzi at least its SCALE)')
     p.add_argument('--out', required=True, help='output directory')
@@ -106,6 +113,9 @@ def parse_args(argv=None):
         p.error('--jpeg-optimize belongs to --jpeg')
     if args.jpeg_progressive and args.jpeg is None:
         p.error('--jpeg-progressive belongs to --jpeg')
+    if args.self_ensemble and (args.view or args.dzi is not None or args.alpha):
+        p.error('--self-ensemble applies to --scale and --window outputs: views, pyramids and RGBA encodes have no ensemble, drop '
+                '--view / --dzi / --alpha')
     return args
 
 
@@ -164,7 +174,8 @@ def main(argv=None):
         enc = model.encode_rgba(lq4.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted))
     else:
         lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
-        enc = model.encode(lq, max_scale=args.max_scale or max(wanted))
+        ens = dict(self_ensemble=True) if args.self_ensemble else {}                 # without --self-ensemble encode is called as before
+        enc = model.encode(lq, max_scale=args.max_scale or max(wanted), **ens)
     name = os.path.splitext(os.path.basename(args.image))[0]
     from ciaosr_amd.scene import Grid, View, view_matrix
     form = output_format(args)

@@ -77,6 +77,9 @@ def parse_args(argv=None):
     p.add_argument('--niqe', default=None, metavar='PARAMS',
                    help='test_cfg.niqe_params = PARAMS (the pristine model, niqe_pris_params.npz) and \'NIQE\' appended to test_cfg.metrics: '
                         'the blind score of every output, computed on the GPU (default: not computed)')
+    p.add_argument('--self-ensemble', action='store_true',
+                   help='test_cfg.self_ensemble = True: every output is the mean over the 8 flips and transposes of the input, mapped back '
+                        '(8 restores per image; single process only; default off)')
     return p.parse_args(argv)
 
 
@@ -92,6 +95,8 @@ def apply_overrides(cfg, args):
         cfg.test_cfg['niqe_params'] = args.niqe
         names = list(cfg.test_cfg.get('metrics', None) or [])
         cfg.test_cfg['metrics'] = names if 'NIQE' in names else names + ['NIQE']
+    if args.self_ensemble:
+        cfg.test_cfg['self_ensemble'] = True
     return cfg
 
 
@@ -120,6 +125,8 @@ def main(argv=None):
     if args.checkpoint in (None, 'None'):
         args.checkpoint = cfg.get('test_checkpoint_path')
     distributed = args.launcher != 'none'
+    if distributed and cfg.test_cfg.get('self_ensemble', None):
+        sys.exit('tools/test.py: test_cfg.self_ensemble (--self-ensemble) runs in a single process only, not with --launcher ' + args.launcher)
     rank, world = 0, 1
     if distributed:
         rccl_env_defaults()      # first: ROCr reads HSA_ENABLE_IPC_MODE_LEGACY at the first HIP call (set_device below), RCCL its NCCL_* at init
