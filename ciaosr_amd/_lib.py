@@ -241,6 +241,9 @@ SIGNATURES = {
     'ciaosr_png_rgba_lz_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
     'ciaosr_png_rgba_lz_tiles_workspace_bytes': (_S, [_P, _I, _I]),
     'ciaosr_png_rgba_lz_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    # grey (version 340): one byte per pixel; the PNG entries are in GREY_PNG_SIGNATURES below
+    'ciaosr_tensor2img_grey_u8': (_I, [_P, _I, _I, _P, _S, _P]),
+    'ciaosr_grey_from_bgr_u8': (_I, [_P, _S, _I, _I, _I, _P, _S, _P]),
     'ciaosr_deflate_lz_workspace_bytes': (_S, [_S, _I]),
     'ciaosr_deflate_lz_u8': (_I, [_P, _P, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
     'ciaosr_jpeg_workspace_bytes': (_S, [_I, _I, _I, _I]),
@@ -265,6 +268,24 @@ SIGNATURES = {
     'ciaosr_jpeg_prog_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
 }
 
+# The grey PNG entry points (include/ciaosr_hip_png_grey.h, which ciaosr_hip.h includes): the arguments of their rgba namesakes.  A table
+# of its own, as the header is: the PNG size exports of SIGNATURES are exactly those that tests/golden/png_sizes.json records;
+# tests/test_grey_host.py holds this table to its header and the sizes to their formulae.  `load` binds both tables.
+GREY_PNG_SIGNATURES = {
+    'ciaosr_png_grey_rows_per_band': (_I, [_I, _I]),
+    'ciaosr_png_grey_filter_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'ciaosr_png_grey_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_grey_capacity_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_grey_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_grey_tiles_workspace_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_grey_tiles_capacity_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_grey_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_grey_lz_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_png_grey_lz_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_png_grey_lz_tiles_workspace_bytes': (_S, [_P, _I, _I]),
+    'ciaosr_png_grey_lz_encode_tiles_u8': (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P]),
+}
+
 # ctypes mirror of every ABI struct, by the header's typedef name (layout checked against ciaosr_sizeof at load time)
 STRUCTS = {'ciaosr_options_t': OptionsT, 'ciaosr_csattn_weights_t': CsAttnWeightsT, 'ciaosr_mlp_t': MlpT,
            'ciaosr_head_weights_t': HeadWeightsT, 'ciaosr_head_scene_t': HeadSceneT, 'ciaosr_conv_t': ConvT, 'ciaosr_rdn_weights_t': RdnWeightsT,
@@ -285,7 +306,7 @@ def load():
             f'(python -c "import __graft_entry__ as g; g.build()" or make -C ciaosr_amd/csrc). '
             f'There is no CPU fallback for the product path.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GREY_PNG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -699,6 +699,7 @@ extern "C" size_t ciaosr_jpeg_prog_capacity_bytes(int H, int W, int subsampling)
 extern "C" int ciaosr_jpeg_prog_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                                 int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                                 void* result, void* workspace, size_t workspace_bytes, void* stream) {
+    if (subsampling == CIAOSR_JPEG_GREY) return CIAOSR_ERR_UNSUPPORTED;      // no one-component progressive files
     CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
     CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);

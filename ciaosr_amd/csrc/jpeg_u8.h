@@ -32,7 +32,7 @@ struct ChunkT {
 };
 
 struct Params {
-    const unsigned char* src;     // [H][pitch], 3 bytes per pixel
+    const unsigned char* src;     // [H][pitch], 3 bytes per pixel (grey: 1)
     size_t pitch;
     int bgr, sub420, nt, nc;
     const Consts* consts;
@@ -57,6 +57,7 @@ struct Params {
     u32* tile_hist;               // [nt][4][256]: symbol counts per table, in the file's order of tables (kTables)
     u32* tile_huff;               // [nt][2][kHuff]: the tile's code tables in the layout of Consts::huff
     unsigned char* dht;          // [nt][4][kDhtRecord]: the tables as DHT segments hold them
+    int grey;                     // one component (CIAOSR_JPEG_GREY): src holds one byte per pixel, one block per MCU, table class 0
 };
 
 // jpeg_u8.hip: the constants of a quality, and its kernels that every kind of file runs.  To jpeg_scan, jpeg_zero, jpeg_ffcount,
@@ -67,9 +68,14 @@ int launch_shared(Shared which, int grid, const Params& p, hipStream_t s);
 constexpr int kZeroGroups = 1024;
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
-static inline int default_mcus(int sub420) { return sub420 ? 128 : 256; }     // 768 blocks per chunk
-// the ABI's subsampling code -> 0 (4:4:4), 1 (4:2:0), -1 (unknown)
-static inline int sub_of(int subsampling) { return subsampling == CIAOSR_JPEG_444 ? 0 : (subsampling == CIAOSR_JPEG_420 ? 1 : -1); }
+// the scan's layout as the plans name it (`sub420` where only the first two can occur)
+enum { kMode444 = 0, kMode420 = 1, kModeGrey = 2 };
+static inline int default_mcus(int mode) { return mode == kModeGrey ? 768 : (mode ? 128 : 256); }     // 768 blocks per chunk
+// the ABI's subsampling code -> kMode444, kMode420, kModeGrey, -1 (unknown)
+static inline int sub_of(int subsampling) {
+    return subsampling == CIAOSR_JPEG_444 ? kMode444 : (subsampling == CIAOSR_JPEG_420 ? kMode420 : (subsampling == CIAOSR_JPEG_GREY ? kModeGrey : -1));
+}
+static inline int blocks_per_mcu(int mode) { return mode == kModeGrey ? 1 : (mode ? 6 : 3); }
 
 // ---- device helpers --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
@@ -142,11 +148,13 @@ __device__ __forceinline__ void wg_prefix_u64(const u64* in, u64* out, int n, u6
     __syncthreads();
 }
 
+__device__ __forceinline__ int bpm_of(const Params& p) { return p.grey ? 1 : (p.sub420 ? 6 : 3); }      // blocks per MCU
+
 __device__ __forceinline__ int bit_length(int a) { return 32 - __clz(a); }       // a >= 0; 0 -> 0
 
 // the quantised DC that block j of the chunk's tile predicts from: the previous block of its component in scan order, 0 at the start
 __device__ __forceinline__ int dc_pred(const Params& p, const TileT& t, u64 blk) {
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const u64 rel = blk - t.block0;
     const int k = (int)(rel % bpm);
     const u64 mcu = rel / bpm;

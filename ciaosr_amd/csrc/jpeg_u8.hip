@@ -156,10 +156,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_coef_kernel(Params p) {
     if (tid < 64) zig[tid] = p.consts->zig_of_nat[tid];
     const ChunkT ch = p.chunks[blockIdx.x];
     const TileT t = p.tiles[ch.tile];
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
     const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
-    const unsigned char* org = p.src + (size_t)t.y0 * p.pitch + 3 * (size_t)t.x0;
+    const unsigned char* org = p.src + (size_t)t.y0 * p.pitch + (p.grey ? 1 : 3) * (size_t)t.x0;
     const int nby = (t.h + 7) >> 3, nbx = (t.w + 7) >> 3;
     __syncthreads();
     for (int j0 = 0; j0 < nblk; j0 += kBlocksPerStep) {
@@ -171,7 +171,11 @@ __global__ __launch_bounds__(kThreads) void jpeg_coef_kernel(Params p) {
         if (active) {
             const int mcu = ch.mcu0 + j / bpm, k = j % bpm;
             const int my = mcu / t.mx, mxi = mcu % t.mx;
-            if (!p.sub420 || k < 4) {                      // a full-resolution block
+            if (p.grey) {                                   // one component: the samples are the bytes
+                const unsigned char* row = org + (size_t)min(my * 8 + l8, t.h - 1) * p.pitch;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) d[i] = (int)row[min(mxi * 8 + i, t.w - 1)] - 128;
+            } else if (!p.sub420 || k < 4) {                // a full-resolution block
                 int by = my, bx = mxi;
                 comp = k;
                 if (p.sub420) {
@@ -314,7 +318,7 @@ struct Packer {
 };
 
 __device__ __forceinline__ int table_of(const Params& p, const TileT& t, u64 blk) {
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const int k = (int)((blk - t.block0) % bpm);
     return p.sub420 ? (k < 4 ? 0 : 1) : (k == 0 ? 0 : 1);
 }
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_count_kernel(Params p) {
     const u32* huff = p.tile_huff ? p.tile_huff + (size_t)ch.tile * (2 * kHuff) : &p.consts->huff[0][0];
     for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = huff[i];
     const TileT t = p.tiles[ch.tile];
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
     const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
     __syncthreads();
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_hist_kernel(Params p) {
     for (int i = tid; i < kTables * 256; i += kThreads) (&hist[0][0])[i] = 0u;
     const ChunkT ch = p.chunks[blockIdx.x];
     const TileT t = p.tiles[ch.tile];
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
     const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
     __syncthreads();
@@ -458,7 +462,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(Params p) {
     const u32* huff = p.tile_huff ? p.tile_huff + (size_t)ch.tile * (2 * kHuff) : &p.consts->huff[0][0];
     for (int i = tid; i < 2 * kHuff; i += kThreads) (&tab[0][0])[i] = huff[i];
     const TileT t = p.tiles[ch.tile];
-    const int bpm = p.sub420 ? 6 : 3;
+    const int bpm = bpm_of(p);
     const int nblk = (ch.mcu1 - ch.mcu0) * bpm;
     const u64 base = (u64)t.block0 + (u64)ch.mcu0 * bpm;
     u64 pos = p.chunk_bitoff[blockIdx.x];
@@ -551,14 +555,14 @@ struct Plan {
     size_t o_tiles, o_chunks, table_bytes;
 };
 // `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
-static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcus_arg, int H, int W, std::vector<unsigned char>* table,
+static Plan plan(const int* rects, int n_tiles, int quality, int mode, int mcus_arg, int H, int W, std::vector<unsigned char>* table,
                  bool opt = false) {
     Plan t{};
     t.opt = opt;
     t.rc = CIAOSR_ERR_BAD_ARG;
-    if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || (sub420 != 0 && sub420 != 1)) return t;
-    const int per = mcus_arg > 0 ? mcus_arg : default_mcus(sub420);
-    const int bpm = sub420 ? 6 : 3, side = sub420 ? 16 : 8;
+    if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || mode < kMode444 || mode > kModeGrey) return t;
+    const int per = mcus_arg > 0 ? mcus_arg : default_mcus(mode);
+    const int bpm = blocks_per_mcu(mode), side = mode == kMode420 ? 16 : 8;
     u64 nc = 0, blocks = 0, opt_bytes = 0;
     bool too_many = false;                                  // optimised: a crop at the frequency limit
     for (int k = 0; k < n_tiles; ++k) {
@@ -663,12 +667,12 @@ int launch_shared(Shared which, int grid, const Params& p, hipStream_t s) {
 }
 
 // every check that the host can make comes before the first launch
-static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int sub420,
+static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int mode,
                   int mcus, unsigned char* out, size_t out_capacity, u64* tile_offs, u64* total, void* workspace, size_t workspace_bytes,
                   hipStream_t s, unsigned char* dht = nullptr /* optimised tables: [n_tiles][4][kDhtRecord] */) {
     std::vector<unsigned char> table;
     const bool opt = dht != nullptr;
-    const Plan t = plan(rects, n_tiles, quality, sub420, mcus, H, W, &table, opt);
+    const Plan t = plan(rects, n_tiles, quality, mode, mcus, H, W, &table, opt);
     CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image; quality; subsampling
     if (t.rc != CIAOSR_OK) return t.rc;
     if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
@@ -680,7 +684,8 @@ static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr,
     p.src = src;
     p.pitch = pitch;
     p.bgr = bgr;
-    p.sub420 = sub420;
+    p.sub420 = mode == kMode420;
+    p.grey = mode == kModeGrey;
     p.nt = t.nt;
     p.nc = t.nc;
     p.consts = reinterpret_cast<const Consts*>(w.table);
@@ -722,6 +727,9 @@ static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr,
     return launch("jpeg_stuff", jpeg_stuff_kernel, t.nc, p, s);
 }
 
+// bytes per pixel of the source that the ABI's subsampling code names
+static inline size_t source_bytes(int subsampling) { return subsampling == CIAOSR_JPEG_GREY ? 1 : 3; }
+
 }  // namespace jpeg
 }  // namespace ciaosr
 
@@ -751,9 +759,9 @@ extern "C" size_t ciaosr_jpeg_capacity_bytes(int H, int W, int subsampling) {
 extern "C" int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                            int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                            unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
     return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, tile_offs, nullptr,
                   workspace, workspace_bytes, (hipStream_t)stream);
@@ -762,9 +770,9 @@ extern "C" int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitc
 extern "C" int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
                                      int mcus_per_chunk, unsigned char* out, size_t out_capacity, unsigned long long* total_bytes,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
     const int rect[4] = {0, 0, H, W};
     return encode(src, pitch, H, W, bgr, rect, 1, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, nullptr, total_bytes, workspace,
@@ -799,9 +807,9 @@ extern "C" size_t ciaosr_jpeg_opt_capacity_bytes(int H, int W, int subsampling) 
 extern "C" int ciaosr_jpeg_opt_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                                int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                                void* result, void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
+    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
     CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
+    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
     CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(result) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
     u64* offs = static_cast<u64*>(result);
     return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, offs, nullptr, workspace,

@@ -119,6 +119,93 @@ __global__ __launch_bounds__(kQThreads) void pack_bgra_u8_kernel(PackAP p) {
     store_bgra(p.dst + (size_t)y * p.pitch, x, (unsigned int)c[0] | (unsigned int)c[1] << 8 | (unsigned int)c[2] << 16 | a << 24, p.vec);
 }
 
+// Grey: ONE byte per pixel, the integer luma of the pixel's three bytes -- Pillow's convert('L') and libjpeg's Y (ycc(.., 0) in
+// jpeg_u8.hip).  The weights sum to 2^16, so a neutral v, v, v is v.  Not alpha_of_bgr: the two differ by 1 on 39 135 triples.
+__device__ __forceinline__ unsigned int grey_of_bgr(unsigned int b, unsigned int g, unsigned int r) {
+    return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16;
+}
+
+constexpr int kGreyPer = 4;       // consecutive output bytes per lane: one 32-bit store where dst and its pitch allow
+
+// bytes [x, x + n) of a row, n <= kGreyPer, packed little-endian in `word`
+__device__ __forceinline__ void store_grey(unsigned char* out, int x, int n, unsigned int word, int vec) {
+    if (vec && n == kGreyPer) {
+        *reinterpret_cast<unsigned int*>(out + x) = word;
+    } else {
+        for (int k = 0; k < n; ++k) out[x + k] = (unsigned char)(word >> (8 * k));
+    }
+}
+
+struct QuantGP {
+    const float* src;             // [3][H][W] RGB
+    unsigned char* dst;           // [H][pitch], one byte per pixel
+    size_t pitch;
+    int H, W;
+    int vec_in;                   // float4 loads (W % 4 == 0, planes 16-byte aligned)
+    int vec_out;                  // 32-bit stores (dst and pitch 4-byte aligned)
+};
+
+__global__ __launch_bounds__(kQThreads) void tensor2img_grey_u8_kernel(QuantGP p) {
+    const int y = blockIdx.y, x = kGreyPer * (blockIdx.x * kQThreads + threadIdx.x);
+    if (x >= p.W) return;
+    const int n = min(kGreyPer, p.W - x);
+    const size_t plane = (size_t)p.H * p.W;
+    const float* row = p.src + (size_t)y * p.W + x;
+    float c[3][kGreyPer];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        if (p.vec_in) {
+            const float4 v = *reinterpret_cast<const float4*>(row + ch * plane);
+            c[ch][0] = v.x, c[ch][1] = v.y, c[ch][2] = v.z, c[ch][3] = v.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < kGreyPer; ++k) c[ch][k] = k < n ? row[ch * plane + k] : 0.0f;
+        }
+    }
+    unsigned int word = 0u;
+#pragma unroll
+    for (int k = 0; k < kGreyPer; ++k) word |= grey_of_bgr(quant8(c[2][k]), quant8(c[1][k]), quant8(c[0][k])) << (8 * k);
+    store_grey(p.dst + (size_t)y * p.pitch, x, n, word, p.vec_out);
+}
+
+struct GreyP {
+    const unsigned char* src;     // [H][pitch_src], 3 bytes per pixel
+    size_t pitch_src;
+    int bgr;                      // the bytes of a pixel are B G R, else R G B
+    unsigned char* dst;           // [H][pitch]
+    size_t pitch;
+    int H, W;
+    int vec_in;                   // three 32-bit loads per lane (src and its pitch 4-byte aligned)
+    int vec_out;
+};
+
+__global__ __launch_bounds__(kQThreads) void grey_from_bgr_u8_kernel(GreyP p) {
+    const int y = blockIdx.y, x = kGreyPer * (blockIdx.x * kQThreads + threadIdx.x);
+    if (x >= p.W) return;
+    const int n = min(kGreyPer, p.W - x);
+    const unsigned char* q = p.src + (size_t)y * p.pitch_src + 3 * (size_t)x;
+    unsigned int b12[3 * kGreyPer];
+    if (p.vec_in && n == kGreyPer) {                      // 12 bytes from a 4-byte aligned address
+        const unsigned int* w = reinterpret_cast<const unsigned int*>(q);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const unsigned int v = w[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) b12[4 * i + k] = v >> (8 * k) & 255u;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3 * kGreyPer; ++i) b12[i] = i < 3 * n ? q[i] : 0u;
+    }
+    unsigned int word = 0u;
+#pragma unroll
+    for (int k = 0; k < kGreyPer; ++k) {
+        const unsigned int c0 = b12[3 * k], g = b12[3 * k + 1], c2 = b12[3 * k + 2];
+        word |= grey_of_bgr(p.bgr ? c0 : c2, g, p.bgr ? c2 : c0) << (8 * k);
+    }
+    store_grey(p.dst + (size_t)y * p.pitch, x, n, word, p.vec_out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct MetricsP {
     const unsigned char* a;
@@ -351,6 +438,27 @@ extern "C" int ciaosr_pack_bgra_u8(const unsigned char* bgr, size_t pitch, const
     ProfScope prof("pack_bgra_u8", s);
     hipLaunchKernelGGL(pack_bgra_u8_kernel, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
     return launch_status("pack_bgra_u8");
+}
+
+extern "C" int ciaosr_tensor2img_grey_u8(const float* src_chw, int H, int W, unsigned char* dst, size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(src_chw && dst && H > 0 && W > 0 && dst_pitch >= (size_t)W);
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    QuantGP p{src_chw, dst, dst_pitch, H, W, (W % 4 == 0) && aligned16(src_chw), bgra_vec(dst, dst_pitch)};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("tensor2img_grey_u8", s);
+    hipLaunchKernelGGL(tensor2img_grey_u8_kernel, dim3(ceil_div(ceil_div(W, kGreyPer), kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("tensor2img_grey_u8");
+}
+
+extern "C" int ciaosr_grey_from_bgr_u8(const unsigned char* bgr, size_t pitch, int bgr_flag, int H, int W, unsigned char* dst,
+                                       size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(bgr && dst && H > 0 && W > 0 && pitch >= 3 * (size_t)W && dst_pitch >= (size_t)W && (bgr_flag == 0 || bgr_flag == 1));
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    GreyP p{bgr, pitch, bgr_flag, dst, dst_pitch, H, W, bgra_vec(bgr, pitch), bgra_vec(dst, dst_pitch)};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("grey_from_bgr_u8", s);
+    hipLaunchKernelGGL(grey_from_bgr_u8_kernel, dim3(ceil_div(ceil_div(W, kGreyPer), kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("grey_from_bgr_u8");
 }
 
 extern "C" size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int convert_to_y) {

@@ -7,7 +7,8 @@
 // filtered bytes have the smallest sum of min(b, 256 - b) -- ties to the lowest number -- and writes the filter byte plus 3 W filtered
 // bytes in RGB order.  The same pass counts the band's 257-bin symbol histogram (256 literals + one end-of-block) in LDS and the band's
 // Adler-32 partial sums.  filter_band is a template over the bytes per pixel: 3 (colour type 2) and 4 (colour type 6, the ciaosr_png_rgba_*
-// entry points: rows of 1 + 4 W bytes in R G B A order, the left predecessor four bytes back, a pixel read as ONE aligned 32-bit word).
+// entry points: rows of 1 + 4 W bytes in R G B A order, the left predecessor four bytes back, a pixel read as ONE aligned 32-bit word)
+// and 1 (colour type 0, the ciaosr_png_grey_* entry points: rows of 1 + W bytes, the left predecessor one byte back, any alignment).
 //
 // Stage 2, four launches over a byte buffer split into bands:
 //   deflate_hist_kernel   the 257-bin histogram of every band (skipped when stage 1 made it);
@@ -98,7 +99,7 @@ struct TileBand {
 };
 
 struct FilterP {
-    const unsigned char* src;     // [H][pitch], 3 or 4 bytes per pixel (the kernel's template argument)
+    const unsigned char* src;     // [H][pitch], 1, 3 or 4 bytes per pixel (the kernel's template argument)
     size_t pitch;
     int H, W, bgr, R;
     unsigned char* dst;           // [H][1 + bytes per pixel * W]
@@ -126,7 +127,12 @@ template <int BPP>
 __device__ __forceinline__ void load_pixel(const unsigned char* cur, const unsigned char* up, int x, int bgr, int v[BPP], int a[BPP],
                                            int b[BPP], int c[BPP]) {
     const int s0 = bgr ? 2 : 0, s2 = bgr ? 0 : 2;
-    if constexpr (BPP == 4) {
+    if constexpr (BPP == 1) {                                 // grey: no channel order, no alignment rule
+        v[0] = cur[x];
+        a[0] = x > 0 ? cur[x - 1] : 0;
+        b[0] = up ? up[x] : 0;
+        c[0] = (up && x > 0) ? up[x - 1] : 0;
+    } else if constexpr (BPP == 4) {
         const u32* q = reinterpret_cast<const u32*>(cur) + x;
         const u32* qu = reinterpret_cast<const u32*>(up) + x;
         const u32 pv = q[0], pa = x > 0 ? q[-1] : 0u;
@@ -1419,6 +1425,7 @@ static int run_filter(int bpp, const unsigned char* src, size_t pitch, int H, in
     f.hist = hist;
     f.adler = adler;
     const int nb = ceil_div(H, R);
+    if (bpp == 1) return launch("png_grey_filter_u8", png_filter_kernel<1>, nb, kThreads, s, f);
     return bpp == 4 ? launch("png_rgba_filter_u8", png_filter_kernel<4>, nb, kThreads, s, f)
                     : launch("png_filter_u8", png_filter_kernel<3>, nb, kThreads, s, f);
 }
@@ -1627,8 +1634,9 @@ static int encode_tiles_entry(int bpp, bool lz, const unsigned char* src, size_t
     f.dst = w.filtered;
     f.hist = w.hist;
     f.adler = w.adler;
-    int rc = bpp == 4 ? launch("png_rgba_filter_tiles_u8", png_filter_tiles_kernel<4>, t.nb, kThreads, s, f)
-                      : launch("png_filter_tiles_u8", png_filter_tiles_kernel<3>, t.nb, kThreads, s, f);
+    int rc = bpp == 1   ? launch("png_grey_filter_tiles_u8", png_filter_tiles_kernel<1>, t.nb, kThreads, s, f)
+             : bpp == 4 ? launch("png_rgba_filter_tiles_u8", png_filter_tiles_kernel<4>, t.nb, kThreads, s, f)
+                        : launch("png_filter_tiles_u8", png_filter_tiles_kernel<3>, t.nb, kThreads, s, f);
     if (rc) return rc;
     DeflateP p = deflate_params(w.filtered, listed_bands(offs, t.nb), w);
     p.out = out;
@@ -1796,5 +1804,48 @@ extern "C" int ciaosr_png_rgba_lz_encode_tiles_u8(const unsigned char* src, size
                                                   int n_tiles, int rows_per_band_arg, unsigned char* out, size_t out_capacity,
                                                   unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
     return encode_tiles_entry(4, true, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
+}
+
+// one byte per pixel (colour type 0): the same entries on rows of 1 + W bytes; bgr is not read
+extern "C" int ciaosr_png_grey_rows_per_band(int W, int rows_per_band_arg) { return rows_per_band_entry(1, W, rows_per_band_arg); }
+
+extern "C" int ciaosr_png_grey_filter_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                         unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {
+    return filter_entry(1, src, pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler, stream);
+}
+extern "C" size_t ciaosr_png_grey_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(1, H, W, rows_per_band_arg, false); }
+extern "C" size_t ciaosr_png_grey_lz_workspace_bytes(int H, int W, int rows_per_band_arg) { return workspace_entry(1, H, W, rows_per_band_arg, true); }
+extern "C" size_t ciaosr_png_grey_capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(1, H, W, rows_per_band_arg); }
+
+extern "C" int ciaosr_png_grey_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                         unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    return encode_entry(1, false, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+}
+extern "C" int ciaosr_png_grey_lz_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,
+                                            unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return encode_entry(1, true, src, pitch, H, W, bgr, rows_per_band_arg, out, out_capacity, total_bytes, workspace, workspace_bytes, stream);
+}
+extern "C" size_t ciaosr_png_grey_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(1, rects, n_tiles, rows_per_band_arg, false);
+}
+extern "C" size_t ciaosr_png_grey_lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_workspace_entry(1, rects, n_tiles, rows_per_band_arg, true);
+}
+extern "C" size_t ciaosr_png_grey_tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {
+    return tiles_capacity_entry(1, rects, n_tiles, rows_per_band_arg);
+}
+extern "C" int ciaosr_png_grey_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
+                                               int rows_per_band_arg, unsigned char* out, size_t out_capacity,
+                                               unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_tiles_entry(1, false, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
+                              workspace_bytes, stream);
+}
+extern "C" int ciaosr_png_grey_lz_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects,
+                                                  int n_tiles, int rows_per_band_arg, unsigned char* out, size_t out_capacity,
+                                                  unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
+    return encode_tiles_entry(1, true, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
                               workspace_bytes, stream);
 }

@@ -22,6 +22,17 @@ def imread_rgba01(path):
     return torch.from_numpy(img.astype(np.float32) / 255.0).permute(2, 0, 1).contiguous(), opaque
 
 
+def imread_grey01(path):
+    """-> (float32 tensor [1,H,W] in [0,1], was_grey): the file through Pillow's convert('L') -- L, LA, palette and colour files alike.
+    `was_grey`: the file's convert('RGB') has three equal channels, so nothing but the grey values was there to lose."""
+    from PIL import Image
+    with Image.open(path) as f:
+        rgb = np.asarray(f.convert('RGB'), dtype=np.uint8)
+        grey = np.asarray(f.convert('L'), dtype=np.uint8)
+    was_grey = bool((rgb[:, :, 0] == rgb[:, :, 1]).all() and (rgb[:, :, 1] == rgb[:, :, 2]).all())
+    return torch.from_numpy(grey.astype(np.float32) / 255.0).unsqueeze(0).contiguous(), was_grey
+
+
 def imread_u8(path):
     """-> HxWx3 uint8 RGB array: LoadImageFromFile(flag='color', channel_order='rgb') before any conversion."""
     from PIL import Image

@@ -16,6 +16,10 @@ synchronises twice, and `header(..., tables=)` writes them into the file's four 
 scans of libjpeg's progressive script, every scan with a table made from its own symbols -- Pillow writes the same bytes with and
 without `optimize=True`, so `optimize` does not matter then.  The device returns the ten scans of every crop and their ten tables in
 the same two copies; `assemble_progressive` writes the SOF2 header and the DHT and SOS headers between them.
+
+A 2-D uint8 [H, W] image is a GREY image: the file is byte for byte `Image.fromarray(grey, 'L').save(format='JPEG', quality=q[,
+optimize=True])` -- one component, one DQT, two DHT (`header(..., grey=True)`); the device codes one block per MCU with the luma tables
+(CIAOSR_JPEG_GREY).  `subsampling` stays '444' (Pillow's '420' file of a grey image has other bytes) and there is no progressive form.
 """
 import ctypes as C
 import os
@@ -26,9 +30,10 @@ import torch
 from . import _lib, hip_ops
 from ._lib import CiaoSRHipError
 from .metrics_hip import _check_image
-from .png_hip import MAX_SIDE, ORDERS, check_rects
+from .png_hip import MAX_SIDE, ORDERS, _check_grey, _pitch, check_rects
 
 SUBSAMPLINGS = {'444': 0, '420': 2}        # CIAOSR_JPEG_444 / CIAOSR_JPEG_420: Pillow's `subsampling=` numbers
+GREY = 4                                    # CIAOSR_JPEG_GREY: one component, what a 2-D image is coded as
 EOI = b'\xff\xd9'
 
 # Annex K base quantisation tables, natural (row-major) order
@@ -100,19 +105,21 @@ def check_progressive(progressive):
     return progressive
 
 
-def scan_block_count(h, w, subsampling):
-    """Blocks of the scan of an h x w image: all components, the dummy blocks of 4:2:0 included."""
+def scan_block_count(h, w, subsampling, grey=False):
+    """Blocks of the scan of an h x w image: all components, the dummy blocks of 4:2:0 included; `grey`: the one component's."""
+    if grey:
+        return -(-h // 8) * -(-w // 8)
     if subsampling == '420':
         return 6 * -(-h // 16) * -(-w // 16)
     return 3 * -(-h // 8) * -(-w // 8)
 
 
-def check_frequency_limit(h, w, subsampling):
+def check_frequency_limit(h, w, subsampling, grey=False):
     """Optimised coding counts symbols in 32 bits and follows libjpeg only below its sentinel frequency: a crop whose scan could hold
     FREQUENCY_LIMIT symbols (64 per block) is a ValueError."""
-    blocks = scan_block_count(h, w, subsampling)
+    blocks = scan_block_count(h, w, subsampling, grey)
     if 64 * blocks >= FREQUENCY_LIMIT:
-        raise ValueError(f'optimize=True: {h} x {w} in {subsampling} has {blocks} blocks; 64 x blocks must stay below {FREQUENCY_LIMIT}')
+        raise ValueError(f'optimize=True: {h} x {w} in {"grey" if grey else subsampling} has {blocks} blocks; 64 x blocks must stay below {FREQUENCY_LIMIT}')
     return blocks
 
 
@@ -122,11 +129,13 @@ def quant_tables(quality):
     return tuple(tuple(min(max((b * s + 50) // 100, 1), 255) for b in base) for base in (BASE_LUMA, BASE_CHROMA))
 
 
-def _frame(h, w, quality, subsampling, sof):
-    """SOI, APP0, the two DQT segments and the frame header under the marker `sof`."""
+def _frame(h, w, quality, subsampling, sof, grey=False):
+    """SOI, APP0, the two DQT segments and the frame header under the marker `sof`; `grey`: the luma DQT and the one-component frame."""
     parts = [b'\xff\xd8', b'\xff\xe0', struct.pack('>H5sBBBHHBB', 16, b'JFIF\0', 1, 1, 0, 1, 1, 0, 0)]
-    for k, q in enumerate(quant_tables(quality)):
+    for k, q in enumerate(quant_tables(quality)[:1 if grey else 2]):
         parts += [b'\xff\xdb', struct.pack('>HB', 67, k), bytes(q[i] for i in ZIGZAG)]
+    if grey:
+        return b''.join(parts + [sof, struct.pack('>HBHHB', 11, 8, h, w, 1), bytes((1, 0x11, 0))])
     parts += [sof, struct.pack('>HBHHB', 17, 8, h, w, 3), bytes((1, 0x22 if subsampling == '420' else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))]
     return b''.join(parts)
 
@@ -170,34 +179,68 @@ def assemble_progressive(h, w, quality, subsampling, scans, tables):
     return b''.join(parts) + EOI
 
 
-def header(h, w, quality, subsampling, tables=None):
+def header(h, w, quality, subsampling='444', tables=None, grey=False):
     """The file from SOI up to and including the SOS header, as Pillow writes it for an h x w RGB image.  `tables`: four (counts,
     symbols) pairs in the file's order (DC luma, AC luma, DC chroma, AC chroma) for the DHT segments of an optimised file -- 16 counts
-    per code length 1..16 and exactly sum(counts) symbols each; None: the Annex K tables."""
+    per code length 1..16 and exactly sum(counts) symbols each; None: the Annex K tables.
+    `grey=True`: as Pillow writes it for a mode-L image -- one DQT, SOF0 with the component (1, 0x11, 0), the two luma DHT segments
+    (of `tables`, an optimised call's four pairs or the first two, only the first two are read) and the one-component SOS."""
     quality, _ = check_params(quality, subsampling)
+    if not isinstance(grey, bool):
+        raise ValueError(f'grey is True or False, got {grey!r}')
+    if grey and subsampling != '444':
+        raise ValueError(f"a grey file has no subsampling: leave it at '444', got {subsampling!r}")
     huffman = HUFFMAN
     if tables is not None:
         tables = [(tuple(int(c) for c in counts), tuple(int(v) for v in symbols)) for counts, symbols in tables]
+        if grey:
+            if len(tables) not in (2, 4):
+                raise ValueError('tables: two or four (16 counts, sum(counts) symbols) pairs')
+            tables = tables[:2] + list(t[1:] for t in HUFFMAN[2:])
         if len(tables) != 4 or any(len(c) != 16 or len(v) != sum(c) or not 1 <= len(v) <= 256 for c, v in tables):
             raise ValueError('tables: four (16 counts, sum(counts) symbols) pairs')
         huffman = tuple((tc_th, c, v) for tc_th, (c, v) in zip(TABLE_IDS, tables))
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
-    parts = [_frame(h, w, quality, subsampling, b'\xff\xc0')]
-    for tc_th, bits, vals in huffman:
+    parts = [_frame(h, w, quality, subsampling, b'\xff\xc0', grey)]
+    for tc_th, bits, vals in huffman[:2 if grey else 4]:
         parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), tc_th), bytes(bits), bytes(vals)]
-    parts += [b'\xff\xda', struct.pack('>HB', 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3f, 0))]
+    if grey:
+        parts += [b'\xff\xda', struct.pack('>HB', 8, 1), bytes((1, 0x00, 0, 0x3f, 0))]
+    else:
+        parts += [b'\xff\xda', struct.pack('>HB', 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3f, 0))]
     return b''.join(parts)
+
+
+def is_grey(img):
+    """A 2-D uint8 tensor: a grey image, coded as a one-component file."""
+    return isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 2
+
+
+def check_not_progressive_grey(img, progressive):
+    """There is no one-component progressive file: ValueError before any device work."""
+    if progressive and is_grey(img):
+        raise ValueError('progressive=True: a grey [H, W] image has no progressive form here')
 
 
 def _check(img, quality, subsampling, order, mcus_per_chunk, what):
     """The argument checks of every entry point, before any device work -> (h, w, quality, subsampling code, mcus_per_chunk)."""
     quality, sub = check_params(quality, subsampling)
-    if order not in ORDERS:
+    grey = is_grey(img)
+    if grey:
+        if subsampling != '444':
+            raise ValueError(f"a grey [H, W] image has no subsampling (Pillow's {subsampling!r} file of it holds other bytes): leave it at '444'")
+        if order not in ('bgr', 'grey'):
+            raise ValueError(f"order of a grey [H, W] image stays at its default or is 'grey', got {order!r}")
+        sub = GREY
+    elif order not in ORDERS:
         raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
     if int(mcus_per_chunk) != mcus_per_chunk or mcus_per_chunk < 0:
         raise ValueError(f'mcus_per_chunk={mcus_per_chunk!r}')
-    _check_image(img)
+    if grey:
+        _check_grey(img, order)
+    else:
+        _check_image(img)
     h, w = img.shape[0], img.shape[1]
     if h < 1 or w < 1 or h > MAX_SIDE or w > MAX_SIDE:
         raise CiaoSRHipError(f'{what}: {h}x{w} is outside 1..{MAX_SIDE} per side')
@@ -239,13 +282,13 @@ def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', 
     `progressive=True` (whatever `optimize` is): ciaosr_jpeg_prog_encode_tiles_u8 -> (scans, result int64 [10 n + 1 + 340 n]): the
     offsets of the crops' ten scans each, then their ten DHT records each (`split_progressive_result`)."""
     check_optimize(optimize)
-    check_progressive(progressive)
+    check_not_progressive_grey(img, check_progressive(progressive))
     h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
     rects = check_rects(rects, h, w)
     n = len(rects)
     if optimize or progressive:
         for r in rects:
-            check_frequency_limit(r[2], r[3], subsampling)
+            check_frequency_limit(r[2], r[3], subsampling, sub == GREY)
     dev = img.device
     lib = _lib.load()
     host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
@@ -259,7 +302,7 @@ def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', 
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
     words = getattr(lib, f'ciaosr_jpeg_{opt}result_bytes')(n) // 8 if opt else n + 1
     offs = torch.empty(words, dtype=torch.int64, device=dev)
-    _lib.call(f'ciaosr_jpeg_{opt}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], host_rects, n, quality, sub,
+    _lib.call(f'ciaosr_jpeg_{opt}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), host_rects, n, quality, sub,
               mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
               C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     return out, offs
@@ -293,7 +336,8 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
     Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes.
     `progressive=True` -> (the file's ten scans, its ten tables)."""
     check_optimize(optimize)
-    if check_progressive(progressive):
+    check_not_progressive_grey(img, check_progressive(progressive))
+    if progressive:
         h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
         scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
         return scans[0], tables[0]
@@ -311,7 +355,7 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
     ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call('ciaosr_jpeg_encode_u8', hip_ops.ptr(img), C.c_size_t(img.stride(0)), h, w, ORDERS[order], quality, sub, mcus,
+    _lib.call('ciaosr_jpeg_encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), quality, sub, mcus,
               hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(total), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     n = int(total.item())                                   # copy 1: the size
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the scan
@@ -319,20 +363,21 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
 
 def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """JPEG file (bytes) of a uint8 [H, W, 3] device image, byte for byte `PIL.Image.save(format='JPEG', quality=quality,
-    subsampling=0 or 2)` of the same pixels; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
+    subsampling=0 or 2)` of the same pixels (a 2-D [H, W] image: of the mode-L image, see the module's text); `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
     larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it.
     `optimize=True`: byte for byte `PIL.Image.save(..., optimize=True)`: Huffman tables made for this file on the device.
     `progressive=True`: byte for byte `PIL.Image.save(..., progressive=True)`, whatever `optimize` is."""
     tables = None
     check_optimize(optimize)
-    if check_progressive(progressive):
+    check_not_progressive_grey(img_u8_hwc, check_progressive(progressive))
+    if progressive:
         scans, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
         return assemble_progressive(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, scans, tables)
     if optimize:
         scan, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=True)
     else:
         scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
-    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, tables) + scan + EOI
+    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, tables, is_grey(img_u8_hwc)) + scan + EOI
 
 
 def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
@@ -343,14 +388,16 @@ def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='b
     `progressive=True`: every file Pillow's `progressive=True` file of the crop; thirteen launches and two copies."""
     rects = list(rects)
     check_optimize(optimize)
-    if check_progressive(progressive):
+    check_not_progressive_grey(img_u8_hwc, check_progressive(progressive))
+    grey = is_grey(img_u8_hwc)
+    if progressive:
         scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
         return [assemble_progressive(int(r[2]), int(r[3]), quality, subsampling, s, t) for r, s, t in zip(rects, scans, tables)]
     if optimize:
         scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=True)
-        return [header(int(r[2]), int(r[3]), quality, subsampling, t) + s + EOI for r, s, t in zip(rects, scans, tables)]
+        return [header(int(r[2]), int(r[3]), quality, subsampling, t, grey) + s + EOI for r, s, t in zip(rects, scans, tables)]
     scans = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
-    return [header(int(r[2]), int(r[3]), quality, subsampling) + s + EOI for r, s in zip(rects, scans)]
+    return [header(int(r[2]), int(r[3]), quality, subsampling, None, grey) + s + EOI for r, s in zip(rects, scans)]
 
 
 def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr', optimize=False, progressive=False):

@@ -66,6 +66,44 @@ def pack_bgra_u8(bgr_u8, grey_u8):
     return img
 
 
+def tensor2img_grey_u8(t, out=None):
+    """The 8-bit GREY image of a render: [1, 3, H, W] or [3, H, W] RGB in [0, 1] -> uint8 [H, W].  With (B, G, R) = `tensor2img_u8`'s
+    bytes of the pixel, L = (19595 R + 38470 G + 7471 B + 32768) >> 16: `Image.convert('L')` of the colour image, and v for a neutral
+    (v, v, v).  One pass.  `out`: a uint8 [H, W] device view to write into (rows may be pitched, any alignment)."""
+    shape = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+    if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4) or t.shape[-3] != 3 or (t.dim() == 4 and t.shape[0] != 1):
+        raise ValueError(f'tensor2img_grey_u8 expects [1, 3, H, W] or [3, H, W], got {shape}')
+    h, w = t.shape[-2], t.shape[-1]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (h, w) or (w > 1 and out.stride(1) != 1) \
+                or (h > 1 and out.stride(0) < w):
+            raise ValueError(f'tensor2img_grey_u8: out must be a uint8 [{h}, {w}] view with contiguous rows')
+    t = t.detach().reshape(3, h, w).float().contiguous()
+    hip_ops.require_gpu(t)
+    if out is not None and out.device != t.device:
+        raise CiaoSRHipError(f'tensor2img_grey_u8: out on {out.device} but the render on {t.device}')
+    img = torch.empty((h, w), dtype=torch.uint8, device=t.device) if out is None else out
+    _lib.call('ciaosr_tensor2img_grey_u8', hip_ops.ptr(t), h, w, hip_ops.ptr(img), C.c_size_t(img.stride(0) if h > 1 else w),
+              hip_ops.stream_ptr(t.device))
+    return img
+
+
+def grey_from_bgr_u8(img_u8, order='bgr'):
+    """uint8 [H, W] grey image of a uint8 [H, W, 3] device image (`order` 'bgr' or 'rgb'; rows may be pitched) by the formula of
+    `tensor2img_grey_u8`: `Image.convert('L')`."""
+    if not isinstance(img_u8, torch.Tensor) or img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        what = f'{img_u8.dtype} {tuple(img_u8.shape)}' if isinstance(img_u8, torch.Tensor) else type(img_u8).__name__
+        raise ValueError(f'grey_from_bgr_u8 expects a uint8 [H, W, 3] image, got {what}')
+    if order not in ('bgr', 'rgb'):
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    _check_image(img_u8)
+    h, w = img_u8.shape[0], img_u8.shape[1]
+    img = torch.empty((h, w), dtype=torch.uint8, device=img_u8.device)
+    _lib.call('ciaosr_grey_from_bgr_u8', hip_ops.ptr(img_u8), C.c_size_t(img_u8.stride(0)), 1 if order == 'bgr' else 0, h, w,
+              hip_ops.ptr(img), C.c_size_t(w), hip_ops.stream_ptr(img_u8.device))
+    return img
+
+
 def _check_image(img):
     if not isinstance(img, torch.Tensor):
         raise CiaoSRHipError(f'expected a uint8 HxWx3 cuda tensor, got {type(img).__name__}')

@@ -86,11 +86,15 @@ def _check_convert(convert_to):
 def moments_u8(img, params, crop_border=0, return_luma=False):
     """The five launches of `ciaosr_niqe_moments_u8` on a uint8 [H, W, 3] BGR device image (rows may be pitched): the float64 device
     tensor [2, blocks, 5, 6] of block sums, blocks in the reference's order (column of blocks outer).  Does not synchronise (the first
-    call with a model copies its window to the device).  `return_luma`: also the rounded Y plane, fp32 [H - 2 crop, W - 2 crop]."""
+    call with a model copies its window to the device).  `return_luma`: also the rounded Y plane, fp32 [H - 2 crop, W - 2 crop].
+    A grey uint8 [H, W] image gives the moments of its (v, v, v) image, bit for bit (through a temporary of 3 H W bytes)."""
     import torch
     from .metrics_hip import _check_image
     params = load_params(params)
     crop = int(crop_border)
+    if isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 2:
+        geometry(img.shape[0], img.shape[1], crop)
+        img = img.unsqueeze(2).expand(-1, -1, 3).contiguous()
     if isinstance(img, torch.Tensor) and img.dim() == 3:
         geometry(img.shape[0], img.shape[1], crop)         # a ValueError of the arguments comes before anything about the device
     _check_image(img)
@@ -194,7 +198,7 @@ def finish(feats, params):
 
 def niqe_u8(img, params, crop_border=0, convert_to='y'):
     """The reference's `niqe(img, crop_border, convert_to='y')` of a uint8 [H, W, 3] BGR device image -> float.  The copy of the block
-    sums to the host is the only synchronisation."""
+    sums to the host is the only synchronisation.  A grey [H, W] image scores as its (v, v, v) image."""
     _check_convert(convert_to)
     params = load_params(params)
     return finish(features(moments_u8(img, params, crop_border)), params)

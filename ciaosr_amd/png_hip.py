@@ -15,6 +15,10 @@ bytes and not one bit per byte, and no file gets larger.
 
 A uint8 [H, W, 4] image (`order` 'bgra', as `metrics_hip.tensor2img_bgra_u8` makes it, or 'rgba') goes through the four-byte-per-pixel
 siblings of the same calls and becomes a colour type 6 file; every entry point here takes either kind.
+
+A 2-D uint8 [H, W] image is a GREY image (`order` left at its default, or 'grey'; as `metrics_hip.tensor2img_grey_u8` makes it): the
+one-byte-per-pixel siblings, rows of 1 + W bytes with the left predecessor one byte back, a colour type 0 file that Pillow opens as
+mode L.  No alignment rule: a crop may start at any byte.
 """
 import ctypes as C
 import os
@@ -33,8 +37,9 @@ ADLER = 65521
 MAX_SIDE = 65535
 ORDERS = {'bgr': 1, 'rgb': 0}
 ORDERS_RGBA = {'bgra': 1, 'rgba': 0}
-COLOUR_TYPES = {3: 2, 4: 6}                # bytes per pixel -> IHDR colour type
-_ABI = {3: 'ciaosr_png_', 4: 'ciaosr_png_rgba_'}
+COLOUR_TYPES = {3: 2, 4: 6}                # bytes per pixel -> IHDR colour type (`container(channels=)`; grey is its own keyword)
+COLOUR_TYPE_GREY = 0
+_ABI = {1: 'ciaosr_png_grey_', 3: 'ciaosr_png_', 4: 'ciaosr_png_rgba_'}
 
 
 def _check_matches(matches):
@@ -45,7 +50,12 @@ def _check_matches(matches):
 
 def _pitch(img):
     """Bytes from one row to the next; a one-row image has no next row, and torch may report any stride for it."""
-    return img.stride(0) if img.shape[0] > 1 else img.shape[1] * img.shape[2]
+    return img.stride(0) if img.shape[0] > 1 else img.shape[1] * channels_of(img)
+
+
+def channels_of(img):
+    """Bytes per pixel of an image tensor: 1 for a 2-D (grey) one."""
+    return 1 if img.dim() == 2 else img.shape[2]
 
 
 def _check_image(img, order):
@@ -53,6 +63,8 @@ def _check_image(img, order):
     `order` of its channel count -> (channels, the ABI's bgr flag).  A wrong order is a ValueError before the device is looked at."""
     if not isinstance(img, torch.Tensor):
         raise CiaoSRHipError(f'expected a uint8 HxWx3 or HxWx4 cuda tensor, got {type(img).__name__}')
+    if img.dtype == torch.uint8 and img.dim() == 2:
+        return _check_grey(img, order)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] not in (3, 4):
         raise CiaoSRHipError(f'expected a uint8 HxWx3 or HxWx4 image, got {img.dtype} {tuple(img.shape)}')
     ch = img.shape[2]
@@ -71,19 +83,37 @@ def _check_image(img, order):
     return ch, orders[order]
 
 
+def _check_grey(img, order):
+    """`_check_image` for a 2-D image: `order` is the default or 'grey'; rows of W contiguous bytes, any pitch >= W, any alignment."""
+    if order not in ('bgr', 'grey'):
+        raise ValueError(f"order of a grey [H, W] image stays at its default or is 'grey', got {order!r}")
+    if not img.is_cuda:
+        hip_ops.require_gpu(img)              # raises: no CPU fallback
+    h, w = img.shape
+    if (w > 1 and img.stride(1) != 1) or (h > 1 and img.stride(0) < w):
+        raise CiaoSRHipError('expected rows of W contiguous bytes (a crop of a larger image is fine)')
+    if img.device.index != torch.cuda.current_device():
+        raise CiaoSRHipError(f'image on cuda:{img.device.index} but the current device is cuda:{torch.cuda.current_device()}')
+    return 1, 0
+
+
 def chunk(tag, data):
     """One PNG chunk: length, type, data, CRC-32 of type + data."""
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(data, zlib.crc32(tag)) & 0xffffffff)
 
 
-def container(h, w, zstream, idat_max=IDAT_MAX, channels=3):
-    """The PNG file of an h x w 8-bit RGB (`channels=4`: RGBA, colour type 6) image whose IDAT data is `zstream` (a zlib stream of the
-    filtered scanlines), split into IDAT chunks of at most `idat_max` bytes."""
+def container(h, w, zstream, idat_max=IDAT_MAX, channels=3, grey=False):
+    """The PNG file of an h x w 8-bit RGB (`channels=4`: RGBA, colour type 6; `grey=True`: one byte per pixel, colour type 0, whatever
+    `channels` is) image whose IDAT data is `zstream` (a zlib stream of the filtered scanlines), split into IDAT chunks of at most
+    `idat_max` bytes."""
     if not (0 < idat_max <= IDAT_MAX):
         raise ValueError(f'idat_max={idat_max}')
+    if not isinstance(grey, bool):
+        raise ValueError(f'grey is True or False, got {grey!r}')
     if channels not in COLOUR_TYPES:
         raise ValueError(f'channels={channels!r}: 3 (RGB) or 4 (RGBA)')
-    parts = [SIGNATURE, chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, COLOUR_TYPES[channels], 0, 0, 0))]
+    colour_type = COLOUR_TYPE_GREY if grey else COLOUR_TYPES[channels]
+    parts = [SIGNATURE, chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, colour_type, 0, 0, 0))]
     view = memoryview(zstream)
     for i in range(0, max(len(view), 1), idat_max):
         parts.append(chunk(b'IDAT', bytes(view[i:i + idat_max])))
@@ -129,7 +159,7 @@ def _geometry(img, order, rows_per_band):
 
 def filter_u8(img, order='bgr', rows_per_band=0):
     """Stage 1 alone: (scanline stream uint8 [H * (1 + C W)], histograms int32 [bands, 260], Adler partials int32 [bands, 2]) on the
-    device, C = 3 or 4 channels; no synchronisation."""
+    device, C = 3 or 4 channels, 1 for a 2-D (grey) image; no synchronisation."""
     h, w, rows, nb, ch, bgr = _geometry(img, order, rows_per_band)
     dev = img.device
     stream = torch.empty(h * (ch * w + 1), dtype=torch.uint8, device=dev)
@@ -196,13 +226,19 @@ def encode_zlib(img, order='bgr', rows_per_band=0, matches=False):
     return out[:n].cpu().numpy().tobytes()                  # copy 2: the stream
 
 
+def _wrap(img, h, w, z):
+    """`container` for an h x w image (or crop) of `img`'s kind"""
+    return container(h, w, z, grey=True) if img.dim() == 2 else container(h, w, z, channels=img.shape[2])
+
+
 def encode_png(img_u8_hwc, order='bgr', rows_per_band=0, matches=False):
     """PNG file (bytes) of a uint8 [H, W, 3] device image; `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched
     (a crop view of a larger image).  `rows_per_band`: image rows per independently coded band, 0 = about 128 KiB of scanline bytes.
-    A [H, W, 4] image with `order` 'bgra' (as `tensor2img_bgra_u8` makes it) or 'rgba' gives an RGBA file.
+    A [H, W, 4] image with `order` 'bgra' (as `tensor2img_bgra_u8` makes it) or 'rgba' gives an RGBA file, a 2-D [H, W] image (as
+    `tensor2img_grey_u8` makes it) a grey one that Pillow opens as mode L.
     `matches=True`: bands may use LZ77 matches (see the module's text); the file is never larger and decodes to the same pixels."""
     z = encode_zlib(img_u8_hwc, order, rows_per_band, matches)
-    return container(img_u8_hwc.shape[0], img_u8_hwc.shape[1], z, channels=img_u8_hwc.shape[2])
+    return _wrap(img_u8_hwc, img_u8_hwc.shape[0], img_u8_hwc.shape[1], z)
 
 
 def check_rects(rects, h, w):
@@ -260,7 +296,7 @@ def encode_png_tiles(img_u8_hwc, rects, order='bgr', rows_per_band=0, matches=Fa
     _check_matches(matches)
     rects = list(rects)
     zs = encode_zlib_tiles(img_u8_hwc, rects, order, rows_per_band, matches)
-    return [container(int(r[2]), int(r[3]), z, channels=img_u8_hwc.shape[2]) for r, z in zip(rects, zs)]
+    return [_wrap(img_u8_hwc, int(r[2]), int(r[3]), z) for r, z in zip(rects, zs)]
 
 
 def imwrite_gpu(img_u8_hwc, path, order='bgr', matches=False):

@@ -4,7 +4,8 @@ above the LR size are the model's own answer at that size, all from one walk ove
 ONE `png_hip.encode_png_tiles` call: two synchronising copies per level, whatever its number of tiles.  `fmt='jpg'` writes
 `<col>_<row>.jpg` tiles through one `jpeg_hip.encode_jpeg_tiles` call per level instead, and `Format="jpg"` in the manifest.  The levels
 of an RGBA encode (`CiaoSR.encode_rgba`) are uint8 [H_l, W_l, 4] images and become RGBA PNG tiles under the same manifest; JPEG has no
-alpha, so `fmt='jpg'` refuses them.
+alpha, so `fmt='jpg'` refuses them.  The levels of a grey encode (`CiaoSR.encode_grey`) are uint8 [H_l, W_l] images and become grey
+PNG tiles (colour type 0) or one-component JPEG tiles -- not progressive ones -- under the same manifest.
 
 Deep Zoom's rules: Lmax = ceil(log2(max(W, H))), levels 0..Lmax; level L is max(1, ceil(W / 2^(Lmax - L))) wide and as high by the same
 rule; on a level, column c spans [c T - (O if c > 0 else 0), min((c + 1) T + O, Wl)) for the tile size T and the overlap O, rows alike,
@@ -85,6 +86,8 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
     """Write the pyramid whose levels are the uint8 [H_l, W_l, 3] device images `levels` (level 0 first, as `CiaoSR.render_pyramid`
     returns them): one `encode_png_tiles` call per level, or for `fmt='jpg'` one `encode_jpeg_tiles` call with `quality` and
     `subsampling` (`optimize=True`: every tile with Huffman tables of its own; `progressive=True`: every tile a progressive file).
+    Two-dimensional levels ([H_l, W_l], grey) are written as grey PNG tiles (`matches` too) or, with `fmt='jpg'`, as one-component
+    JPEG tiles (`optimize` too; `progressive=True` or a `subsampling` other than '444' is a ValueError before any device work).
     Four-channel levels ([H_l, W_l, 4], bytes B G R A for `order` 'bgr' / 'bgra', R G B A for 'rgb' / 'rgba') are written as RGBA PNG
     tiles; with `fmt='jpg'` they are a ValueError before any device work.  `matches=True` (only `fmt='png'`, else a ValueError): the
     tiles are coded with `encode_png_tiles(..., matches=True)` -- flat and transparent tiles get far smaller, none gets larger.
@@ -95,12 +98,21 @@ def write_levels(levels, out_dir, name, tile_size=254, overlap=1, order='bgr', f
         if _check_format(fmt) == 'jpg':
             raise ValueError("fmt='jpg' cannot hold the alpha channel of four-channel levels: write them with fmt='png'")
         order = {'bgr': 'bgra', 'rgb': 'rgba'}.get(order, order)
+    grey = any(getattr(im, 'dim', lambda: 0)() == 2 for im in levels)
+    if grey:
+        if not all(getattr(im, 'dim', lambda: 0)() == 2 for im in levels):
+            raise ValueError('grey [H_l, W_l] levels and colour levels do not mix in one pyramid')
+        if order not in ('bgr', 'grey'):
+            raise ValueError(f"order of grey [H_l, W_l] levels stays at its default or is 'grey', got {order!r}")
+        order = 'grey'
     if _check_format(fmt) == 'jpg':
         from .jpeg_hip import check_optimize, check_params, check_progressive, encode_jpeg_tiles
         check_params(quality, subsampling)
         coding = dict(optimize=True) if check_optimize(optimize) else {}       # without it encode_jpeg_tiles is called as before
         if check_progressive(progressive):
             coding['progressive'] = True
+        if grey and (progressive or subsampling != '444'):
+            raise ValueError("grey levels have no progressive JPEG form and no subsampling: progressive=False, subsampling='444'")
 
         def encode(img, rects):
             return encode_jpeg_tiles(img, rects, quality=quality, subsampling=subsampling, order=order, **coding)
@@ -153,6 +165,8 @@ def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, o
         check_params(quality, subsampling)
         check_optimize(optimize)
         check_progressive(progressive)
+        if getattr(enc, 'grey', False) and (progressive or subsampling != '444'):
+            raise ValueError("a grey encode has no progressive JPEG form and no subsampling: progressive=False, subsampling='444'")
     t0 = time.perf_counter()
     levels = model.render_pyramid(enc, size=size, scale=scale)
     render_s = time.perf_counter() - t0

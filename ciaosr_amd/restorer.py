@@ -520,6 +520,18 @@ class CiaoSR(BasicRestorer):
         return scene_render.encode_rgba(self, lq4, options, max_scale, self_ensemble)
 
     @torch.no_grad()
+    def encode_grey(self, lq1, options=None, max_scale=None, self_ensemble=None):
+        """`encode` of grey images [B, 1, h, w] (float in [0, 1]) as the colour images (v, v, v): the same model, options, tiling,
+        scenes and (with `self_ensemble`) ensemble record, marked `enc.grey`.  Every render of such a record returns with `as_u8` a
+        uint8 [H, W] device image (`metrics_hip.tensor2img_grey_u8`): with (B, G, R) = `tensor2img_u8`'s bytes of the render,
+        L = (19595 R + 38470 G + 7471 B + 32768) >> 16 -- `Image.convert('L')` of the colour render, so the answer is grey whatever
+        the model's three output rows do; quantised once, after the tile blend, the view fill and the ensemble mean (outside a view:
+        the byte of (fill, fill, fill)).  Without `as_u8` the fp32 [B, 3, H, W] of the plain encode, bit for bit.  `render_pyramid`
+        resizes the grey smallest model level below the LR size (Pillow's BICUBIC of the L image).  A tensor that is not
+        [B, 1, h, w] is a ValueError."""
+        return scene_render.encode_grey(self, lq1, options, max_scale, self_ensemble)
+
+    @torch.no_grad()
     def render(self, enc, size=None, scale=None, window=None, as_u8=False):
         """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
         round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,

@@ -337,6 +337,7 @@ class EncodedImage:
         self.cache = SceneCache(budget_bytes, build)
         self.view_tiles = None          # render_view's frame list on the device, uploaded by the first view render
         self.alpha = False              # CiaoSR.encode_rgba: the batch is (colour, alpha as grey) of ONE RGBA image
+        self.grey = False               # CiaoSR.encode_grey: the colour image (v, v, v) of a grey input; `as_u8` renders are [H, W]
 
     @property
     def shape(self):
@@ -357,6 +358,7 @@ class EnsembleEncoded:
         self.members = list(members)
         self._shape = tuple(shape)
         self.alpha = False
+        self.grey = False               # CiaoSR.encode_grey with self_ensemble
 
     @property
     def shape(self):

@@ -53,6 +53,9 @@ def _scene_budget(r):
 def encode_rgba(r, lq4, options=None, max_scale=None, self_ensemble=None):
     """`encode` of the two-item batch of an RGBA image [1, 4, h, w]: item 0 the colour as stored (not premultiplied), item 1 the alpha
     plane in all three channels; `enc.alpha` marks it for the renders.  Not with `self_ensemble` (ValueError)."""
+    if isinstance(lq4, torch.Tensor) and lq4.dim() == 4 and lq4.shape[1] == 2:
+        raise ValueError(f'encode_rgba expects one RGBA image [1, 4, h, w], got {tuple(lq4.shape)}: there is no grey + alpha encode '
+                         f'(PNG colour type 4); repeat the grey channel three times, or drop the alpha and use encode_grey')
     if not isinstance(lq4, torch.Tensor) or lq4.dim() != 4 or lq4.shape[0] != 1 or lq4.shape[1] != 4:
         shape = tuple(lq4.shape) if isinstance(lq4, torch.Tensor) else type(lq4).__name__
         raise ValueError(f'encode_rgba expects one RGBA image [1, 4, h, w], got {shape}')
@@ -60,6 +63,17 @@ def encode_rgba(r, lq4, options=None, max_scale=None, self_ensemble=None):
         raise ValueError('encode_rgba has no self-ensemble: encode the colour image with self_ensemble, or turn the option off')
     enc = encode(r, torch.cat([lq4[:, :3], lq4[:, 3:4].expand(-1, 3, -1, -1)], 0), options, max_scale, self_ensemble=False)
     enc.alpha = True
+    return enc
+
+
+def encode_grey(r, lq1, options=None, max_scale=None, self_ensemble=None):
+    """`encode` of the colour image (v, v, v) of a grey batch [B, 1, h, w]; `enc.grey` marks it for the renders, which quantise to one
+    byte per pixel with `as_u8` (`metrics_hip.tensor2img_grey_u8`).  The record may be an ensemble's."""
+    if not isinstance(lq1, torch.Tensor) or lq1.dim() != 4 or lq1.shape[1] != 1:
+        shape = tuple(lq1.shape) if isinstance(lq1, torch.Tensor) else type(lq1).__name__
+        raise ValueError(f'encode_grey expects grey images [B, 1, h, w], got {shape}')
+    enc = encode(r, lq1.expand(-1, 3, -1, -1).contiguous(), options, max_scale, self_ensemble)
+    enc.grey = True
     return enc
 
 
@@ -113,8 +127,7 @@ def render_ensemble(r, enc, targets, as_u8=False, many=False):
             hip_ops.dihedral_accum(accs[j], out, k, first=(i == 0), divisor=float(n) if i == n - 1 else 0.0)
         del outs
     if as_u8:
-        from . import metrics_hip
-        return [metrics_hip.tensor2img_u8(acc) for acc in accs]
+        return [_quantise(acc, grey=is_grey(enc)) for acc in accs]
     return accs
 
 
@@ -124,6 +137,20 @@ ALPHA_FILL = (0.0, 0.0, 0.0)                  # outside a view the alpha item is
 def is_alpha(enc):
     """Whether `enc` is an `encode_rgba` result (any other record, a test's stand-in included, is not)."""
     return bool(getattr(enc, 'alpha', False))
+
+
+def is_grey(enc):
+    """Whether `enc` is an `encode_grey` result."""
+    return bool(getattr(enc, 'grey', False))
+
+
+def _quantise(out, alpha=False, grey=False):
+    """The ONE place a render becomes bytes, after everything fp32 (the tile blend, the view fill, the self-ensemble mean): BGR, BGRA
+    of the (colour, alpha) pair of an RGBA encode, or one grey byte per pixel of a grey encode."""
+    from . import metrics_hip
+    if grey:
+        return metrics_hip.tensor2img_grey_u8(out)
+    return metrics_hip.tensor2img_bgra_u8(out) if alpha else metrics_hip.tensor2img_u8(out)
 
 
 def _finish(tg, r, enc, b, acc):
@@ -287,13 +314,10 @@ def resolve(r, enc, targets):
     return out
 
 
-def _stacked(outs, as_u8, alpha=False):
-    """The items' outputs as one tensor; with `as_u8` the 8-bit image: BGR, or BGRA of the (colour, alpha) pair of an RGBA encode."""
+def _stacked(outs, as_u8, alpha=False, grey=False):
+    """The items' outputs as one tensor; with `as_u8` the 8-bit image (`_quantise`)."""
     out = torch.stack(outs)
-    if as_u8:
-        from . import metrics_hip
-        return metrics_hip.tensor2img_bgra_u8(out) if alpha else metrics_hip.tensor2img_u8(out)
-    return out
+    return _quantise(out, alpha, grey) if as_u8 else out
 
 
 # -- one target: scenes from the cache, tile by tile ------------------------------------------------------------------------------------
@@ -301,7 +325,7 @@ def render_one(r, enc, tg, as_u8=False):
     """The single calls `render` / `render_view`, of a resolved target: per batch item, every scene taken with `enc.cache.get` when its
     tile's turn comes -- no walk, no batched trunk, no side stream."""
     if isinstance(tg, GridTarget) and tg.tiles is None:
-        return _stacked(tg.render_whole(r, enc), as_u8, is_alpha(enc))
+        return _stacked(tg.render_whole(r, enc), as_u8, is_alpha(enc), is_grey(enc))
     outs = []
     for b in range(enc.x.shape[0]):
         if isinstance(tg, ViewTarget):
@@ -310,7 +334,7 @@ def render_one(r, enc, tg, as_u8=False):
         for k, origin in tg.touched().items():
             tg.query(r.generator, k, enc.cache.get((b, origin)), acc)
         outs.append(_finish(tg, r, enc, b, acc))
-    return _stacked(outs, as_u8, is_alpha(enc))
+    return _stacked(outs, as_u8, is_alpha(enc), is_grey(enc))
 
 
 # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------------
@@ -382,7 +406,7 @@ def render_many(r, enc, targets, as_u8=False):
                 tgs[i].query(r.generator, k, tile_scene, acc[i])
         for i, tg in enumerate(tgs):
             outs[i].append(_finish(tg, r, enc, b, acc[i]))
-    return [_stacked(o, as_u8, is_alpha(enc)) for o in outs]
+    return [_stacked(o, as_u8, is_alpha(enc), is_grey(enc)) for o in outs]
 
 
 def prefetch(r, enc, targets):
@@ -424,6 +448,12 @@ def render_pyramid(r, enc, size=None, scale=None):
     sizes, first = plan_pyramid(r, enc, size, scale)
     model_levels = render_many(r, enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
     base = model_levels[0]
+    if is_grey(enc):
+        # Pillow's resize of an L image is every channel of its resize of (v, v, v): the three-channel resampler on the replicated
+        # level, reduced back (a neutral pixel's grey byte is its value)
+        from . import metrics_hip
+        wide = base.unsqueeze(2).expand(-1, -1, 3).contiguous()
+        return [metrics_hip.grey_from_bgr_u8(degrade.resize_bicubic_u8(wide, (wl, hl))) for hl, wl in sizes[:first]] + list(model_levels)
     if not is_alpha(enc):
         return [degrade.resize_bicubic_u8(base, (wl, hl)) for hl, wl in sizes[:first]] + list(model_levels)
     # RGBA: colour and alpha are resized on their own (Pillow's resize of the RGB image and of the A band, NOT its premultiplied

@@ -887,6 +887,21 @@ size_t ciaosr_png_rgba_tiles_capacity_bytes(const int* rects /*host*/, int n_til
 int ciaosr_png_rgba_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
                                     int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
                                     void* workspace, size_t workspace_bytes, void* stream);
+/* ---- Grey: one byte per pixel, and its PNG (colour type 0) and JPEG (one component) files (version 340) -----------
+ * The grey byte of a pixel whose three bytes are (B, G, R) is L = (19595 R + 38470 G + 7471 B + 32768) >> 16 in integers: Pillow's
+ * convert('L') and libjpeg's luma.  The weights sum to 65536: a neutral v, v, v gives v.  It is NOT the alpha formula above (the two
+ * differ by 1 on 39 135 of the 2^24 triples).
+ * ciaosr_tensor2img_grey_u8: src_chw fp32 [3][H][W] RGB -> dst[y * dst_pitch + x] = L of ciaosr_tensor2img_u8's three bytes of the pixel
+ * (one fp32 multiply, round half to even, clamp, NaN -> 0), in one pass.  dst_pitch >= W, any alignment (a 4-byte aligned dst and
+ * pitch get one 32-bit store per four pixels; any other is written in single bytes).  H <= 65535.
+ * ciaosr_grey_from_bgr_u8: the same reduction from an 8-bit image bgr[y * pitch + 3 x + c], pitch >= 3 W; bgr_flag = 1: the bytes of a
+ * pixel are B G R, 0: R G B. */
+int ciaosr_tensor2img_grey_u8(const float* src_chw, int H, int W, unsigned char* dst, size_t dst_pitch, void* stream);
+int ciaosr_grey_from_bgr_u8(const unsigned char* bgr, size_t pitch, int bgr_flag, int H, int W, unsigned char* dst, size_t dst_pitch,
+                            void* stream);
+/* The one-byte-per-pixel siblings of the PNG calls (ciaosr_png_grey_*, colour type 0) are declared in ciaosr_hip_png_grey.h, which
+ * this header includes at its end: every PNG size export declared in THIS file is one of those that tests/golden/png_sizes.json
+ * records, and that record was made before the grey family existed. */
 /* LZ77 matches, opt-in (version 330; png_hip `matches=True`; DESIGN 4.1i-b3 holds the contract).  The *_lz_* entry points take the
  * arguments of their namesakes above and give streams that decode to the same bytes; out needs the same capacity (stored blocks stay
  * a candidate), the workspace is larger (16 bits of token per filtered byte): ciaosr_png[_rgba]_lz_workspace_bytes and
@@ -945,6 +960,14 @@ int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* ba
  * memory.  The workspace is 8-byte aligned; nothing is allocated. */
 #define CIAOSR_JPEG_444 0   /* Pillow's subsampling=0 */
 #define CIAOSR_JPEG_420 2   /* Pillow's subsampling=2 */
+/* One component (version 340): Pillow's mode-L file, PIL.Image.fromarray(grey, 'L').save(format='JPEG', quality=).  Accepted as
+ * `subsampling` by the ciaosr_jpeg_* and ciaosr_jpeg_opt_* entries: src[y * pitch + x], pitch >= W, bgr is not read; one 8 x 8 block
+ * per MCU, the luma quantisation table, Huffman tables 0, no dummy blocks (edges repeat the crop's last column and row), the DC
+ * predictor chain over consecutive blocks.  Capacity: 416 bytes per block; optimised 2 x ceil(1665 x blocks / 8).  An optimised
+ * call's `result` keeps its layout, the records k = 2, 3 all zero.  The host writes one DQT, SOF0 with the component (1, 0x11, 0), two
+ * DHT (0x00, 0x10) and a one-component SOS.  The ciaosr_jpeg_prog_* entries refuse it: size 0, CIAOSR_ERR_UNSUPPORTED before any
+ * launch.  The values 1 and 3 stay invalid. */
+#define CIAOSR_JPEG_GREY 4
 size_t ciaosr_jpeg_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk);
 size_t ciaosr_jpeg_capacity_bytes(int H, int W, int subsampling);
 int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
@@ -1026,4 +1049,7 @@ int ciaosr_jpeg_prog_encode_tiles_u8(const unsigned char* src, size_t pitch, int
 #ifdef __cplusplus
 }
 #endif
+
+#include "ciaosr_hip_png_grey.h"
+
 #endif /* CIAOSR_HIP_H */

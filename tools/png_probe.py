@@ -64,6 +64,15 @@ host + `PIL.Image.save`.  Inputs: the first size as the RGBA 'view' with the fil
 as that view, the three other `--rgba-cases` and the smooth and noisy RGB images.  Legs alternating in one process, 2 warm-up + 5
 timed rounds; the file bytes of all three and both device coders' kernel times (a profiled call of their own) are recorded.  Default
 --out: profiles/png_matches.txt.
+
+    python tools/png_probe.py --leg grey [--sizes 5424x8160 768x768] [--quality 90] [--out FILE]
+
+Grey files from uint8 [H, W] device images (the integer luma of the smooth and the noisy image), in four formats: PNG, PNG with
+matches, JPEG of --quality plain and optimised.  Per image and format (a) the grey device call, against two baselines: (b) the
+three-channel device call on the (v, v, v) image of the same run, (c) the copy to the host + `PIL.Image.save` of the `L` image.  Legs
+alternating in one process, 2 warm-up + 5 timed rounds; wall times, the kernel times of (a) and (b) (a profiled call of their own) and the
+file bytes of all three are recorded; the PNG pixels of (a) and (c) and the JPEG bytes of (a) and (c) are compared.  Default --out:
+profiles/grey_codecs.txt.
 """
 import json
 import subprocess
@@ -400,6 +409,58 @@ def matches_leg(args, say):
             del img
 
 
+def grey_leg(args, say):
+    """The grey device calls against the three-channel device calls on (v, v, v) and against copy + PIL save of the L image."""
+    import io
+    from PIL import Image
+    from ciaosr_amd.jpeg_hip import encode_jpeg
+    from ciaosr_amd.metrics_hip import grey_from_bgr_u8
+    from ciaosr_amd.png_hip import encode_png
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def pil_l(img, fmt, **kw):
+        bio = io.BytesIO()
+        Image.fromarray(img.cpu().numpy(), 'L').save(bio, format=fmt, **kw)
+        return bio.getvalue()
+
+    formats = [('PNG', lambda im: encode_png(im), lambda im: pil_l(im, 'PNG')),
+               ('PNG, matches=True', lambda im: encode_png(im, matches=True), lambda im: pil_l(im, 'PNG')),
+               (f'JPEG q{args.quality}', lambda im: encode_jpeg(im, quality=args.quality), lambda im: pil_l(im, 'JPEG', quality=args.quality)),
+               (f'JPEG q{args.quality}, optimize=True', lambda im: encode_jpeg(im, quality=args.quality, optimize=True),
+                lambda im: pil_l(im, 'JPEG', quality=args.quality, optimize=True))]
+    import PIL.ImageFile
+    PIL.ImageFile.MAXBLOCK = max(PIL.ImageFile.MAXBLOCK, 1 << 28)      # Pillow codes an optimised file into one buffer
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        for content in args.contents:
+            grey = grey_from_bgr_u8(make_image(h, w, content, dev))
+            wide = grey.unsqueeze(2).expand(-1, -1, 3).contiguous()
+            torch.cuda.synchronize()
+            for name, device_call, pil_call in formats:
+                legs = {'a': lambda: device_call(grey), 'b': lambda: device_call(wide), 'c': lambda: pil_call(grey)}
+                times = run_legs(args, legs)
+                mine, three, pil = legs['a'](), legs['b'](), legs['c']()
+                if name.startswith('PNG'):
+                    im = Image.open(io.BytesIO(mine))
+                    same = f'mode {im.mode}, decoded pixels identical to Pillow\'s: {np.array_equal(np.asarray(im), np.asarray(Image.open(io.BytesIO(pil))))}'
+                else:
+                    same = f'bytes identical to Pillow\'s: {mine == pil}'
+                say(f'{h} x {w} {content}, {name}: {same}; file bytes grey {len(mine)}, three-channel {len(three)}, Pillow L {len(pil)}; '
+                    f'grey / three-channel {len(mine) / len(three):.4f}, grey / Pillow {len(mine) / len(pil):.4f}')
+                say(f'  (a) grey device call                    wall s: {stats(times["a"])}')
+                say(f'  (b) three-channel device call, (v,v,v)  wall s: {stats(times["b"])}')
+                say(f'  (c) copy to the host + PIL save of L    wall s: {stats(times["c"])}')
+                for other, what in (('b', 'three-channel'), ('c', 'host')):
+                    gap = statistics.mean(times[other]) - statistics.mean(times['a'])
+                    spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', other))
+                    say(f'  ({other}) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                        f'{"grey call faster beyond the spread" if gap > spread else (what + " call faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                        f'ratio ({other}) / (a) {statistics.mean(times[other]) / statistics.mean(times["a"]):.2f}x')
+                say(f'  (a) kernels: {kernels(legs["a"])}')
+                say(f'  (b) kernels: {kernels(legs["b"])}')
+            del grey, wide
+
+
 def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
@@ -567,7 +628,7 @@ def jpeg_prog_leg(args, say):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches', 'grey'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -593,6 +654,11 @@ def main(argv=None):
     if args.leg in ('jpeg-opt', 'jpeg-prog'):
         args.contents = ['noisy']
     rgba = args.leg in ('rgba', 'matches')
+    grey = args.leg == 'grey'
+    if grey:                                                 # sizes and file of its own; the shared tail below is the jpeg legs'
+        args.sizes = args.sizes or ['5424x8160', '768x768']
+        args.out = args.out or os.path.join(REPO, 'profiles', 'grey_codecs.txt')
+        jpeg = True
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['768x768', '5424x8160'] if rgba else ['5424x8160', '768x768'])
     args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_matches.txt' if args.leg == 'matches' else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
@@ -619,6 +685,8 @@ def main(argv=None):
         jpeg_opt_leg(args, say)
     if args.leg == 'jpeg-prog':
         jpeg_prog_leg(args, say)
+    if grey:
+        grey_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
         for size in ([] if tiles or jpeg or rgba else args.sizes):
             h, w = (int(v) for v in size.split('x'))

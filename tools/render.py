@@ -44,7 +44,13 @@ without the flag.  Not with --jpeg: JPEG files have no alpha.
 transpose (8 members, `CiaoSR.encode(..., self_ensemble=True)`), every member renders its own transformed window and the results are mapped
 back and averaged on the device in fp32 -- the image `CiaoSR.restore(..., self_ensemble=True)` gives, quantised once after the mean.  Eight
 times the work and scene memory of the plain run.  Not with --view, --dzi or --alpha (an argparse error).
-`--png-matches` (only with --gpu-png or --alpha, never with --jpeg) lets the device PNG coder use LZ77 matches for every .png of the run,
+`--grey` treats the input as a single-channel image: it is read through Pillow's convert('L') (a file that was not grey is reported in
+one line), encoded as the colour image (v, v, v) (CiaoSR.encode_grey), and every --scale, --view and --dzi output is rendered as a uint8
+[H, W] image on the device -- the integer luma of the render's bytes, Pillow's convert('L'), so the answer is grey -- and coded there as
+a grey .png (colour type 0), or with --jpeg Q [--jpeg-optimize] as a one-component .jpg, byte for byte Pillow's mode-L file.
+--png-matches, --niqe and --self-ensemble work as for colour.  Not with --alpha (no grey + alpha files), --jpeg-progressive (no grey
+progressive files) or --jpeg-subsampling 420.
+`--png-matches` (only with --gpu-png, --alpha or --grey, never with --jpeg) lets the device PNG coder use LZ77 matches for every .png of the run,
 pyramid tiles included: transparent and filled regions then cost next to nothing, and no file gets larger (png_hip `matches=True`).
 """
 import argparse
@@ -83,6 +89,8 @@ def parse_args(argv=None):
                    help='with --jpeg: progressive files coded on the GPU, the files of Pillow\'s progressive=True (default off)')
     p.add_argument('--alpha', action='store_true',
                    help='keep the transparency of the input: alpha goes through the model as a grey image, outputs are RGBA PNG files (default off)')
+    p.add_argument('--grey', action='store_true',
+                   help='the input is a single-channel image: outputs are grey .png (or one-component .jpg) files coded on the GPU (default off)')
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
@@ -107,8 +115,14 @@ def parse_args(argv=None):
         p.error('--alpha writes RGBA PNG files: JPEG has no alpha channel, drop --jpeg')
     if args.png_matches and args.jpeg is not None:
         p.error('--png-matches is the PNG coder\'s option: drop --jpeg')
-    if args.png_matches and not (args.gpu_png or args.alpha):
-        p.error('--png-matches belongs to --gpu-png or --alpha, whose files the device codes')
+    if args.grey and args.alpha:
+        p.error('--grey with --alpha: there are no grey + alpha files (PNG colour type 4) here, drop one of them')
+    if args.grey and args.jpeg_progressive:
+        p.error('--grey with --jpeg-progressive: there are no one-component progressive files here, drop --jpeg-progressive')
+    if args.grey and args.jpeg is not None and args.jpeg_subsampling != '444':
+        p.error('--grey has no chroma to subsample: drop --jpeg-subsampling')
+    if args.png_matches and not (args.gpu_png or args.alpha or args.grey):
+        p.error('--png-matches belongs to --gpu-png, --alpha or --grey, whose files the device codes')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
     if args.jpeg_progressive and args.jpeg is None:
@@ -142,7 +156,7 @@ def main(argv=None):
     from ciaosr_amd import metrics
     from ciaosr_amd.checkpoint import load_checkpoint
     from ciaosr_amd.config import Config
-    from ciaosr_amd.imageio import imread_rgb01, imread_rgba01, imwrite
+    from ciaosr_amd.imageio import imread_grey01, imread_rgb01, imread_rgba01, imwrite
 
     cfg = Config.fromfile(args.config)
     if args.checkpoint in (None, 'None'):
@@ -172,6 +186,12 @@ def main(argv=None):
         wanted = wanted + [args.dzi]
     if alpha:
         enc = model.encode_rgba(lq4.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted))
+    elif args.grey:
+        lq1, was_grey = imread_grey01(args.image)
+        if not was_grey:
+            print(f'{args.image}: not a grey image, --grey keeps its luma (convert("L")) only')
+        ens = dict(self_ensemble=True) if args.self_ensemble else {}
+        enc = model.encode_grey(lq1.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted), **ens)
     else:
         lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
         ens = dict(self_ensemble=True) if args.self_ensemble else {}                 # without --self-ensemble encode is called as before
@@ -190,7 +210,7 @@ def main(argv=None):
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
-    as_u8 = gpu_png or form['fmt'] == 'jpg' or alpha
+    as_u8 = gpu_png or form['fmt'] == 'jpg' or alpha or args.grey
     outs = model.render_many(enc, targets, as_u8=as_u8) if targets else []           # one walk over the tile scenes for every output
     scores = {}
     if args.niqe and targets:
@@ -210,8 +230,12 @@ def main(argv=None):
             print(f'{path}: NIQE {scores[os.path.basename(path)]}')
         if form['fmt'] == 'jpg':
             from ciaosr_amd.jpeg_hip import imwrite_gpu_jpeg
-            imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR on the device
+            imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR (--grey: [H, W]) on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
+        elif args.grey:
+            from ciaosr_amd.png_hip import imwrite_gpu
+            imwrite_gpu(out, path, **lz)                               # uint8 [H, W] on the device
+            print(f'{path}: {out.shape[0]} x {out.shape[1]} grey')
         elif alpha:
             from ciaosr_amd.png_hip import imwrite_gpu
             imwrite_gpu(out, path, order='bgra', **lz)                 # uint8 [H, W, 4] B G R A on the device
