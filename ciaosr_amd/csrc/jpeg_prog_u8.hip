@@ -459,185 +459,107 @@ __global__ __launch_bounds__(kThreads) void prog_corr_kernel(PParams p) {
 }
 
 // ---- the host's plan -------------------------------------------------------------------------------------------------------------
-// items of scan s of an h x w crop
-static inline u64 scan_items(const ScanDef& sd, int h, int w, int sub420) {
-    const int side = sub420 ? 16 : 8;
-    const u64 nmcu = (u64)ceil_div(h, side) * (u64)ceil_div(w, side);
-    if (sd.comp < 0) return nmcu * (sub420 ? 6ull : 3ull);
+// items of a scan of an h x w crop
+static inline u64 scan_items(const ScanDef& sd, const Crop& c, int h, int w) {
+    if (sd.comp < 0) return c.blocks;
     if (sd.comp == 0) return (u64)ceil_div(h, 8) * (u64)ceil_div(w, 8);
-    return nmcu;                                             // chroma: ceil(ceil(w / 2) / 8) = ceil(w / 16)
+    return (u64)c.nmcu;                                      // chroma: ceil(ceil(w / 2) / 8) = ceil(w / 16)
 }
 
-// The table as the device reads it: [Consts][crops TileT n][jpeg_coef's chunks][streams TileT 10 n][chunks of the streams].
-struct Plan {
-    int rc;
-    int nt, ncc, ns, nc;          // crops, jpeg_coef's chunks, streams, chunks of the streams
-    u64 blocks, items;
-    size_t capacity, ubytes;
-    size_t o_crops, o_cchunks, o_streams, o_chunks, table_bytes;
+// The table as the device reads it: jpeg_u8.h's head [Consts][crops TileT n][jpeg_coef's chunks], then [streams TileT 10 n][chunks of
+// the streams]: a stream is a tile {first_chunk, block0 = first item, nmcu = items}, its chunks are {stream, item0, item1}.
+struct ProgPlan : CropPlan {
+    u64 items, per_items;         // of all streams; items per chunk (a stream's last chunk may have fewer)
+    size_t o_streams, o_chunks;
 };
-static Plan plan(const int* rects, int n_tiles, int quality, int sub420, int mcus_arg, int H, int W, std::vector<unsigned char>* table) {
-    Plan t{};
-    t.rc = CIAOSR_ERR_BAD_ARG;
-    if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || (sub420 != 0 && sub420 != 1)) return t;
-    const int per = mcus_arg > 0 ? mcus_arg : default_mcus(sub420);
-    const int bpm = sub420 ? 6 : 3, side = sub420 ? 16 : 8;
-    const u64 per_items = (u64)per * bpm;
-    u64 ncc = 0, nc = 0, blocks = 0, items = 0, bytes = 0;
-    bool too_many = false;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
-        if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
-        if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return t;
-        const u64 nmcu = (u64)ceil_div(h, side) * (u64)ceil_div(w, side);
-        ncc += (nmcu + per - 1) / per;
-        blocks += nmcu * bpm;
-        too_many = too_many || 64ull * nmcu * bpm >= kFreqLimit;
-        for (int s = 0; s < kScans; ++s) {
-            const u64 n = scan_items(kScript[s], h, w, sub420);
-            items += n;
-            nc += (n + per_items - 1) / per_items;
-            bytes += (item_bits(kScript[s]) * n + 7ull) / 8ull;
-        }
-    }
-    if (ncc + nc > (u64)INT_MAX / 2 || items > (u64)INT_MAX || (u64)n_tiles * kScans > (u64)INT_MAX / 2 || too_many) {
+static ProgPlan plan(const Request& r, std::vector<unsigned char>* table) {
+    ProgPlan t{};
+    if (r.mode == kModeGrey) {                              // no one-component progressive files
         t.rc = CIAOSR_ERR_UNSUPPORTED;
         return t;
     }
-    t.rc = CIAOSR_OK;
-    t.nt = n_tiles;
-    t.ncc = (int)ncc;
-    t.ns = n_tiles * kScans;
-    t.nc = (int)nc;
-    t.blocks = blocks;
-    t.items = items;
-    t.capacity = (size_t)(2 * bytes);
-    t.ubytes = (size_t)bytes + 4 * (size_t)t.ns;
-    t.o_crops = sizeof(Consts);
-    t.o_cchunks = t.o_crops + sizeof(TileT) * (size_t)n_tiles;
-    t.o_streams = t.o_cchunks + sizeof(ChunkT) * (size_t)ncc;
+    u64 nc = 0, bytes = 0;
+    t.per_items = (u64)chunk_mcus(r.mcus, r.mode) * (u64)blocks_per_mcu(r.mode);
+    plan_crops(r, true, &t, [&](const Crop& c, int h, int w) {
+        for (int s = 0; s < kScans; ++s) {
+            const u64 n = scan_items(kScript[s], c, h, w);
+            t.items += n;
+            nc += (n + t.per_items - 1) / t.per_items;
+            bytes += (item_bits(kScript[s]) * n + 7ull) / 8ull;
+        }
+    });
+    if (t.rc == CIAOSR_ERR_BAD_ARG) return t;
+    if ((u64)t.ncc + nc > (u64)INT_MAX / 2 || t.items > (u64)INT_MAX || (u64)r.n * kScans > (u64)INT_MAX / 2) t.rc = CIAOSR_ERR_UNSUPPORTED;
+    if (t.rc != CIAOSR_OK) return t;
+    plan_streams(&t, (u64)r.n * kScans, nc, bytes);
+    t.o_streams = t.table_bytes;
     t.o_chunks = t.o_streams + sizeof(TileT) * (size_t)t.ns;
     t.table_bytes = t.o_chunks + sizeof(ChunkT) * (size_t)nc;
     if (!table) return t;
     table->resize(t.table_bytes);
-    make_consts(quality, reinterpret_cast<Consts*>(table->data()));
-    TileT* crops = reinterpret_cast<TileT*>(table->data() + t.o_crops);
-    ChunkT* cchunks = reinterpret_cast<ChunkT*>(table->data() + t.o_cchunks);
+    fill_crops(r, t, table->data());
     TileT* streams = reinterpret_cast<TileT*>(table->data() + t.o_streams);
     ChunkT* chunks = reinterpret_cast<ChunkT*>(table->data() + t.o_chunks);
-    u32 cc = 0, c = 0, blk = 0, item = 0;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int h = rects[4 * k + 2], w = rects[4 * k + 3];
-        const int mx = ceil_div(w, side), nmcu = mx * ceil_div(h, side);
-        crops[k] = TileT{rects[4 * k], rects[4 * k + 1], h, w, mx, nmcu, cc, blk};
-        for (int m = 0; m < nmcu; m += per, ++cc) cchunks[cc] = ChunkT{k, m, m + per < nmcu ? m + per : nmcu, 0};
-        blk += (u32)nmcu * (u32)bpm;
+    u32 c = 0, item = 0;
+    for (int k = 0; k < r.n; ++k) {
+        const int* rect = r.rects + 4 * k;
+        Crop g;
+        crop_of(rect, t.mode, 0, 0, false, &g);
         for (int s = 0; s < kScans; ++s) {
-            const u64 n = scan_items(kScript[s], h, w, sub420);
+            const u64 n = scan_items(kScript[s], g, rect[2], rect[3]);
             streams[k * kScans + s] = TileT{0, 0, 0, 0, 0, (int)n, c, item};
-            for (u64 i = 0; i < n; i += per_items, ++c)
-                chunks[c] = ChunkT{k * kScans + s, (int)i, (int)(i + per_items < n ? i + per_items : n), 0};
+            for (u64 i = 0; i < n; i += t.per_items, ++c)
+                chunks[c] = ChunkT{k * kScans + s, (int)i, (int)(i + t.per_items < n ? i + t.per_items : n), 0};
             item += (u32)n;
         }
     }
     return t;
 }
 
-struct Work {
-    unsigned char *table, *summary;
-    short* coef;
-    u32 *block_bits, *chunk_pad, *ubuf, *zeroed, *rstart, *cboff, *codes, *chunk_empty;
-    u64 *corr_pos, *chunk_bits, *chunk_sum, *chunk_bitoff, *chunk_b0, *chunk_b1, *chunk_out, *tile_ubase, *utotal;
+struct ProgWork {
+    StreamWork s;
+    unsigned char* summary;
+    u32 *block_bits, *zeroed, *rstart, *cboff, *codes, *chunk_empty;
+    u64* corr_pos;
     size_t zeroed_words;          // the histograms, pre and post: one memset
+    void carve(Arena& a, const ProgPlan& t) {
+        const size_t items = (size_t)t.items;
+        s.carve_head(a, t);
+        block_bits = a.take<u32>(items);
+        summary = a.take<unsigned char>(items);
+        zeroed_words = (size_t)t.ns * 256 + 2 * items;
+        zeroed = a.take<u32>(zeroed_words);
+        rstart = a.take<u32>(items);
+        cboff = a.take<u32>(items);
+        corr_pos = a.take<u64>(items);
+        codes = a.take<u32>((size_t)t.ns * 256);
+        chunk_empty = a.take<u32>((size_t)t.nc);
+        s.carve_streams(a, t);
+    }
 };
-static inline bool carve(void* ws, size_t bytes, const Plan& t, Work* w, size_t* used) {
-    Arena a(ws, bytes);
-    const size_t nc = (size_t)t.nc, items = (size_t)t.items;
-    w->table = a.take<unsigned char>(t.table_bytes);
-    w->coef = a.take<short>(64 * (size_t)t.blocks);
-    w->block_bits = a.take<u32>(items);
-    w->summary = a.take<unsigned char>(items);
-    w->zeroed_words = (size_t)t.ns * 256 + 2 * items;
-    w->zeroed = a.take<u32>(w->zeroed_words);
-    w->rstart = a.take<u32>(items);
-    w->cboff = a.take<u32>(items);
-    w->corr_pos = a.take<u64>(items);
-    w->codes = a.take<u32>((size_t)t.ns * 256);
-    w->chunk_pad = a.take<u32>(nc);
-    w->chunk_empty = a.take<u32>(nc);
-    w->chunk_bits = a.take<u64>(nc);
-    w->chunk_sum = a.take<u64>(nc + 1);
-    w->chunk_bitoff = a.take<u64>(nc);
-    w->chunk_b0 = a.take<u64>(nc);
-    w->chunk_b1 = a.take<u64>(nc);
-    w->chunk_out = a.take<u64>(nc + 1);
-    w->tile_ubase = a.take<u64>((size_t)t.ns);
-    w->utotal = a.take<u64>(1);
-    w->ubuf = a.take<u32>((t.ubytes + 3) / 4);
-    if (used) *used = a.off;
-    return a.ok;
-}
-static inline size_t work_bytes(const Plan& t) {
-    Work w;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve(origin, ~(size_t)0, t, &w, &used);
-    return used;
-}
 
-template <typename K>
-static int launch(const char* tag, K kernel, int grid, const PParams& p, hipStream_t s) {
-    ProfScope prof(tag, s);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, p);
-    return launch_status(tag);
-}
-
-// every check that the host can make comes before the first launch
-static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int sub420,
-                  int mcus, unsigned char* out, size_t out_capacity, u64* offs /* [10 n + 1] */, unsigned char* dht /* [n][10][kDhtRecord] */,
+static int encode(const Request& r, unsigned char* out, size_t out_capacity, u64* offs /* [10 n + 1] */, unsigned char* dht /* [n][10][kDhtRecord] */,
                   void* workspace, size_t workspace_bytes, hipStream_t s) {
     std::vector<unsigned char> table;
-    const Plan t = plan(rects, n_tiles, quality, sub420, mcus, H, W, &table);
-    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);
-    if (t.rc != CIAOSR_OK) return t.rc;
-    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
-    Work w;
-    if (workspace_bytes < work_bytes(t) || !carve(workspace, workspace_bytes, t, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
-    if (hipMemcpyAsync(w.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    Params c{};                                              // jpeg_coef: the crops and their chunks of MCUs
-    c.src = src;
-    c.pitch = pitch;
-    c.bgr = bgr;
-    c.sub420 = sub420;
-    c.nt = t.nt;
-    c.nc = t.ncc;
-    c.consts = reinterpret_cast<const Consts*>(w.table);
-    c.tiles = reinterpret_cast<const TileT*>(w.table + t.o_crops);
-    c.chunks = reinterpret_cast<const ChunkT*>(w.table + t.o_cchunks);
-    c.coef = w.coef;
+    const ProgPlan t = plan(r, &table);
+    ProgWork w;
+    int rc;
+    if ((rc = prepare(t, table, out_capacity, workspace, workspace_bytes, s, &w))) return rc;
+    const Params c = w.s.coef_params(r, t);                  // jpeg_coef: the crops and their chunks of MCUs
     PParams p{};
     p.b = c;                                                 // everything behind it: the streams and their chunks of items
     p.b.nt = t.ns;
     p.b.nc = t.nc;
-    p.b.tiles = reinterpret_cast<const TileT*>(w.table + t.o_streams);
-    p.b.chunks = reinterpret_cast<const ChunkT*>(w.table + t.o_chunks);
+    p.b.tiles = reinterpret_cast<const TileT*>(w.s.table + t.o_streams);
+    p.b.chunks = reinterpret_cast<const ChunkT*>(w.s.table + t.o_chunks);
+    w.s.bind_streams(&p.b);
     p.b.block_bits = w.block_bits;
-    p.b.chunk_bits = w.chunk_bits;
-    p.b.chunk_sum = w.chunk_sum;
-    p.b.chunk_bitoff = w.chunk_bitoff;
-    p.b.chunk_b0 = w.chunk_b0;
-    p.b.chunk_b1 = w.chunk_b1;
-    p.b.chunk_pad = w.chunk_pad;
-    p.b.chunk_out = w.chunk_out;
-    p.b.tile_ubase = w.tile_ubase;
-    p.b.utotal = w.utotal;
-    p.b.ubuf = w.ubuf;
     p.b.out = out;
     p.b.tile_offs = offs;
     p.crops = c.tiles;
     p.summary = w.summary;
     p.chunk_empty = w.chunk_empty;
-    p.per_items = (u32)(mcus > 0 ? mcus : default_mcus(sub420)) * (sub420 ? 6u : 3u);
+    p.per_items = (u32)t.per_items;
     p.hist = w.zeroed;
     p.pre = w.zeroed + (size_t)t.ns * 256;
     p.post = p.pre + (size_t)t.items;
@@ -647,23 +569,18 @@ static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr,
     p.codes = w.codes;
     p.dht = dht;
     p.ntables = t.ns;
-    int rc;
     // the workspace holds what the last call left: the histograms and the flush marks start from zero in every call
     if (hipMemsetAsync(w.zeroed, 0, sizeof(u32) * w.zeroed_words, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    if ((rc = launch_shared(kCoefKernel, t.ncc, c, s))) return rc;
+    if ((rc = launch_coef(c, s))) return rc;
     if ((rc = launch("prog_summary", prog_summary_kernel, t.nc, p, s))) return rc;
     if ((rc = launch("prog_runs", prog_runs_kernel, t.nc, p, s))) return rc;
     if ((rc = launch("prog_hist", prog_hist_kernel, t.nc, p, s))) return rc;
     if ((rc = launch("prog_tables", prog_tables_kernel, (t.ns + kWaves - 1) / kWaves, p, s))) return rc;
     if ((rc = launch("prog_count", prog_count_kernel, t.nc, p, s))) return rc;
-    if ((rc = launch_shared(kScanKernel, 1, p.b, s))) return rc;
-    const u64 zero_groups = (t.ubytes / 4 + kThreads - 1) / kThreads;
-    if ((rc = launch_shared(kZeroKernel, (int)(zero_groups < (u64)kZeroGroups ? zero_groups : (u64)kZeroGroups), p.b, s))) return rc;
+    if ((rc = launch_scan_zero(p.b, t.ubytes, s))) return rc;
     if ((rc = launch("prog_pack", prog_pack_kernel, t.nc, p, s))) return rc;
     if ((rc = launch("prog_corr", prog_corr_kernel, t.nc, p, s))) return rc;
-    if ((rc = launch_shared(kFfcountKernel, t.nc, p.b, s))) return rc;
-    if ((rc = launch_shared(kScan2Kernel, 1, p.b, s))) return rc;
-    return launch_shared(kStuffKernel, t.nc, p.b, s);
+    return launch_stuff(p.b, s);
 }
 
 }  // namespace jpeg
@@ -675,44 +592,34 @@ using namespace ciaosr::jpeg;
 extern "C" size_t ciaosr_jpeg_prog_result_bytes(int n_tiles) {
     return n_tiles < 1 ? 0 : 8 * ((size_t)kScans * n_tiles + 1) + (size_t)kScans * kDhtRecord * (size_t)n_tiles;
 }
-
 extern "C" size_t ciaosr_jpeg_prog_tiles_workspace_bytes(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? work_bytes(t) : 0;
+    return work_bytes<ProgWork>(plan(size_request(rects, n_tiles, subsampling, mcus_per_chunk), nullptr));
 }
-
 extern "C" size_t ciaosr_jpeg_prog_tiles_capacity_bytes(const int* rects, int n_tiles, int subsampling) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), 0, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? t.capacity : 0;
+    return plan(size_request(rects, n_tiles, subsampling, 0), nullptr).capacity;
 }
-
 extern "C" size_t ciaosr_jpeg_prog_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_prog_tiles_workspace_bytes(rect, 1, subsampling, mcus_per_chunk);
+    return ciaosr_jpeg_prog_tiles_workspace_bytes(Whole(H, W).rect, 1, subsampling, mcus_per_chunk);
 }
-
 extern "C" size_t ciaosr_jpeg_prog_capacity_bytes(int H, int W, int subsampling) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_prog_tiles_capacity_bytes(rect, 1, subsampling);
+    return ciaosr_jpeg_prog_tiles_capacity_bytes(Whole(H, W).rect, 1, subsampling);
 }
 
 extern "C" int ciaosr_jpeg_prog_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                                 int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                                 void* result, void* workspace, size_t workspace_bytes, void* stream) {
-    if (subsampling == CIAOSR_JPEG_GREY) return CIAOSR_ERR_UNSUPPORTED;      // no one-component progressive files
-    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= 3 * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(subsampling == CIAOSR_JPEG_444 || subsampling == CIAOSR_JPEG_420);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(result) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    if (subsampling == CIAOSR_JPEG_GREY) return CIAOSR_ERR_UNSUPPORTED;      // refused before the arguments are looked at, as the plan would
+    Request r;
+    if (const int rc = checked_request(src, pitch, H, W, bgr, rects, n_tiles, quality, subsampling, mcus_per_chunk, out, result, workspace, &r))
+        return rc;
     u64* offs = static_cast<u64*>(result);
-    return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, offs,
-                  reinterpret_cast<unsigned char*>(offs + (size_t)kScans * n_tiles + 1), workspace, workspace_bytes, (hipStream_t)stream);
+    return encode(r, out, out_capacity, offs, reinterpret_cast<unsigned char*>(offs + (size_t)kScans * n_tiles + 1), workspace, workspace_bytes,
+                  (hipStream_t)stream);
 }
 
 extern "C" int ciaosr_jpeg_prog_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
                                           int mcus_per_chunk, unsigned char* out, size_t out_capacity, void* result, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_prog_encode_tiles_u8(src, pitch, H, W, bgr, rect, 1, quality, subsampling, mcus_per_chunk, out, out_capacity, result,
+    return ciaosr_jpeg_prog_encode_tiles_u8(src, pitch, H, W, bgr, Whole(H, W).rect, 1, quality, subsampling, mcus_per_chunk, out, out_capacity, result,
                                             workspace, workspace_bytes, stream);
 }

@@ -1,7 +1,12 @@
 // What the JPEG translation units share (jpeg_u8.hip: baseline and optimised files; jpeg_prog_u8.hip: progressive files): the table
-// that the host uploads, the kernels' parameter block, the workgroup sums and scans, libjpeg's table construction for one wave, and
-// the launchers of the kernels of jpeg_u8.hip that the progressive path runs unchanged.
+// that the host uploads, the kernels' parameter block, the host's parts of a call (request and argument check, crop geometry, the
+// plan's common half, the stream workspace, work_bytes, launch, the driver's prologue and the launchers of the kernels of jpeg_u8.hip
+// that the progressive path runs unchanged), the workgroup sums and scans, and libjpeg's table construction for one wave.
 #pragma once
+#include <climits>
+#include <cstdint>
+#include <vector>
+
 #include "ops.h"
 
 namespace ciaosr {
@@ -63,19 +68,214 @@ struct Params {
 // jpeg_u8.hip: the constants of a quality, and its kernels that every kind of file runs.  To jpeg_scan, jpeg_zero, jpeg_ffcount,
 // jpeg_scan2 and jpeg_stuff a "tile" is one padded stream of the output and a chunk a run of blocks whose bits chunk_bits holds.
 void make_consts(int quality, Consts* c);
-enum Shared { kCoefKernel, kScanKernel, kZeroKernel, kFfcountKernel, kScan2Kernel, kStuffKernel };
-int launch_shared(Shared which, int grid, const Params& p, hipStream_t s);
-constexpr int kZeroGroups = 1024;
+int launch_coef(const Params& p, hipStream_t s);                           // jpeg_coef, one workgroup per chunk of p
+int launch_scan_zero(const Params& p, size_t ubytes, hipStream_t s);       // jpeg_scan, jpeg_zero: the counted bits -> the places, a zeroed buffer
+int launch_stuff(const Params& p, hipStream_t s);                          // jpeg_ffcount, jpeg_scan2, jpeg_stuff: the packed streams -> the output
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
-// the scan's layout as the plans name it (`sub420` where only the first two can occur)
+// the scan's layout as the plans name it
 enum { kMode444 = 0, kMode420 = 1, kModeGrey = 2 };
 static inline int default_mcus(int mode) { return mode == kModeGrey ? 768 : (mode ? 128 : 256); }     // 768 blocks per chunk
+static inline int chunk_mcus(int mcus_arg, int mode) { return mcus_arg > 0 ? mcus_arg : default_mcus(mode); }
 // the ABI's subsampling code -> kMode444, kMode420, kModeGrey, -1 (unknown)
 static inline int sub_of(int subsampling) {
     return subsampling == CIAOSR_JPEG_444 ? kMode444 : (subsampling == CIAOSR_JPEG_420 ? kMode420 : (subsampling == CIAOSR_JPEG_GREY ? kModeGrey : -1));
 }
 static inline int blocks_per_mcu(int mode) { return mode == kModeGrey ? 1 : (mode ? 6 : 3); }
+// bytes per pixel of the source that the ABI's subsampling code names
+static inline size_t source_bytes(int subsampling) { return subsampling == CIAOSR_JPEG_GREY ? 1 : 3; }
+
+// ---- the host's parts: what a call asks for, the crops' geometry, the workspace of the streams, the driver's prologue ---------------
+struct Request {
+    const unsigned char* src;
+    size_t pitch;
+    int H, W, bgr;                // H, W <= 0: the rects are not held against an image
+    const int* rects;             // [n][4]: y0, x0, h, w
+    int n, quality, mode, mcus;   // mode: kMode*, or -1; mcus: MCUs per chunk, 0 = default_mcus
+};
+// the H x W image as a rect list of one: the H x W forms of the entries forward to the rect forms
+struct Whole {
+    int rect[4];
+    Whole(int H, int W) : rect{0, 0, H, W} {}
+};
+// what a size export plans: the geometry alone
+static inline Request size_request(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
+    return Request{nullptr, 0, 0, 0, 0, rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk};
+}
+// The argument check of every *_encode_tiles_u8 entry (`result`: where the offsets go), then the request.
+static inline int checked_request(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality,
+                                  int subsampling, int mcus_per_chunk, const void* out, const void* result, const void* workspace, Request* r) {
+    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
+    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
+    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
+    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(result) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    *r = Request{src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk};
+    return CIAOSR_OK;
+}
+
+// One rect in a mode.  CIAOSR_ERR_BAD_ARG: it is empty, too large or leaves the image; CIAOSR_ERR_UNSUPPORTED (`limited` only): its scan
+// reaches the frequency limit.
+struct Crop {
+    int side, mx, nmcu;           // the MCU's side, MCUs per row, MCUs
+    u64 blocks;
+};
+static inline int crop_of(const int* rect, int mode, int H, int W, bool limited, Crop* c) {
+    const int y0 = rect[0], x0 = rect[1], h = rect[2], w = rect[3];
+    if (!image_ok(h, w) || y0 < 0 || x0 < 0) return CIAOSR_ERR_BAD_ARG;
+    if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return CIAOSR_ERR_BAD_ARG;
+    c->side = mode == kMode420 ? 16 : 8;
+    c->mx = ceil_div(w, c->side);
+    c->nmcu = c->mx * ceil_div(h, c->side);
+    c->blocks = (u64)c->nmcu * (u64)blocks_per_mcu(mode);
+    return limited && 64ull * c->blocks >= kFreqLimit ? CIAOSR_ERR_UNSUPPORTED : CIAOSR_OK;
+}
+
+// What every plan holds.  The table as the device reads it begins [Consts][crops TileT nt][jpeg_coef's chunks ChunkT ncc]; a stream is
+// one padded run of the output (baseline and optimised: a crop's scan, so ns = nt and nc = ncc; progressive: one of its ten scans).
+struct CropPlan {
+    int rc;                       // CIAOSR_OK, or why the rects cannot be coded
+    int mode, per;                // kMode*; MCUs per chunk of jpeg_coef
+    int nt, ncc, ns, nc;          // crops, jpeg_coef's chunks, streams, chunks of the streams
+    u64 blocks;
+    size_t capacity, ubytes;      // the stuffed worst case; the unstuffed one, every stream rounded up to 4 bytes
+    size_t o_crops, o_cchunks, table_bytes;
+};
+// Validates the request and every rect, sums the crops; each(crop, h, w) adds what the caller sums besides.  A bad argument wins over a
+// refusal.  Leaves table_bytes at the end of jpeg_coef's chunks.
+template <typename F>
+static inline void plan_crops(const Request& r, bool limited, CropPlan* t, F each) {
+    t->rc = CIAOSR_ERR_BAD_ARG;
+    if (!r.rects || r.n < 1 || r.mcus < 0 || r.quality < 1 || r.quality > 100 || r.mode < kMode444 || r.mode > kModeGrey) return;
+    t->mode = r.mode;
+    t->per = chunk_mcus(r.mcus, r.mode);
+    u64 ncc = 0;
+    int rc = CIAOSR_OK;
+    for (int k = 0; k < r.n; ++k) {
+        Crop c;
+        const int one = crop_of(r.rects + 4 * k, r.mode, r.H, r.W, limited, &c);
+        if (one == CIAOSR_ERR_BAD_ARG) return;
+        if (one != CIAOSR_OK) rc = one;
+        ncc += ((u64)c.nmcu + t->per - 1) / t->per;
+        t->blocks += c.blocks;
+        each(c, r.rects[4 * k + 2], r.rects[4 * k + 3]);
+    }
+    if (ncc > (u64)INT_MAX / 2 || t->blocks > (u64)INT_MAX) rc = CIAOSR_ERR_UNSUPPORTED;
+    t->rc = rc;
+    t->nt = r.n;
+    t->ncc = (int)ncc;
+    t->o_crops = sizeof(Consts);
+    t->o_cchunks = t->o_crops + sizeof(TileT) * (size_t)r.n;
+    t->table_bytes = t->o_cchunks + sizeof(ChunkT) * (size_t)ncc;
+}
+// the streams of an accepted plan: `bytes` = the most that all of them hold before stuffing
+static inline void plan_streams(CropPlan* t, u64 ns, u64 nc, u64 bytes) {
+    t->ns = (int)ns;
+    t->nc = (int)nc;
+    t->capacity = (size_t)(2 * bytes);
+    t->ubytes = (size_t)bytes + 4 * (size_t)ns;
+}
+// the head of the table: the constants of the quality, the crops, jpeg_coef's chunks of `per` MCUs of ONE crop each
+static inline void fill_crops(const Request& r, const CropPlan& t, unsigned char* table) {
+    make_consts(r.quality, reinterpret_cast<Consts*>(table));
+    TileT* tiles = reinterpret_cast<TileT*>(table + t.o_crops);
+    ChunkT* chunks = reinterpret_cast<ChunkT*>(table + t.o_cchunks);
+    u32 c = 0, blk = 0;
+    for (int k = 0; k < r.n; ++k) {
+        const int* rect = r.rects + 4 * k;
+        Crop g;
+        crop_of(rect, t.mode, 0, 0, false, &g);
+        tiles[k] = TileT{rect[0], rect[1], rect[2], rect[3], g.mx, g.nmcu, c, blk};
+        for (int m = 0; m < g.nmcu; m += t.per, ++c) chunks[c] = ChunkT{k, m, m + t.per < g.nmcu ? m + t.per : g.nmcu, 0};
+        blk += (u32)g.blocks;
+    }
+}
+
+// The arrays that both coders carve: the table, the coefficients, and what jpeg_scan .. jpeg_stuff keep per chunk and stream.  ubuf is
+// the last take (Arena::take aligns before a take and does not round the last one: what follows it decides the exported size).
+struct StreamWork {
+    unsigned char* table;
+    short* coef;
+    u32 *chunk_pad, *ubuf;
+    u64 *chunk_bits, *chunk_sum, *chunk_bitoff, *chunk_b0, *chunk_b1, *chunk_out, *tile_ubase, *utotal;
+    void carve_head(Arena& a, const CropPlan& t) {
+        table = a.take<unsigned char>(t.table_bytes);
+        coef = a.take<short>(64 * (size_t)t.blocks);
+    }
+    void carve_streams(Arena& a, const CropPlan& t) {
+        const size_t nc = (size_t)t.nc;
+        chunk_pad = a.take<u32>(nc);
+        chunk_bits = a.take<u64>(nc);
+        chunk_sum = a.take<u64>(nc + 1);
+        chunk_bitoff = a.take<u64>(nc);
+        chunk_b0 = a.take<u64>(nc);
+        chunk_b1 = a.take<u64>(nc);
+        chunk_out = a.take<u64>(nc + 1);
+        tile_ubase = a.take<u64>((size_t)t.ns);
+        utotal = a.take<u64>(1);
+        ubuf = a.take<u32>((t.ubytes + 3) / 4);
+    }
+    // jpeg_coef's parameters: the crops and their chunks of MCUs
+    Params coef_params(const Request& r, const CropPlan& t) const {
+        Params p{};
+        p.src = r.src;
+        p.pitch = r.pitch;
+        p.bgr = r.bgr;
+        p.sub420 = t.mode == kMode420;
+        p.grey = t.mode == kModeGrey;
+        p.nt = t.nt;
+        p.nc = t.ncc;
+        p.consts = reinterpret_cast<const Consts*>(table);
+        p.tiles = reinterpret_cast<const TileT*>(table + t.o_crops);
+        p.chunks = reinterpret_cast<const ChunkT*>(table + t.o_cchunks);
+        p.coef = coef;
+        return p;
+    }
+    void bind_streams(Params* p) const {
+        p->chunk_bits = chunk_bits;
+        p->chunk_sum = chunk_sum;
+        p->chunk_bitoff = chunk_bitoff;
+        p->chunk_b0 = chunk_b0;
+        p->chunk_b1 = chunk_b1;
+        p->chunk_pad = chunk_pad;
+        p->chunk_out = chunk_out;
+        p->tile_ubase = tile_ubase;
+        p->utotal = utotal;
+        p->ubuf = ubuf;
+    }
+};
+
+// W: a coder's workspace, with carve(Arena&, const P&) over its plan P.  Offsets only: nothing is dereferenced.
+template <typename W, typename P>
+static inline size_t work_bytes(const P& t) {
+    if (t.rc != CIAOSR_OK) return 0;
+    static char origin[1];
+    Arena a(origin, ~(size_t)0);
+    W w;
+    w.carve(a, t);
+    return a.off;
+}
+
+template <typename K, typename P>
+static inline int launch(const char* tag, K kernel, int grid, const P& p, hipStream_t s) {
+    ProfScope prof(tag, s);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, p);
+    return launch_status(tag);
+}
+
+// The driver's prologue, every check that the host can make before the first launch: a bad argument, another refusal of the plan, the
+// output's capacity, the workspace's size; then the carve and the table's upload.
+template <typename W, typename P>
+static inline int prepare(const P& t, const std::vector<unsigned char>& table, size_t out_capacity, void* workspace, size_t workspace_bytes,
+                          hipStream_t s, W* w) {
+    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image; quality; subsampling
+    if (t.rc != CIAOSR_OK) return t.rc;
+    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
+    Arena a(workspace, workspace_bytes);
+    w->carve(a, t);
+    if (!a.ok) return CIAOSR_ERR_WORKSPACE;
+    // from pageable memory: the copy has left `table` when the call returns
+    return hipMemcpyAsync(w->s.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) == hipSuccess ? CIAOSR_OK : CIAOSR_ERR_LAUNCH;
+}
 
 // ---- device helpers --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {

@@ -29,6 +29,8 @@
 //                index) with a pseudo-symbol that reserves the all-ones code, limit the lengths to 16, order the symbols by the
 //                size they had BEFORE limiting -- gives the DHT record for the host and the length << 16 | code table for the scan.
 // No floating point anywhere; the bytes do not depend on mcus_per_chunk, on the stream or on what else is in the list.
+// The host's parts of a call (request and argument check, crop geometry, stream workspace, prologue, launch) are jpeg_u8.h's, shared with
+// jpeg_prog_u8.hip; this unit adds its Plan and Work, and defines the launchers of the kernels that every kind of file runs.
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -542,193 +544,90 @@ __global__ __launch_bounds__(kThreads) void jpeg_stuff_kernel(Params p) {
     }
 }
 
+// ---- the kernels that every kind of file runs (declared in jpeg_u8.h) ----------------------------------------------------------------
+constexpr int kZeroGroups = 1024;
+
+int launch_coef(const Params& p, hipStream_t s) { return launch("jpeg_coef", jpeg_coef_kernel, p.nc, p, s); }
+
+int launch_scan_zero(const Params& p, size_t ubytes, hipStream_t s) {
+    if (const int rc = launch("jpeg_scan", jpeg_scan_kernel, 1, p, s)) return rc;
+    const u64 zero_groups = (ubytes / 4 + kThreads - 1) / kThreads;
+    return launch("jpeg_zero", jpeg_zero_kernel, (int)(zero_groups < (u64)kZeroGroups ? zero_groups : (u64)kZeroGroups), p, s);
+}
+
+int launch_stuff(const Params& p, hipStream_t s) {
+    int rc;
+    if ((rc = launch("jpeg_ffcount", jpeg_ffcount_kernel, p.nc, p, s))) return rc;
+    if ((rc = launch("jpeg_scan2", jpeg_scan2_kernel, 1, p, s))) return rc;
+    return launch("jpeg_stuff", jpeg_stuff_kernel, p.nc, p, s);
+}
+
 // ---- the host's plan -------------------------------------------------------------------------------------------------------------
 
-// The table as the device reads it, one block of memory: [Consts][tiles TileT nt][chunks ChunkT nc].
-struct Plan {
-    int rc;                       // CIAOSR_OK, or why the rects cannot be coded
-    int nt, nc;
-    bool opt;                     // optimised Huffman tables
-    u64 blocks;
-    size_t capacity;              // the stuffed worst case: 2 x 208 bytes per block (optimised: 2 x ceil(1665 x blocks / 8) per tile)
-    size_t ubytes;                // the unstuffed worst case, every tile rounded up to 4 bytes
-    size_t o_tiles, o_chunks, table_bytes;
+// A crop is one stream; the table is jpeg_u8.h's head and nothing more.  The stuffed worst case: 2 x 208 bytes per block (optimised:
+// 2 x ceil(1665 x blocks / 8) per crop).  `table` (optional) receives the table's bytes.
+struct Plan : CropPlan {
+    bool opt;                     // optimised Huffman tables: a crop at the frequency limit is refused
 };
-// `table` (optional) receives the table's bytes.  H, W <= 0: the rects are not held against an image.
-static Plan plan(const int* rects, int n_tiles, int quality, int mode, int mcus_arg, int H, int W, std::vector<unsigned char>* table,
-                 bool opt = false) {
+static Plan plan(const Request& r, bool opt, std::vector<unsigned char>* table) {
     Plan t{};
     t.opt = opt;
-    t.rc = CIAOSR_ERR_BAD_ARG;
-    if (!rects || n_tiles < 1 || mcus_arg < 0 || quality < 1 || quality > 100 || mode < kMode444 || mode > kModeGrey) return t;
-    const int per = mcus_arg > 0 ? mcus_arg : default_mcus(mode);
-    const int bpm = blocks_per_mcu(mode), side = mode == kMode420 ? 16 : 8;
-    u64 nc = 0, blocks = 0, opt_bytes = 0;
-    bool too_many = false;                                  // optimised: a crop at the frequency limit
-    for (int k = 0; k < n_tiles; ++k) {
-        const int y0 = rects[4 * k], x0 = rects[4 * k + 1], h = rects[4 * k + 2], w = rects[4 * k + 3];
-        if (!image_ok(h, w) || y0 < 0 || x0 < 0) return t;
-        if (H > 0 && ((long)y0 + h > H || (long)x0 + w > W)) return t;
-        const u64 nmcu = (u64)ceil_div(h, side) * (u64)ceil_div(w, side);
-        nc += (nmcu + per - 1) / per;
-        blocks += nmcu * bpm;
-        too_many = too_many || 64ull * nmcu * bpm >= kFreqLimit;
-        opt_bytes += (kOptBlockBits * nmcu * bpm + 7ull) / 8ull;
-    }
-    if (nc > (u64)INT_MAX / 2 || blocks > (u64)INT_MAX || (opt && too_many)) {
-        t.rc = CIAOSR_ERR_UNSUPPORTED;
-        return t;
-    }
-    t.rc = CIAOSR_OK;
-    t.nt = n_tiles;
-    t.nc = (int)nc;
-    t.blocks = blocks;
-    t.capacity = (size_t)(2 * kBlockBytes * blocks);
-    t.ubytes = (size_t)(kBlockBytes * blocks) + 4 * (size_t)n_tiles;
-    if (opt) {
-        t.capacity = (size_t)(2 * opt_bytes);
-        t.ubytes = (size_t)opt_bytes + 4 * (size_t)n_tiles;
-    }
-    t.o_tiles = sizeof(Consts);
-    t.o_chunks = t.o_tiles + sizeof(TileT) * (size_t)n_tiles;
-    t.table_bytes = t.o_chunks + sizeof(ChunkT) * (size_t)nc;
+    u64 opt_bytes = 0;
+    plan_crops(r, opt, &t, [&](const Crop& c, int, int) { opt_bytes += (kOptBlockBits * c.blocks + 7ull) / 8ull; });
+    if (t.rc != CIAOSR_OK) return t;
+    plan_streams(&t, (u64)t.nt, (u64)t.ncc, opt ? opt_bytes : kBlockBytes * t.blocks);
     if (!table) return t;
     table->resize(t.table_bytes);
-    make_consts(quality, reinterpret_cast<Consts*>(table->data()));
-    TileT* tiles = reinterpret_cast<TileT*>(table->data() + t.o_tiles);
-    ChunkT* chunks = reinterpret_cast<ChunkT*>(table->data() + t.o_chunks);
-    u32 c = 0, blk = 0;
-    for (int k = 0; k < n_tiles; ++k) {
-        const int h = rects[4 * k + 2], w = rects[4 * k + 3];
-        const int mx = ceil_div(w, side), nmcu = mx * ceil_div(h, side);
-        tiles[k] = TileT{rects[4 * k], rects[4 * k + 1], h, w, mx, nmcu, c, blk};
-        for (int m = 0; m < nmcu; m += per, ++c) chunks[c] = ChunkT{k, m, m + per < nmcu ? m + per : nmcu, 0};
-        blk += (u32)nmcu * (u32)bpm;
-    }
+    fill_crops(r, t, table->data());
     return t;
 }
 
 struct Work {
-    unsigned char* table;
-    short* coef;
-    u32 *block_bits, *chunk_pad, *ubuf, *tile_hist, *tile_huff;
-    u64 *chunk_bits, *chunk_sum, *chunk_bitoff, *chunk_b0, *chunk_b1, *chunk_out, *tile_ubase, *utotal, *offs2;
+    StreamWork s;
+    u32 *block_bits, *tile_hist, *tile_huff;
+    u64* offs2;
+    void carve(Arena& a, const Plan& t) {
+        s.carve_head(a, t);
+        block_bits = a.take<u32>((size_t)t.blocks);
+        offs2 = a.take<u64>(2);
+        s.carve_streams(a, t);
+        tile_hist = tile_huff = nullptr;
+        if (t.opt) {
+            tile_hist = a.take<u32>((size_t)t.nt * kTables * 256);
+            tile_huff = a.take<u32>((size_t)t.nt * 2 * kHuff);
+        }
+    }
 };
-static inline bool carve(void* ws, size_t bytes, const Plan& t, Work* w, size_t* used) {
-    Arena a(ws, bytes);
-    const size_t nc = (size_t)t.nc;
-    w->table = a.take<unsigned char>(t.table_bytes);
-    w->coef = a.take<short>(64 * (size_t)t.blocks);
-    w->block_bits = a.take<u32>((size_t)t.blocks);
-    w->chunk_pad = a.take<u32>(nc);
-    w->chunk_bits = a.take<u64>(nc);
-    w->chunk_sum = a.take<u64>(nc + 1);
-    w->chunk_bitoff = a.take<u64>(nc);
-    w->chunk_b0 = a.take<u64>(nc);
-    w->chunk_b1 = a.take<u64>(nc);
-    w->chunk_out = a.take<u64>(nc + 1);
-    w->tile_ubase = a.take<u64>((size_t)t.nt);
-    w->utotal = a.take<u64>(1);
-    w->offs2 = a.take<u64>(2);
-    w->ubuf = a.take<u32>((t.ubytes + 3) / 4);
-    w->tile_hist = w->tile_huff = nullptr;
-    if (t.opt) {
-        w->tile_hist = a.take<u32>((size_t)t.nt * kTables * 256);
-        w->tile_huff = a.take<u32>((size_t)t.nt * 2 * kHuff);
-    }
-    if (used) *used = a.off;
-    return a.ok;
-}
-static inline size_t work_bytes(const Plan& t) {
-    Work w;
-    size_t used = 0;
-    static char origin[1];                                   // offsets only: nothing is dereferenced
-    carve(origin, ~(size_t)0, t, &w, &used);
-    return used;
-}
 
-template <typename K>
-static int launch(const char* tag, K kernel, int grid, const Params& p, hipStream_t s) {
-    ProfScope prof(tag, s);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, p);
-    return launch_status(tag);
-}
-
-int launch_shared(Shared which, int grid, const Params& p, hipStream_t s) {
-    switch (which) {
-        case kCoefKernel: return launch("jpeg_coef", jpeg_coef_kernel, grid, p, s);
-        case kScanKernel: return launch("jpeg_scan", jpeg_scan_kernel, grid, p, s);
-        case kZeroKernel: return launch("jpeg_zero", jpeg_zero_kernel, grid, p, s);
-        case kFfcountKernel: return launch("jpeg_ffcount", jpeg_ffcount_kernel, grid, p, s);
-        case kScan2Kernel: return launch("jpeg_scan2", jpeg_scan2_kernel, grid, p, s);
-        case kStuffKernel: return launch("jpeg_stuff", jpeg_stuff_kernel, grid, p, s);
-    }
-    return CIAOSR_ERR_BAD_ARG;
-}
-
-// every check that the host can make comes before the first launch
-static int encode(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles, int quality, int mode,
-                  int mcus, unsigned char* out, size_t out_capacity, u64* tile_offs, u64* total, void* workspace, size_t workspace_bytes,
-                  hipStream_t s, unsigned char* dht = nullptr /* optimised tables: [n_tiles][4][kDhtRecord] */) {
+// `dht`: optimised tables, [n][4][kDhtRecord]; null: the Annex K tables
+static int encode(const Request& r, unsigned char* out, size_t out_capacity, u64* tile_offs, u64* total, unsigned char* dht, void* workspace,
+                  size_t workspace_bytes, hipStream_t s) {
     std::vector<unsigned char> table;
-    const bool opt = dht != nullptr;
-    const Plan t = plan(rects, n_tiles, quality, mode, mcus, H, W, &table, opt);
-    CIAOSR_CHECK_ARG(t.rc != CIAOSR_ERR_BAD_ARG);             // a rect is empty or leaves the image; quality; subsampling
-    if (t.rc != CIAOSR_OK) return t.rc;
-    if (out_capacity < t.capacity) return CIAOSR_ERR_WORKSPACE;
+    const Plan t = plan(r, dht != nullptr, &table);
     Work w;
-    if (workspace_bytes < work_bytes(t) || !carve(workspace, workspace_bytes, t, &w, nullptr)) return CIAOSR_ERR_WORKSPACE;
-    // from pageable memory: the copy has left `table` when the call returns
-    if (hipMemcpyAsync(w.table, table.data(), t.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    Params p{};
-    p.src = src;
-    p.pitch = pitch;
-    p.bgr = bgr;
-    p.sub420 = mode == kMode420;
-    p.grey = mode == kModeGrey;
-    p.nt = t.nt;
-    p.nc = t.nc;
-    p.consts = reinterpret_cast<const Consts*>(w.table);
-    p.tiles = reinterpret_cast<const TileT*>(w.table + t.o_tiles);
-    p.chunks = reinterpret_cast<const ChunkT*>(w.table + t.o_chunks);
-    p.coef = w.coef;
+    int rc;
+    if ((rc = prepare(t, table, out_capacity, workspace, workspace_bytes, s, &w))) return rc;
+    Params p = w.s.coef_params(r, t);
+    w.s.bind_streams(&p);
     p.block_bits = w.block_bits;
-    p.chunk_bits = w.chunk_bits;
-    p.chunk_sum = w.chunk_sum;
-    p.chunk_bitoff = w.chunk_bitoff;
-    p.chunk_b0 = w.chunk_b0;
-    p.chunk_b1 = w.chunk_b1;
-    p.chunk_pad = w.chunk_pad;
-    p.chunk_out = w.chunk_out;
-    p.tile_ubase = w.tile_ubase;
-    p.utotal = w.utotal;
-    p.ubuf = w.ubuf;
     p.out = out;
     p.tile_offs = tile_offs ? tile_offs : w.offs2;
     p.total = total;
     p.tile_hist = w.tile_hist;
     p.tile_huff = w.tile_huff;
     p.dht = dht;
-    int rc;
     // the workspace holds what the last call left: the histograms start from zero in every call
-    if (opt && hipMemsetAsync(w.tile_hist, 0, sizeof(u32) * (size_t)t.nt * kTables * 256, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    if ((rc = launch("jpeg_coef", jpeg_coef_kernel, t.nc, p, s))) return rc;
-    if (opt) {
+    if (t.opt && hipMemsetAsync(w.tile_hist, 0, sizeof(u32) * (size_t)t.nt * kTables * 256, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
+    if ((rc = launch_coef(p, s))) return rc;
+    if (t.opt) {
         if ((rc = launch("jpeg_hist", jpeg_hist_kernel, t.nc, p, s))) return rc;
         if ((rc = launch("jpeg_tables", jpeg_tables_kernel, t.nt, p, s))) return rc;
     }
     if ((rc = launch("jpeg_count", jpeg_count_kernel, t.nc, p, s))) return rc;
-    if ((rc = launch("jpeg_scan", jpeg_scan_kernel, 1, p, s))) return rc;
-    const u64 zero_groups = (t.ubytes / 4 + kThreads - 1) / kThreads;
-    if ((rc = launch("jpeg_zero", jpeg_zero_kernel, (int)(zero_groups < (u64)kZeroGroups ? zero_groups : (u64)kZeroGroups), p, s))) return rc;
+    if ((rc = launch_scan_zero(p, t.ubytes, s))) return rc;
     if ((rc = launch("jpeg_pack", jpeg_pack_kernel, t.nc, p, s))) return rc;
-    if ((rc = launch("jpeg_ffcount", jpeg_ffcount_kernel, t.nc, p, s))) return rc;
-    if ((rc = launch("jpeg_scan2", jpeg_scan2_kernel, 1, p, s))) return rc;
-    return launch("jpeg_stuff", jpeg_stuff_kernel, t.nc, p, s);
+    return launch_stuff(p, s);
 }
-
-// bytes per pixel of the source that the ABI's subsampling code names
-static inline size_t source_bytes(int subsampling) { return subsampling == CIAOSR_JPEG_GREY ? 1 : 3; }
 
 }  // namespace jpeg
 }  // namespace ciaosr
@@ -737,89 +636,68 @@ using namespace ciaosr;
 using namespace ciaosr::jpeg;
 
 extern "C" size_t ciaosr_jpeg_tiles_workspace_bytes(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? work_bytes(t) : 0;
+    return work_bytes<Work>(plan(size_request(rects, n_tiles, subsampling, mcus_per_chunk), false, nullptr));
 }
-
 extern "C" size_t ciaosr_jpeg_tiles_capacity_bytes(const int* rects, int n_tiles, int subsampling) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), 0, 0, 0, nullptr);
-    return t.rc == CIAOSR_OK ? t.capacity : 0;
+    return plan(size_request(rects, n_tiles, subsampling, 0), false, nullptr).capacity;
 }
-
 extern "C" size_t ciaosr_jpeg_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_tiles_workspace_bytes(rect, 1, subsampling, mcus_per_chunk);
+    return ciaosr_jpeg_tiles_workspace_bytes(Whole(H, W).rect, 1, subsampling, mcus_per_chunk);
 }
-
 extern "C" size_t ciaosr_jpeg_capacity_bytes(int H, int W, int subsampling) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_tiles_capacity_bytes(rect, 1, subsampling);
+    return ciaosr_jpeg_tiles_capacity_bytes(Whole(H, W).rect, 1, subsampling);
 }
 
 extern "C" int ciaosr_jpeg_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                            int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                            unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && rects && out && tile_offs && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(tile_offs) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, tile_offs, nullptr,
-                  workspace, workspace_bytes, (hipStream_t)stream);
+    Request r;
+    if (const int rc = checked_request(src, pitch, H, W, bgr, rects, n_tiles, quality, subsampling, mcus_per_chunk, out, tile_offs, workspace, &r))
+        return rc;
+    return encode(r, out, out_capacity, tile_offs, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ciaosr_jpeg_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
                                      int mcus_per_chunk, unsigned char* out, size_t out_capacity, unsigned long long* total_bytes,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && out && total_bytes && workspace && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(total_bytes) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
-    const int rect[4] = {0, 0, H, W};
-    return encode(src, pitch, H, W, bgr, rect, 1, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, nullptr, total_bytes, workspace,
-                  workspace_bytes, (hipStream_t)stream);
+    const Whole whole(H, W);
+    Request r;
+    if (const int rc = checked_request(src, pitch, H, W, bgr, whole.rect, 1, quality, subsampling, mcus_per_chunk, out, total_bytes, workspace, &r))
+        return rc;
+    return encode(r, out, out_capacity, nullptr, total_bytes, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- optimised Huffman tables ---------------------------------------------------------------------------------------------------------
 extern "C" size_t ciaosr_jpeg_opt_result_bytes(int n_tiles) {
     return n_tiles < 1 ? 0 : 8 * ((size_t)n_tiles + 1) + (size_t)kTables * kDhtRecord * (size_t)n_tiles;
 }
-
 extern "C" size_t ciaosr_jpeg_opt_tiles_workspace_bytes(const int* rects, int n_tiles, int subsampling, int mcus_per_chunk) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), mcus_per_chunk, 0, 0, nullptr, true);
-    return t.rc == CIAOSR_OK ? work_bytes(t) : 0;
+    return work_bytes<Work>(plan(size_request(rects, n_tiles, subsampling, mcus_per_chunk), true, nullptr));
 }
-
 extern "C" size_t ciaosr_jpeg_opt_tiles_capacity_bytes(const int* rects, int n_tiles, int subsampling) {
-    const Plan t = plan(rects, n_tiles, 50, sub_of(subsampling), 0, 0, 0, nullptr, true);
-    return t.rc == CIAOSR_OK ? t.capacity : 0;
+    return plan(size_request(rects, n_tiles, subsampling, 0), true, nullptr).capacity;
 }
-
 extern "C" size_t ciaosr_jpeg_opt_workspace_bytes(int H, int W, int subsampling, int mcus_per_chunk) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_opt_tiles_workspace_bytes(rect, 1, subsampling, mcus_per_chunk);
+    return ciaosr_jpeg_opt_tiles_workspace_bytes(Whole(H, W).rect, 1, subsampling, mcus_per_chunk);
 }
-
 extern "C" size_t ciaosr_jpeg_opt_capacity_bytes(int H, int W, int subsampling) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_opt_tiles_capacity_bytes(rect, 1, subsampling);
+    return ciaosr_jpeg_opt_tiles_capacity_bytes(Whole(H, W).rect, 1, subsampling);
 }
 
 extern "C" int ciaosr_jpeg_opt_encode_tiles_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,
                                                int quality, int subsampling, int mcus_per_chunk, unsigned char* out, size_t out_capacity,
                                                void* result, void* workspace, size_t workspace_bytes, void* stream) {
-    CIAOSR_CHECK_ARG(src && rects && out && result && workspace && n_tiles > 0 && image_ok(H, W) && pitch >= source_bytes(subsampling) * (size_t)W);
-    CIAOSR_CHECK_ARG((bgr == 0 || bgr == 1) && mcus_per_chunk >= 0 && quality >= 1 && quality <= 100);
-    CIAOSR_CHECK_ARG(sub_of(subsampling) >= 0);
-    CIAOSR_CHECK_ARG((reinterpret_cast<uintptr_t>(result) & 7u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0);
+    Request r;
+    if (const int rc = checked_request(src, pitch, H, W, bgr, rects, n_tiles, quality, subsampling, mcus_per_chunk, out, result, workspace, &r))
+        return rc;
     u64* offs = static_cast<u64*>(result);
-    return encode(src, pitch, H, W, bgr, rects, n_tiles, quality, sub_of(subsampling), mcus_per_chunk, out, out_capacity, offs, nullptr, workspace,
-                  workspace_bytes, (hipStream_t)stream, reinterpret_cast<unsigned char*>(offs + n_tiles + 1));
+    return encode(r, out, out_capacity, offs, nullptr, reinterpret_cast<unsigned char*>(offs + n_tiles + 1), workspace, workspace_bytes,
+                  (hipStream_t)stream);
 }
 
 extern "C" int ciaosr_jpeg_opt_encode_u8(const unsigned char* src, size_t pitch, int H, int W, int bgr, int quality, int subsampling,
                                          int mcus_per_chunk, unsigned char* out, size_t out_capacity, void* result, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-    const int rect[4] = {0, 0, H, W};
-    return ciaosr_jpeg_opt_encode_tiles_u8(src, pitch, H, W, bgr, rect, 1, quality, subsampling, mcus_per_chunk, out, out_capacity, result,
+    return ciaosr_jpeg_opt_encode_tiles_u8(src, pitch, H, W, bgr, Whole(H, W).rect, 1, quality, subsampling, mcus_per_chunk, out, out_capacity, result,
                                            workspace, workspace_bytes, stream);
 }

@@ -20,7 +20,12 @@ the same two copies; `assemble_progressive` writes the SOF2 header and the DHT a
 A 2-D uint8 [H, W] image is a GREY image: the file is byte for byte `Image.fromarray(grey, 'L').save(format='JPEG', quality=q[,
 optimize=True])` -- one component, one DQT, two DHT (`header(..., grey=True)`); the device codes one block per MCU with the luma tables
 (CIAOSR_JPEG_GREY).  `subsampling` stays '444' (Pillow's '420' file of a grey image has other bytes) and there is no progressive form.
+
+The three kinds share one path: `kind_of` checks the two flags once per entry point and names the kind (the ABI's prefix, the streams
+and the DHT records per crop in a result); `_scans_device`, `_scans` and `_scan` do the device work for any kind, `_split` parses any
+result, `_dht` writes and validates every DHT segment and `_file` assembles the file.  Only the return shapes differ by flag.
 """
+import collections
 import ctypes as C
 import os
 import struct
@@ -148,6 +153,16 @@ def progressive_header(h, w, quality, subsampling):
     return _frame(h, w, quality, subsampling, b'\xff\xc2')
 
 
+def _dht(tc_th, table):
+    """The DHT segment of one (counts, symbols) pair under class << 4 | id; ValueError unless it is 16 counts and sum(counts) symbols."""
+    counts, vals = table
+    if len(counts) != 16 or len(vals) != sum(counts) or not 1 <= len(vals) <= 256:
+        raise ValueError('tables: (16 counts, sum(counts) symbols) pairs')
+    return b'\xff\xc4' + struct.pack('>HB', 19 + len(vals), tc_th) + bytes(counts) + bytes(vals)
+
+
+ANNEX_K_DHT = tuple(_dht(t[0], t[1:]) for t in HUFFMAN)     # the four DHT segments of a file without tables of its own
+
 def scan_header(s, tables):
     """What a progressive file holds in front of the entropy-coded data of scan s = 0..9: the DHT segments of the tables the scan is
     coded with (`tables`: the file's ten (counts, symbols) pairs in the order of PROGRESSIVE_TABLE_IDS), then the SOS header."""
@@ -158,12 +173,7 @@ def scan_header(s, tables):
     else:
         slots = (s + 1 if s < 6 else s,)                    # scan 7 (s = 6) has no table
         selectors = (comp + 1, 0 if comp == 0 else 1)
-    parts = []
-    for k in slots:
-        counts, vals = tables[k]
-        if len(counts) != 16 or len(vals) != sum(counts) or not 1 <= len(vals) <= 256:
-            raise ValueError('tables: (16 counts, sum(counts) symbols) pairs')
-        parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), PROGRESSIVE_TABLE_IDS[k]), bytes(counts), bytes(vals)]
+    parts = [_dht(PROGRESSIVE_TABLE_IDS[k], tables[k]) for k in slots]
     n = len(selectors) // 2
     parts += [b'\xff\xda', struct.pack('>HB', 6 + 2 * n, n), bytes(selectors), bytes((ss, se, (ah << 4) | al))]
     return b''.join(parts)
@@ -190,21 +200,15 @@ def header(h, w, quality, subsampling='444', tables=None, grey=False):
         raise ValueError(f'grey is True or False, got {grey!r}')
     if grey and subsampling != '444':
         raise ValueError(f"a grey file has no subsampling: leave it at '444', got {subsampling!r}")
-    huffman = HUFFMAN
+    dht = ANNEX_K_DHT[:2 if grey else 4]
     if tables is not None:
         tables = [(tuple(int(c) for c in counts), tuple(int(v) for v in symbols)) for counts, symbols in tables]
-        if grey:
-            if len(tables) not in (2, 4):
-                raise ValueError('tables: two or four (16 counts, sum(counts) symbols) pairs')
-            tables = tables[:2] + list(t[1:] for t in HUFFMAN[2:])
-        if len(tables) != 4 or any(len(c) != 16 or len(v) != sum(c) or not 1 <= len(v) <= 256 for c, v in tables):
-            raise ValueError('tables: four (16 counts, sum(counts) symbols) pairs')
-        huffman = tuple((tc_th, c, v) for tc_th, (c, v) in zip(TABLE_IDS, tables))
+        if len(tables) not in ((2, 4) if grey else (4,)):
+            raise ValueError(f'tables: {"two or " if grey else ""}four (16 counts, sum(counts) symbols) pairs')
+        dht = [_dht(tc_th, t) for tc_th, t in zip(TABLE_IDS[:len(dht)], tables)]
     if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError(f'{h} x {w} is outside 1..{MAX_SIDE} per side')
-    parts = [_frame(h, w, quality, subsampling, b'\xff\xc0', grey)]
-    for tc_th, bits, vals in huffman[:2 if grey else 4]:
-        parts += [b'\xff\xc4', struct.pack('>HB', 19 + len(vals), tc_th), bytes(bits), bytes(vals)]
+    parts = [_frame(h, w, quality, subsampling, b'\xff\xc0', grey), *dht]
     if grey:
         parts += [b'\xff\xda', struct.pack('>HB', 8, 1), bytes((1, 0x00, 0, 0x3f, 0))]
     else:
@@ -217,10 +221,18 @@ def is_grey(img):
     return isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.dim() == 2
 
 
-def check_not_progressive_grey(img, progressive):
-    """There is no one-component progressive file: ValueError before any device work."""
-    if progressive and is_grey(img):
+# A kind of file: the ABI's prefix of its entry points, the streams per crop in a call's result and the DHT records per crop behind them
+Kind = collections.namedtuple('Kind', 'prefix streams tables')
+BASELINE, OPTIMISED, PROGRESSIVE = Kind('', 1, 0), Kind('opt_', 1, len(TABLE_IDS)), Kind('prog_', len(SCAN_SCRIPT), len(PROGRESSIVE_TABLE_IDS))
+
+
+def kind_of(img, optimize, progressive):
+    """The Kind that the two flags select for `img`; ValueError (before any device work) unless both are bools, and for a grey image
+    with progressive=True: there is no one-component progressive file.  `progressive` wins over `optimize`."""
+    check_optimize(optimize)
+    if check_progressive(progressive) and is_grey(img):
         raise ValueError('progressive=True: a grey [H, W] image has no progressive form here')
+    return PROGRESSIVE if progressive else (OPTIMISED if optimize else BASELINE)
 
 
 def _check(img, quality, subsampling, order, mcus_per_chunk, what):
@@ -247,29 +259,55 @@ def _check(img, quality, subsampling, order, mcus_per_chunk, what):
     return h, w, quality, sub, int(mcus_per_chunk)
 
 
+def _split(result, n, streams, tables):
+    """The host copy (a tensor or a sequence of int64) of a call's result on n crops -> (offsets [streams n + 1], tables): tables[k] holds
+    crop k's `tables` (counts, symbols) pairs, read from the DHT records behind the offsets (None where the kind has no tables)."""
+    raw = bytes(memoryview(result.numpy()).cast('B')) if isinstance(result, torch.Tensor) else bytes(result)
+    at = 8 * (streams * n + 1)
+    offsets = list(struct.unpack(f'<{streams * n + 1}q', raw[:at]))
+    if not tables:
+        return offsets, [None] * n
+    records = [raw[at + DHT_RECORD_BYTES * k:at + DHT_RECORD_BYTES * (k + 1)] for k in range(tables * n)]
+    pairs = [(tuple(rec[:16]), tuple(rec[16:16 + sum(rec[:16])])) for rec in records]
+    return offsets, [pairs[tables * k:tables * (k + 1)] for k in range(n)]
+
+
 def split_result(result, n):
     """The host copy (a sequence of int64) of an optimised call's result -> (offsets [n + 1], tables): tables[k] holds crop k's four
     (counts, symbols) pairs as `header(..., tables=)` takes them."""
-    raw = bytes(memoryview(result.numpy()).cast('B')) if isinstance(result, torch.Tensor) else bytes(result)
-    offsets = list(struct.unpack(f'<{n + 1}q', raw[:8 * (n + 1)]))
-    tables = []
-    for k in range(4 * n):
-        rec = raw[8 * (n + 1) + DHT_RECORD_BYTES * k:8 * (n + 1) + DHT_RECORD_BYTES * (k + 1)]
-        tables.append((tuple(rec[:16]), tuple(rec[16:16 + sum(rec[:16])])))
-    return offsets, [tables[4 * k:4 * k + 4] for k in range(n)]
+    return _split(result, n, OPTIMISED.streams, OPTIMISED.tables)
 
 
 def split_progressive_result(result, n):
     """The host copy of a progressive call's result -> (offsets [10 n + 1], tables): scan s of crop k lies at offsets[10 k + s] ..
     offsets[10 k + s + 1], tables[k] holds crop k's ten (counts, symbols) pairs in the order of PROGRESSIVE_TABLE_IDS."""
-    raw = bytes(memoryview(result.numpy()).cast('B')) if isinstance(result, torch.Tensor) else bytes(result)
-    ns = len(SCAN_SCRIPT)
-    offsets = list(struct.unpack(f'<{ns * n + 1}q', raw[:8 * (ns * n + 1)]))
-    tables = []
-    for k in range(ns * n):
-        rec = raw[8 * (ns * n + 1) + DHT_RECORD_BYTES * k:8 * (ns * n + 1) + DHT_RECORD_BYTES * (k + 1)]
-        tables.append((tuple(rec[:16]), tuple(rec[16:16 + sum(rec[:16])])))
-    return offsets, [tables[ns * k:ns * k + ns] for k in range(n)]
+    return _split(result, n, PROGRESSIVE.streams, PROGRESSIVE.tables)
+
+
+def _scans_device(kind, img, rects, quality, subsampling, order, mcus_per_chunk, out=None, capacity=None):
+    """`encode_scans_device` of a kind: every check, then ciaosr_jpeg_<prefix>encode_tiles_u8 on the current stream."""
+    h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
+    rects = check_rects(rects, h, w)
+    n = len(rects)
+    if kind.tables:
+        for r in rects:
+            check_frequency_limit(r[2], r[3], subsampling, sub == GREY)
+    dev = img.device
+    lib = _lib.load()
+    host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
+    cap = getattr(lib, f'ciaosr_jpeg_{kind.prefix}tiles_capacity_bytes')(host_rects, n, sub)
+    nbytes = getattr(lib, f'ciaosr_jpeg_{kind.prefix}tiles_workspace_bytes')(host_rects, n, sub, mcus)
+    if cap == 0 or nbytes == 0:
+        raise CiaoSRHipError(f'encode_jpeg_tiles: unsupported geometry ({n} rects, mcus_per_chunk={mcus})')
+    ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    words = getattr(lib, f'ciaosr_jpeg_{kind.prefix}result_bytes')(n) // 8 if kind.tables else n + 1
+    offs = torch.empty(words, dtype=torch.int64, device=dev)
+    _lib.call(f'ciaosr_jpeg_{kind.prefix}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), host_rects, n,
+              quality, sub, mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
+              C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
+    return out, offs
 
 
 def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, out=None, capacity=None, optimize=False,
@@ -281,31 +319,19 @@ def encode_scans_device(img, rects, quality=90, subsampling='444', order='bgr', 
     (`split_result` takes the host copy apart); the default capacity is `ciaosr_jpeg_opt_tiles_capacity_bytes`.
     `progressive=True` (whatever `optimize` is): ciaosr_jpeg_prog_encode_tiles_u8 -> (scans, result int64 [10 n + 1 + 340 n]): the
     offsets of the crops' ten scans each, then their ten DHT records each (`split_progressive_result`)."""
-    check_optimize(optimize)
-    check_not_progressive_grey(img, check_progressive(progressive))
-    h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg_tiles')
-    rects = check_rects(rects, h, w)
-    n = len(rects)
-    if optimize or progressive:
-        for r in rects:
-            check_frequency_limit(r[2], r[3], subsampling, sub == GREY)
-    dev = img.device
-    lib = _lib.load()
-    host_rects = (C.c_int * (4 * n))(*[v for r in rects for v in r])
-    opt = 'prog_' if progressive else ('opt_' if optimize else '')
-    cap = getattr(lib, f'ciaosr_jpeg_{opt}tiles_capacity_bytes')(host_rects, n, sub)
-    nbytes = getattr(lib, f'ciaosr_jpeg_{opt}tiles_workspace_bytes')(host_rects, n, sub, mcus)
-    if cap == 0 or nbytes == 0:
-        raise CiaoSRHipError(f'encode_jpeg_tiles: unsupported geometry ({n} rects, mcus_per_chunk={mcus})')
-    ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
-    if out is None:
-        out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    words = getattr(lib, f'ciaosr_jpeg_{opt}result_bytes')(n) // 8 if opt else n + 1
-    offs = torch.empty(words, dtype=torch.int64, device=dev)
-    _lib.call(f'ciaosr_jpeg_{opt}encode_tiles_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), host_rects, n, quality, sub,
-              mcus, hip_ops.ptr(out), C.c_size_t(cap if capacity is None else capacity), hip_ops.ptr(offs), hip_ops.ptr(ws),
-              C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
-    return out, offs
+    return _scans_device(kind_of(img, optimize, progressive), img, rects, quality, subsampling, order, mcus_per_chunk, out, capacity)
+
+
+def _scans(kind, img, rects, quality, subsampling, order, mcus_per_chunk):
+    """(scans, tables) of the crops, one entry per crop: its scan (progressive: the list of its ten), its tables (baseline: None).
+    Synchronises twice: the offsets and the tables, then the bytes."""
+    out, offs = _scans_device(kind, img, rects, quality, subsampling, order, mcus_per_chunk)
+    o, tables = _split(offs.cpu(), len(rects), kind.streams, kind.tables)     # copy 1: the offsets and the tables
+    raw = memoryview(out[:o[-1]].cpu().numpy())                               # copy 2: the scans
+    scans = [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
+    if kind.streams > 1:
+        scans = [scans[kind.streams * k:kind.streams * (k + 1)] for k in range(len(rects))]
+    return scans, tables
 
 
 def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
@@ -314,38 +340,18 @@ def encode_scans(img, rects, quality=90, subsampling='444', order='bgr', mcus_pe
     `optimize=True` -> (scans, tables): tables[k] holds the four (counts, symbols) pairs that scan k is coded with; the first copy
     brings the offsets and the tables.  `progressive=True` -> (scans, tables): scans[k] holds crop k's TEN scans, tables[k] its ten
     tables, as `assemble_progressive` takes them."""
-    rects = list(rects)
-    out, offs = encode_scans_device(img, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=progressive)
-    if progressive:
-        ns = len(SCAN_SCRIPT)
-        o, tables = split_progressive_result(offs.cpu(), len(rects))   # copy 1: the offsets and the tables
-        raw = memoryview(out[:o[-1]].cpu().numpy())                     # copy 2: the scans
-        return [[bytes(raw[o[ns * k + s]:o[ns * k + s + 1]]) for s in range(ns)] for k in range(len(rects))], tables
-    tables = None
-    if optimize:
-        o, tables = split_result(offs.cpu(), len(rects))             # copy 1: the offsets and the tables
-    else:
-        o = offs.cpu().tolist()                             # copy 1: the offsets
-    raw = memoryview(out[:o[-1]].cpu().numpy())             # copy 2: the scans
-    scans = [bytes(raw[o[k]:o[k + 1]]) for k in range(len(o) - 1)]
-    return (scans, tables) if optimize else scans
+    kind = kind_of(img, optimize, progressive)
+    scans, tables = _scans(kind, img, list(rects), quality, subsampling, order, mcus_per_chunk)
+    return (scans, tables) if kind.tables else scans
 
 
-def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
-    """The entropy-coded scan of the image, stuffed and padded (the file between the SOS header and EOI), made on the device -> bytes.
-    Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes.
-    `progressive=True` -> (the file's ten scans, its ten tables)."""
-    check_optimize(optimize)
-    check_not_progressive_grey(img, check_progressive(progressive))
-    if progressive:
-        h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
-        scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
+def _scan(kind, img, quality, subsampling, order, mcus_per_chunk):
+    """(scan, tables) of the whole image, as `_scans` gives them for one crop.  The kinds with tables go through the tiles entry, whose
+    result brings them; the baseline scan through ciaosr_jpeg_encode_u8: size, then bytes."""
+    h, w, quality_, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')
+    if kind.tables:
+        scans, tables = _scans(kind, img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk)
         return scans[0], tables[0]
-    if optimize:
-        h, w = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')[:2]
-        scans, tables = encode_scans(img, [(0, 0, h, w)], quality, subsampling, order, mcus_per_chunk, optimize=True)
-        return scans[0], tables[0]
-    h, w, quality, sub, mcus = _check(img, quality, subsampling, order, mcus_per_chunk, 'encode_jpeg')
     dev = img.device
     lib = _lib.load()
     cap = lib.ciaosr_jpeg_capacity_bytes(h, w, sub)
@@ -355,29 +361,38 @@ def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=
     ws = hip_ops.workspace(nbytes, dev, slot='jpeg')
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call('ciaosr_jpeg_encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), quality, sub, mcus,
+    _lib.call('ciaosr_jpeg_encode_u8', hip_ops.ptr(img), C.c_size_t(_pitch(img)), h, w, ORDERS.get(order, 0), quality_, sub, mcus,
               hip_ops.ptr(out), C.c_size_t(cap), hip_ops.ptr(total), hip_ops.ptr(ws), C.c_size_t(nbytes), hip_ops.stream_ptr(dev))
     n = int(total.item())                                   # copy 1: the size
-    return out[:n].cpu().numpy().tobytes()                  # copy 2: the scan
+    return out[:n].cpu().numpy().tobytes(), None            # copy 2: the scan
+
+
+def encode_scan(img, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
+    """The entropy-coded scan of the image, stuffed and padded (the file between the SOS header and EOI), made on the device -> bytes.
+    Synchronises twice: size, then bytes.  `optimize=True` -> (scan, its four (counts, symbols) tables); size and tables, then bytes.
+    `progressive=True` -> (the file's ten scans, its ten tables)."""
+    kind = kind_of(img, optimize, progressive)
+    scan, tables = _scan(kind, img, quality, subsampling, order, mcus_per_chunk)
+    return (scan, tables) if kind.tables else scan
+
+
+def _file(kind, h, w, quality, subsampling, scan, tables, grey):
+    """The file of an h x w image from what `_scan` or `_scans` returned for it."""
+    if kind.streams > 1:
+        return assemble_progressive(h, w, quality, subsampling, scan, tables)
+    return header(h, w, quality, subsampling, tables, grey) + scan + EOI
 
 
 def encode_jpeg(img_u8_hwc, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
     """JPEG file (bytes) of a uint8 [H, W, 3] device image, byte for byte `PIL.Image.save(format='JPEG', quality=quality,
-    subsampling=0 or 2)` of the same pixels (a 2-D [H, W] image: of the mode-L image, see the module's text); `order`: 'bgr' as `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a
-    larger image).  `mcus_per_chunk`: MCUs per workgroup, 0 = the library's choice; the bytes do not depend on it.
+    subsampling=0 or 2)` of the same pixels (a 2-D [H, W] image: of the mode-L image, see the module's text); `order`: 'bgr' as
+    `tensor2img_u8` makes it, or 'rgb'.  Rows may be pitched (a crop view of a larger image).  `mcus_per_chunk`: MCUs per workgroup,
+    0 = the library's choice; the bytes do not depend on it.
     `optimize=True`: byte for byte `PIL.Image.save(..., optimize=True)`: Huffman tables made for this file on the device.
     `progressive=True`: byte for byte `PIL.Image.save(..., progressive=True)`, whatever `optimize` is."""
-    tables = None
-    check_optimize(optimize)
-    check_not_progressive_grey(img_u8_hwc, check_progressive(progressive))
-    if progressive:
-        scans, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
-        return assemble_progressive(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, scans, tables)
-    if optimize:
-        scan, tables = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk, optimize=True)
-    else:
-        scan = encode_scan(img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
-    return header(img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, tables, is_grey(img_u8_hwc)) + scan + EOI
+    kind = kind_of(img_u8_hwc, optimize, progressive)
+    scan, tables = _scan(kind, img_u8_hwc, quality, subsampling, order, mcus_per_chunk)
+    return _file(kind, img_u8_hwc.shape[0], img_u8_hwc.shape[1], quality, subsampling, scan, tables, is_grey(img_u8_hwc))
 
 
 def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='bgr', mcus_per_chunk=0, optimize=False, progressive=False):
@@ -387,17 +402,10 @@ def encode_jpeg_tiles(img_u8_hwc, rects, quality=90, subsampling='444', order='b
     byte for byte Pillow's `optimize=True` file of the crop; still ten launches and two copies whatever the number of crops.
     `progressive=True`: every file Pillow's `progressive=True` file of the crop; thirteen launches and two copies."""
     rects = list(rects)
-    check_optimize(optimize)
-    check_not_progressive_grey(img_u8_hwc, check_progressive(progressive))
+    kind = kind_of(img_u8_hwc, optimize, progressive)
+    scans, tables = _scans(kind, img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
     grey = is_grey(img_u8_hwc)
-    if progressive:
-        scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=optimize, progressive=True)
-        return [assemble_progressive(int(r[2]), int(r[3]), quality, subsampling, s, t) for r, s, t in zip(rects, scans, tables)]
-    if optimize:
-        scans, tables = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk, optimize=True)
-        return [header(int(r[2]), int(r[3]), quality, subsampling, t, grey) + s + EOI for r, s, t in zip(rects, scans, tables)]
-    scans = encode_scans(img_u8_hwc, rects, quality, subsampling, order, mcus_per_chunk)
-    return [header(int(r[2]), int(r[3]), quality, subsampling, None, grey) + s + EOI for r, s in zip(rects, scans)]
+    return [_file(kind, int(r[2]), int(r[3]), quality, subsampling, s, t, grey) for r, s, t in zip(rects, scans, tables)]
 
 
 def imwrite_gpu_jpeg(img_u8_hwc, path, quality=90, subsampling='444', order='bgr', optimize=False, progressive=False):
