@@ -246,6 +246,24 @@ SIGNATURES = {
     'ciaosr_grey_from_bgr_u8': (_I, [_P, _S, _I, _I, _I, _P, _S, _P]),
     'ciaosr_deflate_lz_workspace_bytes': (_S, [_S, _I]),
     'ciaosr_deflate_lz_u8': (_I, [_P, _P, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    # 16-bit samples (version 350): native uint16 images, pitches in bytes; PNG bit depth 16 with three samples per pixel
+    # (ciaosr_png16_*) or one (ciaosr_png16_grey_*), each with the arguments of its 8-bit namesake
+    'ciaosr_tensor2img_u16': (_I, [_P, _I, _I, _P, _S, _P]),
+    'ciaosr_tensor2img_grey_u16': (_I, [_P, _I, _I, _P, _S, _P]),
+    'ciaosr_grey_from_bgr_u16': (_I, [_P, _S, _I, _I, _I, _P, _S, _P]),
+    **{pre + name: sig for pre in ('ciaosr_png16_', 'ciaosr_png16_grey_') for name, sig in (
+        ('rows_per_band', (_I, [_I, _I])),
+        ('filter_u16', (_I, [_P, _S, _I, _I, _I, _I, _P, _P, _P, _P])),
+        ('workspace_bytes', (_S, [_I, _I, _I])),
+        ('lz_workspace_bytes', (_S, [_I, _I, _I])),
+        ('capacity_bytes', (_S, [_I, _I, _I])),
+        ('encode_u16', (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P])),
+        ('lz_encode_u16', (_I, [_P, _S, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P])),
+        ('tiles_workspace_bytes', (_S, [_P, _I, _I])),
+        ('lz_tiles_workspace_bytes', (_S, [_P, _I, _I])),
+        ('tiles_capacity_bytes', (_S, [_P, _I, _I])),
+        ('encode_tiles_u16', (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P])),
+        ('lz_encode_tiles_u16', (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P])))},
     'ciaosr_jpeg_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_jpeg_capacity_bytes': (_S, [_I, _I, _I]),
     'ciaosr_jpeg_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),

@@ -206,6 +206,59 @@ __global__ __launch_bounds__(kQThreads) void grey_from_bgr_u8_kernel(GreyP p) {
     store_grey(p.dst + (size_t)y * p.pitch, x, n, word, p.vec_out);
 }
 
+// 16-bit samples: tensor2img_u8's rule with 65535 for 255 -- clamp, ONE fp32 multiply, round half to even -- into native uint16.
+// It is its own quantiser, not the 8-bit one widened: k / 255 gives 257 k, and the high byte of a sample is not tensor2img_u8's byte.
+__device__ __forceinline__ unsigned int quant16(float v) {
+    v = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (unsigned int)(int)__builtin_rintf(mul_rn(v, 65535.0f));
+}
+// the grey weights on three 16-bit values, in unsigned 32 bits: at most 65535 * 65536 + 32768 < 2^32; a neutral v, v, v gives v
+__device__ __forceinline__ unsigned int grey16_of_bgr(unsigned int b, unsigned int g, unsigned int r) {
+    return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16;
+}
+
+struct Quant16P {
+    const float* src;             // [3][H][W] RGB
+    unsigned short* dst;          // rows `pitch` BYTES apart (even): [H][W][3] B G R samples, or [H][W] grey ones
+    size_t pitch;
+    int H, W;
+};
+
+template <bool kGrey>
+__global__ __launch_bounds__(kQThreads) void tensor2img_u16_kernel(Quant16P p) {
+    const int y = blockIdx.y, x = blockIdx.x * kQThreads + threadIdx.x;
+    if (x >= p.W) return;
+    const size_t plane = (size_t)p.H * p.W, i = (size_t)y * p.W + x;
+    const unsigned int r = quant16(p.src[i]), g = quant16(p.src[plane + i]), b = quant16(p.src[2 * plane + i]);
+    unsigned short* out = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(p.dst) + (size_t)y * p.pitch);
+    if constexpr (kGrey) {
+        out[x] = (unsigned short)grey16_of_bgr(b, g, r);
+    } else {
+        out[3 * (size_t)x + 0] = (unsigned short)b;
+        out[3 * (size_t)x + 1] = (unsigned short)g;
+        out[3 * (size_t)x + 2] = (unsigned short)r;
+    }
+}
+
+struct Grey16P {
+    const unsigned short* src;    // rows pitch_src BYTES apart, three samples per pixel
+    size_t pitch_src;
+    int bgr;                      // the samples of a pixel are B G R, else R G B
+    unsigned short* dst;          // rows `pitch` BYTES apart
+    size_t pitch;
+    int H, W;
+};
+
+__global__ __launch_bounds__(kQThreads) void grey_from_bgr_u16_kernel(Grey16P p) {
+    const int y = blockIdx.y, x = blockIdx.x * kQThreads + threadIdx.x;
+    if (x >= p.W) return;
+    const unsigned short* q =
+        reinterpret_cast<const unsigned short*>(reinterpret_cast<const unsigned char*>(p.src) + (size_t)y * p.pitch_src) + 3 * (size_t)x;
+    unsigned short* out = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(p.dst) + (size_t)y * p.pitch);
+    const unsigned int c0 = q[0], g = q[1], c2 = q[2];
+    out[x] = (unsigned short)grey16_of_bgr(p.bgr ? c0 : c2, g, p.bgr ? c2 : c0);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct MetricsP {
     const unsigned char* a;
@@ -459,6 +512,40 @@ extern "C" int ciaosr_grey_from_bgr_u8(const unsigned char* bgr, size_t pitch, i
     ProfScope prof("grey_from_bgr_u8", s);
     hipLaunchKernelGGL(grey_from_bgr_u8_kernel, dim3(ceil_div(ceil_div(W, kGreyPer), kQThreads), H), dim3(kQThreads), 0, s, p);
     return launch_status("grey_from_bgr_u8");
+}
+
+static inline bool even2(const void* p, size_t pitch) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0 && (pitch & 1u) == 0; }
+
+extern "C" int ciaosr_tensor2img_u16(const float* src_chw, int H, int W, unsigned short* dst_hwc, size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(src_chw && dst_hwc && H > 0 && W > 0 && dst_pitch >= 6 * (size_t)W && even2(dst_hwc, dst_pitch));
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    Quant16P p{src_chw, dst_hwc, dst_pitch, H, W};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("tensor2img_u16", s);
+    hipLaunchKernelGGL(tensor2img_u16_kernel<false>, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("tensor2img_u16");
+}
+
+extern "C" int ciaosr_tensor2img_grey_u16(const float* src_chw, int H, int W, unsigned short* dst, size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(src_chw && dst && H > 0 && W > 0 && dst_pitch >= 2 * (size_t)W && even2(dst, dst_pitch));
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    Quant16P p{src_chw, dst, dst_pitch, H, W};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("tensor2img_grey_u16", s);
+    hipLaunchKernelGGL(tensor2img_u16_kernel<true>, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("tensor2img_grey_u16");
+}
+
+extern "C" int ciaosr_grey_from_bgr_u16(const unsigned short* bgr, size_t pitch, int bgr_flag, int H, int W, unsigned short* dst,
+                                        size_t dst_pitch, void* stream) {
+    CIAOSR_CHECK_ARG(bgr && dst && H > 0 && W > 0 && pitch >= 6 * (size_t)W && dst_pitch >= 2 * (size_t)W && (bgr_flag == 0 || bgr_flag == 1));
+    CIAOSR_CHECK_ARG(even2(bgr, pitch) && even2(dst, dst_pitch));
+    if (H > 65535 || W > kMaxDim) return CIAOSR_ERR_UNSUPPORTED;        // one grid row per image row
+    Grey16P p{bgr, pitch, bgr_flag, dst, dst_pitch, H, W};
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("grey_from_bgr_u16", s);
+    hipLaunchKernelGGL(grey_from_bgr_u16_kernel, dim3(ceil_div(W, kQThreads), H), dim3(kQThreads), 0, s, p);
+    return launch_status("grey_from_bgr_u16");
 }
 
 extern "C" size_t ciaosr_psnr_ssim_u8_workspace_bytes(int H, int W, int crop_border, int convert_to_y) {

@@ -9,6 +9,9 @@
 // Adler-32 partial sums.  filter_band is a template over the bytes per pixel: 3 (colour type 2) and 4 (colour type 6, the ciaosr_png_rgba_*
 // entry points: rows of 1 + 4 W bytes in R G B A order, the left predecessor four bytes back, a pixel read as ONE aligned 32-bit word)
 // and 1 (colour type 0, the ciaosr_png_grey_* entry points: rows of 1 + W bytes, the left predecessor one byte back, any alignment).
+// Bit depth 16 (the ciaosr_png16_* and ciaosr_png16_grey_* entry points) is the same template at 6 and 2 stream bytes per pixel: the
+// source is native uint16 samples (2-byte aligned, no more), the stream holds each sample high byte first, and the five filters work
+// on those BYTES -- the left predecessor of a byte is the byte 6 or 2 back, and nothing is borrowed between the halves of a sample.
 //
 // Stage 2, four launches over a byte buffer split into bands:
 //   deflate_hist_kernel   the 257-bin histogram of every band (skipped when stage 1 made it);
@@ -99,7 +102,7 @@ struct TileBand {
 };
 
 struct FilterP {
-    const unsigned char* src;     // [H][pitch], 1, 3 or 4 bytes per pixel (the kernel's template argument)
+    const unsigned char* src;     // [H][pitch], 1, 3 or 4 bytes per pixel, or 1 or 3 uint16 samples (the kernel's template argument)
     size_t pitch;
     int H, W, bgr, R;
     unsigned char* dst;           // [H][1 + bytes per pixel * W]
@@ -122,7 +125,8 @@ __device__ __forceinline__ void filters5(int v, int a, int b, int c, u32 f[5]) {
 
 // The pixel at column x of row `cur` in stream order (R G B, then A): v its bytes, a those of the pixel to the left, b of the pixel above
 // (`up`, null for the image's first row), c of the pixel above left; zeros where the image ends.  Four bytes per pixel are ONE aligned
-// 32-bit load per pixel (the host checks src and pitch); three are single bytes.
+// 32-bit load per pixel (the host checks src and pitch); three are single bytes.  BPP 2 and 6 are the 16-bit kinds: one or three native
+// uint16 samples per pixel (16-bit loads: src and pitch are even, the host checks), each split into its high byte, then its low byte.
 template <int BPP>
 __device__ __forceinline__ void load_pixel(const unsigned char* cur, const unsigned char* up, int x, int bgr, int v[BPP], int a[BPP],
                                            int b[BPP], int c[BPP]) {
@@ -145,7 +149,22 @@ __device__ __forceinline__ void load_pixel(const unsigned char* cur, const unsig
             b[k] = (int)(pb >> sh & 255u);
             c[k] = (int)(pc >> sh & 255u);
         }
+    } else if constexpr (BPP == 2 || BPP == 6) {
+        constexpr int C = BPP / 2;
+        const unsigned short* q = reinterpret_cast<const unsigned short*>(cur) + C * (size_t)x;
+        const unsigned short* qu = reinterpret_cast<const unsigned short*>(up) + C * (size_t)x;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const int sc = C == 1 ? 0 : (k == 0 ? s0 : (k == 1 ? 1 : s2));
+            const u32 pv = q[sc], pa = x > 0 ? q[sc - C] : 0u;
+            const u32 pb = up ? qu[sc] : 0u, pc = (up && x > 0) ? qu[sc - C] : 0u;
+            v[2 * k] = (int)(pv >> 8), v[2 * k + 1] = (int)(pv & 255u);
+            a[2 * k] = (int)(pa >> 8), a[2 * k + 1] = (int)(pa & 255u);
+            b[2 * k] = (int)(pb >> 8), b[2 * k + 1] = (int)(pb & 255u);
+            c[2 * k] = (int)(pc >> 8), c[2 * k + 1] = (int)(pc & 255u);
+        }
     } else {
+        static_assert(BPP == 3, "bytes per pixel");
         const unsigned char* q = cur + 3 * (size_t)x;
         const unsigned char* qu = up + 3 * (size_t)x;
 #pragma unroll
@@ -228,7 +247,7 @@ __device__ __forceinline__ void filter_band(const FilterP& p, int band, int r0, 
                 out[j] = (unsigned char)fb;
                 atomicAdd(&h[wave][fb], 1u);
                 a1 += fb;
-                a2 += (L - j) * (u64)fb;              // < 2^19 * 2^8 per byte, < 2^45 per row
+                a2 += (L - j) * (u64)fb;              // L <= 6 * 65535 + 1 < 2^19: < 2^19 * 2^8 per byte, < 2^45 per row
             }
         }
         a1 = wave_sum_u64(a1);
@@ -1426,15 +1445,19 @@ static int run_filter(int bpp, const unsigned char* src, size_t pitch, int H, in
     f.adler = adler;
     const int nb = ceil_div(H, R);
     if (bpp == 1) return launch("png_grey_filter_u8", png_filter_kernel<1>, nb, kThreads, s, f);
+    if (bpp == 2) return launch("png16_grey_filter_u16", png_filter_kernel<2>, nb, kThreads, s, f);
+    if (bpp == 6) return launch("png16_filter_u16", png_filter_kernel<6>, nb, kThreads, s, f);
     return bpp == 4 ? launch("png_rgba_filter_u8", png_filter_kernel<4>, nb, kThreads, s, f)
                     : launch("png_filter_u8", png_filter_kernel<3>, nb, kThreads, s, f);
 }
 
 static inline bool image_ok(int H, int W) { return H > 0 && W > 0 && H <= 65535 && W <= 65535; }
 
-// what the filter asks of a source: rows of at least bpp W bytes; four bytes per pixel are read as aligned 32-bit words
+// what the filter asks of a source: rows of at least bpp W bytes; four bytes per pixel are read as aligned 32-bit words, 16-bit
+// samples (bpp 2 and 6) as aligned 16-bit ones
 static inline bool source_ok(int bpp, const unsigned char* src, size_t pitch, int W) {
     if (!src || pitch < (size_t)bpp * (size_t)W) return false;
+    if (bpp == 2 || bpp == 6) return (reinterpret_cast<uintptr_t>(src) & 1u) == 0 && (pitch & 1u) == 0;
     return bpp != 4 || ((reinterpret_cast<uintptr_t>(src) & 3u) == 0 && (pitch & 3u) == 0);
 }
 
@@ -1530,7 +1553,8 @@ static Layout tile_layout(const TilePlan& t, bool lz) {
 using namespace ciaosr;
 using namespace ciaosr::png;
 
-// ---- the entry points' bodies, for 3 (R G B) or 4 (R G B A) bytes per pixel; lz: the match coder's entry points -------------------
+// ---- the entry points' bodies, for 3 (R G B), 4 (R G B A) or 1 (grey) bytes per pixel, and 6 or 2 at bit depth 16; lz: the match
+// coder's entry points -----------------------------------------------------------------------------------------------------------------
 static int rows_per_band_entry(int bpp, int W, int rows_per_band_arg) {
     if (W <= 0 || W > 65535 || rows_per_band_arg < 0) return 0;
     return rows_per_band(W, rows_per_band_arg, bpp);
@@ -1635,6 +1659,8 @@ static int encode_tiles_entry(int bpp, bool lz, const unsigned char* src, size_t
     f.hist = w.hist;
     f.adler = w.adler;
     int rc = bpp == 1   ? launch("png_grey_filter_tiles_u8", png_filter_tiles_kernel<1>, t.nb, kThreads, s, f)
+             : bpp == 2 ? launch("png16_grey_filter_tiles_u16", png_filter_tiles_kernel<2>, t.nb, kThreads, s, f)
+             : bpp == 6 ? launch("png16_filter_tiles_u16", png_filter_tiles_kernel<6>, t.nb, kThreads, s, f)
              : bpp == 4 ? launch("png_rgba_filter_tiles_u8", png_filter_tiles_kernel<4>, t.nb, kThreads, s, f)
                         : launch("png_filter_tiles_u8", png_filter_tiles_kernel<3>, t.nb, kThreads, s, f);
     if (rc) return rc;
@@ -1849,3 +1875,56 @@ extern "C" int ciaosr_png_grey_lz_encode_tiles_u8(const unsigned char* src, size
     return encode_tiles_entry(1, true, src, pitch, H, W, bgr, rects, n_tiles, rows_per_band_arg, out, out_capacity, tile_offs, workspace,
                               workspace_bytes, stream);
 }
+
+// Bit depth 16: native uint16 samples, three (colour type 2, bpp 6: ciaosr_png16_*) or one (colour type 0, bpp 2: ciaosr_png16_grey_*)
+// per pixel; the same entries on rows of 1 + 6 W or 1 + 2 W bytes.  src and pitch are even (source_ok).
+#define CIAOSR_PNG16_EXPORTS(P, BPP)                                                                                                      \
+    extern "C" int P##rows_per_band(int W, int rows_per_band_arg) { return rows_per_band_entry(BPP, W, rows_per_band_arg); }              \
+    extern "C" int P##filter_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,                   \
+                                 unsigned char* dst, unsigned int* hist, unsigned int* adler, void* stream) {                             \
+        return filter_entry(BPP, reinterpret_cast<const unsigned char*>(src), pitch, H, W, bgr, rows_per_band_arg, dst, hist, adler,      \
+                            stream);                                                                                                      \
+    }                                                                                                                                     \
+    extern "C" size_t P##workspace_bytes(int H, int W, int rows_per_band_arg) {                                                           \
+        return workspace_entry(BPP, H, W, rows_per_band_arg, false);                                                                      \
+    }                                                                                                                                     \
+    extern "C" size_t P##lz_workspace_bytes(int H, int W, int rows_per_band_arg) {                                                        \
+        return workspace_entry(BPP, H, W, rows_per_band_arg, true);                                                                       \
+    }                                                                                                                                     \
+    extern "C" size_t P##capacity_bytes(int H, int W, int rows_per_band_arg) { return capacity_entry(BPP, H, W, rows_per_band_arg); }     \
+    extern "C" int P##encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,                   \
+                                 unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,               \
+                                 size_t workspace_bytes, void* stream) {                                                                  \
+        return encode_entry(BPP, false, reinterpret_cast<const unsigned char*>(src), pitch, H, W, bgr, rows_per_band_arg, out,            \
+                            out_capacity, total_bytes, workspace, workspace_bytes, stream);                                               \
+    }                                                                                                                                     \
+    extern "C" int P##lz_encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band_arg,                \
+                                    unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,            \
+                                    size_t workspace_bytes, void* stream) {                                                               \
+        return encode_entry(BPP, true, reinterpret_cast<const unsigned char*>(src), pitch, H, W, bgr, rows_per_band_arg, out,             \
+                            out_capacity, total_bytes, workspace, workspace_bytes, stream);                                               \
+    }                                                                                                                                     \
+    extern "C" size_t P##tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {                                    \
+        return tiles_workspace_entry(BPP, rects, n_tiles, rows_per_band_arg, false);                                                      \
+    }                                                                                                                                     \
+    extern "C" size_t P##lz_tiles_workspace_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {                                 \
+        return tiles_workspace_entry(BPP, rects, n_tiles, rows_per_band_arg, true);                                                       \
+    }                                                                                                                                     \
+    extern "C" size_t P##tiles_capacity_bytes(const int* rects, int n_tiles, int rows_per_band_arg) {                                     \
+        return tiles_capacity_entry(BPP, rects, n_tiles, rows_per_band_arg);                                                              \
+    }                                                                                                                                     \
+    extern "C" int P##encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,     \
+                                       int rows_per_band_arg, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,     \
+                                       void* workspace, size_t workspace_bytes, void* stream) {                                           \
+        return encode_tiles_entry(BPP, false, reinterpret_cast<const unsigned char*>(src), pitch, H, W, bgr, rects, n_tiles,              \
+                                  rows_per_band_arg, out, out_capacity, tile_offs, workspace, workspace_bytes, stream);                   \
+    }                                                                                                                                     \
+    extern "C" int P##lz_encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects, int n_tiles,  \
+                                          int rows_per_band_arg, unsigned char* out, size_t out_capacity,                                 \
+                                          unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream) {         \
+        return encode_tiles_entry(BPP, true, reinterpret_cast<const unsigned char*>(src), pitch, H, W, bgr, rects, n_tiles,               \
+                                  rows_per_band_arg, out, out_capacity, tile_offs, workspace, workspace_bytes, stream);                   \
+    }
+CIAOSR_PNG16_EXPORTS(ciaosr_png16_, 6)
+CIAOSR_PNG16_EXPORTS(ciaosr_png16_grey_, 2)
+#undef CIAOSR_PNG16_EXPORTS

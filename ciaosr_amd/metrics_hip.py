@@ -104,6 +104,72 @@ def grey_from_bgr_u8(img_u8, order='bgr'):
     return img
 
 
+def tensor2img_u16(t):
+    """`tensor2img_u8` with 16-bit samples: [1, 3, H, W] or [3, H, W] RGB in [0, 1] -> torch.uint16 [H, W, 3] BGR, each sample
+    rint(fp32(clamp(v, 0, 1) * 65535)) (one fp32 multiply, round half to even): bitwise `(t.clamp(0, 1) * 65535).round()`.  A level
+    k / 255 becomes 257 k; otherwise this is NOT the 8-bit image shifted left, and a sample's high byte is NOT `tensor2img_u8`'s."""
+    t = t.detach()
+    while t.dim() > 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f'tensor2img_u16 expects [1, 3, H, W] or [3, H, W], got {tuple(t.shape)}')
+    t = t.float().contiguous()
+    hip_ops.require_gpu(t)
+    h, w = t.shape[1], t.shape[2]
+    img = torch.empty((h, w, 3), dtype=torch.uint16, device=t.device)
+    _lib.call('ciaosr_tensor2img_u16', hip_ops.ptr(t), h, w, hip_ops.ptr(img), C.c_size_t(6 * w), hip_ops.stream_ptr(t.device))
+    return img
+
+
+def tensor2img_grey_u16(t, out=None):
+    """The 16-bit GREY image of a render: [1, 3, H, W] or [3, H, W] RGB in [0, 1] -> torch.uint16 [H, W].  With (B, G, R) =
+    `tensor2img_u16`'s samples of the pixel, L16 = (19595 R + 38470 G + 7471 B + 32768) >> 16 in unsigned 32-bit arithmetic: the
+    weights of `tensor2img_grey_u8`, and v for a neutral (v, v, v).  One pass.  `out`: a uint16 [H, W] device view to write into
+    (rows may be pitched; a crop may start at any pixel)."""
+    shape = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+    if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4) or t.shape[-3] != 3 or (t.dim() == 4 and t.shape[0] != 1):
+        raise ValueError(f'tensor2img_grey_u16 expects [1, 3, H, W] or [3, H, W], got {shape}')
+    h, w = t.shape[-2], t.shape[-1]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or tuple(out.shape) != (h, w) or (w > 1 and out.stride(1) != 1) \
+                or (h > 1 and out.stride(0) < w):
+            raise ValueError(f'tensor2img_grey_u16: out must be a uint16 [{h}, {w}] view with contiguous rows')
+    t = t.detach().reshape(3, h, w).float().contiguous()
+    hip_ops.require_gpu(t)
+    if out is not None and out.device != t.device:
+        raise CiaoSRHipError(f'tensor2img_grey_u16: out on {out.device} but the render on {t.device}')
+    img = torch.empty((h, w), dtype=torch.uint16, device=t.device) if out is None else out
+    _lib.call('ciaosr_tensor2img_grey_u16', hip_ops.ptr(t), h, w, hip_ops.ptr(img), C.c_size_t(2 * (img.stride(0) if h > 1 else w)),
+              hip_ops.stream_ptr(t.device))
+    return img
+
+
+def grey_from_bgr_u16(img_u16, order='bgr'):
+    """uint16 [H, W] grey image of a uint16 [H, W, 3] device image (`order` 'bgr' or 'rgb'; rows may be pitched) by the formula of
+    `tensor2img_grey_u16`."""
+    if not isinstance(img_u16, torch.Tensor) or img_u16.dtype != torch.uint16 or img_u16.dim() != 3 or img_u16.shape[2] != 3:
+        what = f'{img_u16.dtype} {tuple(img_u16.shape)}' if isinstance(img_u16, torch.Tensor) else type(img_u16).__name__
+        raise ValueError(f'grey_from_bgr_u16 expects a uint16 [H, W, 3] image, got {what}')
+    if order not in ('bgr', 'rgb'):
+        raise ValueError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    _check_image_u16(img_u16)
+    h, w = img_u16.shape[0], img_u16.shape[1]
+    img = torch.empty((h, w), dtype=torch.uint16, device=img_u16.device)
+    _lib.call('ciaosr_grey_from_bgr_u16', hip_ops.ptr(img_u16), C.c_size_t(2 * img_u16.stride(0)), 1 if order == 'bgr' else 0, h, w,
+              hip_ops.ptr(img), C.c_size_t(2 * w), hip_ops.stream_ptr(img_u16.device))
+    return img
+
+
+def _check_image_u16(img):
+    """`_check_image` for a uint16 [H, W, 3] tensor (dtype and shape are the caller's to check): strides count samples."""
+    if not img.is_cuda:
+        hip_ops.require_gpu(img)              # raises: no CPU fallback
+    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * img.shape[1]:
+        raise CiaoSRHipError('expected HWC rows of 3*W contiguous samples (a crop of a larger image is fine)')
+    if img.device.index != torch.cuda.current_device():
+        raise CiaoSRHipError(f'image on cuda:{img.device.index} but the current device is cuda:{torch.cuda.current_device()}')
+
+
 def _check_image(img):
     if not isinstance(img, torch.Tensor):
         raise CiaoSRHipError(f'expected a uint8 HxWx3 cuda tensor, got {type(img).__name__}')

@@ -532,16 +532,22 @@ class CiaoSR(BasicRestorer):
         return scene_render.encode_grey(self, lq1, options, max_scale, self_ensemble)
 
     @torch.no_grad()
-    def render(self, enc, size=None, scale=None, window=None, as_u8=False):
+    def render(self, enc, size=None, scale=None, window=None, as_u8=False, as_u16=False):
         """The window (i0, j0, h, w) (HR pixels; default: the whole grid) of the image `restore` gives for the Ht x Wt target -- `size`, or
         round(h * scale), round(w * scale) -- under the same test_cfg, from an `encode` result: [B, 3, h, w], de-normalised and clamped,
-        or with `as_u8` the metrics_hip.tensor2img_u8 image of it.  Only the LR tiles whose HR rectangle meets the window are touched."""
+        or with `as_u8` the metrics_hip.tensor2img_u8 image of it.  Only the LR tiles whose HR rectangle meets the window are touched.
+        `as_u16`: the same render as torch.uint16 samples, q16(v) = rint(fp32(clamp(v, 0, 1) * 65535)) -- [H, W, 3] B G R
+        (`metrics_hip.tensor2img_u16`), or [H, W] on an `encode_grey` record (`tensor2img_grey_u16`: L16 of the three samples) --
+        quantised once, after the tile blend, the view fill and the ensemble mean.  It is NOT the `as_u8` image shifted left, and its
+        high byte is NOT the `as_u8` byte.  With `as_u8` as well, or on an `encode_rgba` record, a ValueError before any device work
+        (`render_view` and `render_many` likewise)."""
+        scene_render.check_quant(enc, as_u8, as_u16)
         if scene_render.is_ensemble(enc):
-            return scene_render.render_ensemble(self, enc, [scene.Grid(size, scale, window)], as_u8)[0]
-        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.Grid(size, scale, window)])[0], as_u8)
+            return scene_render.render_ensemble(self, enc, [scene.Grid(size, scale, window)], as_u8, as_u16=as_u16)[0]
+        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.Grid(size, scale, window)])[0], as_u8, as_u16)
 
     @torch.no_grad()
-    def render_view(self, enc, matrix, size, fill=0.0, as_u8=False):
+    def render_view(self, enc, matrix, size, fill=0.0, as_u8=False, as_u16=False):
         """The Hv x Wv (`size`) affine view `matrix` = (m_yy, m_yx, t_y, m_xy, m_xx, t_x) of an `encode` result (scene.py: the definition,
         `view_matrix`, `view_of_window`): [B, 3, Hv, Wv], de-normalised and clamped, or with `as_u8` the metrics_hip.tensor2img_u8 image
         of it.  A pixel whose centre falls outside the image holds `fill` (one number or three, in the output's [0, 1]).  The queries are
@@ -549,12 +555,14 @@ class CiaoSR(BasicRestorer):
         row-major tile order; a tile without a member is neither built nor queried.  With `test_cfg.tile` this needs
         `test_cfg.tile_any_scale`.  Per batch item ONE device-to-host copy -- the tiles' member counts, which size the per-tile query
         lists -- is the only synchronisation of a view render.  An axis-aligned view is not bitwise the window `render` shows (its
-        coordinates differ by up to 2^-22, see `scene.view_of_window`)."""
+        coordinates differ by up to 2^-22, see `scene.view_of_window`).  `as_u16`: see `render`; outside the view a grey record holds
+        L16 of (q16(fill), q16(fill), q16(fill))."""
+        scene_render.check_quant(enc, as_u8, as_u16)
         scene_render.refuse_ensemble(enc, 'render_view')
-        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.View(matrix, size, fill)])[0], as_u8)
+        return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.View(matrix, size, fill)])[0], as_u8, as_u16)
 
     @torch.no_grad()
-    def render_many(self, enc, targets, as_u8=False):
+    def render_many(self, enc, targets, as_u8=False, as_u16=False):
         """Every target of the list -- scene.Grid(size, scale, window): `render`'s arguments, scene.View(matrix, size, fill):
         `render_view`'s -- from ONE walk over the tile scenes: -> list of [B, 3, h, w], outs[k] bitwise what the single call returns on an
         encode with the same max_scale under the same test_cfg (with `as_u8` the same uint8 image).  Per batch item the union of the
@@ -566,8 +574,8 @@ class CiaoSR(BasicRestorer):
         made `tile_batch()` tiles per trunk call where the trunk batches tiles, with `test_cfg.encoder_ahead` (default on) the next
         group's trunk on the cached side stream under the current group's heads.  All views are counted in one `view_count_many` and
         one device-to-host copy per call (none for grids alone).  An image that is one frame (no `test_cfg.tile`, or an image no larger
-        than the tile) has no schedule to make: its targets are the single calls, in list order."""
-        return scene_render.render_many(self, enc, targets, as_u8)
+        than the tile) has no schedule to make: its targets are the single calls, in list order.  `as_u16`: see `render`."""
+        return scene_render.render_many(self, enc, targets, as_u8, as_u16)
 
     @torch.no_grad()
     def prefetch(self, enc, targets):

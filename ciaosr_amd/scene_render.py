@@ -98,11 +98,12 @@ def refuse_ensemble(enc, what):
                          f'or encode without self_ensemble')
 
 
-def render_ensemble(r, enc, targets, as_u8=False, many=False):
+def render_ensemble(r, enc, targets, as_u8=False, many=False, as_u16=False):
     """The `scene.Grid` targets of an ensemble record: member k renders the `scene.dihedral_window` of each target from its own scenes
     (`many`: all of them in one `render_many` per member, else the single call), and the results are averaged back in member order by
     `hip_ops.dihedral_accum` into one fp32 accumulator per target -- bitwise the window of `restore(..., self_ensemble=enc.ids)`.
-    Quantised once, after the mean, with `as_u8`.  A `scene.View` is a ValueError."""
+    Quantised once, after the mean, with `as_u8` or `as_u16`.  A `scene.View` is a ValueError."""
+    check_quant(enc, as_u8, as_u16)
     targets = list(targets)
     if not targets:
         raise ValueError('no targets: give a list of scene.Grid')
@@ -126,8 +127,8 @@ def render_ensemble(r, enc, targets, as_u8=False, many=False):
                 accs[j] = torch.empty(*out.shape[:2], *resolved[j][2][2:], dtype=torch.float32, device=out.device)
             hip_ops.dihedral_accum(accs[j], out, k, first=(i == 0), divisor=float(n) if i == n - 1 else 0.0)
         del outs
-    if as_u8:
-        return [_quantise(acc, grey=is_grey(enc)) for acc in accs]
+    if as_u8 or as_u16:
+        return [_quantise(acc, grey=is_grey(enc), u16=as_u16) for acc in accs]
     return accs
 
 
@@ -144,10 +145,22 @@ def is_grey(enc):
     return bool(getattr(enc, 'grey', False))
 
 
-def _quantise(out, alpha=False, grey=False):
+def check_quant(enc, as_u8, as_u16):
+    """ValueError, before any device work, for the sample types a render cannot have: both at once, or 16 bits with alpha."""
+    if as_u8 and as_u16:
+        raise ValueError('as_u8 and as_u16 together: a render is quantised once, to 8 or to 16 bits per sample')
+    if as_u16 and is_alpha(enc):
+        raise ValueError('as_u16 on an encode_rgba record: there is no 16-bit alpha (PNG colour type 6 at depth 16 is not built); '
+                         'render with as_u8, or encode the colour image alone')
+
+
+def _quantise(out, alpha=False, grey=False, u16=False):
     """The ONE place a render becomes bytes, after everything fp32 (the tile blend, the view fill, the self-ensemble mean): BGR, BGRA
-    of the (colour, alpha) pair of an RGBA encode, or one grey byte per pixel of a grey encode."""
+    of the (colour, alpha) pair of an RGBA encode, or one grey byte per pixel of a grey encode.  `u16`: uint16 samples, BGR or grey
+    (`metrics_hip.tensor2img_u16` / `tensor2img_grey_u16`; `check_quant` has refused alpha)."""
     from . import metrics_hip
+    if u16:
+        return metrics_hip.tensor2img_grey_u16(out) if grey else metrics_hip.tensor2img_u16(out)
     if grey:
         return metrics_hip.tensor2img_grey_u8(out)
     return metrics_hip.tensor2img_bgra_u8(out) if alpha else metrics_hip.tensor2img_u8(out)
@@ -314,18 +327,18 @@ def resolve(r, enc, targets):
     return out
 
 
-def _stacked(outs, as_u8, alpha=False, grey=False):
-    """The items' outputs as one tensor; with `as_u8` the 8-bit image (`_quantise`)."""
+def _stacked(outs, as_u8, alpha=False, grey=False, as_u16=False):
+    """The items' outputs as one tensor; with `as_u8` the 8-bit image, with `as_u16` the 16-bit one (`_quantise`)."""
     out = torch.stack(outs)
-    return _quantise(out, alpha, grey) if as_u8 else out
+    return _quantise(out, alpha, grey, bool(as_u16)) if (as_u8 or as_u16) else out
 
 
 # -- one target: scenes from the cache, tile by tile ------------------------------------------------------------------------------------
-def render_one(r, enc, tg, as_u8=False):
+def render_one(r, enc, tg, as_u8=False, as_u16=False):
     """The single calls `render` / `render_view`, of a resolved target: per batch item, every scene taken with `enc.cache.get` when its
     tile's turn comes -- no walk, no batched trunk, no side stream."""
     if isinstance(tg, GridTarget) and tg.tiles is None:
-        return _stacked(tg.render_whole(r, enc), as_u8, is_alpha(enc), is_grey(enc))
+        return _stacked(tg.render_whole(r, enc), as_u8, is_alpha(enc), is_grey(enc), as_u16)
     outs = []
     for b in range(enc.x.shape[0]):
         if isinstance(tg, ViewTarget):
@@ -334,7 +347,7 @@ def render_one(r, enc, tg, as_u8=False):
         for k, origin in tg.touched().items():
             tg.query(r.generator, k, enc.cache.get((b, origin)), acc)
         outs.append(_finish(tg, r, enc, b, acc))
-    return _stacked(outs, as_u8, is_alpha(enc), is_grey(enc))
+    return _stacked(outs, as_u8, is_alpha(enc), is_grey(enc), as_u16)
 
 
 # -- many targets from one walk over the tile scenes ------------------------------------------------------------------------------------
@@ -391,12 +404,13 @@ def scene_walk(r, enc, b, tiles):
         trunks.close()
 
 
-def render_many(r, enc, targets, as_u8=False):
+def render_many(r, enc, targets, as_u8=False, as_u16=False):
+    check_quant(enc, as_u8, as_u16)
     if is_ensemble(enc):
-        return render_ensemble(r, enc, targets, as_u8, many=True)
+        return render_ensemble(r, enc, targets, as_u8, many=True, as_u16=as_u16)
     x = enc.x
     if not enc.tile or tuple(x.shape[-2:]) == (enc.tile, enc.tile):     # one frame: no schedule to make
-        return [render_one(r, enc, tg, as_u8) for tg in resolve(r, enc, targets)]
+        return [render_one(r, enc, tg, as_u8, as_u16) for tg in resolve(r, enc, targets)]
     tgs, walk, users = plan_many(r, enc, targets)
     outs = [[] for _ in tgs]
     for b in range(x.shape[0]):
@@ -406,7 +420,7 @@ def render_many(r, enc, targets, as_u8=False):
                 tgs[i].query(r.generator, k, tile_scene, acc[i])
         for i, tg in enumerate(tgs):
             outs[i].append(_finish(tg, r, enc, b, acc[i]))
-    return [_stacked(o, as_u8, is_alpha(enc), is_grey(enc)) for o in outs]
+    return [_stacked(o, as_u8, is_alpha(enc), is_grey(enc), as_u16) for o in outs]
 
 
 def prefetch(r, enc, targets):

@@ -939,6 +939,75 @@ int ciaosr_deflate_lz_u8(const unsigned char* data, const unsigned long long* ba
                          unsigned char* out, size_t out_capacity, unsigned long long* seg_offsets, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- 16-bit samples: uint16 images and their PNG files of bit depth 16 (version 350) -------------------------------------
+ * A 16-bit sample is q16(v) = rint(fp32(clamp(v, 0, 1) * 65535)): ciaosr_tensor2img_u8's rule with 65535 for 255 (one fp32 multiply,
+ * round half to even, NaN -> 0).  An 8-bit level k / 255 becomes exactly 257 k; in general the 16-bit image is NOT the 8-bit image
+ * shifted left, and its high byte is NOT ciaosr_tensor2img_u8's byte.  Samples are native (little-endian) uint16 in memory; every
+ * pitch is in BYTES and, like every image pointer, EVEN (CIAOSR_ERR_BAD_ARG otherwise) -- the only alignment asked for: a crop of a
+ * larger image may start at any pixel.
+ * ciaosr_tensor2img_u16: src_chw fp32 [3][H][W] RGB -> the three samples of pixel (y, x) at byte y * dst_pitch + 6 x in B G R order,
+ * dst_pitch >= 6 W.  ciaosr_tensor2img_grey_u16: one sample at byte y * dst_pitch + 2 x, dst_pitch >= 2 W:
+ * L16 = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel's three 16-bit samples in unsigned 32-bit arithmetic (the largest
+ * intermediate is 65535 * 65536 + 32768 < 2^32; the weights are the 8-bit grey byte's, a neutral v, v, v gives v).
+ * ciaosr_grey_from_bgr_u16: the same reduction from a 16-bit image of three samples per pixel, pitch >= 6 W; bgr_flag as for the
+ * 8-bit call.  H <= 65535. */
+int ciaosr_tensor2img_u16(const float* src_chw, int H, int W, unsigned short* dst_hwc, size_t dst_pitch, void* stream);
+int ciaosr_tensor2img_grey_u16(const float* src_chw, int H, int W, unsigned short* dst, size_t dst_pitch, void* stream);
+int ciaosr_grey_from_bgr_u16(const unsigned short* bgr, size_t pitch, int bgr_flag, int H, int W, unsigned short* dst, size_t dst_pitch,
+                             void* stream);
+/* The PNG calls at bit depth 16, with the arguments and contracts of their 8-bit namesakes (ciaosr_png_*, ciaosr_png_lz_*):
+ * ciaosr_png16_* for three samples per pixel (colour type 2; bgr = 1: B G R as ciaosr_tensor2img_u16 orders them, 0: R G B) and
+ * ciaosr_png16_grey_* for one (colour type 0; bgr must be 0 or 1 and is not read).  With C = 3 or 1: pitch >= 2 C W bytes; a row of
+ * the stream is 1 + 2 C W bytes, the filter type and then every sample BIG-endian, in R G B order; rows of one band: rows_per_band if
+ * > 0, else max(1, 131072 / (2 C W + 1)).  The five filters work per BYTE, as the PNG specification says: the left predecessor of a
+ * byte is the byte 2 C back (bpp = 6 or 2), the upper one the same byte of the row above, zeros left of column 0 and above row 0 (of a
+ * crop too) -- nothing is borrowed between the two bytes of a sample.  The filter choice (smallest sum of min(b, 256 - b) over the
+ * row's bytes, ties to the lowest number), the histograms, the Adler partials and the plan, scan and pack stages are the 8-bit calls'
+ * own on these rows; the match candidates of the *_lz_* entries are 1, 2, 3, 4, 6, 8, 12, 16, L - 2 C, L, L + 2 C with L = 1 + 2 C W.
+ * Tile t is byte for byte the single call on the pitched crop at byte y0 * pitch + 2 C x0.  The host wraps a stream with IHDR bit
+ * depth 16.  (The names say png16_, not png_: the size exports whose values tests/golden/png_sizes.json records are the 8-bit ones.) */
+int ciaosr_png16_rows_per_band(int W, int rows_per_band);
+int ciaosr_png16_filter_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* dst,
+                            unsigned int* hist, unsigned int* adler, void* stream);
+size_t ciaosr_png16_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png16_lz_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png16_capacity_bytes(int H, int W, int rows_per_band);
+int ciaosr_png16_encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                            size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_png16_lz_encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                               size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes,
+                               void* stream);
+size_t ciaosr_png16_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png16_lz_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png16_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png16_encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/, int n_tiles,
+                                  int rows_per_band, unsigned char* out, size_t out_capacity, unsigned long long* tile_offs,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_png16_lz_encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/,
+                                     int n_tiles, int rows_per_band, unsigned char* out, size_t out_capacity,
+                                     unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_png16_grey_rows_per_band(int W, int rows_per_band);
+int ciaosr_png16_grey_filter_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* dst,
+                                 unsigned int* hist, unsigned int* adler, void* stream);
+size_t ciaosr_png16_grey_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png16_grey_lz_workspace_bytes(int H, int W, int rows_per_band);
+size_t ciaosr_png16_grey_capacity_bytes(int H, int W, int rows_per_band);
+int ciaosr_png16_grey_encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band, unsigned char* out,
+                                 size_t out_capacity, unsigned long long* total_bytes, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int ciaosr_png16_grey_lz_encode_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, int rows_per_band,
+                                    unsigned char* out, size_t out_capacity, unsigned long long* total_bytes, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+size_t ciaosr_png16_grey_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png16_grey_lz_tiles_workspace_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+size_t ciaosr_png16_grey_tiles_capacity_bytes(const int* rects /*host*/, int n_tiles, int rows_per_band);
+int ciaosr_png16_grey_encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/,
+                                       int n_tiles, int rows_per_band, unsigned char* out, size_t out_capacity,
+                                       unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_png16_grey_lz_encode_tiles_u16(const unsigned short* src, size_t pitch, int H, int W, int bgr, const int* rects /*host*/,
+                                          int n_tiles, int rows_per_band, unsigned char* out, size_t out_capacity,
+                                          unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Baseline JPEG encoding of 8-bit images (ciaosr_amd/jpeg_hip.py; DESIGN 4.1i-d holds the format contract) ----------------------
  * The device makes the entropy-coded data of ONE interleaved scan of a baseline file -- libjpeg's integer pipeline as Pillow drives
  * it: 16-bit fixed-point RGB -> YCbCr, 4:4:4 or 4:2:0 with the h2v2 box filter, the "islow" forward DCT, the Annex K tables scaled by

@@ -73,6 +73,16 @@ three-channel device call on the (v, v, v) image of the same run, (c) the copy t
 alternating in one process, 2 warm-up + 5 timed rounds; wall times, the kernel times of (a) and (b) (a profiled call of their own) and the
 file bytes of all three are recorded; the PNG pixels of (a) and (c) and the JPEG bytes of (a) and (c) are compared.  Default --out:
 profiles/grey_codecs.txt.
+
+    python tools/png_probe.py --leg depth16 [--sizes 5424x8160 768x768] [--out FILE]
+
+Depth-16 PNG files from torch.uint16 device images: `tensor2img_u16` (RGB16) and `tensor2img_grey_u16` (grey16) of the fp32 synthetic
+image, as is ('smooth') and with Gaussian noise of two 8-bit levels ('noisy'), with `matches` off and on.  (a) the 16-bit device call;
+(b) the 8-bit device call on the `tensor2img_u8` / `tensor2img_grey_u8` image of the same fp32 data; (c) for grey only, the copy to
+the host + `PIL.Image.save` of the `I;16` image (Pillow has no 16-bit RGB writer, so RGB has no host leg).  Legs alternating in one
+process, 2 warm-up + 5 timed rounds, wall time from the device image to the file's bytes; the kernel times of (a) and (b) come from a
+profiled call of their own; the file bytes are held against the raw 2 C H W and, for grey, against Pillow's, whose decoded samples are
+compared.  Default --out: profiles/png_depth16.txt.
 """
 import json
 import subprocess
@@ -461,6 +471,63 @@ def grey_leg(args, say):
             del grey, wide
 
 
+def depth16_leg(args, say):
+    """The 16-bit device calls against the 8-bit device calls on the same fp32 data and, for grey, copy + PIL save of the I;16 image."""
+    import io
+    from PIL import Image
+    from ciaosr_amd.init_utils import synthetic_gt
+    from ciaosr_amd.metrics_hip import tensor2img_grey_u16, tensor2img_grey_u8, tensor2img_u16, tensor2img_u8
+    from ciaosr_amd.png_hip import encode_png
+    dev = torch.device('cuda', torch.cuda.current_device())
+
+    def pil_i16(img):
+        bio = io.BytesIO()
+        Image.fromarray(img.cpu().numpy()).save(bio, format='PNG')                 # uint16 [H, W]: mode I;16
+        return bio.getvalue()
+
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        for content in args.contents:
+            fp = synthetic_gt(h, w).to(dev)
+            if content == 'noisy':
+                g = torch.Generator(device='cpu').manual_seed(h * 7 + w)
+                for ch in range(3):                                                    # plane by plane: the host noise of one plane at a time
+                    fp[..., ch, :, :] += (torch.randn(h, w, generator=g) * (2.0 / 255.0)).to(dev)
+            images = {'grey16': (tensor2img_grey_u16(fp), tensor2img_grey_u8(fp)), 'RGB16': (tensor2img_u16(fp), tensor2img_u8(fp))}
+            del fp
+            torch.cuda.synchronize()
+            for kind, (im16, im8) in images.items():
+                raw = im16.numel() * 2
+                for lz in (False, True):
+                    legs = {'a': lambda: encode_png(im16, matches=lz), 'b': lambda: encode_png(im8, matches=lz)}
+                    if kind == 'grey16':
+                        legs['c'] = lambda: pil_i16(im16)
+                    times = run_legs(args, legs)
+                    mine, eight = legs['a'](), legs['b']()
+                    line = (f'{h} x {w} {content}, {kind}, matches={lz}: file bytes 16-bit {len(mine)}, raw 2 C H W {raw}, 16-bit / raw '
+                            f'{len(mine) / raw:.4f}; 8-bit file {len(eight)}, 16-bit / 8-bit {len(mine) / len(eight):.4f}')
+                    if 'c' in legs:
+                        pil = legs['c']()
+                        same = np.array_equal(np.asarray(Image.open(io.BytesIO(mine))), np.asarray(Image.open(io.BytesIO(pil))))
+                        line += f'; Pillow I;16 {len(pil)}, 16-bit / Pillow {len(mine) / len(pil):.4f}, decoded samples identical to Pillow\'s: {same}'
+                    say(line)
+                    say(f'  (a) 16-bit device call                    wall s: {stats(times["a"])}')
+                    say(f'  (b) 8-bit device call, same fp32 data     wall s: {stats(times["b"])}')
+                    if 'c' in legs:
+                        say(f'  (c) copy to the host + PIL save of I;16   wall s: {stats(times["c"])}')
+                    for other, what in (('b', '8-bit'), ('c', 'host')):
+                        if other not in legs:
+                            continue
+                        gap = statistics.mean(times[other]) - statistics.mean(times['a'])
+                        spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', other))
+                        say(f'  ({other}) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                            f'{"16-bit call faster beyond the spread" if gap > spread else (what + " call faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                            f'ratio ({other}) / (a) {statistics.mean(times[other]) / statistics.mean(times["a"]):.2f}x')
+                    say(f'  (a) kernels: {kernels(legs["a"])}')
+                    say(f'  (b) kernels: {kernels(legs["b"])}')
+            del images, im16, im8
+
+
 def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
@@ -628,7 +695,7 @@ def jpeg_prog_leg(args, say):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches', 'grey'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches', 'grey', 'depth16'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
@@ -659,6 +726,10 @@ def main(argv=None):
         args.sizes = args.sizes or ['5424x8160', '768x768']
         args.out = args.out or os.path.join(REPO, 'profiles', 'grey_codecs.txt')
         jpeg = True
+    if args.leg == 'depth16':                                # likewise
+        args.sizes = args.sizes or ['5424x8160', '768x768']
+        args.out = args.out or os.path.join(REPO, 'profiles', 'png_depth16.txt')
+        jpeg = True
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['768x768', '5424x8160'] if rgba else ['5424x8160', '768x768'])
     args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_matches.txt' if args.leg == 'matches' else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
     from ciaosr_amd import _lib, hip_ops
@@ -687,6 +758,8 @@ def main(argv=None):
         jpeg_prog_leg(args, say)
     if grey:
         grey_leg(args, say)
+    if args.leg == 'depth16':
+        depth16_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
         for size in ([] if tiles or jpeg or rgba else args.sizes):
             h, w = (int(v) for v in size.split('x'))

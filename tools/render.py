@@ -52,6 +52,12 @@ a grey .png (colour type 0), or with --jpeg Q [--jpeg-optimize] as a one-compone
 progressive files) or --jpeg-subsampling 420.
 `--png-matches` (only with --gpu-png, --alpha or --grey, never with --jpeg) lets the device PNG coder use LZ77 matches for every .png of the run,
 pyramid tiles included: transparent and filled regions then cost next to nothing, and no file gets larger (png_hip `matches=True`).
+`--depth16` keeps 16 bits per sample: the input is read with the 16-bit readers (ciaosr_amd.imageio.imread16_rgb01, or imread16_grey01
+with --grey: depth-16 PNG files and 16-bit grey TIFF as sample / 65535, any other file as without the flag) and its bit depth is
+printed; every --scale, --window and --view output is rendered as a torch.uint16 image on the device (`as_u16`: each sample
+rint(clamp(v, 0, 1) * 65535), quantised once) and written as a PNG of bit depth 16 by the device coder, colour type 2, or 0 with
+--grey.  An 8-bit input is allowed: the output then keeps the model's precision.  --png-matches and --self-ensemble work with it.
+Not with --jpeg, --alpha, --dzi or --niqe (an argparse error): those stay 8-bit.
 """
 import argparse
 import os
@@ -91,6 +97,9 @@ def parse_args(argv=None):
                    help='keep the transparency of the input: alpha goes through the model as a grey image, outputs are RGBA PNG files (default off)')
     p.add_argument('--grey', action='store_true',
                    help='the input is a single-channel image: outputs are grey .png (or one-component .jpg) files coded on the GPU (default off)')
+    p.add_argument('--depth16', action='store_true',
+                   help='16 bits per sample: read the input at full precision, write uint16 renders as PNG files of bit depth 16 coded on '
+                        'the GPU (not with --jpeg, --alpha, --dzi or --niqe; default off)')
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
@@ -121,8 +130,13 @@ def parse_args(argv=None):
         p.error('--grey with --jpeg-progressive: there are no one-component progressive files here, drop --jpeg-progressive')
     if args.grey and args.jpeg is not None and args.jpeg_subsampling != '444':
         p.error('--grey has no chroma to subsample: drop --jpeg-subsampling')
-    if args.png_matches and not (args.gpu_png or args.alpha or args.grey):
-        p.error('--png-matches belongs to --gpu-png, --alpha or --grey, whose files the device codes')
+    if args.depth16:
+        for flag, given in (('--jpeg', args.jpeg is not None), ('--alpha', args.alpha), ('--dzi', args.dzi is not None),
+                            ('--niqe', args.niqe is not None)):
+            if given:
+                p.error(f'--depth16 with {flag}: JPEG, alpha, pyramids and NIQE stay 8-bit here, drop one of the two')
+    if args.png_matches and not (args.gpu_png or args.alpha or args.grey or args.depth16):
+        p.error('--png-matches belongs to --gpu-png, --alpha, --grey or --depth16, whose files the device codes')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
     if args.jpeg_progressive and args.jpeg is None:
@@ -156,7 +170,7 @@ def main(argv=None):
     from ciaosr_amd import metrics
     from ciaosr_amd.checkpoint import load_checkpoint
     from ciaosr_amd.config import Config
-    from ciaosr_amd.imageio import imread_grey01, imread_rgb01, imread_rgba01, imwrite
+    from ciaosr_amd.imageio import imread16_grey01, imread16_rgb01, imread_grey01, imread_rgb01, imread_rgba01, imwrite
 
     cfg = Config.fromfile(args.config)
     if args.checkpoint in (None, 'None'):
@@ -187,13 +201,22 @@ def main(argv=None):
     if alpha:
         enc = model.encode_rgba(lq4.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted))
     elif args.grey:
-        lq1, was_grey = imread_grey01(args.image)
+        if args.depth16:
+            lq1, was_grey, bits = imread16_grey01(args.image)
+            print(f'{args.image}: {bits} bits per sample')
+        else:
+            lq1, was_grey = imread_grey01(args.image)
         if not was_grey:
             print(f'{args.image}: not a grey image, --grey keeps its luma (convert("L")) only')
         ens = dict(self_ensemble=True) if args.self_ensemble else {}
         enc = model.encode_grey(lq1.unsqueeze(0).to(dev), max_scale=args.max_scale or max(wanted), **ens)
     else:
-        lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
+        if args.depth16:
+            lq, bits = imread16_rgb01(args.image)
+            print(f'{args.image}: {bits} bits per sample')
+            lq = lq.unsqueeze(0).to(dev)
+        else:
+            lq = imread_rgb01(args.image).unsqueeze(0).to(dev)
         ens = dict(self_ensemble=True) if args.self_ensemble else {}                 # without --self-ensemble encode is called as before
         enc = model.encode(lq, max_scale=args.max_scale or max(wanted), **ens)
     name = os.path.splitext(os.path.basename(args.image))[0]
@@ -210,8 +233,9 @@ def main(argv=None):
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
-    as_u8 = gpu_png or form['fmt'] == 'jpg' or alpha or args.grey
-    outs = model.render_many(enc, targets, as_u8=as_u8) if targets else []           # one walk over the tile scenes for every output
+    as_u8 = (gpu_png or form['fmt'] == 'jpg' or alpha or args.grey) and not args.depth16
+    quant = dict(as_u16=True) if args.depth16 else dict(as_u8=as_u8)                 # without --depth16 render_many is called as before
+    outs = model.render_many(enc, targets, **quant) if targets else []               # one walk over the tile scenes for every output
     scores = {}
     if args.niqe and targets:
         from ciaosr_amd import niqe_hip
@@ -228,7 +252,11 @@ def main(argv=None):
             except ValueError:                                         # fewer than two blocks (or fewer than two without a NaN)
                 scores[os.path.basename(path)] = None
             print(f'{path}: NIQE {scores[os.path.basename(path)]}')
-        if form['fmt'] == 'jpg':
+        if args.depth16:
+            from ciaosr_amd.png_hip import imwrite_gpu
+            imwrite_gpu(out, path, **lz)                               # uint16 [H, W, 3] BGR (--grey: [H, W]) on the device
+            print(f'{path}: {out.shape[0]} x {out.shape[1]}{" grey" if args.grey else ""}, 16 bits per sample')
+        elif form['fmt'] == 'jpg':
             from ciaosr_amd.jpeg_hip import imwrite_gpu_jpeg
             imwrite_gpu_jpeg(out, path, **coding)                      # uint8 [H, W, 3] BGR (--grey: [H, W]) on the device
             print(f'{path}: {out.shape[0]} x {out.shape[1]}')
