@@ -264,6 +264,15 @@ SIGNATURES = {
         ('tiles_capacity_bytes', (_S, [_P, _I, _I])),
         ('encode_tiles_u16', (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P])),
         ('lz_encode_tiles_u16', (_I, [_P, _S, _I, _I, _I, _P, _I, _I, _P, _S, _P, _P, _S, _P])))},
+    # deflate tiles of a pyramidal TIFF level (version 360): bytes per pixel first, then the image as for the PNG tiles, the tile side
+    # for the rects; the box halving of the 16-bit levels below the LR size
+    'ciaosr_tiff_rows_per_band': (_I, [_I, _I, _I]),
+    'ciaosr_tiff_tiles_workspace_bytes': (_S, [_I, _I, _I, _I, _I]),
+    'ciaosr_tiff_lz_tiles_workspace_bytes': (_S, [_I, _I, _I, _I, _I]),
+    'ciaosr_tiff_tiles_capacity_bytes': (_S, [_I, _I, _I, _I, _I]),
+    'ciaosr_tiff_encode_tiles': (_I, [_I, _P, _S, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_tiff_lz_encode_tiles': (_I, [_I, _P, _S, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),
+    'ciaosr_halve_box_u16': (_I, [_P, _S, _I, _I, _I, _P, _S, _P]),
     'ciaosr_jpeg_workspace_bytes': (_S, [_I, _I, _I, _I]),
     'ciaosr_jpeg_capacity_bytes': (_S, [_I, _I, _I]),
     'ciaosr_jpeg_encode_u8': (_I, [_P, _S, _I, _I, _I, _I, _I, _I, _P, _S, _P, _P, _S, _P]),

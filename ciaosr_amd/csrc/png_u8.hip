@@ -45,6 +45,9 @@
 // launch + launch_status, and run_deflate() is the one launch sequence -- plan, scan, pack, and around them the match coder's memset,
 // parse, plan and packer when an LzP is given -- for encode_entry, encode_tiles_entry and deflate_entry.  The extern "C" exports are
 // one-line forwards to these bodies, in one block at the end.
+//
+// tiff_tiles.h, included at the very end, is the second front end of the same coder: the horizontal predictor over the fixed-size,
+// edge-padded tiles of a TIFF level (Compression 8, Predictor 2), with entries and exports of its own (ciaosr_tiff_*).
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -908,8 +911,8 @@ static_assert(31 + kLzChunk * kLitLimit < 32 * (kWin - 1) && kLzHdrWords + 2 < k
 struct LzP {
     DeflateP d;                   // the literal coder's call: data, bands and tiles; mode and seg_bytes hold deflate_plan_kernel's choice
                                   // (mode 2 where matches are smaller); out_offs and out as the scan left them
-    const int* rects;             // with d.tiles: the line of a band is its tile's, 1 + bpp w
-    u64 line;                     // otherwise: every band's line, 0 = none
+    const int* rects;             // the crops of the PNG tiles: the line of a band is its tile's, 1 + bpp w
+    u64 line;                     // without rects (one image; TIFF tiles, tiff_tiles.h): every band's line, 0 = none
     int bpp;
     u64 base0;                    // the first band's offset in data: token slots are counted from there
     const u32* chunk_first;       // [nb + 1] first chunk of every band, or null: uniform bands of cpb chunks
@@ -924,7 +927,7 @@ struct LzP {
 };
 
 __device__ __forceinline__ u64 lz_line(const LzP& p, int band) {
-    return p.d.tiles ? 1ull + (u64)p.bpp * (u64)p.rects[4 * (size_t)p.d.tiles[band].tile + 3] : p.line;
+    return p.rects ? 1ull + (u64)p.bpp * (u64)p.rects[4 * (size_t)p.d.tiles[band].tile + 3] : p.line;
 }
 // candidate c of a band with scanline length `line`: its distance, 0 when there is none
 __device__ __forceinline__ u32 lz_distance(int c, u64 line, int bpp) {
@@ -1928,3 +1931,5 @@ extern "C" int ciaosr_png_grey_lz_encode_tiles_u8(const unsigned char* src, size
 CIAOSR_PNG16_EXPORTS(ciaosr_png16_, 6)
 CIAOSR_PNG16_EXPORTS(ciaosr_png16_grey_, 2)
 #undef CIAOSR_PNG16_EXPORTS
+
+#include "tiff_tiles.h"

@@ -10,6 +10,9 @@ PNG tiles (colour type 0) or one-component JPEG tiles -- not progressive ones --
 Deep Zoom's rules: Lmax = ceil(log2(max(W, H))), levels 0..Lmax; level L is max(1, ceil(W / 2^(Lmax - L))) wide and as high by the same
 rule; on a level, column c spans [c T - (O if c > 0 else 0), min((c + 1) T + O, Wl)) for the tile size T and the overlap O, rows alike,
 ceil(Wl / T) columns.
+
+`write_tiff` writes the same render as ONE pyramidal tiled TIFF instead (tiff_hip.py: an image file directory per level, deflate tiles
+with the horizontal predictor, 8 or 16 bits per sample); `write_dzi`, `write_levels` and `FORMATS` do not know of it.
 """
 import os
 import time
@@ -178,3 +181,53 @@ def write_dzi(model, enc, out_dir, name, scale=None, size=None, tile_size=254, o
     res = write_levels(levels, out_dir, name, tile_size, overlap, order, fmt, quality, subsampling, optimize, **coding)
     res.update(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w], render_s=render_s)
     return res
+
+
+def check_tiff(enc, tile=256, depth=8, matches=False):
+    """The ValueErrors of `write_tiff`, before any device work: the tile rule, a depth other than 8 or 16, 16 bits on an
+    `encode_rgba` record, a record that is grey AND alpha, a non-bool `matches`, an ensemble record."""
+    from . import tiff_hip
+    tiff_hip.check_tile(tile)
+    if isinstance(depth, bool) or depth not in (8, 16):
+        raise ValueError(f'depth={depth!r}: 8 or 16')
+    if not isinstance(matches, bool):
+        raise ValueError(f'matches must be True or False, got {matches!r}')
+    alpha, grey = bool(getattr(enc, 'alpha', False)), bool(getattr(enc, 'grey', False))
+    if depth == 16 and alpha:
+        raise ValueError('depth=16 on an encode_rgba record: there is no 16-bit alpha; write the file with depth=8')
+    if grey and alpha:
+        raise ValueError('a grey + alpha record has no TIFF form here (nor a PNG one)')
+    from .scene_render import refuse_ensemble
+    refuse_ensemble(enc, 'write_tiff')
+
+
+def write_tiff(model, enc, path, scale=None, size=None, tile=256, depth=8, order='bgr', matches=False):
+    """The pyramidal tiled TIFF `path` (tiff_hip.py: one IFD per level, deflate tiles of `tile` x `tile` with the horizontal predictor)
+    of the `size` / `scale` render of `enc`.  The levels are `model.render_pyramid`'s -- with `depth=16` its `as_u16` ones -- from the top
+    down to the first that fits one tile (`tiff_hip.tiff_level_sizes`): a level at or above the LR size is the model's own answer,
+    the ones below are Pillow-exact bicubic resizes of the smallest model level at 8 bits and a chain of box halvings at 16.  Each
+    level's tiles are coded in one set of launches and read in two synchronising copies.  `order`: the byte order of the rendered
+    images, 'bgr' as `render_pyramid` makes them.  `matches=True`: the match coder for every tile (edge padding then costs next to
+    nothing).  -> dict: levels [(H_l, W_l)] top first, model_levels, tiles, bytes, and the seconds render_s (to the last launch, not
+    synchronised), encode_s, write_s."""
+    from . import tiff_hip
+    check_tiff(enc, tile, depth, matches)
+    t0 = time.perf_counter()
+    levels = model.render_pyramid(enc, size=size, scale=scale, **(dict(as_u16=True) if depth == 16 else {}))
+    render_s = time.perf_counter() - t0
+    top = levels[-1]
+    sizes = tiff_hip.tiff_level_sizes(top.shape[0], top.shape[1], tile)
+    levels = levels[::-1][:len(sizes)]                                         # render_pyramid lists the 1 x 1 level first
+    if [(im.shape[0], im.shape[1]) for im in levels] != sizes:
+        raise ValueError(f'the rendered levels are not those of a {top.shape[0]} x {top.shape[1]} pyramid')
+    t1 = time.perf_counter()
+    plan, coded = tiff_hip._encode_file(levels, tile, order, 0, matches)
+    t2 = time.perf_counter()
+    os.makedirs(os.path.dirname(os.path.abspath(path)) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        for piece in tiff_hip._pieces(plan, coded):
+            f.write(piece)
+    h, w = enc.x.shape[-2:]
+    return dict(levels=sizes, model_levels=[k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w],
+                tiles=sum(len(o) - 1 for _, o in coded), bytes=plan['total'], render_s=render_s, encode_s=t2 - t1,
+                write_s=time.perf_counter() - t2)

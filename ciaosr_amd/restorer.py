@@ -585,13 +585,20 @@ class CiaoSR(BasicRestorer):
         return scene_render.prefetch(self, enc, targets)
 
     @torch.no_grad()
-    def render_pyramid(self, enc, size=None, scale=None):
+    def render_pyramid(self, enc, size=None, scale=None, as_u16=False):
         """The levels of the Deep Zoom pyramid (pyramid.py) whose top is the `size` / `scale` render of `enc`: list of uint8 [H_l, W_l, 3]
         device images (`render(..., as_u8=True)`'s), level 0 (1 x 1) first.  A level at least as large as the LR image on both sides is a
         model level: all of them are Grid(size=(H_l, W_l)) targets of ONE `render_many`, hence one walk over the tile scenes, and each is
         bitwise `render(enc, size=(H_l, W_l), as_u8=True)`.  Every smaller level is `degrade.resize_bicubic_u8` -- Pillow's BICUBIC
         resize, exactly -- of the smallest model level, each taken from it directly.  ValueError before any device work: a batch, a top
-        level below the LR size, `test_cfg.tile` without `tile_any_scale`, and whatever `scene.Grid` raises."""
+        level below the LR size, `test_cfg.tile` without `tile_any_scale`, and whatever `scene.Grid` raises.
+        `as_u16`: torch.uint16 levels ([H_l, W_l, 3] B G R, or [H_l, W_l] on an `encode_grey` record).  The model levels are the
+        `as_u16` targets of the one `render_many`, each bitwise `render(enc, size=(H_l, W_l), as_u16=True)`; below the LR size every
+        level is the integer box halving of the level ABOVE it (`tiff_hip.halve_box_u16`: the rounded mean of 2 x 2 samples, the last
+        row / column repeated on odd sizes), a chain from the smallest model level -- not a bicubic resize: Pillow has no exact 16-bit
+        one to be held to.  On an `encode_rgba` record a ValueError (no 16-bit alpha).  Without the keyword nothing changes."""
+        if as_u16:
+            return scene_render.render_pyramid(self, enc, size, scale, as_u16=True)
         return scene_render.render_pyramid(self, enc, size, scale)
 
     def _plan_pyramid(self, enc, size=None, scale=None):

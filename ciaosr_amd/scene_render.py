@@ -457,8 +457,10 @@ def plan_pyramid(r, enc, size=None, scale=None):
     return sizes, min(k for k, (hl, wl) in enumerate(sizes) if hl >= h and wl >= w)
 
 
-def render_pyramid(r, enc, size=None, scale=None):
+def render_pyramid(r, enc, size=None, scale=None, as_u16=False):
     from . import degrade
+    if as_u16:
+        return render_pyramid_u16(r, enc, size, scale)
     sizes, first = plan_pyramid(r, enc, size, scale)
     model_levels = render_many(r, enc, [sc.Grid(size=s) for s in sizes[first:]], as_u8=True)
     base = model_levels[0]
@@ -477,3 +479,17 @@ def render_pyramid(r, enc, size=None, scale=None):
     small = [metrics_hip.pack_bgra_u8(degrade.resize_bicubic_u8(colour, (wl, hl)), degrade.resize_bicubic_u8(grey, (wl, hl)))
              for hl, wl in sizes[:first]]
     return small + list(model_levels)
+
+
+
+def render_pyramid_u16(r, enc, size=None, scale=None):
+    """`render_pyramid` with 16-bit samples: the model levels are the `as_u16` targets of the one `render_many`; below the LR size every
+    level is the integer box halving (`tiff_hip.halve_box_u16`) of the level above, a chain that starts at the smallest model level."""
+    from . import tiff_hip
+    check_quant(enc, False, True)                                       # an RGBA record: no 16-bit alpha, before any device work
+    sizes, first = plan_pyramid(r, enc, size, scale)
+    model_levels = list(render_many(r, enc, [sc.Grid(size=s) for s in sizes[first:]], as_u16=True))
+    small = []
+    for _ in sizes[:first]:
+        small.append(tiff_hip.halve_box_u16(small[-1] if small else model_levels[0]))
+    return small[::-1] + model_levels

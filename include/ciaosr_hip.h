@@ -1008,6 +1008,40 @@ int ciaosr_png16_grey_lz_encode_tiles_u16(const unsigned short* src, size_t pitc
                                           int n_tiles, int rows_per_band, unsigned char* out, size_t out_capacity,
                                           unsigned long long* tile_offs, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Deflate tiles of a pyramidal TIFF level (version 360; ciaosr_amd/tiff_hip.py; DESIGN 4.1i-b7 holds the format contract) ----------
+ * A level is cut into T x T tiles (T a multiple of 16 in 16..4096), row-major, ceil(W / T) x ceil(H / T); a tile that reaches past the
+ * image repeats its last column and row: P[r][c][k] = I[min(ty T + r, H - 1)][min(tx T + c, W - 1)][k], I the samples in stream order
+ * (bgr = 1: the image holds B G R [A] and the stream R G B [A]; 0: as stored; one grey sample: bgr is checked and not read).  The
+ * horizontal predictor (TIFF Predictor = 2) works per SAMPLE of S = 8 or 16 bits: D[r][0][k] = P[r][0][k],
+ * D[r][c][k] = (P[r][c][k] - P[r][c - 1][k]) mod 2^S; the bytes are r, then c, then k, a 16-bit sample low byte first.  Tile t's data
+ * (Compression = 8) is ONE zlib stream of those T * T * bytes_per_pixel bytes, out[tile_offs[t] : tile_offs[t + 1]], made by the PNG
+ * calls' coder on lines of bytes_per_pixel * T bytes (no filter byte): the contracts of ciaosr_png_encode_tiles_u8 for out, capacity,
+ * tile_offs (DEVICE, [tiles + 1], 8-byte aligned), workspace and stream hold, and the host reads tile_offs, then the bytes.
+ * bytes_per_pixel: 1, 3, 4 (uint8 grey, RGB, RGBA) or 2, 6 (native uint16 grey, RGB); pitch in bytes, >= bytes_per_pixel * W; four
+ * bytes per pixel are read as aligned 32-bit words, 16-bit samples as aligned 16-bit ones (image and pitch multiples of 4 / of 2).
+ * Every source index is clamped: nothing is read past row H - 1 or column W - 1.  rows_per_band: tile rows per independently coded
+ * band, at most T; 0 = max(1, min(T, 131072 / (bytes_per_pixel * T))).  ciaosr_tiff_lz_*: the match coder (ciaosr_png_lz_*), far
+ * candidates L - bytes_per_pixel, L, L + bytes_per_pixel with L = bytes_per_pixel * T -- a padding row is a repeat at distance L; no
+ * stream is longer than the literal coder's.  Launches per call, whatever the number of tiles: tiff_predict_tiles, deflate_plan,
+ * png_tiles_scan, deflate_pack; the match coder adds one memset, deflate_lz_match, deflate_lz_plan and deflate_lz_pack.
+ * The size functions return 0 for what the calls refuse (CIAOSR_ERR_BAD_ARG: bytes_per_pixel, T, H, W > 65535, a negative
+ * rows_per_band, alignment).
+ * ciaosr_halve_box_u16: uint16 [h][w][channels] (channels 1 or 3; pitches in bytes, even, >= one row) ->
+ * [ceil(h / 2)][ceil(w / 2)][channels]: out[i][j][k] = (a[2i][2j] + a[2i][j1] + a[i1][2j] + a[i1][j1] + 2) >> 2 with
+ * i1 = min(2i + 1, h - 1), j1 = min(2j + 1, w - 1), in unsigned 32-bit arithmetic. */
+int ciaosr_tiff_rows_per_band(int bytes_per_pixel, int T, int rows_per_band);
+size_t ciaosr_tiff_tiles_workspace_bytes(int bytes_per_pixel, int H, int W, int T, int rows_per_band);
+size_t ciaosr_tiff_lz_tiles_workspace_bytes(int bytes_per_pixel, int H, int W, int T, int rows_per_band);
+size_t ciaosr_tiff_tiles_capacity_bytes(int bytes_per_pixel, int H, int W, int T, int rows_per_band);
+int ciaosr_tiff_encode_tiles(int bytes_per_pixel, const void* image, size_t pitch, int H, int W, int bgr, int T, int rows_per_band,
+                             unsigned char* out, size_t out_capacity, unsigned long long* tile_offs, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int ciaosr_tiff_lz_encode_tiles(int bytes_per_pixel, const void* image, size_t pitch, int H, int W, int bgr, int T, int rows_per_band,
+                                unsigned char* out, size_t out_capacity, unsigned long long* tile_offs, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int ciaosr_halve_box_u16(const unsigned short* src, size_t pitch, int h, int w, int channels, unsigned short* dst, size_t dst_pitch,
+                         void* stream);
+
 /* ---- Baseline JPEG encoding of 8-bit images (ciaosr_amd/jpeg_hip.py; DESIGN 4.1i-d holds the format contract) ----------------------
  * The device makes the entropy-coded data of ONE interleaved scan of a baseline file -- libjpeg's integer pipeline as Pillow drives
  * it: 16-bit fixed-point RGB -> YCbCr, 4:4:4 or 4:2:0 with the h2v2 box filter, the "islow" forward DCT, the Annex K tables scaled by

@@ -83,6 +83,17 @@ the host + `PIL.Image.save` of the `I;16` image (Pillow has no 16-bit RGB writer
 process, 2 warm-up + 5 timed rounds, wall time from the device image to the file's bytes; the kernel times of (a) and (b) come from a
 profiled call of their own; the file bytes are held against the raw 2 C H W and, for grey, against Pillow's, whose decoded samples are
 compared.  Default --out: profiles/png_depth16.txt.
+
+    python tools/png_probe.py --leg tiff [--sizes 5424x8160 768x768] [--tiff-tile 256] [--out FILE]
+
+Pyramidal tiled TIFF files (ciaosr_amd/tiff_hip.py) of the synthetic image as RGB8 (`tensor2img_u8`), RGB16 (`tensor2img_u16`) and
+grey16 (`tensor2img_grey_u16`).  The levels are made before the clock starts: Pillow-exact bicubic resizes of the top at 8 bits, the
+box-halving chain at 16.  (a) `encode_tiff` of all levels, `matches` off; (b) the same with `matches=True`; (c) the copy of the TOP
+level to the host + `PIL.Image.save(format='TIFF', compression='tiff_adobe_deflate')` -- Pillow writes strips and no pyramid, so (c)
+codes about three quarters of the samples of (a) and (b); it has no 16-bit RGB writer, so RGB16 has no host leg.  Legs alternating in
+one process, 2 warm-up + 5 timed rounds, wall time from the device images to the file's bytes; kernel times from a profiled call of
+their own; the file bytes are held against the raw bytes of all levels and against Pillow's, and the top page is read back through
+Pillow and compared.  Default --out: profiles/tiff_gpu.txt.
 """
 import json
 import subprocess
@@ -528,6 +539,74 @@ def depth16_leg(args, say):
             del images, im16, im8
 
 
+def tiff_leg(args, say):
+    """The device pyramid with and without matches against copy + PIL save of the top level as a deflate TIFF (strips, no pyramid)."""
+    import io
+    from PIL import Image
+    from ciaosr_amd import degrade, tiff_hip
+    from ciaosr_amd.init_utils import synthetic_gt
+    from ciaosr_amd.metrics_hip import tensor2img_grey_u16, tensor2img_u16, tensor2img_u8
+    dev = torch.device('cuda', torch.cuda.current_device())
+    tile = args.tiff_tile
+
+    def pil_tiff(top):
+        arr = top.cpu().numpy()
+        bio = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(arr[:, :, ::-1]) if arr.ndim == 3 else arr).save(bio, format='TIFF', compression='tiff_adobe_deflate')
+        return bio.getvalue()
+
+    for size in args.sizes:
+        h, w = (int(v) for v in size.split('x'))
+        sizes = tiff_hip.tiff_level_sizes(h, w, tile)
+        for content in args.contents:
+            fp = synthetic_gt(h, w).to(dev)
+            if content == 'noisy':
+                g = torch.Generator(device='cpu').manual_seed(h * 7 + w)
+                for ch in range(3):
+                    fp[..., ch, :, :] += (torch.randn(h, w, generator=g) * (2.0 / 255.0)).to(dev)
+            tops = {'RGB8': tensor2img_u8(fp), 'RGB16': tensor2img_u16(fp), 'grey16': tensor2img_grey_u16(fp)}
+            del fp
+            for kind, top in tops.items():
+                levels = [top]
+                for hl, wl in sizes[1:]:
+                    levels.append(degrade.resize_bicubic_u8(top, (wl, hl)) if kind == 'RGB8' else tiff_hip.halve_box_u16(levels[-1]))
+                torch.cuda.synchronize()
+                raw = sum(lv.numel() * lv.element_size() for lv in levels)
+                legs = {'a': lambda: tiff_hip.encode_tiff(levels, tile), 'b': lambda: tiff_hip.encode_tiff(levels, tile, matches=True)}
+                if kind != 'RGB16':
+                    legs['c'] = lambda: pil_tiff(top)
+                times = run_legs(args, legs)
+                lit, lz = legs['a'](), legs['b']()
+                tiles = sum(-(-a // tile) * -(-b // tile) for a, b in sizes)
+                line = (f'{h} x {w} {content}, {kind}, tile {tile}: {len(sizes)} levels, {tiles} tiles; file bytes literal {len(lit)}, matches '
+                        f'{len(lz)} ({len(lz) / len(lit):.4f}), raw bytes of all levels {raw}, literal / raw {len(lit) / raw:.4f}')
+                if 'c' in legs:
+                    pil = legs['c']()
+                    page = np.asarray(Image.open(io.BytesIO(lit)))
+                    want = top.cpu().numpy()
+                    same = np.array_equal(page, want[:, :, ::-1] if want.ndim == 3 else want)
+                    line += (f'; Pillow (top level only, strips) {len(pil)}, literal / Pillow {len(lit) / len(pil):.4f}; top page read back by '
+                             f'Pillow identical: {same}')
+                say(line)
+                say(f'  (a) device pyramid, matches off           wall s: {stats(times["a"])}')
+                say(f'  (b) device pyramid, matches on            wall s: {stats(times["b"])}')
+                if 'c' in legs:
+                    say(f'  (c) copy + PIL save, top level, strips    wall s: {stats(times["c"])}')
+                    gap = statistics.mean(times['c']) - statistics.mean(times['a'])
+                    spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', 'c'))
+                    say(f'  (c) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                        f'{"device pyramid faster beyond the spread" if gap > spread else ("host call faster beyond the spread" if -gap > spread else "NOT separated")}; '
+                        f'ratio (c) / (a) {statistics.mean(times["c"]) / statistics.mean(times["a"]):.2f}x')
+                gap = statistics.mean(times['b']) - statistics.mean(times['a'])
+                spread = max(max(times[k_]) - min(times[k_]) for k_ in ('a', 'b'))
+                say(f'  (b) - (a) = {gap:.4f} s, larger round-to-round spread {spread:.4f} s: '
+                    f'{"matches cost time beyond the spread" if gap > spread else ("matches faster beyond the spread" if -gap > spread else "NOT separated")}')
+                say(f'  (a) kernels: {kernels(legs["a"])}')
+                say(f'  (b) kernels: {kernels(legs["b"])}')
+                del levels
+            del tops, top
+
+
 def jpeg_leg(args, say):
     from ciaosr_amd.jpeg_hip import SUBSAMPLINGS, encode_jpeg, encode_jpeg_tiles
     from ciaosr_amd.png_hip import encode_png
@@ -695,13 +774,14 @@ def jpeg_prog_leg(args, say):
 
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches', 'grey', 'depth16'])
+    p.add_argument('--leg', default='files', choices=['files', 'tiles', 'jpeg', 'jpeg-opt', 'jpeg-prog', 'rgba', 'matches', 'grey', 'depth16', 'tiff'])
     p.add_argument('--parent-root', default=None, help='tiles: a built checkout of the parent commit for leg (a)')
     p.add_argument('--root', default=None, help='the tree whose package and library run (the parent-tree child)')
     p.add_argument('--worker', action='store_true', help='serve leg (a) on stdin / stdout (the parent-tree child)')
     p.add_argument('--dzi', action='store_true', help='tiles: also one full write_dzi of the bench output')
     p.add_argument('--tile', type=int, default=254)
     p.add_argument('--overlap', type=int, default=1)
+    p.add_argument('--tiff-tile', type=int, default=256, help='tiff: the tile side')
     p.add_argument('--quality', type=int, default=90, help='jpeg: the quality of every JPEG file')
     p.add_argument('--sizes', nargs='+', default=None)
     p.add_argument('--contents', nargs='+', default=['smooth', 'noisy'], choices=['smooth', 'noisy'])
@@ -729,6 +809,10 @@ def main(argv=None):
     if args.leg == 'depth16':                                # likewise
         args.sizes = args.sizes or ['5424x8160', '768x768']
         args.out = args.out or os.path.join(REPO, 'profiles', 'png_depth16.txt')
+        jpeg = True
+    if args.leg == 'tiff':                                   # likewise
+        args.sizes = args.sizes or ['5424x8160', '768x768']
+        args.out = args.out or os.path.join(REPO, 'profiles', 'tiff_gpu.txt')
         jpeg = True
     args.sizes = args.sizes or (['5424x8160'] if tiles else ['768x768', '5424x8160'] if rgba else ['5424x8160', '768x768'])
     args.out = args.out or os.path.join(REPO, 'profiles', 'png_tiles.txt' if tiles else 'png_matches.txt' if args.leg == 'matches' else 'png_rgba.txt' if rgba else ('jpeg_opt.txt' if args.leg == 'jpeg-opt' else 'jpeg_prog.txt' if args.leg == 'jpeg-prog' else 'jpeg_gpu.txt' if jpeg else 'png_gpu.txt'))
@@ -760,6 +844,8 @@ def main(argv=None):
         grey_leg(args, say)
     if args.leg == 'depth16':
         depth16_leg(args, say)
+    if args.leg == 'tiff':
+        tiff_leg(args, say)
     with tempfile.TemporaryDirectory() as tmp:
         for size in ([] if tiles or jpeg or rgba else args.sizes):
             h, w = (int(v) for v in size.split('x'))

@@ -58,6 +58,14 @@ printed; every --scale, --window and --view output is rendered as a torch.uint16
 rint(clamp(v, 0, 1) * 65535), quantised once) and written as a PNG of bit depth 16 by the device coder, colour type 2, or 0 with
 --grey.  An 8-bit input is allowed: the output then keeps the model's precision.  --png-matches and --self-ensemble work with it.
 Not with --jpeg, --alpha, --dzi or --niqe (an argparse error): those stay 8-bit.
+`--tiff [--tiff-tile 256]` writes every --scale output as ONE pyramidal tiled TIFF, DIR/<image name>_x<S>.tif, instead of a .png
+(ciaosr_amd/tiff_hip.py, pyramid.write_tiff): one image file directory per level from the full render down to the first level that
+fits one tile, each level halving the one above; deflate tiles (Compression 8, Predictor 2) of --tiff-tile pixels a side (a multiple
+of 16 in 16..4096), coded on the device -- what OpenSlide, QuPath / Bio-Formats, libvips, GDAL and Pillow open.  Levels at or above
+the LR size are the model's own renders from the same encode.  With --depth16 the file holds 16-bit samples (the levels below the LR
+size are box halvings there, Pillow-exact bicubic resizes at 8 bits), with --grey one sample per pixel, with --alpha RGBA with
+unassociated alpha, with --png-matches the tiles may use LZ77 matches.  Not with --jpeg, --view, --window, --dzi, --niqe or
+--self-ensemble (an argparse error); --alpha with --depth16 and --grey with --alpha stay refused.
 """
 import argparse
 import os
@@ -103,6 +111,10 @@ def parse_args(argv=None):
     p.add_argument('--dzi', type=float, default=None, metavar='SCALE', help='also write the Deep Zoom pyramid of the SCALE render: <name>.dzi, <name>_files/')
     p.add_argument('--dzi-tile', type=int, default=254, help='Deep Zoom tile size (default 254)')
     p.add_argument('--dzi-overlap', type=int, default=1, help='Deep Zoom overlap (default 1)')
+    p.add_argument('--tiff', action='store_true',
+                   help='write every --scale output as a pyramidal tiled TIFF (.tif) coded on the GPU (with --depth16, --grey, --alpha, '
+                        '--png-matches; not with --jpeg, --view, --window, --dzi, --niqe or --self-ensemble; default off)')
+    p.add_argument('--tiff-tile', type=int, default=256, help='TIFF tile side: a multiple of 16 in 16..4096 (default 256)')
     p.add_argument('--niqe', default=None, metavar='PARAMS',
                    help='score every --scale / --view output with NIQE on the GPU under the pristine model PARAMS (.npz); writes niqe.json')
     p.add_argument('--self-ensemble', action='store_true',
@@ -135,7 +147,16 @@ def parse_args(argv=None):
                             ('--niqe', args.niqe is not None)):
             if given:
                 p.error(f'--depth16 with {flag}: JPEG, alpha, pyramids and NIQE stay 8-bit here, drop one of the two')
-    if args.png_matches and not (args.gpu_png or args.alpha or args.grey or args.depth16):
+    if args.tiff:
+        if not args.scale:
+            p.error('--tiff writes the --scale outputs: give --scale')
+        for flag, given in (('--jpeg', args.jpeg is not None), ('--view', bool(args.view)), ('--window', args.window is not None),
+                            ('--niqe', args.niqe is not None), ('--self-ensemble', args.self_ensemble), ('--dzi', args.dzi is not None)):
+            if given:
+                p.error(f'--tiff with {flag}: a pyramidal TIFF is the whole render of a plain encode in deflate tiles, drop one of the two')
+        if args.tiff_tile < 16 or args.tiff_tile > 4096 or args.tiff_tile % 16:
+            p.error('--tiff-tile is a multiple of 16 in 16..4096')
+    if args.png_matches and not (args.gpu_png or args.alpha or args.grey or args.depth16 or args.tiff):
         p.error('--png-matches belongs to --gpu-png, --alpha, --grey or --depth16, whose files the device codes')
     if args.jpeg_optimize and args.jpeg is None:
         p.error('--jpeg-optimize belongs to --jpeg')
@@ -226,6 +247,15 @@ def main(argv=None):
     dzi_format = dict(fmt='jpg', **coding) if form['fmt'] == 'jpg' else {}           # without --jpeg write_dzi is called as before
     lz = dict(matches=True) if args.png_matches else {}                              # without --png-matches every writer is called as before
     dzi_format.update(lz)
+    if args.tiff:                                                                    # every scale is a file of its own pyramid
+        from ciaosr_amd.pyramid import write_tiff
+        paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}.tif') for s in args.scale]
+        for s, path in zip(args.scale, paths):
+            res = write_tiff(model, enc, path, scale=s, tile=args.tiff_tile, depth=16 if args.depth16 else 8, **lz)
+            top = res['levels'][0]
+            print(f"{path}: {top[0]} x {top[1]}, {len(res['levels'])} levels ({len(res['model_levels'])} from the model), "
+                  f"{res['tiles']} tiles, {res['bytes']} bytes, {16 if args.depth16 else 8} bits per sample")
+        return paths
     targets = [Grid(scale=s, window=args.window) for s in args.scale]
     paths = [os.path.join(args.out, f'{name}_x{scale_tag(s)}{form["ext"]}') for s in args.scale]
     for k, (cy, cx, zoom, angle) in enumerate(args.view):
