@@ -54,7 +54,7 @@ class PackedSwinIR:
             c = n.conv_first.out_channels
             ws = n.window_size
             ok = isinstance(n.layers[0].conv, torch.nn.Conv2d) and isinstance(n.conv_after_body, torch.nn.Conv2d)
-            ok = ok and n.conv_first.in_channels == 3 and c % 4 == 0 and blk.mlp.fc1.out_features % 4 == 0
+            ok = ok and n.conv_first.in_channels == 3 and c % 4 == 0 and c <= 512 and blk.mlp.fc1.out_features % 4 == 0
             ok = ok and ws * ws <= 64 and c % blk.num_heads == 0 and c // blk.num_heads <= 32 and (c // blk.num_heads) % 2 == 0
             ok = ok and n.patch_embed.norm is not None
             depths = {len(l.residual_group.blocks) for l in n.layers}
@@ -65,8 +65,9 @@ class PackedSwinIR:
     def why_unsupported(self):
         n = self.net
         return (f'SwinIR trunk (embed_dim={n.conv_first.out_channels}, window_size={n.window_size}): the HIP trunk needs 3 input '
-                f'channels, resi_connection="1conv", patch_norm=True, window_size <= 8, head_dim even and <= 32, embed_dim and the '
-                f'MLP width multiples of 4, and the same depth in every group')
+                f'channels, resi_connection="1conv", patch_norm=True, window_size <= 8, head_dim even and <= 32, embed_dim <= 512 '
+                f'(a token in one wavefront\'s registers in the LayerNorms), embed_dim and the MLP width multiples of 4, and the same depth '
+                f'in every group')
 
     def struct(self, half=None):
         """The packed fp32 struct; `half == 'f16'` adds (on first use, keyed like the fp32 struct) the IEEE-half copies of the four
