@@ -6,13 +6,6 @@
 
 namespace ciaosr {
 
-int conv2d_hwc(const float* src, int ld_src, int H, int W, int Cin, const float* wgt, int ldw, const float* bias,
-               int Cout, int ksize, float* dst, int ld_dst, float* dst2, int ld_dst2, const float* res, int ld_res,
-               int act, float alpha, float* partial, size_t partial_floats, hipStream_t s, const char* tag);
-
-int dense_scatter_step(float* X, int ldx, int H, int W, int step, int num_layers, const float* wgt, const float* bias_all,
-                       float* acc_buf, float* partial, size_t partial_floats, hipStream_t s);
-
 // dense_scatter_f32.hip
 int dense_scatter_small(float* X, int ldx, int H, int W, int step, int num_layers, const float* frag, const float* bias_all,
                         float* acc_buf, hipStream_t s);
@@ -45,10 +38,6 @@ static int first_conv(const float* x_nchw, int H, int W, const ciaosr_conv_t& c,
     if (rc != CIAOSR_OK) return rc;
     return gemm_f32(rows, 36, c.weight, 36, false, dst, ld_dst, c.bias, (int)HW, c.cout, 36, 1.f, CIAOSR_ACT_NONE, 0.f,
                     s, "enc_conv_first");
-}
-
-static bool conv_ok(const ciaosr_conv_t& c, int cin, int cout, int k) {
-    return c.weight && c.bias && c.cin == cin && c.cout == cout && c.ksize == k;
 }
 
 // 3x3 trunk convolution: the one-launch small-map kernel when the layer has fragment-packed weights, else the generic path
@@ -287,8 +276,8 @@ struct RdnCall : RdnBuffers {
 //   tail         enc_edsr_resident: conv_after_body, residual = first, alpha = 1                X[:, :64), first -> feat
 // X [B HW][128]: group 0 = the running x, group 1 = relu(conv1(x)).  A launch reads one group (with its halo) and writes the other group or
 // another buffer, so no workgroup writes what another reads; the residual is read by the lane that overwrites it, at that pixel alone.
-// Block 0 reads its source and residual from `first`, which nothing writes after the stem.  Route 0 (per image) is the body of
-// ciaosr_edsr_forward_f32, image after image.
+// Block 0 reads its source and residual from `first`, which nothing writes after the stem.  Route 0 (per image) is
+// ciaosr_edsr_forward_f32 (below), image after image.
 struct EdsrPlan {
     int B, H, W, C, NB;
     size_t HW, BHW;
@@ -358,6 +347,40 @@ struct EdsrCall : EdsrBuffers {
         return dense_conv_f32(X, 128, 0, 1, feat_hwc, 64, 0, first, 64, 0, 1, 1.f, H, W, w->conv_after_body.frag, w->conv_after_body.bias, B, s,
                               "enc_edsr_resident");
     }
+};
+
+// ---- EDSR per image (ciaosr_edsr_forward_f32, any C that is a multiple of 32; route 0 of the batched entry runs it image after image): the
+// same plan with B = 1, the same refusals (edsr_args_ok), a carve list of its own (edsr_image_carve) and one function per stage:
+//   stage        launches in order (profiler tags)                                              scratch: reads -> writes
+//   stem         image_to_hwc4, enc_patch_first, enc_conv_first                                 x -> img4 -> rows -> first
+//   block b      enc_conv3x3 x 2: conv1 (relu), conv2 (residual x, alpha = res_scale)           x = in(b) -> tmp -> ab[b & 1] (partials in part)
+//   tail         enc_conv3x3: conv_after_body, residual = first                                 in(NB), first -> feat
+struct EdsrImageBuffers : EdsrPlan {
+    float *img4, *rows, *first, *ab[2], *tmp, *part;
+    size_t pf;                                                  // floats of split-K partials (conv_f32.hip)
+};
+template <class Take>
+static EdsrImageBuffers edsr_image_carve(const EdsrPlan& p, Take take) {
+    EdsrImageBuffers b = {p};
+    const size_t map = p.HW * (size_t)p.C;
+    b.img4 = take(p.HW * 4); b.rows = take(p.HW * 36);          // first-conv temporaries
+    b.first = take(map);
+    b.ab[0] = take(map); b.ab[1] = take(map);                   // block outputs, alternating
+    b.tmp = take(map);                                          // relu(conv1(x))
+    b.pf = 16 * map; b.part = take(b.pf);
+    return b;
+}
+struct EdsrImageCall : EdsrImageBuffers {
+    const ciaosr_edsr_weights_t* w; hipStream_t s;
+
+    const float* in(int b) const { return b ? ab[(b - 1) & 1] : first; }     // what block b reads (b = NB: the tail)
+    int stem(const float* x_nchw) const { return first_conv(x_nchw, H, W, w->conv_first, img4, rows, first, C, s); }
+    // ResidualBlockNoBN: x + conv2(relu(conv1(x))) * res_scale
+    int block(int b) const {
+        RDN_RUN(conv3(in(b), C, H, W, w->conv1[b], tmp, C, nullptr, 0, CIAOSR_ACT_RELU, 1.f, part, pf, s));
+        return conv3(tmp, C, H, W, w->conv2[b], ab[b & 1], C, in(b), C, CIAOSR_ACT_NONE, w->res_scale, part, pf, s);
+    }
+    int tail(float* feat_hwc) const { return conv3(in(NB), C, H, W, w->conv_after_body, feat_hwc, C, first, C, CIAOSR_ACT_NONE, 1.f, part, pf, s); }
 };
 
 }  // namespace ciaosr
@@ -444,45 +467,22 @@ extern "C" int ciaosr_rdn_forward_batch_f16(const float* x_nchw, int B, int H, i
 
 extern "C" size_t ciaosr_edsr_workspace_bytes(int H, int W, const ciaosr_edsr_weights_t* w) {
     if (!w || H <= 0 || W <= 0) return 0;
-    const size_t HW = (size_t)H * W;
-    const int C = w->mid_channels;
-    return (HW * 4 + HW * 36 + 4 * HW * C + 16 * HW * C) * sizeof(float) + 16 * 256;
+    size_t n = 0;
+    edsr_image_carve(edsr_plan(1, H, W, w), [&](size_t floats) { n += floats; return (float*)nullptr; });
+    return n * sizeof(float) + 16 * 256;              // room for the 256-byte alignment of each carve-out
 }
 
 extern "C" int ciaosr_edsr_forward_f32(const float* x_nchw, int H, int W, const ciaosr_edsr_weights_t* w,
                                        float* feat_hwc, void* workspace, size_t workspace_bytes, void* stream_) {
-    CIAOSR_CHECK_ARG(x_nchw && w && feat_hwc && workspace && H > 0 && W > 0);
-    const int C = w->mid_channels, NB = w->num_blocks;
-    CIAOSR_CHECK_ARG(C % 32 == 0 && NB >= 0 && (NB == 0 || (w->conv1 && w->conv2)));
-    CIAOSR_CHECK_ARG(conv_ok(w->conv_first, 3, C, 3) && conv_ok(w->conv_after_body, C, C, 3));
+    CIAOSR_CHECK_ARG(x_nchw && feat_hwc && workspace);
+    RDN_RUN(edsr_args_ok(1, H, W, w, nullptr));                    // every refusal, before the first launch
     if (workspace_bytes < ciaosr_edsr_workspace_bytes(H, W, w)) return CIAOSR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream_;
-    const size_t HW = (size_t)H * W;
     Arena ar(workspace, workspace_bytes);
-    float* img4 = ar.take<float>(HW * 4);
-    float* rows = ar.take<float>(HW * 36);
-    float* first = ar.take<float>(HW * C);
-    float* a = ar.take<float>(HW * C);
-    float* b = ar.take<float>(HW * C);
-    float* tmp = ar.take<float>(HW * C);
-    const size_t pf = 16 * HW * (size_t)C;
-    float* part = ar.take<float>(pf);
+    const EdsrImageCall c = {edsr_image_carve(edsr_plan(1, H, W, w), [&](size_t floats) { return ar.take<float>(floats); }), w, (hipStream_t)stream_};
     if (!ar.ok) return CIAOSR_ERR_WORKSPACE;
-    int rc;
-#define RUN(x) do { rc = (x); if (rc != CIAOSR_OK) return rc; } while (0)
-    RUN(first_conv(x_nchw, H, W, w->conv_first, img4, rows, first, C, s));
-    const float* cur = first;
-    float* pp[2] = {a, b};
-    for (int i = 0; i < NB; ++i) {
-        CIAOSR_CHECK_ARG(conv_ok(w->conv1[i], C, C, 3) && conv_ok(w->conv2[i], C, C, 3));
-        // ResidualBlockNoBN: x + conv2(relu(conv1(x))) * res_scale
-        RUN(conv3(cur, C, H, W, w->conv1[i], tmp, C, nullptr, 0, CIAOSR_ACT_RELU, 1.f, part, pf, s));
-        RUN(conv3(tmp, C, H, W, w->conv2[i], pp[i & 1], C, cur, C, CIAOSR_ACT_NONE, w->res_scale, part, pf, s));
-        cur = pp[i & 1];
-    }
-    RUN(conv3(cur, C, H, W, w->conv_after_body, feat_hwc, C, first, C, CIAOSR_ACT_NONE, 1.f, part, pf, s));
-#undef RUN
-    return CIAOSR_OK;
+    RDN_RUN(c.stem(x_nchw));
+    for (int b = 0; b < c.NB; ++b) RDN_RUN(c.block(b));
+    return c.tail(feat_hwc);
 }
 
 extern "C" size_t ciaosr_edsr_workspace_bytes_batch(int B, int H, int W, const ciaosr_edsr_weights_t* w, const ciaosr_options_t* opt) {

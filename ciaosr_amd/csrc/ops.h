@@ -87,6 +87,16 @@ int csa_scores_box_f32(const float* M, int ldm, int Hp, int Wp, const float* R, 
 bool conv1x1_resident_ok(long M, int N, int K, int ldx, int ldw);
 int conv1x1_resident_f32(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* res, int ldres, float* dst,
                          int ld_dst, float* dst2, int ld_dst2, long M, int K, hipStream_t s, const char* tag);
+// conv_f32.hip: implicit-GEMM convolution on channels-last maps (split-K slabs in `partial`), and one step of the RDN scatter form
+int conv2d_hwc(const float* src, int ld_src, int H, int W, int Cin, const float* wgt, int ldw, const float* bias,
+               int Cout, int ksize, float* dst, int ld_dst, float* dst2, int ld_dst2, const float* res, int ld_res,
+               int act, float alpha, float* partial, size_t partial_floats, hipStream_t s, const char* tag);
+int dense_scatter_step(float* X, int ldx, int H, int W, int step, int num_layers, const float* wgt, const float* bias_all,
+                       float* acc_buf, float* partial, size_t partial_floats, hipStream_t s);
+// a convolution layer of the weights structs: present, and of the shape the trunk expects
+inline bool conv_ok(const ciaosr_conv_t& c, int cin, int cout, int k) {
+    return c.weight && c.bias && c.cin == cin && c.cout == cout && c.ksize == k;
+}
 // conv_small_f32.hip: 3x3 convolutions of small maps in one launch (needs ciaosr_pack_fragments_f32 weights)
 bool conv3x3_small_ok(int H, int W, int Cin, int Cout, int ld_src, int act);
 int conv3x3_small(const float* src, int ld_src, int H, int W, int Cin, const float* frag, const float* bias, int Cout, float* dst,

@@ -136,11 +136,51 @@ __device__ __forceinline__ void window_attention_body(const WinAttnP& p, const i
     }
 }
 
+// sum over the wavefront (the LayerNorm statistics of both trunks)
+__device__ __forceinline__ float wsum64(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
-// swinir.hip: the fp32 stages that both trunks launch
+// ---- host side shared by the two drivers: the plan, the buffers, the common refusals and the fp32 stages both run (swinir.hip) ------
+struct SwinPlan {
+    int B, H, W, Hp, Wp, C, heads, d, ws, hid, ld, ldh, ldq;   // the fp32 entry: B = 1
+    size_t HW, rows;               // tokens of one image, of the batch
+};
+// ld = C rounded up to 64; ldq: the convolution kernels store whole 32-column tiles, so a QKV row has room up to the next multiple of 32
+inline bool swin_plan(int B, int H, int W, const ciaosr_swinir_weights_t* w, SwinPlan* p) {
+    if (!w || B <= 0 || H <= 0 || W <= 0 || w->window_size <= 0) return false;
+    p->B = B; p->H = H; p->W = W; p->ws = w->window_size;
+    p->Hp = (int)round_up((size_t)H, p->ws); p->Wp = (int)round_up((size_t)W, p->ws);
+    p->C = w->embed_dim; p->heads = w->num_heads; p->d = p->heads > 0 ? p->C / p->heads : 0; p->hid = w->hidden;
+    p->ld = (int)round_up((size_t)p->C, 64); p->ldh = (int)round_up((size_t)p->hid, 64);
+    p->ldq = (int)round_up((size_t)3 * p->C, 32);
+    p->HW = (size_t)p->Hp * p->Wp; p->rows = p->HW * (size_t)B;
+    return true;
+}
+// What the shared stages touch, and each driver's own buffers beside them (a driver leaves the other's null)
+struct SwinBufs {
+    float *img4, *rows36;          // conv_first temporaries, one image at a time
+    float *x0, *T, *Tn;            // conv_first of every image (the last residual); group input / output; residual stream of the group's blocks
+    float *Y, *F;                  // normed map (f16: Tn again); conv_after_body of one image (fp32: the blocks' attention output too)
+    float *QKV, *part;
+    size_t part_floats;            // split-K slabs of the per-image 3x3 convolutions
+    float *pad5, *Hb;              // fp32: x0 | T | Tn | Y | F as ONE carve-out, zeroed whole; hidden activations
+    unsigned short *A16, *Hb16;    // f16: attention output, hidden activations
+};
+
+#define SWIN_RUN(x) do { const int rc_ = (x); if (rc_ != CIAOSR_OK) return rc_; } while (0)
+
+// every refusal the two entries share (shapes, the plan, the pointers and convolutions both read); enqueues nothing
+int swin_args_ok(const float* x, int B, int H, int W, const ciaosr_swinir_weights_t* w, const float* feat, const void* workspace, SwinPlan* plan);
 int swin_layernorm(const float* X, int ldx, float* Y, int ldy, const float* g, const float* b, long rows, int C, hipStream_t s);
-int swin_image_to_hwc4(const float* x_chw, float* img4, int H, int W, int Hp, int Wp, hipStream_t s);
-int swin_crop(const float* F, int ld, int Wp, float* feat_hwc, int H, int W, int C, hipStream_t s);
-bool swin_conv_ok(const ciaosr_conv_t& c, int cin, int cout, int k);
+// per image conv_first, then the PatchEmbed norm over all rows: x -> img4 -> rows36 -> x0 -> T
+int swin_embed(const SwinPlan& p, const SwinBufs& b, const float* x, const ciaosr_swinir_weights_t* w, hipStream_t s);
+// 3x3 convolution of ONE image, dst = conv(src) + res: the small-map kernel where the layer has fragments and the map fits, else split-K
+int swin_conv3x3_image(const SwinPlan& p, const SwinBufs& b, const ciaosr_conv_t& c, const float* src, float* dst, const float* res, hipStream_t s,
+                       const char* tag);
+// final norm over all rows, then per image conv_after_body + conv_first's output, crop and repack: T -> Y -> F (+ x0) -> feat
+int swin_tail(const SwinPlan& p, const SwinBufs& b, const ciaosr_swinir_weights_t* w, float* feat, hipStream_t s);
 
 }  // namespace ciaosr

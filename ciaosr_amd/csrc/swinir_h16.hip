@@ -26,7 +26,8 @@
 // written (the epilogues stop at N); the LayerNorm staging writes zeros into LDS for [C, ld).
 //
 // Driver (the shape of encoder.hip / csattn.hip): one plan, one carve list walked by the byte-count export and by the call, a route
-// function that launches nothing and does every refusal, one function per stage.
+// function that launches nothing and does every refusal, one function per stage.  The plan, the refusals both trunks share and the
+// stages outside the blocks (swin_embed, swin_conv3x3_image, swin_tail) are the fp32 trunk's (swin_window.h, swinir.hip).
 #include "h16_util.h"
 #include "ops.h"
 #include "swin_window.h"
@@ -36,10 +37,6 @@
 #endif
 
 namespace ciaosr {
-
-int conv2d_hwc(const float* src, int ld_src, int H, int W, int Cin, const float* wgt, int ldw, const float* bias,
-               int Cout, int ksize, float* dst, int ld_dst, float* dst2, int ld_dst2, const float* res, int ld_res,
-               int act, float alpha, float* partial, size_t partial_floats, hipStream_t s, const char* tag);
 
 namespace CIAOSR_H16_NS {
 
@@ -62,12 +59,6 @@ struct SwinLinP {
     unsigned short* out16; int ldo16;      // kEpiGelu16
     long M; int N, K, tiles_n;
 };
-
-__device__ __forceinline__ float wsum64h(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <bool LN, int EPI>
 __global__ __launch_bounds__(256, 2) void swin_linear_f16_kernel(SwinLinP p) {
@@ -117,11 +108,11 @@ __global__ __launch_bounds__(256, 2) void swin_linear_f16_kernel(SwinLinP p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float4 a = v[j], c2 = v2[j];
-                    const float mean = wsum64h((a.x + a.y) + (a.z + a.w) + (c2.x + c2.y) + (c2.z + c2.w)) / (float)p.C;
+                    const float mean = wsum64((a.x + a.y) + (a.z + a.w) + (c2.x + c2.y) + (c2.z + c2.w)) / (float)p.C;
                     float sq = 0.f;
                     if (lane < n4) sq += (a.x - mean) * (a.x - mean) + (a.y - mean) * (a.y - mean) + (a.z - mean) * (a.z - mean) + (a.w - mean) * (a.w - mean);
                     if (lane + 64 < n4) sq += (c2.x - mean) * (c2.x - mean) + (c2.y - mean) * (c2.y - mean) + (c2.z - mean) * (c2.z - mean) + (c2.w - mean) * (c2.w - mean);
-                    const float rstd = 1.0f / sqrtf(wsum64h(sq) / (float)p.C + 1e-5f);
+                    const float rstd = 1.0f / sqrtf(wsum64(sq) / (float)p.C + 1e-5f);
                     unsigned char* dst = la + (16 * w + r4 + j) * LPITCH;
                     const int ca = 4 * lane - k0, cb = 4 * (lane + 64) - k0;      // column within the staged chunk
                     if (ca >= 0 && ca < kc) {
@@ -232,28 +223,7 @@ static int launch_linear(SwinLinP& p, hipStream_t s, const char* tag) {
     return launch_status(tag);
 }
 
-// ---- plan, carve list, route -------------------------------------------------------------------------------------------------
-struct SwinPlan {
-    int B, H, W, Hp, Wp, C, heads, d, ws, hid, ld, ldh, ldq;
-    size_t HW, rows;               // tokens of one image, of the batch
-};
-struct SwinBufs {
-    float *img4, *rows36, *x0, *T, *Tn, *F, *QKV, *part;
-    unsigned short *A16, *Hb16;
-    size_t part_floats;
-};
-
-static bool swin_plan(int B, int H, int W, const ciaosr_swinir_weights_t* w, SwinPlan* p) {
-    if (!w || B <= 0 || H <= 0 || W <= 0 || w->window_size <= 0 || w->embed_dim <= 0 || w->hidden <= 0 || w->num_heads <= 0) return false;
-    p->B = B; p->H = H; p->W = W; p->ws = w->window_size;
-    p->Hp = (int)round_up((size_t)H, p->ws); p->Wp = (int)round_up((size_t)W, p->ws);
-    p->C = w->embed_dim; p->heads = w->num_heads; p->d = p->C / p->heads; p->hid = w->hidden;
-    p->ld = (int)round_up((size_t)p->C, 64); p->ldh = (int)round_up((size_t)p->hid, 64);
-    p->ldq = (int)round_up((size_t)3 * p->C, 32);
-    p->HW = (size_t)p->Hp * p->Wp; p->rows = p->HW * (size_t)B;
-    return true;
-}
-
+// ---- carve list, route (the plan, SwinBufs and the refusals both trunks share: swin_window.h) ---------------------------------------
 // THE list of workspace buffers: walked with base == nullptr by the byte count, with the workspace by the call
 static size_t swin_carve(const SwinPlan& p, char* base, SwinBufs* b) {
     size_t off = 0;
@@ -263,12 +233,12 @@ static size_t swin_carve(const SwinPlan& p, char* base, SwinBufs* b) {
         off += bytes;
         return r;
     };
-    SwinBufs t;
+    SwinBufs t = {};
     t.img4 = (float*)take(p.HW * 4 * sizeof(float));                  // one image at a time
     t.rows36 = (float*)take(p.HW * 36 * sizeof(float));               // one image at a time
     t.x0 = (float*)take(p.rows * p.ld * sizeof(float));               // conv_first of every image: the last residual
     t.T = (float*)take(p.rows * p.ld * sizeof(float));                // group input / output
-    t.Tn = (float*)take(p.rows * p.ld * sizeof(float));               // residual stream of the group's blocks; final norm
+    t.Y = t.Tn = (float*)take(p.rows * p.ld * sizeof(float));         // residual stream of the group's blocks; final norm
     t.F = (float*)take(p.HW * p.ld * sizeof(float));                  // conv_after_body of one image
     t.QKV = (float*)take(p.rows * p.ldq * sizeof(float));
     t.A16 = (unsigned short*)take(p.rows * p.ld * sizeof(unsigned short));     // attention output
@@ -282,57 +252,37 @@ static size_t swin_carve(const SwinPlan& p, char* base, SwinBufs* b) {
 // every refusal, nothing enqueued
 static int swin_route(const float* x, int B, int H, int W, const ciaosr_swinir_weights_t* w, float* feat, const ciaosr_options_t* opt,
                       void* workspace, size_t workspace_bytes, SwinPlan* plan) {
-    CIAOSR_CHECK_ARG(x && w && feat && workspace && B >= 1 && H > 0 && W > 0);
     CIAOSR_CHECK_ARG(options_ok(opt));
-    const int C = w->embed_dim, heads = w->num_heads, ws = w->window_size, hid = w->hidden;
-    CIAOSR_CHECK_ARG(C > 0 && (C & 3) == 0 && heads > 0 && C % heads == 0 && C / heads <= WMAXD && ws > 0 && ws * ws <= WMAXN);
-    CIAOSR_CHECK_ARG(((C / heads) & 1) == 0);
-    CIAOSR_CHECK_ARG(hid > 0 && (hid & 3) == 0 && w->num_groups >= 1 && w->depth >= 1 && w->blocks && w->group_conv);
-    CIAOSR_CHECK_ARG(w->pe_norm_w && w->pe_norm_b && w->norm_w && w->norm_b);
-    CIAOSR_CHECK_ARG(swin_plan(B, H, W, w, plan));
+    SWIN_RUN(swin_args_ok(x, B, H, W, w, feat, workspace, plan));
     const SwinPlan& p = *plan;
-    CIAOSR_CHECK_ARG(C <= 512);                                        // a token's values in one wave's registers (LayerNorm staging)
-    CIAOSR_CHECK_ARG(p.Hp - H < H && p.Wp - W < W);                    // reflect padding needs pad < size
     CIAOSR_CHECK_ARG(p.rows <= ((size_t)1 << 30));                     // refused, not sub-batched (header)
     CIAOSR_CHECK_ARG(p.HW * (size_t)p.ldq * 4 < 0xFFFFFF00ull);       // one image's QKV under a buffer descriptor
-    CIAOSR_CHECK_ARG(swin_conv_ok(w->conv_first, 3, C, 3) && swin_conv_ok(w->conv_after_body, p.ld, C, 3));
     for (int i = 0; i < w->num_groups * w->depth; ++i) {
         const ciaosr_swin_block_t& b = w->blocks[i];
-        CIAOSR_CHECK_ARG(b.ln1_w && b.ln1_b && b.qkv_b && b.bias && b.proj_b && b.ln2_w && b.ln2_b && b.fc1_b && b.fc2_b);
         CIAOSR_CHECK_ARG(b.qkv_w16 && b.proj_w16 && b.fc1_w16 && b.fc2_w16);
         CIAOSR_CHECK_ARG(aligned16(b.qkv_w16) && aligned16(b.proj_w16) && aligned16(b.fc1_w16) && aligned16(b.fc2_w16));
         CIAOSR_CHECK_ARG(aligned16(b.ln1_w) && aligned16(b.ln1_b) && aligned16(b.ln2_w) && aligned16(b.ln2_b));
         CIAOSR_CHECK_ARG(aligned16(b.qkv_b) && aligned16(b.proj_b) && aligned16(b.fc1_b) && aligned16(b.fc2_b));
-        CIAOSR_CHECK_ARG(b.shift == 0 || b.mask);
     }
-    for (int g = 0; g < w->num_groups; ++g) CIAOSR_CHECK_ARG(swin_conv_ok(w->group_conv[g], p.ld, C, 3));
     if (workspace_bytes < swin_carve(p, nullptr, nullptr)) return CIAOSR_ERR_WORKSPACE;
     return CIAOSR_OK;
 }
 
-#define SWIN_RUN(x) do { const int rc_ = (x); if (rc_ != CIAOSR_OK) return rc_; } while (0)
-
-// ---- stages ------------------------------------------------------------------------------------------------------------------
-// conv_first of every image + the PatchEmbed norm over all rows: x -> x0 -> T
-static int stage_embed(const SwinPlan& p, const SwinBufs& b, const float* x, const ciaosr_swinir_weights_t* w, hipStream_t s) {
+// ---- stages (swin_embed, swin_conv3x3_image and swin_tail are the fp32 trunk's: swinir.hip) ------------------------------------------
+// the padded maps are zeroed once: their pad columns are never written afterwards
+static int zero_pads(const SwinPlan& p, const SwinBufs& b, hipStream_t s) {
     if (hipMemsetAsync(b.x0, 0, p.rows * p.ld * sizeof(float), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
     if (hipMemsetAsync(b.F, 0, p.HW * p.ld * sizeof(float), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
     if (hipMemsetAsync(b.A16, 0, p.rows * p.ld * sizeof(unsigned short), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
     if (hipMemsetAsync(b.Hb16, 0, p.rows * p.ldh * sizeof(unsigned short), s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    for (int i = 0; i < p.B; ++i) {
-        SWIN_RUN(swin_image_to_hwc4(x + (size_t)i * 3 * p.H * p.W, b.img4, p.H, p.W, p.Hp, p.Wp, s));
-        SWIN_RUN(patch_rows(b.img4, 4, p.Hp, p.Wp, 4, 3, 1, 1, p.Hp, p.Wp, b.rows36, 36, 0, 0.f, s, "enc_patch_first"));
-        SWIN_RUN(gemm_f32(b.rows36, 36, w->conv_first.weight, 36, false, b.x0 + (size_t)i * p.HW * p.ld, p.ld, w->conv_first.bias, (int)p.HW, p.C,
-                          36, 1.f, CIAOSR_ACT_NONE, 0.f, s, "enc_conv_first"));
-    }
-    return swin_layernorm(b.x0, p.ld, b.T, p.ld, w->pe_norm_w, w->pe_norm_b, (long)p.rows, p.C, s);
+    return CIAOSR_OK;
 }
 
-// one Swin block on the residual stream t, all images: five launches
-static int stage_block(const SwinPlan& p, const SwinBufs& b, const ciaosr_swin_block_t& k, float* t, hipStream_t s) {
+// one Swin block on the residual stream Tn, all images: five launches
+static int stage_block(const SwinPlan& p, const SwinBufs& b, const ciaosr_swin_block_t& k, hipStream_t s) {
     SwinLinP q{};
     q.M = (long)p.rows;
-    q.X = t; q.ldx = p.ld; q.C = p.C; q.g = k.ln1_w; q.b = k.ln1_b;
+    q.X = b.Tn; q.ldx = p.ld; q.C = p.C; q.g = k.ln1_w; q.b = k.ln1_b;
     q.W = k.qkv_w16; q.ldw = p.ld; q.bias = k.qkv_b; q.out = b.QKV; q.ldo = p.ldq; q.N = 3 * p.C; q.K = p.ld;
     SWIN_RUN((launch_linear<true, kEpiF32>(q, s, "swin_qkv_f16")));
     {
@@ -349,46 +299,26 @@ static int stage_block(const SwinPlan& p, const SwinBufs& b, const ciaosr_swin_b
     }
     SwinLinP r{};
     r.M = (long)p.rows;
-    r.A16 = b.A16; r.lda = p.ld; r.W = k.proj_w16; r.ldw = p.ld; r.bias = k.proj_b; r.out = t; r.ldo = p.ld; r.N = p.C; r.K = p.ld;
+    r.A16 = b.A16; r.lda = p.ld; r.W = k.proj_w16; r.ldw = p.ld; r.bias = k.proj_b; r.out = b.Tn; r.ldo = p.ld; r.N = p.C; r.K = p.ld;
     SWIN_RUN((launch_linear<false, kEpiRes>(r, s, "swin_proj_f16")));
     SwinLinP f{};
     f.M = (long)p.rows;
-    f.X = t; f.ldx = p.ld; f.C = p.C; f.g = k.ln2_w; f.b = k.ln2_b;
+    f.X = b.Tn; f.ldx = p.ld; f.C = p.C; f.g = k.ln2_w; f.b = k.ln2_b;
     f.W = k.fc1_w16; f.ldw = p.ld; f.bias = k.fc1_b; f.out16 = b.Hb16; f.ldo16 = p.ldh; f.N = p.hid; f.K = p.ld;
     SWIN_RUN((launch_linear<true, kEpiGelu16>(f, s, "swin_fc1_f16")));
     SwinLinP g{};
     g.M = (long)p.rows;
-    g.A16 = b.Hb16; g.lda = p.ldh; g.W = k.fc2_w16; g.ldw = p.ldh; g.bias = k.fc2_b; g.out = t; g.ldo = p.ld; g.N = p.C; g.K = p.ldh;
+    g.A16 = b.Hb16; g.lda = p.ldh; g.W = k.fc2_w16; g.ldw = p.ldh; g.bias = k.fc2_b; g.out = b.Tn; g.ldo = p.ld; g.N = p.C; g.K = p.ldh;
     return launch_linear<false, kEpiRes>(g, s, "swin_fc2_f16");
-}
-
-// fp32 3x3 convolution of ONE image on the fp32 trunk's routes: dst = conv(src) + res
-static int conv3x3_image(const SwinPlan& p, const SwinBufs& b, const ciaosr_conv_t& c, const float* src, float* dst, const float* res, hipStream_t s,
-                         const char* tag) {
-    if (c.frag && conv3x3_small_ok(p.Hp, p.Wp, p.ld, p.C, p.ld, CIAOSR_ACT_NONE))
-        return conv3x3_small(src, p.ld, p.Hp, p.Wp, p.ld, c.frag, c.bias, p.C, dst, p.ld, nullptr, 0, res, p.ld, CIAOSR_ACT_NONE, 1.f, s, tag);
-    return conv2d_hwc(src, p.ld, p.Hp, p.Wp, p.ld, c.weight, 9 * p.ld, c.bias, p.C, 3, dst, p.ld, nullptr, 0, res, p.ld, CIAOSR_ACT_NONE, 1.f, b.part,
-                      b.part_floats, s, tag);
 }
 
 // one RSTB: blocks on a copy of the group input, then conv3x3 + the group input, in place over it (per image)
 static int stage_group(const SwinPlan& p, const SwinBufs& b, const ciaosr_swinir_weights_t* w, int g, hipStream_t s) {
     if (hipMemcpyAsync(b.Tn, b.T, p.rows * p.ld * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return CIAOSR_ERR_LAUNCH;
-    for (int l = 0; l < w->depth; ++l) SWIN_RUN(stage_block(p, b, w->blocks[g * w->depth + l], b.Tn, s));
+    for (int l = 0; l < w->depth; ++l) SWIN_RUN(stage_block(p, b, w->blocks[g * w->depth + l], s));
     for (int i = 0; i < p.B; ++i) {
         const size_t o = (size_t)i * p.HW * p.ld;
-        SWIN_RUN(conv3x3_image(p, b, w->group_conv[g], b.Tn + o, b.T + o, b.T + o, s, "swin_group_conv"));
-    }
-    return CIAOSR_OK;
-}
-
-// final norm over all rows, then per image conv_after_body + conv_first's output, crop and repack
-static int stage_tail(const SwinPlan& p, const SwinBufs& b, const ciaosr_swinir_weights_t* w, float* feat, hipStream_t s) {
-    SWIN_RUN(swin_layernorm(b.T, p.ld, b.Tn, p.ld, w->norm_w, w->norm_b, (long)p.rows, p.C, s));
-    for (int i = 0; i < p.B; ++i) {
-        const size_t o = (size_t)i * p.HW * p.ld;
-        SWIN_RUN(conv3x3_image(p, b, w->conv_after_body, b.Tn + o, b.F, b.x0 + o, s, "swin_conv_after_body"));
-        SWIN_RUN(swin_crop(b.F, p.ld, p.Wp, feat + (size_t)i * p.H * p.W * p.C, p.H, p.W, p.C, s));
+        SWIN_RUN(swin_conv3x3_image(p, b, w->group_conv[g], b.Tn + o, b.T + o, b.T + o, s, "swin_group_conv"));
     }
     return CIAOSR_OK;
 }
@@ -401,19 +331,19 @@ using namespace ciaosr::CIAOSR_H16_NS;
 
 extern "C" size_t ciaosr_swinir_workspace_bytes_batch_f16(int B, int H, int W, const ciaosr_swinir_weights_t* w) {
     SwinPlan p;
-    if (!swin_plan(B, H, W, w, &p)) return 0;
+    if (!swin_plan(B, H, W, w, &p) || p.C <= 0 || p.hid <= 0 || p.heads <= 0) return 0;
     return swin_carve(p, nullptr, nullptr);
 }
 
 extern "C" int ciaosr_swinir_forward_batch_f16(const float* x_bchw, int B, int H, int W, const ciaosr_swinir_weights_t* w, float* feat_bhwc,
                                                const ciaosr_options_t* opt, void* workspace, size_t workspace_bytes, void* stream_) {
     SwinPlan p;
-    const int rc = swin_route(x_bchw, B, H, W, w, feat_bhwc, opt, workspace, workspace_bytes, &p);
-    if (rc != CIAOSR_OK) return rc;
+    SWIN_RUN(swin_route(x_bchw, B, H, W, w, feat_bhwc, opt, workspace, workspace_bytes, &p));
     hipStream_t s = (hipStream_t)stream_;
     SwinBufs b;
     swin_carve(p, (char*)workspace, &b);
-    SWIN_RUN(stage_embed(p, b, x_bchw, w, s));
+    SWIN_RUN(zero_pads(p, b, s));
+    SWIN_RUN(swin_embed(p, b, x_bchw, w, s));
     for (int g = 0; g < w->num_groups; ++g) SWIN_RUN(stage_group(p, b, w, g, s));
-    return stage_tail(p, b, w, feat_bhwc, s);
+    return swin_tail(p, b, w, feat_bhwc, s);
 }

@@ -173,17 +173,8 @@ class PackedSwinIR:
         f16-linear entry with B = 1."""
         if self.uses_h16(options):
             return self._forward_h16(x_chw.unsqueeze(0), options)[0]
-        x_chw = x_chw.contiguous().float()
-        hip_ops.require_gpu(x_chw)
-        _, H, W = x_chw.shape
-        st = self.struct()
-        ws = st.window_size
-        hp, wp = (H + ws - 1) // ws * ws, (W + ws - 1) // ws * ws
-        self._set_masks(st, hp, wp, x_chw.device)
-        nbytes = _lib.load().ciaosr_swinir_workspace_bytes(H, W, C.byref(st))
-        wsb = hip_ops.workspace(nbytes, x_chw.device, slot='encoder')
-        out = torch.empty(H, W, st.embed_dim, dtype=torch.float32, device=x_chw.device)
-        _lib.call('ciaosr_swinir_forward_f32', hip_ops.ptr(x_chw), H, W, C.byref(st), hip_ops.ptr(out),
+        x, st, wsb, out = self._prelude(x_chw)
+        _lib.call('ciaosr_swinir_forward_f32', hip_ops.ptr(x), x.shape[1], x.shape[2], C.byref(st), hip_ops.ptr(out),
                   hip_ops.ptr(wsb), wsb.numel(), hip_ops.stream_ptr())
         return out
 
@@ -201,17 +192,22 @@ class PackedSwinIR:
         return self._forward_h16(x_bchw, options)
 
     def _forward_h16(self, x_bchw, options):
-        opt = hip_ops.as_options(options)
-        x_bchw = x_bchw.contiguous().float()
-        hip_ops.require_gpu(x_bchw)
-        B, _, H, W = x_bchw.shape
-        st = self.struct('f16')
-        ws = st.window_size
-        hp, wp = (H + ws - 1) // ws * ws, (W + ws - 1) // ws * ws
-        self._set_masks(st, hp, wp, x_bchw.device)
-        nbytes = _lib.load().ciaosr_swinir_workspace_bytes_batch_f16(B, H, W, C.byref(st))
-        wsb = hip_ops.workspace(nbytes, x_bchw.device, slot='encoder')
-        out = torch.empty(B, H, W, st.embed_dim, dtype=torch.float32, device=x_bchw.device)
-        _lib.call('ciaosr_swinir_forward_batch_f16', hip_ops.ptr(x_bchw), B, H, W, C.byref(st), hip_ops.ptr(out), opt.c_arg(),
+        x, st, wsb, out = self._prelude(x_bchw, 'f16')
+        B, _, H, W = x.shape
+        _lib.call('ciaosr_swinir_forward_batch_f16', hip_ops.ptr(x), B, H, W, C.byref(st), hip_ops.ptr(out), hip_ops.as_options(options).c_arg(),
                   hip_ops.ptr(wsb), wsb.numel(), hip_ops.stream_ptr())
         return out
+
+    def _prelude(self, x, half=None):
+        """What both entries need for x [3,H,W] (fp32 entry) or [B,3,H,W] (`half`): x as contiguous fp32 on the GPU, the struct with
+        this map size's masks set, the entry's workspace and the empty output [H,W,C] / [B,H,W,C]."""
+        x = x.contiguous().float()
+        hip_ops.require_gpu(x)
+        *lead, _, H, W = x.shape
+        st = self.struct(half)
+        ws = st.window_size
+        self._set_masks(st, (H + ws - 1) // ws * ws, (W + ws - 1) // ws * ws, x.device)
+        lib = _lib.load()
+        nbytes = lib.ciaosr_swinir_workspace_bytes_batch_f16(*lead, H, W, C.byref(st)) if half else lib.ciaosr_swinir_workspace_bytes(H, W, C.byref(st))
+        wsb = hip_ops.workspace(nbytes, x.device, slot='encoder')
+        return x, st, wsb, torch.empty(*lead, H, W, st.embed_dim, dtype=torch.float32, device=x.device)
