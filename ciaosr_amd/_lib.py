@@ -202,6 +202,11 @@ SIGNATURES = {
     'ciaosr_view_select_blocks_f32': (_I, [C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P, _P]),
     'ciaosr_view_blend_f32': (_I, [_P, _P, _I, _P, _P, _I, _P]),
     'ciaosr_view_finalize_f32': (_I, [_P, _P, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P]),
+    'ciaosr_warp_workspace_bytes': (_S, [_I, _I, _I]),
+    'ciaosr_warp_coord_cell_f32': (_I, [_P, _P, C.POINTER(C.c_double), _P, C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _P]),
+    'ciaosr_warp_count_i32': (_I, [C.POINTER(C.c_double), _P, C.POINTER(C.c_double), _I, _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_warp_select_f32': (_I, [C.POINTER(C.c_double), _P, C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P,
+                                    _P]),
     'ciaosr_dihedral_f32': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'ciaosr_dihedral_accum_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),

@@ -7,16 +7,12 @@
 #include <cmath>
 
 #include "common.h"
+#include "view_frame.h"
 
 namespace ciaosr {
 
-// A block of kViewThreads threads owns kViewChunk consecutive queries, in kViewRounds rounds of one query per thread: query
-// q = block * kViewChunk + round * kViewThreads + thread, so (round, wave, lane) in lexicographic order is increasing q.
-constexpr int kViewThreads = 256, kViewRounds = 4, kViewChunk = kViewThreads * kViewRounds, kViewWaves = kViewThreads / kWave;
-constexpr int kViewTileBatch = 256;        // tiles whose per-wave counts one pass of the count kernel keeps in LDS
-
+// (the workgroup geometry kViewThreads / kViewRounds / kViewChunk, ViewFrame and what follows a query's LR position: view_frame.h)
 struct ViewP { double myy, myx, ty, mxy, mxx, tx; int Hv, Wv; long Q; };
-struct ViewFrame { double y0, x0, y1, x1, th, tw; };       // [y0, y1) x [x0, x1) in LR pixel units, y1 = y0 + th (exact: integers)
 
 // LR position of the centre of output pixel q, fp64, every operation rounded on its own (an FMA would change the value that the
 // membership tests and the fp32 rounding of the coordinate see)
@@ -26,16 +22,6 @@ __device__ __forceinline__ void view_point(const ViewP& p, long q, double& y, do
     const double v = (double)i + 0.5, u = (double)j + 0.5;
     y = (p.myy * v + p.myx * u) + p.ty;
     x = (p.mxy * v + p.mxx * u) + p.tx;
-}
-__device__ __forceinline__ bool view_member(double y, double x, const ViewFrame& f) {
-    return y >= f.y0 && y < f.y1 && x >= f.x0 && x < f.x1;           // NaN: no member
-}
-__device__ __forceinline__ float2 view_coord(double y, double x, const ViewFrame& f) {
-#pragma clang fp contract(off)
-    return make_float2((float)(((y - f.y0) / f.th) * 2.0 - 1.0), (float)(((x - f.x0) / f.tw) * 2.0 - 1.0));
-}
-__device__ __forceinline__ ViewFrame view_frame(int y0, int x0, int th, int tw) {
-    return ViewFrame{(double)y0, (double)x0, (double)y0 + (double)th, (double)x0 + (double)tw, (double)th, (double)tw};
 }
 
 // part[t * n_blocks + b] = members of tile t among block b's queries.  Per tile one ballot per round and wave; lane 0 of each wave owns
@@ -78,25 +64,6 @@ __global__ __launch_bounds__(kViewThreads) void view_count_kernel(ViewP p, const
                                                                   int* __restrict__ part) {
     __shared__ int s_cnt[kViewTileBatch][kViewWaves];
     view_count_block(p, tiles, n_tiles, n_blocks, (int)blockIdx.x, part, s_cnt);
-}
-
-// One wave: row[*] (a tile's per-block counts) becomes its exclusive scan over the blocks, *total their sum
-__device__ __forceinline__ void view_scan_row(int* __restrict__ row, int n_blocks, int* __restrict__ total) {
-    const int lane = threadIdx.x;
-    int carry = 0;
-    for (int b0 = 0; b0 < n_blocks; b0 += kWave) {
-        const int b = b0 + lane;
-        const int v = b < n_blocks ? row[b] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int up = __shfl_up(incl, d, kWave);
-            if (lane >= d) incl += up;
-        }
-        if (b < n_blocks) row[b] = carry + incl - v;
-        carry += __shfl(incl, kWave - 1, kWave);
-    }
-    if (lane == 0) *total = carry;
 }
 
 // One wave per tile: part[t][*] becomes its exclusive scan over the blocks, counts[t] the total
@@ -327,11 +294,6 @@ __global__ void view_finalize_kernel(const float* __restrict__ E, const float* _
     }
 }
 
-static inline int view_grid(long n) {
-    const long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
-
 static inline bool view_ok(const double* m, int Hv, int Wv) {
     if (!m || Hv <= 0 || Wv <= 0 || (long)Hv * Wv > (long)INT_MAX) return false;
     for (int i = 0; i < 6; ++i)
@@ -339,15 +301,10 @@ static inline bool view_ok(const double* m, int Hv, int Wv) {
     return true;
 }
 static inline ViewP view_p(const double* m, int Hv, int Wv) { return ViewP{m[0], m[1], m[2], m[3], m[4], m[5], Hv, Wv, (long)Hv * Wv}; }
-static inline bool frame_ok(const int* f) { return f && f[0] >= 0 && f[1] >= 0 && f[2] > 0 && f[3] > 0 && f[0] <= INT_MAX - f[2] && f[1] <= INT_MAX - f[3]; }
-static inline ViewFrame frame_of(const int* f) {
-    return ViewFrame{(double)f[0], (double)f[1], (double)f[0] + (double)f[2], (double)f[1] + (double)f[3], (double)f[2], (double)f[3]};
-}
 // the view's cell in a th x tw frame: the norm of a matrix row is the output pixel's extent along that LR axis
 static inline float2 view_cell(const double* m, const int* f) {
     return make_float2((float)(std::hypot(m[0], m[1]) * 2.0 / (double)f[2]), (float)(std::hypot(m[3], m[4]) * 2.0 / (double)f[3]));
 }
-static inline int view_blocks(long Q) { return (int)((Q + kViewChunk - 1) / kViewChunk); }
 // workgroups of the block kernels: one thread per 4 x 2 block of the output grid
 static inline int view_block_wgs(int Hv, int Wv) {
     const long nb = (((long)Wv + 3) >> 2) * (((long)Hv + 1) >> 1);

@@ -407,6 +407,71 @@ def view_finalize(E, Wt, fill, mean, std):
     return out
 
 
+# ---- warps of an encoded scene (include/ciaosr_hip.h, "warps"; the definition and the host helpers: scene.py) --------------------------
+def _warp_source(h, map_, footprint, hv, wv):
+    """The (h9, map, footprint) arguments of a warp entry: exactly one of `h` (nine numbers) and `map_` (a contiguous float64 device
+    tensor [hv, wv, 2]) is given.  There is no CPU fallback: a host map is an error."""
+    if (h is None) == (map_ is None):
+        raise ValueError('a warp has exactly one point source: a homography or a map')
+    fp = (C.c_double * 2)(*[float(v) for v in footprint])
+    if h is not None:
+        h = [float(v) for v in h]
+        if len(h) != 9:
+            raise ValueError(f'a homography is (h00, h01, h02, h10, h11, h12, h20, h21, h22), got {len(h)} numbers')
+        return (C.c_double * 9)(*h), C.c_void_p(0), fp
+    if not map_.is_cuda:
+        raise CiaoSRHipError('a warp map lives on the MI355X: got a CPU tensor (no CPU fallback; move the map to cuda)')
+    if map_.dtype != torch.float64 or tuple(map_.shape) != (hv, wv, 2) or not map_.is_contiguous():
+        raise ValueError(f'a warp map is a contiguous float64 tensor [{hv}, {wv}, 2] of (y_lr, x_lr), got {map_.dtype} {tuple(map_.shape)}')
+    return None, ptr(map_), fp
+
+
+def make_coord_cell_warp(h, map_, footprint, hv, wv, frame, device):
+    """(coord, cell), each [hv * wv, 2], of the whole hv x wv warp -- homography `h` or map `map_`, one of them None -- in the frame
+    (y0, x0, th, tw), made on the device, members of the frame or not.  The grid's width is registered for `grid_width_of`, exactly as
+    `make_coord_cell_view` does: a warp inside one frame is walked as a row-major grid."""
+    h9, mp, fp = _warp_source(h, map_, footprint, hv, wv)
+    n = hv * wv
+    coord = torch.empty(n, 2, dtype=torch.float32, device=device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=device)
+    _lib.call('ciaosr_warp_coord_cell_f32', ptr(coord), ptr(cell), h9, mp, fp, hv, wv, _i4(frame), stream_ptr())
+    if len(_window_width) > 64:
+        _window_width.clear()
+    _window_width[(coord.data_ptr(), n)] = wv
+    return coord, cell
+
+
+def warp_workspace_bytes(hv, wv, n_tiles):
+    return _lib.load().ciaosr_warp_workspace_bytes(hv, wv, n_tiles)
+
+
+def warp_count(h, map_, footprint, hv, wv, tiles, ws=None):
+    """`view_count` of a warp: tiles [n_tiles, 4] int32 on the device -> (counts [n_tiles] int32 on the device, ws), `ws` what
+    `warp_select` places a tile's members with.  `ws`: the caller's own uint8 buffer of at least `warp_workspace_bytes` (several warps
+    counted before one copy of their counts each need their own), default the cached 'warp' scratch.  Nothing synchronises."""
+    require_gpu(tiles)
+    h9, mp, fp = _warp_source(h, map_, footprint, hv, wv)
+    n_tiles = tiles.shape[0]
+    if ws is None:
+        ws = workspace(warp_workspace_bytes(hv, wv, n_tiles), tiles.device, slot='warp')
+    counts = torch.empty(n_tiles, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_warp_count_i32', h9, mp, fp, hv, wv, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws
+
+
+def warp_select(h, map_, footprint, hv, wv, frame, index, n_tiles, ws, n):
+    """The `n` members (warp_count's number) of tile `index` = `frame`, in increasing query index: (q_index [n] int32, coord [n, 2],
+    cell [n, 2] in the tile's frame).  No grid hint is registered: the head sees a caller's own list of coordinates."""
+    h9, mp, fp = _warp_source(h, map_, footprint, hv, wv)
+    q_index = torch.empty(n, dtype=torch.int32, device=ws.device)
+    coord = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    _window_width.pop((coord.data_ptr(), n), None)          # the allocator may hand out the address of a dead grid's coordinates
+    _lib.call('ciaosr_warp_select_f32', h9, mp, fp, hv, wv, _i4(frame), index, n_tiles, ptr(ws), ws.numel(), n, ptr(q_index), ptr(coord),
+              ptr(cell), stream_ptr())
+    return q_index, coord, cell
+
+
 class Mode(namedtuple('Mode', 'name precision f16_pairs bf16_single trunk head')):
     """One named arithmetic mode.  (precision, f16_pairs, bf16_single): the entry suffix and the canonical ciaosr_options_t fields
     (include/ciaosr_hip.h, "Precision modes").  trunk: element type of the RDN trunk's dense layers, None = the fp32 trunk.  head: the

@@ -2,9 +2,10 @@
 
 Pure Python, no GPU: the window planner (which LR tiles a window of the HR grid touches, and which part of each), the least-recently-used
 cache that bounds the bytes of tile scenes kept alive, the record `CiaoSR.encode` returns, and the affine views of
-`CiaoSR.render_view` (their matrices, cells and tile lists, and `view_blocks_fit`: when a cut view may be queried in 4 x 2 blocks),
-and for `CiaoSR.render_many` the target records `Grid` / `View` and the tile-major plan (`plan_union`, `group_missing`).  The device
-work is in `PackedHead.prepare` / `query` (head_hip.py), `hip_ops.make_coord_cell_window` and the `hip_ops.view_*` wrappers.
+`CiaoSR.render_view` (their matrices, cells and tile lists, and `view_blocks_fit`: when a cut view may be queried in 4 x 2 blocks), the
+warps of `CiaoSR.render_warp` (homographies and coordinate maps, their footprints and checks),
+and for `CiaoSR.render_many` the target records `Grid` / `View` / `Warp` and the tile-major plan (`plan_union`, `group_missing`).  The
+device work is in `PackedHead.prepare` / `query` (head_hip.py), `hip_ops.make_coord_cell_window` and the `hip_ops.view_*` / `warp_*` wrappers.
 """
 import ctypes
 import math
@@ -218,6 +219,163 @@ def check_view(matrix, size, fill, h, w, tile=None, overlap=None, any_scale=Fals
     return m, (hv, wv), fill, frames
 
 
+# ---- warps (include/ciaosr_hip.h, "warps") -------------------------------------------------------------------------------------------
+# A warp is an output grid Hv x Wv, a point source that gives every output pixel (i, j) an LR position (y_lr, x_lr) in the views' LR pixel
+# units, and ONE footprint (f_y, f_x): the LR extent of an output pixel along each LR axis.  Two point sources.  A homography
+# h = (h00, h01, h02, h10, h11, h12, h20, h21, h22), y first: with v = i + 0.5, u = j + 0.5, in fp64, every operation rounded on its own,
+#     Y = (h00 v + h01 u) + h02,  X = (h10 v + h11 u) + h12,  D = (h20 v + h21 u) + h22,  y_lr = Y / D,  x_lr = X / D
+# -- a view's position, bit for bit, when the last row is (0, 0, 1).  Or a map: a device tensor [Hv, Wv, 2] of (y_lr, x_lr).  After the
+# position everything is the view's rule: membership, frame coordinate, tile plan, blend order, fill.  The footprint is what reaches the
+# model (the cell, and through it the shift radius): ONE per warp, so a warp whose local scale varies strongly over the output -- strong
+# perspective -- should be cut into several warps by the caller.
+def homography_of_view(matrix):
+    """The nine numbers of an affine view: its two rows and (0, 0, 1).  The warp of it is `render_view` of the matrix, bit for bit."""
+    m = [float(v) for v in matrix]
+    if len(m) != 6:
+        raise ValueError(f'a view matrix is six numbers (m_yy, m_yx, t_y, m_xy, m_xx, t_x), got {matrix!r}')
+    return (*m, 0.0, 0.0, 1.0)
+
+
+def homography_from_points(out_pts4, lr_pts4):
+    """The homography (h22 = 1) that takes the four output-pixel positions `out_pts4` = [(v, u)] * 4 (pixel (i, j) has its centre at
+    (i + 0.5, j + 0.5); the corners of an Hv x Wv output are (0, 0), (0, Wv), (Hv, Wv), (Hv, 0)) to the four LR positions `lr_pts4` =
+    [(y, x)] * 4: one float64 solve of the 8 x 8 system.  ValueError when the points do not determine it (three on a line)."""
+    import numpy as np
+    src, dst = np.asarray(out_pts4, dtype=np.float64), np.asarray(lr_pts4, dtype=np.float64)
+    if src.shape != (4, 2) or dst.shape != (4, 2) or not (np.isfinite(src).all() and np.isfinite(dst).all()):
+        raise ValueError('homography_from_points takes four finite (v, u) output positions and four finite (y, x) LR positions')
+    a, b = np.zeros((8, 8)), np.zeros(8)
+    for k, ((v, u), (y, x)) in enumerate(zip(src, dst)):
+        a[2 * k] = (v, u, 1.0, 0.0, 0.0, 0.0, -y * v, -y * u)
+        a[2 * k + 1] = (0.0, 0.0, 0.0, v, u, 1.0, -x * v, -x * u)
+        b[2 * k], b[2 * k + 1] = y, x
+    try:
+        sol = np.linalg.solve(a, b)
+    except np.linalg.LinAlgError:
+        raise ValueError('homography_from_points: the four point pairs do not determine a homography (three points on a line?)') from None
+    if not np.isfinite(sol).all():
+        raise ValueError('homography_from_points: the four point pairs do not determine a homography (three points on a line?)')
+    return (*(float(v) for v in sol), 1.0)
+
+
+def _h9(homography):
+    h = tuple(float(v) for v in homography)
+    if len(h) != 9 or not all(math.isfinite(v) for v in h):
+        raise ValueError(f'a homography is nine finite numbers (h00, h01, h02, h10, h11, h12, h20, h21, h22), got {homography!r}')
+    return h
+
+
+def warp_footprint(homography, size):
+    """The default footprint (f_y, f_x) of a homography on an Hv x Wv (`size`) output: the norms of the rows of its Jacobian at the
+    output centre (v, u) = (Hv / 2, Wv / 2), fp64:
+        J_yv = (h00 - y h20) / D, J_yu = (h01 - y h21) / D, f_y = hypot(J_yv, J_yu); likewise x.
+    With the last row (0, 0, 1) exactly hypot(m_yy, m_yx), hypot(m_xy, m_xx): the cell is then bitwise the view's."""
+    h = _h9(homography)
+    v, u = int(size[0]) / 2.0, int(size[1]) / 2.0
+    d = (h[6] * v + h[7] * u) + h[8]
+    if not d > 0.0:
+        raise ValueError(f'homography denominator {d} <= 0 at the output centre: the horizon crosses the output')
+    y, x = ((h[0] * v + h[1] * u) + h[2]) / d, ((h[3] * v + h[4] * u) + h[5]) / d
+    return (math.hypot((h[0] - y * h[6]) / d, (h[1] - y * h[7]) / d), math.hypot((h[3] - x * h[6]) / d, (h[4] - x * h[7]) / d))
+
+
+def _footprint(footprint):
+    try:
+        fp = tuple(float(v) for v in footprint)
+    except TypeError:
+        fp = ()
+    if len(fp) != 2 or not all(math.isfinite(v) and v > 0.0 for v in fp):
+        raise ValueError(f'a footprint is two finite positive numbers (f_y, f_x): the LR extent of an output pixel, got {footprint!r}')
+    return fp
+
+
+def warp_cell(footprint, th, tw):
+    """(cell_y, cell_x) of a warp in a th x tw frame, the fp32 values the kernels write: f * 2 / t, `view_cell`'s operations.  ValueError
+    for a footprint that is not finite and positive and for a cell component >= 1 (the reference divides by 1 - cell)."""
+    fp = _footprint(footprint)
+    cell = (_f32(fp[0] * 2.0 / th), _f32(fp[1] * 2.0 / tw))
+    if max(cell) >= 1.0:
+        raise ValueError(f'warp cell {cell} >= 1 in a {th} x {tw} frame: an output pixel may span less than half the frame '
+                         f'(the reference divides by 1 - cell)')
+    return cell
+
+
+def warp_max_scale(footprint):
+    """Output pixels per LR pixel along the finer of the two LR axes: what `encode`'s max_scale is set to by a first warp render
+    (`view_max_scale`'s value when the warp is affine)."""
+    fp = _footprint(footprint)
+    return max(1.0 / fp[0], 1.0 / fp[1])
+
+
+def map_footprint(map):
+    """A footprint for a coordinate map [Hv, Wv, 2] from central differences at its centre pixel (i, j) = (Hv // 2, Wv // 2):
+    f_y = hypot(dy/dv, dy/du), f_x = hypot(dx/dv, dx/du), one-sided where the centre lies on the border of the grid.  Costs ONE small
+    device-to-host copy (the centre's 3 x 3 neighbourhood), which synchronises: call it once per map, not per render.  ValueError where
+    the neighbourhood is not finite or the differences vanish -- give the footprint yourself then."""
+    shape = tuple(map.shape)
+    if len(shape) != 3 or shape[2] != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f'a warp map is [Hv, Wv, 2] of (y_lr, x_lr), got {shape}')
+    ci, cj = shape[0] // 2, shape[1] // 2
+    i0, i1, j0, j1 = max(ci - 1, 0), min(ci + 1, shape[0] - 1), max(cj - 1, 0), min(cj + 1, shape[1] - 1)
+    nb = map[i0:i1 + 1, j0:j1 + 1].cpu().double().tolist()             # the one copy
+    out = []
+    for c in range(2):
+        dv = (nb[i1 - i0][cj - j0][c] - nb[0][cj - j0][c]) / (i1 - i0) if i1 > i0 else 0.0
+        du = (nb[ci - i0][j1 - j0][c] - nb[ci - i0][0][c]) / (j1 - j0) if j1 > j0 else 0.0
+        out.append(math.hypot(dv, du))
+    if not all(math.isfinite(v) and v > 0.0 for v in out):
+        raise ValueError(f'map_footprint: the central differences at pixel {(ci, cj)} give {tuple(out)}; pass footprint=(f_y, f_x)')
+    return tuple(out)
+
+
+def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=None, any_scale=False):
+    """The arguments of a warp render, checked in `CiaoSR.render_warp`'s order, all on the host: -> (h9 or None, map or None, (hv, wv),
+    (f_y, f_x), fill3, frames) with frames = `plan_view`'s list.  ValueError for: not exactly one point source; an empty grid; tiles
+    without `tile_any_scale`; a non-finite homography entry; a denominator <= 0 at a corner (0, 0), (Hv, 0), (0, Wv), (Hv, Wv) of the grid
+    (D is affine in (v, u): positive corners mean positive everywhere -- the horizon must not cross the output); a map that is not a
+    float64 / float32 tensor [Hv, Wv, 2]; a map without a footprint; a footprint that is not finite and positive; a cell >= 1; a fill
+    outside [0, 1].  A map on the host is a CiaoSRHipError: there is no CPU fallback."""
+    if (homography is None) == (map is None):
+        raise ValueError('a warp has exactly one point source: give homography=(nine numbers) or map=(device tensor [Hv, Wv, 2])')
+    if map is not None:
+        shape = tuple(getattr(map, 'shape', ()))
+        if len(shape) != 3 or shape[2] != 2 or str(getattr(map, 'dtype', None)) not in ('torch.float64', 'torch.float32'):
+            raise ValueError(f'a warp map is a float64 (or float32) tensor [Hv, Wv, 2] of (y_lr, x_lr), got '
+                             f'{getattr(map, "dtype", type(map).__name__)} {shape}')
+        if size is None:
+            size = shape[:2]
+    if size is None:
+        raise ValueError('a homography warp needs size=(Hv, Wv)')
+    hv, wv = int(size[0]), int(size[1])
+    if hv < 1 or wv < 1:
+        raise ValueError(f'empty warp grid {hv} x {wv}')
+    frames = plan_view(h, w, tile, overlap, any_scale)
+    if map is not None:
+        if shape[:2] != (hv, wv):
+            raise ValueError(f'a warp map is [Hv, Wv, 2] = [{hv}, {wv}, 2] for size {(hv, wv)}, got {shape}')
+        if not map.is_cuda:
+            from ._lib import CiaoSRHipError
+            raise CiaoSRHipError('a warp map lives on the MI355X: got a CPU tensor (no CPU fallback; move the map to cuda)')
+        if footprint is None:
+            raise ValueError('a map warp needs footprint=(f_y, f_x), the LR extent of an output pixel (scene.map_footprint(map) offers one)')
+        h9 = None
+    else:
+        h9 = _h9(homography)
+        for v, u in ((0.0, 0.0), (float(hv), 0.0), (0.0, float(wv)), (float(hv), float(wv))):
+            d = (h9[6] * v + h9[7] * u) + h9[8]
+            if not d > 0.0:
+                raise ValueError(f'homography denominator {d} <= 0 at the grid corner (v, u) = {(v, u)}: the horizon must not cross '
+                                 f'the {hv} x {wv} output')
+        if footprint is None:
+            footprint = warp_footprint(h9, (hv, wv))
+    fp = _footprint(footprint)
+    warp_cell(fp, frames[0][2], frames[0][3])                     # ValueError: a cell >= 1
+    fill = tuple(float(v) for v in fill) if hasattr(fill, '__len__') else (float(fill),) * 3
+    if len(fill) != 3 or not all(0.0 <= v <= 1.0 for v in fill):
+        raise ValueError(f'fill is one number or three in [0, 1], got {fill}')
+    return h9, map, (hv, wv), fp, fill, frames
+
+
 # ---- many targets from one walk over the tiles (CiaoSR.render_many / prefetch) --------------------------------------------------------
 class Grid:
     """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render`."""
@@ -248,6 +406,22 @@ class View:
 
     def __repr__(self):
         return f'View({self.matrix!r}, size={self.size!r}, fill={self.fill!r})'
+
+
+class Warp:
+    """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render_warp`."""
+    __slots__ = ('homography', 'map', 'size', 'footprint', 'fill')
+
+    def __init__(self, homography=None, map=None, size=None, footprint=None, fill=0.0):
+        self.homography, self.map, self.size, self.footprint, self.fill = homography, map, size, footprint, fill
+
+    def resolve(self, h, w, tile=None, overlap=None, any_scale=False):
+        """`check_warp` of the record: (h9 or None, map or None, (hv, wv), footprint, fill3, frames), with `render_warp`'s errors."""
+        return check_warp(self.homography, self.map, self.size, self.footprint, self.fill, h, w, tile, overlap, any_scale)
+
+    def __repr__(self):
+        source = f'homography={self.homography!r}' if self.map is None else f'map=<{tuple(getattr(self.map, "shape", ()))}>'
+        return f'Warp({source}, size={self.size!r}, footprint={self.footprint!r}, fill={self.fill!r})'
 
 
 def plan_union(touched):

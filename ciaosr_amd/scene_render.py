@@ -1,5 +1,6 @@
-"""The scene renderer behind CiaoSR.encode / render / render_view / render_many / prefetch / render_pyramid (an extension, absent from the
-reference): the device side of scene.py.  A target -- `scene.Grid` or `scene.View`, resolved into a `GridTarget` or a `ViewTarget` --
+"""The scene renderer behind CiaoSR.encode / render / render_view / render_warp / render_many / prefetch / render_pyramid (an extension,
+absent from the reference): the device side of scene.py.  A target -- `scene.Grid`, `scene.View` or `scene.Warp`, resolved into a
+`GridTarget`, a `ViewTarget` or a `WarpTarget` --
 knows the tiles it touches, its accumulators, how to query one tile's scene into them and how to finish them; the single calls take the
 scenes from the cache tile by tile, `render_many` and `prefetch` from one walk over the union of the tiles (`scene_walk`), whose missing
 scenes are built from batched trunk calls on `CiaoSR.trunk_ahead`.  Every function takes the restorer first."""
@@ -110,6 +111,8 @@ def render_ensemble(r, enc, targets, as_u8=False, many=False, as_u16=False):
     for tg in targets:
         if isinstance(tg, sc.View):
             refuse_ensemble(enc, 'a view')
+        if isinstance(tg, sc.Warp):
+            refuse_ensemble(enc, 'a warp')
         if not isinstance(tg, sc.Grid):
             raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
     h, w = enc.shape
@@ -264,6 +267,39 @@ class ViewTarget:
         return hip_ops.denorm_clamp(hip_ops.view_finalize(*acc, fill, r.rgb_mean, r.rgb_std), *self.size, r.rgb_mean, r.rgb_std)
 
 
+class WarpTarget(ViewTarget):
+    """A resolved scene.Warp: its point source -- the homography `h` (nine numbers) or the device map `map` [hv, wv, 2] float64, the other
+    None --, the `footprint`, output `size`, `fill` and the frames.  Everything after the LR position is the view's: `touched`, `alloc` and
+    `finish` are ViewTarget's own.  `test_cfg.view_blocks` is ignored: a cut warp's member lists stay in index order."""
+
+    def __init__(self, cfg, h, map_, size, footprint, fill, frames):
+        self.h, self.footprint, self.size, self.fill, self.frames = h, footprint, size, fill, frames
+        # a float32 map is widened exactly; the kernels read one aligned 16-byte (y_lr, x_lr) pair per query
+        self.map = None if map_ is None else map_.detach().to(torch.float64).contiguous()
+        self.max_scale = sc.warp_max_scale(footprint)
+        self.tiled = bool(cfg.get('tile', None))
+        self.counts = self.n_blocks = self.ws = None
+
+    def count(self, r, enc):
+        """Count this warp alone: the ONE device-to-host copy, and the only synchronisation, of a single warp render of a batch item."""
+        self.counts = self.launch_count(enc).tolist()
+
+    def launch_count(self, enc, ws=None):
+        """The count launch pair without the copy: -> the counts on the device (`render_many` copies every target's at once)."""
+        counts, self.ws = hip_ops.warp_count(self.h, self.map, self.footprint, *self.size, _view_tiles(enc, self.frames), ws)
+        return counts
+
+    def query(self, gen, k, tile_scene, acc):
+        """Frame k's members from its scene, blended into `acc`."""
+        (hv, wv), frame, n = self.size, self.frames[k], self.counts[k]
+        if n == hv * wv:                                                # the frame owns every query: a grid, known to the head as one
+            q_index = None
+            coord, cell = hip_ops.make_coord_cell_warp(self.h, self.map, self.footprint, hv, wv, frame, tile_scene.x.device)
+        else:
+            q_index, coord, cell = hip_ops.warp_select(self.h, self.map, self.footprint, hv, wv, frame, k, len(self.frames), self.ws, n)
+        hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell)[0])
+
+
 def view_blocks(r, enc, m, frames):
     """Whether the partial member lists of view `m` are selected in 4 x 2 blocks (`hip_ops.view_select_blocks`): `test_cfg.view_blocks`
     is on, `scene.view_blocks_fit(m)` holds, and the route the tile scenes are planned under runs the chained 16-bit kv kernel --
@@ -281,10 +317,11 @@ def _view_tiles(enc, frames):
     return enc.view_tiles
 
 
-def count_views(r, enc, views):
+def count_views(r, enc, views, warps=()):
     """`ViewTarget.count` for ALL views of a `render_many` / `prefetch` in one `view_count_many` (and one `view_count_blocks_many` for
-    those selected in blocks) and one device-to-host copy -- per call, not per batch item: the counts do not depend on the item."""
-    frames = views[0].frames                                            # the image's: the same for every view
+    those selected in blocks) and one device-to-host copy -- per call, not per batch item: the counts do not depend on the item.
+    `warps`: each is counted by its own launch pair, into its own part of one workspace, and its counts ride in the same copy."""
+    frames = (list(views) + list(warps))[0].frames                      # the image's: the same for every view and warp
     n_t = len(frames)
     plain, blk = [], []
     for v in views:
@@ -296,6 +333,13 @@ def count_views(r, enc, views):
             flat.append(counts.flatten())
             for v, off in zip(group, offsets):
                 v.ws = ws[off:]
+    if warps:
+        sizes = [(hip_ops.warp_workspace_bytes(*wp.size, n_t) + 255) & ~255 for wp in warps]
+        ws = hip_ops.workspace(sum(sizes), enc.x.device, slot='warp_many')
+        off = 0
+        for wp, nbytes in zip(warps, sizes):
+            flat.append(wp.launch_count(enc, ws[off:off + nbytes]))
+            off += nbytes
     flat = (flat[0] if len(flat) == 1 else torch.cat(flat)).tolist()    # the one synchronisation of the call
     for i, v in enumerate(plain):
         v.counts = flat[i * n_t:(i + 1) * n_t]
@@ -303,6 +347,9 @@ def count_views(r, enc, views):
     for i, v in enumerate(blk):                                         # per tile (members, live blocks of 4 x 2 output pixels)
         both = flat[base + 2 * i * n_t:base + 2 * (i + 1) * n_t]
         v.counts, v.n_blocks = both[0::2], both[1::2]
+    base += 2 * len(blk) * n_t
+    for i, wp in enumerate(warps):
+        wp.counts = flat[base + i * n_t:base + (i + 1) * n_t]
 
 
 def resolve(r, enc, targets):
@@ -320,8 +367,10 @@ def resolve(r, enc, targets):
             out.append(GridTarget(cfg, h, w, *tg.resolve(h, w)))
         elif isinstance(tg, sc.View):
             out.append(ViewTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale)))
+        elif isinstance(tg, sc.Warp):
+            out.append(WarpTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale)))
         else:
-            raise TypeError(f'a target is a scene.Grid or a scene.View, got {type(tg).__name__}')
+            raise TypeError(f'a target is a scene.Grid, a scene.View or a scene.Warp, got {type(tg).__name__}')
     if enc.max_scale is None:
         enc.max_scale = max(tg.max_scale for tg in out)
     return out
@@ -355,9 +404,10 @@ def plan_many(r, enc, targets):
     """Everything `render_many` / `prefetch` know before a scene is touched: -> (the resolved targets, walk, users).  walk: the union
     of the tiles the targets touch as [(tile index, origin)], row-major; users[tile index]: the targets that touch it, in list order."""
     tgs = resolve(r, enc, targets)
-    views = [tg for tg in tgs if isinstance(tg, ViewTarget)]
-    if views:
-        count_views(r, enc, views)
+    warps = [tg for tg in tgs if isinstance(tg, WarpTarget)]
+    views = [tg for tg in tgs if isinstance(tg, ViewTarget) and not isinstance(tg, WarpTarget)]
+    if views or warps:
+        count_views(r, enc, views, warps)
     origins = {}
     for tg in tgs:
         origins.update(tg.touched())

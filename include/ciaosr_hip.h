@@ -722,6 +722,30 @@ int ciaosr_view_blend_f32(float* E, float* Wt, int Q, const int* q_index /*may b
 int ciaosr_view_finalize_f32(const float* E, const float* Wt, float* out_q3, int Q, const float* fill3 /*host*/, const float* mean3 /*host*/,
                              const float* std3 /*host*/, void* stream);
 
+/* ---- warps: an encoded scene seen through a homography or a per-pixel coordinate map (an extension, absent from the reference) --------
+ * A warp is an output grid Hv x Wv, a POINT SOURCE that gives output pixel (i, j), query q = i Wv + j, an LR position (y_lr, x_lr) in the
+ * views' LR pixel units, and ONE footprint {f_y, f_x} (host doubles): the LR extent of an output pixel along each LR axis.  Every entry
+ * takes exactly one point source, the other pointer NULL (else CIAOSR_ERR_BAD_ARG):
+ *   h9  (host [9]) = {h00, h01, h02, h10, h11, h12, h20, h21, h22}, y first.  With v = i + 0.5, u = j + 0.5, in fp64, every operation
+ *       rounded on its own (no FMA), IEEE division:
+ *           Y = (h00 v + h01 u) + h02,  X = (h10 v + h11 u) + h12,  D = (h20 v + h21 u) + h22,  y_lr = Y / D,  x_lr = X / D.
+ *       Finite entries, and D > 0 at the corners (v, u) = (0, 0), (Hv, 0), (0, Wv), (Hv, Wv) of the grid -- D is affine, so it is then
+ *       positive on all of it: the horizon does not cross the output.  With the last row {0, 0, 1} the position is a view's, bit for bit.
+ *   map (device, 16-byte aligned, [Hv Wv][2] doubles) = (y_lr, x_lr) of every query, read as one 16-byte load.  A NaN or infinite entry
+ *       belongs to no tile.
+ * After the position everything is the view's: membership and coord as above, cell = fp32(f_y 2 / th), fp32(f_x 2 / tw) -- constant over
+ * the warp -- and blend / finalize are ciaosr_view_blend_f32 / ciaosr_view_finalize_f32.  The footprint is finite and positive.  Count,
+ * workspace and select are ciaosr_view_count_i32's scheme and layout (ciaosr_view_block_queries() queries per workgroup); sizes are 0
+ * for what count refuses.  Hv Wv <= 2^31 - 1.  No entry allocates, synchronises or keeps state; no atomics: bitwise repeatable. */
+size_t ciaosr_warp_workspace_bytes(int Hv, int Wv, int n_tiles);
+int ciaosr_warp_coord_cell_f32(float* coord, float* cell, const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/,
+                               const double* footprint /*host [2]*/, int Hv, int Wv, const int* frame /*host [4]*/, void* stream);
+int ciaosr_warp_count_i32(const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, const double* footprint /*host [2]*/,
+                          int Hv, int Wv, const int* tiles, int n_tiles, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_warp_select_f32(const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, const double* footprint /*host [2]*/,
+                           int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles, const void* workspace,
+                           size_t workspace_bytes, int n, int* q_index, float* coord, float* cell, void* stream);
+
 /* ---- self-ensemble: the eight flips and transposes of an image, and the mean through their inverses (an extension, absent from the
  * reference) ---------------------------------------------------------------------------------------------------------------------------
  * k in 0..7.  T_k acts on the last two axes of [planes][H][W]: k & 1: flip the columns; then k & 2: flip the rows; then k & 4: transpose

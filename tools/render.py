@@ -3,6 +3,7 @@
 
     python tools/render.py CONFIG CHECKPOINT IMAGE --scale S [S ...] [--window I0 J0 H W] [--precision P] --out DIR
     python tools/render.py CONFIG CHECKPOINT IMAGE [--scale ...] --view CY CX ZOOM ANGLE --size H W [--view ... --size ...] --out DIR
+    python tools/render.py CONFIG CHECKPOINT IMAGE [--scale ...] --homography H00 H01 H02 H10 H11 H12 H20 H21 H22 --size H W --out DIR
 
 Config and checkpoint as for tools/test.py.  The trunk, cs_attn and the head's per-image tables run once (CiaoSR.encode); every
 scale and view is a target of ONE CiaoSR.render_many -- a single walk over the tile scenes, each built once however many outputs touch
@@ -14,6 +15,12 @@ largest --scale; without --scale the largest view ZOOM).  Every `--view` (repeat
 ciaosr_amd.scene.view_matrix((CY, CX), ZOOM, ANGLE, (H, W)): an H x W picture whose centre looks at LR position (CY, CX) with ZOOM output
 pixels per LR pixel, turned by ANGLE degrees (positive: the picture turns clockwise), written to DIR/<image name>_view<k>.png, k = 0,
 1, ... in command-line order; one `--size` per `--view`, or a single one for all of them.  Pixels outside the image are black.
+Every `--homography` (repeatable; alone or alongside --scale and --view) is a CiaoSR.render_warp: an H x W picture whose pixel centre
+(v, u) = (i + 0.5, j + 0.5) looks at the LR position y = (H00 v + H01 u + H02) / D, x = (H10 v + H11 u + H12) / D, D = H20 v + H21 u + H22
+(ciaosr_amd.scene: keystone and perspective correction; `homography_from_points` makes one from four point pairs), written to DIR/<image
+name>_warp<k>.png in command-line order.  `--size` follows the rule of `--view`: one per --view and --homography, the views first, or a
+single one for all of them.  D must be positive on the whole output; the model sees ONE footprint per warp, the Jacobian at the output
+centre, so strong perspective is better cut into several warps.  Not with --self-ensemble or --tiff (an argparse error).
 `--gpu-png` sets `test_cfg.gpu_png`: every output is rendered as a uint8 image on the device and PNG-encoded there (ciaosr_amd/png_hip.py);
 the files decode to the pixels of the default run.
 `--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
@@ -85,7 +92,11 @@ def parse_args(argv=None):
     p.add_argument('--scale', type=float, nargs='+', default=[], help='one output per scale: round(h * s) x round(w * s)')
     p.add_argument('--view', type=float, nargs=4, action='append', default=[], metavar=('CY', 'CX', 'ZOOM', 'ANGLE'),
                    help='one output per view: centre in LR pixels, output pixels per LR pixel, degrees (repeatable)')
-    p.add_argument('--size', type=int, nargs=2, action='append', default=[], metavar=('H', 'W'), help='output size of each --view')
+    p.add_argument('--homography', type=float, nargs=9, action='append', default=[],
+                   metavar=('H00', 'H01', 'H02', 'H10', 'H11', 'H12', 'H20', 'H21', 'H22'),
+                   help='one output per homography: output pixel centres (v, u) to LR positions (y, x), y first (repeatable)')
+    p.add_argument('--size', type=int, nargs=2, action='append', default=[], metavar=('H', 'W'),
+                   help='output size of each --view and --homography')
     p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
     p.add_argument('--view-blocks', action='store_true',
@@ -124,11 +135,13 @@ def parse_args(argv=None):
                    help='the scale the scenes are planned for (default: the largest --scale, else the largest ZOOM; with --dzi at least its SCALE)')
     p.add_argument('--out', required=True, help='output directory')
     args = p.parse_args(argv)
-    if not args.scale and not args.view and args.dzi is None:
+    if not args.scale and not args.view and not args.homography and args.dzi is None:
         p.error('give --scale, --view, --dzi or several of them')
-    if args.view and len(args.size) not in (1, len(args.view)):
+    if args.view and not args.homography and len(args.size) not in (1, len(args.view)):
         p.error('give one --size H W per --view, or a single one for all views')
-    if args.size and not args.view:
+    if args.homography and len(args.size) not in (1, len(args.view) + len(args.homography)):
+        p.error('give one --size H W per --view and --homography (the views first), or a single one for all of them')
+    if args.size and not args.view and not args.homography:
         p.error('--size belongs to --view')
     if args.jpeg is not None and not 1 <= args.jpeg <= 100:
         p.error('--jpeg takes a quality in 1..100')
@@ -154,6 +167,8 @@ def parse_args(argv=None):
                             ('--niqe', args.niqe is not None), ('--self-ensemble', args.self_ensemble), ('--dzi', args.dzi is not None)):
             if given:
                 p.error(f'--tiff with {flag}: a pyramidal TIFF is the whole render of a plain encode in deflate tiles, drop one of the two')
+        if args.homography:
+            p.error('--tiff with --homography: a pyramidal TIFF is the whole render of a plain encode in deflate tiles, drop one of the two')
         if args.tiff_tile < 16 or args.tiff_tile > 4096 or args.tiff_tile % 16:
             p.error('--tiff-tile is a multiple of 16 in 16..4096')
     if args.png_matches and not (args.gpu_png or args.alpha or args.grey or args.depth16 or args.tiff):
@@ -165,6 +180,8 @@ def parse_args(argv=None):
     if args.self_ensemble and (args.view or args.dzi is not None or args.alpha):
         p.error('--self-ensemble applies to --scale and --window outputs: views, pyramids and RGBA encodes have no ensemble, drop '
                 '--view / --dzi / --alpha')
+    if args.self_ensemble and args.homography:
+        p.error('--self-ensemble applies to --scale and --window outputs: warps have no ensemble, drop --homography')
     return args
 
 
@@ -217,6 +234,10 @@ def main(argv=None):
             print(f'{args.image}: no transparent pixel, --alpha changes nothing')
         alpha = not opaque
     wanted = args.scale or [v[2] for v in args.view]
+    sizes = [args.size[k if len(args.size) > 1 else 0] for k in range(len(args.view) + len(args.homography))]
+    if args.homography and not args.scale:                                           # without --homography `wanted` is what it was
+        from ciaosr_amd.scene import warp_footprint, warp_max_scale
+        wanted = wanted + [warp_max_scale(warp_footprint(h, size)) for h, size in zip(args.homography, sizes[len(args.view):])]
     if args.dzi is not None:
         wanted = wanted + [args.dzi]
     if alpha:
@@ -241,7 +262,7 @@ def main(argv=None):
         ens = dict(self_ensemble=True) if args.self_ensemble else {}                 # without --self-ensemble encode is called as before
         enc = model.encode(lq, max_scale=args.max_scale or max(wanted), **ens)
     name = os.path.splitext(os.path.basename(args.image))[0]
-    from ciaosr_amd.scene import Grid, View, view_matrix
+    from ciaosr_amd.scene import Grid, View, Warp, view_matrix
     form = output_format(args)
     coding = {k: form[k] for k in ('quality', 'subsampling', 'optimize', 'progressive') if k in form}
     dzi_format = dict(fmt='jpg', **coding) if form['fmt'] == 'jpg' else {}           # without --jpeg write_dzi is called as before
@@ -262,6 +283,9 @@ def main(argv=None):
         size = args.size[k if len(args.size) > 1 else 0]
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
+    for k, h in enumerate(args.homography):
+        targets.append(Warp(homography=h, size=sizes[len(args.view) + k]))
+        paths.append(os.path.join(args.out, f'{name}_warp{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
     as_u8 = (gpu_png or form['fmt'] == 'jpg' or alpha or args.grey) and not args.depth16
     quant = dict(as_u16=True) if args.depth16 else dict(as_u8=as_u8)                 # without --depth16 render_many is called as before

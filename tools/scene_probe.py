@@ -18,6 +18,9 @@ to that file: profiles/view_blocks.txt) holds per precision and leg the wall tim
 8 * blocks / members - 1 of the block list, and the flag of the leg's head query (`PackedHead.query(..., return_flag=True)` on the
 list the leg selects: 1 = the chained 16-bit kernel gave the launch up to the gated 128-row kernel; n/a where no chained kernel runs).
 
+`--legs warp` (profiles/warp_render.txt, with `--out`): the affine-degenerate homography, the same points as a map, and `render_view` of
+that matrix, alternating, by the protocol of the view legs (`warp_legs`).
+
 `--legs many` (profiles/render_many.txt, with `--out`) is the tiled image of bench.py -- LR 1356 x 2040, tile 192 / overlap 32,
 `tile_any_scale`: 9 x 13 = 117 tiles -- rendered at x2, x3.3 and x4 (full grids) from one encode, per precision and for two scene caches
 (the default `scene_cache_mb`, and one that holds every scene):
@@ -42,7 +45,7 @@ ap.add_argument('--sizes', default='192,48')
 ap.add_argument('--precisions', default='fp32,f16')
 ap.add_argument('--scales', default='4,2,3.3')
 ap.add_argument('--reps', type=int, default=5)
-ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many'))
+ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many', 'warp'))
 ap.add_argument('--view-size', type=int, default=768)
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help='tree whose package and library run')
 ap.add_argument('--parent-root', default=None, help='--legs many: a built checkout of the parent commit for leg (a)')
@@ -164,6 +167,62 @@ def view_legs():
         hip_ops.release_workspaces()
         torch.cuda.empty_cache()
     print()
+    print('\n'.join(report))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(report) + '\n')
+
+
+def warp_legs():
+    """`--legs warp`: per precision three legs alternating in one process on the first of `--sizes` (the C3 tile, whole-image test_cfg,
+    scene planned for x4), `--view-size` squared at zoom x4 turned by 30 degrees: the affine-degenerate homography, the same points as
+    a map, and `render_view` of that matrix -- all three the same picture, bit for bit.  2 warm-up rounds, `--reps` timed rounds, wall
+    time between device synchronisations; one more round under hip_ops.profile gives the device time of the warp / view kernels, of the
+    coordinate kernels and of the head query.  With `--out` the report is also written to that file (profiles/warp_render.txt)."""
+    from ciaosr_amd.scene import homography_of_view, view_matrix, warp_footprint
+    size, n = int(args.sizes.split(',')[0]), args.view_size
+    report = [f'tools/scene_probe.py --legs warp --reps {args.reps}: library version {_lib.load().ciaosr_version()}, '
+              f'{torch.cuda.get_device_name(0)}; {size}x{size} LR, {n} x {n} output at x4 turned by 30 degrees, three legs alternating in one '
+              f'process (2 warm-up rounds, {args.reps} timed rounds)']
+    lq = synthetic_pair(size, size, 4)[0].to(dev)
+    groups = (('warp / view kernels', lambda k: k.startswith(('view_', 'warp_')) and k not in ('view_coord_cell', 'warp_coord_cell')),
+              ('coordinates', lambda k: k in ('view_coord_cell', 'warp_coord_cell')),
+              ('head query', lambda k: not k.startswith(('view_', 'warp_', 'make_coord_cell')) and k != 'denorm_clamp'))
+    m = view_matrix((size / 2, size / 2), 4.0, 30, (n, n))
+    h = homography_of_view(m)
+    fp = warp_footprint(h, (n, n))
+    v = (torch.arange(n, dtype=torch.float64, device=dev) + 0.5).view(n, 1)
+    u = (torch.arange(n, dtype=torch.float64, device=dev) + 0.5).view(1, n)
+    points = torch.stack([(m[0] * v + m[1] * u) + m[2], (m[3] * v + m[4] * u) + m[5]], -1).contiguous()
+    for precision in args.precisions.split(','):
+        model.test_cfg = dict(scale=4, precision=precision)
+        enc = model.encode(lq)
+        calls = {'homography': lambda: model.render_warp(enc, homography=h, size=(n, n)),
+                 'map': lambda: model.render_warp(enc, map=points, footprint=fp),
+                 'render_view': lambda: model.render_view(enc, m, (n, n))}
+        outs = {k: fn() for k, fn in calls.items()}
+        same = all(torch.equal(outs[k], outs['render_view']) for k in ('homography', 'map'))
+        report.append(f'  {precision}: both warps bitwise render_view: {same}; {(outs["render_view"].sum(1) == 0).float().mean().item():.1%} of '
+                      f'the pixels outside')
+        del outs
+        for _ in range(2):
+            for fn in calls.values():
+                fn()
+        times = {k: [] for k in calls}
+        for _ in range(args.reps):
+            for k, fn in calls.items():
+                times[k].append(timed(fn)[0])
+        for k, fn in calls.items():
+            with hip_ops.profile():
+                fn()
+            prof = hip_ops.profile.results()
+            t = times[k]
+            parts = ', '.join(f'{name} {sum(r["total_ms"] for kk, r in prof.items() if pick(kk)):8.3f} ms '
+                              f'({sum(r["launches"] for kk, r in prof.items() if pick(kk))} launches)' for name, pick in groups)
+            report.append(f'    {k:12s} wall mean {sum(t) / len(t):8.3f} ms  min {min(t):8.3f}  max {max(t):8.3f} | device: {parts}')
+        del enc, calls
+        hip_ops.release_workspaces()
+        torch.cuda.empty_cache()
     print('\n'.join(report))
     if args.out:
         with open(args.out, 'w') as f:
@@ -333,6 +392,8 @@ def many_legs():
 scales = [float(s) for s in args.scales.split(',')]
 if args.legs == 'view':
     view_legs()
+if args.legs == 'warp':
+    warp_legs()
 if args.legs == 'many':
     many_worker() if args.worker else many_legs()
 for size in (int(v) for v in args.sizes.split(',') if args.legs == 'scene'):
