@@ -207,6 +207,12 @@ SIGNATURES = {
     'ciaosr_warp_count_i32': (_I, [C.POINTER(C.c_double), _P, C.POINTER(C.c_double), _I, _I, _P, _I, _P, _P, _S, _P]),
     'ciaosr_warp_select_f32': (_I, [C.POINTER(C.c_double), _P, C.POINTER(C.c_double), _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _P, _P, _P,
                                     _P]),
+    # per-pixel warps (version 371): (mode, range [2], tensor) in place of the footprint
+    'ciaosr_ppwarp_coord_cell_f32': (_I, [_P, _P, C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, C.POINTER(_I), _P]),
+    'ciaosr_ppwarp_count_i32': (_I, [C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_ppwarp_select_f32': (_I, [C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I,
+                                      _P, _P, _P, _P]),
+    'ciaosr_ppwarp_footprints_f64': (_I, [_P, C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, _P]),
     'ciaosr_dihedral_f32': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'ciaosr_dihedral_accum_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),

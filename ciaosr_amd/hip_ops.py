@@ -472,6 +472,69 @@ def warp_select(h, map_, footprint, hv, wv, frame, index, n_tiles, ws, n):
     return q_index, coord, cell
 
 
+# ---- per-pixel warps (include/ciaosr_hip.h, "per-pixel warps"): `spec` is a scene.PerPixel with a float64 contiguous device tensor -------
+def _warp_pp_source(h, map_, spec, hv, wv):
+    """The (h9, map, mode, range, tensor) arguments of a per-pixel warp entry."""
+    h9, mp, _ = _warp_source(h, map_, (1.0, 1.0), hv, wv)
+    tensor = C.c_void_p(0)
+    if spec.tensor is not None:
+        t = spec.tensor
+        if not t.is_cuda:
+            raise CiaoSRHipError('a footprint tensor lives on the MI355X: got a CPU tensor (no CPU fallback; move it to cuda)')
+        if t.dtype != torch.float64 or tuple(t.shape) != (hv, wv, 2) or not t.is_contiguous():
+            raise ValueError(f'a footprint tensor is a contiguous float64 tensor [{hv}, {wv}, 2] of (g_y, g_x), got {t.dtype} {tuple(t.shape)}')
+        tensor = ptr(t)
+    return h9, mp, int(spec.mode), (C.c_double * 2)(*[float(v) for v in spec.range]), tensor
+
+
+def make_coord_cell_warp_pp(h, map_, spec, hv, wv, frame, device):
+    """`make_coord_cell_warp` of a per-pixel warp: cell [hv * wv, 2] holds every query's own cell (NaN where the pixel has no footprint)."""
+    src = _warp_pp_source(h, map_, spec, hv, wv)
+    n = hv * wv
+    coord = torch.empty(n, 2, dtype=torch.float32, device=device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=device)
+    _lib.call('ciaosr_ppwarp_coord_cell_f32', ptr(coord), ptr(cell), *src, hv, wv, _i4(frame), stream_ptr())
+    if len(_window_width) > 64:
+        _window_width.clear()
+    _window_width[(coord.data_ptr(), n)] = wv
+    return coord, cell
+
+
+def warp_pp_count(h, map_, spec, hv, wv, tiles, ws=None):
+    """`warp_count` of a per-pixel warp: a pixel without a footprint is a member of no tile.  The workspace is `warp_count`'s."""
+    require_gpu(tiles)
+    src = _warp_pp_source(h, map_, spec, hv, wv)
+    n_tiles = tiles.shape[0]
+    if ws is None:
+        ws = workspace(warp_workspace_bytes(hv, wv, n_tiles), tiles.device, slot='warp')
+    counts = torch.empty(n_tiles, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_ppwarp_count_i32', *src, hv, wv, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws
+
+
+def warp_pp_select(h, map_, spec, hv, wv, frame, index, n_tiles, ws, n):
+    """`warp_select` of a per-pixel warp (`n`, `ws`: warp_pp_count's): cell [n, 2] holds each member's own cell in the tile's frame."""
+    src = _warp_pp_source(h, map_, spec, hv, wv)
+    q_index = torch.empty(n, dtype=torch.int32, device=ws.device)
+    coord = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    _window_width.pop((coord.data_ptr(), n), None)          # the allocator may hand out the address of a dead grid's coordinates
+    _lib.call('ciaosr_ppwarp_select_f32', *src, hv, wv, _i4(frame), index, n_tiles, ptr(ws), ws.numel(), n, ptr(q_index), ptr(coord),
+              ptr(cell), stream_ptr())
+    return q_index, coord, cell
+
+
+def warp_footprints(h, map_, spec, hv, wv, device=None):
+    """The clamped footprints (f_y, f_x) of the whole grid of a per-pixel warp, [hv, wv, 2] float64 on the device, NaN where the pixel has
+    none: a warp's scale field, for inspection.  Nothing synchronises."""
+    src = _warp_pp_source(h, map_, spec, hv, wv)
+    if device is None:
+        device = map_.device if map_ is not None else (spec.tensor.device if spec.tensor is not None else torch.device('cuda'))
+    out = torch.empty(hv, wv, 2, dtype=torch.float64, device=device)
+    _lib.call('ciaosr_ppwarp_footprints_f64', ptr(out), *src, hv, wv, stream_ptr())
+    return out
+
+
 class Mode(namedtuple('Mode', 'name precision f16_pairs bf16_single trunk head')):
     """One named arithmetic mode.  (precision, f16_pairs, bf16_single): the entry suffix and the canonical ciaosr_options_t fields
     (include/ciaosr_hip.h, "Precision modes").  trunk: element type of the RDN trunk's dense layers, None = the fp32 trunk.  head: the

@@ -131,14 +131,15 @@ class LocalImplicitSRNet(nn.Module):
         return EncodedFeatures([self._head.prepare(None, options, q_plan, feature_hwc=feats[b]) for b in range(x.shape[0])], x, options)
 
     @torch.no_grad()
-    def render(self, enc, coord, cell, return_flags=False):
+    def render(self, enc, coord, cell, return_flags=False, chunk=None):
         """`forward(x, coord, cell, test_mode=True)` from an `encode` result: coord/cell [B,Q,2] (or [Q,2], shared by the batch) -> [B,Q,3],
-        for any Q, any number of times.  `return_flags`: -> ([B,Q,3], [B] int32 on the device), per item the flag of
+        for any Q, any number of times.  `chunk`: the number of consecutive queries that share the shift radius of their first one,
+        None: `eval_bsize` (1: every query has the radius of its own cell -- per-pixel warps).  `return_flags`: -> ([B,Q,3], [B] int32 on the device), per item the flag of
         `PackedHead.query(..., return_flag=True)` (scenes on the chained 16-bit kv kernel only)."""
         outs, flags = [], []
         for b, scene in enumerate(enc.scenes):
             cq, cl = (coord, cell) if coord.dim() == 2 else (coord[b], cell[b])
-            out = self._head.query(scene, enc.x[b], cq, cl, self.eval_bsize, return_flag=return_flags)
+            out = self._head.query(scene, enc.x[b], cq, cl, self.eval_bsize if chunk is None else chunk, return_flag=return_flags)
             if return_flags:
                 out, flag = out
                 flags.append(flag)

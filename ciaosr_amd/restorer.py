@@ -562,7 +562,8 @@ class CiaoSR(BasicRestorer):
         return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [scene.View(matrix, size, fill)])[0], as_u8, as_u16)
 
     @torch.no_grad()
-    def render_warp(self, enc, homography=None, map=None, size=None, footprint=None, fill=0.0, as_u8=False, as_u16=False):
+    def render_warp(self, enc, homography=None, map=None, size=None, footprint=None, fill=0.0, as_u8=False, as_u16=False,
+                    footprint_range=None):
         """The Hv x Wv (`size`) warp of an `encode` result (scene.py: the definition): every output pixel is answered by the model at its
         own LR position, which comes from ONE of two point sources.  `homography` = (h00, h01, h02, h10, h11, h12, h20, h21, h22), y
         first: y_lr = Y / D, x_lr = X / D of Y = (h00 v + h01 u) + h02, X = (h10 v + h11 u) + h12, D = (h20 v + h21 u) + h22 at the pixel
@@ -571,20 +572,26 @@ class CiaoSR(BasicRestorer):
         shape; NaN or infinite: the pixel holds `fill`).  `footprint` = (f_y, f_x), the LR extent of an output pixel along each LR axis, is
         what the model sees as the cell -- ONE per warp: default for a homography its Jacobian at the output centre
         (`scene.warp_footprint`), required for a map (`scene.map_footprint` offers one, at the cost of a copy).  Under strong perspective
-        the local scale varies over the output: cut it into several warps.  Everything else is `render_view`'s: tiles (with
+        the local scale varies over the output: `footprint='per-pixel'` gives every output pixel its own footprint -- the norms of the
+        rows of the homography's Jacobian at the pixel, or central differences of the map -- and a device tensor [Hv, Wv, 2] of
+        (g_y, g_x) gives the caller's own; both are clamped to `footprint_range` = (lo, hi), default (1 / max_scale, 1.0) with the
+        encode's max_scale (else `test_cfg.scale`), the warp plans for max_scale = 1 / lo, a pixel whose footprint is NaN or undefined
+        holds `fill`, and the head is asked with chunk = 1 so that the shift radius of a query comes from its own cell (scene.py,
+        "per-pixel warps": the definition).  A per-pixel warp whose footprints are constant is bitwise the single-footprint warp of
+        that constant.  Everything else is `render_view`'s: tiles (with
         `test_cfg.tile`: `tile_any_scale`), row-major blend, `fill`, `as_u8` / `as_u16`, grey and RGBA records, one device-to-host copy per
         batch item.  A warp that is affine -- last row (0, 0, 1), or a map of a view's points with its footprint -- is bitwise
         `render_view` of that matrix.  `test_cfg.view_blocks` is ignored.  ValueError before any device work for what
         `scene.check_warp` lists, and for a self-ensemble encode."""
         scene_render.check_quant(enc, as_u8, as_u16)
         scene_render.refuse_ensemble(enc, 'render_warp')
-        target = scene.Warp(homography, map, size, footprint, fill)
+        target = scene.Warp(homography, map, size, footprint, fill, footprint_range)
         return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [target])[0], as_u8, as_u16)
 
     @torch.no_grad()
     def render_many(self, enc, targets, as_u8=False, as_u16=False):
         """Every target of the list -- scene.Grid(size, scale, window): `render`'s arguments, scene.View(matrix, size, fill):
-        `render_view`'s, scene.Warp(homography, map, size, footprint, fill): `render_warp`'s (each warp is counted by its own launch
+        `render_view`'s, scene.Warp(homography, map, size, footprint, fill, footprint_range): `render_warp`'s (each warp is counted by its own launch
         pair; its counts ride in the views' one copy) -- from ONE walk over the tile scenes: -> list of [B, 3, h, w], outs[k] bitwise what the single call returns on an
         encode with the same max_scale under the same test_cfg (with `as_u8` the same uint8 image).  Per batch item the union of the
         tiles the targets touch is walked in row-major order; each tile's scene is taken from the cache once and every target that

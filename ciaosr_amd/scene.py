@@ -227,7 +227,7 @@ def check_view(matrix, size, fill, h, w, tile=None, overlap=None, any_scale=Fals
 # -- a view's position, bit for bit, when the last row is (0, 0, 1).  Or a map: a device tensor [Hv, Wv, 2] of (y_lr, x_lr).  After the
 # position everything is the view's rule: membership, frame coordinate, tile plan, blend order, fill.  The footprint is what reaches the
 # model (the cell, and through it the shift radius): ONE per warp, so a warp whose local scale varies strongly over the output -- strong
-# perspective -- should be cut into several warps by the caller.
+# perspective -- should be cut into several warps by the caller, or rendered as a per-pixel warp (below).
 def homography_of_view(matrix):
     """The nine numbers of an affine view: its two rows and (0, 0, 1).  The warp of it is `render_view` of the matrix, bit for bit."""
     m = [float(v) for v in matrix]
@@ -328,13 +328,110 @@ def map_footprint(map):
     return tuple(out)
 
 
-def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=None, any_scale=False):
+# ---- per-pixel warps (include/ciaosr_hip.h, "per-pixel warps") -----------------------------------------------------------------------
+# A per-pixel warp is a warp whose footprint is a function of the output pixel.  Positions, membership, frame coordinates, tile plan,
+# blend, `fill`, `as_u8` / `as_u16` / grey / RGBA, and the one device-to-host copy are the existing warp's, unchanged.  The raw footprint
+# (g_y, g_x) of output pixel (i, j) is computed in fp64, every operation rounded on its own, from one of three sources: the Jacobian of
+# the homography (`footprint='per-pixel'`): g_y = sqrt(a a + b b), a = (h00 - y_lr h20) / D, b = (h01 - y_lr h21) / D, g_x likewise with
+# h10, h11, x_lr; differences of the map (`footprint='per-pixel'`): central where both neighbours lie in the grid and are finite, else
+# one-sided, else the pixel has no footprint; or a device tensor [Hv, Wv, 2] of (g_y, g_x).  Clamp: f = min(max(g, lo), hi) per axis with
+# `footprint_range=(lo, hi)`, default hi = 1.0 (no minification: the model was never trained below x1) and lo = 1 / M, M = the encode's
+# max_scale when it is set, else what `encode` would default it to (`test_cfg`'s scale).  A NaN component, or no footprint, makes the pixel
+# a non-member: it holds `fill` and A = 0, exactly as a NaN position does; +inf clamps to hi.  The cell of a member in a th x tw frame is
+# fp32(f_y 2 / th), fp32(f_x 2 / tw); the warp's max_scale is 1 / lo; the head is queried with chunk = 1, so the shift radius of a query
+# comes from its own cell.  A per-pixel warp whose footprints happen to be constant is the single-footprint warp of that constant.
+FP_JACOBIAN, FP_DIFFERENCES, FP_TENSOR = 1, 2, 3
+
+
+class PerPixel:
+    """The resolved footprint of a per-pixel warp: `mode` (FP_JACOBIAN, FP_DIFFERENCES or FP_TENSOR), `range` = (lo, hi) and, in mode
+    FP_TENSOR, the caller's `tensor` [Hv, Wv, 2]."""
+    __slots__ = ('mode', 'range', 'tensor')
+
+    def __init__(self, mode, range, tensor=None):
+        self.mode, self.range, self.tensor = mode, range, tensor
+
+    def __repr__(self):
+        return f'PerPixel(mode={self.mode}, range={self.range!r})'
+
+
+def resolve_range(range=None, max_scale=None):
+    """(lo, hi) of a per-pixel warp: `range`, two finite doubles 0 < lo <= hi, default (1 / max_scale, 1.0)."""
+    if range is None:
+        if max_scale is None or not (math.isfinite(float(max_scale)) and float(max_scale) >= 1.0):
+            raise ValueError(f'a per-pixel footprint needs footprint_range=(lo, hi): the default lo = 1 / max_scale needs the encode\'s '
+                             f'max_scale or test_cfg.scale (>= 1), got {max_scale!r}')
+        return (1.0 / float(max_scale), 1.0)
+    try:
+        rg = tuple(float(v) for v in range)
+    except (TypeError, ValueError):
+        rg = ()
+    if len(rg) != 2 or not all(math.isfinite(v) for v in rg) or not 0.0 < rg[0] <= rg[1]:
+        raise ValueError(f'footprint_range is (lo, hi), two finite numbers with 0 < lo <= hi, got {range!r}')
+    return rg
+
+
+def _per_pixel(footprint, range_, max_scale, has_map, hv, wv, frame):
+    """`check_warp`'s per-pixel branch: -> PerPixel.  `footprint`: 'per-pixel' or a tensor."""
+    if isinstance(footprint, str):
+        if footprint != 'per-pixel':
+            raise ValueError(f"footprint is (f_y, f_x), 'per-pixel' or a device tensor [Hv, Wv, 2], got {footprint!r}")
+        if has_map and (hv < 2 or wv < 2):
+            raise ValueError(f'a per-pixel footprint from the differences of a map needs two pixels along each grid axis, got {hv} x {wv}')
+        mode, tensor = (FP_DIFFERENCES if has_map else FP_JACOBIAN), None
+    else:
+        shape = tuple(footprint.shape)
+        if shape != (hv, wv, 2) or str(footprint.dtype) not in ('torch.float64', 'torch.float32'):
+            raise ValueError(f'a footprint tensor is a float64 (or float32) tensor [Hv, Wv, 2] = [{hv}, {wv}, 2] of (g_y, g_x), got '
+                             f'{footprint.dtype} {shape}')
+        if not footprint.is_cuda:
+            from ._lib import CiaoSRHipError
+            raise CiaoSRHipError('a footprint tensor lives on the MI355X: got a CPU tensor (no CPU fallback; move it to cuda)')
+        mode, tensor = FP_TENSOR, footprint
+    lo, hi = resolve_range(range_, max_scale)
+    cell = (_f32(hi * 2.0 / frame[2]), _f32(hi * 2.0 / frame[3]))
+    if max(cell) >= 1.0:
+        raise ValueError(f'warp cell {cell} >= 1 at the upper end hi = {hi} of footprint_range in a {frame[2]} x {frame[3]} frame: an '
+                         f'output pixel may span less than half the frame (the reference divides by 1 - cell)')
+    return PerPixel(mode, (lo, hi), tensor)
+
+
+def warp_footprints(homography, size, footprint_range):
+    """The clamped per-pixel footprints of a homography on an Hv x Wv (`size`) output, [Hv, Wv, 2] float64 on the host: the definition
+    above restated in plain Python doubles, one rounded operation at a time -- what `hip_ops.warp_footprints` computes on the device,
+    bit for bit.  For small grids and for checks: NOT a fast path (a Python loop over the pixels)."""
+    import torch
+    h = _h9(homography)
+    hv, wv = int(size[0]), int(size[1])
+    lo, hi = resolve_range(footprint_range)
+    out = []
+    for i in range(hv):
+        for j in range(wv):
+            v, u = i + 0.5, j + 0.5
+            d = (h[6] * v + h[7] * u) + h[8]
+            y, x = ((h[0] * v + h[1] * u) + h[2]) / d, ((h[3] * v + h[4] * u) + h[5]) / d
+            for c, p in ((0, y), (3, x)):
+                a, b = (h[c] - p * h[6]) / d, (h[c + 1] - p * h[7]) / d
+                g = math.sqrt(a * a + b * b)
+                out.append(g if g != g else min(max(g, lo), hi))
+    return torch.tensor(out, dtype=torch.float64).view(hv, wv, 2)
+
+
+def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=None, any_scale=False, footprint_range=None,
+               max_scale=None):
     """The arguments of a warp render, checked in `CiaoSR.render_warp`'s order, all on the host: -> (h9 or None, map or None, (hv, wv),
     (f_y, f_x), fill3, frames) with frames = `plan_view`'s list.  ValueError for: not exactly one point source; an empty grid; tiles
     without `tile_any_scale`; a non-finite homography entry; a denominator <= 0 at a corner (0, 0), (Hv, 0), (0, Wv), (Hv, Wv) of the grid
     (D is affine in (v, u): positive corners mean positive everywhere -- the horizon must not cross the output); a map that is not a
     float64 / float32 tensor [Hv, Wv, 2]; a map without a footprint; a footprint that is not finite and positive; a cell >= 1; a fill
-    outside [0, 1].  A map on the host is a CiaoSRHipError: there is no CPU fallback."""
+    outside [0, 1].  A map on the host is a CiaoSRHipError: there is no CPU fallback.
+    `footprint` = 'per-pixel' or a device tensor [Hv, Wv, 2] makes a per-pixel warp: the fourth result is then a `PerPixel` record with
+    `footprint_range` resolved (default (1 / `max_scale`, 1.0), `max_scale` = the encode's or `test_cfg.scale`).  ValueError as well for:
+    an unknown string; a tensor of the wrong shape or dtype; `footprint_range` without a per-pixel footprint; a range that is not
+    0 < lo <= hi and finite; an upper end whose cell is >= 1; differences on a grid axis of length 1.  A host tensor is a CiaoSRHipError."""
+    per_pixel = isinstance(footprint, str) or (hasattr(footprint, 'shape') and hasattr(footprint, 'dtype') and tuple(footprint.shape) != (2,))
+    if footprint_range is not None and not per_pixel:
+        raise ValueError("footprint_range=(lo, hi) clamps a per-pixel footprint: give footprint='per-pixel' or a footprint tensor with it")
     if (homography is None) == (map is None):
         raise ValueError('a warp has exactly one point source: give homography=(nine numbers) or map=(device tensor [Hv, Wv, 2])')
     if map is not None:
@@ -368,8 +465,11 @@ def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=
                                  f'the {hv} x {wv} output')
         if footprint is None:
             footprint = warp_footprint(h9, (hv, wv))
-    fp = _footprint(footprint)
-    warp_cell(fp, frames[0][2], frames[0][3])                     # ValueError: a cell >= 1
+    if per_pixel:
+        fp = _per_pixel(footprint, footprint_range, max_scale, map is not None, hv, wv, frames[0])
+    else:
+        fp = _footprint(footprint)
+        warp_cell(fp, frames[0][2], frames[0][3])                 # ValueError: a cell >= 1
     fill = tuple(float(v) for v in fill) if hasattr(fill, '__len__') else (float(fill),) * 3
     if len(fill) != 3 or not all(0.0 <= v <= 1.0 for v in fill):
         raise ValueError(f'fill is one number or three in [0, 1], got {fill}')
@@ -410,18 +510,23 @@ class View:
 
 class Warp:
     """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render_warp`."""
-    __slots__ = ('homography', 'map', 'size', 'footprint', 'fill')
+    __slots__ = ('homography', 'map', 'size', 'footprint', 'fill', 'footprint_range')
 
-    def __init__(self, homography=None, map=None, size=None, footprint=None, fill=0.0):
+    def __init__(self, homography=None, map=None, size=None, footprint=None, fill=0.0, footprint_range=None):
         self.homography, self.map, self.size, self.footprint, self.fill = homography, map, size, footprint, fill
+        self.footprint_range = footprint_range
 
-    def resolve(self, h, w, tile=None, overlap=None, any_scale=False):
-        """`check_warp` of the record: (h9 or None, map or None, (hv, wv), footprint, fill3, frames), with `render_warp`'s errors."""
-        return check_warp(self.homography, self.map, self.size, self.footprint, self.fill, h, w, tile, overlap, any_scale)
+    def resolve(self, h, w, tile=None, overlap=None, any_scale=False, max_scale=None):
+        """`check_warp` of the record: (h9 or None, map or None, (hv, wv), footprint, fill3, frames), with `render_warp`'s errors; the
+        footprint is (f_y, f_x) or, for a per-pixel warp, a `PerPixel` record (`max_scale`: the default of its range)."""
+        return check_warp(self.homography, self.map, self.size, self.footprint, self.fill, h, w, tile, overlap, any_scale,
+                          self.footprint_range, max_scale)
 
     def __repr__(self):
         source = f'homography={self.homography!r}' if self.map is None else f'map=<{tuple(getattr(self.map, "shape", ()))}>'
-        return f'Warp({source}, size={self.size!r}, footprint={self.footprint!r}, fill={self.fill!r})'
+        fp = self.footprint if not hasattr(self.footprint, 'shape') else f'<{tuple(self.footprint.shape)}>'
+        rg = '' if self.footprint_range is None else f', footprint_range={self.footprint_range!r}'
+        return f'Warp({source}, size={self.size!r}, footprint={fp!r}{rg}, fill={self.fill!r})'
 
 
 def plan_union(touched):

@@ -270,13 +270,21 @@ class ViewTarget:
 class WarpTarget(ViewTarget):
     """A resolved scene.Warp: its point source -- the homography `h` (nine numbers) or the device map `map` [hv, wv, 2] float64, the other
     None --, the `footprint`, output `size`, `fill` and the frames.  Everything after the LR position is the view's: `touched`, `alloc` and
-    `finish` are ViewTarget's own.  `test_cfg.view_blocks` is ignored: a cut warp's member lists stay in index order."""
+    `finish` are ViewTarget's own.  `test_cfg.view_blocks` is ignored: a cut warp's member lists stay in index order.  A per-pixel warp
+    (`footprint` a `scene.PerPixel`, kept as `pp`) runs the per-pixel count / select / coordinate entries and queries the head with
+    chunk = 1: the shift radius of a query comes from its own cell."""
 
     def __init__(self, cfg, h, map_, size, footprint, fill, frames):
         self.h, self.footprint, self.size, self.fill, self.frames = h, footprint, size, fill, frames
         # a float32 map is widened exactly; the kernels read one aligned 16-byte (y_lr, x_lr) pair per query
         self.map = None if map_ is None else map_.detach().to(torch.float64).contiguous()
-        self.max_scale = sc.warp_max_scale(footprint)
+        self.pp = None
+        if isinstance(footprint, sc.PerPixel):
+            tensor = None if footprint.tensor is None else footprint.tensor.detach().to(torch.float64).contiguous()
+            self.pp = sc.PerPixel(footprint.mode, footprint.range, tensor)
+            self.max_scale = 1.0 / footprint.range[0]
+        else:
+            self.max_scale = sc.warp_max_scale(footprint)
         self.tiled = bool(cfg.get('tile', None))
         self.counts = self.n_blocks = self.ws = None
 
@@ -286,12 +294,23 @@ class WarpTarget(ViewTarget):
 
     def launch_count(self, enc, ws=None):
         """The count launch pair without the copy: -> the counts on the device (`render_many` copies every target's at once)."""
-        counts, self.ws = hip_ops.warp_count(self.h, self.map, self.footprint, *self.size, _view_tiles(enc, self.frames), ws)
+        if self.pp is not None:
+            counts, self.ws = hip_ops.warp_pp_count(self.h, self.map, self.pp, *self.size, _view_tiles(enc, self.frames), ws)
+        else:
+            counts, self.ws = hip_ops.warp_count(self.h, self.map, self.footprint, *self.size, _view_tiles(enc, self.frames), ws)
         return counts
 
     def query(self, gen, k, tile_scene, acc):
         """Frame k's members from its scene, blended into `acc`."""
         (hv, wv), frame, n = self.size, self.frames[k], self.counts[k]
+        if self.pp is not None:
+            if n == hv * wv:                                            # every query is a member, so every query has a footprint
+                q_index = None
+                coord, cell = hip_ops.make_coord_cell_warp_pp(self.h, self.map, self.pp, hv, wv, frame, tile_scene.x.device)
+            else:
+                q_index, coord, cell = hip_ops.warp_pp_select(self.h, self.map, self.pp, hv, wv, frame, k, len(self.frames), self.ws, n)
+            hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell, chunk=1)[0])
+            return
         if n == hv * wv:                                                # the frame owns every query: a grid, known to the head as one
             q_index = None
             coord, cell = hip_ops.make_coord_cell_warp(self.h, self.map, self.footprint, hv, wv, frame, tile_scene.x.device)
@@ -368,7 +387,8 @@ def resolve(r, enc, targets):
         elif isinstance(tg, sc.View):
             out.append(ViewTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale)))
         elif isinstance(tg, sc.Warp):
-            out.append(WarpTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale)))
+            default = enc.max_scale if enc.max_scale is not None else cfg.get('scale', None)    # what `encode` would default it to
+            out.append(WarpTarget(cfg, *tg.resolve(h, w, tile, overlap, any_scale, max_scale=default)))
         else:
             raise TypeError(f'a target is a scene.Grid, a scene.View or a scene.Warp, got {type(tg).__name__}')
     if enc.max_scale is None:

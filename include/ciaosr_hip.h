@@ -746,6 +746,39 @@ int ciaosr_warp_select_f32(const double* h9 /*host [9] or NULL*/, const double* 
                            int Hv, int Wv, const int* tile /*host [4]*/, int tile_index, int n_tiles, const void* workspace,
                            size_t workspace_bytes, int n, int* q_index, float* coord, float* cell, void* stream);
 
+/* ---- per-pixel warps: a footprint per output pixel ---------------------------------------------------------------------------------------
+ * A per-pixel warp is a warp whose footprint is a function of the output pixel.  Positions, membership, frame coordinates, tile plan,
+ * blend, fill, the quantised / grey / RGBA outputs and the one device-to-host copy are the existing warp's, unchanged.
+ * RAW FOOTPRINT (g_y, g_x) of output pixel (i, j), in fp64, every operation rounded on its own, no FMA, from one of three sources (mode):
+ *   1  Jacobian (h9 only).  v = i + 0.5, u = j + 0.5, and D, y_lr, x_lr the warp's:  g_y = sqrt(a a + b b) with a = (h00 - y_lr h20) / D,
+ *      b = (h01 - y_lr h21) / D;  g_x the same with h10, h11, x_lr.  sqrt of the rounded sum, not hypot.
+ *   2  Differences (map only; Hv > 1 and Wv > 1).  Per map component c and grid axis the derivative is (p[+1] - p[-1]) * 0.5 where both
+ *      neighbours lie in the grid and are finite, else the one-sided difference with the one neighbour that is in the grid and finite
+ *      (p[+1] - p[0] or p[0] - p[-1]), else the pixel has no footprint.  g_y = sqrt(dv_y dv_y + du_y du_y), likewise g_x.  The four
+ *      neighbours are 16-byte loads like the centre's.
+ *   3  Tensor (either point source): tensor (device, 16-byte aligned, [Hv Wv][2] doubles) = (g_y, g_x), one 16-byte load per query.
+ * CLAMP  range = {lo, hi} (host doubles, finite, 0 < lo <= hi): f = min(max(g, lo), hi) per axis; +inf clamps to hi.  A raw footprint with
+ * a NaN component, or a pixel without footprint, makes the pixel a non-member of every tile, exactly as a NaN position does.
+ * CELL of a member in a th x tw frame: fp32(f_y 2 / th), fp32(f_x 2 / tw), written per member by select and coord_cell (a NaN cell in
+ * coord_cell where the pixel has no footprint).  The head is queried with chunk = 1 for such a warp: the shift radius of a query comes
+ * from its own cell.  A per-pixel warp whose footprints happen to be constant is the single-footprint warp of that constant, bit for bit.
+ * ciaosr_ppwarp_footprints_f64 writes the clamped footprints of the whole grid, out (device, 16-byte aligned) [Hv Wv][2] doubles, NaN
+ * where the pixel has none.  Workspace and layout are ciaosr_warp_workspace_bytes / ciaosr_warp_count_i32's.  CIAOSR_ERR_BAD_ARG before
+ * any launch for: what the warp entries refuse, a mode that does not fit the point source, a null or misaligned tensor in mode 3,
+ * lo <= 0, lo > hi, a non-finite range, a grid axis of 1 in mode 2. */
+int ciaosr_ppwarp_coord_cell_f32(float* coord, float* cell, const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/,
+                                 int mode, const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int Hv, int Wv,
+                                 const int* frame /*host [4]*/, void* stream);
+int ciaosr_ppwarp_count_i32(const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, int mode,
+                            const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int Hv, int Wv, const int* tiles,
+                            int n_tiles, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+int ciaosr_ppwarp_select_f32(const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, int mode,
+                             const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int Hv, int Wv,
+                             const int* tile /*host [4]*/, int tile_index, int n_tiles, const void* workspace, size_t workspace_bytes, int n,
+                             int* q_index, float* coord, float* cell, void* stream);
+int ciaosr_ppwarp_footprints_f64(double* out, const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, int mode,
+                                 const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int Hv, int Wv, void* stream);
+
 /* ---- self-ensemble: the eight flips and transposes of an image, and the mean through their inverses (an extension, absent from the
  * reference) ---------------------------------------------------------------------------------------------------------------------------
  * k in 0..7.  T_k acts on the last two axes of [planes][H][W]: k & 1: flip the columns; then k & 2: flip the rows; then k & 4: transpose

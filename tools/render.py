@@ -20,7 +20,9 @@ Every `--homography` (repeatable; alone or alongside --scale and --view) is a Ci
 (ciaosr_amd.scene: keystone and perspective correction; `homography_from_points` makes one from four point pairs), written to DIR/<image
 name>_warp<k>.png in command-line order.  `--size` follows the rule of `--view`: one per --view and --homography, the views first, or a
 single one for all of them.  D must be positive on the whole output; the model sees ONE footprint per warp, the Jacobian at the output
-centre, so strong perspective is better cut into several warps.  Not with --self-ensemble or --tiff (an argparse error).
+centre, unless `--footprint per-pixel` gives every output pixel of every --homography its own (the Jacobian at the pixel, clamped to
+`--footprint-range LO HI`, default 1 / max scale and 1.0; the file names do not change): the choice under strong perspective.
+`--footprint-range` without `--footprint per-pixel` is an argparse error.  Not with --self-ensemble or --tiff (an argparse error).
 `--gpu-png` sets `test_cfg.gpu_png`: every output is rendered as a uint8 image on the device and PNG-encoded there (ciaosr_amd/png_hip.py);
 the files decode to the pixels of the default run.
 `--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
@@ -97,6 +99,10 @@ def parse_args(argv=None):
                    help='one output per homography: output pixel centres (v, u) to LR positions (y, x), y first (repeatable)')
     p.add_argument('--size', type=int, nargs=2, action='append', default=[], metavar=('H', 'W'),
                    help='output size of each --view and --homography')
+    p.add_argument('--footprint', choices=['per-pixel'], default=None,
+                   help='every --homography gives each output pixel its own footprint, its Jacobian there (default: one per warp)')
+    p.add_argument('--footprint-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                   help='with --footprint per-pixel: clamp the footprints to [LO, HI] LR pixels (default: 1 / max scale, 1.0)')
     p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
     p.add_argument('--view-blocks', action='store_true',
@@ -143,6 +149,12 @@ def parse_args(argv=None):
         p.error('give one --size H W per --view and --homography (the views first), or a single one for all of them')
     if args.size and not args.view and not args.homography:
         p.error('--size belongs to --view')
+    if args.footprint and not args.homography:
+        p.error('--footprint per-pixel applies to --homography outputs')
+    if args.footprint_range and not args.footprint:
+        p.error('--footprint-range clamps per-pixel footprints: give --footprint per-pixel with it')
+    if args.footprint_range and not 0.0 < args.footprint_range[0] <= args.footprint_range[1] < float('inf'):
+        p.error('--footprint-range takes 0 < LO <= HI')
     if args.jpeg is not None and not 1 <= args.jpeg <= 100:
         p.error('--jpeg takes a quality in 1..100')
     if args.alpha and args.jpeg is not None:
@@ -238,6 +250,8 @@ def main(argv=None):
     if args.homography and not args.scale:                                           # without --homography `wanted` is what it was
         from ciaosr_amd.scene import warp_footprint, warp_max_scale
         wanted = wanted + [warp_max_scale(warp_footprint(h, size)) for h, size in zip(args.homography, sizes[len(args.view):])]
+        if args.footprint_range:                                                     # a per-pixel warp plans for 1 / lo
+            wanted = wanted + [1.0 / args.footprint_range[0]]
     if args.dzi is not None:
         wanted = wanted + [args.dzi]
     if alpha:
@@ -284,7 +298,8 @@ def main(argv=None):
         targets.append(View(view_matrix((cy, cx), zoom, angle, size), size))
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     for k, h in enumerate(args.homography):
-        targets.append(Warp(homography=h, size=sizes[len(args.view) + k]))
+        per_pixel = dict(footprint=args.footprint, footprint_range=args.footprint_range) if args.footprint else {}
+        targets.append(Warp(homography=h, size=sizes[len(args.view) + k], **per_pixel))
         paths.append(os.path.join(args.out, f'{name}_warp{k}{form["ext"]}'))
     gpu_png = model.gpu_png()
     as_u8 = (gpu_png or form['fmt'] == 'jpg' or alpha or args.grey) and not args.depth16

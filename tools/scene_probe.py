@@ -20,6 +20,8 @@ list the leg selects: 1 = the chained 16-bit kernel gave the launch up to the ga
 
 `--legs warp` (profiles/warp_render.txt, with `--out`): the affine-degenerate homography, the same points as a map, and `render_view` of
 that matrix, alternating, by the protocol of the view legs (`warp_legs`).
+`--legs warp-pp` (profiles/warp_pp.txt, with `--out`): a projective homography with its centre footprint, with a footprint per output
+pixel, and as a map with differences, alternating, by the same protocol (`warp_pp_legs`).
 
 `--legs many` (profiles/render_many.txt, with `--out`) is the tiled image of bench.py -- LR 1356 x 2040, tile 192 / overlap 32,
 `tile_any_scale`: 9 x 13 = 117 tiles -- rendered at x2, x3.3 and x4 (full grids) from one encode, per precision and for two scene caches
@@ -45,7 +47,7 @@ ap.add_argument('--sizes', default='192,48')
 ap.add_argument('--precisions', default='fp32,f16')
 ap.add_argument('--scales', default='4,2,3.3')
 ap.add_argument('--reps', type=int, default=5)
-ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many', 'warp'))
+ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many', 'warp', 'warp-pp'))
 ap.add_argument('--view-size', type=int, default=768)
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help='tree whose package and library run')
 ap.add_argument('--parent-root', default=None, help='--legs many: a built checkout of the parent commit for leg (a)')
@@ -229,6 +231,67 @@ def warp_legs():
             f.write('\n'.join(report) + '\n')
 
 
+def warp_pp_legs():
+    """`--legs warp-pp`: the warp legs' protocol (the C3 tile, whole-image test_cfg, scene planned for x4, `--view-size` squared, 2
+    warm-up + `--reps` timed rounds, legs alternating in one process, one profiled round per leg) on a projective homography -- zoom
+    x3 turned by 30 degrees with the last row of the test warps scaled to the output, so that most footprints lie above the default
+    lower clamp 1 / 4 of the x4 plan -- with its centre footprint, with
+    `footprint='per-pixel'`, and as a map with differences.  The comparison is against the single-footprint leg of the same run.  With
+    `--out` the report is also written to that file (profiles/warp_pp.txt)."""
+    from ciaosr_amd.scene import FP_JACOBIAN, PerPixel, view_matrix, warp_footprint
+    size, n = int(args.sizes.split(',')[0]), args.view_size
+    report = [f'tools/scene_probe.py --legs warp-pp --reps {args.reps}: library version {_lib.load().ciaosr_version()}, '
+              f'{torch.cuda.get_device_name(0)}; {size}x{size} LR, {n} x {n} output, three legs alternating in one process (2 warm-up '
+              f'rounds, {args.reps} timed rounds)']
+    lq = synthetic_pair(size, size, 4)[0].to(dev)
+    coords = ('view_coord_cell', 'warp_coord_cell', 'warp_pp_coord_cell')
+    groups = (('warp kernels', lambda k: k.startswith(('view_', 'warp_')) and k not in coords),
+              ('coordinates', lambda k: k in coords),
+              ('head query', lambda k: not k.startswith(('view_', 'warp_', 'make_coord_cell')) and k != 'denorm_clamp'))
+    h = (*view_matrix((size / 2, size / 2), 3.0, 30, (n, n)), 0.0025 * 61 / n, -0.002 * 83 / n, 1.0)
+    v = (torch.arange(n, dtype=torch.float64, device=dev) + 0.5).view(n, 1)
+    u = (torch.arange(n, dtype=torch.float64, device=dev) + 0.5).view(1, n)
+    d = (h[6] * v + h[7] * u) + h[8]
+    points = torch.stack([((h[0] * v + h[1] * u) + h[2]) / d, ((h[3] * v + h[4] * u) + h[5]) / d], -1).contiguous()
+    raw = hip_ops.warp_footprints(h, None, PerPixel(FP_JACOBIAN, (1e-6, 1e6)), n, n, dev)
+    fp = warp_footprint(h, (n, n))
+    report.append(f'  footprints: centre {fp[0]:.4f} x {fp[1]:.4f}, per pixel {raw.min().item():.4f} .. {raw.max().item():.4f}; the default range '
+                  f'(0.25, 1.0) clamps {(raw < 0.25).any(-1).float().mean().item():.1%} of the pixels at lo')
+    for precision in args.precisions.split(','):
+        model.test_cfg = dict(scale=4, precision=precision)
+        enc = model.encode(lq)
+        calls = {'centre': lambda: model.render_warp(enc, homography=h, size=(n, n)),
+                 'per-pixel': lambda: model.render_warp(enc, homography=h, size=(n, n), footprint='per-pixel'),
+                 'map, differences': lambda: model.render_warp(enc, map=points, footprint='per-pixel')}
+        outs = {k: fn() for k, fn in calls.items()}
+        report.append(f'  {precision}: max |per-pixel - centre| = {(outs["per-pixel"] - outs["centre"]).abs().max().item():.3e}, max |map - '
+                      f'per-pixel| = {(outs["map, differences"] - outs["per-pixel"]).abs().max().item():.3e}; '
+                      f'{(outs["centre"].sum(1) == 0).float().mean().item():.1%} of the pixels outside')
+        del outs
+        for _ in range(2):
+            for fn in calls.values():
+                fn()
+        times = {k: [] for k in calls}
+        for _ in range(args.reps):
+            for k, fn in calls.items():
+                times[k].append(timed(fn)[0])
+        for k, fn in calls.items():
+            with hip_ops.profile():
+                fn()
+            prof = hip_ops.profile.results()
+            t = times[k]
+            parts = ', '.join(f'{name} {sum(r["total_ms"] for kk, r in prof.items() if pick(kk)):8.3f} ms '
+                              f'({sum(r["launches"] for kk, r in prof.items() if pick(kk))} launches)' for name, pick in groups)
+            report.append(f'    {k:16s} wall mean {sum(t) / len(t):8.3f} ms  min {min(t):8.3f}  max {max(t):8.3f} | device: {parts}')
+        del enc, calls
+        hip_ops.release_workspaces()
+        torch.cuda.empty_cache()
+    print('\n'.join(report))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(report) + '\n')
+
+
 MANY_LR, MANY_SCALES = (1356, 2040), (2.0, 3.3, 4.0)
 
 
@@ -394,6 +457,8 @@ if args.legs == 'view':
     view_legs()
 if args.legs == 'warp':
     warp_legs()
+if args.legs == 'warp-pp':
+    warp_pp_legs()
 if args.legs == 'many':
     many_worker() if args.worker else many_legs()
 for size in (int(v) for v in args.sizes.split(',') if args.legs == 'scene'):
