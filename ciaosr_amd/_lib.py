@@ -213,6 +213,12 @@ SIGNATURES = {
     'ciaosr_ppwarp_select_f32': (_I, [C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I,
                                       _P, _P, _P, _P]),
     'ciaosr_ppwarp_footprints_f64': (_I, [_P, C.POINTER(C.c_double), _P, _I, C.POINTER(C.c_double), _P, _I, _I, _P]),
+    # area-sampled warps (version 372): a homography, (mode, range [2], tensor), max_samples; the table lives in the workspace
+    'ciaosr_areawarp_workspace_bytes': (_S, [_I, _I, _I, _I]),
+    'ciaosr_areawarp_count_i32': (_I, [C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _P, _I, _I, _I, _P, _I, _P, _P, _S, _P]),
+    'ciaosr_areawarp_select_f32': (_I, [C.POINTER(C.c_double), _I, _I, _I, C.POINTER(_I), _I, _I, _P, _S, _I, _I, _P, _P, _P, _P]),
+    'ciaosr_areawarp_resolve_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _S, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P]),
+    'ciaosr_areawarp_table_i32': (_I, [_P, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _P, _I, _I, _I, _I, _P, _S, _P]),
     'ciaosr_dihedral_f32': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'ciaosr_dihedral_accum_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'ciaosr_resample_u8_workspace_bytes': (_S, [_I, _I, _I, _I]),

@@ -1,8 +1,10 @@
 // What view_ops.hip (affine views) and warp_ops.hip (homographies and coordinate maps) share: everything that follows the LR position of a
 // query -- the frame a query is sorted into, its membership test and its coordinate in the frame, the geometry of the count / select
-// workgroups, the scan of a tile's per-workgroup counts -- and the host checks of a frame.  Where the position comes from is each file's own.
+// workgroups, the scan of a tile's per-workgroup counts -- the host checks of a frame, and the fill value both files' finishing kernels
+// write where no tile claimed a query.  Where the position comes from is each file's own.
 #pragma once
 #include <climits>
+#include <cmath>
 
 #include "common.h"
 
@@ -55,5 +57,31 @@ static inline ViewFrame frame_of(const int* f) {
     return ViewFrame{(double)f[0], (double)f[1], (double)f[0] + (double)f[2], (double)f[1] + (double)f[3], (double)f[2], (double)f[3]};
 }
 static inline int view_blocks(long Q) { return (int)((Q + kViewChunk - 1) / kViewChunk); }
+
+struct Fill3 { float v[3]; };
+
+// The value v with clamp(v * std + mean, 0, 1) == fill in ciaosr_denorm_clamp_f32's arithmetic (two rounded fp32 operations), searched
+// among the neighbours of (fill - mean) / std; where no fp32 value maps onto fill, the one that comes nearest
+static inline float fill_preimage(float fill, float mean, float std_) {
+#pragma clang fp contract(off)
+    float best = (float)(((double)fill - (double)mean) / (double)std_);
+    float lo = best, hi = best;
+    double best_err = HUGE_VAL;
+    float pick = best;
+    for (int k = 0; k <= 8; ++k) {
+        const float cand[2] = {lo, hi};
+        for (int s = 0; s < 2; ++s) {
+            volatile float prod = cand[s] * std_;
+            volatile float sum = prod + mean;
+            const float got = fminf(fmaxf(sum, 0.f), 1.f);
+            const double err = std::fabs((double)got - (double)fill);
+            if (err < best_err) { best_err = err; pick = cand[s]; }
+        }
+        if (best_err == 0.0) break;
+        lo = std::nextafterf(lo, -HUGE_VALF);
+        hi = std::nextafterf(hi, HUGE_VALF);
+    }
+    return pick;
+}
 
 }  // namespace ciaosr

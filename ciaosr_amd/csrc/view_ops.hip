@@ -283,7 +283,6 @@ __global__ void view_blend_kernel(float* __restrict__ E, float* __restrict__ Wt,
     }
 }
 
-struct Fill3 { float v[3]; };
 __global__ void view_finalize_kernel(const float* __restrict__ E, const float* __restrict__ Wt, float* __restrict__ out, long Q, Fill3 fill) {
     const long n = 3 * Q;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -309,30 +308,6 @@ static inline float2 view_cell(const double* m, const int* f) {
 static inline int view_block_wgs(int Hv, int Wv) {
     const long nb = (((long)Wv + 3) >> 2) * (((long)Hv + 1) >> 1);
     return (int)((nb + kViewThreads - 1) / kViewThreads);
-}
-
-// The value v with clamp(v * std + mean, 0, 1) == fill in ciaosr_denorm_clamp_f32's arithmetic (two rounded fp32 operations), searched
-// among the neighbours of (fill - mean) / std; where no fp32 value maps onto fill, the one that comes nearest
-static float fill_preimage(float fill, float mean, float std_) {
-#pragma clang fp contract(off)
-    float best = (float)(((double)fill - (double)mean) / (double)std_);
-    float lo = best, hi = best;
-    double best_err = HUGE_VAL;
-    float pick = best;
-    for (int k = 0; k <= 8; ++k) {
-        const float cand[2] = {lo, hi};
-        for (int s = 0; s < 2; ++s) {
-            volatile float prod = cand[s] * std_;
-            volatile float sum = prod + mean;
-            const float got = fminf(fmaxf(sum, 0.f), 1.f);
-            const double err = std::fabs((double)got - (double)fill);
-            if (err < best_err) { best_err = err; pick = cand[s]; }
-        }
-        if (best_err == 0.0) break;
-        lo = std::nextafterf(lo, -HUGE_VALF);
-        hi = std::nextafterf(hi, HUGE_VALF);
-    }
-    return pick;
 }
 
 }  // namespace ciaosr

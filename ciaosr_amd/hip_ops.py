@@ -535,6 +535,78 @@ def warp_footprints(h, map_, spec, hv, wv, device=None):
     return out
 
 
+# ---- area-sampled warps (include/ciaosr_hip.h, "area-sampled warps"): `spec` is a scene.PerPixel with `samples` = max_samples ---------------
+def _warp_area_source(h, spec, hv, wv):
+    """The (h9, mode, range, tensor, max_samples) arguments of the area entries that build the table: a homography only."""
+    if h is None:
+        raise ValueError('an area-sampled warp has a homography as its point source')
+    h9, _, mode, rng, tensor = _warp_pp_source(h, None, spec, hv, wv)
+    return h9, mode, rng, tensor, int(spec.samples)
+
+
+def warp_area_workspace_bytes(hv, wv, n_tiles, max_samples):
+    return _lib.load().ciaosr_areawarp_workspace_bytes(hv, wv, n_tiles, max_samples)
+
+
+def _warp_area_ws(hv, wv, n_tiles, max_samples, device, ws):
+    nbytes = warp_area_workspace_bytes(hv, wv, n_tiles, max_samples)
+    if nbytes == 0:
+        raise ValueError(f'no area-sampled warp of {hv} x {wv} pixels with max_samples {max_samples} over {n_tiles} tiles')
+    return workspace(nbytes, device, slot='warp_area') if ws is None else ws
+
+
+def warp_area_count(h, spec, hv, wv, tiles, ws=None):
+    """The sample table of an area-sampled warp and its tile membership: tiles [n_tiles, 4] int32 on the device -> (counts [n_tiles + 2]
+    int32 on the device: the samples in each tile, then S, the number of samples, then the number of pixels with exactly one sample;
+    ws).  `ws` holds the table and the partial counts for `warp_area_select` / `warp_area_resolve`: the caller's own uint8 buffer of at
+    least `warp_area_workspace_bytes`, default the cached 'warp_area' scratch.  Nothing synchronises."""
+    require_gpu(tiles)
+    src = _warp_area_source(h, spec, hv, wv)
+    n_tiles = tiles.shape[0]
+    ws = _warp_area_ws(hv, wv, n_tiles, src[-1], tiles.device, ws)
+    counts = torch.empty(n_tiles + 2, dtype=torch.int32, device=tiles.device)
+    _lib.call('ciaosr_areawarp_count_i32', *src, hv, wv, ptr(tiles), n_tiles, ptr(counts), ptr(ws), ws.numel(), stream_ptr())
+    return counts, ws
+
+
+def warp_area_select(h, max_samples, hv, wv, frame, index, n_tiles, ws, n_samples, n):
+    """The `n` samples (warp_area_count's number) of tile `index` = `frame` among the `n_samples` of the warp, in increasing sample id:
+    (s_index [n] int32, coord [n, 2], cell [n, 2] in the tile's frame)."""
+    h9 = (C.c_double * 9)(*[float(v) for v in h])
+    s_index = torch.empty(n, dtype=torch.int32, device=ws.device)
+    coord = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    cell = torch.empty(n, 2, dtype=torch.float32, device=ws.device)
+    _window_width.pop((coord.data_ptr(), n), None)          # the allocator may hand out the address of a dead grid's coordinates
+    _lib.call('ciaosr_areawarp_select_f32', h9, int(max_samples), hv, wv, _i4(frame), index, n_tiles, ptr(ws), ws.numel(), n_samples, n,
+              ptr(s_index), ptr(coord), ptr(cell), stream_ptr())
+    return s_index, coord, cell
+
+
+def warp_area_resolve(E, Wt, n_samples, max_samples, hv, wv, n_tiles, ws, fill, mean, std):
+    """The finished image [3, hv, wv] of the sample accumulators E [3, S], Wt [S] (S = `n_samples`; tensors of one column where S is 0):
+    per pixel the mean of its samples' values, each finished as `view_finalize` + `denorm_clamp` finish a query."""
+    require_gpu(E, Wt)
+    if E.shape != (3, Wt.shape[0]) or Wt.shape[0] != max(n_samples, 1):   # the channel stride of E is the number of samples
+        raise ValueError(f'warp_area_resolve: E {tuple(E.shape)}, Wt {tuple(Wt.shape)} are not the accumulators of {n_samples} samples')
+    out = torch.empty(3, hv, wv, dtype=torch.float32, device=E.device)
+    _lib.call('ciaosr_areawarp_resolve_f32', ptr(E), ptr(Wt), ptr(out), n_samples, int(max_samples), hv, wv, n_tiles, ptr(ws), ws.numel(),
+              _f3(fill), _f3(mean), _f3(std), stream_ptr())
+    return out
+
+
+def warp_area_table(h, spec, hv, wv, device=None):
+    """The sample table of an area-sampled warp, for inspection and tests: (first [hv * wv + 1] int32, n [hv, wv, 2] int32 = (n_y, n_x),
+    (0, 0) where the pixel has no samples), on the device; first[-1] is S.  Nothing synchronises."""
+    src = _warp_area_source(h, spec, hv, wv)
+    if device is None:
+        device = spec.tensor.device if spec.tensor is not None else torch.device('cuda')
+    ws = _warp_area_ws(hv, wv, 1, src[-1], device, None)
+    first = torch.empty(hv * wv + 1, dtype=torch.int32, device=device)
+    n = torch.empty(hv, wv, 2, dtype=torch.int32, device=device)
+    _lib.call('ciaosr_areawarp_table_i32', ptr(first), ptr(n), *src, hv, wv, 1, ptr(ws), ws.numel(), stream_ptr())
+    return first, n
+
+
 class Mode(namedtuple('Mode', 'name precision f16_pairs bf16_single trunk head')):
     """One named arithmetic mode.  (precision, f16_pairs, bf16_single): the entry suffix and the canonical ciaosr_options_t fields
     (include/ciaosr_hip.h, "Precision modes").  trunk: element type of the RDN trunk's dense layers, None = the fp32 trunk.  head: the

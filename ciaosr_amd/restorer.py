@@ -563,7 +563,7 @@ class CiaoSR(BasicRestorer):
 
     @torch.no_grad()
     def render_warp(self, enc, homography=None, map=None, size=None, footprint=None, fill=0.0, as_u8=False, as_u16=False,
-                    footprint_range=None):
+                    footprint_range=None, minify='clamp', max_samples=4):
         """The Hv x Wv (`size`) warp of an `encode` result (scene.py: the definition): every output pixel is answered by the model at its
         own LR position, which comes from ONE of two point sources.  `homography` = (h00, h01, h02, h10, h11, h12, h20, h21, h22), y
         first: y_lr = Y / D, x_lr = X / D of Y = (h00 v + h01 u) + h02, X = (h10 v + h11 u) + h12, D = (h20 v + h21 u) + h22 at the pixel
@@ -578,20 +578,25 @@ class CiaoSR(BasicRestorer):
         encode's max_scale (else `test_cfg.scale`), the warp plans for max_scale = 1 / lo, a pixel whose footprint is NaN or undefined
         holds `fill`, and the head is asked with chunk = 1 so that the shift radius of a query comes from its own cell (scene.py,
         "per-pixel warps": the definition).  A per-pixel warp whose footprints are constant is bitwise the single-footprint warp of
-        that constant.  Everything else is `render_view`'s: tiles (with
+        that constant.  A footprint above hi is clamped, so where the warp minifies a pixel is one point query and aliases:
+        `minify='area'` (a homography with a per-pixel footprint; `max_samples` = N in 1, 2, 4, 8) gives such a pixel n_y x n_x samples,
+        n = the smallest power of two <= N with g <= hi n per axis, each with the footprint g / n, and the pixel holds the mean of
+        their finished values -- the caller's `fill` for a sample outside the image, so RGBA alpha is the covered fraction (scene.py,
+        "area-sampled warps": the definition).  The head answers exactly the samples that lie inside; where nothing minifies the
+        render is bitwise `minify='clamp'`, the default.  Everything else is `render_view`'s: tiles (with
         `test_cfg.tile`: `tile_any_scale`), row-major blend, `fill`, `as_u8` / `as_u16`, grey and RGBA records, one device-to-host copy per
         batch item.  A warp that is affine -- last row (0, 0, 1), or a map of a view's points with its footprint -- is bitwise
         `render_view` of that matrix.  `test_cfg.view_blocks` is ignored.  ValueError before any device work for what
         `scene.check_warp` lists, and for a self-ensemble encode."""
         scene_render.check_quant(enc, as_u8, as_u16)
         scene_render.refuse_ensemble(enc, 'render_warp')
-        target = scene.Warp(homography, map, size, footprint, fill, footprint_range)
+        target = scene.Warp(homography, map, size, footprint, fill, footprint_range, minify, max_samples)
         return scene_render.render_one(self, enc, scene_render.resolve(self, enc, [target])[0], as_u8, as_u16)
 
     @torch.no_grad()
     def render_many(self, enc, targets, as_u8=False, as_u16=False):
         """Every target of the list -- scene.Grid(size, scale, window): `render`'s arguments, scene.View(matrix, size, fill):
-        `render_view`'s, scene.Warp(homography, map, size, footprint, fill, footprint_range): `render_warp`'s (each warp is counted by its own launch
+        `render_view`'s, scene.Warp(homography, map, size, footprint, fill, footprint_range, minify, max_samples): `render_warp`'s (each warp is counted by its own launch
         pair; its counts ride in the views' one copy) -- from ONE walk over the tile scenes: -> list of [B, 3, h, w], outs[k] bitwise what the single call returns on an
         encode with the same max_scale under the same test_cfg (with `as_u8` the same uint8 image).  Per batch item the union of the
         tiles the targets touch is walked in row-major order; each tile's scene is taken from the cache once and every target that

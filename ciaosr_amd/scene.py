@@ -3,7 +3,7 @@
 Pure Python, no GPU: the window planner (which LR tiles a window of the HR grid touches, and which part of each), the least-recently-used
 cache that bounds the bytes of tile scenes kept alive, the record `CiaoSR.encode` returns, and the affine views of
 `CiaoSR.render_view` (their matrices, cells and tile lists, and `view_blocks_fit`: when a cut view may be queried in 4 x 2 blocks), the
-warps of `CiaoSR.render_warp` (homographies and coordinate maps, their footprints and checks),
+warps of `CiaoSR.render_warp` (homographies and coordinate maps, their footprints and checks, the sample counts of `minify='area'`),
 and for `CiaoSR.render_many` the target records `Grid` / `View` / `Warp` and the tile-major plan (`plan_union`, `group_missing`).  The
 device work is in `PackedHead.prepare` / `query` (head_hip.py), `hip_ops.make_coord_cell_window` and the `hip_ops.view_*` / `warp_*` wrappers.
 """
@@ -345,14 +345,15 @@ FP_JACOBIAN, FP_DIFFERENCES, FP_TENSOR = 1, 2, 3
 
 class PerPixel:
     """The resolved footprint of a per-pixel warp: `mode` (FP_JACOBIAN, FP_DIFFERENCES or FP_TENSOR), `range` = (lo, hi) and, in mode
-    FP_TENSOR, the caller's `tensor` [Hv, Wv, 2]."""
-    __slots__ = ('mode', 'range', 'tensor')
+    FP_TENSOR, the caller's `tensor` [Hv, Wv, 2].  `samples`: 0, or the `max_samples` of an area-sampled warp (`minify='area'`)."""
+    __slots__ = ('mode', 'range', 'tensor', 'samples')
 
-    def __init__(self, mode, range, tensor=None):
-        self.mode, self.range, self.tensor = mode, range, tensor
+    def __init__(self, mode, range, tensor=None, samples=0):
+        self.mode, self.range, self.tensor, self.samples = mode, range, tensor, samples
 
     def __repr__(self):
-        return f'PerPixel(mode={self.mode}, range={self.range!r})'
+        area = f', samples={self.samples}' if self.samples else ''
+        return f'PerPixel(mode={self.mode}, range={self.range!r}{area})'
 
 
 def resolve_range(range=None, max_scale=None):
@@ -417,8 +418,73 @@ def warp_footprints(homography, size, footprint_range):
     return torch.tensor(out, dtype=torch.float64).view(hv, wv, 2)
 
 
+# ---- area-sampled warps (include/ciaosr_hip.h, "area-sampled warps") -------------------------------------------------------------------
+# `minify='area'` on a per-pixel homography warp: where the raw footprint g of an output pixel exceeds hi, the pixel is answered by
+# n_y x n_x point samples spread over it, n = `area_samples(g, hi, N)` per axis with N = `max_samples`, each with the footprint
+# f = min(max(g / n, lo), hi), and holds the mean of their finished values (the box filter).  Sample s = a n_x + b of pixel (i, j) sits at
+# v = i + (2a + 1) / (2 n_y), u = j + (2b + 1) / (2 n_x); its LR position is the homography's formula there; membership, frame coordinate
+# and cell follow the warp's rules per sample.  Sample ids run through the pixels in row-major order (`first` = the exclusive prefix sum of
+# n_y n_x, S the total); a pixel whose raw footprint has a NaN component has no samples and holds `fill`.  Where g > N hi the pixel stays
+# under-sampled (f = hi).  `minify='clamp'`, the default, is the per-pixel warp as it was.
+MAX_SAMPLES = (1, 2, 4, 8)
+INT_MAX = 2 ** 31 - 1
+
+
+def area_samples(g, hi, max_samples):
+    """Samples per axis of a pixel whose raw footprint along the axis is `g`: n = 1; while n < max_samples and g > hi n: n = 2 n.  A
+    footprint of exactly hi n stays at n; +inf gives max_samples; NaN gives 0 (the pixel has no samples)."""
+    g, hi, n_max = float(g), float(hi), int(max_samples)
+    if g != g:
+        return 0
+    n = 1
+    while n < n_max and g > hi * n:
+        n *= 2
+    return n
+
+
+def check_minify(minify='clamp', max_samples=4):
+    """-> 0 for 'clamp', `max_samples` for 'area'.  ValueError for another `minify` and for a `max_samples` outside 1, 2, 4, 8."""
+    if minify not in ('clamp', 'area'):
+        raise ValueError(f"minify is 'clamp' (a footprint above the range is clamped: one query per pixel) or 'area' (supersample where "
+                         f"the warp minifies), got {minify!r}")
+    if isinstance(max_samples, bool) or max_samples not in MAX_SAMPLES:
+        raise ValueError(f'max_samples is one of {MAX_SAMPLES} (samples per axis and pixel, a power of two), got {max_samples!r}')
+    return int(max_samples) if minify == 'area' else 0
+
+
+def warp_area_table(homography, size, footprint_range, max_samples, tensor=None):
+    """The sample table of an area-sampled homography warp on an Hv x Wv (`size`) output, in plain Python doubles: -> (first, n, f) with
+    first a list of Hv Wv + 1 ints, n a list of (n_y, n_x) -- (0, 0) without samples -- and f a list of the samples' (f_y, f_x) or None,
+    per pixel in row-major order -- what `hip_ops.warp_area_table` computes on the device.  `tensor`: the raw footprints as nested lists
+    [Hv][Wv][2] (default: the Jacobian).  For small grids and for checks: a Python loop over the pixels."""
+    h = _h9(homography)
+    hv, wv = int(size[0]), int(size[1])
+    lo, hi = resolve_range(footprint_range)
+    n_max = check_minify('area', max_samples)
+    first, ns, fs = [0], [], []
+    for i in range(hv):
+        for j in range(wv):
+            if tensor is not None:
+                g = [float(tensor[i][j][0]), float(tensor[i][j][1])]
+            else:
+                v, u = i + 0.5, j + 0.5
+                d = (h[6] * v + h[7] * u) + h[8]
+                y, x = ((h[0] * v + h[1] * u) + h[2]) / d, ((h[3] * v + h[4] * u) + h[5]) / d
+                g = []
+                for c, p in ((0, y), (3, x)):
+                    a, b = (h[c] - p * h[6]) / d, (h[c + 1] - p * h[7]) / d
+                    g.append(math.sqrt(a * a + b * b))
+            n = (area_samples(g[0], hi, n_max), area_samples(g[1], hi, n_max))
+            if 0 in n:
+                n = (0, 0)
+            ns.append(n)
+            fs.append(None if n == (0, 0) else tuple(min(max(gc / nc, lo), hi) for gc, nc in zip(g, n)))
+            first.append(first[-1] + n[0] * n[1])
+    return first, ns, fs
+
+
 def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=None, any_scale=False, footprint_range=None,
-               max_scale=None):
+               max_scale=None, minify='clamp', max_samples=4):
     """The arguments of a warp render, checked in `CiaoSR.render_warp`'s order, all on the host: -> (h9 or None, map or None, (hv, wv),
     (f_y, f_x), fill3, frames) with frames = `plan_view`'s list.  ValueError for: not exactly one point source; an empty grid; tiles
     without `tile_any_scale`; a non-finite homography entry; a denominator <= 0 at a corner (0, 0), (Hv, 0), (0, Wv), (Hv, Wv) of the grid
@@ -428,12 +494,21 @@ def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=
     `footprint` = 'per-pixel' or a device tensor [Hv, Wv, 2] makes a per-pixel warp: the fourth result is then a `PerPixel` record with
     `footprint_range` resolved (default (1 / `max_scale`, 1.0), `max_scale` = the encode's or `test_cfg.scale`).  ValueError as well for:
     an unknown string; a tensor of the wrong shape or dtype; `footprint_range` without a per-pixel footprint; a range that is not
-    0 < lo <= hi and finite; an upper end whose cell is >= 1; differences on a grid axis of length 1.  A host tensor is a CiaoSRHipError."""
+    0 < lo <= hi and finite; an upper end whose cell is >= 1; differences on a grid axis of length 1.  A host tensor is a CiaoSRHipError.
+    `minify='area'` with `max_samples` = N makes it an area-sampled warp (`PerPixel.samples` = N).  ValueError as well for: a `minify`
+    that is neither 'clamp' nor 'area'; N outside 1, 2, 4, 8; 'area' with a single footprint (given or defaulted) or with a map (the
+    sub-pixel positions of a map would need an interpolation rule); Hv Wv N N > 2^31 - 1."""
+    samples = check_minify(minify, max_samples)
     per_pixel = isinstance(footprint, str) or (hasattr(footprint, 'shape') and hasattr(footprint, 'dtype') and tuple(footprint.shape) != (2,))
     if footprint_range is not None and not per_pixel:
         raise ValueError("footprint_range=(lo, hi) clamps a per-pixel footprint: give footprint='per-pixel' or a footprint tensor with it")
+    if samples and not per_pixel:
+        raise ValueError("minify='area' supersamples a per-pixel warp: give footprint='per-pixel' or a footprint tensor with it (one "
+                         "footprint for the whole warp says nothing about where it minifies)")
     if (homography is None) == (map is None):
         raise ValueError('a warp has exactly one point source: give homography=(nine numbers) or map=(device tensor [Hv, Wv, 2])')
+    if samples and map is not None:
+        raise ValueError("minify='area' needs a homography: the sub-pixel positions of a map would need an interpolation rule")
     if map is not None:
         shape = tuple(getattr(map, 'shape', ()))
         if len(shape) != 3 or shape[2] != 2 or str(getattr(map, 'dtype', None)) not in ('torch.float64', 'torch.float32'):
@@ -446,6 +521,8 @@ def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=
     hv, wv = int(size[0]), int(size[1])
     if hv < 1 or wv < 1:
         raise ValueError(f'empty warp grid {hv} x {wv}')
+    if samples and hv * wv * samples * samples > INT_MAX:
+        raise ValueError(f"minify='area': {hv} x {wv} pixels of up to {samples} x {samples} samples are more than 2^31 - 1 samples")
     frames = plan_view(h, w, tile, overlap, any_scale)
     if map is not None:
         if shape[:2] != (hv, wv):
@@ -467,6 +544,7 @@ def check_warp(homography, map, size, footprint, fill, h, w, tile=None, overlap=
             footprint = warp_footprint(h9, (hv, wv))
     if per_pixel:
         fp = _per_pixel(footprint, footprint_range, max_scale, map is not None, hv, wv, frames[0])
+        fp.samples = samples
     else:
         fp = _footprint(footprint)
         warp_cell(fp, frames[0][2], frames[0][3])                 # ValueError: a cell >= 1
@@ -510,22 +588,25 @@ class View:
 
 class Warp:
     """One target of `CiaoSR.render_many`: the arguments of `CiaoSR.render_warp`."""
-    __slots__ = ('homography', 'map', 'size', 'footprint', 'fill', 'footprint_range')
+    __slots__ = ('homography', 'map', 'size', 'footprint', 'fill', 'footprint_range', 'minify', 'max_samples')
 
-    def __init__(self, homography=None, map=None, size=None, footprint=None, fill=0.0, footprint_range=None):
+    def __init__(self, homography=None, map=None, size=None, footprint=None, fill=0.0, footprint_range=None, minify='clamp',
+                 max_samples=4):
         self.homography, self.map, self.size, self.footprint, self.fill = homography, map, size, footprint, fill
-        self.footprint_range = footprint_range
+        self.footprint_range, self.minify, self.max_samples = footprint_range, minify, max_samples
 
     def resolve(self, h, w, tile=None, overlap=None, any_scale=False, max_scale=None):
         """`check_warp` of the record: (h9 or None, map or None, (hv, wv), footprint, fill3, frames), with `render_warp`'s errors; the
         footprint is (f_y, f_x) or, for a per-pixel warp, a `PerPixel` record (`max_scale`: the default of its range)."""
         return check_warp(self.homography, self.map, self.size, self.footprint, self.fill, h, w, tile, overlap, any_scale,
-                          self.footprint_range, max_scale)
+                          self.footprint_range, max_scale, self.minify, self.max_samples)
 
     def __repr__(self):
         source = f'homography={self.homography!r}' if self.map is None else f'map=<{tuple(getattr(self.map, "shape", ()))}>'
         fp = self.footprint if not hasattr(self.footprint, 'shape') else f'<{tuple(self.footprint.shape)}>'
         rg = '' if self.footprint_range is None else f', footprint_range={self.footprint_range!r}'
+        if self.minify != 'clamp':
+            rg += f', minify={self.minify!r}, max_samples={self.max_samples!r}'
         return f'Warp({source}, size={self.size!r}, footprint={fp!r}{rg}, fill={self.fill!r})'
 
 

@@ -272,28 +272,55 @@ class WarpTarget(ViewTarget):
     None --, the `footprint`, output `size`, `fill` and the frames.  Everything after the LR position is the view's: `touched`, `alloc` and
     `finish` are ViewTarget's own.  `test_cfg.view_blocks` is ignored: a cut warp's member lists stay in index order.  A per-pixel warp
     (`footprint` a `scene.PerPixel`, kept as `pp`) runs the per-pixel count / select / coordinate entries and queries the head with
-    chunk = 1: the shift radius of a query comes from its own cell."""
+    chunk = 1: the shift radius of a query comes from its own cell.  An area-sampled warp (`pp.samples` = max_samples, `area`) counts
+    SAMPLES: the count's copy carries `n_samples` = S and the number of one-sample pixels beside the tiles' counts.  Where every pixel has
+    exactly one sample (`supersampled` False) the samples are the pixels and it runs as the per-pixel warp it is; else its accumulators
+    are S wide, every touched tile is answered as a list of samples, and `finish` is the resolve that averages them."""
 
     def __init__(self, cfg, h, map_, size, footprint, fill, frames):
         self.h, self.footprint, self.size, self.fill, self.frames = h, footprint, size, fill, frames
         # a float32 map is widened exactly; the kernels read one aligned 16-byte (y_lr, x_lr) pair per query
         self.map = None if map_ is None else map_.detach().to(torch.float64).contiguous()
         self.pp = None
+        self.area = False
         if isinstance(footprint, sc.PerPixel):
             tensor = None if footprint.tensor is None else footprint.tensor.detach().to(torch.float64).contiguous()
-            self.pp = sc.PerPixel(footprint.mode, footprint.range, tensor)
+            self.pp = sc.PerPixel(footprint.mode, footprint.range, tensor, footprint.samples)
+            self.area = bool(footprint.samples)
             self.max_scale = 1.0 / footprint.range[0]
         else:
             self.max_scale = sc.warp_max_scale(footprint)
         self.tiled = bool(cfg.get('tile', None))
         self.counts = self.n_blocks = self.ws = None
+        self.n_samples, self.supersampled = None, False
+
+    def n_counts(self):
+        """How many numbers the count of this warp adds to the copy."""
+        return len(self.frames) + (2 if self.area else 0)
+
+    def workspace_bytes(self):
+        n_t = len(self.frames)
+        if self.area:
+            return hip_ops.warp_area_workspace_bytes(*self.size, n_t, self.pp.samples)
+        return hip_ops.warp_workspace_bytes(*self.size, n_t)
+
+    def take_counts(self, counts):
+        """`counts`: the `n_counts()` numbers of this warp, on the host."""
+        n_t = len(self.frames)
+        self.counts = counts[:n_t]
+        if self.area:
+            self.n_samples = counts[n_t]
+            self.supersampled = counts[n_t + 1] != self.size[0] * self.size[1]
 
     def count(self, r, enc):
         """Count this warp alone: the ONE device-to-host copy, and the only synchronisation, of a single warp render of a batch item."""
-        self.counts = self.launch_count(enc).tolist()
+        self.take_counts(self.launch_count(enc).tolist())
 
     def launch_count(self, enc, ws=None):
-        """The count launch pair without the copy: -> the counts on the device (`render_many` copies every target's at once)."""
+        """The count launches without the copy: -> the counts on the device (`render_many` copies every target's at once)."""
+        if self.area:
+            counts, self.ws = hip_ops.warp_area_count(self.h, self.pp, *self.size, _view_tiles(enc, self.frames), ws)
+            return counts
         if self.pp is not None:
             counts, self.ws = hip_ops.warp_pp_count(self.h, self.map, self.pp, *self.size, _view_tiles(enc, self.frames), ws)
         else:
@@ -304,9 +331,12 @@ class WarpTarget(ViewTarget):
         """Frame k's members from its scene, blended into `acc`."""
         (hv, wv), frame, n = self.size, self.frames[k], self.counts[k]
         if self.pp is not None:
-            if n == hv * wv:                                            # every query is a member, so every query has a footprint
+            if n == hv * wv and not self.supersampled:                  # every query is a member, so every query has a footprint
                 q_index = None
                 coord, cell = hip_ops.make_coord_cell_warp_pp(self.h, self.map, self.pp, hv, wv, frame, tile_scene.x.device)
+            elif self.area:                                             # samples in increasing id (the pixels' own where none is split)
+                q_index, coord, cell = hip_ops.warp_area_select(self.h, self.pp.samples, hv, wv, frame, k, len(self.frames), self.ws,
+                                                                self.n_samples, n)
             else:
                 q_index, coord, cell = hip_ops.warp_pp_select(self.h, self.map, self.pp, hv, wv, frame, k, len(self.frames), self.ws, n)
             hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell, chunk=1)[0])
@@ -317,6 +347,20 @@ class WarpTarget(ViewTarget):
         else:
             q_index, coord, cell = hip_ops.warp_select(self.h, self.map, self.footprint, hv, wv, frame, k, len(self.frames), self.ws, n)
         hip_ops.view_blend(*acc, q_index, gen.render(tile_scene, coord, cell)[0])
+
+    def alloc(self, device):
+        """One accumulator column per query; per SAMPLE where the warp is supersampled (one column where it has no sample at all)."""
+        if not self.supersampled:
+            return super().alloc(device)
+        n_s = max(self.n_samples, 1)
+        return torch.zeros(3, n_s, dtype=torch.float32, device=device), torch.zeros(n_s, dtype=torch.float32, device=device)
+
+    def finish(self, r, acc, fill=None):
+        if not self.supersampled:
+            return super().finish(r, acc, fill)
+        fill = self.fill if fill is None else fill
+        return hip_ops.warp_area_resolve(*acc, self.n_samples, self.pp.samples, *self.size, len(self.frames), self.ws, fill,
+                                         r.rgb_mean, r.rgb_std)
 
 
 def view_blocks(r, enc, m, frames):
@@ -339,7 +383,8 @@ def _view_tiles(enc, frames):
 def count_views(r, enc, views, warps=()):
     """`ViewTarget.count` for ALL views of a `render_many` / `prefetch` in one `view_count_many` (and one `view_count_blocks_many` for
     those selected in blocks) and one device-to-host copy -- per call, not per batch item: the counts do not depend on the item.
-    `warps`: each is counted by its own launch pair, into its own part of one workspace, and its counts ride in the same copy."""
+    `warps`: each is counted by its own launches, into its own part of one workspace, and its counts ride in the same copy -- behind
+    them, for an area-sampled warp, its number of samples S and of one-sample pixels (`WarpTarget.take_counts`)."""
     frames = (list(views) + list(warps))[0].frames                      # the image's: the same for every view and warp
     n_t = len(frames)
     plain, blk = [], []
@@ -353,7 +398,7 @@ def count_views(r, enc, views, warps=()):
             for v, off in zip(group, offsets):
                 v.ws = ws[off:]
     if warps:
-        sizes = [(hip_ops.warp_workspace_bytes(*wp.size, n_t) + 255) & ~255 for wp in warps]
+        sizes = [(wp.workspace_bytes() + 255) & ~255 for wp in warps]
         ws = hip_ops.workspace(sum(sizes), enc.x.device, slot='warp_many')
         off = 0
         for wp, nbytes in zip(warps, sizes):
@@ -367,8 +412,9 @@ def count_views(r, enc, views, warps=()):
         both = flat[base + 2 * i * n_t:base + 2 * (i + 1) * n_t]
         v.counts, v.n_blocks = both[0::2], both[1::2]
     base += 2 * len(blk) * n_t
-    for i, wp in enumerate(warps):
-        wp.counts = flat[base + i * n_t:base + (i + 1) * n_t]
+    for wp in warps:                                                    # an area-sampled warp's S rides behind its tiles' counts
+        wp.take_counts(flat[base:base + wp.n_counts()])
+        base += wp.n_counts()
 
 
 def resolve(r, enc, targets):

@@ -779,6 +779,40 @@ int ciaosr_ppwarp_select_f32(const double* h9 /*host [9] or NULL*/, const double
 int ciaosr_ppwarp_footprints_f64(double* out, const double* h9 /*host [9] or NULL*/, const double* map /*device or NULL*/, int mode,
                                  const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int Hv, int Wv, void* stream);
 
+/* ---- area-sampled warps: a per-pixel warp that supersamples where it minifies (version 372) -----------------------------------------------
+ * A homography warp (h9; there is no map source) with the per-pixel warp's raw footprint (g_y, g_x), mode 1 (Jacobian) or 3 (tensor), and
+ * N = max_samples in {1, 2, 4, 8}.  Per output pixel q = i Wv + j, fp64, every operation rounded on its own:
+ *   COUNT per axis: n = 1; while n < N and g > hi n: n = 2 n (+inf: N).  A NaN component: the pixel has no samples.
+ *   FOOTPRINT of its samples: f = min(max(g / n, lo), hi) per axis (where g > N hi the pixel is under-sampled, f = hi).
+ *   SAMPLE s = a n_x + b (a < n_y, b < n_x) sits at v = i + (2a + 1) / (2 n_y), u = j + (2b + 1) / (2 n_x) (exact), its LR position is the
+ *   warp's homography formula at (v, u); membership, coord and cell = fp32(f 2 / t) follow the warp's rules, per sample.
+ *   SAMPLE ID = first[q] + s, first the exclusive prefix sum of n_y n_x in row-major q, S = first[Hv Wv] the total.
+ * The accumulators are E [3][S], Wt [S]; ciaosr_view_blend_f32 blends a tile's answers with Q = S.  Hv Wv N N <= 2^31 - 1.
+ * count builds the table in the workspace (per-workgroup sums of a wave-prefix scan, a one-wave scan over the workgroups, no atomics), then
+ * counts and scans tile membership over SAMPLES (ciaosr_view_block_queries() consecutive sample ids per workgroup):
+ *   counts [n_tiles + 2] = the samples in each tile, then S, then the number of pixels with exactly one sample (== Hv Wv: nothing is
+ *   supersampled and every pixel has a footprint -- the warp is the per-pixel warp).
+ * select writes the n samples of one tile in increasing sample id: s_index, coord, cell.  resolve writes the image out_chw [3][Hv][Wv]:
+ * per pixel and channel the fp32 sum, in the order s = 0 .. n_y n_x - 1, of clamp(add(mul(x, std), mean), 0, 1) -- ciaosr_denorm_clamp_f32's
+ * arithmetic -- of x = E / Wt where Wt > 0, else ciaosr_view_finalize_f32's fill value; times 1 / (n_y n_x); a pixel without samples holds
+ * what the fill value gives.  table exports first [Hv Wv + 1] and n [Hv Wv][2] = (n_y, n_x), (0, 0) without samples.  select and resolve
+ * read the workspace count (or table) filled for the same arguments.  CIAOSR_ERR_BAD_ARG before any launch for a null or misaligned pointer,
+ * a bad size, mode or range, max_samples outside {1, 2, 4, 8}; CIAOSR_ERR_WORKSPACE for a short workspace; the size is 0 for what count
+ * refuses.  Nothing allocates, synchronises or keeps state; bitwise repeatable. */
+size_t ciaosr_areawarp_workspace_bytes(int Hv, int Wv, int n_tiles, int max_samples);
+int ciaosr_areawarp_count_i32(const double* h9 /*host [9]*/, int mode, const double* range /*host [2]*/, const double* tensor /*device or NULL*/,
+                              int max_samples, int Hv, int Wv, const int* tiles, int n_tiles, int* counts /*[n_tiles + 2]*/, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int ciaosr_areawarp_select_f32(const double* h9 /*host [9]*/, int max_samples, int Hv, int Wv, const int* tile /*host [4]*/, int tile_index,
+                               int n_tiles, const void* workspace, size_t workspace_bytes, int S, int n, int* s_index, float* coord,
+                               float* cell, void* stream);
+int ciaosr_areawarp_resolve_f32(const float* E, const float* Wt, float* out_chw, int S, int max_samples, int Hv, int Wv, int n_tiles,
+                                const void* workspace, size_t workspace_bytes, const float* fill3 /*host*/, const float* mean3 /*host*/,
+                                const float* std3 /*host*/, void* stream);
+int ciaosr_areawarp_table_i32(int* first /*[Hv Wv + 1]*/, int* n /*[Hv Wv][2]*/, const double* h9 /*host [9]*/, int mode,
+                              const double* range /*host [2]*/, const double* tensor /*device or NULL*/, int max_samples, int Hv, int Wv,
+                              int n_tiles, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- self-ensemble: the eight flips and transposes of an image, and the mean through their inverses (an extension, absent from the
  * reference) ---------------------------------------------------------------------------------------------------------------------------
  * k in 0..7.  T_k acts on the last two axes of [planes][H][W]: k & 1: flip the columns; then k & 2: flip the rows; then k & 4: transpose

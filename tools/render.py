@@ -22,7 +22,9 @@ name>_warp<k>.png in command-line order.  `--size` follows the rule of `--view`:
 single one for all of them.  D must be positive on the whole output; the model sees ONE footprint per warp, the Jacobian at the output
 centre, unless `--footprint per-pixel` gives every output pixel of every --homography its own (the Jacobian at the pixel, clamped to
 `--footprint-range LO HI`, default 1 / max scale and 1.0; the file names do not change): the choice under strong perspective.
-`--footprint-range` without `--footprint per-pixel` is an argparse error.  Not with --self-ensemble or --tiff (an argparse error).
+`--footprint-range` without `--footprint per-pixel` is an argparse error.  `--minify area [--max-samples N]` with it supersamples the
+pixels whose footprint exceeds HI -- up to N x N samples, N in 1, 2, 4, 8 (default 4), averaged -- instead of clamping them to one
+aliasing point query; `--minify` without `--footprint per-pixel` is an argparse error too.  Not with --self-ensemble or --tiff (an argparse error).
 `--gpu-png` sets `test_cfg.gpu_png`: every output is rendered as a uint8 image on the device and PNG-encoded there (ciaosr_amd/png_hip.py);
 the files decode to the pixels of the default run.
 `--view-blocks` sets `test_cfg.view_blocks` (CiaoSR.render_view): in f16 / bf16 a view that the tile seams or the image border cut is
@@ -103,6 +105,10 @@ def parse_args(argv=None):
                    help='every --homography gives each output pixel its own footprint, its Jacobian there (default: one per warp)')
     p.add_argument('--footprint-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                    help='with --footprint per-pixel: clamp the footprints to [LO, HI] LR pixels (default: 1 / max scale, 1.0)')
+    p.add_argument('--minify', choices=['clamp', 'area'], default=None,
+                   help='with --footprint per-pixel: area supersamples the pixels whose footprint exceeds HI and averages (default: clamp)')
+    p.add_argument('--max-samples', type=int, choices=[1, 2, 4, 8], default=None,
+                   help='with --minify area: samples per axis and pixel at the most (default 4)')
     p.add_argument('--window', type=int, nargs=4, default=None, metavar=('I0', 'J0', 'H', 'W'), help='HR pixels; default: the whole grid')
     p.add_argument('--precision', default=None, help='test_cfg.precision (default: the config\'s, else fp32)')
     p.add_argument('--view-blocks', action='store_true',
@@ -153,6 +159,10 @@ def parse_args(argv=None):
         p.error('--footprint per-pixel applies to --homography outputs')
     if args.footprint_range and not args.footprint:
         p.error('--footprint-range clamps per-pixel footprints: give --footprint per-pixel with it')
+    if args.minify and not args.footprint:
+        p.error('--minify chooses what a per-pixel footprint above the range does: give --footprint per-pixel with it')
+    if args.max_samples and args.minify != 'area':
+        p.error('--max-samples bounds the samples of --minify area: give --minify area with it')
     if args.footprint_range and not 0.0 < args.footprint_range[0] <= args.footprint_range[1] < float('inf'):
         p.error('--footprint-range takes 0 < LO <= HI')
     if args.jpeg is not None and not 1 <= args.jpeg <= 100:
@@ -299,6 +309,8 @@ def main(argv=None):
         paths.append(os.path.join(args.out, f'{name}_view{k}{form["ext"]}'))
     for k, h in enumerate(args.homography):
         per_pixel = dict(footprint=args.footprint, footprint_range=args.footprint_range) if args.footprint else {}
+        if args.minify:
+            per_pixel.update(minify=args.minify, max_samples=args.max_samples or 4)
         targets.append(Warp(homography=h, size=sizes[len(args.view) + k], **per_pixel))
         paths.append(os.path.join(args.out, f'{name}_warp{k}{form["ext"]}'))
     gpu_png = model.gpu_png()

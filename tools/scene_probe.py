@@ -22,6 +22,8 @@ list the leg selects: 1 = the chained 16-bit kernel gave the launch up to the ga
 that matrix, alternating, by the protocol of the view legs (`warp_legs`).
 `--legs warp-pp` (profiles/warp_pp.txt, with `--out`): a projective homography with its centre footprint, with a footprint per output
 pixel, and as a map with differences, alternating, by the same protocol (`warp_pp_legs`).
+`--legs warp-area` (profiles/warp_area.txt, with `--out`): a homography that minifies its far side as a per-pixel warp with
+`minify='clamp'`, with `minify='area'`, and as the 4 x 4 times finer single-footprint warp box-averaged with torch (`warp_area_legs`).
 
 `--legs many` (profiles/render_many.txt, with `--out`) is the tiled image of bench.py -- LR 1356 x 2040, tile 192 / overlap 32,
 `tile_any_scale`: 9 x 13 = 117 tiles -- rendered at x2, x3.3 and x4 (full grids) from one encode, per precision and for two scene caches
@@ -47,7 +49,7 @@ ap.add_argument('--sizes', default='192,48')
 ap.add_argument('--precisions', default='fp32,f16')
 ap.add_argument('--scales', default='4,2,3.3')
 ap.add_argument('--reps', type=int, default=5)
-ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many', 'warp', 'warp-pp'))
+ap.add_argument('--legs', default='scene', choices=('scene', 'view', 'many', 'warp', 'warp-pp', 'warp-area'))
 ap.add_argument('--view-size', type=int, default=768)
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help='tree whose package and library run')
 ap.add_argument('--parent-root', default=None, help='--legs many: a built checkout of the parent commit for leg (a)')
@@ -292,6 +294,78 @@ def warp_pp_legs():
             f.write('\n'.join(report) + '\n')
 
 
+def warp_area_legs():
+    """`--legs warp-area`: the warp legs' protocol (the C3 tile, whole-image test_cfg, scene planned for x4, `--view-size` squared, 2
+    warm-up + `--reps` timed rounds, legs alternating in one process, one profiled round per leg) on a projective homography that looks
+    along the image like a floor -- x2 at the near edge, its far side minified -- as a per-pixel warp with `minify='clamp'`, with
+    `minify='area'` (max_samples 4), and as the caller's alternative: the single-footprint warp of the 4 x 4 times finer grid, box-averaged
+    with torch.  Reports the histogram of the samples per axis, S, and the inside samples each leg asks of the head.  With `--out` the
+    report is also written to that file (profiles/warp_area.txt)."""
+    from ciaosr_amd.scene import FP_JACOBIAN, PerPixel, view_matrix, warp_footprint
+    size, n, n_max = int(args.sizes.split(',')[0]), args.view_size, 4
+    report = [f'tools/scene_probe.py --legs warp-area --reps {args.reps}: library version {_lib.load().ciaosr_version()}, '
+              f'{torch.cuda.get_device_name(0)}; {size}x{size} LR, {n} x {n} output, three legs alternating in one process (2 warm-up '
+              f'rounds, {args.reps} timed rounds)']
+    lq = synthetic_pair(size, size, 4)[0].to(dev)
+    rng = (0.25, 1.0)
+    h = (*view_matrix((size / 2, size / 2), 2.0, 0, (n, n)), -0.7 / n, -0.15 / n, 1.0)      # D = 0.15 at the far corner: no horizon
+    fine_h = tuple(c / n_max if k % 3 < 2 else c for k, c in enumerate(h))
+    fine_fp = tuple(min(max(f, rng[0]), rng[1]) for f in warp_footprint(fine_h, (n_max * n, n_max * n)))
+    spec = PerPixel(FP_JACOBIAN, rng, None, n_max)
+    tiles = torch.tensor([(0, 0, size, size)], dtype=torch.int32).to(dev)
+    first, n_yx = hip_ops.warp_area_table(h, spec, n, n, dev)
+    counts, _ = hip_ops.warp_area_count(h, spec, n, n, tiles)
+    inside_samples, n_samples, _ = counts.tolist()
+    inside_px = hip_ops.warp_pp_count(h, None, PerPixel(FP_JACOBIAN, rng), n, n, tiles)[0].tolist()[0]
+    inside_fine = hip_ops.warp_count(fine_h, None, fine_fp, n_max * n, n_max * n, tiles)[0].tolist()[0]
+    hist = ', '.join(f'n_{ax} ' + ' / '.join(str(int((n_yx[..., k] == v).sum())) for v in (1, 2, 4)) for k, ax in enumerate('yx'))
+    report.append(f'  samples per axis over 1 / 2 / 4: {hist}; S = {n_samples} samples for {n * n} pixels; the head answers {inside_px} '
+                  f'queries (clamp), {inside_samples} (area), {inside_fine} (the {n_max * n} x {n_max * n} grid)')
+    chunk = _lib.load().ciaosr_view_block_queries()
+    report.append(f'  the count launches {-(-n * n * n_max * n_max // chunk)} workgroups of {chunk} sample ids, the blocks of the largest S; '
+                  f'{-(-n_samples // chunk)} hold a sample; workspace {hip_ops.warp_area_workspace_bytes(n, n, 1, n_max) / 2 ** 20:.1f} MiB')
+    groups = (('count (table included)', lambda k: k in ('warp_area_count', 'warp_pp_count', 'warp_count')),
+              ('count + select + blend + resolve', lambda k: k.startswith(('view_', 'warp_')) or k == 'denorm_clamp'),
+              ('head query', lambda k: not k.startswith(('view_', 'warp_', 'make_coord_cell')) and k != 'denorm_clamp'))
+    for precision in args.precisions.split(','):
+        model.test_cfg = dict(scale=4, precision=precision)
+        enc = model.encode(lq)
+        pp = dict(homography=h, size=(n, n), footprint='per-pixel', footprint_range=rng)
+
+        def alternative():
+            fine = model.render_warp(enc, homography=fine_h, size=(n_max * n, n_max * n), footprint=fine_fp)
+            return fine.view(1, 3, n, n_max, n, n_max).mean((3, 5))
+
+        calls = {'clamp': lambda: model.render_warp(enc, **pp), 'area': lambda: model.render_warp(enc, minify='area', max_samples=n_max, **pp),
+                 'fine grid + box': alternative}
+        outs = {k: fn() for k, fn in calls.items()}
+        report.append(f'  {precision}: max |area - clamp| = {(outs["area"] - outs["clamp"]).abs().max().item():.3e}, max |area - fine grid| = '
+                      f'{(outs["area"] - outs["fine grid + box"]).abs().max().item():.3e}')
+        del outs
+        for _ in range(2):
+            for fn in calls.values():
+                fn()
+        times = {k: [] for k in calls}
+        for _ in range(args.reps):
+            for k, fn in calls.items():
+                times[k].append(timed(fn)[0])
+        for k, fn in calls.items():
+            with hip_ops.profile():
+                fn()
+            prof = hip_ops.profile.results()
+            t = times[k]
+            parts = ', '.join(f'{name} {sum(r["total_ms"] for kk, r in prof.items() if pick(kk)):8.3f} ms '
+                              f'({sum(r["launches"] for kk, r in prof.items() if pick(kk))} launches)' for name, pick in groups)
+            report.append(f'    {k:16s} wall mean {sum(t) / len(t):8.3f} ms  min {min(t):8.3f}  max {max(t):8.3f} | device: {parts}')
+        del enc, calls
+        hip_ops.release_workspaces()
+        torch.cuda.empty_cache()
+    print('\n'.join(report))
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(report) + '\n')
+
+
 MANY_LR, MANY_SCALES = (1356, 2040), (2.0, 3.3, 4.0)
 
 
@@ -459,6 +533,8 @@ if args.legs == 'warp':
     warp_legs()
 if args.legs == 'warp-pp':
     warp_pp_legs()
+if args.legs == 'warp-area':
+    warp_area_legs()
 if args.legs == 'many':
     many_worker() if args.worker else many_legs()
 for size in (int(v) for v in args.sizes.split(',') if args.legs == 'scene'):
